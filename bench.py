@@ -1,28 +1,36 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the MI355X k-mer hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL - either launched by the driver through torch.distributed.run, or, typed as it stands
 (`python bench.py --gpus 8`), bench.py starts torch.distributed.run itself as a child process (launch_ranks).
 A "step" is one pass of the hot path over one batch of synthetic reads that is already
 resident in HBM.
 
-Default (no --workload) = BASELINE.json's whole headline metric, one after the other:
-  * `comp oligo k=4`, 10 M x 150 bp reads per GPU, f64 rows (configs[1]) - the line's top-level
-    `value` / `roofline` / `cpu_baseline`;
+Default (no --workload): `comp oligo k=4`, 10 M x 150 bp reads per GPU, f64 rows (configs[1]) - the line's top-level
+`value` / `ms_per_step` / `roofline`.  A plain run does only that: set-up, W warm-up and exactly K timed steps between
+barrier + synchronize brackets (max over ranks), the line.
+
+--full adds everything else, as objects of the same line: the rest of BASELINE.json's headline metric, one after the other -
   * `ctr k=31`, 25 M x 150 bp reads per GPU (at --gpus 8 that is configs[3]) - the `ctr_k31` object with
-    its own `value`, `ms_per_step`, `roofline`, `cpu_baseline` and the genome-sampled read distribution.
+    its own `value`, `ms_per_step`, `roofline`, `cpu_baseline` and the genome-sampled read distribution;
   * `ctr k=15` (configs[2]) and `comp cgr k=7` f32 (configs[4]) as the `ctr_k15` / `comp_cgr_k7` objects, each
-    with its own `roofline`.
-All run W warm-up and exactly K timed steps between barrier + synchronize brackets (max over ranks).
+    with its own `roofline`;
+- the CPU baselines (`cpu_baseline`, N = 1 only; --no-cpu leaves them out) and the output checks below.
 
 Self-certification: the line's `kt_env` lists every KT_* variable the process saw; a variable that can switch
-work off (ablation builds only) makes bench.py exit non-zero before anything is timed.  After each timed loop,
-untimed, the output is checked (`output_check`): oligo rows sum to 1 over the whole output and a 4096-row slice
+work off (ablation builds only) makes bench.py exit non-zero before anything is timed.  With --full, after each timed
+loop, untimed, the output is checked (`output_check`): oligo rows sum to 1 over the whole output and a 4096-row slice
 is compared with the CPU oracle inside the cpu_baseline leg; ctr's exported counts sum to reads x (L - k + 1), and the
 k-mers of a 20 000-read sample of rank 0's batch, counted by the CPU oracle, are looked up in the shards of all ranks
 (`output_check.sampled_oracle`: each found on exactly one rank - its owner - with at least the sample's count).
+
+--dump-outputs DIR: after the timed steps of every workload the run times (the genome-sampled ctr run excepted), rank 0
+writes what the last step computed as DIR/<workload>.npy, a fixed, seeded sample of at most DUMP_BYTES (the same
+arguments give the same inputs, so two builds can be compared output for output): oligo / cov / cgr rows in the output's
+own float type; min (minimiser, start, end) triples and ctr (key >> 31, key & (2^31 - 1), count) as float64 rows, ctr's
+sample being the exported keys divisible by a stride chosen from the distinct count, in key order.
 
 Array placement (oligo / cgr workloads, untimed, before the ramp): where an array lies in the HBM moves the store-bound
 kernels by up to 20 %, so the output array - and for one-batch workloads the input array - is the
@@ -83,6 +91,7 @@ HEADLINE = ("comp_oligo_k4", "ctr_k31", "ctr_k15", "comp_cgr_k7")
 WORK_SKIPPING_ENV = ("KT_OLIGO_DEBUG", "KT_BUILD_DBG")
 CHECK_ROWS = 4096
 GENOME_LEN = 1_000_000_000   # second ctr distribution, reads sampled from a random 1 Gbp genome
+DUMP_BYTES = 8 << 20         # --dump-outputs, per workload: the four of a --full headline run stay under 64 MB
 
 
 def parse():
@@ -93,10 +102,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="headline", choices=["headline"] + sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="headline: every workload of it; and the output checks and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of what the last timed step computed to DIR/<workload>.npy")
     ap.add_argument("--reads", type=int, default=0, help="override reads per GPU (debug; marks the line as reduced)")
     ap.add_argument("--genome", type=int, default=0, help="ctr: sample reads from a random genome of this length")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-genome", action="store_true", help="headline: skip ctr's genome-sampled distribution")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-genome", action="store_true", help="--full headline: skip ctr's genome-sampled distribution")
     ap.add_argument("--no-export", action="store_true", help="ctr: time clear + insert only (round-1 region; experiments)")
     ap.add_argument("--cap-log2", type=int, default=0, help="ctr: override log2 of the table capacity (experiments)")
     ap.add_argument("--cap-slots", type=float, default=0, help="ctr: override the requested table capacity (experiments)")
@@ -281,6 +294,14 @@ def cpu_baseline_for(wl, args, genome):
 
 # ---- one workload: setup, W warm-up steps, exactly K timed steps -------------------------------------------
 
+def sample_index(n, m):
+    """--dump-outputs: a fixed, seeded sample of m of the n items of an output (all of them when n <= m), in order"""
+    import numpy as np
+    if n <= m:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(SEED).choice(n, m, replace=False))
+
+
 class Env:
     """what every workload run shares: torch, the process group, the library context"""
 
@@ -326,8 +347,9 @@ class Env:
             self.dist.destroy_process_group()
 
 
-def run_workload(env, name, args, genome=0, steps=None, warmup=None):
-    """-> dict(value, ms_per_step, ms_median, ms_min, roofline, config, dtype, extra...) for one workload"""
+def run_workload(env, name, args, genome=0, steps=None, warmup=None, dump=True):
+    """-> dict(value, ms_per_step, ms_median, ms_min, roofline, config, dtype, extra...) for one workload; `dump`: its
+    outputs go to --dump-outputs"""
     torch, device, ctx = env.torch, env.device, env.ctx
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -339,6 +361,9 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
         reduced = True
     n, L, k = wl["n"], wl["L"], wl["k"]
     world, rank = env.world, env.rank
+
+    def sample_rows(count, row_bytes):   # --dump-outputs: the device indices of outputs()'s sample of `count` rows
+        return torch.from_numpy(sample_index(count, DUMP_BYTES // row_bytes)).to("cuda")
 
     bases = torch.empty(n * L, dtype=torch.uint8, device="cuda")
     offsets = torch.empty(n + 1, dtype=torch.int64, device="cuda")
@@ -411,6 +436,10 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
         def step():
             for (bb, oo, cnt) in batch_args:
                 ctx.oligo(bb, oo, cnt, k, out, count_min=True, norm=True, total_step=1, dtype=wl["dtype"])
+
+        def outputs():   # the rows of the step's last batch (the earlier ones were overwritten by it)
+            cnt = batch_args[-1][2]
+            return out[:cnt][sample_rows(cnt, bins * esz)].cpu().numpy()
     elif wl["kind"] == "min":
         w = wl["w"]
         evo = torch.empty(n + 1, dtype=torch.int64, device="cuda")
@@ -426,6 +455,10 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
 
         def step():
             ctx.minimisers(bases, offsets, n, w, k, evo, mk, ms, me, n_ev)
+
+        def outputs():
+            idx = sample_rows(n_ev, 24)
+            return torch.stack([mk[idx], ms[idx], me[idx]], dim=1).double().cpu().numpy()
     elif wl["kind"] == "cgr":
         bad = torch.zeros(1, dtype=torch.int64, device="cuda")
         if args.no_place or env.share_gpu:
@@ -440,6 +473,9 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
 
         def step():
             ctx.cgr(bases, offsets, n, 1, out, bad)
+
+        def outputs():
+            return out[sample_rows(n * L, 16)].cpu().numpy()
     elif wl["kind"] == "cov":
         kmers_per_read = L - k + 1
         max_distinct = min(n * kmers_per_read, (4 ** k + 2 ** k) // 2)
@@ -456,6 +492,9 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
 
         def step():
             table.cov(bases, offsets, n, wl["bin_size"], bc, out, norm=True, dtype="f64")
+
+        def outputs():
+            return out[sample_rows(n, bc * 8)].cpu().numpy()
     else:
         from kmertools_amd import dist as ktdist
         kmers_per_read = L - k + 1
@@ -510,6 +549,21 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
                 assert got == d
                 state["distinct"] = d
 
+        def outputs():
+            # the pairs come in the table's order, which is not part of the result: the sample is the keys divisible by a
+            # stride chosen from the distinct count, in key order (masked a chunk at a time: 3 G keys at k = 31)
+            d, cap_rows, chunk = state["distinct"], DUMP_BYTES // 24, 1 << 28
+            stride = max(1, d // cap_rows)
+            ks, cs = [xk[:0]], [xc[:0]]
+            for i in range(0, d, chunk):
+                kk, cc = xk[i:min(d, i + chunk)], xc[i:min(d, i + chunk)]
+                sel = kk % stride == 0
+                ks.append(kk[sel])
+                cs.append(cc[sel])
+            kk, order = torch.sort(torch.cat(ks))
+            kk, cc = kk[:cap_rows], torch.cat(cs)[order][:cap_rows].to(torch.int64)
+            return torch.stack([kk >> 31, kk & 0x7FFFFFFF, cc], dim=1).double().cpu().numpy()
+
     # Ramp: untimed launches ahead of the W warm-up steps.  The store-bound kernels reach their steady rate only after
     # ~20 launches (clocks / power state after the idle set-up phase): oligo k=4 measured 2.115 ms per step with
     # --steps 10 --warmup 3, 2.03 with 20 / 5, 2.00 with 100 / 20 and with 10 / 60, same box, same minute.  The count
@@ -561,9 +615,15 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
     except (OSError, ValueError, KeyError):
         traffic = None
 
-    # ---- untimed: is the output the timed steps produced the right one? ------------------------------------------
+    if dump and args.dump_outputs and rank == 0:
+        import numpy as np
+        dump_dir = pathlib.Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        np.save(dump_dir / (name + ".npy"), outputs())
+
+    # ---- untimed (--full): is the output the timed steps produced the right one? ------------------------------------
     check, check_slice = None, None
-    if wl["kind"] == "oligo":
+    if args.full and wl["kind"] == "oligo":
         # one more pass over every batch: every row must sum to 1 (synthetic reads have L - k + 1 k-mers each); the
         # first CHECK_ROWS rows go to the host for the oracle comparison made in the cpu_baseline leg
         tol = 1e-12 if wl["dtype"] == "f64" else 1e-6
@@ -580,7 +640,7 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
                                    out=out[:m].cpu().numpy())
             del sums
         check = {"rows": rows, "rows_not_summing_to_1": bad, "tolerance": tol, "ok": bad == 0}
-    elif wl["kind"] == "ctr" and not args.no_export:
+    elif args.full and wl["kind"] == "ctr" and not args.no_export:
         d = state["distinct"]
         tot = torch.stack([xc[:d].sum(dtype=torch.int64), torch.tensor(d, device="cuda")])
         if world > 1:
@@ -594,12 +654,12 @@ def run_workload(env, name, args, genome=0, steps=None, warmup=None):
         # each must be found on exactly one rank - the rank kt_shard_owner_of gives it - with at least the sample's count.
         check["sampled_oracle"] = sampled_oracle_check(env, counter, bases, offsets, n, L, k)
         check["ok"] = check["ok"] and check["sampled_oracle"]["ok"]
+    if wl["kind"] == "oligo" and k == 4:   # the launch shape this process measured for itself (kt_oligo_launch_info)
+        info = ctx.oligo_launch_info()
+        info["ns_per_read"] = {str(a): round(b, 4) for a, b in info["ns_per_read"].items()}
+        extra["oligo_launch"] = info
     if check is not None:
         extra["output_check"] = check
-        if wl["kind"] == "oligo" and k == 4:   # the launch shape this process measured for itself (kt_oligo_launch_info)
-            info = ctx.oligo_launch_info()
-            info["ns_per_read"] = {str(a): round(b, 4) for a, b in info["ns_per_read"].items()}
-            extra["oligo_launch"] = info
         if not check["ok"]:
             sys.exit("bench.py: %s produced a wrong output: %r" % (name, check))
 
@@ -753,16 +813,22 @@ def launch_ranks(args):
 def main():
     args = parse()
     kt_env = kt_environment()
+    if args.dump_outputs and args.no_export:
+        sys.exit("bench.py: --dump-outputs writes ctr's exported pairs; --no-export leaves none")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     env = Env(args)
-    names = HEADLINE if args.workload == "headline" else (args.workload,)
+    if args.workload != "headline":
+        names = (args.workload,)
+    else:   # a plain run: the headline figure alone (the line's top level)
+        names = HEADLINE if args.full else HEADLINE[:1]
     results = []
     for name in names:
         res, wl = run_workload(env, name, args, genome=args.genome if WORKLOADS[name]["kind"] in ("ctr", "cov") else 0)
-        if (args.workload == "headline" and name == "ctr_k31" and not args.no_genome and not args.genome):
+        if (args.full and args.workload == "headline" and name == "ctr_k31" and not args.no_genome and not args.genome):
             # the second read distribution for ctr (uniform reads make nearly every 31-mer unique)
-            g, _ = run_workload(env, name, args, genome=GENOME_LEN, steps=min(args.steps, 5), warmup=min(args.warmup, 2))
+            g, _ = run_workload(env, name, args, genome=GENOME_LEN, steps=min(args.steps, 5), warmup=min(args.warmup, 2),
+                                dump=False)
             res["genome_sampled"] = {key: g[key] for key in ("value", "ms_per_step", "ms_median", "ms_min", "roofline",
                                                              "distinct_rank0")}
             res["genome_sampled"]["genome_len"] = GENOME_LEN
@@ -776,14 +842,14 @@ def main():
                 "vs_baseline": None, "dtype": top["dtype"], "data": "synthetic"}
         line.update({key: v for key, v in top.items() if key not in line})
         line["kt_env"] = kt_env
-        if env.world == 1 and not args.no_cpu:
+        if args.full and env.world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline_for(wl, args, args.genome)
             if wl.get("_check_slice"):
                 line["output_check"]["oracle_slice"] = oracle_slice_check(wl["_check_slice"])
         for name, res, wl in results[1:]:
             obj = dict(res)
             obj.update({"n_gpus": env.world, "steps": args.steps, "warmup": args.warmup, "scaling": "weak"})
-            if env.world == 1 and not args.no_cpu:
+            if args.full and env.world == 1 and not args.no_cpu:
                 if name in ("ctr_k31",):   # the headline's second half has its own CPU leg; the extra configs do not
                     obj["cpu_baseline"] = cpu_baseline_for(wl, args, 0)
                 if wl.get("_check_slice"):

@@ -1672,7 +1672,8 @@ def test_bench_two_rank_launch(workload, ranks, plain):
     sock.bind(("127.0.0.1", 0))
     port = sock.getsockname()[1]
     sock.close()
-    tail = [str(root / "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--workload", workload, "--reads", "200000"]
+    tail = [str(root / "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--workload", workload, "--reads", "200000",
+            "--full"]
     if plain:
         cmd = [sys.executable] + tail
     else:
@@ -1740,7 +1741,7 @@ def test_bench_places_its_arrays():
     root = pathlib.Path(__file__).resolve().parents[1]
     for flag in ([], ["--no-place"]):
         cmd = [sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "comp_oligo_k4",
-               "--reads", "300000", "--cpu-seconds", "1"] + flag
+               "--reads", "300000", "--cpu-seconds", "1", "--full"] + flag
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1756,6 +1757,35 @@ def test_bench_places_its_arrays():
                 assert p["candidates"] == len(p["ms"]) >= 1 and 0 <= p["picked"] < p["candidates"]
                 assert p["ms"][p["picked"]] == min(p["ms"])
             assert 0 < j["roofline"]["frac_plain_allocation"] <= j["roofline"]["frac"] + 1e-9
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path, oracle):
+    """a plain bench.py run (no --full) times the headline workload alone - no other workload, output check or CPU
+    baseline - for exactly --steps steps, and --dump-outputs writes the seeded row sample of its last step's output: the
+    oracle's rows for the same reads, bit for bit"""
+    import importlib.util, json, subprocess, sys, pathlib
+    root = pathlib.Path(__file__).resolve().parents[1]
+    n, L = 300000, 150
+    cmd = [sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--reads", str(n),
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dtype"] == "f64" and j["higher_is_better"] is True
+    assert not {"ctr_k31", "ctr_k15", "comp_cgr_k7", "cpu_baseline", "output_check"} & set(j)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["comp_oligo_k4.npy"]
+    got = np.load(tmp_path / "comp_oligo_k4.npy")
+    spec = importlib.util.spec_from_file_location("bench", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    idx = bench.sample_index(n, bench.DUMP_BYTES // (136 * 8))
+    assert got.dtype == np.float64 and got.shape == (len(idx), 136) and got.nbytes <= bench.DUMP_BYTES
+    hb, _ = oracle.synth_reads(bench.SEED + bench.WORKLOADS["comp_oligo_k4"]["cfg"], n, L)
+    sb = np.ascontiguousarray(hb.reshape(n, L)[idx]).reshape(-1)
+    want = oracle.oligo_batch(sb, np.arange(len(idx) + 1, dtype=np.uint64) * np.uint64(L), 4, True, True, 1.0, threads=8)
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
 
 
 def test_ctr_cfg3_full_size_properties(torch_mod, ctx):
