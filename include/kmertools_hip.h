@@ -216,6 +216,21 @@ int kt_ctr_export(kt_ctr *ctr, uint64_t *keys, uint32_t *counts, uint64_t max_ou
 int kt_ctr_export_stage(kt_ctr *ctr, uint64_t *n_out);
 int kt_ctr_export_fetch(kt_ctr *ctr, uint64_t first, uint64_t count, uint64_t *keys_host, uint32_t *counts_host);
 
+/* kt_ctr_export_stage restricted to the entries with min_count <= count <= max_count (kt_ctr_export_stage is
+ * (1, UINT32_MAX)); kt_ctr_export_fetch then reads the kept entries.  min_count > max_count is KT_ERR_ARG. The table
+ * and an export target's arrays are not changed.  (jellyfish dump -L/-U, kmc -ci/-cx: only the kept entries cross to
+ * the host.) */
+int kt_ctr_export_stage_range(kt_ctr *ctr, uint32_t min_count, uint32_t max_count, uint64_t *n_out);
+
+/* The table's abundance spectrum, ADDED into hist (the caller zeroes it once; hash-partition passes and the shards
+ * of a sharded counter accumulate into one array): for 1 <= c < n_bins, hist[c] += distinct k-mers with exactly c
+ * occurrences; hist[n_bins - 1] += those with n_bins - 1 or more; hist[0] is not touched.  totals (may be NULL):
+ * totals[0] += distinct k-mers, totals[1] += occurrences (exact, whatever n_bins).  2 <= n_bins <= 2^24, else
+ * KT_ERR_ARG; an overflowed table is KT_ERR_FULL as in kt_ctr_size.  mem: where hist / totals are.  KT_MEM_HOST
+ * synchronises; KT_MEM_DEVICE is enqueued on the context's stream.  The table is not changed.
+ * (jellyfish histo, kmc_tools histogram) */
+int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *totals, int mem);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

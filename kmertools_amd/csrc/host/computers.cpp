@@ -703,9 +703,12 @@ class TableWriter {
         if (slab_ > (1ull << 20)) slab_ = 1ull << 20;
         if (slab_ < (1ull << 16)) slab_ = 1ull << 16;
     }
+    // --min-count / --max-count: only the entries with lo <= count <= hi are staged (kt_ctr_export_stage_range; the full
+    // range is kt_ctr_export_stage itself)
+    void set_range(uint32_t lo, uint32_t hi) { lo_ = lo, hi_ = hi; }
     std::string write(FILE *out, kt_ctr *ctr, uint64_t *n_out) {
         uint64_t n = 0;
-        if (kt_ctr_export_stage(ctr, &n) != KT_OK) return kt_last_error();
+        if (kt_ctr_export_stage_range(ctr, lo_, hi_, &n) != KT_OK) return kt_last_error();
         if (n && keys_.empty()) {
             keys_.resize((size_t)slab_);
             counts_.resize((size_t)slab_);
@@ -753,11 +756,35 @@ class TableWriter {
   private:
     bool acgt_;
     int k_, threads_;
+    uint32_t lo_ = 1, hi_ = 0xFFFFFFFFu;
     uint64_t slab_ = 0, slabs_ = 0, entries_ = 0, heap_peak_kb_ = 0;
     std::vector<uint64_t> keys_;
     std::vector<uint32_t> counts_;
     std::vector<std::string> pieces_;
 };
+
+// the spectrum of table t added to histo_ (out-of-core passes and shards: one table after the other into one array)
+std::string CountComputer::add_spectrum(kt_ctr *t) {
+    if (histo_.empty()) histo_.assign((size_t)histo_max_ + 1, 0);
+    if (kt_ctr_spectrum(t, histo_.data(), histo_max_ + 1, nullptr, KT_MEM_HOST) != KT_OK) return kt_last_error();
+    return "";
+}
+
+// {out_dir}/kmers.histo: "c\tn" for c = 1..H, zeros included, the last line the k-mers with H or more occurrences
+std::string CountComputer::write_histo() const {
+    const std::string path = out_dir_ + "/kmers.histo";
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + path;
+    std::string s;
+    for (uint32_t c = 1; c <= histo_max_; c++) {
+        s += std::to_string(c);
+        s += '\t';
+        s += std::to_string(c < histo_.size() ? histo_[c] : 0);
+        s += '\n';
+    }
+    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+    return fclose(out) == 0 && ok ? "" : "Unable to write to file: " + path;
+}
 
 static uint64_t env_u64_host(const char *name, uint64_t dflt) {
     const char *v = getenv(name);
@@ -836,6 +863,7 @@ std::string CountComputer::count() {
     if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
+    writer.set_range(min_count_, max_count_);
     uint64_t heap_after_first = 0, rss_after_first = 0;
     for (uint32_t pass = 0; pass < passes_; pass++) {
         if (pass && !reader.rewind()) return reader.error();
@@ -855,11 +883,16 @@ std::string CountComputer::count() {
         // out of core: this partition is complete - whoever needs to look k-mers up does it now (cov) -
         if (pass_hook_)
             if (std::string e = pass_hook_(pass, passes_, ctr_); !e.empty()) return e;
+        // - its spectrum is added to the whole table's (a k-mer lives in one partition) -
+        if (histo_max_)
+            if (std::string e = add_spectrum(ctr_); !e.empty()) return e;
         // - its lines go to kmers.counts, and the table is reused
-        if (!out) out = fopen(path.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + path;
         uint64_t n_pass = 0;
-        if (std::string e = writer.write(out, ctr_, &n_pass); !e.empty()) return e;
+        if (!histo_only_) {
+            if (!out) out = fopen(path.c_str(), "wb");
+            if (!out) return "Unable to write to file: " + path;
+            if (std::string e = writer.write(out, ctr_, &n_pass); !e.empty()) return e;
+        }
         pt.t[3] += lap();
         if (timing) {
             // the ceiling's books, per pass: the program's own buffers by their capacities, the allocator's total, and
@@ -1045,19 +1078,26 @@ std::string CountComputer::count_sharded(uint64_t max_distinct) {
 }
 
 std::string CountComputer::merge(bool /*del: no temp files exist to delete*/) {
-    if (passes_ > 1) return "";  // out of core: count() wrote every partition's lines as it completed
+    // out of core: count() wrote every partition's lines as it completed (and summed their spectra)
+    if (passes_ > 1) return histo_max_ ? write_histo() : "";
     const std::string path = out_dir_ + "/kmers.counts";
     if (sharded_done_) {  // the shards, one after the other, each in slabs (the reference's line order is unspecified)
-        FILE *out = fopen(path.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + path;
+        FILE *out = nullptr;
+        if (!histo_only_) {
+            out = fopen(path.c_str(), "wb");
+            if (!out) return "Unable to write to file: " + path;
+        }
         std::string err;
         TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
+        writer.set_range(min_count_, max_count_);
         for (size_t r = 0; r < shards_.size() && err.empty(); r++) {
             kt_ctr *t = nullptr;
             if (kt_sharded_table(shards_[r], &t) != KT_OK) err = kt_last_error();
-            else err = writer.write(out, t, nullptr);
+            else if (histo_max_ && !(err = add_spectrum(t)).empty()) break;  // (the shards' spectra are summed)
+            else if (out) err = writer.write(out, t, nullptr);
         }
-        fclose(out);
+        if (out) fclose(out);
+        if (err.empty() && histo_max_) err = write_histo();
         if (getenv("KT_CLI_TIMING"))
             fprintf(stderr, "[timing] ctr --devices %d written: VmHWM %llu kB\n", n_devices_, (unsigned long long)peak_rss_kb());
         if (!keep_shards_) release_shards();
@@ -1066,9 +1106,15 @@ std::string CountComputer::merge(bool /*del: no temp files exist to delete*/) {
     if (!ctr_) return "count() has not run";
     PhaseTimer pt("ctr merge");
     Lap lap;
+    if (histo_max_) {
+        if (std::string e = add_spectrum(ctr_); !e.empty()) return e;
+        if (std::string e = write_histo(); !e.empty()) return e;
+        if (histo_only_) return "";
+    }
     FILE *out = fopen(path.c_str(), "wb");
     if (!out) return "Unable to write to file: " + path;
     TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
+    writer.set_range(min_count_, max_count_);
     const std::string e = writer.write(out, ctr_, nullptr);
     pt.t[2] += lap();
     fclose(out);

@@ -98,6 +98,11 @@ class CountComputer {
     void set_acgt_output(bool a) { acgt_ = a; }
     void set_device(int d) { dev_.index = d; }
     void set_devices(int n) { n_devices_ = n < 1 ? 1 : n; }  // --devices N: the table sharded over N GPUs (kt_sharded_*)
+    // --min-count / --max-count: only the entries with lo <= count <= hi go to kmers.counts (filtered on the device)
+    void set_count_range(uint32_t lo, uint32_t hi) { min_count_ = lo, max_count_ = hi; }
+    // --histo-max H (--histo): merge() also writes {out_dir}/kmers.histo, the spectrum of the whole table in H lines (the
+    // last: H or more occurrences); only = --histo-only: no kmers.counts at all
+    void set_histo(uint32_t h, bool only) { histo_max_ = h, histo_only_ = only; }
     // counter/src/lib.rs:69-90.  No temp files: one resident table - or, when the distinct k-mers cannot fit the HBM,
     // `passes()` passes over the input, one hash partition each, written to kmers.counts as they complete.
     std::string count();
@@ -124,6 +129,11 @@ class CountComputer {
     int n_devices_ = 1;
     uint32_t passes_ = 1;
     bool sharded_done_ = false, keep_shards_ = false;
+    uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu, histo_max_ = 0;  // histo_max_ = 0: no kmers.histo
+    bool histo_only_ = false;
+    std::vector<uint64_t> histo_;  // the spectrum, summed over passes / shards (histo_max_ + 1 bins)
+    std::string add_spectrum(kt_ctr *t);
+    std::string write_histo() const;
     // --devices N: the shards stay on their GPUs after count(); merge() writes them out one after the other, in slabs
     std::vector<kt_sharded *> shards_;
     std::vector<kt_ctx *> shard_ctx_;

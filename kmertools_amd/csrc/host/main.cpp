@@ -171,6 +171,12 @@ const char *HELP_CTR =
     "  -t, --threads <THREADS>  Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>    GPU index [default: 0]\n"
     "      --devices <N>        Shard the table over N GPUs, --device .. --device + N - 1 [default: 1]\n"
+    "      --min-count <N>      Write only k-mers that occur at least N times [default: 1]\n"
+    "      --max-count <N>      Write only k-mers that occur at most N times [default: 4294967295]\n"
+    "      --histo              Also write the abundance spectrum of the whole table to {output}/kmers.histo\n"
+    "                           (lines \"count<TAB>k-mers\", count = 1..H; the last line counts H or more)\n"
+    "      --histo-max <H>      Highest count of kmers.histo [default: 10000]\n"
+    "      --histo-only         Write kmers.histo and no kmers.counts (implies --histo)\n"
     "  -h, --help               Print help\n";
 
 const char *HELP_COV =
@@ -348,12 +354,22 @@ int cmd_cgr(int argc, char **argv, int from) {
 int cmd_ctr(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},  {'o', "output", true}, {'k', "k-size", true},
                                      {'m', "memory", true}, {'a', "acgt", false},  {'t', "threads", true},
-                                     {0, "device", true},   {0, "devices", true}};
+                                     {0, "device", true},   {0, "devices", true},
+                                     {0, "min-count", true}, {0, "max-count", true}, {0, "histo", false},
+                                     {0, "histo-max", true}, {0, "histo-only", false}};
     const auto f = parse_flags(argc, argv, from, specs, HELP_CTR);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    // the output filters and the spectrum (jellyfish dump -L/-U and histo --high, kmc -ci/-cx): checked before any device work
+    const uint64_t min_count = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
+    const uint64_t max_count = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (min_count > max_count)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(min_count) + " is greater than " +
+                    std::to_string(max_count));
+    const uint64_t histo_max = ranged(f, "histo-max", 1, (1u << 24) - 1, false, 10000);
+    const bool histo_only = f.count("histo-only") != 0, histo = histo_only || f.count("histo") != 0;
     if (int rc = make_out_dir(out)) return rc;
     if (format_from_path(in) == SeqFormat::Unknown) {
         // CountComputer::new unwraps SeqFormat::get (counter/src/lib.rs:38): unknown extension - "-" included - panics
@@ -366,6 +382,8 @@ int cmd_ctr(int argc, char **argv, int from) {
     if (f.count("acgt")) ctr.set_acgt_output(true);
     ctr.set_max_memory((double)mem);
     ctr.set_device((int)ranged(f, "device", 0, 63, false, 0));
+    ctr.set_count_range((uint32_t)min_count, (uint32_t)max_count);
+    if (histo) ctr.set_histo((uint32_t)histo_max, histo_only);
     std::string e = ctr.count();
     if (e.empty()) e = ctr.merge(true);
     if (!e.empty()) {

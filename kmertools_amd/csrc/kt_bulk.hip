@@ -2887,15 +2887,56 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(uint64_t *__restrict__ 
     }
     if (threadIdx.x == 0) tile_sums[n_tiles] = carry;
 }
+// the counting pass of a filtered export (kt_table_dense_export_range): kept[r] = entries of range r with lo <= occurrences
+// <= hi, tile_sums[tile] = their sum over the tile's 256 ranges.  A wave per range, four 16-byte loads of counts in
+// flight per lane.
+__global__ __launch_bounds__(XT) void dense_kept_kernel(const Slot *__restrict__ slots, uint32_t RS, uint64_t n_ranges,
+                                                        const uint32_t *__restrict__ range_counts, uint32_t lo, uint32_t hi,
+                                                        uint32_t *__restrict__ kept, uint64_t *__restrict__ tile_sums) {
+    __shared__ uint32_t wsum[XT / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t r0 = (uint64_t)blockIdx.x * XT;
+    uint32_t mine = 0;
+    for (uint32_t r = wave; r < XT && r0 + r < n_ranges; r += XT / 64) {
+        const uint32_t D = range_counts[r0 + r], nq = (D + 3u) / 4u;
+        const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(slots + (r0 + r) * RS) + (size_t)RS * 8);
+        uint32_t k = 0;
+        for (uint32_t q0 = 0; q0 < nq; q0 += 256) {
+            uint4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t qi = q0 + 64u * u + lane;
+                v[u] = qi < nq ? q[qi] : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t e = (q0 + 64u * u + lane) * 4u;
+                const uint32_t c0 = v[u].x + 1u, c1 = v[u].y + 1u, c2 = v[u].z + 1u, c3 = v[u].w + 1u;  // occurrences
+                k += (e < D && c0 >= lo && c0 <= hi) + (e + 1u < D && c1 >= lo && c1 <= hi) +
+                     (e + 2u < D && c2 >= lo && c2 <= hi) + (e + 3u < D && c3 >= lo && c3 <= hi);
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) k += __shfl_down(k, o, 64);
+        if (lane == 0) kept[r0 + r] = k;
+        mine += k;  // (lane 0's sum is the wave's)
+    }
+    if (lane == 0) wsum[wave] = mine;
+    __syncthreads();
+    if (tid == 0) tile_sums[blockIdx.x] = (uint64_t)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// FILTER: the ranges' offsets come from kept[] (dense_kept_kernel) and only the entries with lo <= occurrences <= hi are
+// copied (a ballot per 64 entries, in the range's order)
+template <bool FILTER>
 __global__ __launch_bounds__(XT) void dense_export_kernel(const Slot *__restrict__ slots, uint32_t RS, uint64_t n_ranges,
                                                           const uint32_t *__restrict__ range_counts,
                                                           const uint64_t *__restrict__ tile_offsets,
                                                           uint64_t *__restrict__ out_keys,
-                                                          uint32_t *__restrict__ out_counts, uint64_t max_out) {
+                                                          uint32_t *__restrict__ out_counts, uint64_t max_out,
+                                                          const uint32_t *__restrict__ kept, uint32_t lo, uint32_t hi) {
     __shared__ uint32_t offs[XT + 1], cnt[XT], wt[XT / 64];
     const uint32_t tid = threadIdx.x;
     const uint64_t r0 = (uint64_t)blockIdx.x * XT;
-    const uint32_t c = r0 + tid < n_ranges ? range_counts[r0 + tid] : 0u;
+    const uint32_t c = r0 + tid < n_ranges ? (FILTER ? kept : range_counts)[r0 + tid] : 0u;
     uint32_t inc = c;
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t u = __shfl_up(inc, off, 64);
@@ -2909,6 +2950,39 @@ __global__ __launch_bounds__(XT) void dense_export_kernel(const Slot *__restrict
     cnt[tid] = c;
     __syncthreads();
     const uint64_t t0 = tile_offsets[blockIdx.x];
+    if constexpr (FILTER) {
+        const uint32_t lane = tid & 63u;
+        for (uint32_t r = tid >> 6; r < XT && r0 + r < n_ranges; r += XT / 64) {
+            const uint32_t D = range_counts[r0 + r];
+            uint64_t o = t0 + offs[r];
+            const char *rs = reinterpret_cast<const char *>(slots + (r0 + r) * RS);
+            const uint64_t *dkeys = reinterpret_cast<const uint64_t *>(rs);
+            const uint32_t *dcounts = reinterpret_cast<const uint32_t *>(rs + (size_t)RS * 8);
+            for (uint32_t i0 = 0; i0 < D; i0 += 256) {
+                uint32_t vc[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t i = i0 + 64u * u + lane;
+                    vc[u] = i < D ? dcounts[i] + 1u : 0u;  // occurrences (0: beyond the range's entries)
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t i = i0 + 64u * u + lane;
+                    const bool keep = i < D && vc[u] >= lo && vc[u] <= hi;
+                    const uint64_t bal = __ballot(keep);
+                    if (keep) {
+                        const uint64_t at = o + __popcll(bal & ((1ull << lane) - 1ull));
+                        if (at < max_out) {
+                            out_keys[at] = dkeys[i];
+                            out_counts[at] = vc[u];
+                        }
+                    }
+                    o += __popcll(bal);
+                }
+            }
+        }
+        return;
+    }
     // every wave copies ranges of its own (no workgroup barrier in the loop), four loads in flight per lane
     for (uint32_t r = tid >> 6; r < XT && r0 + r < n_ranges; r += XT / 64) {
         const uint32_t D = cnt[r];
@@ -3705,8 +3779,31 @@ int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uin
     hipLaunchKernelGGL(tile_sums_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, ctr->range_counts, n_ranges, tiles);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles);
     if (max_out)
-        hipLaunchKernelGGL(dense_export_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
-                           n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out);
+        hipLaunchKernelGGL(dense_export_kernel<false>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
+                           n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, nullptr, 1u, 0xFFFFFFFFu);
+    KT_HIP(hipGetLastError());
+    KT_HIP(hipMemcpyAsync(n, tiles + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KT_HIP(hipStreamSynchronize(ctx->stream));
+    return KT_OK;
+}
+
+// the same restricted to the entries with lo <= occurrences <= hi of a dense table whose ranges are its own slots (not an
+// export target): a counting pass over the ranges' counts (kept per range + tile sums), the tile scan, the filtered copy.
+// *n = the entries kept.  Scratch: the tile offsets and one u32 per range, next to each other in the context's s_aux0.
+int kt_table_dense_export_range(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint32_t lo, uint32_t hi,
+                                uint64_t *n) {
+    kt_ctx *ctx = ctr->ctx;
+    const uint32_t RS = ctr->m8 << (LOG2_S - 3);
+    const uint64_t n_ranges = ctr->cap / RS, n_tiles = (n_ranges + XT - 1) / XT;
+    if (int rc = ctx->s_aux0.reserve((n_tiles + 1) * 8 + n_ranges * 4)) return rc;
+    uint64_t *tiles = (uint64_t *)ctx->s_aux0.p;
+    uint32_t *kept = (uint32_t *)(tiles + n_tiles + 1);
+    hipLaunchKernelGGL(dense_kept_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS, n_ranges,
+                       ctr->range_counts, lo, hi, kept, tiles);
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles);
+    if (max_out)
+        hipLaunchKernelGGL(dense_export_kernel<true>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
+                           n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, kept, lo, hi);
     KT_HIP(hipGetLastError());
     KT_HIP(hipMemcpyAsync(n, tiles + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
     KT_HIP(hipStreamSynchronize(ctx->stream));

@@ -84,10 +84,13 @@ __global__ __launch_bounds__(BLOCK) void table_clear_kernel(Slot *__restrict__ s
 #define KT_EXPORT_XPT 16
 #endif
 constexpr uint32_t XPT = KT_EXPORT_XPT, XTILE = BLOCK * XPT;
+// FILTER (kt_ctr_export_stage_range): only the slots whose occurrences lie in [lo, hi] are in the ballot
+template <bool FILTER = false>
 __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restrict__ slots, uint64_t cap,
                                                              uint64_t *__restrict__ out_keys,
                                                              uint32_t *__restrict__ out_counts, uint64_t max_out,
-                                                             uint64_t *__restrict__ cursor) {
+                                                             uint64_t *__restrict__ cursor, uint32_t lo,
+                                                             uint32_t hi) {
     __shared__ uint32_t runs[BLOCK / 64 * XPT];  // occupied slots per (wave, load), then their exclusive prefix
     static_assert(BLOCK / 64 * XPT == 64, "one wave scans the runs, one per lane");
     __shared__ uint64_t tile_base;
@@ -113,7 +116,12 @@ __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restr
         uint64_t bal[XPT];
 #pragma unroll
         for (uint32_t j = 0; j < XPT; j++) {
-            bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu);  // key != KT_EMPTY_KEY
+            if constexpr (FILTER) {
+                const uint32_t occ = v[j].z + 1u;
+                bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu && occ >= lo && occ <= hi);
+            } else {
+                bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu);  // key != KT_EMPTY_KEY
+            }
             if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
         }
         ktd::lds_barrier();
@@ -148,6 +156,199 @@ __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restr
         }
         ktd::lds_barrier();  // runs[] / tile_base are rewritten by the next tile
     }
+}
+
+// (key, occurrences) pairs -> the entries with lo <= occurrences <= hi, compacted (kt_ctr_export_stage_range over a table
+// whose entries are an export target's arrays).  The tiles of table_export_kernel over 4-byte counts; a key is read only
+// for an entry that is kept and fits: with max_out = 0 the kernel only counts, and reads the counts alone.
+__global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__restrict__ keys,
+                                                             const uint32_t *__restrict__ counts, uint64_t n,
+                                                             uint32_t lo, uint32_t hi, uint64_t *__restrict__ out_keys,
+                                                             uint32_t *__restrict__ out_counts, uint64_t max_out,
+                                                             uint64_t *__restrict__ cursor) {
+    __shared__ uint32_t runs[BLOCK / 64 * XPT];
+    __shared__ uint64_t tile_base;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t n_tiles = (n + XTILE - 1) / XTILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        uint32_t c[XPT];
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++) {
+            const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
+            c[j] = i < n ? counts[i] : 0u;
+        }
+        uint64_t bal[XPT];
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++) {
+            const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
+            bal[j] = __ballot(i < n && c[j] >= lo && c[j] <= hi);
+            if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
+        }
+        ktd::lds_barrier();
+        if (wave == 0) {
+            const uint32_t v = runs[lane];
+            uint32_t inc = v;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t u = __shfl_up(inc, off, 64);
+                if (lane >= (uint32_t)off) inc += u;
+            }
+            runs[lane] = inc - v;
+            if (lane == 63)
+                tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;
+        }
+        ktd::lds_barrier();
+        const uint64_t base = tile_base;
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++) {
+            if ((bal[j] >> lane) & 1ull) {
+                const uint64_t pos = base + runs[wave * XPT + j] + __popcll(bal[j] & ((1ull << lane) - 1ull));
+                if (pos < max_out) {
+                    out_keys[pos] = keys[tile * XTILE + (uint64_t)j * BLOCK + tid];
+                    out_counts[pos] = c[j];
+                }
+            }
+        }
+        ktd::lds_barrier();
+    }
+}
+
+// ---- the abundance spectrum (kt_ctr_spectrum) ---------------------------------------------------------------------
+// One pass over what the table's form keeps, counts only (+ the keys where emptiness is in them): hist[min(c, top)] += 1
+// per entry of c occurrences.  The spectrum is skewed - nearly every entry of uniform random reads has c = 1, of reads
+// sampled from a genome c near the coverage - so a same-address atomic per entry would serialise a wave on one bin.
+// Counts 1..SPEC_REG are tallied in registers (an unrolled compare, no dynamic indexing) and reduced once per wave at the
+// end; SPEC_REG < c < SPEC_LDS go to a workgroup histogram in LDS (no-return adds, the bins of a coverage peak spread
+// the lanes over many addresses); c >= SPEC_LDS to 64-bit global atomics (rare: the repeats).  Every workgroup merges
+// its non-zero bins once, at the end.  The register and LDS tallies are u32: a workgroup's share of the entries is
+// bounded below 2^31 by the grid (spectrum_grid).
+constexpr uint32_t SPEC_REG = 8, SPEC_LDS = 4096, SPEC_UNROLL = 4;
+enum SpecForm { SPEC_PROBE = 0, SPEC_DENSE = 1, SPEC_PAIRS = 2 };
+
+struct SpecTally {
+    uint32_t reg[SPEC_REG] = {};
+    uint32_t n = 0;
+    uint64_t occ = 0;
+    __device__ __forceinline__ void add(uint32_t c, uint32_t top, uint32_t *lds, uint64_t *hist) {
+        n++;
+        occ += c;
+        const uint32_t b = c < top ? c : top;
+#pragma unroll
+        for (uint32_t j = 0; j < SPEC_REG; j++) reg[j] += b == j + 1u;
+        if (b > SPEC_REG) {
+            if (b < SPEC_LDS) atomicAdd(&lds[b], 1u);  // (the result is unused: a no-return ds_add)
+            else atomicAdd(reinterpret_cast<unsigned long long *>(hist + b), 1ull);
+        }
+    }
+};
+
+// FORM = SPEC_PROBE: `src` is the slots [n) (16-byte slots; stored count = occurrences - 1, KT_EMPTY_KEY free);
+// SPEC_DENSE: the ranges of a dense table, n of them, RS slots each, range r's range_counts[r] counts (occurrences - 1)
+// from byte 8 * RS of the range on; SPEC_PAIRS: n counts (occurrences) from `src` on, which may start anywhere (a
+// caller's array): the 16-byte quads are aligned down, `head` counts of the first quad lie before the array.
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void spectrum_kernel(const void *__restrict__ src, uint64_t n, uint32_t RS, uint32_t head,
+                                                         const uint32_t *__restrict__ range_counts,
+                                                         uint64_t *__restrict__ hist, uint32_t n_bins,
+                                                         uint64_t *__restrict__ totals) {
+    __shared__ uint32_t lds[SPEC_LDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t top = n_bins - 1u, lds_bins = n_bins < SPEC_LDS ? n_bins : SPEC_LDS;
+    for (uint32_t b = tid; b < lds_bins; b += BLOCK) lds[b] = 0u;
+    ktd::lds_barrier();
+    SpecTally t;
+    if constexpr (FORM == SPEC_PROBE) {
+        const uint4 *slots = reinterpret_cast<const uint4 *>(src);
+        constexpr uint32_t TILE = BLOCK * SPEC_UNROLL;
+        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
+            uint4 v[SPEC_UNROLL];
+#pragma unroll
+            for (uint32_t u = 0; u < SPEC_UNROLL; u++) {
+                const uint64_t i = i0 + u * BLOCK + tid;
+                v[u] = i < n ? slots[i] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < SPEC_UNROLL; u++)
+                if ((v[u].x & v[u].y) != 0xFFFFFFFFu) t.add(v[u].z + 1u, top, lds, hist);
+        }
+    } else if constexpr (FORM == SPEC_DENSE) {
+        // a wave per range: the range's counts as quads, SPEC_UNROLL 16-byte loads in flight per lane
+        const uint32_t wave = tid >> 6;
+        const uint64_t waves = (uint64_t)gridDim.x * (BLOCK / 64);
+        for (uint64_t r = (uint64_t)blockIdx.x * (BLOCK / 64) + wave; r < n; r += waves) {
+            const uint32_t D = range_counts[r];
+            const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(src) + r * RS * 16ull + RS * 8ull);
+            const uint32_t nq = (D + 3u) / 4u;
+            for (uint32_t q0 = 0; q0 < nq; q0 += 64u * SPEC_UNROLL) {
+                uint4 v[SPEC_UNROLL];
+#pragma unroll
+                for (uint32_t u = 0; u < SPEC_UNROLL; u++) {
+                    const uint32_t qi = q0 + u * 64u + lane;
+                    v[u] = qi < nq ? q[qi] : make_uint4(0u, 0u, 0u, 0u);
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < SPEC_UNROLL; u++) {
+                    const uint32_t e = (q0 + u * 64u + lane) * 4u;
+                    if (e < D) t.add(v[u].x + 1u, top, lds, hist);
+                    if (e + 1u < D) t.add(v[u].y + 1u, top, lds, hist);
+                    if (e + 2u < D) t.add(v[u].z + 1u, top, lds, hist);
+                    if (e + 3u < D) t.add(v[u].w + 1u, top, lds, hist);
+                }
+            }
+        }
+    } else {
+        const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint32_t *>(src) - head);
+        const uint64_t end = n + head, nq = (end + 3u) / 4u;
+        constexpr uint32_t TILE = BLOCK * SPEC_UNROLL;
+        for (uint64_t q0 = (uint64_t)blockIdx.x * TILE; q0 < nq; q0 += (uint64_t)gridDim.x * TILE) {
+            uint4 v[SPEC_UNROLL];
+#pragma unroll
+            for (uint32_t u = 0; u < SPEC_UNROLL; u++) {
+                const uint64_t qi = q0 + u * BLOCK + tid;
+                v[u] = qi < nq ? q[qi] : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < SPEC_UNROLL; u++) {
+                const uint64_t e = (q0 + u * BLOCK + tid) * 4u;
+                if (e >= head && e < end) t.add(v[u].x, top, lds, hist);
+                if (e + 1u >= head && e + 1u < end) t.add(v[u].y, top, lds, hist);
+                if (e + 2u >= head && e + 2u < end) t.add(v[u].z, top, lds, hist);
+                if (e + 3u >= head && e + 3u < end) t.add(v[u].w, top, lds, hist);
+            }
+        }
+    }
+    // the register tallies: one wave reduction per bin, lane 0 adds the wave's sums to the LDS bins
+#pragma unroll
+    for (uint32_t j = 0; j < SPEC_REG; j++) {
+        uint32_t s = t.reg[j];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        if (lane == 0 && s) atomicAdd(&lds[j + 1u], s);  // (j + 1 <= top < lds_bins whenever s != 0)
+    }
+    if (totals) {
+        uint64_t n_e = t.n, occ = t.occ;
+        for (int o = 32; o > 0; o >>= 1) {
+            n_e += __shfl_down(n_e, o, 64);
+            occ += __shfl_down(occ, o, 64);
+        }
+        if (lane == 0 && n_e) {
+            atomicAdd(reinterpret_cast<unsigned long long *>(totals), (unsigned long long)n_e);
+            atomicAdd(reinterpret_cast<unsigned long long *>(totals + 1), (unsigned long long)occ);
+        }
+    }
+    ktd::lds_barrier();
+    for (uint32_t b = 1u + tid; b < lds_bins; b += BLOCK)
+        if (const uint32_t v = lds[b]) atomicAdd(reinterpret_cast<unsigned long long *>(hist + b), (unsigned long long)v);
+}
+
+// workgroups of a spectrum launch over `items` entries (slots / counts): ~4 per CU, and enough that no workgroup's share
+// reaches 2^31 entries (its u32 tallies)
+uint32_t spectrum_grid(const kt_ctx *ctx, uint64_t work_items, uint64_t entries) {
+    uint64_t g = (uint64_t)ctx->n_cu * 4;
+    if (g > work_items) g = work_items;
+    const uint64_t need = (entries >> 31) + 1;
+    if (g < need) g = need;
+    if (g < 1) g = 1;
+    return (uint32_t)g;
 }
 
 // ---- routing (multi-GPU ownership) ------------------------------------------------------
@@ -566,8 +767,8 @@ int kt_ctr_export(kt_ctr *ctr, uint64_t *keys, uint32_t *counts, uint64_t max_ou
         return KT_OK;
     }
     KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(table_export_kernel, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0,
-                       ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, max_out, ctr->cursor);
+    hipLaunchKernelGGL(table_export_kernel<false>, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0,
+                       ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, max_out, ctr->cursor, 1u, 0xFFFFFFFFu);
     KT_HIP(hipGetLastError());
     uint64_t n = 0;
     KT_HIP(hipMemcpyAsync(&n, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -612,6 +813,117 @@ int kt_ctr_export_stage(kt_ctr *ctr, uint64_t *n_out) {
     }
     ctr->stage_n = n;
     *n_out = n;
+    return KT_OK;
+}
+
+// kt_ctr_export_stage restricted to lo <= occurrences <= hi, in whatever form the table is in: the probing image through
+// the export ballot with the predicate in it, dense ranges through a counting pass + the tile scan + a filtered copy
+// (kt_table_dense_export_range), an export target's pairs compacted into the table's own stage buffers (counted first:
+// kept x 12 bytes).  The first two stage into buffers of the table's size, as the unfiltered stage does.
+int kt_ctr_export_stage_range(kt_ctr *ctr, uint32_t min_count, uint32_t max_count, uint64_t *n_out) {
+    if (!ctr || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: null");
+    if (min_count > max_count) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: min_count > max_count");
+    if (min_count <= 1u && max_count == 0xFFFFFFFFu) return kt_ctr_export_stage(ctr, n_out);
+    kt_ctx *ctx = ctr->ctx;
+    if (int rc = ctx->use()) return rc;
+    uint64_t n = 0;
+    if (int rc = kt_ctr_size(ctr, &n)) return rc;
+    ctr->stage_keys = nullptr;
+    ctr->stage_counts = nullptr;
+    ctr->stage_n = 0;
+    uint64_t kept = 0;
+    if (n) {
+        if (ctr->dense && ctr->dense_ext) {
+            const uint32_t grid = grid_for(ctx, (n + XTILE - 1) / XTILE, 8);
+            KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
+            hipLaunchKernelGGL(pairs_filter_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, ctr->xt_keys, ctr->xt_counts, n,
+                               min_count, max_count, nullptr, nullptr, 0ull, ctr->cursor);
+            KT_HIP(hipGetLastError());
+            KT_HIP(hipMemcpyAsync(&kept, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KT_HIP(hipStreamSynchronize(ctx->stream));
+            if (kept) {
+                if (int rc = ctr->b_stage_k.reserve(kept * 8)) return rc;
+                if (int rc = ctr->b_stage_c.reserve(kept * 4)) return rc;
+                KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
+                hipLaunchKernelGGL(pairs_filter_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, ctr->xt_keys, ctr->xt_counts,
+                                   n, min_count, max_count, (uint64_t *)ctr->b_stage_k.p, (uint32_t *)ctr->b_stage_c.p, kept,
+                                   ctr->cursor);
+                KT_HIP(hipGetLastError());
+                KT_HIP(hipStreamSynchronize(ctx->stream));
+            }
+        } else {
+            if (int rc = ctr->b_stage_k.reserve(n * 8)) return rc;
+            if (int rc = ctr->b_stage_c.reserve(n * 4)) return rc;
+            uint64_t *d_keys = (uint64_t *)ctr->b_stage_k.p;
+            uint32_t *d_counts = (uint32_t *)ctr->b_stage_c.p;
+            if (ctr->dense) {
+                if (int rc = kt_table_dense_export_range(ctr, d_keys, d_counts, n, min_count, max_count, &kept)) return rc;
+            } else {
+                if (int rc = ensure_cleared(ctr)) return rc;
+                KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
+                hipLaunchKernelGGL(table_export_kernel<true>, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)),
+                                   dim3(BLOCK), 0, ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, n,
+                                   ctr->cursor, min_count, max_count);
+                KT_HIP(hipGetLastError());
+                KT_HIP(hipMemcpyAsync(&kept, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+                KT_HIP(hipStreamSynchronize(ctx->stream));
+            }
+            if (kept > n) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: more entries than the table's size");
+        }
+        if (kept) {
+            ctr->stage_keys = (const uint64_t *)ctr->b_stage_k.p;
+            ctr->stage_counts = (const uint32_t *)ctr->b_stage_c.p;
+        }
+    }
+    ctr->stage_n = kept;
+    *n_out = kept;
+    return KT_OK;
+}
+
+int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *totals, int mem) {
+    if (!ctr || !hist) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: null");
+    if (n_bins < 2 || n_bins > (1u << 24)) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: n_bins must be in 2..2^24");
+    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: bad mem");
+    kt_ctx *ctx = ctr->ctx;
+    if (int rc = ctx->use()) return rc;
+    uint64_t n = 0;
+    if (int rc = kt_ctr_size(ctr, &n)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    if (!n) return KT_OK;                           // nothing to add (a table pending its clear is empty too)
+    uint64_t *d_hist = hist, *d_totals = totals;
+    if (mem == KT_MEM_HOST) {
+        if (int rc = ctx->s_aux1.reserve(((size_t)n_bins + 2) * 8)) return rc;
+        d_hist = (uint64_t *)ctx->s_aux1.p;
+        d_totals = totals ? d_hist + n_bins : nullptr;
+        KT_HIP(hipMemsetAsync(d_hist, 0, ((size_t)n_bins + 2) * 8, ctx->stream));
+    }
+    constexpr uint64_t TILE = (uint64_t)BLOCK * SPEC_UNROLL;
+    if (ctr->dense && ctr->dense_ext) {
+        const uint32_t head = (uint32_t)(((uintptr_t)ctr->xt_counts & 15u) / 4u);
+        const uint64_t nq = (n + head + 3) / 4;
+        hipLaunchKernelGGL(spectrum_kernel<SPEC_PAIRS>, dim3(spectrum_grid(ctx, (nq + TILE - 1) / TILE, n)), dim3(BLOCK), 0,
+                           ctx->stream, (const void *)ctr->xt_counts, n, 0u, head, nullptr, d_hist, n_bins, d_totals);
+    } else if (ctr->dense) {
+        const uint32_t RS = ctr->m8 << (kttab::LOG2_RANGE - 3);
+        const uint64_t n_ranges = ctr->cap / RS;
+        hipLaunchKernelGGL(spectrum_kernel<SPEC_DENSE>, dim3(spectrum_grid(ctx, (n_ranges + 3) / 4, n)), dim3(BLOCK), 0,
+                           ctx->stream, (const void *)ctr->slots, n_ranges, RS, 0u, ctr->range_counts, d_hist, n_bins,
+                           d_totals);
+    } else {
+        hipLaunchKernelGGL(spectrum_kernel<SPEC_PROBE>, dim3(spectrum_grid(ctx, (ctr->cap + TILE - 1) / TILE, ctr->cap)),
+                           dim3(BLOCK), 0, ctx->stream, (const void *)ctr->slots, ctr->cap, 0u, 0u, nullptr, d_hist, n_bins,
+                           d_totals);
+    }
+    KT_HIP(hipGetLastError());
+    if (mem == KT_MEM_HOST) {
+        std::vector<uint64_t> h((size_t)n_bins + 2);
+        KT_HIP(hipMemcpyAsync(h.data(), d_hist, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint32_t b = 1; b < n_bins; b++) hist[b] += h[b];
+        if (totals) {
+            totals[0] += h[n_bins];
+            totals[1] += h[(size_t)n_bins + 1];
+        }
+    }
     return KT_OK;
 }
 

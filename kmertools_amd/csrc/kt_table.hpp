@@ -144,3 +144,6 @@ int kt_table_image(kt_ctr *ctr);
 // kt_table_image does for a table whose entries live in the export target)
 int kt_ctr_reload_pairs(kt_ctr *ctr, const uint64_t *d_keys, const uint32_t *d_counts);
 int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint64_t *n);
+// ... only the entries with lo <= occurrences <= hi (kt_ctr_export_stage_range); not for a table in an export target
+int kt_table_dense_export_range(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint32_t lo, uint32_t hi,
+                                uint64_t *n);

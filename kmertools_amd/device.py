@@ -414,12 +414,45 @@ class Counter:
                      dtype, KT_MEM_HOST)
         return out
 
-    def export_host(self, sort=True):
-        n = self.size()
-        keys = np.zeros(max(n, 1), np.uint64)
-        counts = np.zeros(max(n, 1), np.uint32)
-        got = self.export(keys, counts, n, KT_MEM_HOST) if n else 0
-        keys, counts = keys[:got], counts[:got]
+    def spectrum(self, n_bins=10001, totals=False):
+        """The table's abundance spectrum (jellyfish histo): hist[c] = distinct k-mers with exactly c occurrences for
+        1 <= c < n_bins - 1, hist[n_bins - 1] = those with n_bins - 1 or more, hist[0] = 0.  totals=True: also
+        (distinct k-mers, occurrences), exact whatever n_bins."""
+        hist = np.zeros(int(n_bins), np.uint64)
+        tot = np.zeros(2, np.uint64)
+        check(_lib.lib().kt_ctr_spectrum(self._h, _ptr(hist), int(n_bins), _ptr(tot) if totals else None, KT_MEM_HOST))
+        return (hist, (int(tot[0]), int(tot[1]))) if totals else hist
+
+    def spectrum_into(self, hist, n_bins, totals=None, mem=KT_MEM_DEVICE):
+        """adds the spectrum into `hist` (n_bins u64) and (distinct, occurrences) into `totals` (2 u64, or None)"""
+        check(_lib.lib().kt_ctr_spectrum(self._h, _ptr(hist), int(n_bins), _ptr(totals), mem))
+        return hist
+
+    def export_stage_range(self, min_count=1, max_count=None):
+        """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
+        n = C.c_uint64()
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        check(_lib.lib().kt_ctr_export_stage_range(self._h, int(min_count), hi, C.byref(n)))
+        return n.value
+
+    def export_fetch(self, first, count):
+        keys = np.zeros(max(count, 1), np.uint64)
+        counts = np.zeros(max(count, 1), np.uint32)
+        if count:
+            check(_lib.lib().kt_ctr_export_fetch(self._h, int(first), int(count), _ptr(keys), _ptr(counts)))
+        return keys[:count], counts[:count]
+
+    def export_host(self, sort=True, min_count=1, max_count=None):
+        """(keys, counts) of the table; with a count range (min_count > 1 or max_count given) only the entries in it,
+        filtered on the device (kt_ctr_export_stage_range)"""
+        if min_count > 1 or max_count is not None:
+            keys, counts = self.export_fetch(0, self.export_stage_range(min_count, max_count))
+        else:
+            n = self.size()
+            keys = np.zeros(max(n, 1), np.uint64)
+            counts = np.zeros(max(n, 1), np.uint32)
+            got = self.export(keys, counts, n, KT_MEM_HOST) if n else 0
+            keys, counts = keys[:got], counts[:got]
         if sort:
             order = np.argsort(keys, kind="stable")
             keys, counts = keys[order], counts[order]
