@@ -305,6 +305,23 @@ int kt_cov_batch_part(kt_ctr *table, const uint8_t *bases, const uint64_t *offse
                       uint64_t bin_size, uint64_t bin_count, uint32_t *counts, int mem, uint32_t n_parts,
                       uint32_t part);
 
+/* Per-read k-mer solidity against the table (the read filter, `kmertools filter`).  A read's k-mers are its valid windows
+ * (a window holding a non-ACGT byte is none, as for every other k-mer walk here), canonical; a k-mer's count is the
+ * table's, 0 when absent.  A k-mer is SOLID when min_count <= count <= max_count (min_count >= 1: an absent k-mer is
+ * never solid), WEAK otherwise.  Per read i, for the k-mers of hash partition `part` of n_parts:
+ *   n_kmers[i]    += the k-mers,
+ *   n_solid[i]    += the solid ones,
+ *   first_weak[i]  = min(first_weak[i], start in the read of the first weak one) - 0xFFFFFFFF when there is none.
+ * The caller initialises the arrays once to 0 / 0 / 0xFFFFFFFF; combined over parts 0..n_parts-1 (the tables of an
+ * out-of-core count, kt_ctr_add_reads_part) they are the whole table's answer.  first_weak may be NULL (its work is
+ * then skipped).  `mem` says where bases, offsets and the three arrays live; KT_MEM_HOST synchronises.
+ * KT_ERR_ARG: min_count == 0, min_count > max_count, part >= n_parts, a bad mem, a null buffer with n_reads > 0, a read
+ * of 2^32 bases or more (positions are u32), or a table that is one shard of a sharded table (n_owners > 1: a shard
+ * cannot tell a k-mer absent here from one absent everywhere - shards are not supported). */
+int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                         uint32_t min_count, uint32_t max_count, uint32_t *n_kmers, uint32_t *n_solid,
+                         uint32_t *first_weak, int mem, uint32_t n_parts, uint32_t part);
+
 /* Multi-GPU routing step (the reference's `min_mer % n_parts` partitioning,
  * counter/src/lib.rs:127, re-expressed as hash-prefix ownership):
  * writes every canonical k-mer of the reads into keys_out grouped by owner

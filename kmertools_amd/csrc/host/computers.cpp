@@ -1292,6 +1292,136 @@ std::string CovComputer::compute_coverages() {
 }
 
 // ---------------------------------------------------------------------------------------------
+FilterComputer::FilterComputer(std::string in_path, std::string out_path, int ksize)
+    : in_path_(in_path), in_path_kmer_(std::move(in_path)), out_path_(std::move(out_path)), ksize_(ksize) {}
+
+FilterComputer::~FilterComputer() { delete ctr_; }
+
+static constexpr uint32_t NO_WEAK = 0xFFFFFFFFu;  // first_weak of a read without a weak k-mer
+
+// one pass of an out-of-core table is complete: every read's numbers for the k-mers of this hash partition
+std::string FilterComputer::filter_pass(uint32_t pass, uint32_t passes, kt_ctr *table) {
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    Batch b;
+    uint64_t at = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20));
+        const uint64_t n = b.n_reads();
+        if (n) {
+            if (pass == 0) {
+                acc_n_.resize(at + n, 0u);
+                acc_s_.resize(at + n, 0u);
+                if (trim_) acc_w_.resize(at + n, NO_WEAK);
+            } else if (at + n > acc_n_.size()) {
+                return "filter: the input changed between the passes";
+            }
+            if (kt_ctr_read_solidity(table, bases_ptr(b), b.offsets.data(), n, min_count_, max_count_, acc_n_.data() + at,
+                                     acc_s_.data() + at, trim_ ? acc_w_.data() + at : nullptr, KT_MEM_HOST, passes, pass) != KT_OK)
+                return kt_last_error();
+            at += n;
+        }
+        if (!more) break;
+    }
+    if (reader.failed()) return reader.error();
+    acc_reads_ = at;
+    return "";
+}
+
+void FilterComputer::emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const {
+    const uint64_t k = (uint64_t)ksize_;
+    for (uint64_t i = 0; i < b.n_reads(); i++) {
+        if (n[i] == 0) continue;  // no k-mer: dropped in either mode
+        const uint64_t o = b.offsets[i];
+        uint64_t keep = b.offsets[i + 1] - o;
+        if (trim_) {
+            if (w[i] != NO_WEAK) keep = (uint64_t)w[i] + k - 1;  // up to the base before the first weak k-mer's last
+            if (keep < k) continue;
+        } else if (!((double)s[i] >= min_solid_ * (double)n[i])) {
+            continue;
+        }
+        out += fastq ? '@' : '>';
+        out += b.headers[i];
+        out += '\n';
+        out.append((const char *)b.bases.data() + o, keep);
+        out += '\n';
+        if (fastq) {
+            out += "+\n";
+            out.append((const char *)b.quals.data() + o, keep);
+            out += '\n';
+        }
+    }
+}
+
+std::string FilterComputer::filter() {
+    delete ctr_;
+    acc_n_.clear();
+    acc_s_.clear();
+    acc_w_.clear();
+    acc_reads_ = 0;
+    ctr_ = new CountComputer(in_path_kmer_, ".", ksize_);
+    ctr_->set_threads(threads_);
+    ctr_->set_max_memory(memory_ceil_gb_);
+    ctr_->set_device(device_);
+    ctr_->set_histo(0, true);  // no kmers.histo and no kmers.counts: the table is only looked up
+    ctr_->set_pass_hook([this](uint32_t pass, uint32_t passes, kt_ctr *t) { return filter_pass(pass, passes, t); });
+    if (std::string e = ctr_->count(); !e.empty()) return e;
+    const bool resident = ctr_->passes() == 1;  // else: the numbers were combined pass by pass (filter_pass)
+    if (resident && !ctr_->table()) return "filter: no table";
+    const bool fastq = format_from_path(in_path_) == SeqFormat::Fastq;
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    FILE *out = fopen(out_path_.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + out_path_;
+    PhaseTimer pt("filter");
+    Lap lap;
+    Batch b;
+    std::string text, err;
+    std::vector<uint32_t> nk, ns, fw;
+    uint64_t at = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
+        pt.t[0] += lap();
+        const uint64_t n = b.n_reads();
+        if (n) {
+            const uint32_t *pn, *ps, *pw;
+            if (resident) {
+                nk.assign(n, 0u);
+                ns.assign(n, 0u);
+                fw.assign(trim_ ? n : 0, NO_WEAK);
+                if (kt_ctr_read_solidity(ctr_->table(), bases_ptr(b), b.offsets.data(), n, min_count_, max_count_, nk.data(),
+                                         ns.data(), trim_ ? fw.data() : nullptr, KT_MEM_HOST, 1, 0) != KT_OK) {
+                    err = kt_last_error();
+                    break;
+                }
+                pn = nk.data(), ps = ns.data(), pw = fw.data();
+            } else {
+                if (at + n > acc_reads_) {
+                    err = "filter: the input changed between the passes";
+                    break;
+                }
+                pn = acc_n_.data() + at, ps = acc_s_.data() + at, pw = trim_ ? acc_w_.data() + at : nullptr;
+            }
+            pt.t[1] += lap();
+            text.clear();
+            emit(b, pn, ps, pw, fastq, text);
+            pt.t[2] += lap();
+            if (fwrite(text.data(), 1, text.size(), out) != text.size()) {
+                err = "Unable to write to file: " + out_path_;
+                break;
+            }
+            pt.t[3] += lap();
+            at += n;
+        }
+        if (!more) break;
+    }
+    if (err.empty() && reader.failed()) err = reader.error();
+    if (err.empty() && !resident && at != acc_reads_) err = "filter: the input changed between the passes";
+    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path_;
+    return err;
+}
+
+// ---------------------------------------------------------------------------------------------
 // minimisers: one C-ABI call per batch; the capacity is a guess that is corrected on the first miss
 static std::string minimiser_batch(kt_ctx *ctx, Work &w, uint64_t wsize, int msize) {
     const uint64_t n = w.b.n_reads();

@@ -20,6 +20,8 @@
 
 namespace kthost {
 
+struct Batch;  // seqio.hpp
+
 // Rust `format!("{:.6}", x)` (oligo.rs:132-134) and `Display` for f64 (shortest round-trip,
 // positional notation, integral values without ".0": oligo.rs:136, oligocgr.rs:95)
 constexpr size_t FIXED6_BUF = 352;  // "%.6f" of DBL_MAX is 316 characters
@@ -182,6 +184,43 @@ class CovComputer {
     ~CovComputer();
     CovComputer(const CovComputer &) = delete;
     CovComputer &operator=(const CovComputer &) = delete;
+};
+
+// `filter`: drops or trims reads by the abundance of their k-mers (kmc_tools filter, BBDuk-style k-mer cleaning).  The
+// table is counted from kmer_path (default: the input) as by CountComputer - resident, or out of core in passes whose
+// per-read numbers are combined here -, then every read's k-mers are looked up (kt_ctr_read_solidity).  A k-mer is solid
+// when min_count <= count <= max_count.  Fraction mode keeps a read with >= 1 k-mer and solid >= F * k-mers; trim mode
+// keeps the prefix up to the last base before the end of the first weak k-mer ([0, first_weak + k - 1)), the whole read
+// without one, and drops what is left shorter than k.  Records are written in the input's format and order, bytes as
+// read (FASTA: header line + the sequence on one line; FASTQ: header, sequence, "+", the quality cut as the sequence).
+class FilterComputer {
+  public:
+    FilterComputer(std::string in_path, std::string out_path, int ksize);
+    ~FilterComputer();
+    FilterComputer(const FilterComputer &) = delete;
+    FilterComputer &operator=(const FilterComputer &) = delete;
+    void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    void set_count_range(uint32_t lo, uint32_t hi) { min_count_ = lo, max_count_ = hi; }
+    void set_min_solid(double f) { min_solid_ = f; }
+    void set_trim(bool t) { trim_ = t; }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }
+    void set_device(int d) { device_ = d; }
+    std::string filter();  // "" or the error message
+
+  private:
+    std::string in_path_, in_path_kmer_, out_path_;
+    int ksize_, threads_ = 0, device_ = 0;
+    uint32_t min_count_ = 2, max_count_ = 0xFFFFFFFFu;
+    double min_solid_ = 1.0, memory_ceil_gb_ = 6.0;
+    bool trim_ = false;
+    CountComputer *ctr_ = nullptr;
+    // out of core: the reads' numbers, combined over the passes as each pass's table is complete (filter_pass)
+    std::vector<uint32_t> acc_n_, acc_s_, acc_w_;
+    uint64_t acc_reads_ = 0;
+    std::string filter_pass(uint32_t pass, uint32_t passes, kt_ctr *table);
+    // appends the kept records of batch b (its numbers: n, s, w) to `out`
+    void emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const;
 };
 
 }  // namespace kthost

@@ -1,7 +1,8 @@
 // kmertools (GPU drop-in) - command line with the reference's `comp oligo`, `comp cgr -k` and
 // `ctr` flags (kmertools/src/args.rs:70-130, 208-236; dispatcher :239-368) and `cov`
 // (args.rs:132-172, :299-325).  clap conventions are kept: kebab-case long flags, the
-// auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.
+// auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.  `filter` (a k-mer read
+// filter, not in the reference) follows the same conventions.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -123,11 +124,12 @@ const char *HELP_MAIN =
     "(MI355X build: every subcommand's per-base work runs on the GPU)\n\n"
     "Usage: kmertools <COMMAND>\n\n"
     "Commands:\n"
-    "  comp  Generate sequence composition based features\n"
-    "  cov   Generates coverage histogram based on the reads\n"
-    "  min   Bin reads using minimisers\n"
-    "  ctr   Count k-mers\n"
-    "  help  Print this message or the help of the given subcommand(s)\n\n"
+    "  comp    Generate sequence composition based features\n"
+    "  cov     Generates coverage histogram based on the reads\n"
+    "  min     Bin reads using minimisers\n"
+    "  ctr     Count k-mers\n"
+    "  filter  Drop or trim reads by the abundance of their k-mers\n"
+    "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
 
 const char *HELP_OLIGO =
@@ -393,6 +395,75 @@ int cmd_ctr(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_FILTER =
+    "Drop or trim reads by the abundance of their k-mers\n\n"
+    "A k-mer is solid when min-count <= its count <= max-count in the table counted from --alt-input (default: the\n"
+    "input), weak otherwise (an absent k-mer is weak).  Reads without a k-mer are dropped.  Kept records are written in\n"
+    "the input's format and order, uncompressed, bytes unchanged (FASTA: the sequence on one line).\n\n"
+    "Usage: kmertools filter [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path (reads to filter)\n"
+    "  -o, --output <OUTPUT>        Output file path (kept reads)\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "  -a, --alt-input <ALT_INPUT>  Input file path, for k-mer counting [default: the input]\n"
+    "      --min-count <N>          Lowest count of a solid k-mer [default: 2]\n"
+    "      --max-count <N>          Highest count of a solid k-mer [default: 4294967295]\n"
+    "      --min-solid <F>          Keep a read when at least this fraction of its k-mers is solid [default: 1.0]\n"
+    "      --trim                   Instead: cut every read before the last base of its first weak k-mer, drop it\n"
+    "                               when less than k bases are left\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted; the table lives in HBM)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_filter(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},      {'o', "output", true},     {'k', "k-size", true},
+                                     {'a', "alt-input", true},  {0, "min-count", true},    {0, "max-count", true},
+                                     {0, "min-solid", true},    {0, "trim", false},        {'m', "memory", true},
+                                     {'t', "threads", true},    {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_FILTER);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work
+    const uint64_t min_count = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 2);
+    const uint64_t max_count = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (min_count > max_count)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(min_count) + " is greater than " +
+                    std::to_string(max_count));
+    const bool trim = f.count("trim") != 0;
+    double min_solid = 1.0;
+    if (auto it = f.find("min-solid"); it != f.end()) {
+        if (trim) usage_error("the argument '--trim' cannot be used with '--min-solid <F>'");
+        char *end = nullptr;
+        min_solid = strtod(it->second.c_str(), &end);
+        if (it->second.empty() || *end || !(min_solid >= 0.0 && min_solid <= 1.0))
+            usage_error("invalid value '" + it->second + "' for '--min-solid': not a number in 0..=1");
+    }
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : {in, kin}) {
+        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    FilterComputer flt(in, out, k);
+    if (threads > 0) flt.set_threads(threads);
+    flt.set_kmer_path(kin);
+    flt.set_count_range((uint32_t)min_count, (uint32_t)max_count);
+    flt.set_min_solid(min_solid);
+    flt.set_trim(trim);
+    flt.set_max_memory((double)mem);
+    flt.set_device(device);
+    if (std::string e = flt.filter(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -407,16 +478,23 @@ int cmd_debug_read(int argc, char **argv, int from) {
     // KT_DEBUG_READ_PASSES=N: the records N times over ONE reader (rewind(): the passes of an out-of-core count); every
     // odd pass before the last is left half-way (a rewind in the middle of the stream, pieces parsed ahead and never taken)
     const int passes = getenv("KT_DEBUG_READ_PASSES") ? atoi(getenv("KT_DEBUG_READ_PASSES")) : 1;
+    // KT_DEBUG_READ_RECORDS=1: whole records (keep_records) - each line also carries the header and the quality
+    const bool records = getenv("KT_DEBUG_READ_RECORDS") != nullptr;
     for (int pass = 0; pass < passes; pass++) {
         if (pass && !r.rewind()) break;
         const bool cut_short = (pass & 1) && pass + 1 < passes;
         if (pass) printf("#pass\t%d\n", pass);
         total = count = 0;
         for (;;) {
-            const bool more = r.next_batch(b, 64, 2, true);  // tiny batches: exercises batch boundaries
+            const bool more = r.next_batch(b, 64, 2, true, records);  // tiny batches: exercises batch boundaries
             for (uint64_t i = 0; i < b.n_reads(); i++) {
                 printf("%llu\t%s\t", (unsigned long long)(b.first_record + i), b.ids[i].c_str());
+                if (records) printf("%s\t", b.headers[i].c_str());
                 fwrite(b.bases.data() + b.offsets[i], 1, b.offsets[i + 1] - b.offsets[i], stdout);
+                if (records && !b.quals.empty()) {
+                    printf("\t");
+                    fwrite(b.quals.data() + b.offsets[i], 1, b.offsets[i + 1] - b.offsets[i], stdout);
+                }
                 printf("\n");
             }
             count += b.n_reads();
@@ -510,5 +588,6 @@ int main(int argc, char **argv) {
     }
     if (cmd == "cov") return cmd_cov(argc, argv, 2);
     if (cmd == "min") return cmd_min(argc, argv, 2);
+    if (cmd == "filter") return cmd_filter(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

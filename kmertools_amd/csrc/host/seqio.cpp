@@ -44,7 +44,7 @@ struct SeqReader::Parallel {
     SeqFormat fmt = SeqFormat::Fasta;
     std::vector<size_t> cuts;  // piece i = [cuts[i], cuts[i + 1])
     uint64_t max_bases = 0, max_reads = 0;
-    bool keep_ids = false, started = false;
+    bool keep_ids = false, keep_records = false, started = false;
     // pieces are parsed by `workers` threads in order of their index; a piece's batches wait in `done` until the
     // consumer has taken every earlier piece (at most `window` pieces are parsed ahead of the consumer)
     struct Piece {
@@ -159,7 +159,7 @@ struct SeqReader::Parallel {
                         spare.pop_back();
                     }
                 }
-                const bool more = r.next_batch(out.back(), max_bases, max_reads, keep_ids);
+                const bool more = r.next_batch(out.back(), max_bases, max_reads, keep_ids, keep_records);
                 if (out.back().n_reads() == 0) out.pop_back();
                 if (!more) break;
             }
@@ -420,11 +420,12 @@ static std::string first_token(const std::string &hdr) {
     return hdr.substr(i, j - i);
 }
 
-bool SeqReader::next_batch_parallel(Batch &b, bool keep_ids) {
+bool SeqReader::next_batch_parallel(Batch &b, bool keep_ids, bool keep_records) {
     Parallel &P = *par_;
     if (!P.started) {
         P.started = true;
         P.keep_ids = keep_ids;
+        P.keep_records = keep_records;
         // one piece should parse into one batch of the caller's size (small batches cost every later stage a call, a
         // thread start, a synchronisation): bytes per record and the share of sequence bytes from the head of the file
         {
@@ -474,6 +475,8 @@ bool SeqReader::next_batch_parallel(Batch &b, bool keep_ids) {
             b.bases.assign(src.bases.begin(), src.bases.end());
             b.offsets.assign(src.offsets.begin(), src.offsets.end());
             b.ids.swap(src.ids);
+            b.headers.swap(src.headers);
+            b.quals.swap(src.quals);
             lk.lock();
             P.spare.emplace_back();
             P.spare.back().bases.swap(src.bases);
@@ -500,13 +503,13 @@ bool SeqReader::next_batch_parallel(Batch &b, bool keep_ids) {
     }
 }
 
-bool SeqReader::next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, bool keep_ids) {
+bool SeqReader::next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, bool keep_ids, bool keep_records) {
     if (par_) {
         if (!par_->started) {
             par_->max_bases = max_bases;
             par_->max_reads = max_reads;
         }
-        return next_batch_parallel(b, keep_ids);
+        return next_batch_parallel(b, keep_ids, keep_records);
     }
     b.clear();
     b.first_record = n_records_;
@@ -529,6 +532,7 @@ bool SeqReader::next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, boo
                 return false;
             }
             if (keep_ids) b.ids.push_back(first_token(pending_));
+            if (keep_records) b.headers.push_back(pending_.substr(1));
             have_pending_ = false;
             const char *lp;
             size_t ln;
@@ -547,6 +551,7 @@ bool SeqReader::next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, boo
                 return false;
             }
             if (keep_ids) b.ids.push_back(first_token(pending_));
+            if (keep_records) b.headers.push_back(pending_.substr(1));
             have_pending_ = false;
             uint64_t seq_lines = 0;
             const size_t start = b.bases.size();
@@ -571,6 +576,7 @@ bool SeqReader::next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, boo
                 if (!read_line_view(lp, ln)) break;
                 trim_end_view(lp, ln);
                 qual += ln;
+                if (keep_records) b.quals.insert(b.quals.end(), lp, lp + ln);
             }
             if (qual != b.bases.size() - start) {
                 err_ = "Unequal length of sequence an qualities.";

@@ -38,11 +38,17 @@ struct Batch {
     std::vector<uint8_t> bases;
     std::vector<uint64_t> offsets;  // n + 1 entries, offsets[0] == 0
     std::vector<std::string> ids;   // filled only when keep_ids
+    // filled only when keep_records (a filter writes back what it read): the whole header line without its '>' / '@'
+    // (trailing whitespace removed), and for FASTQ the quality bytes, concatenated with the same offsets as bases
+    std::vector<std::string> headers;
+    std::vector<uint8_t> quals;
     uint64_t first_record = 0;      // ordinal of the batch's first record (Sequence::n)
     void clear() {
         bases.clear();
         offsets.assign(1, 0);
         ids.clear();
+        headers.clear();
+        quals.clear();
     }
     uint64_t n_reads() const { return offsets.empty() ? 0 : offsets.size() - 1; }
 };
@@ -59,7 +65,8 @@ class SeqReader {
     bool open(const std::string &path, bool sniff);
     // Appends records until the batch holds >= max_bases bases or max_reads reads.
     // Returns false at end of input (the batch may still hold records) or on a parse error.
-    bool next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, bool keep_ids = false);
+    // keep_records: also the headers and (FASTQ) the qualities (Batch::headers, Batch::quals).
+    bool next_batch(Batch &b, uint64_t max_bases, uint64_t max_reads, bool keep_ids = false, bool keep_records = false);
     // Back to the first record, keeping threads and buffers (false: the input cannot be read twice - stdin)
     bool rewind();
     size_t buffer_bytes();  // what the reader's own buffers hold right now
@@ -76,7 +83,7 @@ class SeqReader {
   private:
     struct Parallel;  // the mapped file, its pieces, the worker pool (seqio.cpp)
     std::shared_ptr<Parallel> par_;
-    bool next_batch_parallel(Batch &b, bool keep_ids);
+    bool next_batch_parallel(Batch &b, bool keep_ids, bool keep_records);
     bool fill();
     bool read_line(std::string &line);  // without the trailing '\n'; false at EOF
     // same, without a copy when the whole line sits in the read buffer: [p, p + n) stays valid until the next call

@@ -12,6 +12,8 @@
 // segment); the image is flushed with one global atomic per non-zero cell, so a read that
 // straddles segments is still summed exactly.  Segments made of very many tiny reads (image
 // larger than the LDS budget) add to global memory directly.
+//
+// The read filter's kt_ctr_read_solidity walks and probes the same way and keeps three numbers per read (solidity_kernel).
 #include "kt_internal.hpp"
 #include "kt_launch.hpp"
 #include "kt_segment.hpp"
@@ -47,14 +49,14 @@ __device__ __forceinline__ uint4 load_slot(const Slot *slots, uint64_t slot) {
 
 // occurrences of `key` given the already-loaded home slot `v`; walks on (round the key's range, kt_table.hpp)
 // only on a collision - the probe sequence is recomputed then, so that the common case carries no state for it
-__device__ __forceinline__ uint32_t resolve_count(const CovArgs &c, uint4 v, uint64_t key) {
+__device__ __forceinline__ uint32_t resolve_count(const Slot *slots, const kttab::Geom &g, uint4 v, uint64_t key) {
     uint64_t kk = ((uint64_t)v.y << 32) | v.x;
     if (kk == key) return v.z + 1u;  // stored value is occurrences - 1
     if (kk == KT_EMPTY_KEY) return 0u;
-    kttab::Probe p = kttab::probe_of(key, c.g);
+    kttab::Probe p = kttab::probe_of(key, g);
     for (uint32_t probe = 1; probe < p.rs; probe++) {
         p.next();
-        v = load_slot(c.slots, p.slot());
+        v = load_slot(slots, p.slot());
         kk = ((uint64_t)v.y << 32) | v.x;
         if (kk == key) return v.z + 1u;
         if (kk == KT_EMPTY_KEY) return 0u;
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(BLOCK) void cov_kernel(SegArgs a, CovArgs c) {
                     if (!((ok >> (jj + u)) & 1u)) continue;
                     // (a k-mer that another pass / another shard answers for is not "absent" here: it is skipped)
                     if (c.n_parts > 1 && ktd::owner_of(key[u], c.n_parts) != c.part) continue;
-                    const uint32_t cnt = resolve_count(c, v[u], key[u]);
+                    const uint32_t cnt = resolve_count(c.slots, c.g, v[u], key[u]);
                     uint32_t bin = c.bin_size ? cnt / c.bin_size : 0u;  // coverage/src/lib.rs:172
                     bin = bin < last_bin ? bin : last_bin;              // :173
                     const uint64_t s = s0 + jj + u;
@@ -170,6 +172,138 @@ __global__ __launch_bounds__(BLOCK) void lookup_kernel(const Slot *__restrict__ 
         }
         out[i] = key == KT_EMPTY_KEY ? 0u : cnt;
     }
+}
+
+// ---- per-read k-mer solidity (kt_ctr_read_solidity: the read filter) ------------------------------------------------
+// cov_kernel's walk and probes; per read only three numbers, each combining with an add or a min: the k-mers, the solid
+// ones (min_count <= count <= max_count) and the start in the read of the first weak one.  A thread's 32 window starts
+// are consecutive, so it keeps a running (read, n, solid, first weak) in registers and flushes it when the read changes
+// and at the end - one flush per read boundary, not one per k-mer.  A flush goes to a per-segment LDS image of the
+// segment's reads (3 cells per read: add, add, min), which is flushed with one global atomic per non-default cell.  A
+// segment of more than READS_LDS reads (reads below ~32 bases) flushes to global memory directly.
+constexpr uint32_t READS_LDS = 256;
+constexpr uint32_t NO_POS = 0xFFFFFFFFu;
+
+struct SolidArgs {
+    const Slot *slots;
+    kttab::Geom g;
+    uint32_t min_count, max_count;  // 1 <= min_count <= max_count: an absent k-mer (count 0) is weak
+    uint32_t *n_kmers, *n_solid, *first_weak;  // n_reads each, combined into (first_weak only when FIRST)
+    uint32_t n_parts, part;  // only the k-mers of hash partition `part` are looked at
+};
+
+template <bool FIRST>
+__global__ __launch_bounds__(BLOCK) void solidity_kernel(SegArgs a, SolidArgs c) {
+    __shared__ SegShared sm;
+    __shared__ uint32_t img_n[READS_LDS], img_s[READS_LDS], img_w[READS_LDS];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < READS_LDS; i += BLOCK) {
+        img_n[i] = 0;
+        img_s[i] = 0;
+        img_w[i] = NO_POS;
+    }
+
+    for (uint64_t g = blockIdx.x; g < a.n_seg; g += gridDim.x) {
+        ktseg::stage_segment(a, g, sm);  // its barriers also order the image's initialisation / reset
+        ktseg::Window w(sm, tid, a.k);
+        uint32_t ok = 0;
+        for (uint32_t j = 0; j < ktseg::PER_THREAD; j++) ok |= (w.ok(j) ? 1u : 0u) << j;
+
+        // reads that can own a k-mer starting in this segment: [rbase, r_hi) (as in cov_kernel)
+        const uint64_t B0 = g * ktseg::SEG;
+        const uint64_t r_first = a.seg_first[g];
+        const uint64_t r_hi = a.seg_first[g + 1];
+        const uint64_t rbase = r_first ? r_first - 1 : 0;
+        const uint64_t n_img = r_hi - rbase;
+        const bool in_lds = n_img <= READS_LDS;
+
+        if (ok) {
+            const uint64_t s0 = B0 + (uint64_t)ktseg::PER_THREAD * tid;
+            uint64_t lo = rbase, hi = r_hi;
+            {
+                const uint64_t s = s0 + (uint32_t)__builtin_ctz(ok);
+                while (hi - lo > 1) {
+                    const uint64_t mid = (lo + hi) >> 1;
+                    if (a.offsets[mid] <= s) lo = mid; else hi = mid;
+                }
+            }
+            uint64_t rid = lo;
+            uint64_t start = a.offsets[rid], next = a.offsets[rid + 1];
+            // the running read: `run` (~0: none yet), its k-mers, solid k-mers and first weak start seen by this thread
+            uint64_t run = ~0ull;
+            uint32_t n = 0, sol = 0, weak = NO_POS;
+            auto flush = [&]() {
+                if (in_lds) {
+                    const uint32_t i = (uint32_t)(run - rbase);
+                    atomicAdd(&img_n[i], n);
+                    if (sol) atomicAdd(&img_s[i], sol);
+                    if (FIRST && weak != NO_POS) atomicMin(&img_w[i], weak);
+                } else {
+                    atomicAdd(&c.n_kmers[run], n);
+                    if (sol) atomicAdd(&c.n_solid[run], sol);
+                    if (FIRST && weak != NO_POS) atomicMin(&c.first_weak[run], weak);
+                }
+            };
+#pragma unroll 1
+            for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
+                uint64_t key[GROUP];
+                uint4 v[GROUP];
+#pragma unroll
+                for (uint32_t u = 0; u < GROUP; u++) {
+                    key[u] = w.f < w.r ? w.f : w.r;
+                    w.step();
+                    v[u] = load_slot(c.slots, kttab::probe_of(key[u], c.g).slot());
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < GROUP; u++) {
+                    if (!((ok >> (jj + u)) & 1u)) continue;
+                    if (c.n_parts > 1 && ktd::owner_of(key[u], c.n_parts) != c.part) continue;
+                    const uint32_t cnt = resolve_count(c.slots, c.g, v[u], key[u]);
+                    const uint64_t s = s0 + jj + u;
+                    while (s >= next) {  // empty reads are stepped over
+                        start = next;
+                        next = a.offsets[++rid + 1];
+                    }
+                    if (rid != run) {
+                        if (run != ~0ull) flush();
+                        run = rid;
+                        n = sol = 0;
+                        weak = NO_POS;
+                    }
+                    n++;
+                    if (cnt >= c.min_count && cnt <= c.max_count) sol++;
+                    else if (FIRST && weak == NO_POS) weak = (uint32_t)(s - start);  // starts ascend: the first is the least
+                }
+            }
+            if (run != ~0ull) flush();
+        }
+        __syncthreads();  // sm is restaged by the next segment; the image is complete
+        if (in_lds) {
+            for (uint32_t i = tid; i < (uint32_t)n_img; i += BLOCK) {
+                const uint32_t nk = img_n[i];
+                if (!nk) continue;  // (a read with no k-mer here has no solid or weak one either)
+                atomicAdd(&c.n_kmers[rbase + i], nk);
+                img_n[i] = 0;
+                if (const uint32_t ns = img_s[i]) {
+                    atomicAdd(&c.n_solid[rbase + i], ns);
+                    img_s[i] = 0;
+                }
+                if (FIRST) {
+                    if (const uint32_t wp = img_w[i]; wp != NO_POS) {
+                        atomicMin(&c.first_weak[rbase + i], wp);
+                        img_w[i] = NO_POS;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// flag = 1 when a read holds 2^32 bases or more (its positions would not fit the u32 first_weak)
+__global__ __launch_bounds__(BLOCK) void long_read_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads,
+                                                          uint32_t *__restrict__ flag) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * BLOCK)
+        if (offsets[i + 1] - offsets[i] >= (1ull << 32)) atomicOr(flag, 1u);
 }
 
 // one thread per read: total = sum of the row, out = count / max(1, total) (:180-182)
@@ -327,5 +461,89 @@ extern "C" int kt_cov_batch(kt_ctr *table, const uint8_t *bases, const uint64_t 
         KT_HIP(hipMemcpyAsync(out, d_out, n_cells * esz, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
     }
+    return KT_OK;
+}
+
+// the solidity pass into device arrays (combined into: add, add, min)
+static int solidity_counts(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
+                           uint64_t total, uint32_t min_count, uint32_t max_count, uint32_t *d_n, uint32_t *d_s, uint32_t *d_w,
+                           uint32_t n_parts, uint32_t part) {
+    if (!total) return KT_OK;
+    SegArgs a;
+    if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
+    SolidArgs c{(const Slot *)table->slots, ktl::geom_of(table), min_count, max_count, d_n, d_s, d_w, n_parts, part};
+    if (d_w)
+        hipLaunchKernelGGL(solidity_kernel<true>, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
+    else
+        hipLaunchKernelGGL(solidity_kernel<false>, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
+    KT_HIP(hipGetLastError());
+    return KT_OK;
+}
+
+extern "C" int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                                    uint32_t min_count, uint32_t max_count, uint32_t *n_kmers, uint32_t *n_solid,
+                                    uint32_t *first_weak, int mem, uint32_t n_parts, uint32_t part) {
+    if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null table");
+    if (min_count == 0) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: min_count must be >= 1");
+    if (min_count > max_count) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: min_count > max_count");
+    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: need part < n_parts");
+    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: bad mem");
+    if (table->n_owners > 1)
+        return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: the table is one shard of a sharded table - shards are not supported "
+                                    "(a shard cannot tell a k-mer absent here from one absent everywhere)");
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !n_kmers || !n_solid) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null buffer");
+    kt_ctx *ctx = table->ctx;
+    if (int rc = ctx->use()) return rc;
+    uint64_t total = 0;
+    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
+    if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null bases");
+    if (total >= (1ull << 32)) {  // (below that no read can be this long)
+        bool too_long = false;
+        if (mem == KT_MEM_HOST) {
+            for (uint64_t i = 0; i < n_reads && !too_long; i++) too_long = offsets[i + 1] - offsets[i] >= (1ull << 32);
+        } else {
+            if (int rc = ctx->s_aux2.reserve(4)) return rc;
+            uint32_t *d_flag = (uint32_t *)ctx->s_aux2.p, flag = 0;
+            KT_HIP(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
+            hipLaunchKernelGGL(long_read_kernel, dim3(grid_for(ctx, (n_reads + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
+                               offsets, n_reads, d_flag);
+            KT_HIP(hipGetLastError());
+            KT_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+            KT_HIP(hipStreamSynchronize(ctx->stream));
+            too_long = flag != 0;
+        }
+        if (too_long) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: a read of 2^32 bases or more (positions are u32)");
+    }
+    if (int rc = table_ready(table)) return rc;
+    if (mem == KT_MEM_DEVICE)
+        return solidity_counts(table, ctx, bases, offsets, n_reads, total, min_count, max_count, n_kmers, n_solid, first_weak,
+                               n_parts, part);
+    // host arrays: this call's numbers are made on the device from 0 / 0 / NO_POS and combined into the caller's
+    if (!total) return KT_OK;
+    const uint8_t *d_bases = bases;
+    const uint64_t *d_offsets = offsets;
+    if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
+    const uint64_t n_arr = first_weak ? 3 : 2;
+    if (int rc = ctx->s_aux1.reserve(n_reads * 4 * n_arr)) return rc;
+    uint32_t *d_n = (uint32_t *)ctx->s_aux1.p, *d_s = d_n + n_reads, *d_w = first_weak ? d_s + n_reads : nullptr;
+    KT_HIP(hipMemsetAsync(d_n, 0, n_reads * 8, ctx->stream));
+    if (d_w) KT_HIP(hipMemsetAsync(d_w, 0xFF, n_reads * 4, ctx->stream));
+    if (int rc = solidity_counts(table, ctx, d_bases, d_offsets, n_reads, total, min_count, max_count, d_n, d_s, d_w, n_parts, part))
+        return rc;
+    uint32_t *tmp = (uint32_t *)malloc(n_reads * 4 * n_arr);
+    if (!tmp) return kt::fail(KT_ERR_NOMEM, "kt_ctr_read_solidity: host alloc");
+    hipError_t e = hipMemcpyAsync(tmp, d_n, n_reads * 4 * n_arr, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) {
+        const uint32_t *tn = tmp, *ts = tmp + n_reads, *tw = tmp + 2 * n_reads;
+        for (uint64_t i = 0; i < n_reads; i++) {
+            n_kmers[i] += tn[i];
+            n_solid[i] += ts[i];
+            if (first_weak && tw[i] < first_weak[i]) first_weak[i] = tw[i];
+        }
+    }
+    free(tmp);
+    if (e != hipSuccess) return kt::fail(KT_ERR_HIP, std::string("kt_ctr_read_solidity: ") + hipGetErrorString(e));
     return KT_OK;
 }

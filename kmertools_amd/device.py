@@ -414,6 +414,31 @@ class Counter:
                      dtype, KT_MEM_HOST)
         return out
 
+    # -- filter: per-read k-mer solidity against this table ------------------------------------
+    def read_solidity(self, bases, offsets, n_reads, min_count, max_count, n_kmers, n_solid, first_weak=None,
+                      mem=KT_MEM_DEVICE, n_parts=1, part=0):
+        """combines into n_kmers (+), n_solid (+) and first_weak (min; may be None) the reads' k-mers of hash partition
+        `part` of n_parts, those with min_count <= count <= max_count and the start of the first other one - u32 arrays
+        of n_reads, initialised by the caller to 0 / 0 / 0xFFFFFFFF (kt_ctr_read_solidity)"""
+        check(_lib.lib().kt_ctr_read_solidity(self._h, _ptr(bases), _ptr(offsets), int(n_reads), int(min_count),
+                                              int(max_count), _ptr(n_kmers), _ptr(n_solid), _ptr(first_weak), mem,
+                                              int(n_parts), int(part)))
+        return n_kmers, n_solid, first_weak
+
+    def read_solidity_host(self, bases, offsets, min_count=2, max_count=None):
+        """-> (n_kmers, n_solid, first_weak) u32 arrays of the whole table (first_weak 0xFFFFFFFF: no weak k-mer)"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        nk = np.zeros(n, np.uint32)
+        ns = np.zeros(n, np.uint32)
+        fw = np.full(n, 0xFFFFFFFF, np.uint32)
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        if n:
+            self.read_solidity(bases if bases.size else np.zeros(1, np.uint8), offsets, n, min_count, hi, nk, ns, fw,
+                               KT_MEM_HOST)
+        return nk, ns, fw
+
     def spectrum(self, n_bins=10001, totals=False):
         """The table's abundance spectrum (jellyfish histo): hist[c] = distinct k-mers with exactly c occurrences for
         1 <= c < n_bins - 1, hist[n_bins - 1] = those with n_bins - 1 or more, hist[0] = 0.  totals=True: also
