@@ -231,6 +231,23 @@ int kt_ctr_export_stage_range(kt_ctr *ctr, uint32_t min_count, uint32_t max_coun
  * (jellyfish histo, kmc_tools histogram) */
 int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *totals, int mem);
 
+/* The comparison matrix of two tables of the same k (KAT comp / spectra-cn; with the totals, the Jaccard, containment
+ * and weighted Jaccard of the two k-mer sets).  Its cell [r * n_cols + c] counts the distinct canonical k-mers with
+ * min(count_a, n_rows - 1) == r and min(count_b, n_cols - 1) == c, where a count of 0 means the k-mer is absent from
+ * that table.  Results are ADDED into matrix (n_rows x n_cols u64, row-major); cell [0][0] is never touched, so the
+ * caller keeps 0 there.  totals (may be NULL) gets 6 u64 added, exact whatever the bin counts are:
+ *   distinct_a, distinct_b, shared (in both), occurrences_a, occurrences_b,
+ *   shared_min (sum over shared k-mers of min(count_a, count_b)).
+ * If a and b hold the same hash partition of n_parts (kt_ctr_add_reads_part), the sum over the partitions equals the
+ * call on the whole tables.  a == b is allowed (the diagonal: kt_ctr_spectrum of the table).  Neither table's content
+ * changes; b is probed, so a b that is densely packed or lives in its export target gets its probing image first, as in
+ * kt_ctr_lookup; a is read in whatever form it is in.  Empty tables add nothing.  mem says where matrix and totals live;
+ * KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the context's stream.  KT_ERR_ARG: a null table or matrix,
+ * different k, tables on different contexts, a table that is one shard of a sharded table (n_owners > 1: not
+ * supported), n_rows < 2, n_cols < 2, n_rows * n_cols > 2^24, a bad mem.  An overflowed table is KT_ERR_FULL as in
+ * kt_ctr_size. */
+int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n_rows, uint32_t n_cols, uint64_t *totals, int mem);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

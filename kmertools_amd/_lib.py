@@ -57,6 +57,7 @@ SYMBOLS = {
     "kt_ctr_export_fetch": (_i, [_vp, _u64, _u64, _vp, _vp]),
     "kt_ctr_export_stage_range": (_i, [_vp, _u32, _u32, C.POINTER(_u64)]),
     "kt_ctr_spectrum": (_i, [_vp, _vp, _u32, _vp, _i]),
+    "kt_ctr_compare": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _i]),
     "kt_cgr_points": (_i, [_vp, _vp, _vp, _u64, C.c_double, _vp, _vp, _i]),
     "kt_minimisers": (_i, [_vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _i]),
     "kt_cov_batch": (_i, [_vp, _vp, _vp, _u64, _u64, _u64, _i, _i, _vp, _i]),

@@ -1422,6 +1422,151 @@ std::string FilterComputer::filter() {
 }
 
 // ---------------------------------------------------------------------------------------------
+CompareComputer::CompareComputer(std::string in_a, std::string in_b, std::string out_dir, int ksize)
+    : in_a_(std::move(in_a)), in_b_(std::move(in_b)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
+
+CompareComputer::~CompareComputer() { release(); }
+
+void CompareComputer::release() {
+    if (ta_) kt_ctr_destroy(ta_);
+    if (tb_) kt_ctr_destroy(tb_);
+    ta_ = tb_ = nullptr;
+}
+
+// slots for the distinct k-mers of one input, as CountComputer::count sizes its table: an upper bound of the bases (a
+// plain file's size, half of it for FASTQ; the pre-pass for compressed input), at most the canonical k-mers of k <= 15,
+// 1.9 slots per possible key
+static std::string compare_want(const std::string &path, int k, uint64_t *want) {
+    uint64_t total = 0, n_seq = 0;
+    std::string err;
+    struct stat st;
+    const bool plain = !(path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) && stat(path.c_str(), &st) == 0 &&
+                       S_ISREG(st.st_mode);
+    if (plain) total = format_from_path(path) == SeqFormat::Fastq ? (uint64_t)st.st_size / 2 : (uint64_t)st.st_size;
+    else if (!SeqReader::seq_stats(path, n_seq, total, err)) return err;
+    uint64_t max_distinct = total;
+    if (k <= 15) {
+        const uint64_t n4k = 1ull << (2 * k);
+        const uint64_t canon = (k & 1) ? n4k / 2 : (n4k + (1ull << k)) / 2;
+        if (canon < max_distinct) max_distinct = canon;
+    }
+    *want = max_distinct + max_distinct / 10 * 9;
+    if (*want < 1024) *want = 1024;
+    return "";
+}
+
+std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_t *tot) const {
+    const uint32_t R = max_a_ + 1, C = max_b_ + 1;
+    std::string s;
+    s.reserve((size_t)R * C * 2);
+    char buf[24];
+    for (uint32_t r = 0; r < R; r++)
+        for (uint32_t c = 0; c < C; c++) {
+            const auto e = std::to_chars(buf, buf + sizeof buf, m[(size_t)r * C + c]);
+            s.append(buf, (size_t)(e.ptr - buf));
+            s += c + 1 < C ? '\t' : '\n';
+        }
+    const std::string mpath = out_dir_ + "/compare.matrix", spath = out_dir_ + "/compare.stats";
+    FILE *out = fopen(mpath.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + mpath;
+    bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + mpath;
+    // distinct_a, distinct_b, shared, occurrences_a, occurrences_b, shared_min; then the ratios (0 over a zero denominator)
+    static const char *names[6] = {"distinct_a", "distinct_b", "shared", "occurrences_a", "occurrences_b", "shared_min"};
+    s.clear();
+    for (int j = 0; j < 6; j++) s += std::string(names[j]) + '\t' + std::to_string(tot[j]) + '\n';
+    auto ratio = [&](const char *name, uint64_t num, uint64_t den) {
+        char b[FIXED6_BUF + 64];
+        snprintf(b, sizeof b, "%s\t%.6f\n", name, den ? (double)num / (double)den : 0.0);
+        s += b;
+    };
+    const uint64_t da = tot[0], db = tot[1], sh = tot[2], oa = tot[3], ob = tot[4], smin = tot[5];
+    ratio("jaccard", sh, da + db - sh);
+    ratio("containment_a", sh, da);
+    ratio("containment_b", sh, db);
+    ratio("weighted_jaccard", smin, oa + ob - smin);
+    out = fopen(spath.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + spath;
+    ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
+    return "";
+}
+
+std::string CompareComputer::compare() {
+    release();
+    Lap setup;
+    uint64_t want_a = 0, want_b = 0;
+    if (std::string e = compare_want(in_a_, ksize_, &want_a); !e.empty()) return e;
+    if (std::string e = compare_want(in_b_, ksize_, &want_b); !e.empty()) return e;
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
+    // both tables of a pass share the HBM next to the build's buffers (CountComputer::count's reserve); KT_CTR_MAX_SLOTS
+    // bounds each table (tests: force the out-of-core passes)
+    const uint64_t batch_bases = 256ull << 20;
+    uint64_t free_b = 0, total_b = 0, fit_both = want_a + want_b;
+    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
+        const uint64_t reserve = batch_bases * 20 + (1ull << 30);
+        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
+        fit_both = usable / 10 * 9 / 16;
+    }
+    if (fit_both < 2048) fit_both = 2048;
+    uint64_t fit_each = env_u64_host("KT_CTR_MAX_SLOTS", ~0ull);
+    if (fit_each < 1024) fit_each = 1024;
+    uint64_t p = (want_a + want_b + fit_both - 1) / fit_both;
+    p = std::max(p, (want_a + fit_each - 1) / fit_each);
+    p = std::max(p, (want_b + fit_each - 1) / fit_each);
+    passes_ = (uint32_t)std::max<uint64_t>(p, 1);
+    // a partition's share of the keys varies a little: 1 / passes + 5 sigma of room; more passes when the tables do not fit
+    uint64_t cap_a = 0, cap_b = 0;
+    for (;; passes_++) {
+        cap_a = passes_ == 1 ? want_a : want_a / passes_ + want_a / passes_ / 16 + 4096;
+        cap_b = passes_ == 1 ? want_b : want_b / passes_ + want_b / passes_ / 16 + 4096;
+        int rc = kt_ctr_create(dev_.ctx, ksize_, cap_a, &ta_);
+        if (rc == KT_OK) rc = kt_ctr_create(dev_.ctx, ksize_, cap_b, &tb_);
+        if (rc == KT_OK) break;
+        release();
+        if (rc != KT_ERR_NOMEM || passes_ >= 4096) return kt_last_error();
+    }
+    if (getenv("KT_CLI_TIMING")) {
+        uint64_t sa = cap_a, sb = cap_b;
+        (void)kt_ctr_capacity(ta_, &sa);
+        (void)kt_ctr_capacity(tb_, &sb);
+        fprintf(stderr, "[timing] compare setup: tables of %llu + %llu slots, %u pass(es) %.3f s\n", (unsigned long long)sa,
+                (unsigned long long)sb, passes_, setup());
+    }
+    const uint32_t R = max_a_ + 1, C = max_b_ + 1;
+    std::vector<uint64_t> m((size_t)R * C, 0);
+    uint64_t tot[6] = {0, 0, 0, 0, 0, 0};
+    PhaseTimer pt("compare");
+    SeqReader ra, rb;
+    if (!ra.open(in_a_, false)) return ra.error();
+    if (!rb.open(in_b_, false)) return rb.error();
+    Batch b;
+    for (uint32_t pass = 0; pass < passes_; pass++) {
+        Lap lap;
+        if (pass && (kt_ctr_clear(ta_) != KT_OK || kt_ctr_clear(tb_) != KT_OK)) return kt_last_error();
+        for (auto [reader, table] : {std::make_pair(&ra, ta_), std::make_pair(&rb, tb_)}) {
+            if (pass && !reader->rewind()) return reader->error();
+            for (;;) {
+                const bool more = reader->next_batch(b, cli_batch_bases(batch_bases), cli_batch_reads(1ull << 22));
+                pt.t[0] += lap();
+                if (b.n_reads() && !b.bases.empty())
+                    if (kt_ctr_add_reads_part(table, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST, passes_, pass) != KT_OK)
+                        return kt_last_error();
+                pt.t[1] += lap();
+                if (!more) break;
+            }
+            if (reader->failed()) return reader->error();
+        }
+        if (kt_ctr_compare(ta_, tb_, m.data(), R, C, tot, KT_MEM_HOST) != KT_OK) return kt_last_error();
+        pt.t[1] += lap();
+    }
+    Lap lap;
+    std::string e = write(m, tot);
+    pt.t[3] += lap();
+    return e;
+}
+
+// ---------------------------------------------------------------------------------------------
 // minimisers: one C-ABI call per batch; the capacity is a guess that is corrected on the first miss
 static std::string minimiser_batch(kt_ctx *ctx, Work &w, uint64_t wsize, int msize) {
     const uint64_t n = w.b.n_reads();

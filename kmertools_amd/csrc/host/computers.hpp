@@ -223,4 +223,34 @@ class FilterComputer {
     void emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const;
 };
 
+// `compare`: the comparison matrix of two inputs' k-mer tables (KAT comp / spectra-cn) and the similarity of their k-mer
+// sets (Jaccard, containment, weighted Jaccard).  Both tables live on one Device, sized from their inputs as CountComputer
+// sizes its table; when the two cannot share the HBM (or KT_CTR_MAX_SLOTS bounds a table) the inputs are counted in
+// `passes()` passes, pass p holding hash partition p of both (kt_ctr_add_reads_part), and every pass's kt_ctr_compare is
+// added into one matrix.  Writes {out_dir}/compare.matrix ((max_a + 1) lines of max_b + 1 tab-separated counts; the last
+// row and column: that count or more) and {out_dir}/compare.stats ("name\tvalue" lines).
+class CompareComputer {
+  public:
+    CompareComputer(std::string in_a, std::string in_b, std::string out_dir, int ksize);
+    ~CompareComputer();
+    CompareComputer(const CompareComputer &) = delete;
+    CompareComputer &operator=(const CompareComputer &) = delete;
+    void set_max_counts(uint32_t max_a, uint32_t max_b) { max_a_ = max_a, max_b_ = max_b; }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // (accepted; the tables live in HBM)
+    void set_device(int d) { dev_.index = d; }
+    std::string compare();  // "" or the error message
+    uint32_t passes() const { return passes_; }
+
+  private:
+    std::string in_a_, in_b_, out_dir_;
+    int ksize_, threads_ = 0;
+    uint32_t max_a_ = 1000, max_b_ = 100, passes_ = 1;
+    double memory_ceil_gb_ = 6.0;
+    Device dev_;
+    kt_ctr *ta_ = nullptr, *tb_ = nullptr;
+    void release();
+    std::string write(const std::vector<uint64_t> &m, const uint64_t *tot) const;
+};
+
 }  // namespace kthost

@@ -2,7 +2,7 @@
 // `ctr` flags (kmertools/src/args.rs:70-130, 208-236; dispatcher :239-368) and `cov`
 // (args.rs:132-172, :299-325).  clap conventions are kept: kebab-case long flags, the
 // auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.  `filter` (a k-mer read
-// filter, not in the reference) follows the same conventions.
+// filter, not in the reference) follows the same conventions, and so does `compare` (two inputs' k-mer tables side by side).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -129,6 +129,7 @@ const char *HELP_MAIN =
     "  min     Bin reads using minimisers\n"
     "  ctr     Count k-mers\n"
     "  filter  Drop or trim reads by the abundance of their k-mers\n"
+    "  compare Compare the k-mer counts of two inputs (matrix and set similarity)\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
 
@@ -464,6 +465,62 @@ int cmd_filter(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_COMPARE =
+    "Compare the k-mer counts of two inputs (matrix and set similarity)\n\n"
+    "Counts the canonical k-mers of both inputs and writes {output}/compare.matrix: line r (r = 0..max-a) holds max-b + 1\n"
+    "tab-separated numbers, the number of k-mers that occur r times in the input and c times in the alt input (0: absent;\n"
+    "the last line and the last column: that count or more; the first number of the first line is 0), and\n"
+    "{output}/compare.stats: distinct_a, distinct_b, shared, occurrences_a, occurrences_b, shared_min, jaccard,\n"
+    "containment_a, containment_b and weighted_jaccard, one \"name<TAB>value\" line each.\n\n"
+    "Usage: kmertools compare [OPTIONS] --input <INPUT> --alt-input <ALT_INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path (the rows)\n"
+    "  -a, --alt-input <ALT_INPUT>  Input file path to compare with (the columns)\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "      --max-a <N>              Highest count of the rows; the last row counts N or more [default: 1000]\n"
+    "      --max-b <N>              Highest count of the columns; the last column counts N or more [default: 100]\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted; the tables live in HBM: when both cannot\n"
+    "                               hold every distinct k-mer, the inputs are counted in several passes)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_compare(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},  {'a', "alt-input", true}, {'o', "output", true},
+                                     {'k', "k-size", true}, {0, "max-a", true},       {0, "max-b", true},
+                                     {'m', "memory", true}, {'t', "threads", true},   {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_COMPARE);
+    const std::string in = required_str(f, "input"), alt = required_str(f, "alt-input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work
+    const uint64_t max_a = ranged(f, "max-a", 1, (1u << 24) - 1, false, 1000);
+    const uint64_t max_b = ranged(f, "max-b", 1, (1u << 24) - 1, false, 100);
+    if ((max_a + 1) * (max_b + 1) > (1ull << 24))
+        usage_error("invalid values for '--max-a' and '--max-b': (" + std::to_string(max_a) + " + 1) x (" + std::to_string(max_b) +
+                    " + 1) cells is more than 16777216");
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    if (int rc = make_out_dir(out)) return rc;
+    for (const std::string &p : {in, alt}) {
+        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    CompareComputer cmp(in, alt, out, k);
+    cmp.set_max_counts((uint32_t)max_a, (uint32_t)max_b);
+    if (threads > 0) cmp.set_threads(threads);
+    cmp.set_max_memory((double)mem);
+    cmp.set_device(device);
+    if (std::string e = cmp.compare(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -589,5 +646,6 @@ int main(int argc, char **argv) {
     if (cmd == "cov") return cmd_cov(argc, argv, 2);
     if (cmd == "min") return cmd_min(argc, argv, 2);
     if (cmd == "filter") return cmd_filter(argc, argv, 2);
+    if (cmd == "compare") return cmd_compare(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

@@ -351,6 +351,223 @@ uint32_t spectrum_grid(const kt_ctx *ctx, uint64_t work_items, uint64_t entries)
     return (uint32_t)g;
 }
 
+// ---- the comparison matrix of two tables (kt_ctr_compare) ------------------------------------------------------------
+// spectrum_kernel's walk of table A, read-only, in whatever form A is in; for every entry (key, a) the key is probed in B
+// (B's probing image, B's geometry: lookup_kernel's probe) for its count b (0: absent), and cell (min(a, R - 1),
+// min(b, C - 1)) gets one.  The pass is bound by the random 16-byte reads into B: a lane first loads CMP_UNROLL entries of
+// A, then issues the B home-slot loads of all of them, and only then resolves them (a walk past the home slot is rare).
+// The matrix is skewed as the spectrum is - uniform reads put nearly everything into (1, 0) or (1, 1), reads sampled from
+// a genome into a spot around (coverage, coverage) or (coverage, 1) - so the cells are tallied in three tiers: rows 1..4 x
+// columns 0..1 in registers (an unrolled compare, reduced once per wave), a low corner of tile_rows x tile_cols (up to
+// CMP_LDS cells, at least 128 x 64 or the whole matrix) in LDS with no-return adds, the rest in 64-bit global atomics.
+// Every workgroup merges its non-zero LDS cells once, at the end; u32 tallies as in the spectrum (spectrum_grid bounds a
+// workgroup's share below 2^31).  Column 0 (B's k-mers absent from A) is not probed for: compare_row0_kernel takes it from
+// B's spectrum with the same saturation, minus this call's column sums over rows >= 1.
+#ifndef KT_CMP_UNROLL
+#define KT_CMP_UNROLL 8
+#endif
+constexpr uint32_t CMP_UNROLL = KT_CMP_UNROLL, CMP_LDS = 8192, CMP_REG = 8, CMP_TILE_COLS = 64;
+
+struct CmpArgs {
+    const Slot *b_slots;  // B's probing image
+    kttab::Geom bg;
+    uint64_t *cells;      // this call's n_rows x n_cols cells (zeroed; row 0 is left to compare_row0_kernel)
+    uint64_t *totals;     // distinct_a, occurrences_a, shared, shared_min
+    uint32_t n_rows, n_cols, tile_rows, tile_cols;
+};
+
+__device__ __forceinline__ uint4 cmp_home(const CmpArgs &c, uint64_t key) {
+    return *reinterpret_cast<const uint4 *>(c.b_slots + kttab::probe_of(key, c.bg).slot());
+}
+
+// B's count of `key` given its loaded home slot `v`; walks on round the key's range only on a collision
+__device__ __forceinline__ uint32_t cmp_resolve(const CmpArgs &c, uint4 v, uint64_t key) {
+    uint64_t kk = ((uint64_t)v.y << 32) | v.x;
+    if (kk == key) return v.z + 1u;
+    if (kk == KT_EMPTY_KEY) return 0u;
+    kttab::Probe p = kttab::probe_of(key, c.bg);
+    for (uint32_t probe = 1; probe < p.rs; probe++) {
+        p.next();
+        v = *reinterpret_cast<const uint4 *>(c.b_slots + p.slot());
+        kk = ((uint64_t)v.y << 32) | v.x;
+        if (kk == key) return v.z + 1u;
+        if (kk == KT_EMPTY_KEY) return 0u;
+    }
+    return 0u;
+}
+
+struct CmpTally {
+    uint32_t reg[CMP_REG] = {};  // cell (j / 2 + 1, j % 2)
+    uint32_t n = 0, shared = 0;
+    uint64_t occ = 0, smin = 0;
+    __device__ __forceinline__ void add(uint32_t ca, uint32_t cb, const CmpArgs &c, uint32_t *lds) {
+        n++;
+        occ += ca;
+        if (cb) {
+            shared++;
+            smin += ca < cb ? ca : cb;
+        }
+        const uint32_t r = ca < c.n_rows - 1u ? ca : c.n_rows - 1u;  // >= 1: an entry of A occurs at least once
+        const uint32_t col = cb < c.n_cols - 1u ? cb : c.n_cols - 1u;
+        const uint32_t id = r <= CMP_REG / 2 && col <= 1u ? (r - 1u) * 2u + col : CMP_REG;
+#pragma unroll
+        for (uint32_t j = 0; j < CMP_REG; j++) reg[j] += id == j;
+        if (id == CMP_REG) {
+            if (r < c.tile_rows && col < c.tile_cols) atomicAdd(&lds[r * c.tile_cols + col], 1u);  // (no-return ds_add)
+            else atomicAdd(reinterpret_cast<unsigned long long *>(c.cells + (uint64_t)r * c.n_cols + col), 1ull);
+        }
+    }
+};
+
+// FORM as in spectrum_kernel: SPEC_PROBE: `src` = A's slots [n); SPEC_DENSE: A's n ranges of RS slots, range r's
+// range_counts[r] keys from its start and counts (occurrences - 1) from byte 8 * RS on; SPEC_PAIRS: n keys at `src`, their
+// occurrences at `counts` (an export target's arrays)
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void compare_kernel(const void *__restrict__ src, const uint32_t *__restrict__ counts,
+                                                        uint64_t n, uint32_t RS, const uint32_t *__restrict__ range_counts,
+                                                        CmpArgs c) {
+    __shared__ uint32_t lds[CMP_LDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t tile = c.tile_rows * c.tile_cols;
+    for (uint32_t b = tid; b < tile; b += BLOCK) lds[b] = 0u;
+    ktd::lds_barrier();
+    CmpTally t;
+    const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+    if constexpr (FORM == SPEC_PROBE) {
+        const uint4 *slots = reinterpret_cast<const uint4 *>(src);
+        constexpr uint32_t TILE = BLOCK * CMP_UNROLL;
+        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
+            uint4 v[CMP_UNROLL], h[CMP_UNROLL];
+#pragma unroll
+            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
+                const uint64_t i = i0 + u * BLOCK + tid;
+                v[u] = i < n ? slots[i] : none;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
+                const uint64_t key = ((uint64_t)v[u].y << 32) | v[u].x;
+                h[u] = key != KT_EMPTY_KEY ? cmp_home(c, key) : none;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
+                const uint64_t key = ((uint64_t)v[u].y << 32) | v[u].x;
+                if (key != KT_EMPTY_KEY) t.add(v[u].z + 1u, cmp_resolve(c, h[u], key), c, lds);
+            }
+        }
+    } else if constexpr (FORM == SPEC_DENSE) {
+        // a wave per range: the range's keys and counts, coalesced, CMP_UNROLL entries per lane
+        const uint32_t wave = tid >> 6;
+        const uint64_t waves = (uint64_t)gridDim.x * (BLOCK / 64);
+        for (uint64_t r = (uint64_t)blockIdx.x * (BLOCK / 64) + wave; r < n; r += waves) {
+            const uint32_t D = range_counts[r];
+            const char *base = reinterpret_cast<const char *>(src) + r * RS * 16ull;
+            const uint64_t *keys = reinterpret_cast<const uint64_t *>(base);
+            const uint32_t *cnts = reinterpret_cast<const uint32_t *>(base + RS * 8ull);
+            for (uint32_t e0 = 0; e0 < D; e0 += 64u * CMP_UNROLL) {
+                uint64_t key[CMP_UNROLL];
+                uint32_t cnt[CMP_UNROLL];
+                uint4 h[CMP_UNROLL];
+#pragma unroll
+                for (uint32_t u = 0; u < CMP_UNROLL; u++) {
+                    const uint32_t e = e0 + u * 64u + lane;
+                    key[u] = e < D ? keys[e] : KT_EMPTY_KEY;
+                    cnt[u] = e < D ? cnts[e] + 1u : 0u;
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < CMP_UNROLL; u++) h[u] = key[u] != KT_EMPTY_KEY ? cmp_home(c, key[u]) : none;
+#pragma unroll
+                for (uint32_t u = 0; u < CMP_UNROLL; u++)
+                    if (key[u] != KT_EMPTY_KEY) t.add(cnt[u], cmp_resolve(c, h[u], key[u]), c, lds);
+            }
+        }
+    } else {
+        const uint64_t *keys = reinterpret_cast<const uint64_t *>(src);
+        constexpr uint32_t TILE = BLOCK * CMP_UNROLL;
+        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
+            uint64_t key[CMP_UNROLL];
+            uint32_t cnt[CMP_UNROLL];
+            uint4 h[CMP_UNROLL];
+#pragma unroll
+            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
+                const uint64_t i = i0 + u * BLOCK + tid;
+                key[u] = i < n ? keys[i] : KT_EMPTY_KEY;
+                cnt[u] = i < n ? counts[i] : 0u;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < CMP_UNROLL; u++) h[u] = key[u] != KT_EMPTY_KEY ? cmp_home(c, key[u]) : none;
+#pragma unroll
+            for (uint32_t u = 0; u < CMP_UNROLL; u++)
+                if (key[u] != KT_EMPTY_KEY) t.add(cnt[u], cmp_resolve(c, h[u], key[u]), c, lds);
+        }
+    }
+    // the register cells: one wave reduction each, lane 0 adds the wave's sums to the LDS cells (a non-zero register cell
+    // is a cell of the matrix, and rows <= 4, columns <= 1 of the matrix lie inside the tile)
+#pragma unroll
+    for (uint32_t j = 0; j < CMP_REG; j++) {
+        uint32_t s = t.reg[j];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        if (lane == 0 && s) atomicAdd(&lds[(j / 2u + 1u) * c.tile_cols + (j & 1u)], s);
+    }
+    {
+        uint64_t n_e = t.n, occ = t.occ, sh = t.shared, smin = t.smin;
+        for (int o = 32; o > 0; o >>= 1) {
+            n_e += __shfl_down(n_e, o, 64);
+            occ += __shfl_down(occ, o, 64);
+            sh += __shfl_down(sh, o, 64);
+            smin += __shfl_down(smin, o, 64);
+        }
+        if (lane == 0 && n_e) {
+            atomicAdd(reinterpret_cast<unsigned long long *>(c.totals), (unsigned long long)n_e);
+            atomicAdd(reinterpret_cast<unsigned long long *>(c.totals + 1), (unsigned long long)occ);
+            if (sh) {
+                atomicAdd(reinterpret_cast<unsigned long long *>(c.totals + 2), (unsigned long long)sh);
+                atomicAdd(reinterpret_cast<unsigned long long *>(c.totals + 3), (unsigned long long)smin);
+            }
+        }
+    }
+    ktd::lds_barrier();
+    for (uint32_t b = tid; b < tile; b += BLOCK)
+        if (const uint32_t v = lds[b])
+            atomicAdd(reinterpret_cast<unsigned long long *>(c.cells + (uint64_t)(b / c.tile_cols) * c.n_cols + b % c.tile_cols),
+                      (unsigned long long)v);
+}
+
+// this call's cells S, rows >= 1: their column sums into colsum, and (out != nullptr) S added into the caller's out.  A
+// thread per column of a block of BLOCK columns (blockIdx.y) over CMP_FIN_ROWS rows (blockIdx.x): coalesced row by row,
+// every cell read by one thread.
+constexpr uint32_t CMP_FIN_ROWS = 64;
+__global__ __launch_bounds__(BLOCK) void compare_colsum_kernel(const uint64_t *__restrict__ S, uint32_t n_rows, uint32_t n_cols,
+                                                               uint64_t *__restrict__ colsum, uint64_t *__restrict__ out) {
+    const uint32_t col = blockIdx.y * BLOCK + threadIdx.x;
+    if (col >= n_cols) return;
+    const uint32_t r0 = 1u + blockIdx.x * CMP_FIN_ROWS, r1 = r0 + CMP_FIN_ROWS < n_rows ? r0 + CMP_FIN_ROWS : n_rows;
+    uint64_t s = 0;
+    for (uint32_t r = r0; r < r1; r++) {
+        const uint64_t i = (uint64_t)r * n_cols + col, v = S[i];
+        s += v;
+        if (out && v) out[i] += v;
+    }
+    if (s) atomicAdd(reinterpret_cast<unsigned long long *>(colsum + col), (unsigned long long)s);
+}
+
+// row 0 of the matrix: row0[c] += specB[c] - colsum[c] for 1 <= c < n_cols (B's k-mers of column c that A does not hold;
+// [0][0] is not touched), and the six totals (totals_out may be null)
+__global__ __launch_bounds__(BLOCK) void compare_row0_kernel(const uint64_t *__restrict__ spec_b, const uint64_t *__restrict__ colsum,
+                                                             uint32_t n_cols, uint64_t *__restrict__ row0,
+                                                             const uint64_t *__restrict__ tot_a, const uint64_t *__restrict__ tot_b,
+                                                             uint64_t *__restrict__ totals_out) {
+    const uint64_t c = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= 1 && c < n_cols) row0[c] += spec_b[c] - colsum[c];
+    if (c == 0 && totals_out) {
+        totals_out[0] += tot_a[0];  // distinct_a
+        totals_out[1] += tot_b[0];  // distinct_b
+        totals_out[2] += tot_a[2];  // shared
+        totals_out[3] += tot_a[1];  // occurrences_a
+        totals_out[4] += tot_b[1];  // occurrences_b
+        totals_out[5] += tot_a[3];  // shared_min
+    }
+}
+
 // ---- routing (multi-GPU ownership) ------------------------------------------------------
 
 constexpr int MAX_OWNERS = 64;
@@ -715,6 +932,8 @@ int kt_ctr_reload_pairs(kt_ctr *ctr, const uint64_t *d_keys, const uint32_t *d_c
     return KT_OK;
 }
 
+static int launch_spectrum(kt_ctr *ctr, uint64_t n, uint64_t *d_hist, uint32_t n_bins, uint64_t *d_totals);
+
 extern "C" {
 
 int kt_ctr_capacity(kt_ctr *ctr, uint64_t *slots) {
@@ -896,6 +1115,25 @@ int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *tota
         d_totals = totals ? d_hist + n_bins : nullptr;
         KT_HIP(hipMemsetAsync(d_hist, 0, ((size_t)n_bins + 2) * 8, ctx->stream));
     }
+    if (int rc = launch_spectrum(ctr, n, d_hist, n_bins, d_totals)) return rc;
+    if (mem == KT_MEM_HOST) {
+        std::vector<uint64_t> h((size_t)n_bins + 2);
+        KT_HIP(hipMemcpyAsync(h.data(), d_hist, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint32_t b = 1; b < n_bins; b++) hist[b] += h[b];
+        if (totals) {
+            totals[0] += h[n_bins];
+            totals[1] += h[(size_t)n_bins + 1];
+        }
+    }
+    return KT_OK;
+}
+
+}  // extern "C"
+
+// the spectrum launch of a table of n > 0 entries, in the form it is in, into device arrays (kt_ctr_spectrum, kt_ctr_compare)
+static int launch_spectrum(kt_ctr *ctr, uint64_t n, uint64_t *d_hist, uint32_t n_bins, uint64_t *d_totals) {
+    kt_ctx *ctx = ctr->ctx;
     constexpr uint64_t TILE = (uint64_t)BLOCK * SPEC_UNROLL;
     if (ctr->dense && ctr->dense_ext) {
         const uint32_t head = (uint32_t)(((uintptr_t)ctr->xt_counts & 15u) / 4u);
@@ -914,18 +1152,73 @@ int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *tota
                            d_totals);
     }
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) {
-        std::vector<uint64_t> h((size_t)n_bins + 2);
-        KT_HIP(hipMemcpyAsync(h.data(), d_hist, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-        for (uint32_t b = 1; b < n_bins; b++) hist[b] += h[b];
-        if (totals) {
-            totals[0] += h[n_bins];
-            totals[1] += h[(size_t)n_bins + 1];
+    return KT_OK;
+}
+
+extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n_rows, uint32_t n_cols, uint64_t *totals, int mem) {
+    if (!a || !b || !matrix) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: null");
+    if (a->k != b->k) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: the tables have different k");
+    if (a->ctx != b->ctx) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: the tables are on different contexts");
+    if (a->n_owners > 1 || b->n_owners > 1)
+        return kt::fail(KT_ERR_ARG, "kt_ctr_compare: a table is one shard of a sharded table - shards are not supported");
+    if (n_rows < 2 || n_cols < 2) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: n_rows and n_cols must be >= 2");
+    if ((uint64_t)n_rows * n_cols > (1ull << 24)) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: n_rows * n_cols must be <= 2^24");
+    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: bad mem");
+    kt_ctx *ctx = a->ctx;
+    if (int rc = ctx->use()) return rc;
+    uint64_t n_a = 0, n_b = 0;
+    if (int rc = kt_ctr_size(a, &n_a)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    if (int rc = kt_ctr_size(b, &n_b)) return rc;
+    if (!n_a && !n_b) return KT_OK;
+    // B is probed: its probing image first.  A's form is read only after that - with a == b, or a B whose image was built
+    // from A's arrays, A is walked as it is now
+    if (int rc = table_ready(b)) return rc;
+    // scratch (u64): this call's cells | B's spectrum | column sums | A's totals (4) | B's totals (2) | the six totals
+    const uint64_t cells = (uint64_t)n_rows * n_cols, words = cells + 2ull * n_cols + 12;
+    if (int rc = ctx->s_aux1.reserve(words * 8)) return rc;
+    uint64_t *S = (uint64_t *)ctx->s_aux1.p, *spec_b = S + cells, *colsum = spec_b + n_cols, *tot_a = colsum + n_cols,
+             *tot_b = tot_a + 4, *tot6 = tot_b + 2;
+    KT_HIP(hipMemsetAsync(S, 0, words * 8, ctx->stream));
+    if (n_a) {
+        const uint32_t tile_cols = n_cols < CMP_TILE_COLS ? n_cols : CMP_TILE_COLS;
+        const uint32_t tile_rows = n_rows < CMP_LDS / tile_cols ? n_rows : CMP_LDS / tile_cols;
+        const CmpArgs c{(const Slot *)b->slots, ktl::geom_of(b), S, tot_a, n_rows, n_cols, tile_rows, tile_cols};
+        constexpr uint64_t TILE = (uint64_t)BLOCK * CMP_UNROLL;
+        if (a->dense && a->dense_ext) {
+            hipLaunchKernelGGL(compare_kernel<SPEC_PAIRS>, dim3(spectrum_grid(ctx, (n_a + TILE - 1) / TILE, n_a)), dim3(BLOCK), 0,
+                               ctx->stream, (const void *)a->xt_keys, (const uint32_t *)a->xt_counts, n_a, 0u, nullptr, c);
+        } else if (a->dense) {
+            const uint32_t RS = a->m8 << (kttab::LOG2_RANGE - 3);
+            const uint64_t n_ranges = a->cap / RS;
+            hipLaunchKernelGGL(compare_kernel<SPEC_DENSE>, dim3(spectrum_grid(ctx, (n_ranges + 3) / 4, n_a)), dim3(BLOCK), 0,
+                               ctx->stream, (const void *)a->slots, nullptr, n_ranges, RS, a->range_counts, c);
+        } else {
+            hipLaunchKernelGGL(compare_kernel<SPEC_PROBE>, dim3(spectrum_grid(ctx, (a->cap + TILE - 1) / TILE, a->cap)),
+                               dim3(BLOCK), 0, ctx->stream, (const void *)a->slots, nullptr, a->cap, 0u, nullptr, c);
         }
+        KT_HIP(hipGetLastError());
+    }
+    if (n_b)
+        if (int rc = launch_spectrum(b, n_b, spec_b, n_cols, tot_b)) return rc;
+    const bool host = mem == KT_MEM_HOST;
+    hipLaunchKernelGGL(compare_colsum_kernel, dim3((n_rows - 1 + CMP_FIN_ROWS - 1) / CMP_FIN_ROWS, (n_cols + BLOCK - 1) / BLOCK),
+                       dim3(BLOCK), 0, ctx->stream, (const uint64_t *)S, n_rows, n_cols, colsum, host ? nullptr : matrix);
+    hipLaunchKernelGGL(compare_row0_kernel, dim3((n_cols + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream,
+                       (const uint64_t *)spec_b, (const uint64_t *)colsum, n_cols, host ? S : matrix, (const uint64_t *)tot_a,
+                       (const uint64_t *)tot_b, host ? tot6 : totals);
+    KT_HIP(hipGetLastError());
+    if (host) {
+        std::vector<uint64_t> h(words);
+        KT_HIP(hipMemcpyAsync(h.data(), S, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint64_t i = 1; i < cells; i++) matrix[i] += h[i];
+        if (totals)
+            for (int j = 0; j < 6; j++) totals[j] += h[cells + 2ull * n_cols + 6 + j];
     }
     return KT_OK;
 }
+
+extern "C" {
 
 int kt_ctr_export_fetch(kt_ctr *ctr, uint64_t first, uint64_t count, uint64_t *keys_host, uint32_t *counts_host) {
     if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_export_fetch: null");

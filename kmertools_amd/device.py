@@ -453,6 +453,24 @@ class Counter:
         check(_lib.lib().kt_ctr_spectrum(self._h, _ptr(hist), int(n_bins), _ptr(totals), mem))
         return hist
 
+    COMPARE_TOTALS = ("distinct_a", "distinct_b", "shared", "occurrences_a", "occurrences_b", "shared_min")
+
+    def compare(self, other, n_rows=1001, n_cols=101, totals=False):
+        """The comparison matrix of this table (rows) and `other` (columns), same k (KAT comp / spectra-cn): m[r, c] =
+        distinct k-mers with min(count here, n_rows - 1) == r and min(count in other, n_cols - 1) == c, a count of 0 for
+        an absent k-mer; m[0, 0] = 0.  totals=True: also a dict of the exact distinct_a, distinct_b, shared,
+        occurrences_a, occurrences_b and shared_min (kt_ctr_compare)."""
+        m = np.zeros((int(n_rows), int(n_cols)), np.uint64)
+        tot = np.zeros(6, np.uint64)
+        self.compare_into(other, m, n_rows, n_cols, tot if totals else None, KT_MEM_HOST)
+        return (m, dict(zip(self.COMPARE_TOTALS, (int(v) for v in tot)))) if totals else m
+
+    def compare_into(self, other, matrix, n_rows, n_cols, totals=None, mem=KT_MEM_DEVICE):
+        """adds the comparison matrix into `matrix` (n_rows x n_cols u64) and the six totals into `totals` (6 u64, or
+        None)"""
+        check(_lib.lib().kt_ctr_compare(self._h, other._h, _ptr(matrix), int(n_rows), int(n_cols), _ptr(totals), mem))
+        return matrix
+
     def export_stage_range(self, min_count=1, max_count=None):
         """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
         n = C.c_uint64()
