@@ -339,6 +339,34 @@ int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const uint64_t *of
                          uint32_t min_count, uint32_t max_count, uint32_t *n_kmers, uint32_t *n_solid,
                          uint32_t *first_weak, int mem, uint32_t n_parts, uint32_t part);
 
+/* Per-position k-mer counts against the table (`kmertools profile`, the coverage track of a sequence).  `profile` has
+ * offsets[n_reads] u32 entries, indexed by the global base index g (as the xy of the CGR points call is).  Every valid window that
+ * STARTS at base g (inside one read, no non-ACGT byte - as for every other k-mer walk here) and whose canonical k-mer
+ * belongs to hash partition `part` of n_parts gets profile[g] = min(count, 0xFFFFFFFE); a k-mer absent from the table
+ * has count 0.  Every other entry is NOT WRITTEN: the last k-1 positions of a read, windows over an N, reads shorter
+ * than k, k-mers of other partitions.  The caller fills the array with KT_NO_KMER once; after parts 0..n_parts-1 (the
+ * tables of an out-of-core count) it is the whole table's answer.  There is no read-length limit: positions are global.
+ * `mem` says where bases, offsets and profile live; KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the
+ * context's stream.
+ * KT_ERR_ARG: part >= n_parts, a bad mem, a null buffer with n_reads > 0, or a table that is one shard of a sharded
+ * table (as for the read solidity call). */
+#define KT_NO_KMER 0xFFFFFFFFu
+int kt_ctr_profile(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *profile,
+                   int mem, uint32_t n_parts, uint32_t part);
+
+/* Per-read statistics of such a profile (any u32 array of offsets[n_reads] entries: no table, no k).  For read i, over
+ * its entries that are not KT_NO_KMER:
+ *   n_kmers[i]   = how many there are,            n_present[i] = those with count >= 1,
+ *   min_count[i] / max_count[i] = the least / greatest,   sum[i] = their exact sum (u64),
+ *   median[i]    = element n_kmers / 2 (0-based) of them sorted ascending - the upper median of an even number, the
+ *                  convention of khmer's get_median_count.
+ * A read with no k-mer gets 0 in every output.  Any output pointer may be NULL (its work is then skipped); the others
+ * are overwritten, not accumulated.  `mem` says where all the arrays live; KT_MEM_HOST synchronises.
+ * KT_ERR_ARG: a bad mem, a null input with n_reads > 0, a read of 2^32 bases or more. */
+int kt_profile_stats(kt_ctx *ctx, const uint32_t *profile, const uint64_t *offsets, uint64_t n_reads, uint32_t *n_kmers,
+                     uint32_t *n_present, uint32_t *min_count, uint32_t *median, uint32_t *max_count, uint64_t *sum,
+                     int mem);
+
 /* Multi-GPU routing step (the reference's `min_mer % n_parts` partitioning,
  * counter/src/lib.rs:127, re-expressed as hash-prefix ownership):
  * writes every canonical k-mer of the reads into keys_out grouped by owner

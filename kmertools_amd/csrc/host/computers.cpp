@@ -1422,6 +1422,176 @@ std::string FilterComputer::filter() {
 }
 
 // ---------------------------------------------------------------------------------------------
+ProfileComputer::ProfileComputer(std::string in_path, std::string out_dir, int ksize)
+    : in_path_(in_path), in_path_kmer_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
+
+ProfileComputer::~ProfileComputer() { delete ctr_; }
+
+// one pass of an out-of-core table is complete: the positions whose k-mers belong to this hash partition
+std::string ProfileComputer::profile_pass(uint32_t pass, uint32_t passes, kt_ctr *table) {
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    const double ceil_bytes = memory_ceil_gb_ * (double)(1ull << 30);
+    Batch b;
+    uint64_t at = 0, base = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20));
+        const uint64_t n = b.n_reads();
+        if (n) {
+            const uint64_t total = b.offsets[n];
+            if (pass == 0) {
+                if ((double)(base + total) * 4.0 > ceil_bytes) {
+                    char msg[256];
+                    snprintf(msg, sizeof msg,
+                             "profile: the table takes %u passes, and the per-base counts of the input kept across them (4 bytes "
+                             "per base, more than %.1f GB) do not fit the memory ceiling of %.0f GB: raise -m or split the input",
+                             passes, (double)(base + total) * 4.0 / (double)(1ull << 30), memory_ceil_gb_);
+                    return msg;
+                }
+                acc_.resize(base + total, KT_NO_KMER);
+            } else if (base + total > acc_.size()) {
+                return "profile: the input changed between the passes";
+            }
+            if (total && kt_ctr_profile(table, bases_ptr(b), b.offsets.data(), n, acc_.data() + base, KT_MEM_HOST, passes, pass) != KT_OK)
+                return kt_last_error();
+            at += n;
+            base += total;
+        }
+        if (!more) break;
+    }
+    if (reader.failed()) return reader.error();
+    if (pass && (at != acc_reads_ || base != acc_.size())) return "profile: the input changed between the passes";
+    acc_reads_ = at;
+    return "";
+}
+
+static void append_uint(std::string &out, uint64_t v) {
+    char buf[24];
+    const auto e = std::to_chars(buf, buf + sizeof buf, v);
+    out.append(buf, (size_t)(e.ptr - buf));
+}
+
+// a record's name: its header up to the first white space
+static void append_name(std::string &out, const std::string &header) {
+    size_t e = 0;
+    while (e < header.size() && !isspace((unsigned char)header[e])) e++;
+    out.append(header, 0, e);
+}
+
+std::string ProfileComputer::profile() {
+    delete ctr_;
+    acc_.clear();
+    acc_.shrink_to_fit();
+    acc_reads_ = 0;
+    ctr_ = new CountComputer(in_path_kmer_, ".", ksize_);
+    ctr_->set_threads(threads_);
+    ctr_->set_max_memory(memory_ceil_gb_);
+    ctr_->set_device(device_);
+    ctr_->set_histo(0, true);  // no kmers.histo and no kmers.counts: the table is only looked up
+    ctr_->set_pass_hook([this](uint32_t pass, uint32_t passes, kt_ctr *t) { return profile_pass(pass, passes, t); });
+    if (std::string e = ctr_->count(); !e.empty()) return e;
+    const bool resident = ctr_->passes() == 1;  // else: the positions were filled pass by pass (profile_pass)
+    if (resident && !ctr_->table()) return "profile: no table";
+    kt_ctx *ctx = ctr_->context();
+    if (!ctx) return "profile: no device context";
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    const std::string spath = out_dir_ + "/profile.stats", cpath = out_dir_ + "/profile.counts";
+    FILE *fs = fopen(spath.c_str(), "wb");
+    if (!fs) return "Unable to write to file: " + spath;
+    FILE *fc = positions_ ? fopen(cpath.c_str(), "wb") : nullptr;
+    if (positions_ && !fc) {
+        fclose(fs);
+        return "Unable to write to file: " + cpath;
+    }
+    PhaseTimer pt("profile");
+    Lap lap;
+    Batch b;
+    std::string text = "#name\tlength\tkmers\tpresent\tmin\tmedian\tmean\tmax\n", err;
+    std::vector<std::string> pieces;
+    std::vector<uint32_t> prof, st;
+    std::vector<uint64_t> sum;
+    uint64_t at = 0, base = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
+        pt.t[0] += lap();
+        const uint64_t n = b.n_reads();
+        if (n) {
+            const uint64_t total = b.offsets[n];
+            const uint32_t *p;
+            if (resident) {
+                prof.assign(total, KT_NO_KMER);
+                if (total && kt_ctr_profile(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), KT_MEM_HOST, 1, 0) != KT_OK) {
+                    err = kt_last_error();
+                    break;
+                }
+                p = prof.data();
+            } else {
+                if (at + n > acc_reads_ || base + total > acc_.size()) {
+                    err = "profile: the input changed between the passes";
+                    break;
+                }
+                p = acc_.data() + base;
+            }
+            st.resize(n * 5);
+            sum.resize(n);
+            uint32_t *nk = st.data(), *np = nk + n, *mn = np + n, *md = mn + n, *mx = md + n;
+            if (kt_profile_stats(ctx, p, b.offsets.data(), n, nk, np, mn, md, mx, sum.data(), KT_MEM_HOST) != KT_OK) {
+                err = kt_last_error();
+                break;
+            }
+            pt.t[1] += lap();
+            for (uint64_t i = 0; i < n; i++) {
+                append_name(text, b.headers[i]);
+                text += '\t';
+                append_uint(text, b.offsets[i + 1] - b.offsets[i]);
+                for (const uint32_t *col : {nk, np, mn, md}) {
+                    text += '\t';
+                    append_uint(text, col[i]);
+                }
+                text += '\t';
+                append_fixed6(text, (double)sum[i] / (double)(nk[i] ? nk[i] : 1u));
+                text += '\t';
+                append_uint(text, mx[i]);
+                text += '\n';
+            }
+            if (fc)
+                format_rows(n, threads_, 512, pieces, [&](uint64_t i, std::string &s) {
+                    s += '>';
+                    append_name(s, b.headers[i]);
+                    s += '\n';
+                    for (uint64_t g = b.offsets[i]; g < b.offsets[i + 1]; g++) {
+                        if (g != b.offsets[i]) s += ' ';
+                        if (p[g] == KT_NO_KMER) s += "-1";
+                        else append_uint(s, p[g]);
+                    }
+                    s += '\n';
+                });
+            pt.t[2] += lap();
+            bool ok = fwrite(text.data(), 1, text.size(), fs) == text.size();
+            text.clear();
+            if (fc)
+                for (const std::string &piece : pieces) ok = ok && fwrite(piece.data(), 1, piece.size(), fc) == piece.size();
+            if (!ok) {
+                err = "Unable to write to directory: " + out_dir_;
+                break;
+            }
+            pt.t[3] += lap();
+            at += n;
+            base += total;
+        }
+        if (!more) break;
+    }
+    if (err.empty() && !text.empty() && fwrite(text.data(), 1, text.size(), fs) != text.size())  // (an input without records: the header line)
+        err = "Unable to write to file: " + spath;
+    if (err.empty() && reader.failed()) err = reader.error();
+    if (err.empty() && !resident && (at != acc_reads_ || base != acc_.size())) err = "profile: the input changed between the passes";
+    if (fclose(fs) != 0 && err.empty()) err = "Unable to write to file: " + spath;
+    if (fc && fclose(fc) != 0 && err.empty()) err = "Unable to write to file: " + cpath;
+    return err;
+}
+
+// ---------------------------------------------------------------------------------------------
 CompareComputer::CompareComputer(std::string in_a, std::string in_b, std::string out_dir, int ksize)
     : in_a_(std::move(in_a)), in_b_(std::move(in_b)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
 

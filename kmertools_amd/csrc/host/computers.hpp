@@ -223,6 +223,40 @@ class FilterComputer {
     void emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const;
 };
 
+// `profile`: how often every position of the input's sequences occurs in a counted sample (KAT sect, jellyfish query -s)
+// and each sequence's k-mers, present k-mers, min / median / mean / max count (the median: element n / 2 of the sorted
+// counts, khmer's get_median_count).  The table is counted from kmer_path (default: the input) as by CountComputer; every
+// batch's positions are then looked up (kt_ctr_profile) and reduced per record (kt_profile_stats).  Out of core the
+// per-base array of the WHOLE input (4 bytes per base) is kept on the host and filled pass by pass - a median cannot be
+// combined over hash partitions, the array can -, and the statistics are taken after the last pass; an array larger than
+// the memory ceiling (-m) is refused.  Writes {out_dir}/profile.stats (a header line, then per record
+// name, length, kmers, present, min, median, mean, max, tab-separated) and with positions {out_dir}/profile.counts
+// (per record ">name" and one line of `length` space-separated counts, -1 where no k-mer starts).
+class ProfileComputer {
+  public:
+    ProfileComputer(std::string in_path, std::string out_dir, int ksize);
+    ~ProfileComputer();
+    ProfileComputer(const ProfileComputer &) = delete;
+    ProfileComputer &operator=(const ProfileComputer &) = delete;
+    void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    void set_positions(bool p) { positions_ = p; }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }
+    void set_device(int d) { device_ = d; }
+    std::string profile();  // "" or the error message
+
+  private:
+    std::string in_path_, in_path_kmer_, out_dir_;
+    int ksize_, threads_ = 0, device_ = 0;
+    double memory_ceil_gb_ = 6.0;
+    bool positions_ = false;
+    CountComputer *ctr_ = nullptr;
+    // out of core: the whole input's per-base counts, filled over the passes as each pass's table is complete
+    std::vector<uint32_t> acc_;
+    uint64_t acc_reads_ = 0;
+    std::string profile_pass(uint32_t pass, uint32_t passes, kt_ctr *table);
+};
+
 // `compare`: the comparison matrix of two inputs' k-mer tables (KAT comp / spectra-cn) and the similarity of their k-mer
 // sets (Jaccard, containment, weighted Jaccard).  Both tables live on one Device, sized from their inputs as CountComputer
 // sizes its table; when the two cannot share the HBM (or KT_CTR_MAX_SLOTS bounds a table) the inputs are counted in

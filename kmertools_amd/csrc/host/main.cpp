@@ -2,7 +2,8 @@
 // `ctr` flags (kmertools/src/args.rs:70-130, 208-236; dispatcher :239-368) and `cov`
 // (args.rs:132-172, :299-325).  clap conventions are kept: kebab-case long flags, the
 // auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.  `filter` (a k-mer read
-// filter, not in the reference) follows the same conventions, and so does `compare` (two inputs' k-mer tables side by side).
+// filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
+// and `profile` (per-position k-mer counts and per-sequence medians).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -130,6 +131,7 @@ const char *HELP_MAIN =
     "  ctr     Count k-mers\n"
     "  filter  Drop or trim reads by the abundance of their k-mers\n"
     "  compare Compare the k-mer counts of two inputs (matrix and set similarity)\n"
+    "  profile Per-position k-mer counts and per-sequence min / median / mean / max\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
 
@@ -521,6 +523,62 @@ int cmd_compare(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_PROFILE =
+    "Per-position k-mer counts and per-sequence min / median / mean / max\n\n"
+    "Counts the canonical k-mers of --alt-input (default: the input) and looks up the k-mer that starts at every base of\n"
+    "every input record.  Writes {output}/profile.stats: a header line, then one line per record in input order with its\n"
+    "name (the header up to the first white space), length, k-mers, k-mers present in the table, min, median, mean and max\n"
+    "count, tab-separated; the median is element n/2 of the n sorted counts (the upper one of an even number), the mean\n"
+    "has six decimals, a record without a k-mer has zeros.  With --positions also {output}/profile.counts: per record\n"
+    "\">name\" and one line of `length` space-separated counts, -1 where no k-mer starts (the last k-1 bases, windows over\n"
+    "a non-ACGT base).  When the table does not fit the device memory it is counted in several passes; the per-base counts\n"
+    "of the whole input (4 bytes per base) are then kept in host memory across the passes and the statistics are taken\n"
+    "after the last one - refused when that array is larger than --memory.\n\n"
+    "Usage: kmertools profile [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path (sequences to profile)\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting (1..31)\n"
+    "  -a, --alt-input <ALT_INPUT>  Input file path, for k-mer counting [default: the input]\n"
+    "      --positions              Also write profile.counts, the count at every base\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (the table lives in HBM; bounds the per-base counts\n"
+    "                               kept across the passes of an out-of-core count)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_profile(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},  {'k', "k-size", true},
+                                     {'a', "alt-input", true}, {0, "positions", false}, {'m', "memory", true},
+                                     {'t', "threads", true},   {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_PROFILE);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 1, 31, true, 0);
+    // everything is checked before any device work and before the output directory is made
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : {in, kin}) {
+        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    ProfileComputer prof(in, out, k);
+    if (threads > 0) prof.set_threads(threads);
+    prof.set_kmer_path(kin);
+    prof.set_positions(f.count("positions") != 0);
+    prof.set_max_memory((double)mem);
+    prof.set_device(device);
+    if (std::string e = prof.profile(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -647,5 +705,6 @@ int main(int argc, char **argv) {
     if (cmd == "min") return cmd_min(argc, argv, 2);
     if (cmd == "filter") return cmd_filter(argc, argv, 2);
     if (cmd == "compare") return cmd_compare(argc, argv, 2);
+    if (cmd == "profile") return cmd_profile(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

@@ -14,6 +14,8 @@
 // larger than the LDS budget) add to global memory directly.
 //
 // The read filter's kt_ctr_read_solidity walks and probes the same way and keeps three numbers per read (solidity_kernel).
+// kt_ctr_profile walks and probes the same way again and keeps the count itself, one u32 per window start (profile_kernel);
+// what is made of those per read - the median among them - is kt_profile.hip's.
 #include "kt_internal.hpp"
 #include "kt_launch.hpp"
 #include "kt_segment.hpp"
@@ -306,6 +308,71 @@ __global__ __launch_bounds__(BLOCK) void long_read_kernel(const uint64_t *__rest
         if (offsets[i + 1] - offsets[i] >= (1ull << 32)) atomicOr(flag, 1u);
 }
 
+// ---- per-position k-mer counts (kt_ctr_profile) --------------------------------------------------------------------
+// solidity_kernel's walk and probes with the simplest sink there is: the count of the window that starts at global base s
+// goes to profile[s] - no read lookup, no LDS image, nothing combined.  Only the valid windows of this hash partition are
+// stored (the caller's fill stays everywhere else), so the thread's 32 consecutive entries go out as they are resolved: four
+// at a time as one 16-byte store where all four are written and the array is 16-byte aligned, one by one otherwise.
+struct ProfileArgs {
+    const Slot *slots;
+    kttab::Geom g;
+    uint32_t *profile;       // offsets[n_reads] entries, indexed by global base index
+    uint32_t n_parts, part;  // only the k-mers of hash partition `part` are written
+};
+
+__global__ __launch_bounds__(BLOCK) void profile_kernel(SegArgs a, ProfileArgs c) {
+    __shared__ SegShared sm;
+    const uint32_t tid = threadIdx.x;
+    const bool aligned = ((uintptr_t)c.profile & 15u) == 0;
+
+    for (uint64_t g = blockIdx.x; g < a.n_seg; g += gridDim.x) {
+        ktseg::stage_segment(a, g, sm);
+        ktseg::Window w(sm, tid, a.k);
+        uint32_t ok = 0;
+        for (uint32_t j = 0; j < ktseg::PER_THREAD; j++) ok |= (w.ok(j) ? 1u : 0u) << j;
+        if (ok) {
+            // (a valid window lies inside the batch, so every entry written is below offsets[n_reads])
+            uint32_t *dst = c.profile + g * ktseg::SEG + (uint64_t)ktseg::PER_THREAD * tid;
+#pragma unroll 1
+            for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
+                uint64_t key[GROUP];
+                uint4 v[GROUP];
+#pragma unroll
+                for (uint32_t u = 0; u < GROUP; u++) {
+                    key[u] = w.f < w.r ? w.f : w.r;
+                    w.step();
+                    v[u] = load_slot(c.slots, kttab::probe_of(key[u], c.g).slot());
+                }
+                uint32_t cnt[GROUP];
+                uint32_t wr = (ok >> jj) & ((1u << GROUP) - 1u);
+#pragma unroll
+                for (uint32_t u = 0; u < GROUP; u++) {
+                    cnt[u] = 0;
+                    if (!((wr >> u) & 1u)) continue;
+                    if (c.n_parts > 1 && ktd::owner_of(key[u], c.n_parts) != c.part) {
+                        wr &= ~(1u << u);
+                        continue;
+                    }
+                    const uint32_t n = resolve_count(c.slots, c.g, v[u], key[u]);
+                    cnt[u] = n < KT_NO_KMER ? n : KT_NO_KMER - 1u;  // (the sentinel is no count)
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < GROUP; q += 4) {
+                    const uint32_t m = (wr >> q) & 15u;
+                    if (m == 15u && aligned) {
+                        *reinterpret_cast<uint4 *>(dst + jj + q) = make_uint4(cnt[q], cnt[q + 1], cnt[q + 2], cnt[q + 3]);
+                    } else {
+#pragma unroll
+                        for (uint32_t u = 0; u < 4; u++)
+                            if ((m >> u) & 1u) dst[jj + q + u] = cnt[q + u];
+                    }
+                }
+            }
+        }
+        __syncthreads();  // sm is restaged by the next segment
+    }
+}
+
 // one thread per read: total = sum of the row, out = count / max(1, total) (:180-182)
 template <class T>
 __global__ __launch_bounds__(BLOCK) void cov_finalize_kernel(const uint32_t *__restrict__ counts, uint64_t n_reads,
@@ -329,6 +396,26 @@ __global__ __launch_bounds__(BLOCK) void cov_finalize_kernel(const uint32_t *__r
 }  // namespace
 
 using namespace ktl;
+
+// *too_long = a read of the batch holds 2^32 bases or more (a device read-back for KT_MEM_DEVICE; uses ctx scratch s_aux2)
+int ktl::has_read_of_2_32(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int mem, bool *too_long) {
+    *too_long = false;
+    if (total < (1ull << 32)) return KT_OK;  // (below that no read can be this long)
+    if (mem == KT_MEM_HOST) {
+        for (uint64_t i = 0; i < n_reads && !*too_long; i++) *too_long = offsets[i + 1] - offsets[i] >= (1ull << 32);
+        return KT_OK;
+    }
+    if (int rc = ctx->s_aux2.reserve(4)) return rc;
+    uint32_t *d_flag = (uint32_t *)ctx->s_aux2.p, flag = 0;
+    KT_HIP(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(long_read_kernel, dim3(grid_for(ctx, (n_reads + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
+                       offsets, n_reads, d_flag);
+    KT_HIP(hipGetLastError());
+    KT_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KT_HIP(hipStreamSynchronize(ctx->stream));
+    *too_long = flag != 0;
+    return KT_OK;
+}
 
 // the lookup pass: u32 bin counts of the reads' k-mers (those of hash partition `part` of n_parts) into d_counts
 static int cov_counts(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
@@ -498,23 +585,9 @@ extern "C" int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const u
     uint64_t total = 0;
     if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
     if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null bases");
-    if (total >= (1ull << 32)) {  // (below that no read can be this long)
-        bool too_long = false;
-        if (mem == KT_MEM_HOST) {
-            for (uint64_t i = 0; i < n_reads && !too_long; i++) too_long = offsets[i + 1] - offsets[i] >= (1ull << 32);
-        } else {
-            if (int rc = ctx->s_aux2.reserve(4)) return rc;
-            uint32_t *d_flag = (uint32_t *)ctx->s_aux2.p, flag = 0;
-            KT_HIP(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-            hipLaunchKernelGGL(long_read_kernel, dim3(grid_for(ctx, (n_reads + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
-                               offsets, n_reads, d_flag);
-            KT_HIP(hipGetLastError());
-            KT_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-            KT_HIP(hipStreamSynchronize(ctx->stream));
-            too_long = flag != 0;
-        }
-        if (too_long) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: a read of 2^32 bases or more (positions are u32)");
-    }
+    bool too_long = false;
+    if (int rc = ktl::has_read_of_2_32(ctx, offsets, n_reads, total, mem, &too_long)) return rc;
+    if (too_long) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: a read of 2^32 bases or more (positions are u32)");
     if (int rc = table_ready(table)) return rc;
     if (mem == KT_MEM_DEVICE)
         return solidity_counts(table, ctx, bases, offsets, n_reads, total, min_count, max_count, n_kmers, n_solid, first_weak,
@@ -545,5 +618,43 @@ extern "C" int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const u
     }
     free(tmp);
     if (e != hipSuccess) return kt::fail(KT_ERR_HIP, std::string("kt_ctr_read_solidity: ") + hipGetErrorString(e));
+    return KT_OK;
+}
+
+extern "C" int kt_ctr_profile(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *profile,
+                              int mem, uint32_t n_parts, uint32_t part) {
+    if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: null table");
+    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: need part < n_parts");
+    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: bad mem");
+    if (table->n_owners > 1)
+        return kt::fail(KT_ERR_ARG, "kt_ctr_profile: the table is one shard of a sharded table - shards are not supported "
+                                    "(a shard cannot tell a k-mer absent here from one absent everywhere)");
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !profile) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: null buffer");
+    kt_ctx *ctx = table->ctx;
+    if (int rc = ctx->use()) return rc;
+    uint64_t total = 0;
+    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
+    if (!total) return KT_OK;
+    if (!bases) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: null bases");
+    if (int rc = table_ready(table)) return rc;
+    const uint8_t *d_bases = bases;
+    const uint64_t *d_offsets = offsets;
+    uint32_t *d_profile = profile;
+    if (mem == KT_MEM_HOST) {  // the caller's entries go up and come back: what this part does not write stays as it was
+        if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
+        if (int rc = ctx->s_out.reserve(total * 4)) return rc;
+        d_profile = (uint32_t *)ctx->s_out.p;
+        KT_HIP(hipMemcpyAsync(d_profile, profile, total * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    SegArgs a;
+    if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
+    ProfileArgs c{(const Slot *)table->slots, ktl::geom_of(table), d_profile, n_parts, part};
+    hipLaunchKernelGGL(profile_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
+    KT_HIP(hipGetLastError());
+    if (mem == KT_MEM_HOST) {
+        KT_HIP(hipMemcpyAsync(profile, d_profile, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return KT_OK;
 }

@@ -17,6 +17,9 @@ int total_bases_of(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, int m
 // copies a host CSR batch into ctx scratch (s_bases, s_offsets)
 int stage_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                 const uint8_t **d_bases, const uint64_t **d_offsets);
+// *too_long = a read of the batch holds 2^32 bases or more (total = offsets[n_reads]; a device read-back for KT_MEM_DEVICE;
+// uses ctx scratch s_aux2).  Defined in kt_cov.hip.
+int has_read_of_2_32(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int mem, bool *too_long);
 // the table's geometry as the device functions take it (kt_table.hpp)
 inline kttab::Geom geom_of(const kt_ctr *ctr) { return kttab::Geom{ctr->cap, ctr->shift, ctr->m8, ctr->kbits}; }
 // makes the table readable: performs a deferred clear, reports KT_ERR_FULL if it overflowed

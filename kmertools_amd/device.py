@@ -17,6 +17,7 @@ from ._lib import KT_F32, KT_F64, KT_MEM_DEVICE, KT_MEM_HOST, KT_U32, check
 
 _DT = {"f64": KT_F64, "f32": KT_F32, "u32": KT_U32, np.float64: KT_F64, np.float32: KT_F32, np.uint32: KT_U32}
 _NP = {KT_F64: np.float64, KT_F32: np.float32, KT_U32: np.uint32}
+NO_KMER = 0xFFFFFFFF  # KT_NO_KMER: the entry of a profile where no k-mer starts
 
 
 def _ptr(x):
@@ -304,6 +305,27 @@ class Context:
         return keys[: int(counts.sum())], counts
 
     # -- synthetic reads (device only) ----------------------------------------------------------
+    # -- profile: per-read statistics of a per-position count array (Counter.profile) ----------
+    def profile_stats(self, profile, offsets, n_reads, n_kmers=None, n_present=None, min_count=None, median=None,
+                      max_count=None, sum=None, mem=KT_MEM_DEVICE):
+        """per read, over its entries of `profile` that are not 0xFFFFFFFF: how many, those >= 1, the least, element
+        n // 2 of them sorted ascending, the greatest (u32 arrays of n_reads) and their sum (u64) - overwritten; any of
+        them may be None (kt_profile_stats)"""
+        check(_lib.lib().kt_profile_stats(self._h, _ptr(profile), _ptr(offsets), int(n_reads), _ptr(n_kmers),
+                                          _ptr(n_present), _ptr(min_count), _ptr(median), _ptr(max_count), _ptr(sum), mem))
+
+    def profile_stats_host(self, profile, offsets):
+        """-> {"n_kmers", "n_present", "min", "median", "max": u32 arrays, "sum": u64 array}, one entry per read"""
+        profile = np.ascontiguousarray(profile, np.uint32)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        out = {name: np.zeros(n, np.uint32) for name in ("n_kmers", "n_present", "min", "median", "max")}
+        out["sum"] = np.zeros(n, np.uint64)
+        if n:
+            self.profile_stats(profile if profile.size else np.zeros(1, np.uint32), offsets, n, out["n_kmers"],
+                               out["n_present"], out["min"], out["median"], out["max"], out["sum"], KT_MEM_HOST)
+        return out
+
     def synth_reads(self, seed, n_reads, read_len, bases_dev, offsets_dev=None, noise=False, genome_len=0,
                     first_read=0):
         check(_lib.lib().kt_synth_reads(self._h, seed, first_read, n_reads, read_len, int(bool(noise)),
@@ -438,6 +460,25 @@ class Counter:
             self.read_solidity(bases if bases.size else np.zeros(1, np.uint8), offsets, n, min_count, hi, nk, ns, fw,
                                KT_MEM_HOST)
         return nk, ns, fw
+
+    # -- profile: the count of the k-mer that starts at every base --------------------------------
+    def profile(self, bases, offsets, n_reads, profile, mem=KT_MEM_DEVICE, n_parts=1, part=0):
+        """writes min(count, 0xFFFFFFFE) of every valid window of hash partition `part` of n_parts into profile[global
+        base index of its start] - a u32 array of offsets[n_reads] entries that the caller filled with NO_KMER; every
+        other entry is left as it is (kt_ctr_profile)"""
+        check(_lib.lib().kt_ctr_profile(self._h, _ptr(bases), _ptr(offsets), int(n_reads), _ptr(profile), mem,
+                                        int(n_parts), int(part)))
+        return profile
+
+    def profile_host(self, bases, offsets):
+        """-> u32 array, one entry per base: the whole table's count of the k-mer that starts there, NO_KMER where none does"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        prof = np.full(int(offsets[-1]) if n > 0 else 0, NO_KMER, np.uint32)
+        if n > 0 and prof.size:
+            self.profile(bases, offsets, n, prof, KT_MEM_HOST)
+        return prof
 
     def spectrum(self, n_bins=10001, totals=False):
         """The table's abundance spectrum (jellyfish histo): hist[c] = distinct k-mers with exactly c occurrences for
