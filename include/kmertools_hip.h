@@ -248,6 +248,42 @@ int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *tota
  * kt_ctr_size. */
 int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n_rows, uint32_t n_cols, uint64_t *totals, int mem);
 
+/* Which k-mers kt_ctr_compare counted: the intersection, difference, union or symmetric difference of two tables of the
+ * same k as (key, count) pairs (kmc_tools simple intersect / kmers_subtract / union, meryl intersect / difference /
+ * union, kat filter kmer). */
+#define KT_SET_INTERSECT 0   /* in A and in B            */
+#define KT_SET_SUBTRACT  1   /* in A and not in B        */
+#define KT_SET_UNION     2   /* in A or in B             */
+#define KT_SET_XOR       3   /* in exactly one of them   */
+#define KT_SETCNT_FIRST  0   /* a' if a' != 0, else b'   */
+#define KT_SETCNT_MIN    1   /* the smaller of the non-zero ones among a', b' */
+#define KT_SETCNT_MAX    2   /* max(a', b')              */
+#define KT_SETCNT_SUM    3   /* a' + b', saturating at 0xFFFFFFFF */
+/* count_a / count_b are the tables' occurrences of a canonical k-mer, 0 when absent.  The k-mer is IN A when
+ * min_a <= count_a <= max_a, IN B when min_b <= count_b <= max_b (min_* >= 1: an absent k-mer is never a member;
+ * (1, UINT32_MAX) is plain presence).  a' = in A ? count_a : 0, b' likewise: a count outside its range is treated as
+ * absent, in the membership test and in the count rule alike, so every emitted count is >= 1.
+ * Every distinct k-mer for which op(in A, in B) holds is emitted exactly once as (key, count_rule(a', b')).  sorted == 0:
+ * in unspecified order (as kt_ctr_export); sorted != 0: in ascending key order (a radix sort of the result on the
+ * device).  *n_out = the number of entries that qualify, always exact.  max_out == 0 (keys / counts may be NULL) only
+ * counts and stores nothing.  If 0 < max_out < *n_out, nothing past max_out is written (what is written is unsorted and
+ * of no use) and the call returns KT_ERR_ARG with *n_out set, so that the caller can resize and repeat.
+ * If a and b hold the same hash partition of n_parts (kt_ctr_add_reads_part), the concatenation of the outputs over the
+ * partitions is the whole tables' answer (a k-mer lives in exactly one partition, in both tables); with sorted, each
+ * partition's output is sorted, not the concatenation.
+ * a == b is allowed.  Neither table's content changes; a table that is probed gets its probing image first, as in
+ * kt_ctr_lookup / kt_ctr_compare, and the walked table's form is read only after that.  Intersect and subtract walk A
+ * and probe B.  Union and xor add a second walk: B's entries whose key is absent from A's TABLE (count_a == 0, not merely
+ * outside A's range - those were decided in A's walk), probing A; each key is thus visited exactly once.
+ * mem says where keys / counts live.  KT_MEM_HOST synchronises; KT_MEM_DEVICE writes on the context's stream, but the
+ * call still synchronises once, to learn *n_out.
+ * KT_ERR_ARG: a null table or n_out, different k, tables on different contexts, a table that is one shard of a sharded
+ * table (n_owners > 1: not supported), an unknown op or count_rule, min_a == 0 or min_b == 0, min_a > max_a or
+ * min_b > max_b, a bad mem, null outputs with max_out > 0.  An overflowed table is KT_ERR_FULL as in kt_ctr_size.  On
+ * every one of these errors the output arrays are untouched. */
+int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32_t min_a, uint32_t max_a, uint32_t min_b, uint32_t max_b,
+                 uint64_t *keys, uint32_t *counts, uint64_t max_out, uint64_t *n_out, int mem, int sorted);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

@@ -716,31 +716,20 @@ class TableWriter {
         for (uint64_t i0 = 0; i0 < n; i0 += slab_) {
             const uint64_t m = n - i0 < slab_ ? n - i0 : slab_;
             if (kt_ctr_export_fetch(ctr, i0, m, keys_.data(), counts_.data()) != KT_OK) return kt_last_error();
-            // "{kmer}\t{count}\n" (or the ACGT form), counter/src/lib.rs:220-230
-            const uint64_t *keys = keys_.data();
-            const uint32_t *counts = counts_.data();
-            format_rows(m, threads_, acgt_ ? (size_t)k_ + 13 : 32, pieces_, [&](uint64_t i, std::string &s) {
-                char buf[40];
-                if (acgt_) {
-                    kt_numeric_to_kmer(keys[i], k_, buf);  // counter/src/lib.rs:221-226
-                    s += buf;
-                } else {
-                    const auto rr = std::to_chars(buf, buf + sizeof buf, keys[i]);
-                    s.append(buf, (size_t)(rr.ptr - buf));
-                }
-                s += '\t';
-                const auto r2 = std::to_chars(buf, buf + sizeof buf, counts[i]);
-                s.append(buf, (size_t)(r2.ptr - buf));
-                s += '\n';
-            });
-            const uint64_t h = heap_in_use_kb();  // with a slab's pairs and its text in hand: the writer's high point
-            if (h > heap_peak_kb_) heap_peak_kb_ = h;
-            for (const auto &p : pieces_)
-                if (fwrite(p.data(), 1, p.size(), out) != p.size()) return "Unable to write the table's lines";
+            if (std::string e = emit(out, keys_.data(), counts_.data(), m); !e.empty()) return e;
             slabs_++;
         }
         entries_ += n;
         if (n_out) *n_out = n;
+        return "";
+    }
+    // the same lines from (key, count) pairs the caller holds on the host (setop's result), the text a slab at a time
+    std::string write_pairs(FILE *out, const uint64_t *keys, const uint32_t *counts, uint64_t n) {
+        for (uint64_t i0 = 0; i0 < n; i0 += slab_) {
+            if (std::string e = emit(out, keys + i0, counts + i0, n - i0 < slab_ ? n - i0 : slab_); !e.empty()) return e;
+            slabs_++;
+        }
+        entries_ += n;
         return "";
     }
     // bytes held in the writer's own buffers (capacities: what stays allocated between slabs)
@@ -754,6 +743,29 @@ class TableWriter {
     uint64_t slabs() const { return slabs_; }
 
   private:
+    // one slab's text, formatted on the workers and written
+    std::string emit(FILE *out, const uint64_t *keys, const uint32_t *counts, uint64_t m) {
+        // "{kmer}\t{count}\n" (or the ACGT form), counter/src/lib.rs:220-230
+        format_rows(m, threads_, acgt_ ? (size_t)k_ + 13 : 32, pieces_, [&](uint64_t i, std::string &s) {
+            char buf[40];
+            if (acgt_) {
+                kt_numeric_to_kmer(keys[i], k_, buf);  // counter/src/lib.rs:221-226
+                s += buf;
+            } else {
+                const auto rr = std::to_chars(buf, buf + sizeof buf, keys[i]);
+                s.append(buf, (size_t)(rr.ptr - buf));
+            }
+            s += '\t';
+            const auto r2 = std::to_chars(buf, buf + sizeof buf, counts[i]);
+            s.append(buf, (size_t)(r2.ptr - buf));
+            s += '\n';
+        });
+        const uint64_t h = heap_in_use_kb();  // with a slab's pairs and its text in hand: the writer's high point
+        if (h > heap_peak_kb_) heap_peak_kb_ = h;
+        for (const auto &p : pieces_)
+            if (fwrite(p.data(), 1, p.size(), out) != p.size()) return "Unable to write the table's lines";
+        return "";
+    }
     bool acgt_;
     int k_, threads_;
     uint32_t lo_ = 1, hi_ = 0xFFFFFFFFu;
@@ -1662,21 +1674,23 @@ std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_
     return "";
 }
 
-std::string CompareComputer::compare() {
-    release();
+// What `compare` and `setop` share.  Both tables of a pass live on one device next to the build's buffers
+// (CountComputer::count's reserve), `bytes_per_slot` of HBM for every slot of either (16: the slot itself); when they cannot,
+// or KT_CTR_MAX_SLOTS bounds a table (tests: force the out-of-core passes), the inputs are counted in *passes passes,
+// pass p holding hash partition p of both.  Creates the tables; on an error none is left.
+static const uint64_t TWO_TABLE_BATCH_BASES = 256ull << 20;
+static std::string two_tables_setup(Device &dev, const std::string &in_a, const std::string &in_b, int k, uint64_t bytes_per_slot,
+                                    const char *what, uint32_t *passes, kt_ctr **ta, kt_ctr **tb) {
     Lap setup;
     uint64_t want_a = 0, want_b = 0;
-    if (std::string e = compare_want(in_a_, ksize_, &want_a); !e.empty()) return e;
-    if (std::string e = compare_want(in_b_, ksize_, &want_b); !e.empty()) return e;
-    if (std::string e = dev_.ensure(); !e.empty()) return e;
-    // both tables of a pass share the HBM next to the build's buffers (CountComputer::count's reserve); KT_CTR_MAX_SLOTS
-    // bounds each table (tests: force the out-of-core passes)
-    const uint64_t batch_bases = 256ull << 20;
+    if (std::string e = compare_want(in_a, k, &want_a); !e.empty()) return e;
+    if (std::string e = compare_want(in_b, k, &want_b); !e.empty()) return e;
+    if (std::string e = dev.ensure(); !e.empty()) return e;
     uint64_t free_b = 0, total_b = 0, fit_both = want_a + want_b;
-    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
-        const uint64_t reserve = batch_bases * 20 + (1ull << 30);
+    if (kt_device_memory(dev.ctx, &free_b, &total_b) == KT_OK) {
+        const uint64_t reserve = TWO_TABLE_BATCH_BASES * 20 + (1ull << 30);
         const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
-        fit_both = usable / 10 * 9 / 16;
+        fit_both = usable / 10 * 9 / bytes_per_slot;
     }
     if (fit_both < 2048) fit_both = 2048;
     uint64_t fit_each = env_u64_host("KT_CTR_MAX_SLOTS", ~0ull);
@@ -1684,25 +1698,53 @@ std::string CompareComputer::compare() {
     uint64_t p = (want_a + want_b + fit_both - 1) / fit_both;
     p = std::max(p, (want_a + fit_each - 1) / fit_each);
     p = std::max(p, (want_b + fit_each - 1) / fit_each);
-    passes_ = (uint32_t)std::max<uint64_t>(p, 1);
+    *passes = (uint32_t)std::max<uint64_t>(p, 1);
     // a partition's share of the keys varies a little: 1 / passes + 5 sigma of room; more passes when the tables do not fit
     uint64_t cap_a = 0, cap_b = 0;
-    for (;; passes_++) {
-        cap_a = passes_ == 1 ? want_a : want_a / passes_ + want_a / passes_ / 16 + 4096;
-        cap_b = passes_ == 1 ? want_b : want_b / passes_ + want_b / passes_ / 16 + 4096;
-        int rc = kt_ctr_create(dev_.ctx, ksize_, cap_a, &ta_);
-        if (rc == KT_OK) rc = kt_ctr_create(dev_.ctx, ksize_, cap_b, &tb_);
+    for (;; ++*passes) {
+        cap_a = *passes == 1 ? want_a : want_a / *passes + want_a / *passes / 16 + 4096;
+        cap_b = *passes == 1 ? want_b : want_b / *passes + want_b / *passes / 16 + 4096;
+        int rc = kt_ctr_create(dev.ctx, k, cap_a, ta);
+        if (rc == KT_OK) rc = kt_ctr_create(dev.ctx, k, cap_b, tb);
         if (rc == KT_OK) break;
-        release();
-        if (rc != KT_ERR_NOMEM || passes_ >= 4096) return kt_last_error();
+        if (*ta) kt_ctr_destroy(*ta);
+        if (*tb) kt_ctr_destroy(*tb);
+        *ta = *tb = nullptr;
+        if (rc != KT_ERR_NOMEM || *passes >= 4096) return kt_last_error();
     }
     if (getenv("KT_CLI_TIMING")) {
         uint64_t sa = cap_a, sb = cap_b;
-        (void)kt_ctr_capacity(ta_, &sa);
-        (void)kt_ctr_capacity(tb_, &sb);
-        fprintf(stderr, "[timing] compare setup: tables of %llu + %llu slots, %u pass(es) %.3f s\n", (unsigned long long)sa,
-                (unsigned long long)sb, passes_, setup());
+        (void)kt_ctr_capacity(*ta, &sa);
+        (void)kt_ctr_capacity(*tb, &sb);
+        fprintf(stderr, "[timing] %s setup: tables of %llu + %llu slots, %u pass(es) %.3f s\n", what, (unsigned long long)sa,
+                (unsigned long long)sb, *passes, setup());
     }
+    return "";
+}
+
+// pass `pass` of `passes`: both tables cleared (after the first pass) and filled with their inputs' hash partition
+static std::string two_tables_count(uint32_t pass, uint32_t passes, SeqReader &ra, SeqReader &rb, kt_ctr *ta, kt_ctr *tb,
+                                    Batch &b, PhaseTimer &pt, Lap &lap) {
+    if (pass && (kt_ctr_clear(ta) != KT_OK || kt_ctr_clear(tb) != KT_OK)) return kt_last_error();
+    for (auto [reader, table] : {std::make_pair(&ra, ta), std::make_pair(&rb, tb)}) {
+        if (pass && !reader->rewind()) return reader->error();
+        for (;;) {
+            const bool more = reader->next_batch(b, cli_batch_bases(TWO_TABLE_BATCH_BASES), cli_batch_reads(1ull << 22));
+            pt.t[0] += lap();
+            if (b.n_reads() && !b.bases.empty())
+                if (kt_ctr_add_reads_part(table, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST, passes, pass) != KT_OK)
+                    return kt_last_error();
+            pt.t[1] += lap();
+            if (!more) break;
+        }
+        if (reader->failed()) return reader->error();
+    }
+    return "";
+}
+
+std::string CompareComputer::compare() {
+    release();
+    if (std::string e = two_tables_setup(dev_, in_a_, in_b_, ksize_, 16, "compare", &passes_, &ta_, &tb_); !e.empty()) return e;
     const uint32_t R = max_a_ + 1, C = max_b_ + 1;
     std::vector<uint64_t> m((size_t)R * C, 0);
     uint64_t tot[6] = {0, 0, 0, 0, 0, 0};
@@ -1713,20 +1755,7 @@ std::string CompareComputer::compare() {
     Batch b;
     for (uint32_t pass = 0; pass < passes_; pass++) {
         Lap lap;
-        if (pass && (kt_ctr_clear(ta_) != KT_OK || kt_ctr_clear(tb_) != KT_OK)) return kt_last_error();
-        for (auto [reader, table] : {std::make_pair(&ra, ta_), std::make_pair(&rb, tb_)}) {
-            if (pass && !reader->rewind()) return reader->error();
-            for (;;) {
-                const bool more = reader->next_batch(b, cli_batch_bases(batch_bases), cli_batch_reads(1ull << 22));
-                pt.t[0] += lap();
-                if (b.n_reads() && !b.bases.empty())
-                    if (kt_ctr_add_reads_part(table, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST, passes_, pass) != KT_OK)
-                        return kt_last_error();
-                pt.t[1] += lap();
-                if (!more) break;
-            }
-            if (reader->failed()) return reader->error();
-        }
+        if (std::string e = two_tables_count(pass, passes_, ra, rb, ta_, tb_, b, pt, lap); !e.empty()) return e;
         if (kt_ctr_compare(ta_, tb_, m.data(), R, C, tot, KT_MEM_HOST) != KT_OK) return kt_last_error();
         pt.t[1] += lap();
     }
@@ -1734,6 +1763,86 @@ std::string CompareComputer::compare() {
     std::string e = write(m, tot);
     pt.t[3] += lap();
     return e;
+}
+
+// ---------------------------------------------------------------------------------------------
+SetopComputer::SetopComputer(std::string in_a, std::string in_b, std::string out_dir, int ksize)
+    : in_a_(std::move(in_a)), in_b_(std::move(in_b)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
+
+SetopComputer::~SetopComputer() { release(); }
+
+void SetopComputer::release() {
+    if (ta_) kt_ctr_destroy(ta_);
+    if (tb_) kt_ctr_destroy(tb_);
+    ta_ = tb_ = nullptr;
+}
+
+std::string SetopComputer::setop() {
+    release();
+    // HBM per slot: the slot (16) + its share of the result and of the sort's second pair - at most every entry of both
+    // tables, 12 bytes, twice, with 1.9 slots per entry: 24 / 1.9 < 13
+    if (std::string e = two_tables_setup(dev_, in_a_, in_b_, ksize_, 16 + 13, "setop", &passes_, &ta_, &tb_); !e.empty()) return e;
+    const std::string cpath = out_dir_ + "/kmers.counts", spath = out_dir_ + "/setop.stats";
+    FILE *out = fopen(cpath.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + cpath;
+    struct Closer {
+        FILE *f;
+        ~Closer() {
+            if (f) fclose(f);
+        }
+    } closer{out};
+    // distinct_a, distinct_b, in_a, in_b, emitted, emitted_occurrences
+    uint64_t tot[6] = {0, 0, 0, 0, 0, 0};
+    TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> counts;
+    PhaseTimer pt("setop");
+    SeqReader ra, rb;
+    if (!ra.open(in_a_, false)) return ra.error();
+    if (!rb.open(in_b_, false)) return rb.error();
+    Batch b;
+    const bool plain_a = min_a_ == 1 && max_a_ == 0xFFFFFFFFu, plain_b = min_b_ == 1 && max_b_ == 0xFFFFFFFFu;
+    for (uint32_t pass = 0; pass < passes_; pass++) {
+        Lap lap;
+        if (std::string e = two_tables_count(pass, passes_, ra, rb, ta_, tb_, b, pt, lap); !e.empty()) return e;
+        uint64_t n_a = 0, n_b = 0, in_a = 0, in_b = 0, n = 0;
+        if (kt_ctr_size(ta_, &n_a) != KT_OK || kt_ctr_size(tb_, &n_b) != KT_OK) return kt_last_error();
+        // what can qualify at most sizes the host arrays: one call, no counting call before it
+        const uint64_t bound = op_ == KT_SET_INTERSECT ? std::min(n_a, n_b) : op_ == KT_SET_SUBTRACT ? n_a : n_a + n_b;
+        if (keys.size() < bound) {
+            keys.resize((size_t)bound);
+            counts.resize((size_t)bound);
+        }
+        if (bound && kt_ctr_setop(ta_, tb_, op_, rule_, min_a_, max_a_, min_b_, max_b_, keys.data(), counts.data(), bound, &n,
+                                  KT_MEM_HOST, 1) != KT_OK)
+            return kt_last_error();
+        // the members of each side under its range: the table's size, or (a range given) the table intersected with itself
+        in_a = n_a, in_b = n_b;
+        if (!plain_a && n_a &&
+            kt_ctr_setop(ta_, ta_, KT_SET_INTERSECT, KT_SETCNT_FIRST, min_a_, max_a_, min_a_, max_a_, nullptr, nullptr, 0, &in_a,
+                         KT_MEM_HOST, 0) != KT_OK)
+            return kt_last_error();
+        if (!plain_b && n_b &&
+            kt_ctr_setop(tb_, tb_, KT_SET_INTERSECT, KT_SETCNT_FIRST, min_b_, max_b_, min_b_, max_b_, nullptr, nullptr, 0, &in_b,
+                         KT_MEM_HOST, 0) != KT_OK)
+            return kt_last_error();
+        pt.t[1] += lap();
+        uint64_t occ = 0;
+        for (uint64_t i = 0; i < n; i++) occ += counts[i];
+        tot[0] += n_a, tot[1] += n_b, tot[2] += in_a, tot[3] += in_b, tot[4] += n, tot[5] += occ;
+        if (std::string e = writer.write_pairs(out, keys.data(), counts.data(), n); !e.empty()) return e;
+        pt.t[3] += lap();
+    }
+    closer.f = nullptr;
+    if (fclose(out) != 0) return "Unable to write to file: " + cpath;
+    static const char *names[6] = {"distinct_a", "distinct_b", "in_a", "in_b", "emitted", "emitted_occurrences"};
+    std::string s;
+    for (int j = 0; j < 6; j++) s += std::string(names[j]) + '\t' + std::to_string(tot[j]) + '\n';
+    out = fopen(spath.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + spath;
+    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
+    return "";
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -287,4 +287,37 @@ class CompareComputer {
     std::string write(const std::vector<uint64_t> &m, const uint64_t *tot) const;
 };
 
+// `setop`: WHICH k-mers `compare` counted - the intersection, difference, union or symmetric difference of two inputs'
+// k-mer tables (kmc_tools simple, meryl, kat filter kmer), counted and passed over as CompareComputer does; every pass runs
+// kt_ctr_setop (sorted) on its two tables and appends its lines.  Writes {out_dir}/kmers.counts in `ctr`'s line format -
+// ascending numeric key within a pass, the passes one after the other - and {out_dir}/setop.stats ("name\tvalue" lines:
+// distinct_a, distinct_b, in_a, in_b, emitted, emitted_occurrences).  The host holds one pass's result as pairs (12 bytes
+// an entry); its text is made a slab at a time.
+class SetopComputer {
+  public:
+    SetopComputer(std::string in_a, std::string in_b, std::string out_dir, int ksize);
+    ~SetopComputer();
+    SetopComputer(const SetopComputer &) = delete;
+    SetopComputer &operator=(const SetopComputer &) = delete;
+    void set_op(int op, int rule) { op_ = op, rule_ = rule; }  // KT_SET_*, KT_SETCNT_*
+    void set_ranges(uint32_t min_a, uint32_t max_a, uint32_t min_b, uint32_t max_b) {
+        min_a_ = min_a, max_a_ = max_a, min_b_ = min_b, max_b_ = max_b;
+    }
+    void set_acgt_output(bool a) { acgt_ = a; }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // the text slabs shrink with it; the tables live in HBM
+    void set_device(int d) { dev_.index = d; }
+    std::string setop();  // "" or the error message
+
+  private:
+    std::string in_a_, in_b_, out_dir_;
+    int ksize_, threads_ = 0, op_ = 0, rule_ = 0;
+    uint32_t min_a_ = 1, max_a_ = 0xFFFFFFFFu, min_b_ = 1, max_b_ = 0xFFFFFFFFu, passes_ = 1;
+    bool acgt_ = false;
+    double memory_ceil_gb_ = 6.0;
+    Device dev_;
+    kt_ctr *ta_ = nullptr, *tb_ = nullptr;
+    void release();
+};
+
 }  // namespace kthost

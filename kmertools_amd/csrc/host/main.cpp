@@ -3,7 +3,8 @@
 // (args.rs:132-172, :299-325).  clap conventions are kept: kebab-case long flags, the
 // auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.  `filter` (a k-mer read
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
-// and `profile` (per-position k-mer counts and per-sequence medians).
+// and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
+// inputs' k-mer tables).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -132,6 +133,7 @@ const char *HELP_MAIN =
     "  filter  Drop or trim reads by the abundance of their k-mers\n"
     "  compare Compare the k-mer counts of two inputs (matrix and set similarity)\n"
     "  profile Per-position k-mer counts and per-sequence min / median / mean / max\n"
+    "  setop   Intersect, subtract, union or xor the k-mer sets of two inputs\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
 
@@ -579,6 +581,98 @@ int cmd_profile(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_SETOP =
+    "Intersect, subtract, union or xor the k-mer sets of two inputs\n\n"
+    "Counts the canonical k-mers of both inputs.  A k-mer is in the input when min-a <= its count there <= max-a, in the alt\n"
+    "input when min-b <= its count there <= max-b (an absent k-mer is in neither; a count outside its range is taken as 0).\n"
+    "Writes the k-mers for which --op holds to {output}/kmers.counts, one \"kmer<TAB>count\" line each as `ctr` writes them,\n"
+    "in ascending order of the numeric k-mer (with --acgt too; when the tables do not fit the device memory they are\n"
+    "counted in several passes and each pass's lines are in that order, the passes one after the other), and\n"
+    "{output}/setop.stats: distinct_a, distinct_b, in_a, in_b, emitted and emitted_occurrences, one \"name<TAB>value\" line each.\n\n"
+    "Usage: kmertools setop [OPTIONS] --input <INPUT> --alt-input <ALT_INPUT> --output <OUTPUT> --k-size <K_SIZE> --op <OP>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path (A)\n"
+    "  -a, --alt-input <ALT_INPUT>  Input file path (B)\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "      --op <OP>                Which k-mers to write [possible values: intersect, subtract, union, xor]\n"
+    "                               (in A and B; in A, not in B; in A or B; in exactly one)\n"
+    "      --count <COUNT>          The count to write, from the in-range counts a and b [default: first]\n"
+    "                               [possible values: first, min, max, sum] (first: a, else b; min / max of the non-zero\n"
+    "                               ones; sum saturates at 4294967295)\n"
+    "      --min-a <N>              Lowest count of a k-mer of A [default: 1]\n"
+    "      --max-a <N>              Highest count of a k-mer of A [default: 4294967295]\n"
+    "      --min-b <N>              Lowest count of a k-mer of B [default: 1]\n"
+    "      --max-b <N>              Highest count of a k-mer of B [default: 4294967295]\n"
+    "      --acgt                   Output ACGT instead of numeric values\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (the tables live in HBM: when both and the result cannot\n"
+    "                               fit, the inputs are counted in several passes; the text is written in slabs)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+// the index of flag `name`'s value among `values` (clap's possible values)
+int one_of(const std::map<std::string, std::string> &f, const char *name, const std::vector<std::string> &values, bool required,
+           int dflt) {
+    auto it = f.find(name);
+    if (it == f.end()) {
+        if (required) usage_error(std::string("the following required arguments were not provided:\n  --") + name);
+        return dflt;
+    }
+    std::string all;
+    for (size_t i = 0; i < values.size(); i++) {
+        if (it->second == values[i]) return (int)i;
+        all += (i ? ", " : "") + values[i];
+    }
+    usage_error("invalid value '" + it->second + "' for '--" + name + "'\n  [possible values: " + all + "]");
+}
+
+int cmd_setop(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},  {'a', "alt-input", true}, {'o', "output", true}, {'k', "k-size", true},
+                                     {0, "op", true},       {0, "count", true},       {0, "min-a", true},    {0, "max-a", true},
+                                     {0, "min-b", true},    {0, "max-b", true},       {0, "acgt", false},    {'m', "memory", true},
+                                     {'t', "threads", true}, {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_SETOP);
+    const std::string in = required_str(f, "input"), alt = required_str(f, "alt-input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work and before the output directory is made
+    static_assert(KT_SET_INTERSECT == 0 && KT_SET_SUBTRACT == 1 && KT_SET_UNION == 2 && KT_SET_XOR == 3, "the order of --op's values");
+    static_assert(KT_SETCNT_FIRST == 0 && KT_SETCNT_MIN == 1 && KT_SETCNT_MAX == 2 && KT_SETCNT_SUM == 3, "... and of --count's");
+    const int op = one_of(f, "op", {"intersect", "subtract", "union", "xor"}, true, 0);     // = KT_SET_*
+    const int rule = one_of(f, "count", {"first", "min", "max", "sum"}, false, 0);          // = KT_SETCNT_*
+    uint64_t lo[2], hi[2];
+    for (int j = 0; j < 2; j++) {
+        const std::string mn = j ? "min-b" : "min-a", mx = j ? "max-b" : "max-a";
+        lo[j] = ranged(f, mn.c_str(), 1, 0xFFFFFFFFull, false, 1);
+        hi[j] = ranged(f, mx.c_str(), 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+        if (lo[j] > hi[j])
+            usage_error("invalid values for '--" + mn + "' and '--" + mx + "': " + std::to_string(lo[j]) + " is greater than " +
+                        std::to_string(hi[j]));
+    }
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    for (const std::string &p : {in, alt}) {
+        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    SetopComputer so(in, alt, out, k);
+    so.set_op(op, rule);
+    so.set_ranges((uint32_t)lo[0], (uint32_t)hi[0], (uint32_t)lo[1], (uint32_t)hi[1]);
+    so.set_acgt_output(f.count("acgt") != 0);
+    if (threads > 0) so.set_threads(threads);
+    so.set_max_memory((double)mem);
+    so.set_device(device);
+    if (std::string e = so.setop(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -706,5 +800,6 @@ int main(int argc, char **argv) {
     if (cmd == "filter") return cmd_filter(argc, argv, 2);
     if (cmd == "compare") return cmd_compare(argc, argv, 2);
     if (cmd == "profile") return cmd_profile(argc, argv, 2);
+    if (cmd == "setop") return cmd_setop(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

@@ -131,6 +131,10 @@ struct kt_ctr {
 int kt_oligo_generic_launch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k,
                             int count_min, int norm, int total_step, int dt, void *out);
 
+// kt_sort.hip: (key, count) pairs in device memory into ascending key order (LSD radix sort over key_bits bits, on the
+// context's stream; scratch: the context's s_out and s_aux0)
+int kt_sort_pairs(kt_ctx *ctx, uint64_t *keys, uint32_t *counts, uint64_t n, uint32_t key_bits);
+
 namespace kt {
 // host-side table builders (kt_host.cpp)
 uint64_t rev_comp_bits(uint64_t kmer, int k);

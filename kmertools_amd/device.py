@@ -512,6 +512,46 @@ class Counter:
         check(_lib.lib().kt_ctr_compare(self._h, other._h, _ptr(matrix), int(n_rows), int(n_cols), _ptr(totals), mem))
         return matrix
 
+    SET_OPS = {"intersect": 0, "subtract": 1, "union": 2, "xor": 3}
+    SET_COUNTS = {"first": 0, "min": 1, "max": 2, "sum": 3}
+
+    @classmethod
+    def _setop_args(cls, op, count, a_range, b_range):
+        """the strings and ranges of setop / setop_device as kt_ctr_setop's integers (ValueError before any library call)"""
+        if op not in cls.SET_OPS:
+            raise ValueError("setop: unknown op %r (one of %s)" % (op, ", ".join(cls.SET_OPS)))
+        if count not in cls.SET_COUNTS:
+            raise ValueError("setop: unknown count rule %r (one of %s)" % (count, ", ".join(cls.SET_COUNTS)))
+        lo_a, hi_a = a_range
+        lo_b, hi_b = b_range
+        return (cls.SET_OPS[op], cls.SET_COUNTS[count], int(lo_a), 0xFFFFFFFF if hi_a is None else int(hi_a), int(lo_b),
+                0xFFFFFFFF if hi_b is None else int(hi_b))
+
+    def setop(self, other, op, count="first", a_range=(1, None), b_range=(1, None), sort=True):
+        """The k-mers of this table (A) and `other` (B), same k, for which `op` holds - "intersect" (in A and in B),
+        "subtract" (in A, not in B), "union", "xor" - as (keys u64, counts u32) numpy arrays, ascending by key with sort.
+        A k-mer is in a table when its count there lies in that table's (min, max) range (None: no upper bound); a count
+        outside the range is taken as 0.  `count`: "first" (A's, else B's), "min" / "max" of the non-zero ones, "sum"
+        (saturating).  A count-only call, then one call sized by it (kt_ctr_setop)."""
+        args = self._setop_args(op, count, a_range, b_range)
+        n = C.c_uint64()
+        check(_lib.lib().kt_ctr_setop(self._h, other._h, *args, None, None, 0, C.byref(n), KT_MEM_HOST, 0))
+        keys = np.zeros(n.value, np.uint64)
+        counts = np.zeros(n.value, np.uint32)
+        if n.value:
+            check(_lib.lib().kt_ctr_setop(self._h, other._h, *args, _ptr(keys), _ptr(counts), n.value, C.byref(n),
+                                          KT_MEM_HOST, int(bool(sort))))
+        return keys, counts
+
+    def setop_device(self, other, op, keys, counts, max_out, count="first", a_range=(1, None), b_range=(1, None), sort=True):
+        """setop into device tensors of max_out entries (keys u64 / counts u32 bit patterns; None, None, 0 only counts);
+        returns the number of entries that qualify.  Raises KmertoolsError (KT_ERR_ARG) when 0 < max_out < that number."""
+        args = self._setop_args(op, count, a_range, b_range)
+        n = C.c_uint64()
+        check(_lib.lib().kt_ctr_setop(self._h, other._h, *args, _ptr(keys), _ptr(counts), int(max_out), C.byref(n),
+                                      KT_MEM_DEVICE, int(bool(sort))))
+        return n.value
+
     def export_stage_range(self, min_count=1, max_count=None):
         """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
         n = C.c_uint64()
