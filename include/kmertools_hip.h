@@ -403,6 +403,45 @@ int kt_profile_stats(kt_ctx *ctx, const uint32_t *profile, const uint64_t *offse
                      uint32_t *n_present, uint32_t *min_count, uint32_t *median, uint32_t *max_count, uint64_t *sum,
                      int mem);
 
+/* k-mer spectrum error correction of reads against the table (`kmertools correct`; what Musket, Lighter and BFC do on the
+ * CPU).  replaces: nothing - the reference has no such operation.  Two calls, split as kt_ctr_profile / kt_profile_stats
+ * are: this one needs the table and adds over hash partitions, kt_correct_apply is a pure function of arrays.
+ * The rule is decided from the UNCORRECTED read, base by base, so no order of evaluation matters.  A window is k
+ * consecutive bases inside one read, named by the global index j of its first base; a k-mer is solid when
+ * min_count <= count <= max_count, as in kt_ctr_read_solidity.  For base g of read [o, o') the windows that contain it
+ * are j in [max(o, g - k + 1), min(g, o' - k)].
+ *   covered   g is covered when one of those windows is valid and solid.  That is taken from `profile`, the COMPLETE
+ *             answer of kt_ctr_profile for the same batch (offsets[n_reads] entries, all partitions done): window j counts
+ *             iff profile[j] != KT_NO_KMER and min_count <= profile[j] <= max_count.  No probe is made for it, and a
+ *             profile the caller made up works as well.  A covered base is trusted; so is every base of a read shorter
+ *             than k.
+ *   support   for an uncovered g (its own byte may be valid or not) and every nucleotide x in 0..3 other than its own
+ *             code, s(g, x) = the number of those windows in which every byte other than g is valid and whose canonical
+ *             k-mer, with x written at g, is solid.  Byte x (bits 8x .. 8x+7) of support[g] GAINS the part of s(g, x)
+ *             whose substituted k-mers belong to hash partition `part` of n_parts.  The caller zeroes `support`
+ *             (offsets[n_reads] u32 entries) once; summed over parts 0..n_parts-1 a byte is at most k <= 31, so no byte
+ *             carries into the next.  Entries of covered bases and of reads shorter than k are not written.
+ * `mem` says where bases, offsets, profile and support live; KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the
+ * context's stream.  KT_ERR_ARG: min_count == 0, min_count > max_count, part >= n_parts, a bad mem, a null buffer with
+ * n_reads > 0, or a table that is one shard of a sharded table (as for the read solidity call). */
+int kt_ctr_correct_support(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                           const uint32_t *profile, uint32_t min_count, uint32_t max_count, uint32_t *support, int mem,
+                           uint32_t n_parts, uint32_t part);
+
+/* The decision over such a support array (no table, no k: its bytes are compared with min_support and that is all).
+ * Base g is SINGLE when exactly one byte of support[g] is >= min_support, AMBIGUOUS when two or more are.
+ *   n_single[i] / n_ambiguous[i] = the single / ambiguous bases of read i (overwritten; either may be NULL),
+ *   out_bases[g] = "ACGT"[x] at the single bases of the reads with n_single <= max_corrections (0: no limit) - a read that
+ *                  needs more repairs than that is left as it is -, bases[g] everywhere else: case, N, U and raw codes
+ *                  untouched, ambiguous bases never changed.  Every byte of the batch is written.  May be NULL (counts
+ *                  only) and may be `bases` itself (in place).
+ * There is no second round: repairing a base cannot uncover another one, and two errors closer than k with no solid
+ * window between them stay.  `mem` says where all the arrays live; KT_MEM_HOST synchronises.
+ * KT_ERR_ARG: min_support == 0 or > 255, a bad mem, a null input with n_reads > 0, a read of 2^32 bases or more. */
+int kt_correct_apply(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, const uint32_t *support,
+                     uint32_t min_support, uint32_t max_corrections, uint8_t *out_bases, uint32_t *n_single,
+                     uint32_t *n_ambiguous, int mem);
+
 /* Multi-GPU routing step (the reference's `min_mer % n_parts` partitioning,
  * counter/src/lib.rs:127, re-expressed as hash-prefix ownership):
  * writes every canonical k-mer of the reads into keys_out grouped by owner

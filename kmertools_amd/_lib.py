@@ -69,6 +69,8 @@ SYMBOLS = {
     "kt_ctr_read_solidity": (_i, [_vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _i, _u32, _u32]),
     "kt_ctr_profile": (_i, [_vp, _vp, _vp, _u64, _vp, _i, _u32, _u32]),
     "kt_profile_stats": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "kt_ctr_correct_support": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _i, _u32, _u32]),
+    "kt_correct_apply": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _i]),
     "kt_ctr_route": (_i, [_vp, _vp, _vp, _u64, _i, _i, _vp, _vp, _i]),
     "kt_owner_of": (_u32, [_u64, _u32]),
     "kt_rccl_unique_id": (_i, [_vp]),

@@ -1604,6 +1604,177 @@ std::string ProfileComputer::profile() {
 }
 
 // ---------------------------------------------------------------------------------------------
+CorrectComputer::CorrectComputer(std::string in_path, std::string out_path, int ksize)
+    : in_path_(in_path), in_path_kmer_(std::move(in_path)), out_path_(std::move(out_path)), ksize_(ksize) {}
+
+CorrectComputer::~CorrectComputer() { delete ctr_; }
+
+// one pass of an out-of-core table is complete.  First pass loop (support = false): the positions whose k-mers belong to this
+// hash partition (the profile).  Second (support = true): the supports whose substituted k-mers do, against the complete profile.
+std::string CorrectComputer::table_pass(bool support, uint32_t pass, uint32_t passes, kt_ctr *table) {
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    const double ceil_bytes = memory_ceil_gb_ * (double)(1ull << 30);
+    Batch b;
+    uint64_t at = 0, base = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20));
+        const uint64_t n = b.n_reads();
+        if (n) {
+            const uint64_t total = b.offsets[n];
+            if (!support && pass == 0) {
+                if ((double)(base + total) * 8.0 > ceil_bytes) {
+                    char msg[320];
+                    snprintf(msg, sizeof msg,
+                             "correct: the table takes %u passes, and the per-base counts and supports of the input kept across "
+                             "them (8 bytes per base, more than %.1f GB) do not fit the memory ceiling of %.0f GB: raise -m or "
+                             "split the input",
+                             passes, (double)(base + total) * 8.0 / (double)(1ull << 30), memory_ceil_gb_);
+                    return msg;
+                }
+                acc_prof_.resize(base + total, KT_NO_KMER);
+            } else if (base + total > acc_prof_.size()) {
+                return "correct: the input changed between the passes";
+            }
+            if (total) {
+                const int rc = support ? kt_ctr_correct_support(table, bases_ptr(b), b.offsets.data(), n, acc_prof_.data() + base, min_count_,
+                                                                max_count_, acc_sup_.data() + base, KT_MEM_HOST, passes, pass)
+                                       : kt_ctr_profile(table, bases_ptr(b), b.offsets.data(), n, acc_prof_.data() + base, KT_MEM_HOST, passes, pass);
+                if (rc != KT_OK) return kt_last_error();
+            }
+            at += n;
+            base += total;
+        }
+        if (!more) break;
+    }
+    if (reader.failed()) return reader.error();
+    if ((support || pass) && (at != acc_reads_ || base != acc_prof_.size())) return "correct: the input changed between the passes";
+    acc_reads_ = at;
+    return "";
+}
+
+CountComputer *CorrectComputer::new_counter(bool support) {
+    CountComputer *c = new CountComputer(in_path_kmer_, ".", ksize_);
+    c->set_threads(threads_);
+    c->set_max_memory(memory_ceil_gb_);
+    c->set_device(device_);
+    c->set_histo(0, true);  // no kmers.histo and no kmers.counts: the table is only looked up
+    c->set_pass_hook([this, support](uint32_t pass, uint32_t passes, kt_ctr *t) { return table_pass(support, pass, passes, t); });
+    return c;
+}
+
+std::string CorrectComputer::correct() {
+    delete ctr_;
+    ctr_ = nullptr;
+    acc_prof_.clear();
+    acc_prof_.shrink_to_fit();
+    acc_sup_.clear();
+    acc_sup_.shrink_to_fit();
+    acc_reads_ = 0;
+    ctr_ = new_counter(false);
+    if (std::string e = ctr_->count(); !e.empty()) return e;
+    const bool resident = ctr_->passes() == 1;
+    if (resident && !ctr_->table()) return "correct: no table";
+    if (!resident) {  // the profile is complete: the tables once more, for the supports
+        delete ctr_;
+        ctr_ = nullptr;
+        acc_sup_.assign(acc_prof_.size(), 0u);
+        ctr_ = new_counter(true);
+        if (std::string e = ctr_->count(); !e.empty()) return e;
+        if (ctr_->passes() == 1) return "correct: the table fitted the second time only";
+    }
+    kt_ctx *ctx = ctr_->context();
+    if (!ctx) return "correct: no device context";
+    const bool fastq = format_from_path(in_path_) == SeqFormat::Fastq;
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    FILE *out = fopen(out_path_.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + out_path_;
+    PhaseTimer pt("correct");
+    Lap lap;
+    Batch b;
+    std::string text, err;
+    std::vector<uint32_t> prof, sup, ns, na;
+    std::vector<uint8_t> fixed;
+    uint64_t at = 0, base = 0;
+    uint64_t reads_corrected = 0, bases_corrected = 0, ambiguous = 0, over_limit = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
+        pt.t[0] += lap();
+        const uint64_t n = b.n_reads();
+        if (n) {
+            const uint64_t total = b.offsets[n];
+            const uint32_t *s;
+            if (resident) {
+                prof.assign(total, KT_NO_KMER);
+                sup.assign(total, 0u);
+                if (total && (kt_ctr_profile(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), KT_MEM_HOST, 1, 0) != KT_OK ||
+                              kt_ctr_correct_support(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), min_count_, max_count_,
+                                                     sup.data(), KT_MEM_HOST, 1, 0) != KT_OK)) {
+                    err = kt_last_error();
+                    break;
+                }
+                s = sup.data();
+            } else {
+                if (at + n > acc_reads_ || base + total > acc_sup_.size()) {
+                    err = "correct: the input changed between the passes";
+                    break;
+                }
+                s = acc_sup_.data() + base;
+            }
+            fixed.resize(total);
+            ns.resize(n);
+            na.resize(n);
+            if (kt_correct_apply(ctx, bases_ptr(b), b.offsets.data(), n, s, min_support_, max_corrections_, fixed.data(), ns.data(),
+                                 na.data(), KT_MEM_HOST) != KT_OK) {
+                err = kt_last_error();
+                break;
+            }
+            pt.t[1] += lap();
+            text.clear();
+            for (uint64_t i = 0; i < n; i++) {
+                const uint64_t o = b.offsets[i], len = b.offsets[i + 1] - o;
+                ambiguous += na[i];
+                if (max_corrections_ && ns[i] > max_corrections_) over_limit++;
+                else if (ns[i]) reads_corrected++, bases_corrected += ns[i];
+                text += fastq ? '@' : '>';
+                text += b.headers[i];
+                text += '\n';
+                text.append((const char *)fixed.data() + o, len);
+                text += '\n';
+                if (fastq) {
+                    text += "+\n";
+                    text.append((const char *)b.quals.data() + o, len);
+                    text += '\n';
+                }
+            }
+            pt.t[2] += lap();
+            if (fwrite(text.data(), 1, text.size(), out) != text.size()) {
+                err = "Unable to write to file: " + out_path_;
+                break;
+            }
+            pt.t[3] += lap();
+            at += n;
+            base += total;
+        }
+        if (!more) break;
+    }
+    if (err.empty() && reader.failed()) err = reader.error();
+    if (err.empty() && !resident && (at != acc_reads_ || base != acc_sup_.size())) err = "correct: the input changed between the passes";
+    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path_;
+    if (err.empty() && !stats_path_.empty()) {
+        FILE *fs = fopen(stats_path_.c_str(), "wb");
+        if (!fs) return "Unable to write to file: " + stats_path_;
+        const int w = fprintf(fs, "reads\t%llu\nbases\t%llu\nreads_corrected\t%llu\nbases_corrected\t%llu\npositions_ambiguous\t%llu\n"
+                                  "reads_over_limit\t%llu\n",
+                              (unsigned long long)at, (unsigned long long)base, (unsigned long long)reads_corrected,
+                              (unsigned long long)bases_corrected, (unsigned long long)ambiguous, (unsigned long long)over_limit);
+        if ((fclose(fs) != 0 || w < 0) && err.empty()) err = "Unable to write to file: " + stats_path_;
+    }
+    return err;
+}
+
+// ---------------------------------------------------------------------------------------------
 CompareComputer::CompareComputer(std::string in_a, std::string in_b, std::string out_dir, int ksize)
     : in_a_(std::move(in_a)), in_b_(std::move(in_b)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
 

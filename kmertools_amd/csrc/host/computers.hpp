@@ -223,6 +223,43 @@ class FilterComputer {
     void emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const;
 };
 
+// `correct`: repairs substitution errors of reads from the solid k-mers of a counted table (k-mer spectrum correction; what
+// Musket, Lighter and BFC do on the CPU) instead of cutting the read as `filter --trim` does.  The table is counted from
+// kmer_path (default: the input) as by CountComputer; per batch the positions' counts (kt_ctr_profile) say which bases lie in
+// a solid k-mer, the others get their candidates' support (kt_ctr_correct_support) and the decision (kt_correct_apply).
+// EVERY record is written, in the input's format and order (FASTA: header line + the sequence on one line; FASTQ: header,
+// sequence, "+", quality unchanged).  Out of core the pass loop runs twice - the support needs the COMPLETE profile -: the
+// first count fills the per-base counts of the whole input on the host, the second the per-base supports (8 bytes per base
+// together; refused when more than the memory ceiling), and the decision runs batch by batch at the end.
+class CorrectComputer {
+  public:
+    CorrectComputer(std::string in_path, std::string out_path, int ksize);
+    ~CorrectComputer();
+    CorrectComputer(const CorrectComputer &) = delete;
+    CorrectComputer &operator=(const CorrectComputer &) = delete;
+    void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    void set_count_range(uint32_t lo, uint32_t hi) { min_count_ = lo, max_count_ = hi; }
+    void set_min_support(uint32_t s) { min_support_ = s; }
+    void set_max_corrections(uint32_t n) { max_corrections_ = n; }  // 0: no limit
+    void set_stats_path(std::string p) { stats_path_ = std::move(p); }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }
+    void set_device(int d) { device_ = d; }
+    std::string correct();  // "" or the error message
+
+  private:
+    std::string in_path_, in_path_kmer_, out_path_, stats_path_;
+    int ksize_, threads_ = 0, device_ = 0;
+    uint32_t min_count_ = 2, max_count_ = 0xFFFFFFFFu, min_support_ = 1, max_corrections_ = 0;
+    double memory_ceil_gb_ = 6.0;
+    CountComputer *ctr_ = nullptr;
+    // out of core: the whole input's per-base counts (first pass loop) and supports (second), filled as each pass's table is complete
+    std::vector<uint32_t> acc_prof_, acc_sup_;
+    uint64_t acc_reads_ = 0;
+    std::string table_pass(bool support, uint32_t pass, uint32_t passes, kt_ctr *table);
+    CountComputer *new_counter(bool support);
+};
+
 // `profile`: how often every position of the input's sequences occurs in a counted sample (KAT sect, jellyfish query -s)
 // and each sequence's k-mers, present k-mers, min / median / mean / max count (the median: element n / 2 of the sorted
 // counts, khmer's get_median_count).  The table is counted from kmer_path (default: the input) as by CountComputer; every

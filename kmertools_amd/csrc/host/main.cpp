@@ -131,6 +131,7 @@ const char *HELP_MAIN =
     "  min     Bin reads using minimisers\n"
     "  ctr     Count k-mers\n"
     "  filter  Drop or trim reads by the abundance of their k-mers\n"
+    "  correct Repair read errors from the solid k-mers of the table\n"
     "  compare Compare the k-mer counts of two inputs (matrix and set similarity)\n"
     "  profile Per-position k-mer counts and per-sequence min / median / mean / max\n"
     "  setop   Intersect, subtract, union or xor the k-mer sets of two inputs\n"
@@ -469,6 +470,76 @@ int cmd_filter(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_CORRECT =
+    "Repair read errors from the solid k-mers of the table\n\n"
+    "A k-mer is solid when min-count <= its count <= max-count in the table counted from --alt-input (default: the\n"
+    "input).  A base that lies in a solid k-mer of its read is trusted.  Any other base is rewritten when exactly one\n"
+    "other nucleotide there makes at least min-support of the k-mers over it solid; a base with several such nucleotides\n"
+    "is left alone, and so is a read that would need more than max-corrections repairs.  Substitutions only, decided\n"
+    "from the uncorrected read; two errors closer than k with no solid k-mer between them stay.  Every record is\n"
+    "written, in the input's format and order, uncompressed (FASTA: the sequence on one line; FASTQ: qualities unchanged).\n"
+    "When the table does not fit the device memory it is counted in several passes, twice over; per-base counts and\n"
+    "supports of the whole input (8 bytes per base) are then kept in host memory - refused when larger than --memory.\n\n"
+    "Usage: kmertools correct [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path (reads to correct)\n"
+    "  -o, --output <OUTPUT>        Output file path (every read, repaired where possible)\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "  -a, --alt-input <ALT_INPUT>  Input file path, for k-mer counting [default: the input]\n"
+    "      --min-count <N>          Lowest count of a solid k-mer [default: 2]\n"
+    "      --max-count <N>          Highest count of a solid k-mer [default: 4294967295]\n"
+    "      --min-support <N>        Solid k-mers a replacement must make, 1..255 [default: 1]\n"
+    "      --max-corrections <N>    Leave a read with more repairable bases than this as it is, 0 = no limit [default: 0]\n"
+    "      --stats <FILE>           Write reads, bases, reads_corrected, bases_corrected, positions_ambiguous and\n"
+    "                               reads_over_limit as name<TAB>value lines\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (the table lives in HBM; bounds the per-base arrays\n"
+    "                               kept across the passes of an out-of-core count)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_correct(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},       {'o', "output", true},          {'k', "k-size", true},
+                                     {'a', "alt-input", true},   {0, "min-count", true},         {0, "max-count", true},
+                                     {0, "min-support", true},   {0, "max-corrections", true},   {0, "stats", true},
+                                     {'m', "memory", true},      {'t', "threads", true},         {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_CORRECT);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work
+    const uint64_t min_count = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 2);
+    const uint64_t max_count = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (min_count > max_count)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(min_count) + " is greater than " +
+                    std::to_string(max_count));
+    const uint64_t min_support = ranged(f, "min-support", 1, 255, false, 1);
+    const uint64_t max_corrections = ranged(f, "max-corrections", 0, 0xFFFFFFFFull, false, 0);
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : {in, kin}) {
+        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    CorrectComputer cor(in, out, k);
+    if (threads > 0) cor.set_threads(threads);
+    cor.set_kmer_path(kin);
+    cor.set_count_range((uint32_t)min_count, (uint32_t)max_count);
+    cor.set_min_support((uint32_t)min_support);
+    cor.set_max_corrections((uint32_t)max_corrections);
+    if (f.count("stats")) cor.set_stats_path(f.at("stats"));
+    cor.set_max_memory((double)mem);
+    cor.set_device(device);
+    if (std::string e = cor.correct(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 const char *HELP_COMPARE =
     "Compare the k-mer counts of two inputs (matrix and set similarity)\n\n"
     "Counts the canonical k-mers of both inputs and writes {output}/compare.matrix: line r (r = 0..max-a) holds max-b + 1\n"
@@ -798,6 +869,7 @@ int main(int argc, char **argv) {
     if (cmd == "cov") return cmd_cov(argc, argv, 2);
     if (cmd == "min") return cmd_min(argc, argv, 2);
     if (cmd == "filter") return cmd_filter(argc, argv, 2);
+    if (cmd == "correct") return cmd_correct(argc, argv, 2);
     if (cmd == "compare") return cmd_compare(argc, argv, 2);
     if (cmd == "profile") return cmd_profile(argc, argv, 2);
     if (cmd == "setop") return cmd_setop(argc, argv, 2);

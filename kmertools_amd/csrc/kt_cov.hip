@@ -30,6 +30,8 @@ namespace {
 using ktseg::SegArgs;
 using ktseg::SegShared;
 using kttab::Slot;
+using kttab::load_slot;
+using kttab::resolve_count;
 
 constexpr int BLOCK = ktseg::BLOCK;
 constexpr uint32_t GROUP = KT_COV_GROUP;  // table probes in flight per thread
@@ -44,27 +46,6 @@ struct CovArgs {
     uint32_t n_parts, part;  // n_parts > 1: only the k-mers of hash partition `part` are binned (kt_cov_batch_part)
     uint32_t shard;          // the table is a shard of a sharded table (1; 2: the first shard - see cov_kernel): the rows are summed over the shards
 };
-
-__device__ __forceinline__ uint4 load_slot(const Slot *slots, uint64_t slot) {
-    return *reinterpret_cast<const uint4 *>(slots + slot);
-}
-
-// occurrences of `key` given the already-loaded home slot `v`; walks on (round the key's range, kt_table.hpp)
-// only on a collision - the probe sequence is recomputed then, so that the common case carries no state for it
-__device__ __forceinline__ uint32_t resolve_count(const Slot *slots, const kttab::Geom &g, uint4 v, uint64_t key) {
-    uint64_t kk = ((uint64_t)v.y << 32) | v.x;
-    if (kk == key) return v.z + 1u;  // stored value is occurrences - 1
-    if (kk == KT_EMPTY_KEY) return 0u;
-    kttab::Probe p = kttab::probe_of(key, g);
-    for (uint32_t probe = 1; probe < p.rs; probe++) {
-        p.next();
-        v = load_slot(slots, p.slot());
-        kk = ((uint64_t)v.y << 32) | v.x;
-        if (kk == key) return v.z + 1u;
-        if (kk == KT_EMPTY_KEY) return 0u;
-    }
-    return 0u;
-}
 
 __global__ __launch_bounds__(BLOCK) void cov_kernel(SegArgs a, CovArgs c) {
     __shared__ SegShared sm;

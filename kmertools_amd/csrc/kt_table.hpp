@@ -108,6 +108,30 @@ __device__ __forceinline__ uint32_t table_add(const TableRef &t, uint64_t key, u
     return 0u;
 }
 
+#ifdef __HIPCC__
+// ---- lookups (kt_cov.hip, kt_correct.hip) ----
+__device__ __forceinline__ uint4 load_slot(const Slot *slots, uint64_t slot) {
+    return *reinterpret_cast<const uint4 *>(slots + slot);
+}
+
+// occurrences of `key` given the already-loaded home slot `v`; walks on (round the key's range, kt_table.hpp)
+// only on a collision - the probe sequence is recomputed then, so that the common case carries no state for it
+__device__ __forceinline__ uint32_t resolve_count(const Slot *slots, const kttab::Geom &g, uint4 v, uint64_t key) {
+    uint64_t kk = ((uint64_t)v.y << 32) | v.x;
+    if (kk == key) return v.z + 1u;  // stored value is occurrences - 1
+    if (kk == KT_EMPTY_KEY) return 0u;
+    kttab::Probe p = kttab::probe_of(key, g);
+    for (uint32_t probe = 1; probe < p.rs; probe++) {
+        p.next();
+        v = load_slot(slots, p.slot());
+        kk = ((uint64_t)v.y << 32) | v.x;
+        if (kk == key) return v.z + 1u;
+        if (kk == KT_EMPTY_KEY) return 0u;
+    }
+    return 0u;
+}
+#endif
+
 }  // namespace kttab
 
 // kt_bulk.hip: adds a whole read batch to the table without global atomics (partition by hash prefix, then every

@@ -326,6 +326,18 @@ class Context:
                                out["n_present"], out["min"], out["median"], out["max"], out["sum"], KT_MEM_HOST)
         return out
 
+    # -- correct: the decision over a support array (Counter.correct_support) ------------------
+    def correct_apply(self, bases, offsets, n_reads, support, min_support=1, max_corrections=0, out_bases=None,
+                      n_single=None, n_ambiguous=None, mem=KT_MEM_DEVICE):
+        """a base is single when exactly one byte of its support entry is >= min_support, ambiguous when several are:
+        n_single / n_ambiguous (u32 arrays of n_reads, overwritten) count them per read, out_bases gets "ACGT"[x] at the
+        single bases of reads with at most max_corrections of them (0: no limit) and the input byte everywhere else; any
+        of the three may be None, out_bases may be `bases` (kt_correct_apply)"""
+        check(_lib.lib().kt_correct_apply(self._h, _ptr(bases), _ptr(offsets), int(n_reads), _ptr(support),
+                                          int(min_support), int(max_corrections), _ptr(out_bases), _ptr(n_single),
+                                          _ptr(n_ambiguous), mem))
+        return out_bases, n_single, n_ambiguous
+
     def synth_reads(self, seed, n_reads, read_len, bases_dev, offsets_dev=None, noise=False, genome_len=0,
                     first_read=0):
         check(_lib.lib().kt_synth_reads(self._h, seed, first_read, n_reads, read_len, int(bool(noise)),
@@ -479,6 +491,34 @@ class Counter:
         if n > 0 and prof.size:
             self.profile(bases, offsets, n, prof, KT_MEM_HOST)
         return prof
+
+    # -- correct: repair read errors from the solid k-mers of this table ---------------------------
+    def correct_support(self, bases, offsets, n_reads, profile, min_count, max_count, support, mem=KT_MEM_DEVICE,
+                        n_parts=1, part=0):
+        """for every base that no solid window of `profile` (the complete Counter.profile of the batch) covers, adds to
+        byte x of support[base] the windows in which nucleotide x there makes a solid k-mer of hash partition `part` of
+        n_parts - a u32 array of offsets[n_reads] entries that the caller zeroed (kt_ctr_correct_support)"""
+        check(_lib.lib().kt_ctr_correct_support(self._h, _ptr(bases), _ptr(offsets), int(n_reads), _ptr(profile),
+                                                int(min_count), int(max_count), _ptr(support), mem, int(n_parts),
+                                                int(part)))
+        return support
+
+    def correct_host(self, bases, offsets, min_count=2, max_count=None, min_support=1, max_corrections=0):
+        """-> (out_bases u8, n_single u32, n_ambiguous u32): the batch with its repairable bases rewritten, and per read
+        how many bases were repairable / had several supported candidates (profile, support and apply for this table)"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        out = bases.copy()
+        ns = np.zeros(max(n, 0), np.uint32)
+        na = np.zeros(max(n, 0), np.uint32)
+        if n > 0 and bases.size:
+            hi = 0xFFFFFFFF if max_count is None else int(max_count)
+            prof = self.profile_host(bases, offsets)
+            sup = np.zeros(bases.size, np.uint32)
+            self.correct_support(bases, offsets, n, prof, min_count, hi, sup, KT_MEM_HOST)
+            self.ctx.correct_apply(bases, offsets, n, sup, min_support, max_corrections, out, ns, na, KT_MEM_HOST)
+        return out, ns, na
 
     def spectrum(self, n_bins=10001, totals=False):
         """The table's abundance spectrum (jellyfish histo): hist[c] = distinct k-mers with exactly c occurrences for
