@@ -15,11 +15,11 @@
 //                   each - so the (window, base) pairs of the segment are compacted: every thread counts the pairs of its 32
 //                   window starts from the bit masks alone, a workgroup scan numbers them, they go to an LDS list (in rounds
 //                   of LIST when a segment has more) and are dealt to the lanes, PAIRS per lane and round with all their
-//                   home-slot loads in flight together (as the GROUP loops of kt_cov.hip).  The substituted k-mer is the
+//                   home-slot loads in flight together (kttab::Probed's home, then count, as kt_cov.hip's probe_windows).  The substituted k-mer is the
 //                   window's forward / reverse word with one 2-bit field replaced.  A pair ends in one 32-bit atomic add on
 //                   support[g]: byte x gains 1 when candidate x is solid there.
 //   apply_*_kernel  the decision, streaming passes over support (+ bases): counts per read and the corrected bytes.  The
-//                   read of a base is looked up (binary search among its segment's reads) only where a candidate is supported.
+//                   read of a base is looked up (ktseg::ReadCursor) only where a candidate is supported.
 #include "kt_internal.hpp"
 #include "kt_launch.hpp"
 #include "kt_segment.hpp"
@@ -33,7 +33,6 @@ namespace {
 
 using ktseg::SegArgs;
 using ktseg::SegShared;
-using kttab::Slot;
 
 constexpr int BLOCK = ktseg::BLOCK;
 constexpr uint32_t WAVES = BLOCK / 64;
@@ -73,21 +72,12 @@ __global__ __launch_bounds__(BLOCK) void todo_kernel(SegArgs a, TodoArgs c) {
             } else {
                 for (uint32_t q = 0; q < n; q++) S |= solid_bit(c.profile[p0 + q], c) << (32 + q);
             }
-            // the read of the first base (between the segment's reads, as cov_kernel finds it), then walk forward
-            const uint64_t seg = p0 / ktseg::SEG;
-            const uint64_t r_first = a.seg_first[seg];
-            uint64_t lo = r_first ? r_first - 1 : 0, hi = a.seg_first[seg + 1];
-            while (hi - lo > 1) {
-                const uint64_t mid = (lo + hi) >> 1;
-                if (a.offsets[mid] <= p0) lo = mid; else hi = mid;
-            }
-            uint64_t rid = lo, start = a.offsets[rid], next = a.offsets[rid + 1];
+            // the read of the first base, then walk forward
+            ktseg::ReadCursor rd(a.offsets, a.seg_first, p0 / ktseg::SEG, p0);
             for (uint32_t q = 0; q < n; q++) {
                 const uint64_t g = p0 + q;
-                while (g >= next) {  // empty reads are stepped over
-                    start = next;
-                    next = a.offsets[++rid + 1];
-                }
+                rd.advance(g);
+                const uint64_t start = rd.start, next = rd.next;
                 if (next - start < k) continue;  // (a read shorter than k has no window: nothing to do)
                 // the windows of the read that contain g: starts [max(start, g - k + 1), min(g, next - k)]
                 uint64_t wl = g + 1 >= k ? g + 1 - k : 0;
@@ -103,12 +93,10 @@ __global__ __launch_bounds__(BLOCK) void todo_kernel(SegArgs a, TodoArgs c) {
 }
 
 struct SupportArgs {
-    const Slot *slots;
-    kttab::Geom g;
+    kttab::Probed t;                // (its hash partition: only the substituted k-mers of that one are looked at)
     const uint32_t *todo;           // todo_kernel's bits
     uint32_t min_count, max_count;  // 1 <= min_count <= max_count
     uint32_t *support;              // offsets[n_reads] entries, added into
-    uint32_t n_parts, part;         // only the substituted k-mers of hash partition `part` are looked at
 };
 
 __global__ __launch_bounds__(BLOCK) void support_kernel(SegArgs a, SupportArgs c) {
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(BLOCK) void support_kernel(SegArgs a, SupportArgs c
                         const uint32_t x = bad ? t : (code[u] + 1u + t) & 3u;
                         const uint64_t fx = f0[u] | ((uint64_t)x << sf), rx = r0w[u] | ((uint64_t)(3u - x) << sr);
                         key[u][t] = fx < rx ? fx : rx;
-                        v[u][t] = kttab::load_slot(c.slots, kttab::probe_of(key[u][t], c.g).slot());
+                        v[u][t] = c.t.home(key[u][t]);
                     }
                 }
 #pragma unroll
@@ -206,8 +194,8 @@ __global__ __launch_bounds__(BLOCK) void support_kernel(SegArgs a, SupportArgs c
                     const uint32_t j = e[u] >> 5, d = e[u] & 31u;
                     uint32_t inc = 0;
                     auto solid = [&](uint64_t key_x, uint4 home) -> uint32_t {
-                        if (c.n_parts > 1 && ktd::owner_of(key_x, c.n_parts) != c.part) return 0u;
-                        const uint32_t n_occ = kttab::resolve_count(c.slots, c.g, home, key_x);
+                        if (!c.t.mine(key_x)) return 0u;
+                        const uint32_t n_occ = c.t.count(home, key_x);
                         return (n_occ >= c.min_count && n_occ <= c.max_count) ? 1u : 0u;
                     };
 #pragma unroll
@@ -219,7 +207,7 @@ __global__ __launch_bounds__(BLOCK) void support_kernel(SegArgs a, SupportArgs c
                         const uint32_t sf = 2u * (k - 1u - d);
                         const uint64_t fx = f0[u] | (3ull << sf), rx = r0w[u];
                         const uint64_t key_x = fx < rx ? fx : rx;
-                        inc |= solid(key_x, kttab::load_slot(c.slots, kttab::probe_of(key_x, c.g).slot())) << 24;
+                        inc |= solid(key_x, c.t.home(key_x)) << 24;
                     }
                     const uint64_t pos = B0 + j + d;
                     if (inc && pos < total) atomicAdd(&c.support[pos], inc);
@@ -253,17 +241,9 @@ __device__ __forceinline__ uint32_t decide(uint32_t s, uint32_t min_support) {
     return (m & (m - 1u)) ? 5u : 1u + (uint32_t)__builtin_ctz(m);
 }
 
-// the read that holds base g < offsets[n_reads] (empty reads hold nothing): searched between the reads of g's segment, as
-// cov_kernel finds a thread's first read - six steps for 150-base reads, not the 24 of a search in all the offsets
+// the read that holds base g < offsets[n_reads] (empty reads hold nothing)
 __device__ __forceinline__ uint64_t read_of(const ApplyArgs &a, uint64_t g) {
-    const uint64_t seg = g / ktseg::SEG;
-    const uint64_t r_first = a.seg_first[seg];
-    uint64_t lo = r_first ? r_first - 1 : 0, hi = a.seg_first[seg + 1];  // offsets[lo] <= g < offsets[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a.offsets[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
+    return ktseg::ReadCursor(a.offsets, a.seg_first, g / ktseg::SEG, g).rid;
 }
 
 // n_single[i] / n_ambiguous[i] += the single / ambiguous bases of read i.  One base per lane; a wave whose decided bases all lie
@@ -346,7 +326,7 @@ static int support_device(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, co
     TodoArgs t{d_profile, min_count, max_count, d_todo, n_words};
     hipLaunchKernelGGL(todo_kernel, dim3(grid_for(ctx, (n_words + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream, a, t);
     KT_HIP(hipGetLastError());
-    SupportArgs c{(const Slot *)table->slots, ktl::geom_of(table), d_todo, min_count, max_count, d_support, n_parts, part};
+    SupportArgs c{probed_of(table, n_parts, part), d_todo, min_count, max_count, d_support};
     hipLaunchKernelGGL(support_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
     KT_HIP(hipGetLastError());
     return KT_OK;

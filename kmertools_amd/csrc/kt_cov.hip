@@ -6,16 +6,16 @@
 // re-reads kmers.counts into a host HashMap; here the table built by kt_ctr_add_reads is
 // probed where it lies.  HBM-bound random 16-byte reads; no MFMA.
 //
-// Same segment front-end as the counting kernels.  A thread walks its 32 window starts in groups:
+// Same segment front-end as the counting kernels.  A thread walks its 32 window starts in groups (probe_windows):
 // generate GROUP canonical k-mers, issue their home-slot loads together, then add into a per-segment LDS image
 // of the bin rows of the reads that touch the segment (row = read id - first read of the
 // segment); the image is flushed with one global atomic per non-zero cell, so a read that
 // straddles segments is still summed exactly.  Segments made of very many tiny reads (image
 // larger than the LDS budget) add to global memory directly.
 //
-// The read filter's kt_ctr_read_solidity walks and probes the same way and keeps three numbers per read (solidity_kernel).
-// kt_ctr_profile walks and probes the same way again and keeps the count itself, one u32 per window start (profile_kernel);
-// what is made of those per read - the median among them - is kt_profile.hip's.
+// The read filter's kt_ctr_read_solidity keeps three numbers per read instead (solidity_kernel), kt_ctr_profile the count
+// itself, one u32 per window start (profile_kernel); what is made of those per read - the median among them - is
+// kt_profile.hip's.
 #include "kt_internal.hpp"
 #include "kt_launch.hpp"
 #include "kt_segment.hpp"
@@ -29,22 +29,40 @@ namespace {
 
 using ktseg::SegArgs;
 using ktseg::SegShared;
-using kttab::Slot;
-using kttab::load_slot;
-using kttab::resolve_count;
+using kttab::Probed;
 
 constexpr int BLOCK = ktseg::BLOCK;
 constexpr uint32_t GROUP = KT_COV_GROUP;  // table probes in flight per thread
 constexpr uint32_t ROWS_LDS = 6144;  // u32 cells of bin rows staged per segment (24 KB)
 
+// The probe pipeline over a thread's 32 window starts of a staged segment, GROUP at a time (rolled, so the k-mers never sit
+// in registers all at once): the group's canonical k-mers, the home-slot loads of those that are k-mers (w.okm) of the
+// table's hash partition in flight together, then sink(jj, wr, cnt): bit u of `wr` = window start jj + u was looked up,
+// cnt[u] = its occurrences (0: absent).
+template <class Sink>
+__device__ __forceinline__ void probe_windows(const Probed &t, ktseg::Window &w, Sink &&sink) {
+#pragma unroll 1
+    for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
+        uint64_t key[GROUP];
+        uint32_t cnt[GROUP] = {};
+        uint32_t wr = (w.okm >> jj) & ((1u << GROUP) - 1u);
+#pragma unroll
+        for (uint32_t u = 0; u < GROUP; u++) {
+            key[u] = w.f < w.r ? w.f : w.r;
+            w.step();
+            if (!t.mine(key[u])) wr &= ~(1u << u);
+        }
+        t.counts(key, wr, [&](uint32_t u, uint32_t n) { cnt[u] = n; });
+        sink(jj, wr, cnt);
+    }
+}
+
 struct CovArgs {
-    const Slot *slots;
-    kttab::Geom g;       // capacity and hash -> home slot mapping
+    Probed t;
     uint32_t bin_size;   // 0 = wider than any u32 count: every k-mer falls in bin 0
     uint32_t bin_count;
     uint32_t *counts;    // n_reads x bin_count, zeroed
-    uint32_t n_parts, part;  // n_parts > 1: only the k-mers of hash partition `part` are binned (kt_cov_batch_part)
-    uint32_t shard;          // the table is a shard of a sharded table (1; 2: the first shard - see cov_kernel): the rows are summed over the shards
+    uint32_t shard;      // the table is a shard of a sharded table (1; 2: the first shard - see cov_kernel): the rows are summed over the shards
 };
 
 __global__ __launch_bounds__(BLOCK) void cov_kernel(SegArgs a, CovArgs c) {
@@ -57,55 +75,29 @@ __global__ __launch_bounds__(BLOCK) void cov_kernel(SegArgs a, CovArgs c) {
     for (uint64_t g = blockIdx.x; g < a.n_seg; g += gridDim.x) {
         ktseg::stage_segment(a, g, sm);  // its barriers also order the rows[] zeroing
         ktseg::Window w(sm, tid, a.k);
-        uint32_t ok = 0;
-        for (uint32_t j = 0; j < ktseg::PER_THREAD; j++) ok |= (w.ok(j) ? 1u : 0u) << j;
 
         // reads that can own a k-mer starting in this segment: [rbase, r_hi)
-        const uint64_t B0 = g * ktseg::SEG;
         const uint64_t r_first = a.seg_first[g];
         const uint64_t r_hi = a.seg_first[g + 1];
-        const uint64_t rbase = r_first ? r_first - 1 : 0;  // offsets[rbase] <= B0
+        const uint64_t rbase = r_first ? r_first - 1 : 0;  // offsets[rbase] <= g * SEG
         const uint64_t cells = (r_hi - rbase) * (uint64_t)c.bin_count;
         const bool in_lds = cells <= ROWS_LDS;
 
-        if (ok) {
-            // read id of the thread's first valid window start, then walk forward
-            const uint64_t s0 = B0 + (uint64_t)ktseg::PER_THREAD * tid;
-            uint64_t lo = rbase, hi = r_hi;
-            {
-                const uint64_t s = s0 + (uint32_t)__builtin_ctz(ok);
-                while (hi - lo > 1) {
-                    const uint64_t mid = (lo + hi) >> 1;
-                    if (a.offsets[mid] <= s) lo = mid; else hi = mid;
-                }
-            }
-            uint64_t rid = lo;
-            uint64_t next = a.offsets[rid + 1];
-            // GROUP probes in flight per thread; rolled so the k-mers never sit in registers all at once
-#pragma unroll 1
-            for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
-                uint64_t key[GROUP];
-                uint4 v[GROUP];
+        if (w.okm) {
+            // the read of the thread's first valid window start, then walk forward
+            const uint64_t s0 = g * ktseg::SEG + (uint64_t)ktseg::PER_THREAD * tid;
+            ktseg::ReadCursor rd(a.offsets, a.seg_first, g, s0 + (uint32_t)__builtin_ctz(w.okm));
+            auto add = [&](uint32_t b, uint32_t n) {
+                if (in_lds) atomicAdd(&rows[(uint32_t)(rd.rid - rbase) * c.bin_count + b], n);
+                else atomicAdd(&c.counts[rd.rid * c.bin_count + b], n);
+            };
+            probe_windows(c.t, w, [&](uint32_t jj, uint32_t wr, const uint32_t (&cnt)[GROUP]) {
 #pragma unroll
                 for (uint32_t u = 0; u < GROUP; u++) {
-                    key[u] = w.f < w.r ? w.f : w.r;
-                    w.step();
-                    v[u] = load_slot(c.slots, kttab::probe_of(key[u], c.g).slot());
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < GROUP; u++) {
-                    if (!((ok >> (jj + u)) & 1u)) continue;
-                    // (a k-mer that another pass / another shard answers for is not "absent" here: it is skipped)
-                    if (c.n_parts > 1 && ktd::owner_of(key[u], c.n_parts) != c.part) continue;
-                    const uint32_t cnt = resolve_count(c.slots, c.g, v[u], key[u]);
-                    uint32_t bin = c.bin_size ? cnt / c.bin_size : 0u;  // coverage/src/lib.rs:172
-                    bin = bin < last_bin ? bin : last_bin;              // :173
-                    const uint64_t s = s0 + jj + u;
-                    while (s >= next) next = a.offsets[++rid + 1];      // empty reads are stepped over
-                    auto add = [&](uint32_t b, uint32_t n) {
-                        if (in_lds) atomicAdd(&rows[(uint32_t)(rid - rbase) * c.bin_count + b], n);
-                        else atomicAdd(&c.counts[rid * c.bin_count + b], n);
-                    };
+                    if (!((wr >> u) & 1u)) continue;
+                    uint32_t bin = c.bin_size ? cnt[u] / c.bin_size : 0u;  // coverage/src/lib.rs:172
+                    bin = bin < last_bin ? bin : last_bin;                 // :173
+                    rd.advance(s0 + jj + u);
                     if (!c.shard) {
                         add(bin, 1u);
                     } else {
@@ -114,13 +106,13 @@ __global__ __launch_bounds__(BLOCK) void cov_kernel(SegArgs a, CovArgs c) {
                         // absent everywhere); the one shard that holds a k-mer moves it from there to its bin.  The shards'
                         // rows, summed modulo 2^32 (u32 cells), are the rows of the whole table.
                         if (c.shard == 2u) add(0u, 1u);
-                        if (cnt && bin) {
+                        if (cnt[u] && bin) {
                             add(bin, 1u);
                             add(0u, 0xFFFFFFFFu);
                         }
                     }
                 }
-            }
+            });
         }
         __syncthreads();  // sm is restaged by the next segment; rows[] is complete
         if (in_lds) {
@@ -137,29 +129,17 @@ __global__ __launch_bounds__(BLOCK) void cov_kernel(SegArgs a, CovArgs c) {
 }
 
 // occurrences of keys[i] in the table (0: absent), one thread per key
-__global__ __launch_bounds__(BLOCK) void lookup_kernel(const Slot *__restrict__ slots, kttab::Geom g, const uint64_t *__restrict__ keys,
-                                                       uint64_t n, uint32_t *__restrict__ out) {
+__global__ __launch_bounds__(BLOCK) void lookup_kernel(Probed t, const uint64_t *__restrict__ keys, uint64_t n,
+                                                       uint32_t *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) {
         const uint64_t key = keys[i];
-        kttab::Probe p = kttab::probe_of(key, g);
-        uint32_t cnt = 0;
-        for (uint32_t probe = 0; probe < p.rs; probe++) {
-            const uint4 v = load_slot(slots, p.slot());
-            const uint64_t kk = ((uint64_t)v.y << 32) | v.x;
-            if (kk == key) {
-                cnt = v.z + 1u;
-                break;
-            }
-            if (kk == KT_EMPTY_KEY) break;
-            p.next();
-        }
-        out[i] = key == KT_EMPTY_KEY ? 0u : cnt;
+        out[i] = key == KT_EMPTY_KEY ? 0u : t.count(t.home(key), key);
     }
 }
 
 // ---- per-read k-mer solidity (kt_ctr_read_solidity: the read filter) ------------------------------------------------
-// cov_kernel's walk and probes; per read only three numbers, each combining with an add or a min: the k-mers, the solid
-// ones (min_count <= count <= max_count) and the start in the read of the first weak one.  A thread's 32 window starts
+// Per read only three numbers, each combining with an add or a min: the k-mers, the solid ones (min_count <= count <=
+// max_count) and the start in the read of the first weak one.  A thread's 32 window starts
 // are consecutive, so it keeps a running (read, n, solid, first weak) in registers and flushes it when the read changes
 // and at the end - one flush per read boundary, not one per k-mer.  A flush goes to a per-segment LDS image of the
 // segment's reads (3 cells per read: add, add, min), which is flushed with one global atomic per non-default cell.  A
@@ -168,11 +148,9 @@ constexpr uint32_t READS_LDS = 256;
 constexpr uint32_t NO_POS = 0xFFFFFFFFu;
 
 struct SolidArgs {
-    const Slot *slots;
-    kttab::Geom g;
+    Probed t;
     uint32_t min_count, max_count;  // 1 <= min_count <= max_count: an absent k-mer (count 0) is weak
     uint32_t *n_kmers, *n_solid, *first_weak;  // n_reads each, combined into (first_weak only when FIRST)
-    uint32_t n_parts, part;  // only the k-mers of hash partition `part` are looked at
 };
 
 template <bool FIRST>
@@ -189,29 +167,17 @@ __global__ __launch_bounds__(BLOCK) void solidity_kernel(SegArgs a, SolidArgs c)
     for (uint64_t g = blockIdx.x; g < a.n_seg; g += gridDim.x) {
         ktseg::stage_segment(a, g, sm);  // its barriers also order the image's initialisation / reset
         ktseg::Window w(sm, tid, a.k);
-        uint32_t ok = 0;
-        for (uint32_t j = 0; j < ktseg::PER_THREAD; j++) ok |= (w.ok(j) ? 1u : 0u) << j;
 
         // reads that can own a k-mer starting in this segment: [rbase, r_hi) (as in cov_kernel)
-        const uint64_t B0 = g * ktseg::SEG;
         const uint64_t r_first = a.seg_first[g];
         const uint64_t r_hi = a.seg_first[g + 1];
         const uint64_t rbase = r_first ? r_first - 1 : 0;
         const uint64_t n_img = r_hi - rbase;
         const bool in_lds = n_img <= READS_LDS;
 
-        if (ok) {
-            const uint64_t s0 = B0 + (uint64_t)ktseg::PER_THREAD * tid;
-            uint64_t lo = rbase, hi = r_hi;
-            {
-                const uint64_t s = s0 + (uint32_t)__builtin_ctz(ok);
-                while (hi - lo > 1) {
-                    const uint64_t mid = (lo + hi) >> 1;
-                    if (a.offsets[mid] <= s) lo = mid; else hi = mid;
-                }
-            }
-            uint64_t rid = lo;
-            uint64_t start = a.offsets[rid], next = a.offsets[rid + 1];
+        if (w.okm) {
+            const uint64_t s0 = g * ktseg::SEG + (uint64_t)ktseg::PER_THREAD * tid;
+            ktseg::ReadCursor rd(a.offsets, a.seg_first, g, s0 + (uint32_t)__builtin_ctz(w.okm));
             // the running read: `run` (~0: none yet), its k-mers, solid k-mers and first weak start seen by this thread
             uint64_t run = ~0ull;
             uint32_t n = 0, sol = 0, weak = NO_POS;
@@ -227,37 +193,23 @@ __global__ __launch_bounds__(BLOCK) void solidity_kernel(SegArgs a, SolidArgs c)
                     if (FIRST && weak != NO_POS) atomicMin(&c.first_weak[run], weak);
                 }
             };
-#pragma unroll 1
-            for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
-                uint64_t key[GROUP];
-                uint4 v[GROUP];
+            probe_windows(c.t, w, [&](uint32_t jj, uint32_t wr, const uint32_t (&cnt)[GROUP]) {
 #pragma unroll
                 for (uint32_t u = 0; u < GROUP; u++) {
-                    key[u] = w.f < w.r ? w.f : w.r;
-                    w.step();
-                    v[u] = load_slot(c.slots, kttab::probe_of(key[u], c.g).slot());
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < GROUP; u++) {
-                    if (!((ok >> (jj + u)) & 1u)) continue;
-                    if (c.n_parts > 1 && ktd::owner_of(key[u], c.n_parts) != c.part) continue;
-                    const uint32_t cnt = resolve_count(c.slots, c.g, v[u], key[u]);
+                    if (!((wr >> u) & 1u)) continue;
                     const uint64_t s = s0 + jj + u;
-                    while (s >= next) {  // empty reads are stepped over
-                        start = next;
-                        next = a.offsets[++rid + 1];
-                    }
-                    if (rid != run) {
+                    rd.advance(s);
+                    if (rd.rid != run) {
                         if (run != ~0ull) flush();
-                        run = rid;
+                        run = rd.rid;
                         n = sol = 0;
                         weak = NO_POS;
                     }
                     n++;
-                    if (cnt >= c.min_count && cnt <= c.max_count) sol++;
-                    else if (FIRST && weak == NO_POS) weak = (uint32_t)(s - start);  // starts ascend: the first is the least
+                    if (cnt[u] >= c.min_count && cnt[u] <= c.max_count) sol++;
+                    else if (FIRST && weak == NO_POS) weak = (uint32_t)(s - rd.start);  // starts ascend: the first is the least
                 }
-            }
+            });
             if (run != ~0ull) flush();
         }
         __syncthreads();  // sm is restaged by the next segment; the image is complete
@@ -290,15 +242,13 @@ __global__ __launch_bounds__(BLOCK) void long_read_kernel(const uint64_t *__rest
 }
 
 // ---- per-position k-mer counts (kt_ctr_profile) --------------------------------------------------------------------
-// solidity_kernel's walk and probes with the simplest sink there is: the count of the window that starts at global base s
-// goes to profile[s] - no read lookup, no LDS image, nothing combined.  Only the valid windows of this hash partition are
-// stored (the caller's fill stays everywhere else), so the thread's 32 consecutive entries go out as they are resolved: four
-// at a time as one 16-byte store where all four are written and the array is 16-byte aligned, one by one otherwise.
+// The simplest sink there is: the count of the window that starts at global base s goes to profile[s] - no read lookup, no
+// LDS image, nothing combined.  Only the valid windows of this hash partition are stored (the caller's fill stays everywhere
+// else), so the thread's 32 consecutive entries go out group by group: four at a time as one 16-byte store where all four
+// are written and the array is 16-byte aligned, one by one otherwise.
 struct ProfileArgs {
-    const Slot *slots;
-    kttab::Geom g;
-    uint32_t *profile;       // offsets[n_reads] entries, indexed by global base index
-    uint32_t n_parts, part;  // only the k-mers of hash partition `part` are written
+    Probed t;
+    uint32_t *profile;  // offsets[n_reads] entries, indexed by global base index
 };
 
 __global__ __launch_bounds__(BLOCK) void profile_kernel(SegArgs a, ProfileArgs c) {
@@ -309,46 +259,23 @@ __global__ __launch_bounds__(BLOCK) void profile_kernel(SegArgs a, ProfileArgs c
     for (uint64_t g = blockIdx.x; g < a.n_seg; g += gridDim.x) {
         ktseg::stage_segment(a, g, sm);
         ktseg::Window w(sm, tid, a.k);
-        uint32_t ok = 0;
-        for (uint32_t j = 0; j < ktseg::PER_THREAD; j++) ok |= (w.ok(j) ? 1u : 0u) << j;
-        if (ok) {
+        if (w.okm) {
             // (a valid window lies inside the batch, so every entry written is below offsets[n_reads])
             uint32_t *dst = c.profile + g * ktseg::SEG + (uint64_t)ktseg::PER_THREAD * tid;
-#pragma unroll 1
-            for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
-                uint64_t key[GROUP];
-                uint4 v[GROUP];
-#pragma unroll
-                for (uint32_t u = 0; u < GROUP; u++) {
-                    key[u] = w.f < w.r ? w.f : w.r;
-                    w.step();
-                    v[u] = load_slot(c.slots, kttab::probe_of(key[u], c.g).slot());
-                }
-                uint32_t cnt[GROUP];
-                uint32_t wr = (ok >> jj) & ((1u << GROUP) - 1u);
-#pragma unroll
-                for (uint32_t u = 0; u < GROUP; u++) {
-                    cnt[u] = 0;
-                    if (!((wr >> u) & 1u)) continue;
-                    if (c.n_parts > 1 && ktd::owner_of(key[u], c.n_parts) != c.part) {
-                        wr &= ~(1u << u);
-                        continue;
-                    }
-                    const uint32_t n = resolve_count(c.slots, c.g, v[u], key[u]);
-                    cnt[u] = n < KT_NO_KMER ? n : KT_NO_KMER - 1u;  // (the sentinel is no count)
-                }
+            probe_windows(c.t, w, [&](uint32_t jj, uint32_t wr, const uint32_t (&cnt)[GROUP]) {
+                auto capped = [&](uint32_t u) { return cnt[u] < KT_NO_KMER ? cnt[u] : KT_NO_KMER - 1u; };  // (the sentinel is no count)
 #pragma unroll
                 for (uint32_t q = 0; q < GROUP; q += 4) {
                     const uint32_t m = (wr >> q) & 15u;
                     if (m == 15u && aligned) {
-                        *reinterpret_cast<uint4 *>(dst + jj + q) = make_uint4(cnt[q], cnt[q + 1], cnt[q + 2], cnt[q + 3]);
+                        *reinterpret_cast<uint4 *>(dst + jj + q) = make_uint4(capped(q), capped(q + 1), capped(q + 2), capped(q + 3));
                     } else {
 #pragma unroll
                         for (uint32_t u = 0; u < 4; u++)
-                            if ((m >> u) & 1u) dst[jj + q + u] = cnt[q + u];
+                            if ((m >> u) & 1u) dst[jj + q + u] = capped(q + u);
                     }
                 }
-            }
+            });
         }
         __syncthreads();  // sm is restaged by the next segment
     }
@@ -405,8 +332,8 @@ static int cov_counts(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, const 
     if (!total) return KT_OK;
     SegArgs a;
     if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
-    CovArgs c{(const Slot *)table->slots, ktl::geom_of(table), bin_size > 0xFFFFFFFFull ? 0u : (uint32_t)bin_size,
-              (uint32_t)bin_count, d_counts, n_parts, part, table->n_owners > 1 ? (table->owner == 0 ? 2u : 1u) : 0u};
+    CovArgs c{probed_of(table, n_parts, part), bin_size > 0xFFFFFFFFull ? 0u : (uint32_t)bin_size, (uint32_t)bin_count, d_counts,
+              table->n_owners > 1 ? (table->owner == 0 ? 2u : 1u) : 0u};
     hipLaunchKernelGGL(cov_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
     KT_HIP(hipGetLastError());
     return KT_OK;
@@ -468,7 +395,7 @@ extern "C" int kt_ctr_lookup(kt_ctr *table, const uint64_t *keys, uint64_t n, ui
         d_counts = (uint32_t *)ctx->s_aux2.p;
     }
     hipLaunchKernelGGL(lookup_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
-                       (const Slot *)table->slots, ktl::geom_of(table), d_keys, n, d_counts);
+                       probed_of(table), d_keys, n, d_counts);
     KT_HIP(hipGetLastError());
     if (mem == KT_MEM_HOST) {
         KT_HIP(hipMemcpyAsync(counts, d_counts, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -539,7 +466,7 @@ static int solidity_counts(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, c
     if (!total) return KT_OK;
     SegArgs a;
     if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
-    SolidArgs c{(const Slot *)table->slots, ktl::geom_of(table), min_count, max_count, d_n, d_s, d_w, n_parts, part};
+    SolidArgs c{probed_of(table, n_parts, part), min_count, max_count, d_n, d_s, d_w};
     if (d_w)
         hipLaunchKernelGGL(solidity_kernel<true>, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
     else
@@ -630,7 +557,7 @@ extern "C" int kt_ctr_profile(kt_ctr *table, const uint8_t *bases, const uint64_
     }
     SegArgs a;
     if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
-    ProfileArgs c{(const Slot *)table->slots, ktl::geom_of(table), d_profile, n_parts, part};
+    ProfileArgs c{probed_of(table, n_parts, part), d_profile};
     hipLaunchKernelGGL(profile_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
     KT_HIP(hipGetLastError());
     if (mem == KT_MEM_HOST) {

@@ -9,6 +9,7 @@
 // atomic add that counts it touch the same 64-byte line, which halves the DRAM lines moved
 // per insert compared with separate key/count arrays - profiles/r1_ctr_*).  HBM-bound
 // random access; no MFMA.
+#include <type_traits>
 #include <vector>
 
 #include "kt_internal.hpp"
@@ -84,6 +85,42 @@ __global__ __launch_bounds__(BLOCK) void table_clear_kernel(Slot *__restrict__ s
 #define KT_EXPORT_XPT 16
 #endif
 constexpr uint32_t XPT = KT_EXPORT_XPT, XTILE = BLOCK * XPT;
+
+// the tile reservation: bal[j] = the wave's ballot of the entries of load j that are kept
+struct TileShared {
+    uint32_t runs[BLOCK / 64 * XPT];  // kept entries per (wave, load), then their exclusive prefix
+    uint64_t tile_base;
+    static_assert(BLOCK / 64 * XPT == 64, "one wave scans the runs, one per lane");
+    // reserves the tile's output range at the cursor and returns its start.  Every thread of the workgroup must be here (two
+    // barriers; one more is due before the next tile's call rewrites runs[] / tile_base).
+    __device__ __forceinline__ uint64_t reserve(const uint64_t (&bal)[XPT], uint64_t *cursor) {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++)
+            if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
+        ktd::lds_barrier();
+        if (wave == 0) {  // 64 runs: one wave scans them and reserves the tile's output range
+            const uint32_t c = runs[lane];
+            uint32_t inc = c;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t u = __shfl_up(inc, off, 64);
+                if (lane >= (uint32_t)off) inc += u;
+            }
+            runs[lane] = inc - c;
+            if (lane == 63)
+                tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;
+        }
+        ktd::lds_barrier();
+        return tile_base;
+    }
+    // where this lane's kept entry of load j goes (base = what reserve returned)
+    __device__ __forceinline__ uint64_t pos(uint64_t base, uint64_t bal_j, uint32_t j) const {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        return base + runs[wave * XPT + j] + __popcll(bal_j & ((1ull << lane) - 1ull));
+    }
+};
+
 // FILTER (kt_ctr_export_stage_range): only the slots whose occurrences lie in [lo, hi] are in the ballot
 template <bool FILTER = false>
 __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restrict__ slots, uint64_t cap,
@@ -91,10 +128,8 @@ __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restr
                                                              uint32_t *__restrict__ out_counts, uint64_t max_out,
                                                              uint64_t *__restrict__ cursor, uint32_t lo,
                                                              uint32_t hi) {
-    __shared__ uint32_t runs[BLOCK / 64 * XPT];  // occupied slots per (wave, load), then their exclusive prefix
-    static_assert(BLOCK / 64 * XPT == 64, "one wave scans the runs, one per lane");
-    __shared__ uint64_t tile_base;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ TileShared sm;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint64_t n_tiles = (cap + XTILE - 1) / XTILE;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         uint4 v[XPT];
@@ -122,27 +157,12 @@ __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restr
             } else {
                 bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu);  // key != KT_EMPTY_KEY
             }
-            if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
         }
-        ktd::lds_barrier();
-        if (wave == 0) {  // 64 runs: one wave scans them and reserves the tile's output range
-            const uint32_t c = runs[lane];
-            uint32_t inc = c;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t u = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += u;
-            }
-            runs[lane] = inc - c;
-            if (lane == 63)
-                tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;
-        }
-        ktd::lds_barrier();
-        const uint64_t base = tile_base;
+        const uint64_t base = sm.reserve(bal, cursor);
 #pragma unroll
         for (uint32_t j = 0; j < XPT; j++) {
             if ((bal[j] >> lane) & 1ull) {
-                const uint64_t pos = base + runs[wave * XPT + j] + __popcll(bal[j] & ((1ull << lane) - 1ull));
+                const uint64_t pos = sm.pos(base, bal[j], j);
                 if (pos < max_out) {
 #if KT_EXPORT_NT & 2
                     __builtin_nontemporal_store(((uint64_t)v[j].y << 32) | v[j].x, out_keys + pos);
@@ -154,7 +174,7 @@ __global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restr
                 }
             }
         }
-        ktd::lds_barrier();  // runs[] / tile_base are rewritten by the next tile
+        ktd::lds_barrier();  // the reservation's LDS is rewritten by the next tile
     }
 }
 
@@ -166,9 +186,8 @@ __global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__r
                                                              uint32_t lo, uint32_t hi, uint64_t *__restrict__ out_keys,
                                                              uint32_t *__restrict__ out_counts, uint64_t max_out,
                                                              uint64_t *__restrict__ cursor) {
-    __shared__ uint32_t runs[BLOCK / 64 * XPT];
-    __shared__ uint64_t tile_base;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ TileShared sm;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint64_t n_tiles = (n + XTILE - 1) / XTILE;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         uint32_t c[XPT];
@@ -182,27 +201,12 @@ __global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__r
         for (uint32_t j = 0; j < XPT; j++) {
             const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
             bal[j] = __ballot(i < n && c[j] >= lo && c[j] <= hi);
-            if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
         }
-        ktd::lds_barrier();
-        if (wave == 0) {
-            const uint32_t v = runs[lane];
-            uint32_t inc = v;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t u = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += u;
-            }
-            runs[lane] = inc - v;
-            if (lane == 63)
-                tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;
-        }
-        ktd::lds_barrier();
-        const uint64_t base = tile_base;
+        const uint64_t base = sm.reserve(bal, cursor);
 #pragma unroll
         for (uint32_t j = 0; j < XPT; j++) {
             if ((bal[j] >> lane) & 1ull) {
-                const uint64_t pos = base + runs[wave * XPT + j] + __popcll(bal[j] & ((1ull << lane) - 1ull));
+                const uint64_t pos = sm.pos(base, bal[j], j);
                 if (pos < max_out) {
                     out_keys[pos] = keys[tile * XTILE + (uint64_t)j * BLOCK + tid];
                     out_counts[pos] = c[j];
@@ -213,6 +217,89 @@ __global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__r
     }
 }
 
+// ---- a table's entries in the form they are in (view_of builds it; the walks of spectrum, compare and setop read it) ---------
+// The form is the kernels' template argument; the view holds what they read.
+enum Form { FORM_PROBE = 0, FORM_DENSE = 1, FORM_PAIRS = 2 };
+struct TableView {
+    const void *src;         // FORM_PROBE: the slots [n) (16-byte slots; stored count = occurrences - 1, KT_EMPTY_KEY free);
+                             // FORM_DENSE: the n ranges of a dense table, RS slots each, range r's range_counts[r] keys from its
+                             // start and counts (occurrences - 1) from byte 8 * RS on; FORM_PAIRS: n keys (an export target's)
+    const uint32_t *counts;  // FORM_PAIRS: the keys' occurrences, from anywhere (a caller's array): `head` = how many
+                             // counts of its first aligned 16 bytes lie before the array
+    uint64_t n;
+    uint32_t RS, head;
+    const uint32_t *range_counts;
+};
+
+// The entry walk: every thread of the workgroup calls it, and `step` gets the lane's next UNROLL (key, occurrences) pairs -
+// KT_EMPTY_KEY: no entry - until the grid has covered the table.  The flat forms go by grid-stride tiles of BLOCK * UNROLL
+// slots / pairs; a dense table is walked a wave per range, BLOCK / 64 consecutive ranges per workgroup step, coalesced.
+// UNIFORM: every wave takes the steps of the longest of the workgroup's ranges (for a `step` with barriers in it; the flat
+// forms are uniform anyway); otherwise a wave takes its own range's steps only.  The uniform walk reads range_counts
+// through the scalar cache (ktd::load_uniform), so nothing may write range_counts while the kernel runs - a kernel that
+// walks a table must not change that table (its stores would also keep a plain uniform load off the scalar unit).
+template <int FORM, uint32_t UNROLL, bool UNIFORM, class Step>
+__device__ __forceinline__ void walk_entries(const TableView &t, Step &&step) {
+    const uint32_t tid = threadIdx.x;
+    uint64_t key[UNROLL];
+    uint32_t cnt[UNROLL];
+    if constexpr (FORM == FORM_DENSE) {
+        constexpr uint32_t WAVES = BLOCK / 64;
+        const uint32_t lane = tid & 63u, wave = tid >> 6;
+        for (uint64_t r0 = (uint64_t)blockIdx.x * WAVES; r0 < t.n; r0 += (uint64_t)gridDim.x * WAVES) {
+            uint32_t D = 0, D_max = 0;  // the entries of this wave's range, and how far the wave steps
+            if constexpr (UNIFORM) {     // (loads through the scalar cache: the step count stays on the scalar unit)
+#pragma unroll
+                for (uint32_t w = 0; w < WAVES; w++) {
+                    const uint32_t d = r0 + w < t.n ? ktd::load_uniform(t.range_counts + r0 + w) : 0u;
+                    D = w == wave ? d : D;
+                    D_max = d > D_max ? d : D_max;
+                }
+            } else {
+                D = D_max = r0 + wave < t.n ? t.range_counts[r0 + wave] : 0u;
+            }
+            const char *base = reinterpret_cast<const char *>(t.src) + (r0 + wave) * t.RS * 16ull;  // (read only below D)
+            const uint64_t *keys = reinterpret_cast<const uint64_t *>(base);
+            const uint32_t *cnts = reinterpret_cast<const uint32_t *>(base + t.RS * 8ull);
+            for (uint32_t e0 = 0; e0 < D_max; e0 += 64u * UNROLL) {
+#pragma unroll
+                for (uint32_t u = 0; u < UNROLL; u++) {
+                    const uint32_t e = e0 + u * 64u + lane;
+                    key[u] = e < D ? keys[e] : KT_EMPTY_KEY;
+                    cnt[u] = e < D ? cnts[e] + 1u : 0u;
+                }
+                step(key, cnt);
+            }
+        }
+    } else {
+        constexpr uint32_t TILE = BLOCK * UNROLL;
+        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < t.n; i0 += (uint64_t)gridDim.x * TILE) {
+#pragma unroll
+            for (uint32_t u = 0; u < UNROLL; u++) {
+                const uint64_t i = i0 + u * BLOCK + tid;
+                if constexpr (FORM == FORM_PROBE) {
+                    const uint4 v = i < t.n ? reinterpret_cast<const uint4 *>(t.src)[i] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+                    key[u] = ((uint64_t)v.y << 32) | v.x;
+                    cnt[u] = v.z + 1u;
+                } else {
+                    key[u] = i < t.n ? reinterpret_cast<const uint64_t *>(t.src)[i] : KT_EMPTY_KEY;
+                    cnt[u] = i < t.n ? t.counts[i] : 0u;
+                }
+            }
+            step(key, cnt);
+        }
+    }
+}
+
+// bit u = key[u] is an entry
+template <uint32_t N>
+__device__ __forceinline__ uint32_t present(const uint64_t (&key)[N]) {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < N; u++) m |= (key[u] != KT_EMPTY_KEY ? 1u : 0u) << u;
+    return m;
+}
+
 // ---- the abundance spectrum (kt_ctr_spectrum) ---------------------------------------------------------------------
 // One pass over what the table's form keeps, counts only (+ the keys where emptiness is in them): hist[min(c, top)] += 1
 // per entry of c occurrences.  The spectrum is skewed - nearly every entry of uniform random reads has c = 1, of reads
@@ -221,9 +308,8 @@ __global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__r
 // end; SPEC_REG < c < SPEC_LDS go to a workgroup histogram in LDS (no-return adds, the bins of a coverage peak spread
 // the lanes over many addresses); c >= SPEC_LDS to 64-bit global atomics (rare: the repeats).  Every workgroup merges
 // its non-zero bins once, at the end.  The register and LDS tallies are u32: a workgroup's share of the entries is
-// bounded below 2^31 by the grid (spectrum_grid).
+// bounded below 2^31 by the grid (launch_walk).
 constexpr uint32_t SPEC_REG = 8, SPEC_LDS = 4096, SPEC_UNROLL = 4;
-enum SpecForm { SPEC_PROBE = 0, SPEC_DENSE = 1, SPEC_PAIRS = 2 };
 
 struct SpecTally {
     uint32_t reg[SPEC_REG] = {};
@@ -242,23 +328,20 @@ struct SpecTally {
     }
 };
 
-// FORM = SPEC_PROBE: `src` is the slots [n) (16-byte slots; stored count = occurrences - 1, KT_EMPTY_KEY free);
-// SPEC_DENSE: the ranges of a dense table, n of them, RS slots each, range r's range_counts[r] counts (occurrences - 1)
-// from byte 8 * RS of the range on; SPEC_PAIRS: n counts (occurrences) from `src` on, which may start anywhere (a
-// caller's array): the 16-byte quads are aligned down, `head` counts of the first quad lie before the array.
+// Reads the view with loads of its own, not walk_entries': it needs no key where emptiness is not in the key, so the
+// dense and pairs forms read the counts alone, 4 bytes per entry as aligned 16-byte quads.
 template <int FORM>
-__global__ __launch_bounds__(BLOCK) void spectrum_kernel(const void *__restrict__ src, uint64_t n, uint32_t RS, uint32_t head,
-                                                         const uint32_t *__restrict__ range_counts,
-                                                         uint64_t *__restrict__ hist, uint32_t n_bins,
+__global__ __launch_bounds__(BLOCK) void spectrum_kernel(TableView tv, uint64_t *__restrict__ hist, uint32_t n_bins,
                                                          uint64_t *__restrict__ totals) {
+    const uint64_t n = tv.n;
     __shared__ uint32_t lds[SPEC_LDS];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t top = n_bins - 1u, lds_bins = n_bins < SPEC_LDS ? n_bins : SPEC_LDS;
     for (uint32_t b = tid; b < lds_bins; b += BLOCK) lds[b] = 0u;
     ktd::lds_barrier();
     SpecTally t;
-    if constexpr (FORM == SPEC_PROBE) {
-        const uint4 *slots = reinterpret_cast<const uint4 *>(src);
+    if constexpr (FORM == FORM_PROBE) {
+        const uint4 *slots = reinterpret_cast<const uint4 *>(tv.src);
         constexpr uint32_t TILE = BLOCK * SPEC_UNROLL;
         for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
             uint4 v[SPEC_UNROLL];
@@ -271,13 +354,13 @@ __global__ __launch_bounds__(BLOCK) void spectrum_kernel(const void *__restrict_
             for (uint32_t u = 0; u < SPEC_UNROLL; u++)
                 if ((v[u].x & v[u].y) != 0xFFFFFFFFu) t.add(v[u].z + 1u, top, lds, hist);
         }
-    } else if constexpr (FORM == SPEC_DENSE) {
+    } else if constexpr (FORM == FORM_DENSE) {
         // a wave per range: the range's counts as quads, SPEC_UNROLL 16-byte loads in flight per lane
         const uint32_t wave = tid >> 6;
         const uint64_t waves = (uint64_t)gridDim.x * (BLOCK / 64);
         for (uint64_t r = (uint64_t)blockIdx.x * (BLOCK / 64) + wave; r < n; r += waves) {
-            const uint32_t D = range_counts[r];
-            const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(src) + r * RS * 16ull + RS * 8ull);
+            const uint32_t D = tv.range_counts[r];
+            const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(tv.src) + r * tv.RS * 16ull + tv.RS * 8ull);
             const uint32_t nq = (D + 3u) / 4u;
             for (uint32_t q0 = 0; q0 < nq; q0 += 64u * SPEC_UNROLL) {
                 uint4 v[SPEC_UNROLL];
@@ -297,7 +380,8 @@ __global__ __launch_bounds__(BLOCK) void spectrum_kernel(const void *__restrict_
             }
         }
     } else {
-        const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint32_t *>(src) - head);
+        const uint32_t head = tv.head;
+        const uint4 *q = reinterpret_cast<const uint4 *>(tv.counts - head);
         const uint64_t end = n + head, nq = (end + 3u) / 4u;
         constexpr uint32_t TILE = BLOCK * SPEC_UNROLL;
         for (uint64_t q0 = (uint64_t)blockIdx.x * TILE; q0 < nq; q0 += (uint64_t)gridDim.x * TILE) {
@@ -340,27 +424,16 @@ __global__ __launch_bounds__(BLOCK) void spectrum_kernel(const void *__restrict_
         if (const uint32_t v = lds[b]) atomicAdd(reinterpret_cast<unsigned long long *>(hist + b), (unsigned long long)v);
 }
 
-// workgroups of a spectrum launch over `items` entries (slots / counts): ~4 per CU, and enough that no workgroup's share
-// reaches 2^31 entries (its u32 tallies)
-uint32_t spectrum_grid(const kt_ctx *ctx, uint64_t work_items, uint64_t entries) {
-    uint64_t g = (uint64_t)ctx->n_cu * 4;
-    if (g > work_items) g = work_items;
-    const uint64_t need = (entries >> 31) + 1;
-    if (g < need) g = need;
-    if (g < 1) g = 1;
-    return (uint32_t)g;
-}
-
 // ---- the comparison matrix of two tables (kt_ctr_compare) ------------------------------------------------------------
-// spectrum_kernel's walk of table A, read-only, in whatever form A is in; for every entry (key, a) the key is probed in B
-// (B's probing image, B's geometry: lookup_kernel's probe) for its count b (0: absent), and cell (min(a, R - 1),
+// The entry walk of table A, read-only, in whatever form A is in (walk_entries); for every entry (key, a) the key is probed
+// in B (B's probing image, B's geometry: kttab::Probed) for its count b (0: absent), and cell (min(a, R - 1),
 // min(b, C - 1)) gets one.  The pass is bound by the random 16-byte reads into B: a lane first loads CMP_UNROLL entries of
 // A, then issues the B home-slot loads of all of them, and only then resolves them (a walk past the home slot is rare).
 // The matrix is skewed as the spectrum is - uniform reads put nearly everything into (1, 0) or (1, 1), reads sampled from
 // a genome into a spot around (coverage, coverage) or (coverage, 1) - so the cells are tallied in three tiers: rows 1..4 x
 // columns 0..1 in registers (an unrolled compare, reduced once per wave), a low corner of tile_rows x tile_cols (up to
 // CMP_LDS cells, at least 128 x 64 or the whole matrix) in LDS with no-return adds, the rest in 64-bit global atomics.
-// Every workgroup merges its non-zero LDS cells once, at the end; u32 tallies as in the spectrum (spectrum_grid bounds a
+// Every workgroup merges its non-zero LDS cells once, at the end; u32 tallies as in the spectrum (launch_walk bounds a
 // workgroup's share below 2^31).  Column 0 (B's k-mers absent from A) is not probed for: compare_row0_kernel takes it from
 // B's spectrum with the same saturation, minus this call's column sums over rows >= 1.
 #ifndef KT_CMP_UNROLL
@@ -369,32 +442,11 @@ uint32_t spectrum_grid(const kt_ctx *ctx, uint64_t work_items, uint64_t entries)
 constexpr uint32_t CMP_UNROLL = KT_CMP_UNROLL, CMP_LDS = 8192, CMP_REG = 8, CMP_TILE_COLS = 64;
 
 struct CmpArgs {
-    const Slot *b_slots;  // B's probing image
-    kttab::Geom bg;
+    kttab::Probed b;      // B's probing image
     uint64_t *cells;      // this call's n_rows x n_cols cells (zeroed; row 0 is left to compare_row0_kernel)
     uint64_t *totals;     // distinct_a, occurrences_a, shared, shared_min
     uint32_t n_rows, n_cols, tile_rows, tile_cols;
 };
-
-__device__ __forceinline__ uint4 cmp_home(const CmpArgs &c, uint64_t key) {
-    return *reinterpret_cast<const uint4 *>(c.b_slots + kttab::probe_of(key, c.bg).slot());
-}
-
-// B's count of `key` given its loaded home slot `v`; walks on round the key's range only on a collision
-__device__ __forceinline__ uint32_t cmp_resolve(const CmpArgs &c, uint4 v, uint64_t key) {
-    uint64_t kk = ((uint64_t)v.y << 32) | v.x;
-    if (kk == key) return v.z + 1u;
-    if (kk == KT_EMPTY_KEY) return 0u;
-    kttab::Probe p = kttab::probe_of(key, c.bg);
-    for (uint32_t probe = 1; probe < p.rs; probe++) {
-        p.next();
-        v = *reinterpret_cast<const uint4 *>(c.b_slots + p.slot());
-        kk = ((uint64_t)v.y << 32) | v.x;
-        if (kk == key) return v.z + 1u;
-        if (kk == KT_EMPTY_KEY) return 0u;
-    }
-    return 0u;
-}
 
 struct CmpTally {
     uint32_t reg[CMP_REG] = {};  // cell (j / 2 + 1, j % 2)
@@ -419,87 +471,19 @@ struct CmpTally {
     }
 };
 
-// FORM as in spectrum_kernel: SPEC_PROBE: `src` = A's slots [n); SPEC_DENSE: A's n ranges of RS slots, range r's
-// range_counts[r] keys from its start and counts (occurrences - 1) from byte 8 * RS on; SPEC_PAIRS: n keys at `src`, their
-// occurrences at `counts` (an export target's arrays)
+// a: table A's view, FORM = its form
 template <int FORM>
-__global__ __launch_bounds__(BLOCK) void compare_kernel(const void *__restrict__ src, const uint32_t *__restrict__ counts,
-                                                        uint64_t n, uint32_t RS, const uint32_t *__restrict__ range_counts,
-                                                        CmpArgs c) {
+__global__ __launch_bounds__(BLOCK) void compare_kernel(TableView a, CmpArgs c) {
     __shared__ uint32_t lds[CMP_LDS];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t tile = c.tile_rows * c.tile_cols;
     for (uint32_t b = tid; b < tile; b += BLOCK) lds[b] = 0u;
     ktd::lds_barrier();
     CmpTally t;
-    const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-    if constexpr (FORM == SPEC_PROBE) {
-        const uint4 *slots = reinterpret_cast<const uint4 *>(src);
-        constexpr uint32_t TILE = BLOCK * CMP_UNROLL;
-        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
-            uint4 v[CMP_UNROLL], h[CMP_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
-                const uint64_t i = i0 + u * BLOCK + tid;
-                v[u] = i < n ? slots[i] : none;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
-                const uint64_t key = ((uint64_t)v[u].y << 32) | v[u].x;
-                h[u] = key != KT_EMPTY_KEY ? cmp_home(c, key) : none;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
-                const uint64_t key = ((uint64_t)v[u].y << 32) | v[u].x;
-                if (key != KT_EMPTY_KEY) t.add(v[u].z + 1u, cmp_resolve(c, h[u], key), c, lds);
-            }
-        }
-    } else if constexpr (FORM == SPEC_DENSE) {
-        // a wave per range: the range's keys and counts, coalesced, CMP_UNROLL entries per lane
-        const uint32_t wave = tid >> 6;
-        const uint64_t waves = (uint64_t)gridDim.x * (BLOCK / 64);
-        for (uint64_t r = (uint64_t)blockIdx.x * (BLOCK / 64) + wave; r < n; r += waves) {
-            const uint32_t D = range_counts[r];
-            const char *base = reinterpret_cast<const char *>(src) + r * RS * 16ull;
-            const uint64_t *keys = reinterpret_cast<const uint64_t *>(base);
-            const uint32_t *cnts = reinterpret_cast<const uint32_t *>(base + RS * 8ull);
-            for (uint32_t e0 = 0; e0 < D; e0 += 64u * CMP_UNROLL) {
-                uint64_t key[CMP_UNROLL];
-                uint32_t cnt[CMP_UNROLL];
-                uint4 h[CMP_UNROLL];
-#pragma unroll
-                for (uint32_t u = 0; u < CMP_UNROLL; u++) {
-                    const uint32_t e = e0 + u * 64u + lane;
-                    key[u] = e < D ? keys[e] : KT_EMPTY_KEY;
-                    cnt[u] = e < D ? cnts[e] + 1u : 0u;
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < CMP_UNROLL; u++) h[u] = key[u] != KT_EMPTY_KEY ? cmp_home(c, key[u]) : none;
-#pragma unroll
-                for (uint32_t u = 0; u < CMP_UNROLL; u++)
-                    if (key[u] != KT_EMPTY_KEY) t.add(cnt[u], cmp_resolve(c, h[u], key[u]), c, lds);
-            }
-        }
-    } else {
-        const uint64_t *keys = reinterpret_cast<const uint64_t *>(src);
-        constexpr uint32_t TILE = BLOCK * CMP_UNROLL;
-        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
-            uint64_t key[CMP_UNROLL];
-            uint32_t cnt[CMP_UNROLL];
-            uint4 h[CMP_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < CMP_UNROLL; u++) {
-                const uint64_t i = i0 + u * BLOCK + tid;
-                key[u] = i < n ? keys[i] : KT_EMPTY_KEY;
-                cnt[u] = i < n ? counts[i] : 0u;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < CMP_UNROLL; u++) h[u] = key[u] != KT_EMPTY_KEY ? cmp_home(c, key[u]) : none;
-#pragma unroll
-            for (uint32_t u = 0; u < CMP_UNROLL; u++)
-                if (key[u] != KT_EMPTY_KEY) t.add(cnt[u], cmp_resolve(c, h[u], key[u]), c, lds);
-        }
-    }
+    // (a wave of a dense table walks its range on its own: nothing below waits for the other waves)
+    walk_entries<FORM, CMP_UNROLL, false>(a, [&](const uint64_t (&key)[CMP_UNROLL], const uint32_t (&ca)[CMP_UNROLL]) {
+        c.b.counts(key, present(key), [&](uint32_t u, uint32_t cb) { t.add(ca[u], cb, c, lds); });
+    });
     // the register cells: one wave reduction each, lane 0 adds the wave's sums to the LDS cells (a non-zero register cell
     // is a cell of the matrix, and rows <= 4, columns <= 1 of the matrix lie inside the tile)
 #pragma unroll
@@ -573,20 +557,20 @@ __global__ __launch_bounds__(BLOCK) void compare_row0_kernel(const uint64_t *__r
 constexpr int MAX_OWNERS = 64;
 
 // ---- set operations of two tables (kt_ctr_setop) ---------------------------------------------------------------------
-// compare_kernel's walk and probes (one table walked read-only in the form it is in, every key resolved against the other
-// table's probing image with the home-slot loads of SET_UNROLL entries in flight together), but instead of tallying a
-// matrix every entry is decided - membership of both sides under their count ranges, the operation, the count rule - and
+// One table walked read-only in the form it is in (walk_entries), every key resolved against the other table's probing
+// image with the home-slot loads of SET_UNROLL entries in flight together (kttab::Probed), as compare_kernel does; what
+// this adds: every entry is decided - membership of both sides under their count ranges, the operation, the count rule - and
 // the kept (key, count) pairs are compacted as the export kernels compact: a ballot per entry, the workgroup's waves add
 // up their popcounts and ONE cursor atomic reserves the tile's output range (BLOCK x SET_UNROLL entries; every store
 // instruction writes one contiguous run).  The cursor is the limit to watch: same-address atomics retire at ~12 ns each,
 // and a first version that took one per wave (512 entries) was bound by them, not by the probes - 13.2 ms against
 // compare's 7.3 ms on the full-size pair, 87 ms for a union that walks two probing images.  A dense table is
-// still walked a wave per range, four ranges per workgroup step, every wave running the steps of the longest of the four
-// so that all reach the barriers.  max_out = 0 only counts: the position test keeps every store away.
+// walked with uniform steps (every wave runs the steps of the longest of the workgroup's four ranges) so that all reach
+// the barriers.  max_out = 0 only counts: the position test keeps every store away.
 constexpr uint32_t SET_UNROLL = CMP_UNROLL;
 
 struct SetArgs {
-    CmpArgs probe;       // the probed table's image and geometry (cells / totals unused)
+    kttab::Probed probed;  // the other table's probing image
     uint32_t op, rule;   // KT_SET_*, KT_SETCNT_*
     uint32_t lo_w, hi_w; // the walked table's count range
     uint32_t lo_p, hi_p; // the probed table's (lo_p >= 1: an absent key is never a member)
@@ -658,78 +642,16 @@ __device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)
     }
 }
 
-// FORM and the source arguments as compare_kernel's
+// w: the walked table's view, FORM = its form
 template <int FORM, bool SECOND>
-__global__ __launch_bounds__(BLOCK) void setop_kernel(const void *__restrict__ src, const uint32_t *__restrict__ counts,
-                                                      uint64_t n, uint32_t RS, const uint32_t *__restrict__ range_counts,
-                                                      SetArgs s) {
+__global__ __launch_bounds__(BLOCK) void setop_kernel(TableView w, SetArgs s) {
     __shared__ SetShared sm;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     uint32_t step = 0;
-    uint64_t key[SET_UNROLL];
-    uint32_t cnt[SET_UNROLL];
-    uint4 h[SET_UNROLL];
-    // key[] / cnt[] loaded (KT_EMPTY_KEY: no entry): the home-slot loads of all of them, then resolve + decide, then compact
-    auto tile = [&]() {
-        const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-#pragma unroll
-        for (uint32_t u = 0; u < SET_UNROLL; u++) h[u] = key[u] != KT_EMPTY_KEY ? cmp_home(s.probe, key[u]) : none;
-#pragma unroll
-        for (uint32_t u = 0; u < SET_UNROLL; u++)
-            cnt[u] = key[u] != KT_EMPTY_KEY ? set_decide<SECOND>(s, cnt[u], cmp_resolve(s.probe, h[u], key[u])) : 0u;
-        set_emit(s, key, cnt, sm, step);
-    };
-    if constexpr (FORM == SPEC_PROBE) {
-        const uint4 *slots = reinterpret_cast<const uint4 *>(src);
-        constexpr uint32_t TILE = BLOCK * SET_UNROLL;
-        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
-#pragma unroll
-            for (uint32_t u = 0; u < SET_UNROLL; u++) {
-                const uint64_t i = i0 + u * BLOCK + tid;
-                const uint4 v = i < n ? slots[i] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-                key[u] = ((uint64_t)v.y << 32) | v.x;
-                cnt[u] = v.z + 1u;
-            }
-            tile();
-        }
-    } else if constexpr (FORM == SPEC_DENSE) {
-        // a wave per range, BLOCK / 64 consecutive ranges per workgroup step
-        constexpr uint32_t WAVES = BLOCK / 64;
-        const uint32_t wave = tid >> 6;
-        for (uint64_t r0 = (uint64_t)blockIdx.x * WAVES; r0 < n; r0 += (uint64_t)gridDim.x * WAVES) {
-            uint32_t D = 0, D_max = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < WAVES; w++) {
-                const uint32_t d = r0 + w < n ? range_counts[r0 + w] : 0u;
-                D = w == wave ? d : D;
-                D_max = d > D_max ? d : D_max;
-            }
-            const char *base = reinterpret_cast<const char *>(src) + (r0 + wave) * RS * 16ull;  // (read only below D)
-            const uint64_t *keys = reinterpret_cast<const uint64_t *>(base);
-            const uint32_t *cnts = reinterpret_cast<const uint32_t *>(base + RS * 8ull);
-            for (uint32_t e0 = 0; e0 < D_max; e0 += 64u * SET_UNROLL) {
-#pragma unroll
-                for (uint32_t u = 0; u < SET_UNROLL; u++) {
-                    const uint32_t e = e0 + u * 64u + lane;
-                    key[u] = e < D ? keys[e] : KT_EMPTY_KEY;
-                    cnt[u] = e < D ? cnts[e] + 1u : 0u;
-                }
-                tile();
-            }
-        }
-    } else {
-        const uint64_t *keys = reinterpret_cast<const uint64_t *>(src);
-        constexpr uint32_t TILE = BLOCK * SET_UNROLL;
-        for (uint64_t i0 = (uint64_t)blockIdx.x * TILE; i0 < n; i0 += (uint64_t)gridDim.x * TILE) {
-#pragma unroll
-            for (uint32_t u = 0; u < SET_UNROLL; u++) {
-                const uint64_t i = i0 + u * BLOCK + tid;
-                key[u] = i < n ? keys[i] : KT_EMPTY_KEY;
-                cnt[u] = i < n ? counts[i] : 0u;
-            }
-            tile();
-        }
-    }
+    walk_entries<FORM, SET_UNROLL, true>(w, [&](const uint64_t (&key)[SET_UNROLL], const uint32_t (&cw)[SET_UNROLL]) {
+        uint32_t out[SET_UNROLL] = {};
+        s.probed.counts(key, present(key), [&](uint32_t u, uint32_t cp) { out[u] = set_decide<SECOND>(s, cw[u], cp); });
+        set_emit(s, key, out, sm, step);
+    });
 }
 
 __global__ __launch_bounds__(BLOCK) void route_count_kernel(SegArgs a, uint32_t n_owners,
@@ -1291,28 +1213,49 @@ int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *tota
 
 }  // extern "C"
 
-// the spectrum launch of a table of n > 0 entries, in the form it is in, into device arrays (kt_ctr_spectrum, kt_ctr_compare)
-static int launch_spectrum(kt_ctr *ctr, uint64_t n, uint64_t *d_hist, uint32_t n_bins, uint64_t *d_totals) {
-    kt_ctx *ctx = ctr->ctx;
-    constexpr uint64_t TILE = (uint64_t)BLOCK * SPEC_UNROLL;
-    if (ctr->dense && ctr->dense_ext) {
-        const uint32_t head = (uint32_t)(((uintptr_t)ctr->xt_counts & 15u) / 4u);
-        const uint64_t nq = (n + head + 3) / 4;
-        hipLaunchKernelGGL(spectrum_kernel<SPEC_PAIRS>, dim3(spectrum_grid(ctx, (nq + TILE - 1) / TILE, n)), dim3(BLOCK), 0,
-                           ctx->stream, (const void *)ctr->xt_counts, n, 0u, head, nullptr, d_hist, n_bins, d_totals);
-    } else if (ctr->dense) {
+// the table's n > 0 entries as the kernels walk them, in the form they are in now: the form, the view the kernels read
+// and what a launch's workgroups share out (the slots of a probing image, else the entries)
+struct TableWalk {
+    Form form;
+    TableView v;
+    uint64_t entries;
+};
+static TableWalk view_of(const kt_ctr *ctr, uint64_t n) {
+    if (ctr->dense && ctr->dense_ext)
+        return {FORM_PAIRS, {ctr->xt_keys, ctr->xt_counts, n, 0u, (uint32_t)(((uintptr_t)ctr->xt_counts & 15u) / 4u), nullptr}, n};
+    if (ctr->dense) {
         const uint32_t RS = ctr->m8 << (kttab::LOG2_RANGE - 3);
-        const uint64_t n_ranges = ctr->cap / RS;
-        hipLaunchKernelGGL(spectrum_kernel<SPEC_DENSE>, dim3(spectrum_grid(ctx, (n_ranges + 3) / 4, n)), dim3(BLOCK), 0,
-                           ctx->stream, (const void *)ctr->slots, n_ranges, RS, 0u, ctr->range_counts, d_hist, n_bins,
-                           d_totals);
-    } else {
-        hipLaunchKernelGGL(spectrum_kernel<SPEC_PROBE>, dim3(spectrum_grid(ctx, (ctr->cap + TILE - 1) / TILE, ctr->cap)),
-                           dim3(BLOCK), 0, ctx->stream, (const void *)ctr->slots, ctr->cap, 0u, 0u, nullptr, d_hist, n_bins,
-                           d_totals);
+        return {FORM_DENSE, {ctr->slots, nullptr, ctr->cap / RS, RS, 0u, ctr->range_counts}, n};
     }
+    return {FORM_PROBE, {ctr->slots, nullptr, ctr->cap, 0u, 0u, nullptr}, ctr->cap};
+}
+
+// One launch over a table: launch(the form as a compile-time constant, the grid).  A flat form is shared out in tiles of
+// `tile` of its `flat_items` (what a workgroup takes per step: BLOCK x the kernel's unroll, in slots or pairs - v.n of them
+// - or in whatever else the kernel reads a flat form by); a dense table goes four ranges per workgroup.  ~4 workgroups per
+// CU, and enough that no workgroup's share reaches 2^31 entries (the kernels' u32 tallies).
+template <class Launch>
+static int launch_walk(kt_ctx *ctx, const TableWalk &w, uint64_t flat_items, uint64_t tile, Launch &&launch) {
+    const uint64_t work_items = w.form == FORM_DENSE ? (w.v.n + 3) / 4 : (flat_items + tile - 1) / tile;
+    uint64_t g = (uint64_t)ctx->n_cu * 4;
+    if (g > work_items) g = work_items;
+    if (g < (w.entries >> 31) + 1) g = (w.entries >> 31) + 1;
+    const dim3 grid((uint32_t)g);
+    if (w.form == FORM_PAIRS) launch(std::integral_constant<int, FORM_PAIRS>{}, grid);
+    else if (w.form == FORM_DENSE) launch(std::integral_constant<int, FORM_DENSE>{}, grid);
+    else launch(std::integral_constant<int, FORM_PROBE>{}, grid);
     KT_HIP(hipGetLastError());
     return KT_OK;
+}
+
+// the spectrum launch of a table of n > 0 entries, in the form it is in, into device arrays (kt_ctr_spectrum, kt_ctr_compare)
+static int launch_spectrum(kt_ctr *ctr, uint64_t n, uint64_t *d_hist, uint32_t n_bins, uint64_t *d_totals) {
+    const TableWalk w = view_of(ctr, n);
+    // (the kernel reads the counts of the pairs form as aligned 16-byte quads)
+    const uint64_t flat_items = w.form == FORM_PAIRS ? (w.v.n + w.v.head + 3) / 4 : w.v.n;
+    return launch_walk(ctr->ctx, w, flat_items, (uint64_t)BLOCK * SPEC_UNROLL, [&](auto form, dim3 grid) {
+        hipLaunchKernelGGL(spectrum_kernel<decltype(form)::value>, grid, dim3(BLOCK), 0, ctr->ctx->stream, w.v, d_hist, n_bins, d_totals);
+    });
 }
 
 extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n_rows, uint32_t n_cols, uint64_t *totals, int mem) {
@@ -1342,21 +1285,12 @@ extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n
     if (n_a) {
         const uint32_t tile_cols = n_cols < CMP_TILE_COLS ? n_cols : CMP_TILE_COLS;
         const uint32_t tile_rows = n_rows < CMP_LDS / tile_cols ? n_rows : CMP_LDS / tile_cols;
-        const CmpArgs c{(const Slot *)b->slots, ktl::geom_of(b), S, tot_a, n_rows, n_cols, tile_rows, tile_cols};
-        constexpr uint64_t TILE = (uint64_t)BLOCK * CMP_UNROLL;
-        if (a->dense && a->dense_ext) {
-            hipLaunchKernelGGL(compare_kernel<SPEC_PAIRS>, dim3(spectrum_grid(ctx, (n_a + TILE - 1) / TILE, n_a)), dim3(BLOCK), 0,
-                               ctx->stream, (const void *)a->xt_keys, (const uint32_t *)a->xt_counts, n_a, 0u, nullptr, c);
-        } else if (a->dense) {
-            const uint32_t RS = a->m8 << (kttab::LOG2_RANGE - 3);
-            const uint64_t n_ranges = a->cap / RS;
-            hipLaunchKernelGGL(compare_kernel<SPEC_DENSE>, dim3(spectrum_grid(ctx, (n_ranges + 3) / 4, n_a)), dim3(BLOCK), 0,
-                               ctx->stream, (const void *)a->slots, nullptr, n_ranges, RS, a->range_counts, c);
-        } else {
-            hipLaunchKernelGGL(compare_kernel<SPEC_PROBE>, dim3(spectrum_grid(ctx, (a->cap + TILE - 1) / TILE, a->cap)),
-                               dim3(BLOCK), 0, ctx->stream, (const void *)a->slots, nullptr, a->cap, 0u, nullptr, c);
-        }
-        KT_HIP(hipGetLastError());
+        const CmpArgs c{probed_of(b), S, tot_a, n_rows, n_cols, tile_rows, tile_cols};
+        const TableWalk w = view_of(a, n_a);
+        if (int rc = launch_walk(ctx, w, w.v.n, (uint64_t)BLOCK * CMP_UNROLL, [&](auto form, dim3 grid) {
+                hipLaunchKernelGGL(compare_kernel<decltype(form)::value>, grid, dim3(BLOCK), 0, ctx->stream, w.v, c);
+            }))
+            return rc;
     }
     if (n_b)
         if (int rc = launch_spectrum(b, n_b, spec_b, n_cols, tot_b)) return rc;
@@ -1378,25 +1312,13 @@ extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n
     return KT_OK;
 }
 
-// one walk of kt_ctr_setop: table `w` (n_w > 0 entries) in the form it is in, probing s.probe
+// one walk of kt_ctr_setop: table `t` (n_w > 0 entries) in the form it is in, probing s.probed
 template <bool SECOND>
-static int launch_setop(kt_ctr *w, uint64_t n_w, const SetArgs &s) {
-    kt_ctx *ctx = w->ctx;
-    constexpr uint64_t TILE = (uint64_t)BLOCK * SET_UNROLL;
-    if (w->dense && w->dense_ext) {
-        hipLaunchKernelGGL((setop_kernel<SPEC_PAIRS, SECOND>), dim3(spectrum_grid(ctx, (n_w + TILE - 1) / TILE, n_w)), dim3(BLOCK),
-                           0, ctx->stream, (const void *)w->xt_keys, (const uint32_t *)w->xt_counts, n_w, 0u, nullptr, s);
-    } else if (w->dense) {
-        const uint32_t RS = w->m8 << (kttab::LOG2_RANGE - 3);
-        const uint64_t n_ranges = w->cap / RS;
-        hipLaunchKernelGGL((setop_kernel<SPEC_DENSE, SECOND>), dim3(spectrum_grid(ctx, (n_ranges + 3) / 4, n_w)), dim3(BLOCK), 0,
-                           ctx->stream, (const void *)w->slots, nullptr, n_ranges, RS, w->range_counts, s);
-    } else {
-        hipLaunchKernelGGL((setop_kernel<SPEC_PROBE, SECOND>), dim3(spectrum_grid(ctx, (w->cap + TILE - 1) / TILE, w->cap)),
-                           dim3(BLOCK), 0, ctx->stream, (const void *)w->slots, nullptr, w->cap, 0u, nullptr, s);
-    }
-    KT_HIP(hipGetLastError());
-    return KT_OK;
+static int launch_setop(kt_ctr *t, uint64_t n_w, const SetArgs &s) {
+    const TableWalk w = view_of(t, n_w);
+    return launch_walk(t->ctx, w, w.v.n, (uint64_t)BLOCK * SET_UNROLL, [&](auto form, dim3 grid) {
+        hipLaunchKernelGGL((setop_kernel<decltype(form)::value, SECOND>), grid, dim3(BLOCK), 0, t->ctx->stream, w.v, s);
+    });
 }
 
 extern "C" int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32_t min_a, uint32_t max_a, uint32_t min_b,
@@ -1435,17 +1357,13 @@ extern "C" int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32
     }
     uint64_t *cursor = a->cursor;
     KT_HIP(hipMemsetAsync(cursor, 0, 8, ctx->stream));
-    const CmpArgs none{};
-    SetArgs s{none, (uint32_t)op, (uint32_t)count_rule, min_a, max_a, min_b, max_b, d_keys, d_counts, max_out, cursor};
+    SetArgs s{probed_of(b), (uint32_t)op, (uint32_t)count_rule, min_a, max_a, min_b, max_b, d_keys, d_counts, max_out, cursor};
     if (n_a) {
-        s.probe.b_slots = (const Slot *)b->slots;
-        s.probe.bg = ktl::geom_of(b);
         if (int rc = launch_setop<false>(a, n_a, s)) return rc;
     }
     if (two) {
         if (int rc = table_ready(a)) return rc;  // (behind A's walk on the stream; uses neither the cursor nor the context's scratch)
-        s.probe.b_slots = (const Slot *)a->slots;
-        s.probe.bg = ktl::geom_of(a);
+        s.probed = probed_of(a);
         s.lo_w = min_b, s.hi_w = max_b;
         if (int rc = launch_setop<true>(b, n_b, s)) return rc;
     }

@@ -1,5 +1,5 @@
 // kt_launch.hpp - host-side launch helpers shared by the translation units that use the
-// segment front-end (kt_ctr.hip, kt_cov.hip).  Defined in kt_ctr.hip.
+// segment front-end (kt_ctr.hip, kt_cov.hip, kt_correct.hip).  Defined in kt_ctr.hip.
 #pragma once
 #include "kt_internal.hpp"
 #include "kt_segment.hpp"
@@ -22,6 +22,10 @@ int stage_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint
 int has_read_of_2_32(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int mem, bool *too_long);
 // the table's geometry as the device functions take it (kt_table.hpp)
 inline kttab::Geom geom_of(const kt_ctr *ctr) { return kttab::Geom{ctr->cap, ctr->shift, ctr->m8, ctr->kbits}; }
+// the table as the kernels that probe it take it (after table_ready: the slots hold the probing image)
+inline kttab::Probed probed_of(const kt_ctr *ctr, uint32_t n_parts = 1, uint32_t part = 0) {
+    return kttab::Probed{(const kttab::Slot *)ctr->slots, geom_of(ctr), n_parts, part};
+}
 // makes the table readable: performs a deferred clear, reports KT_ERR_FULL if it overflowed
 int table_ready(kt_ctr *ctr);
 

@@ -415,4 +415,30 @@ __device__ __forceinline__ void collect_kmers(const SegArgs &a, uint64_t g, SegS
     ktd::lds_barrier();  // LDS is reused by the next segment
 }
 
+// The read that holds global base s: searched between the reads that touch s's segment `seg`,
+// [seg_first[seg] - 1, seg_first[seg + 1]) - six steps for 150-base reads, not the 24 of a search in all the offsets.
+// advance(s) moves on to the read of a later base (empty reads hold nothing and are stepped over).
+struct ReadCursor {
+    const uint64_t *offsets;
+    uint64_t rid, start, next;  // the read and its bases [start, next)
+    __device__ __forceinline__ ReadCursor(const uint64_t *offsets_, const uint64_t *seg_first, uint64_t seg, uint64_t s)
+        : offsets(offsets_) {
+        const uint64_t r_first = seg_first[seg];
+        uint64_t lo = r_first ? r_first - 1 : 0, hi = seg_first[seg + 1];  // offsets[lo] <= s < offsets[hi]
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (offsets[mid] <= s) lo = mid; else hi = mid;
+        }
+        rid = lo;
+        start = offsets[rid];
+        next = offsets[rid + 1];
+    }
+    __device__ __forceinline__ void advance(uint64_t s) {
+        while (s >= next) {
+            start = next;
+            next = offsets[++rid + 1];
+        }
+    }
+};
+
 }  // namespace ktseg

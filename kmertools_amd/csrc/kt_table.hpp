@@ -1,5 +1,5 @@
 // kt_table.hpp - the HBM-resident canonical k-mer table shared by the incremental (atomic)
-// path in kt_ctr.hip, the lookups of kt_cov.hip and the bulk (partition + LDS build) path in kt_bulk.hip.
+// path in kt_ctr.hip, the lookups (struct Probed) and the bulk (partition + LDS build) path in kt_bulk.hip.
 //
 // Layout: 16-byte slots {u64 key, u32 occurrences-1, u32 pad}; KT_EMPTY_KEY marks a free slot.  The table is a
 // row of independent RANGES: with x = the top n bits of khash(key), the top n - 13 bits of x select the range
@@ -109,27 +109,47 @@ __device__ __forceinline__ uint32_t table_add(const TableRef &t, uint64_t key, u
 }
 
 #ifdef __HIPCC__
-// ---- lookups (kt_cov.hip, kt_correct.hip) ----
-__device__ __forceinline__ uint4 load_slot(const Slot *slots, uint64_t slot) {
-    return *reinterpret_cast<const uint4 *>(slots + slot);
-}
+// ---- lookups: a table that is probed, read-only (kt_cov.hip, kt_correct.hip, kt_ctr.hip's compare / setop) ----
+struct Probed {
+    const Slot *slots;  // the probing image
+    Geom g;             // capacity and hash -> home slot mapping
+    uint32_t n_parts = 1, part = 0;  // n_parts > 1: the caller answers only for the keys of hash partition `part`
 
-// occurrences of `key` given the already-loaded home slot `v`; walks on (round the key's range, kt_table.hpp)
-// only on a collision - the probe sequence is recomputed then, so that the common case carries no state for it
-__device__ __forceinline__ uint32_t resolve_count(const Slot *slots, const kttab::Geom &g, uint4 v, uint64_t key) {
-    uint64_t kk = ((uint64_t)v.y << 32) | v.x;
-    if (kk == key) return v.z + 1u;  // stored value is occurrences - 1
-    if (kk == KT_EMPTY_KEY) return 0u;
-    kttab::Probe p = kttab::probe_of(key, g);
-    for (uint32_t probe = 1; probe < p.rs; probe++) {
-        p.next();
-        v = load_slot(slots, p.slot());
-        kk = ((uint64_t)v.y << 32) | v.x;
-        if (kk == key) return v.z + 1u;
-        if (kk == KT_EMPTY_KEY) return 0u;
+    // (a key that another pass / another shard answers for is not "absent": it is skipped)
+    __device__ __forceinline__ bool mine(uint64_t key) const { return n_parts <= 1 || ktd::owner_of(key, n_parts) == part; }
+    // the key's home slot: one 16-byte load
+    __device__ __forceinline__ uint4 home(uint64_t key) const {
+        return *reinterpret_cast<const uint4 *>(slots + probe_of(key, g).slot());
     }
-    return 0u;
-}
+    // occurrences of `key` given the already-loaded home slot `v`; walks on (round the key's range) only on a collision -
+    // the probe sequence is recomputed then, so that the common case carries no state for it
+    __device__ __forceinline__ uint32_t count(uint4 v, uint64_t key) const {
+        uint32_t n = 0;
+        auto settled = [&](const uint4 &s) {  // the slot holds the key (n = its occurrences) or ends the probe sequence
+            const uint64_t kk = ((uint64_t)s.y << 32) | s.x;
+            if (kk == key) n = s.z + 1u;  // stored value is occurrences - 1
+            return kk == key || kk == KT_EMPTY_KEY;
+        };
+        if (settled(v)) return n;
+        Probe p = probe_of(key, g);
+        for (uint32_t probe = 1; probe < p.rs; probe++) {
+            p.next();
+            if (settled(*reinterpret_cast<const uint4 *>(slots + p.slot()))) return n;
+        }
+        return 0u;
+    }
+    // the probe pipeline: the home-slot loads of the keys whose bit is set in `want`, all in flight together, then each
+    // resolved in turn: sink(u, occurrences of key[u]) (0: absent)
+    template <uint32_t N, class Sink>
+    __device__ __forceinline__ void counts(const uint64_t (&key)[N], uint32_t want, Sink &&sink) const {
+        uint4 h[N];
+#pragma unroll
+        for (uint32_t u = 0; u < N; u++) h[u] = (want >> u) & 1u ? home(key[u]) : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+#pragma unroll
+        for (uint32_t u = 0; u < N; u++)
+            if ((want >> u) & 1u) sink(u, count(h[u], key[u]));
+    }
+};
 #endif
 
 }  // namespace kttab
