@@ -442,6 +442,48 @@ int kt_correct_apply(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
                      uint32_t min_support, uint32_t max_corrections, uint8_t *out_bases, uint32_t *n_single,
                      uint32_t *n_ambiguous, int mem);
 
+/* Bottom-s MinHash sketches of the reads of a batch (`kmertools sketch`; what Mash does, and sourmash with `num`).
+ * replaces: nothing - the reference has no such operation.  No table is involved.
+ * A read's k-mers are its valid windows, canonical, as for every other k-mer walk here (1 <= k <= 31); a k-mer's hash is
+ * splitmix64's finaliser of (k-mer ^ seed) - a bijection of the 64-bit words, so distinct k-mers have distinct hashes:
+ *   z = (kmer ^ seed) + 0x9e3779b97f4a7c15; z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;
+ *   z = (z ^ (z >> 27)) * 0x94d049bb133111eb; hash = z ^ (z >> 31).
+ * Row i of `hashes` (hashes[i*s .. i*s+s)) = the s smallest DISTINCT hashes of read i, ascending; sizes[i] = how many there
+ * are = min(s, distinct k-mers of the read), 0 for a read shorter than k or without a valid window; the entries at and
+ * after sizes[i] are KT_EMPTY_KEY.  sizes is the authority: a hash may in principle equal KT_EMPTY_KEY.  n_kmers[i] (may
+ * be NULL) = the windows of read i, counted with multiplicity.  Every output element is overwritten.  The result is exact
+ * for every input (repeats included) and a function of the inputs alone.
+ * `mem` says where bases, offsets and the outputs live; KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the
+ * context's stream (after one read-back of the longest read's length).
+ * KT_ERR_ARG: k outside 1..31, s outside 1..KT_SKETCH_MAX_S, a bad mem, a null buffer with n_reads > 0, a read of 2^32
+ * bases or more. */
+#define KT_SKETCH_MAX_S 16384
+int kt_sketch_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k, uint32_t s,
+                    uint64_t seed, uint64_t *hashes, uint32_t *sizes, uint32_t *n_kmers, int mem);
+
+/* Sketches of unions: row g of out_hashes (n_groups rows of s, out_sizes[g] entries, KT_EMPTY_KEY behind them) = the s
+ * smallest distinct hashes among rows group_offsets[g] .. group_offsets[g+1] of `hashes` (n rows of s, sizes[i] entries
+ * each, strictly ascending - the layout kt_sketch_batch writes; an empty group gives size 0).  Exact: the bottom-s of a
+ * union of bottom-s sets is the bottom-s of the union of the sets - the sketch of a sample given in several batches, or
+ * of all the records of a file.  out_hashes must not overlap hashes.  `mem` as above.
+ * KT_ERR_ARG: s outside 1..KT_SKETCH_MAX_S, a bad mem, a null buffer with n_groups > 0, group_offsets that decrease or
+ * end above n. */
+int kt_sketch_merge(kt_ctx *ctx, const uint64_t *hashes, const uint32_t *sizes, uint64_t n, uint32_t s,
+                    const uint64_t *group_offsets, uint64_t n_groups, uint64_t *out_hashes, uint32_t *out_sizes, int mem);
+
+/* Mash's merge walk for every pair (row i of A, row j of B), both n x s in kt_sketch_batch's layout:
+ *   denom[i*n_b + j]  = min(s, |A_i u B_j|)   (may be NULL),
+ *   shared[i*n_b + j] = how many of the denom smallest hashes of A_i u B_j are in both.
+ * The full n_a x n_b matrices, row-major; a_hashes == b_hashes is allowed (all against all: the matrix is symmetric, the
+ * diagonal is (size, size)).  Rows must be strictly ascending within their size: a precondition, not checked.  `mem` as
+ * above.  KT_ERR_ARG: s outside 1..KT_SKETCH_MAX_S, a bad mem, a null buffer with n_a, n_b > 0. */
+int kt_sketch_pairs(kt_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_sizes, uint64_t n_a, const uint64_t *b_hashes,
+                    const uint32_t *b_sizes, uint64_t n_b, uint32_t s, uint32_t *shared, uint32_t *denom, int mem);
+
+/* The Mash distance of such a pair (host helper, the one implementation of the formula): j = shared / denom (0 when
+ * denom == 0); 1 when j == 0, else min(1, -ln(2j / (1 + j)) / k); j == 1 gives 0. */
+double kt_mash_distance(uint32_t shared, uint32_t denom, int k);
+
 /* Multi-GPU routing step (the reference's `min_mer % n_parts` partitioning,
  * counter/src/lib.rs:127, re-expressed as hash-prefix ownership):
  * writes every canonical k-mer of the reads into keys_out grouped by owner

@@ -16,6 +16,7 @@ KT_ERR_ARG, KT_ERR_HIP, KT_ERR_NOMEM, KT_ERR_FULL, KT_ERR_NODEVICE, KT_ERR_BADNT
 KT_MEM_HOST, KT_MEM_DEVICE = 0, 1
 KT_F64, KT_F32, KT_U32 = 0, 1, 2
 KT_EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
+KT_SKETCH_MAX_S = 16384
 KT_SET_INTERSECT, KT_SET_SUBTRACT, KT_SET_UNION, KT_SET_XOR = 0, 1, 2, 3
 KT_SETCNT_FIRST, KT_SETCNT_MIN, KT_SETCNT_MAX, KT_SETCNT_SUM = 0, 1, 2, 3
 
@@ -71,6 +72,10 @@ SYMBOLS = {
     "kt_profile_stats": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "kt_ctr_correct_support": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _i, _u32, _u32]),
     "kt_correct_apply": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _i]),
+    "kt_sketch_batch": (_i, [_vp, _vp, _vp, _u64, _i, _u32, _u64, _vp, _vp, _vp, _i]),
+    "kt_sketch_merge": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _vp, _i]),
+    "kt_sketch_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _i]),
+    "kt_mash_distance": (C.c_double, [_u32, _u32, _i]),
     "kt_ctr_route": (_i, [_vp, _vp, _vp, _u64, _i, _i, _vp, _vp, _i]),
     "kt_owner_of": (_u32, [_u64, _u32]),
     "kt_rccl_unique_id": (_i, [_vp]),

@@ -2192,4 +2192,173 @@ std::string bin_sequences(uint64_t wsize, int msize, const std::string &in_path,
     return "";
 }
 
+// ---------------------------------------------------------------------------------------------
+SketchComputer::SketchComputer(std::string in_path, std::string out_dir, int ksize, uint32_t sketch_size)
+    : in_path_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize), s_(sketch_size) {}
+
+static void append_sketch_line(std::string &text, const std::string &id, uint64_t length, uint64_t kmers, uint32_t size,
+                               const uint64_t *row) {
+    text += id;
+    text += '\t';
+    append_uint(text, length);
+    text += '\t';
+    append_uint(text, kmers);
+    text += '\t';
+    append_uint(text, size);
+    text += '\t';
+    for (uint32_t t = 0; t < size; t++) {
+        if (t) text += ',';
+        append_uint(text, row[t]);
+    }
+    text += '\n';
+}
+
+// the sketches of one input: its lines into out_path, the sketches themselves into `set` when the distances want them
+std::string SketchComputer::sketch_input(const std::string &path, const std::string &out_path, Set &set, bool keep) {
+    SeqReader reader;
+    if (!reader.open(path, false)) return reader.error();
+    FILE *out = fopen(out_path.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + out_path;
+    PhaseTimer pt("sketch");
+    Lap lap;
+    Batch b;
+    std::string text, err, name;
+    std::vector<uint64_t> hashes, run_h, merged_h;  // run_h: --single, the sketch of everything read so far in front of the batch's rows
+    std::vector<uint32_t> sizes, nk, run_s, merged_s(1);
+    uint64_t all_bases = 0, all_kmers = 0;
+    bool any = false;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
+        pt.t[0] += lap();
+        const uint64_t n = b.n_reads();
+        if (n) {
+            hashes.resize(n * s_);
+            sizes.resize(n);
+            nk.resize(n);
+            if (kt_sketch_batch(dev_.ctx, bases_ptr(b), b.offsets.data(), n, ksize_, s_, seed_, hashes.data(), sizes.data(), nk.data(),
+                                KT_MEM_HOST) != KT_OK) {
+                err = kt_last_error();
+                break;
+            }
+            if (single_) {
+                // one group: the running sketch and the batch's rows
+                const uint64_t rows = n + (any ? 1 : 0);
+                run_h.resize((any ? s_ : 0));
+                run_h.insert(run_h.end(), hashes.begin(), hashes.end());
+                run_s.resize(any ? 1 : 0);
+                run_s.insert(run_s.end(), sizes.begin(), sizes.end());
+                const uint64_t go[2] = {0, rows};
+                merged_h.resize(s_);
+                if (kt_sketch_merge(dev_.ctx, run_h.data(), run_s.data(), rows, s_, go, 1, merged_h.data(), merged_s.data(), KT_MEM_HOST) !=
+                    KT_OK) {
+                    err = kt_last_error();
+                    break;
+                }
+                run_h.assign(merged_h.begin(), merged_h.end());
+                run_s.assign(1, merged_s[0]);
+                any = true;
+                all_bases += b.offsets[n];
+                for (uint64_t i = 0; i < n; i++) all_kmers += nk[i];
+                pt.t[1] += lap();
+            } else {
+                pt.t[1] += lap();
+                text.clear();
+                for (uint64_t i = 0; i < n; i++) {
+                    name.clear();
+                    append_name(name, b.headers[i]);
+                    append_sketch_line(text, name, b.offsets[i + 1] - b.offsets[i], nk[i], sizes[i], hashes.data() + i * s_);
+                    if (keep) set.ids.push_back(name);
+                }
+                if (keep) {
+                    set.hashes.insert(set.hashes.end(), hashes.begin(), hashes.end());
+                    set.sizes.insert(set.sizes.end(), sizes.begin(), sizes.end());
+                }
+                pt.t[2] += lap();
+                if (fwrite(text.data(), 1, text.size(), out) != text.size()) {
+                    err = "Unable to write to file: " + out_path;
+                    break;
+                }
+                pt.t[3] += lap();
+            }
+        }
+        if (!more) break;
+    }
+    if (err.empty() && reader.failed()) err = reader.error();
+    if (err.empty() && single_) {
+        const size_t slash = path.find_last_of('/');
+        name = slash == std::string::npos ? path : path.substr(slash + 1);
+        if (!any) {
+            run_h.assign(s_, KT_EMPTY_KEY);
+            run_s.assign(1, 0u);
+        }
+        text.clear();
+        append_sketch_line(text, name, all_bases, all_kmers, run_s[0], run_h.data());
+        if (keep) {
+            set.ids.push_back(name);
+            set.hashes.assign(run_h.begin(), run_h.begin() + s_);
+            set.sizes.assign(1, run_s[0]);
+        }
+        if (fwrite(text.data(), 1, text.size(), out) != text.size()) err = "Unable to write to file: " + out_path;
+    }
+    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path;
+    return err;
+}
+
+// sketch.dist: the pairs i < j of `a` (b == nullptr) or every (i of a, j of b), a block of rows of the matrix at a time
+std::string SketchComputer::write_dist(const Set &a, const Set *b) {
+    const std::string path = out_dir_ + "/sketch.dist";
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + path;
+    const Set &bb = b ? *b : a;
+    const uint64_t n_a = a.sizes.size(), n_b = bb.sizes.size();
+    std::string err, text;
+    if (n_a && n_b) {
+        // the block's two u32 matrices stay within 1 GiB
+        uint64_t rows = (1ull << 30) / (8 * n_b);
+        rows = rows < 1 ? 1 : (rows > n_a ? n_a : rows);
+        std::vector<uint32_t> shared(rows * n_b), denom(rows * n_b);
+        for (uint64_t i0 = 0; i0 < n_a && err.empty(); i0 += rows) {
+            const uint64_t r = n_a - i0 < rows ? n_a - i0 : rows;
+            if (kt_sketch_pairs(dev_.ctx, a.hashes.data() + i0 * s_, a.sizes.data() + i0, r, bb.hashes.data(), bb.sizes.data(), n_b, s_,
+                                shared.data(), denom.data(), KT_MEM_HOST) != KT_OK) {
+                err = kt_last_error();
+                break;
+            }
+            text.clear();
+            for (uint64_t i = i0; i < i0 + r; i++) {
+                for (uint64_t j = b ? 0 : i + 1; j < n_b; j++) {
+                    const uint32_t sh = shared[(i - i0) * n_b + j], dn = denom[(i - i0) * n_b + j];
+                    const double d = kt_mash_distance(sh, dn, ksize_);
+                    if (d > max_dist_) continue;
+                    text += a.ids[i];
+                    text += '\t';
+                    text += bb.ids[j];
+                    text += '\t';
+                    append_uint(text, sh);
+                    text += '/';
+                    append_uint(text, dn);
+                    text += '\t';
+                    append_display(text, dn ? (double)sh / (double)dn : 0.0);
+                    text += '\t';
+                    append_display(text, d);
+                    text += '\n';
+                }
+            }
+            if (fwrite(text.data(), 1, text.size(), out) != text.size()) err = "Unable to write to file: " + path;
+        }
+    }
+    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + path;
+    return err;
+}
+
+std::string SketchComputer::sketch() {
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
+    Set a, b;
+    if (std::string e = sketch_input(in_path_, out_dir_ + "/sketch.tsv", a, dist_); !e.empty()) return e;
+    if (!alt_path_.empty())
+        if (std::string e = sketch_input(alt_path_, out_dir_ + "/sketch.alt.tsv", b, dist_); !e.empty()) return e;
+    if (dist_) return write_dist(a, alt_path_.empty() ? nullptr : &b);
+    return "";
+}
+
 }  // namespace kthost

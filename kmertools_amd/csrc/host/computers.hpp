@@ -357,4 +357,37 @@ class SetopComputer {
     void release();
 };
 
+// `sketch`: bottom-s MinHash sketches of the records of an input (kt_sketch_batch), of the whole input (--single: the
+// batches' sketches merged by kt_sketch_merge) and the Mash distances between them (kt_sketch_pairs, a block of rows of the
+// matrix at a time; the formula is kt_mash_distance).  Writes {out_dir}/sketch.tsv ("id\tlength\tkmers\tsize\th0,h1,..."
+// per sketch, in input order), {out_dir}/sketch.alt.tsv for the second input and {out_dir}/sketch.dist
+// ("id_a\tid_b\tshared/denom\tjaccard\tdistance": the pairs i < j of the input, or every pair (input, alt input)).
+class SketchComputer {
+  public:
+    SketchComputer(std::string in_path, std::string out_dir, int ksize, uint32_t sketch_size);
+    void set_seed(uint64_t seed) { seed_ = seed; }
+    void set_single(bool s) { single_ = s; }
+    void set_alt_path(std::string p) { alt_path_ = std::move(p); }
+    void set_dist(bool d, double max_dist) { dist_ = d, max_dist_ = max_dist; }
+    void set_threads(int t) { threads_ = t; }
+    void set_device(int d) { dev_.index = d; }
+    std::string sketch();  // "" or the error message
+
+  private:
+    struct Set {  // the sketches of one input, kept for the distances
+        std::vector<std::string> ids;
+        std::vector<uint64_t> hashes;  // rows of s
+        std::vector<uint32_t> sizes;
+    };
+    std::string in_path_, alt_path_, out_dir_;
+    int ksize_, threads_ = 0;
+    uint32_t s_;
+    uint64_t seed_ = 0;
+    bool single_ = false, dist_ = false;
+    double max_dist_ = 1.0;
+    Device dev_;
+    std::string sketch_input(const std::string &path, const std::string &out_path, Set &set, bool keep);
+    std::string write_dist(const Set &a, const Set *b);
+};
+
 }  // namespace kthost

@@ -4,7 +4,7 @@
 // auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.  `filter` (a k-mer read
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
 // and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
-// inputs' k-mer tables).
+// inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -135,6 +135,7 @@ const char *HELP_MAIN =
     "  compare Compare the k-mer counts of two inputs (matrix and set similarity)\n"
     "  profile Per-position k-mer counts and per-sequence min / median / mean / max\n"
     "  setop   Intersect, subtract, union or xor the k-mer sets of two inputs\n"
+    "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
 
@@ -652,6 +653,75 @@ int cmd_profile(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_SKETCH =
+    "MinHash sketches of sequences and the Mash distances between them\n\n"
+    "A record's sketch is the --sketch-size smallest distinct hashes of its canonical k-mers (windows over a non-ACGT base\n"
+    "are none), hash = splitmix64 finaliser of (k-mer xor --seed).  Writes {output}/sketch.tsv: one line per record in input\n"
+    "order with its name (the header up to the first white space), length, k-mers, sketch size and the hashes, decimal,\n"
+    "ascending, comma-separated (empty at size 0), tab-separated.  With --single one sketch of the whole input: its name is\n"
+    "the input's file name, its length the total number of bases.  With --alt-input the second input's sketches go to\n"
+    "{output}/sketch.alt.tsv.  With --dist also {output}/sketch.dist, one line \"id_a<TAB>id_b<TAB>shared/denom<TAB>jaccard<TAB>distance\"\n"
+    "per pair: the pairs i < j of the input, or every pair (record of the input, record of the alt input); denom = min(sketch\n"
+    "size, hashes of the union), shared = those of the denom smallest of the union that both hold, jaccard = shared / denom,\n"
+    "distance = 1 when nothing is shared, else min(1, -ln(2j / (1 + j)) / k) (Mash).\n\n"
+    "Usage: kmertools sketch [OPTIONS] --input <INPUT> --output <OUTPUT>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size (1..31) [default: 21]\n"
+    "  -s, --sketch-size <S>        Hashes per sketch (1..16384) [default: 1000]\n"
+    "      --seed <SEED>            Hash seed [default: 0]\n"
+    "      --single                 One sketch for the whole input\n"
+    "  -a, --alt-input <ALT_INPUT>  Second input: its sketches, and the distances input x alt input\n"
+    "      --dist                   Also write sketch.dist\n"
+    "      --max-dist <D>           Keep the lines of sketch.dist with distance <= D (0..1) [default: 1]\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_sketch(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},   {'o', "output", true},    {'k', "k-size", true}, {'s', "sketch-size", true},
+                                     {0, "seed", true},      {0, "single", false},     {'a', "alt-input", true}, {0, "dist", false},
+                                     {0, "max-dist", true},  {'t', "threads", true},   {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_SKETCH);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    // everything is checked before any device work and before the output directory is made
+    const int k = (int)ranged(f, "k-size", 1, 31, false, 21);
+    const uint32_t s = (uint32_t)ranged(f, "sketch-size", 1, KT_SKETCH_MAX_S, false, 1000);
+    const uint64_t seed = ranged(f, "seed", 0, UINT64_MAX, false, 0);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const bool dist = f.count("dist") != 0;
+    double max_dist = 1.0;
+    if (auto it = f.find("max-dist"); it != f.end()) {
+        if (!dist) usage_error("the argument '--max-dist <D>' requires '--dist'");
+        char *end = nullptr;
+        max_dist = strtod(it->second.c_str(), &end);
+        if (it->second.empty() || *end || !(max_dist >= 0.0 && max_dist <= 1.0))
+            usage_error("invalid value '" + it->second + "' for '--max-dist': not a number in 0..=1");
+    }
+    const std::string alt = f.count("alt-input") ? f.at("alt-input") : "";
+    for (const std::string &p : {in, alt}) {
+        if (!p.empty() && format_from_path(p) == SeqFormat::Unknown) {
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    SketchComputer sk(in, out, k, s);
+    sk.set_seed(seed);
+    sk.set_single(f.count("single") != 0);
+    sk.set_alt_path(alt);
+    sk.set_dist(dist, max_dist);
+    if (threads > 0) sk.set_threads(threads);
+    sk.set_device(device);
+    if (std::string e = sk.sketch(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 const char *HELP_SETOP =
     "Intersect, subtract, union or xor the k-mer sets of two inputs\n\n"
     "Counts the canonical k-mers of both inputs.  A k-mer is in the input when min-a <= its count there <= max-a, in the alt\n"
@@ -872,6 +942,7 @@ int main(int argc, char **argv) {
     if (cmd == "correct") return cmd_correct(argc, argv, 2);
     if (cmd == "compare") return cmd_compare(argc, argv, 2);
     if (cmd == "profile") return cmd_profile(argc, argv, 2);
+    if (cmd == "sketch") return cmd_sketch(argc, argv, 2);
     if (cmd == "setop") return cmd_setop(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

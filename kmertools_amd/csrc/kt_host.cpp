@@ -3,6 +3,7 @@
 // Behaviour follows the reference functions cited in include/kmertools_hip.h; the
 // implementations are this library's own (enumeration in ascending order instead
 // of HashSet+sort, bit tricks instead of per-base loops).
+#include <math.h>
 #include <string.h>
 
 #include <new>
@@ -355,6 +356,14 @@ int kt_cgr_coords(int k, double vecsize, double *xy) {
 
 uint32_t kt_owner_of(uint64_t kmer, uint32_t n_owners) {
     return n_owners ? ktd::owner_of(kmer, n_owners) : 0;
+}
+
+double kt_mash_distance(uint32_t shared, uint32_t denom, int k) {
+    if (!shared || !denom || k < 1) return 1.0;
+    if (shared >= denom) return 0.0;
+    const double j = (double)shared / (double)denom;
+    const double d = -log(2.0 * j / (1.0 + j)) / (double)k;
+    return d > 1.0 ? 1.0 : d;
 }
 
 }  // extern "C"

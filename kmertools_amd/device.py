@@ -87,6 +87,12 @@ def shard_owner_of(kmer, k, n_ranks):
     return int(_lib.lib().kt_shard_owner_of(int(kmer), int(k), int(n_ranks)))
 
 
+def mash_distance(shared, denom, k):
+    """the Mash distance of a sketch pair: 1 when nothing is shared, else min(1, -ln(2j / (1 + j)) / k) with
+    j = shared / denom (kt_mash_distance, the one implementation of the formula)"""
+    return float(_lib.lib().kt_mash_distance(int(shared), int(denom), int(k)))
+
+
 def to_csr(seqs):
     """list[str|bytes] -> (bases u8[total], offsets u64[n+1])"""
     bs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
@@ -337,6 +343,64 @@ class Context:
                                           int(min_support), int(max_corrections), _ptr(out_bases), _ptr(n_single),
                                           _ptr(n_ambiguous), mem))
         return out_bases, n_single, n_ambiguous
+
+    # -- sketch: bottom-s MinHash sketches, their unions, all-pairs merge walks -----------------
+    def sketch(self, bases, offsets, n_reads, k, s, hashes, sizes, n_kmers=None, seed=0, mem=KT_MEM_DEVICE):
+        """row i of hashes (u64, n_reads x s) = the s smallest distinct mix64(canonical k-mer ^ seed) of read i, ascending,
+        KT_EMPTY_KEY behind sizes[i] (u32) of them; n_kmers (u32, may be None) = the read's windows (kt_sketch_batch)"""
+        check(_lib.lib().kt_sketch_batch(self._h, _ptr(bases), _ptr(offsets), int(n_reads), int(k), int(s), int(seed),
+                                         _ptr(hashes), _ptr(sizes), _ptr(n_kmers), mem))
+
+    def sketch_host(self, bases, offsets, k, s, seed=0):
+        """-> (hashes u64[n, s], sizes u32[n], n_kmers u32[n])"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        hashes = np.zeros((n, int(s)), np.uint64)
+        sizes, n_kmers = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        if n:
+            self.sketch(bases if bases.size else np.zeros(1, np.uint8), offsets, n, k, s, hashes, sizes, n_kmers, seed,
+                        KT_MEM_HOST)
+        return hashes, sizes, n_kmers
+
+    def sketch_merge(self, hashes, sizes, group_offsets, out_hashes=None, out_sizes=None, s=None, mem=KT_MEM_HOST):
+        """row g of the result = the bottom-s of the union of rows group_offsets[g] .. group_offsets[g+1] of hashes
+        (kt_sketch_merge).  Host arrays: -> (out_hashes u64[n_groups, s], out_sizes u32[n_groups]); device tensors
+        (mem=KT_MEM_DEVICE): out_hashes, out_sizes and s are given, n and n_groups are taken from sizes / group_offsets."""
+        if mem == KT_MEM_HOST:
+            hashes = np.ascontiguousarray(hashes, np.uint64)
+            sizes = np.ascontiguousarray(sizes, np.uint32)
+            group_offsets = np.ascontiguousarray(group_offsets, np.uint64)
+            s = int(hashes.shape[1]) if s is None else int(s)
+            n_groups = len(group_offsets) - 1
+            out_hashes, out_sizes = np.zeros((n_groups, s), np.uint64), np.zeros(n_groups, np.uint32)
+        else:
+            n_groups = len(group_offsets) - 1
+        check(_lib.lib().kt_sketch_merge(self._h, _ptr(hashes), _ptr(sizes), len(sizes), int(s), _ptr(group_offsets),
+                                         n_groups, _ptr(out_hashes), _ptr(out_sizes), mem))
+        return out_hashes, out_sizes
+
+    def sketch_pairs(self, a_hashes, a_sizes, n_a, b_hashes, b_sizes, n_b, s, shared, denom=None, mem=KT_MEM_DEVICE):
+        """shared / denom (u32, n_a x n_b, denom may be None): Mash's merge walk of every (row of a, row of b)
+        (kt_sketch_pairs); b may be a itself"""
+        check(_lib.lib().kt_sketch_pairs(self._h, _ptr(a_hashes), _ptr(a_sizes), int(n_a), _ptr(b_hashes), _ptr(b_sizes),
+                                         int(n_b), int(s), _ptr(shared), _ptr(denom), mem))
+
+    def sketch_pairs_host(self, a_hashes, a_sizes, b_hashes=None, b_sizes=None):
+        """-> (shared u32[n_a, n_b], denom u32[n_a, n_b]); without b: a against itself"""
+        a_hashes = np.ascontiguousarray(a_hashes, np.uint64)
+        a_sizes = np.ascontiguousarray(a_sizes, np.uint32)
+        if b_hashes is None:
+            b_hashes, b_sizes = a_hashes, a_sizes
+        else:
+            b_hashes = np.ascontiguousarray(b_hashes, np.uint64)
+            b_sizes = np.ascontiguousarray(b_sizes, np.uint32)
+        s = int(a_hashes.shape[1])
+        assert b_hashes.shape[1] == s
+        shared = np.zeros((len(a_sizes), len(b_sizes)), np.uint32)
+        denom = np.zeros_like(shared)
+        self.sketch_pairs(a_hashes, a_sizes, len(a_sizes), b_hashes, b_sizes, len(b_sizes), s, shared, denom, KT_MEM_HOST)
+        return shared, denom
 
     def synth_reads(self, seed, n_reads, read_len, bases_dev, offsets_dev=None, noise=False, genome_len=0,
                     first_read=0):
