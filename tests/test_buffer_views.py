@@ -14,14 +14,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from read_batches import (ACGT, GUARD, SLACK, Batch, Fenced, HostFenced, bases_view, host_bases_view,  # noqa: F401
+                          noisy_reads, offsets_view)
+
 pytestmark = pytest.mark.gpu
 
 SHIFTS = (0, 1, 2, 3, 4, 5, 8, 12, 15, 16, 17, 31)   # odd, 4-aligned but not 16-aligned, aligned
 CTR_SHIFTS = (0, 1, 3, 4, 15)                       # 1 and 3: the halo of kt_segment.hpp through the byte path
-SLACK = 4096
-GUARD = 0xA5
 U32_MAX = 0xFFFFFFFF
-ACGT = np.frombuffer(b"ACGT", np.uint8)
 
 
 @pytest.fixture(scope="module")
@@ -49,41 +49,6 @@ def hctx():
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------
 
-class Batch:
-    def __init__(self, name, seqs):
-        from kmertools_amd import device
-        self.name, self.seqs = name, seqs
-        self.bases, self.offsets = device.to_csr(seqs)
-        self.n = len(seqs)
-        self.total = int(self.offsets[-1])
-
-
-def noisy_reads(seed, n, max_len=400):
-    """empty reads, reads shorter than k, N runs, lower case, U, raw 0..3 codes, IUPAC bytes, reads over several 8192-base
-    segments; the batch ends off a 16- and a 32-byte boundary"""
-    rng = np.random.default_rng(seed)
-    lens = rng.integers(0, max_len, size=n)
-    lens[:8] = (0, 1, 2, 31, 64, 0, 9000, 8192)
-    seqs = []
-    for L in lens:
-        s = ACGT[rng.integers(0, 4, size=L)].copy()
-        if L:
-            m = rng.random(L)
-            s[m < 0.01] = ord("N")
-            s[(m > 0.01) & (m < 0.05)] |= 0x20
-            s[(m > 0.05) & (m < 0.055)] = ord("U")
-            s[(m > 0.055) & (m < 0.057)] = 2
-            s[(m > 0.057) & (m < 0.059)] = ord("R")
-        if L > 100 and rng.random() < 0.1:
-            a = int(rng.integers(0, L - 30))
-            s[a:a + 25] = ord("N")
-        seqs.append(s.tobytes())
-    total = sum(len(s) for s in seqs)
-    tail = next(t for t in range(1, 40) if (total + t) % 16)
-    seqs.append(ACGT[rng.integers(0, 4, size=tail)].tobytes())
-    return seqs
-
-
 def equal_reads(seed, n=1001, L=150):
     """reads of one length >= 16 (kt_oligo.hip's non-general tiles), N and lower case sprinkled in; n odd: the batch
     ends off a 16-byte boundary"""
@@ -105,86 +70,6 @@ def equal():
     b = Batch("equal", equal_reads(0x5eee))
     assert b.total % 16
     return b
-
-
-def _place(addr, slack, mod):
-    """offset from addr of the first address >= addr + slack that is `mod` past a 256-byte boundary"""
-    return ((addr + slack + 255) & ~255) + mod - addr
-
-
-def bases_view(torch, bases, shift, slack=SLACK, seed=0):
-    """the bases inside one device buffer of random ACGT bytes, starting `shift` bytes after a 256-byte boundary, with
-    >= slack bytes of poison on both sides"""
-    n = len(bases)
-    raw = torch.from_numpy(ACGT[np.random.default_rng(seed + 1000 * shift).integers(0, 4, size=2 * slack + 512 + n)]).cuda()
-    start = _place(raw.data_ptr(), slack, shift)
-    v = raw[start:start + n]
-    if n:
-        v.copy_(torch.from_numpy(np.ascontiguousarray(bases)))
-    assert v.data_ptr() % 256 == shift and raw.numel() - (start + n) >= slack
-    return v
-
-
-def offsets_view(torch, offsets):
-    """the int64 offsets at an address that is 8 mod 16 (one leading element)"""
-    raw = torch.zeros(len(offsets) + 2, dtype=torch.int64, device="cuda")
-    raw[1:len(offsets) + 1] = torch.from_numpy(np.asarray(offsets).astype(np.int64))
-    v = raw[1:len(offsets) + 1]
-    assert v.data_ptr() % 16 == 8
-    return v
-
-
-def host_bases_view(bases, shift, slack=SLACK):
-    """host-mode counterpart of bases_view: a numpy slice at `shift` past a 256-byte boundary inside random ACGT"""
-    n = len(bases)
-    raw = ACGT[np.random.default_rng(7 + shift).integers(0, 4, size=2 * slack + 512 + n)]
-    start = _place(raw.ctypes.data, slack, shift)
-    v = raw[start:start + n]
-    v[:] = bases
-    return v
-
-
-class Fenced:
-    """a device output of `shape` / `dtype` at `align` past a 256-byte boundary, inside guard bands of GUARD bytes;
-    prefill: the body's initial value (default: the guard byte itself)"""
-
-    def __init__(self, torch, shape, dtype, guard=4096, align=0, prefill=None):
-        shape = tuple(shape) if isinstance(shape, (tuple, list)) else (int(shape),)
-        nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((2 * guard + 512 + nbytes,), GUARD, dtype=torch.uint8, device="cuda")
-        self.lo = _place(self.raw.data_ptr(), guard, align)
-        self.hi = self.lo + nbytes
-        self.t = self.raw[self.lo:self.hi].view(dtype).view(shape)
-        assert self.t.data_ptr() % 256 == align
-        if prefill is not None:
-            self.t.copy_(torch.as_tensor(prefill).to(dtype).view(shape))
-
-    def check(self, what=""):
-        head = self.raw[:self.lo].cpu().numpy()
-        tail = self.raw[self.hi:].cpu().numpy()
-        assert (head == GUARD).all(), ("written before the output", what, self.lo - np.flatnonzero(head != GUARD)[-8:])
-        assert (tail == GUARD).all(), ("written after the output", what, np.flatnonzero(tail != GUARD)[:8])
-
-    def np(self, dtype):
-        return self.t.cpu().numpy().view(dtype)
-
-
-class HostFenced:
-    """the same for host-mode calls: a numpy body between guard bands"""
-
-    def __init__(self, shape, dtype, guard=4096, prefill=None):
-        shape = tuple(shape) if isinstance(shape, (tuple, list)) else (int(shape),)
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        self.raw = np.full(2 * guard + nbytes, GUARD, np.uint8)
-        self.lo, self.hi = guard, guard + nbytes
-        self.a = self.raw[self.lo:self.hi].view(dtype).reshape(shape)
-        if prefill is not None:
-            self.a[...] = prefill
-
-    def check(self, what=""):
-        assert (self.raw[:self.lo] == GUARD).all(), ("written before the output", what)
-        assert (self.raw[self.hi:] == GUARD).all(), ("written after the output", what,
-                                                     np.flatnonzero(self.raw[self.hi:] != GUARD)[:8])
 
 
 # ---- oracle answers, computed once per module ------------------------------------------------------------------------
