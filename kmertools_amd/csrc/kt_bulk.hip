@@ -3372,13 +3372,14 @@ int finish_typed(kt_ctr *ctr, kt_bulk_job &j) {
 // in a partitioned mode may show one XCD: one set then, and a region is one plain stream).
 static int xcc_sets(kt_ctx *ctx, uint32_t *nxs, uint32_t *xmap) {
     if (!ctx->xcc_n) {
-        if (int rc = ctx->s_aux2.reserve(256)) return rc;
-        uint32_t *mask = (uint32_t *)ctx->s_aux2.p, h = 0;
+        uint32_t *mask = nullptr, h = 0;
+        if (int rc = ctx->claim(kt::AUX2, 256, "xcc_sets", &mask)) return rc;
         KT_HIP(hipMemsetAsync(mask, 0, 4, ctx->stream));
         hipLaunchKernelGGL(xcc_census_kernel, dim3((uint32_t)ctx->n_cu * 4), dim3(64), 0, ctx->stream, mask);
         KT_HIP(hipGetLastError());
         KT_HIP(hipMemcpyAsync(&h, mask, 4, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->unclaim(kt::AUX2);  // (read back: whoever plans the job may hold AUX2 next)
         if (!(h & 0xFFu)) h = 1;
         uint32_t n = 0, map = 0;
         for (uint32_t id = 0; id < 8; id++)
@@ -3649,10 +3650,11 @@ int kt_ctr_count_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs)
     ctr->stage_n = 0;
     if (int rc = ktl::table_ready(ctr)) return rc;  // (a dense table gets its probing image, a deferred clear happens now)
     ctr->empty = false;
-    if (int rc = ctx->s_aux2.reserve(h.size() * 8)) return rc;
-    KT_HIP(hipMemcpyAsync(ctx->s_aux2.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint64_t *d = nullptr;
+    if (int rc = ctx->claim(kt::AUX2, h.size() * 8, "kt_ctr_count_records", &d)) return rc;
+    KT_HIP(hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     KT_HIP(hipStreamSynchronize(ctx->stream));  // (h lives on this frame)
-    RecordSource src{(const ktsk::RecRun *)ctx->s_aux2.p, (const uint64_t *)ctx->s_aux2.p + 2 * (size_t)n_runs, n_runs, (uint32_t)ctr->k, blocks};
+    RecordSource src{(const ktsk::RecRun *)d, (const uint64_t *)d + 2 * (size_t)n_runs, n_runs, (uint32_t)ctr->k, blocks};
     TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
     hipLaunchKernelGGL(count_records_kernel, dim3(ktl::grid_for(ctx, blocks, 8)), dim3(BLOCK), 0, ctx->stream, src, t, ctr->distinct);
     KT_HIP(hipGetLastError());
@@ -3690,8 +3692,8 @@ int kt_bulk_build(kt_ctr *ctr, const uint8_t *d_bases, const uint64_t *d_offsets
     if (int rc = kt_bulk_begin(ctr, n_seg * ktseg::SEG, &eligible)) return rc;  // at most one k-mer per base
     if (!eligible) return KT_OK;
     // the segment index (seg_first) lives in ctx scratch; same helper kernel as the other paths
-    if (int rc = ctx->s_aux0.reserve((n_seg + 2) * sizeof(uint64_t))) return rc;
-    uint64_t *seg_first = (uint64_t *)ctx->s_aux0.p;
+    uint64_t *seg_first = nullptr;
+    if (int rc = ctx->claim(kt::AUX0, (n_seg + 2) * sizeof(uint64_t), "kt_bulk_build", &seg_first)) return rc;
     hipLaunchKernelGGL(ktseg::seg_index_kernel, dim3((uint32_t)((n_reads + 1 + 255) / 256)), dim3(256), 0, ctx->stream,
                        d_offsets, n_reads, seg_first, n_seg);
     // A pass of its own packs the reads (16 bytes per 32 bases: codes, invalid-base mask, read-start mask - what stage_segment
@@ -3774,8 +3776,8 @@ int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uin
     }
     const uint32_t RS = ctr->m8 << (LOG2_S - 3);
     const uint64_t n_ranges = ctr->cap / RS, n_tiles = (n_ranges + XT - 1) / XT;
-    if (int rc = ctx->s_aux0.reserve((n_tiles + 1) * 8)) return rc;
-    uint64_t *tiles = (uint64_t *)ctx->s_aux0.p;
+    uint64_t *tiles = nullptr;
+    if (int rc = ctx->claim(kt::AUX0, (n_tiles + 1) * 8, "kt_table_dense_export", &tiles)) return rc;
     hipLaunchKernelGGL(tile_sums_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, ctr->range_counts, n_ranges, tiles);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles);
     if (max_out)
@@ -3789,14 +3791,14 @@ int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uin
 
 // the same restricted to the entries with lo <= occurrences <= hi of a dense table whose ranges are its own slots (not an
 // export target): a counting pass over the ranges' counts (kept per range + tile sums), the tile scan, the filtered copy.
-// *n = the entries kept.  Scratch: the tile offsets and one u32 per range, next to each other in the context's s_aux0.
+// *n = the entries kept.  Scratch: the tile offsets and one u32 per range, next to each other in the context's AUX0.
 int kt_table_dense_export_range(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint32_t lo, uint32_t hi,
                                 uint64_t *n) {
     kt_ctx *ctx = ctr->ctx;
     const uint32_t RS = ctr->m8 << (LOG2_S - 3);
     const uint64_t n_ranges = ctr->cap / RS, n_tiles = (n_ranges + XT - 1) / XT;
-    if (int rc = ctx->s_aux0.reserve((n_tiles + 1) * 8 + n_ranges * 4)) return rc;
-    uint64_t *tiles = (uint64_t *)ctx->s_aux0.p;
+    uint64_t *tiles = nullptr;
+    if (int rc = ctx->claim(kt::AUX0, (n_tiles + 1) * 8 + n_ranges * 4, "kt_table_dense_export_range", &tiles)) return rc;
     uint32_t *kept = (uint32_t *)(tiles + n_tiles + 1);
     hipLaunchKernelGGL(dense_kept_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS, n_ranges,
                        ctr->range_counts, lo, hi, kept, tiles);

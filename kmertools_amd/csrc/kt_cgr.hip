@@ -251,45 +251,39 @@ using namespace ktl;
 extern "C" int kt_cgr_points(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                              double vecsize, double *xy, uint64_t *bad_pos, int mem) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_cgr_points: null ctx");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_cgr_points: bad mem");
-    if (!(vecsize >= 0.0)) return kt::fail(KT_ERR_ARG, "kt_cgr_points: vecsize must be >= 0");
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
+    Call call(ctx, mem, "kt_cgr_points");
+    if (int rc = call.enter()) return rc;
+    if (!(vecsize >= 0.0)) return call.fail("vecsize must be >= 0");
     if (n_reads) {
-        if (!offsets) return kt::fail(KT_ERR_ARG, "kt_cgr_points: null offsets");
-        if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
+        if (!offsets) return call.fail("null offsets");
+        if (int rc = call.batch(bases, offsets, n_reads, nullptr)) return rc;
     }
+    const uint64_t total = call.total;
     // device scalar for the first bad index
-    if (int rc = ctx->s_aux2.reserve(64)) return rc;
-    unsigned long long *d_bad = (unsigned long long *)ctx->s_aux2.p;
+    unsigned long long *d_bad = nullptr;
+    if (int rc = call.scratch(kt::AUX2, 64, &d_bad)) return rc;
     KT_HIP(hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
     if (total) {
-        if (!bases || !xy) return kt::fail(KT_ERR_ARG, "kt_cgr_points: null buffer");
-        const uint8_t *d_bases = bases;
-        const uint64_t *d_offsets = offsets;
-        double *d_out = xy;
-        if (mem == KT_MEM_HOST) {
-            if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-            if (int rc = ctx->s_out.reserve(total * 16)) return rc;
-            d_out = (double *)ctx->s_out.p;
-        }
+        if (!bases || !xy) return call.fail("null buffer");
+        if (int rc = call.stage()) return rc;
+        double *d_out = nullptr;
+        if (int rc = call.out(kt::OUT, xy, total * 2, &d_out)) return rc;
         ktseg::SegArgs sa;
-        if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, 1, &sa)) return rc;
+        if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, total, 1, &sa)) return rc;
         CgrShape a{n_reads, total, vecsize};
         const uint64_t n_span = (total + SPAN - 1) / SPAN;
         const uint32_t grid = (uint32_t)((n_span + WAVES - 1) / WAVES);
-        hipLaunchKernelGGL(cgr_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, d_bases, d_offsets, sa.seg_first, a,
+        hipLaunchKernelGGL(cgr_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, call.bases, call.offsets, sa.seg_first, a,
                            (double2 *)d_out, d_bad);
         KT_HIP(hipGetLastError());
-        if (mem == KT_MEM_HOST) KT_HIP(hipMemcpyAsync(xy, d_out, total * 16, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (mem == KT_MEM_DEVICE) {
+    if (!call.host()) {
         if (bad_pos) KT_HIP(hipMemcpyAsync(bad_pos, d_bad, 8, hipMemcpyDeviceToDevice, ctx->stream));
         return KT_OK;
     }
-    uint64_t bad = ~0ull;
-    KT_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
+    unsigned long long bad = ~0ull;
+    call.back(&bad, (const unsigned long long *)d_bad, 1);
+    if (int rc = call.finish()) return rc;
     if (bad_pos) *bad_pos = bad;
     if (bad != ~0ull) return kt::fail(KT_ERR_BADNT, "Bad nucleotide, unable to proceed");  // cgr.rs:140
     return KT_OK;

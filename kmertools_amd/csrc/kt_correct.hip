@@ -321,8 +321,8 @@ static int support_device(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, co
     SegArgs a;
     if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
     const uint64_t n_words = a.n_seg * BLOCK + 1;
-    if (int rc = ctx->s_aux1.reserve(n_words * 4)) return rc;
-    uint32_t *d_todo = (uint32_t *)ctx->s_aux1.p;
+    uint32_t *d_todo = nullptr;
+    if (int rc = ctx->claim(kt::AUX1, n_words * 4, "kt_ctr_correct_support", &d_todo)) return rc;
     TodoArgs t{d_profile, min_count, max_count, d_todo, n_words};
     hipLaunchKernelGGL(todo_kernel, dim3(grid_for(ctx, (n_words + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream, a, t);
     KT_HIP(hipGetLastError());
@@ -338,42 +338,32 @@ extern "C" int kt_ctr_correct_support(kt_ctr *table, const uint8_t *bases, const
     if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: null table");
     if (min_count == 0) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: min_count must be >= 1");
     if (min_count > max_count) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: min_count > max_count");
-    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: need part < n_parts");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: bad mem");
-    if (table->n_owners > 1)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: the table is one shard of a sharded table - shards are not supported "
-                                    "(a shard cannot tell a k-mer absent here from one absent everywhere)");
-    if (n_reads == 0) return KT_OK;
-    if (!offsets || !profile || !support) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: null buffer");
     kt_ctx *ctx = table->ctx;
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
+    Call call(ctx, mem, "kt_ctr_correct_support");
+    if (int rc = call.check_part(n_parts, part)) return rc;
+    if (int rc = call.enter()) return rc;
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !profile || !support) return call.fail("null buffer");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    const uint64_t total = call.total;
     if (!total) return KT_OK;
-    if (!bases) return kt::fail(KT_ERR_ARG, "kt_ctr_correct_support: null bases");
     if (int rc = table_ready(table)) return rc;
-    if (mem == KT_MEM_DEVICE)
-        return support_device(table, ctx, bases, offsets, n_reads, total, profile, min_count, max_count, support, n_parts, part);
-    // host arrays: this call's support is made on the device from zero and added to the caller's
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
-    if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-    if (int rc = ctx->s_out.reserve(total * 4)) return rc;
-    if (int rc = ctx->s_aux2.reserve(total * 4)) return rc;
-    uint32_t *d_profile = (uint32_t *)ctx->s_out.p, *d_support = (uint32_t *)ctx->s_aux2.p;
-    KT_HIP(hipMemcpyAsync(d_profile, profile, total * 4, hipMemcpyHostToDevice, ctx->stream));
-    KT_HIP(hipMemsetAsync(d_support, 0, total * 4, ctx->stream));
-    if (int rc = support_device(table, ctx, d_bases, d_offsets, n_reads, total, d_profile, min_count, max_count, d_support, n_parts, part))
+    if (int rc = call.stage()) return rc;
+    const uint32_t *d_profile = nullptr;
+    uint32_t *d_support = support;
+    if (int rc = call.in(kt::OUT, profile, total, &d_profile)) return rc;
+    if (call.host()) {  // host arrays: this call's support is made on the device from zero and added to the caller's
+        if (int rc = call.scratch(kt::AUX2, total * 4, &d_support)) return rc;
+        KT_HIP(hipMemsetAsync(d_support, 0, total * 4, ctx->stream));
+    }
+    if (int rc = support_device(table, ctx, call.bases, call.offsets, n_reads, total, d_profile, min_count, max_count, d_support, n_parts, part))
         return rc;
-    uint32_t *tmp = (uint32_t *)malloc(total * 4);
-    if (!tmp) return kt::fail(KT_ERR_NOMEM, "kt_ctr_correct_support: host alloc");
-    hipError_t e = hipMemcpyAsync(tmp, d_support, total * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess)
-        for (uint64_t i = 0; i < total; i++)
-            if (tmp[i]) support[i] += tmp[i];
-    free(tmp);
-    if (e != hipSuccess) return kt::fail(KT_ERR_HIP, std::string("kt_ctr_correct_support: ") + hipGetErrorString(e));
+    if (!call.host()) return KT_OK;
+    std::unique_ptr<uint32_t[]> h;
+    if (int rc = call.fetch((const uint32_t *)d_support, total, &h)) return rc;
+    for (uint64_t i = 0; i < total; i++)
+        if (h[i]) support[i] += h[i];
     return KT_OK;
 }
 
@@ -401,44 +391,38 @@ extern "C" int kt_correct_apply(kt_ctx *ctx, const uint8_t *bases, const uint64_
                                 uint32_t *n_ambiguous, int mem) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_correct_apply: null ctx");
     if (min_support == 0 || min_support > 255) return kt::fail(KT_ERR_ARG, "kt_correct_apply: min_support must be in 1..255");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_correct_apply: bad mem");
+    Call call(ctx, mem, "kt_correct_apply");
+    if (int rc = call.enter()) return rc;
     if (n_reads == 0) return KT_OK;
-    if (!offsets) return kt::fail(KT_ERR_ARG, "kt_correct_apply: null buffer");
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && (!bases || !support)) return kt::fail(KT_ERR_ARG, "kt_correct_apply: null buffer");
-    bool too_long = false;
-    if (int rc = has_read_of_2_32(ctx, offsets, n_reads, total, mem, &too_long)) return rc;
-    if (too_long) return kt::fail(KT_ERR_ARG, "kt_correct_apply: a read of 2^32 bases or more (the numbers of bases are u32)");
+    if (!offsets) return call.fail("null buffer");
+    if (int rc = call.batch(bases, offsets, n_reads, "null buffer")) return rc;
+    const uint64_t total = call.total;
+    if (total && !support) return call.fail("null buffer");
+    if (int rc = call.refuse_long_reads("the numbers of bases are u32")) return rc;
     if (!out_bases && !n_single && !n_ambiguous) return KT_OK;
     const bool limit = max_corrections != 0 && out_bases;  // the write pass then needs n_single whether the caller wants it or not
 
-    if (mem == KT_MEM_DEVICE) {
+    if (!call.host()) {
         uint32_t *d_single = n_single;
-        if (!d_single && limit) {
-            if (int rc = ctx->s_aux2.reserve(n_reads * 4)) return rc;
-            d_single = (uint32_t *)ctx->s_aux2.p;
-        }
+        if (!d_single && limit)
+            if (int rc = call.scratch(kt::AUX2, n_reads * 4, &d_single)) return rc;
         return apply_device(ctx, bases, offsets, n_reads, total, support, min_support, max_corrections, out_bases, d_single, n_ambiguous);
     }
     // host arrays: staged in ctx scratch, the outputs the caller asked for made there and copied back
-    const uint8_t *d_bases = nullptr;
-    const uint64_t *d_offsets = nullptr;
-    if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-    if (int rc = ctx->s_aux1.reserve(total * 4 + 4)) return rc;
-    if (int rc = ctx->s_out.reserve(total + 4)) return rc;
-    if (int rc = ctx->s_aux2.reserve(n_reads * 8)) return rc;
-    uint32_t *d_support = (uint32_t *)ctx->s_aux1.p;
-    uint8_t *d_out = out_bases ? (uint8_t *)ctx->s_out.p : nullptr;
-    uint32_t *d_single = (n_single || limit) ? (uint32_t *)ctx->s_aux2.p : nullptr;
-    uint32_t *d_ambiguous = n_ambiguous ? (uint32_t *)ctx->s_aux2.p + n_reads : nullptr;
-    if (total) KT_HIP(hipMemcpyAsync(d_support, support, total * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = apply_device(ctx, d_bases, d_offsets, n_reads, total, d_support, min_support, max_corrections, d_out, d_single, d_ambiguous))
+    if (int rc = call.stage()) return rc;
+    uint32_t *d_support = nullptr, *d_counts = nullptr;  // d_counts: single | ambiguous in one buffer
+    uint8_t *d_room = nullptr;
+    if (int rc = call.scratch(kt::AUX1, total * 4 + 4, &d_support)) return rc;
+    if (int rc = call.scratch(kt::OUT, total + 4, &d_room)) return rc;
+    if (int rc = call.scratch(kt::AUX2, n_reads * 8, &d_counts)) return rc;
+    uint8_t *d_out = out_bases ? d_room : nullptr;
+    uint32_t *d_single = (n_single || limit) ? d_counts : nullptr;
+    uint32_t *d_ambiguous = n_ambiguous ? d_counts + n_reads : nullptr;
+    if (int rc = call.up(d_support, support, total)) return rc;
+    if (int rc = apply_device(ctx, call.bases, call.offsets, n_reads, total, d_support, min_support, max_corrections, d_out, d_single, d_ambiguous))
         return rc;
-    if (out_bases && total) KT_HIP(hipMemcpyAsync(out_bases, d_out, total, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_single) KT_HIP(hipMemcpyAsync(n_single, d_single, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_ambiguous) KT_HIP(hipMemcpyAsync(n_ambiguous, d_ambiguous, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    call.back(out_bases, (const uint8_t *)d_out, total);
+    call.back(n_single, (const uint32_t *)d_single, n_reads);
+    call.back(n_ambiguous, (const uint32_t *)d_ambiguous, n_reads);
+    return call.finish();
 }

@@ -234,13 +234,6 @@ __global__ __launch_bounds__(BLOCK) void solidity_kernel(SegArgs a, SolidArgs c)
     }
 }
 
-// flag = 1 when a read holds 2^32 bases or more (its positions would not fit the u32 first_weak)
-__global__ __launch_bounds__(BLOCK) void long_read_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads,
-                                                          uint32_t *__restrict__ flag) {
-    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * BLOCK)
-        if (offsets[i + 1] - offsets[i] >= (1ull << 32)) atomicOr(flag, 1u);
-}
-
 // ---- per-position k-mer counts (kt_ctr_profile) --------------------------------------------------------------------
 // The simplest sink there is: the count of the window that starts at global base s goes to profile[s] - no read lookup, no
 // LDS image, nothing combined.  Only the valid windows of this hash partition are stored (the caller's fill stays everywhere
@@ -305,26 +298,6 @@ __global__ __launch_bounds__(BLOCK) void cov_finalize_kernel(const uint32_t *__r
 
 using namespace ktl;
 
-// *too_long = a read of the batch holds 2^32 bases or more (a device read-back for KT_MEM_DEVICE; uses ctx scratch s_aux2)
-int ktl::has_read_of_2_32(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int mem, bool *too_long) {
-    *too_long = false;
-    if (total < (1ull << 32)) return KT_OK;  // (below that no read can be this long)
-    if (mem == KT_MEM_HOST) {
-        for (uint64_t i = 0; i < n_reads && !*too_long; i++) *too_long = offsets[i + 1] - offsets[i] >= (1ull << 32);
-        return KT_OK;
-    }
-    if (int rc = ctx->s_aux2.reserve(4)) return rc;
-    uint32_t *d_flag = (uint32_t *)ctx->s_aux2.p, flag = 0;
-    KT_HIP(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(long_read_kernel, dim3(grid_for(ctx, (n_reads + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
-                       offsets, n_reads, d_flag);
-    KT_HIP(hipGetLastError());
-    KT_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    *too_long = flag != 0;
-    return KT_OK;
-}
-
 // the lookup pass: u32 bin counts of the reads' k-mers (those of hash partition `part` of n_parts) into d_counts
 static int cov_counts(kt_ctr *table, kt_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                       uint64_t total, uint64_t bin_size, uint64_t bin_count, uint32_t *d_counts, uint32_t n_parts,
@@ -345,63 +318,46 @@ extern "C" int kt_cov_batch_part(kt_ctr *table, const uint8_t *bases, const uint
     if (!table) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: null table");
     if (bin_size == 0) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: bin_size must be >= 1");
     if (bin_count == 0 || bin_count > 0xFFFFFFFFull) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: bin_count must be in 1..2^32-1");
-    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: need part < n_parts");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: bad mem");
-    if (n_reads == 0) return KT_OK;
-    if (!offsets || !counts) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: null buffer");
     kt_ctx *ctx = table->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_cov_batch_part");
+    if (int rc = call.check_part(n_parts, part)) return rc;
+    if (int rc = call.enter()) return rc;
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !counts) return call.fail("null buffer");
     if (int rc = table_ready(table)) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_cov_batch_part: null bases");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
     const uint64_t n_cells = n_reads * bin_count;
-    if (mem == KT_MEM_DEVICE) return cov_counts(table, ctx, bases, offsets, n_reads, total, bin_size, bin_count, counts, n_parts, part);
-    // host rows: this call's counts are made on the device from zero and added to the caller's
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
-    if (total)
-        if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-    if (int rc = ctx->s_aux1.reserve(n_cells * 4)) return rc;
-    uint32_t *d_counts = (uint32_t *)ctx->s_aux1.p;
-    KT_HIP(hipMemsetAsync(d_counts, 0, n_cells * 4, ctx->stream));
-    if (int rc = cov_counts(table, ctx, d_bases, d_offsets, n_reads, total, bin_size, bin_count, d_counts, n_parts, part)) return rc;
-    uint32_t *tmp = (uint32_t *)malloc(n_cells * 4);
-    if (!tmp) return kt::fail(KT_ERR_NOMEM, "kt_cov_batch_part: host alloc");
-    hipError_t e = hipMemcpyAsync(tmp, d_counts, n_cells * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess)
-        for (uint64_t i = 0; i < n_cells; i++) counts[i] += tmp[i];
-    free(tmp);
-    if (e != hipSuccess) return kt::fail(KT_ERR_HIP, std::string("kt_cov_batch_part: ") + hipGetErrorString(e));
+    uint32_t *d_counts = counts;
+    if (call.host()) {  // host rows: this call's counts are made on the device from zero and added to the caller's
+        if (call.total)
+            if (int rc = call.stage()) return rc;
+        if (int rc = call.scratch(kt::AUX1, n_cells * 4, &d_counts)) return rc;
+        KT_HIP(hipMemsetAsync(d_counts, 0, n_cells * 4, ctx->stream));
+    }
+    if (int rc = cov_counts(table, ctx, call.bases, call.offsets, n_reads, call.total, bin_size, bin_count, d_counts, n_parts, part)) return rc;
+    if (!call.host()) return KT_OK;
+    std::unique_ptr<uint32_t[]> h;
+    if (int rc = call.fetch((const uint32_t *)d_counts, n_cells, &h)) return rc;
+    for (uint64_t i = 0; i < n_cells; i++) counts[i] += h[i];
     return KT_OK;
 }
 
 extern "C" int kt_ctr_lookup(kt_ctr *table, const uint64_t *keys, uint64_t n, uint32_t *counts, int mem) {
     if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_lookup: null table");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_lookup: bad mem");
-    if (n == 0) return KT_OK;
-    if (!keys || !counts) return kt::fail(KT_ERR_ARG, "kt_ctr_lookup: null buffer");
     kt_ctx *ctx = table->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_ctr_lookup");
+    if (int rc = call.enter()) return rc;
+    if (n == 0) return KT_OK;
+    if (!keys || !counts) return call.fail("null buffer");
     if (int rc = table_ready(table)) return rc;  // (a densely packed table gets its probing image first)
-    const uint64_t *d_keys = keys;
-    uint32_t *d_counts = counts;
-    if (mem == KT_MEM_HOST) {
-        if (int rc = ctx->s_aux1.reserve(n * 8)) return rc;
-        if (int rc = ctx->s_aux2.reserve(n * 4)) return rc;
-        KT_HIP(hipMemcpyAsync(ctx->s_aux1.p, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_keys = (const uint64_t *)ctx->s_aux1.p;
-        d_counts = (uint32_t *)ctx->s_aux2.p;
-    }
+    const uint64_t *d_keys = nullptr;
+    uint32_t *d_counts = nullptr;
+    if (int rc = call.in(kt::AUX1, keys, n, &d_keys)) return rc;
+    if (int rc = call.out(kt::AUX2, counts, n, &d_counts)) return rc;
     hipLaunchKernelGGL(lookup_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
                        probed_of(table), d_keys, n, d_counts);
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) {
-        KT_HIP(hipMemcpyAsync(counts, d_counts, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return KT_OK;
+    return call.finish();
 }
 
 extern "C" int kt_cov_batch(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
@@ -412,38 +368,27 @@ extern "C" int kt_cov_batch(kt_ctr *table, const uint8_t *bases, const uint64_t 
     if (out_dtype != KT_F64 && out_dtype != KT_F32 && out_dtype != KT_U32)
         return kt::fail(KT_ERR_ARG, "kt_cov_batch: bad out_dtype");
     if (out_dtype == KT_U32 && norm) return kt::fail(KT_ERR_ARG, "kt_cov_batch: KT_U32 output needs norm = 0");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_cov_batch: bad mem");
-    if (n_reads == 0) return KT_OK;
-    if (!offsets || !out) return kt::fail(KT_ERR_ARG, "kt_cov_batch: null buffer");
-    if (table->n_owners > 1)
-        return kt::fail(KT_ERR_ARG, "kt_cov_batch: the table is one shard of a sharded table - kt_cov_batch_part on every shard, summed");
     kt_ctx *ctx = table->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_cov_batch");
+    if (int rc = call.enter()) return rc;
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !out) return call.fail("null buffer");
+    if (table->n_owners > 1) return call.fail("the table is one shard of a sharded table - kt_cov_batch_part on every shard, summed");
     if (int rc = table_ready(table)) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_cov_batch: null bases");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
 
     const uint64_t n_cells = n_reads * bin_count;
     const size_t esz = out_dtype == KT_F64 ? 8 : 4;
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
-    void *d_out = out;
-    if (mem == KT_MEM_HOST) {
-        if (total) {
-            if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-        }
-        if (int rc = ctx->s_out.reserve(n_cells * esz)) return rc;
-        d_out = ctx->s_out.p;
-    }
+    if (call.total)
+        if (int rc = call.stage()) return rc;
+    char *d_out = nullptr;
+    if (int rc = call.out(kt::OUT, (char *)out, n_cells * esz, &d_out)) return rc;
     // u32 bin counts: the output itself for KT_U32, otherwise scratch
     uint32_t *d_counts = (uint32_t *)d_out;
-    if (out_dtype != KT_U32) {
-        if (int rc = ctx->s_aux1.reserve(n_cells * 4)) return rc;
-        d_counts = (uint32_t *)ctx->s_aux1.p;
-    }
+    if (out_dtype != KT_U32)
+        if (int rc = call.scratch(kt::AUX1, n_cells * 4, &d_counts)) return rc;
     KT_HIP(hipMemsetAsync(d_counts, 0, n_cells * 4, ctx->stream));
-    if (int rc = cov_counts(table, ctx, d_bases, d_offsets, n_reads, total, bin_size, bin_count, d_counts, 1, 0)) return rc;
+    if (int rc = cov_counts(table, ctx, call.bases, call.offsets, n_reads, call.total, bin_size, bin_count, d_counts, 1, 0)) return rc;
     const uint32_t fb = (uint32_t)((n_reads + BLOCK - 1) / BLOCK);
     if (out_dtype == KT_F64)
         hipLaunchKernelGGL(cov_finalize_kernel<double>, dim3(fb), dim3(BLOCK), 0, ctx->stream, d_counts, n_reads,
@@ -452,11 +397,7 @@ extern "C" int kt_cov_batch(kt_ctr *table, const uint8_t *bases, const uint64_t 
         hipLaunchKernelGGL(cov_finalize_kernel<float>, dim3(fb), dim3(BLOCK), 0, ctx->stream, d_counts, n_reads,
                            (uint32_t)bin_count, norm, (float *)d_out);
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) {
-        KT_HIP(hipMemcpyAsync(out, d_out, n_cells * esz, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return KT_OK;
+    return call.finish();
 }
 
 // the solidity pass into device arrays (combined into: add, add, min)
@@ -481,88 +422,63 @@ extern "C" int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const u
     if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null table");
     if (min_count == 0) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: min_count must be >= 1");
     if (min_count > max_count) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: min_count > max_count");
-    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: need part < n_parts");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: bad mem");
-    if (table->n_owners > 1)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: the table is one shard of a sharded table - shards are not supported "
-                                    "(a shard cannot tell a k-mer absent here from one absent everywhere)");
-    if (n_reads == 0) return KT_OK;
-    if (!offsets || !n_kmers || !n_solid) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null buffer");
     kt_ctx *ctx = table->ctx;
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: null bases");
-    bool too_long = false;
-    if (int rc = ktl::has_read_of_2_32(ctx, offsets, n_reads, total, mem, &too_long)) return rc;
-    if (too_long) return kt::fail(KT_ERR_ARG, "kt_ctr_read_solidity: a read of 2^32 bases or more (positions are u32)");
+    Call call(ctx, mem, "kt_ctr_read_solidity");
+    if (int rc = call.check_part(n_parts, part)) return rc;
+    if (int rc = call.enter()) return rc;
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !n_kmers || !n_solid) return call.fail("null buffer");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    if (int rc = call.refuse_long_reads("positions are u32")) return rc;
     if (int rc = table_ready(table)) return rc;
-    if (mem == KT_MEM_DEVICE)
-        return solidity_counts(table, ctx, bases, offsets, n_reads, total, min_count, max_count, n_kmers, n_solid, first_weak,
+    if (!call.host())
+        return solidity_counts(table, ctx, bases, offsets, n_reads, call.total, min_count, max_count, n_kmers, n_solid, first_weak,
                                n_parts, part);
     // host arrays: this call's numbers are made on the device from 0 / 0 / NO_POS and combined into the caller's
-    if (!total) return KT_OK;
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
-    if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
+    if (!call.total) return KT_OK;
+    if (int rc = call.stage()) return rc;
     const uint64_t n_arr = first_weak ? 3 : 2;
-    if (int rc = ctx->s_aux1.reserve(n_reads * 4 * n_arr)) return rc;
-    uint32_t *d_n = (uint32_t *)ctx->s_aux1.p, *d_s = d_n + n_reads, *d_w = first_weak ? d_s + n_reads : nullptr;
+    uint32_t *d_n = nullptr;
+    if (int rc = call.scratch(kt::AUX1, n_reads * 4 * n_arr, &d_n)) return rc;
+    uint32_t *d_s = d_n + n_reads, *d_w = first_weak ? d_s + n_reads : nullptr;
     KT_HIP(hipMemsetAsync(d_n, 0, n_reads * 8, ctx->stream));
     if (d_w) KT_HIP(hipMemsetAsync(d_w, 0xFF, n_reads * 4, ctx->stream));
-    if (int rc = solidity_counts(table, ctx, d_bases, d_offsets, n_reads, total, min_count, max_count, d_n, d_s, d_w, n_parts, part))
+    if (int rc = solidity_counts(table, ctx, call.bases, call.offsets, n_reads, call.total, min_count, max_count, d_n, d_s, d_w, n_parts, part))
         return rc;
-    uint32_t *tmp = (uint32_t *)malloc(n_reads * 4 * n_arr);
-    if (!tmp) return kt::fail(KT_ERR_NOMEM, "kt_ctr_read_solidity: host alloc");
-    hipError_t e = hipMemcpyAsync(tmp, d_n, n_reads * 4 * n_arr, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) {
-        const uint32_t *tn = tmp, *ts = tmp + n_reads, *tw = tmp + 2 * n_reads;
-        for (uint64_t i = 0; i < n_reads; i++) {
-            n_kmers[i] += tn[i];
-            n_solid[i] += ts[i];
-            if (first_weak && tw[i] < first_weak[i]) first_weak[i] = tw[i];
-        }
+    std::unique_ptr<uint32_t[]> h;
+    if (int rc = call.fetch((const uint32_t *)d_n, n_reads * n_arr, &h)) return rc;
+    const uint32_t *tn = h.get(), *ts = tn + n_reads, *tw = ts + n_reads;
+    for (uint64_t i = 0; i < n_reads; i++) {
+        n_kmers[i] += tn[i];
+        n_solid[i] += ts[i];
+        if (first_weak && tw[i] < first_weak[i]) first_weak[i] = tw[i];
     }
-    free(tmp);
-    if (e != hipSuccess) return kt::fail(KT_ERR_HIP, std::string("kt_ctr_read_solidity: ") + hipGetErrorString(e));
     return KT_OK;
 }
 
 extern "C" int kt_ctr_profile(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *profile,
                               int mem, uint32_t n_parts, uint32_t part) {
     if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: null table");
-    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: need part < n_parts");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: bad mem");
-    if (table->n_owners > 1)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_profile: the table is one shard of a sharded table - shards are not supported "
-                                    "(a shard cannot tell a k-mer absent here from one absent everywhere)");
-    if (n_reads == 0) return KT_OK;
-    if (!offsets || !profile) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: null buffer");
     kt_ctx *ctx = table->ctx;
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (!total) return KT_OK;
-    if (!bases) return kt::fail(KT_ERR_ARG, "kt_ctr_profile: null bases");
+    Call call(ctx, mem, "kt_ctr_profile");
+    if (int rc = call.check_part(n_parts, part)) return rc;
+    if (int rc = call.enter()) return rc;
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (n_reads == 0) return KT_OK;
+    if (!offsets || !profile) return call.fail("null buffer");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    if (!call.total) return KT_OK;
     if (int rc = table_ready(table)) return rc;
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
-    uint32_t *d_profile = profile;
-    if (mem == KT_MEM_HOST) {  // the caller's entries go up and come back: what this part does not write stays as it was
-        if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-        if (int rc = ctx->s_out.reserve(total * 4)) return rc;
-        d_profile = (uint32_t *)ctx->s_out.p;
-        KT_HIP(hipMemcpyAsync(d_profile, profile, total * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (int rc = call.stage()) return rc;
+    // (host: the caller's entries go up and come back: what this part does not write stays as it was)
+    uint32_t *d_profile = nullptr;
+    if (int rc = call.out(kt::OUT, profile, call.total, &d_profile)) return rc;
+    if (int rc = call.up(d_profile, (const uint32_t *)profile, call.total)) return rc;
     SegArgs a;
-    if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, table->k, &a)) return rc;
+    if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, table->k, &a)) return rc;
     ProfileArgs c{probed_of(table, n_parts, part), d_profile};
     hipLaunchKernelGGL(profile_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, c);
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) {
-        KT_HIP(hipMemcpyAsync(profile, d_profile, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return KT_OK;
+    return call.finish();
 }

@@ -746,69 +746,7 @@ int check_overflow(kt_ctr *ctr) {
 
 }  // namespace
 
-namespace ktl {
-
-// ---- host helpers ----------------------------------------------------------------------------
-
-uint32_t grid_for(const kt_ctx *ctx, uint64_t work_items, uint32_t per_cu) {
-    uint64_t g = (uint64_t)ctx->n_cu * per_cu;
-    if (g > work_items) g = work_items;
-    if (g < 1) g = 1;
-    return (uint32_t)g;
-}
-
-// Builds SegArgs for device-resident CSR input (seg_first lives in ctx scratch s_aux0).
-int make_seg_args(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
-                  uint64_t total_bases, int k, SegArgs *out) {
-    const uint64_t n_seg = (total_bases + ktseg::SEG - 1) / ktseg::SEG;
-    if (int rc = ctx->s_aux0.reserve((n_seg + 2) * sizeof(uint64_t))) return rc;
-    uint64_t *seg_first = (uint64_t *)ctx->s_aux0.p;
-    const uint64_t threads = n_reads + 1;
-    const uint32_t blocks = (uint32_t)((threads + 255) / 256);
-    hipLaunchKernelGGL(ktseg::seg_index_kernel, dim3(blocks), dim3(256), 0, ctx->stream, offsets, n_reads,
-                       seg_first, n_seg);
-    KT_HIP(hipGetLastError());
-    out->bases = bases;
-    out->offsets = offsets;
-    out->seg_first = seg_first;
-    out->n_reads = n_reads;
-    out->n_seg = n_seg;
-    out->k = (uint32_t)k;
-    return KT_OK;
-}
-
-// total number of bases = offsets[n_reads]; needs a read-back for device offsets
-int total_bases_of(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, int mem, uint64_t *total) {
-    if (mem == KT_MEM_HOST) {
-        *total = offsets[n_reads];
-        return KT_OK;
-    }
-    KT_HIP(hipMemcpyAsync(total, offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
-}
-
-// copies a host CSR batch into ctx scratch; returns device pointers
-int stage_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
-                const uint8_t **d_bases, const uint64_t **d_offsets) {
-    const uint64_t total = offsets[n_reads];
-    if (offsets[0] != 0) return kt::fail(KT_ERR_ARG, "offsets[0] must be 0");
-    if (int rc = ctx->s_bases.reserve(total + 64)) return rc;
-    if (int rc = ctx->s_offsets.reserve((n_reads + 1) * 8)) return rc;
-    if (total) KT_HIP(hipMemcpyAsync(ctx->s_bases.p, bases, total, hipMemcpyHostToDevice, ctx->stream));
-    KT_HIP(hipMemcpyAsync(ctx->s_offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    *d_bases = (const uint8_t *)ctx->s_bases.p;
-    *d_offsets = (const uint64_t *)ctx->s_offsets.p;
-    return KT_OK;
-}
-
-}  // namespace ktl
-
 using namespace ktl;
-
-extern "C" {
-
-}  // extern "C"
 
 extern "C" {
 
@@ -917,70 +855,53 @@ int kt_ctr_add_reads(kt_ctr *ctr, const uint8_t *bases, const uint64_t *offsets,
 int kt_ctr_add_reads_part(kt_ctr *ctr, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int mem,
                           uint32_t n_parts, uint32_t part) {
     if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_add_reads: null ctr");
-    if (n_parts < 1 || part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_add_reads_part: need part < n_parts");
+    if (part >= n_parts) return kt::fail(KT_ERR_ARG, "kt_ctr_add_reads_part: need part < n_parts");
+    kt_ctx *ctx = ctr->ctx;
+    Call call(ctx, mem, "kt_ctr_add_reads");
+    if (int rc = call.enter()) return rc;
     if (n_reads == 0) return KT_OK;
     ctr->stage_n = 0;  // the table changes: what kt_ctr_export_stage staged is no longer the table (fetch says so)
-    if (!offsets) return kt::fail(KT_ERR_ARG, "kt_ctr_add_reads: null offsets");
-    kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total == 0) return KT_OK;
-    if (!bases) return kt::fail(KT_ERR_ARG, "kt_ctr_add_reads: null bases");
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
-    if (mem == KT_MEM_HOST) {
-        if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-    }
+    if (!offsets) return call.fail("null offsets");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    if (call.total == 0) return KT_OK;
+    if (int rc = call.stage()) return rc;
     {
         // a whole batch: partition by hash prefix + one LDS build per range of the table, no global atomics.  Into a
         // table that holds data the ranges are rebuilt from what they have + the batch (worth it for large batches)
         int done = 0;
-        if (int rc = kt_bulk_build(ctr, d_bases, d_offsets, n_reads, total, n_parts, part, &done)) return rc;
-        if (done) {
-            if (mem == KT_MEM_HOST) KT_HIP(hipStreamSynchronize(ctx->stream));
-            return KT_OK;
-        }
+        if (int rc = kt_bulk_build(ctr, call.bases, call.offsets, n_reads, call.total, n_parts, part, &done)) return rc;
+        if (done) return call.finish();
     }
     ctr->empty = false;
     if (int rc = ensure_cleared(ctr)) return rc;
     SegArgs a;
-    if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, ctr->k, &a)) return rc;
+    if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, ctr->k, &a)) return rc;
     TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
     hipLaunchKernelGGL(count_reads_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, t, n_parts,
                        part, ctr->distinct);
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    return call.finish();
 }
 
 int kt_ctr_add_pairs(kt_ctr *ctr, const uint64_t *keys, const uint32_t *counts, uint64_t n, int mem) {
     if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_add_pairs: null ctr");
-    if (n == 0) return KT_OK;
-    if (!keys) return kt::fail(KT_ERR_ARG, "kt_ctr_add_pairs: null keys");
-    ctr->stage_n = 0;  // (see kt_ctr_add_reads_part)
     kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
-    const uint64_t *d_keys = keys;
-    const uint32_t *d_counts = counts;
-    if (mem == KT_MEM_HOST) {
-        if (int rc = ctx->s_aux1.reserve(n * 8)) return rc;
-        KT_HIP(hipMemcpyAsync(ctx->s_aux1.p, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_keys = (const uint64_t *)ctx->s_aux1.p;
-        if (counts) {
-            if (int rc = ctx->s_aux2.reserve(n * 4)) return rc;
-            KT_HIP(hipMemcpyAsync(ctx->s_aux2.p, counts, n * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_counts = (const uint32_t *)ctx->s_aux2.p;
-        }
-    }
+    Call call(ctx, mem, "kt_ctr_add_pairs");
+    if (int rc = call.enter()) return rc;
+    if (n == 0) return KT_OK;
+    if (!keys) return call.fail("null keys");
+    ctr->stage_n = 0;  // (see kt_ctr_add_reads_part)
+    const uint64_t *d_keys = nullptr;
+    const uint32_t *d_counts = nullptr;
+    if (int rc = call.in(kt::AUX1, keys, n, &d_keys)) return rc;
+    if (counts)
+        if (int rc = call.in(kt::AUX2, counts, n, &d_counts)) return rc;
     if (!d_counts) {
-        // raw k-mers (routed from other GPUs): the bulk build, no global atomics
+        // raw k-mers (routed from other GPUs): the bulk build, no global atomics (it takes AUX2 for its census, which
+        // the counts do not hold on this branch)
         int done = 0;
         if (int rc = kt_bulk_build_keys(ctr, d_keys, n, &done)) return rc;
-        if (done) {
-            if (mem == KT_MEM_HOST) KT_HIP(hipStreamSynchronize(ctx->stream));
-            return KT_OK;
-        }
+        if (done) return call.finish();
     }
     ctr->empty = false;
     if (int rc = ensure_cleared(ctr)) return rc;
@@ -988,8 +909,7 @@ int kt_ctr_add_pairs(kt_ctr *ctr, const uint64_t *keys, const uint32_t *counts, 
     hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0,
                        ctx->stream, d_keys, d_counts, n, t, ctr->distinct);
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    return call.finish();
 }
 
 }  // extern "C"
@@ -1037,50 +957,40 @@ int kt_ctr_size(kt_ctr *ctr, uint64_t *distinct) {
 
 int kt_ctr_export(kt_ctr *ctr, uint64_t *keys, uint32_t *counts, uint64_t max_out, uint64_t *n_out, int mem) {
     if (!ctr || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export: null");
-    if (max_out && (!keys || !counts)) return kt::fail(KT_ERR_ARG, "kt_ctr_export: null output");
     kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_ctr_export");
+    if (int rc = call.enter()) return rc;
+    if (max_out && (!keys || !counts)) return call.fail("null output");
     if (!ctr->dense)
         if (int rc = ensure_cleared(ctr)) return rc;
     if (int rc = check_overflow(ctr)) return rc;
     uint64_t *d_keys = keys;
     uint32_t *d_counts = counts;
-    if (mem == KT_MEM_HOST && max_out) {
-        if (int rc = ctx->s_aux1.reserve(max_out * 8)) return rc;
-        if (int rc = ctx->s_aux2.reserve(max_out * 4)) return rc;
-        d_keys = (uint64_t *)ctx->s_aux1.p;
-        d_counts = (uint32_t *)ctx->s_aux2.p;
+    if (call.host() && max_out) {  // (what comes back is the entries written, known only after the pass)
+        if (int rc = call.scratch(kt::AUX1, max_out * 8, &d_keys)) return rc;
+        if (int rc = call.scratch(kt::AUX2, max_out * 4, &d_counts)) return rc;
     }
+    uint64_t n = 0;
     if (ctr->dense) {  // packed ranges: a coalesced copy, no compaction
-        uint64_t n = 0;
-        if (ctr->dense_ext) {  // ... or no copy at all: the build wrote the entries to the export target
-            d_keys = mem == KT_MEM_HOST ? ctr->xt_keys : keys;
-            d_counts = mem == KT_MEM_HOST ? ctr->xt_counts : counts;
+        if (ctr->dense_ext && call.host()) {  // ... or no copy at all: the build wrote the entries to the export target
+            d_keys = ctr->xt_keys;
+            d_counts = ctr->xt_counts;
         }
         if (int rc = kt_table_dense_export(ctr, d_keys, d_counts, max_out, &n)) return rc;
-        const uint64_t written = n < max_out ? n : max_out;
-        if (mem == KT_MEM_HOST && written) {
-            KT_HIP(hipMemcpy(keys, d_keys, written * 8, hipMemcpyDeviceToHost));
-            KT_HIP(hipMemcpy(counts, d_counts, written * 4, hipMemcpyDeviceToHost));
-        }
-        *n_out = written;
-        if (n > max_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export: max_out smaller than the table's size");
-        return KT_OK;
+    } else {
+        KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(table_export_kernel<false>, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0,
+                           ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, max_out, ctr->cursor, 1u, 0xFFFFFFFFu);
+        KT_HIP(hipGetLastError());
+        KT_HIP(hipMemcpyAsync(&n, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
     }
-    KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(table_export_kernel<false>, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0,
-                       ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, max_out, ctr->cursor, 1u, 0xFFFFFFFFu);
-    KT_HIP(hipGetLastError());
-    uint64_t n = 0;
-    KT_HIP(hipMemcpyAsync(&n, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
     const uint64_t written = n < max_out ? n : max_out;
-    if (mem == KT_MEM_HOST && written) {
-        KT_HIP(hipMemcpy(keys, d_keys, written * 8, hipMemcpyDeviceToHost));
-        KT_HIP(hipMemcpy(counts, d_counts, written * 4, hipMemcpyDeviceToHost));
-    }
+    call.back(keys, (const uint64_t *)d_keys, written);
+    call.back(counts, (const uint32_t *)d_counts, written);
+    if (int rc = call.finish()) return rc;
     *n_out = written;
-    if (n > max_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export: max_out smaller than the table's size");
+    if (n > max_out) return call.fail("max_out smaller than the table's size");
     return KT_OK;
 }
 
@@ -1090,6 +1000,7 @@ int kt_ctr_export(kt_ctr *ctr, uint64_t *keys, uint32_t *counts, uint64_t max_ou
 int kt_ctr_export_stage(kt_ctr *ctr, uint64_t *n_out) {
     if (!ctr || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage: null");
     kt_ctx *ctx = ctr->ctx;
+    kt::ClaimScope scope(ctx);
     if (int rc = ctx->use()) return rc;
     uint64_t n = 0;
     if (int rc = kt_ctr_size(ctr, &n)) return rc;
@@ -1126,6 +1037,7 @@ int kt_ctr_export_stage_range(kt_ctr *ctr, uint32_t min_count, uint32_t max_coun
     if (min_count > max_count) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: min_count > max_count");
     if (min_count <= 1u && max_count == 0xFFFFFFFFu) return kt_ctr_export_stage(ctr, n_out);
     kt_ctx *ctx = ctr->ctx;
+    kt::ClaimScope scope(ctx);
     if (int rc = ctx->use()) return rc;
     uint64_t n = 0;
     if (int rc = kt_ctr_size(ctr, &n)) return rc;
@@ -1183,25 +1095,23 @@ int kt_ctr_export_stage_range(kt_ctr *ctr, uint32_t min_count, uint32_t max_coun
 
 int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *totals, int mem) {
     if (!ctr || !hist) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: null");
-    if (n_bins < 2 || n_bins > (1u << 24)) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: n_bins must be in 2..2^24");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: bad mem");
     kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_ctr_spectrum");
+    if (n_bins < 2 || n_bins > (1u << 24)) return call.fail("n_bins must be in 2..2^24");
+    if (int rc = call.enter()) return rc;
     uint64_t n = 0;
     if (int rc = kt_ctr_size(ctr, &n)) return rc;  // (KT_ERR_FULL for an overflowed table)
     if (!n) return KT_OK;                           // nothing to add (a table pending its clear is empty too)
     uint64_t *d_hist = hist, *d_totals = totals;
-    if (mem == KT_MEM_HOST) {
-        if (int rc = ctx->s_aux1.reserve(((size_t)n_bins + 2) * 8)) return rc;
-        d_hist = (uint64_t *)ctx->s_aux1.p;
+    if (call.host()) {  // this call's bins are made on the device from zero and added to the caller's
+        if (int rc = call.scratch(kt::AUX1, ((size_t)n_bins + 2) * 8, &d_hist)) return rc;
         d_totals = totals ? d_hist + n_bins : nullptr;
         KT_HIP(hipMemsetAsync(d_hist, 0, ((size_t)n_bins + 2) * 8, ctx->stream));
     }
     if (int rc = launch_spectrum(ctr, n, d_hist, n_bins, d_totals)) return rc;
-    if (mem == KT_MEM_HOST) {
-        std::vector<uint64_t> h((size_t)n_bins + 2);
-        KT_HIP(hipMemcpyAsync(h.data(), d_hist, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
+    if (call.host()) {
+        std::unique_ptr<uint64_t[]> h;
+        if (int rc = call.fetch((const uint64_t *)d_hist, (uint64_t)n_bins + 2, &h)) return rc;
         for (uint32_t b = 1; b < n_bins; b++) hist[b] += h[b];
         if (totals) {
             totals[0] += h[n_bins];
@@ -1262,13 +1172,12 @@ extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n
     if (!a || !b || !matrix) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: null");
     if (a->k != b->k) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: the tables have different k");
     if (a->ctx != b->ctx) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: the tables are on different contexts");
-    if (a->n_owners > 1 || b->n_owners > 1)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_compare: a table is one shard of a sharded table - shards are not supported");
-    if (n_rows < 2 || n_cols < 2) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: n_rows and n_cols must be >= 2");
-    if ((uint64_t)n_rows * n_cols > (1ull << 24)) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: n_rows * n_cols must be <= 2^24");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_compare: bad mem");
     kt_ctx *ctx = a->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_ctr_compare");
+    if (a->n_owners > 1 || b->n_owners > 1) return call.fail("a table is one shard of a sharded table - shards are not supported");
+    if (n_rows < 2 || n_cols < 2) return call.fail("n_rows and n_cols must be >= 2");
+    if ((uint64_t)n_rows * n_cols > (1ull << 24)) return call.fail("n_rows * n_cols must be <= 2^24");
+    if (int rc = call.enter()) return rc;
     uint64_t n_a = 0, n_b = 0;
     if (int rc = kt_ctr_size(a, &n_a)) return rc;  // (KT_ERR_FULL for an overflowed table)
     if (int rc = kt_ctr_size(b, &n_b)) return rc;
@@ -1278,8 +1187,9 @@ extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n
     if (int rc = table_ready(b)) return rc;
     // scratch (u64): this call's cells | B's spectrum | column sums | A's totals (4) | B's totals (2) | the six totals
     const uint64_t cells = (uint64_t)n_rows * n_cols, words = cells + 2ull * n_cols + 12;
-    if (int rc = ctx->s_aux1.reserve(words * 8)) return rc;
-    uint64_t *S = (uint64_t *)ctx->s_aux1.p, *spec_b = S + cells, *colsum = spec_b + n_cols, *tot_a = colsum + n_cols,
+    uint64_t *S = nullptr;
+    if (int rc = call.scratch(kt::AUX1, words * 8, &S)) return rc;
+    uint64_t *spec_b = S + cells, *colsum = spec_b + n_cols, *tot_a = colsum + n_cols,
              *tot_b = tot_a + 4, *tot6 = tot_b + 2;
     KT_HIP(hipMemsetAsync(S, 0, words * 8, ctx->stream));
     if (n_a) {
@@ -1294,7 +1204,7 @@ extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n
     }
     if (n_b)
         if (int rc = launch_spectrum(b, n_b, spec_b, n_cols, tot_b)) return rc;
-    const bool host = mem == KT_MEM_HOST;
+    const bool host = call.host();
     hipLaunchKernelGGL(compare_colsum_kernel, dim3((n_rows - 1 + CMP_FIN_ROWS - 1) / CMP_FIN_ROWS, (n_cols + BLOCK - 1) / BLOCK),
                        dim3(BLOCK), 0, ctx->stream, (const uint64_t *)S, n_rows, n_cols, colsum, host ? nullptr : matrix);
     hipLaunchKernelGGL(compare_row0_kernel, dim3((n_cols + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream,
@@ -1302,9 +1212,8 @@ extern "C" int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n
                        (const uint64_t *)tot_b, host ? tot6 : totals);
     KT_HIP(hipGetLastError());
     if (host) {
-        std::vector<uint64_t> h(words);
-        KT_HIP(hipMemcpyAsync(h.data(), S, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
+        std::unique_ptr<uint64_t[]> h;
+        if (int rc = call.fetch((const uint64_t *)S, words, &h)) return rc;
         for (uint64_t i = 1; i < cells; i++) matrix[i] += h[i];
         if (totals)
             for (int j = 0; j < 6; j++) totals[j] += h[cells + 2ull * n_cols + 6 + j];
@@ -1327,16 +1236,15 @@ extern "C" int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32
     if (!a || !b || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: null");
     if (a->k != b->k) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: the tables have different k");
     if (a->ctx != b->ctx) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: the tables are on different contexts");
-    if (a->n_owners > 1 || b->n_owners > 1)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_setop: a table is one shard of a sharded table - shards are not supported");
-    if (op < KT_SET_INTERSECT || op > KT_SET_XOR) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: unknown op");
-    if (count_rule < KT_SETCNT_FIRST || count_rule > KT_SETCNT_SUM) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: unknown count_rule");
-    if (min_a == 0 || min_b == 0) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: min_a and min_b must be >= 1");
-    if (min_a > max_a || min_b > max_b) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: a count range with min > max");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: bad mem");
-    if (max_out && (!keys || !counts)) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: null output");
     kt_ctx *ctx = a->ctx;
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_ctr_setop");
+    if (a->n_owners > 1 || b->n_owners > 1) return call.fail("a table is one shard of a sharded table - shards are not supported");
+    if (op < KT_SET_INTERSECT || op > KT_SET_XOR) return call.fail("unknown op");
+    if (count_rule < KT_SETCNT_FIRST || count_rule > KT_SETCNT_SUM) return call.fail("unknown count_rule");
+    if (min_a == 0 || min_b == 0) return call.fail("min_a and min_b must be >= 1");
+    if (min_a > max_a || min_b > max_b) return call.fail("a count range with min > max");
+    if (int rc = call.enter()) return rc;
+    if (max_out && (!keys || !counts)) return call.fail("null output");
     uint64_t n_a = 0, n_b = 0;
     if (int rc = kt_ctr_size(a, &n_a)) return rc;  // (KT_ERR_FULL for an overflowed table)
     if (int rc = kt_ctr_size(b, &n_b)) return rc;
@@ -1349,11 +1257,9 @@ extern "C" int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32
         if (int rc = table_ready(b)) return rc;
     uint64_t *d_keys = keys;
     uint32_t *d_counts = counts;
-    if (mem == KT_MEM_HOST && max_out) {
-        if (int rc = ctx->s_aux1.reserve(max_out * 8)) return rc;
-        if (int rc = ctx->s_aux2.reserve(max_out * 4)) return rc;
-        d_keys = (uint64_t *)ctx->s_aux1.p;
-        d_counts = (uint32_t *)ctx->s_aux2.p;
+    if (call.host() && max_out) {  // (what comes back is the entries written, known only after the walks)
+        if (int rc = call.scratch(kt::AUX1, max_out * 8, &d_keys)) return rc;
+        if (int rc = call.scratch(kt::AUX2, max_out * 4, &d_counts)) return rc;
     }
     uint64_t *cursor = a->cursor;
     KT_HIP(hipMemsetAsync(cursor, 0, 8, ctx->stream));
@@ -1374,12 +1280,10 @@ extern "C" int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32
     const uint64_t written = n < max_out ? n : max_out;
     if (sorted && written == n)  // (a result that did not fit is not a result: the caller repeats the call)
         if (int rc = kt_sort_pairs(ctx, d_keys, d_counts, n, 2u * (uint32_t)a->k)) return rc;
-    if (mem == KT_MEM_HOST && written) {
-        KT_HIP(hipMemcpyAsync(keys, d_keys, written * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipMemcpyAsync(counts, d_counts, written * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    if (max_out && n > max_out) return kt::fail(KT_ERR_ARG, "kt_ctr_setop: max_out smaller than the result (*n_out entries)");
+    call.back(keys, (const uint64_t *)d_keys, written);
+    call.back(counts, (const uint32_t *)d_counts, written);
+    if (int rc = call.finish()) return rc;
+    if (max_out && n > max_out) return call.fail("max_out smaller than the result (*n_out entries)");
     return KT_OK;
 }
 
@@ -1404,29 +1308,25 @@ int kt_ctr_route(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uin
     if (!ctx || !owner_counts) return kt::fail(KT_ERR_ARG, "kt_ctr_route: null");
     if (k < 1 || k > 31) return kt::fail(KT_ERR_ARG, "kt_ctr_route: k must be in 1..31");
     if (n_owners < 1 || n_owners > MAX_OWNERS) return kt::fail(KT_ERR_ARG, "kt_ctr_route: n_owners must be in 1..64");
-    if (int rc = ctx->use()) return rc;
+    Call call(ctx, mem, "kt_ctr_route");
+    if (int rc = call.enter()) return rc;
     // device scalars: [0..63] owner counts, [64..127] cursors
-    if (int rc = ctx->s_aux2.reserve(2 * MAX_OWNERS * 8)) return rc;
-    uint64_t *d_counts = (uint64_t *)ctx->s_aux2.p;
+    uint64_t *d_counts = nullptr;
+    if (int rc = call.scratch(kt::AUX2, 2 * MAX_OWNERS * 8, &d_counts)) return rc;
     uint64_t *d_cursors = d_counts + MAX_OWNERS;
     KT_HIP(hipMemsetAsync(d_counts, 0, 2 * MAX_OWNERS * 8, ctx->stream));
-    uint64_t total = 0;
     if (n_reads) {
-        if (!offsets) return kt::fail(KT_ERR_ARG, "kt_ctr_route: null offsets");
-        if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
+        if (!offsets) return call.fail("null offsets");
+        if (int rc = call.batch(bases, offsets, n_reads, nullptr)) return rc;
     }
     uint64_t *d_keys = keys_out;
-    if (total) {
-        if (!bases || !keys_out) return kt::fail(KT_ERR_ARG, "kt_ctr_route: null buffer");
-        const uint8_t *d_bases = bases;
-        const uint64_t *d_offsets = offsets;
-        if (mem == KT_MEM_HOST) {
-            if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-            if (int rc = ctx->s_aux1.reserve(total * 8)) return rc;
-            d_keys = (uint64_t *)ctx->s_aux1.p;
-        }
+    if (call.total) {
+        if (!bases || !keys_out) return call.fail("null buffer");
+        if (int rc = call.stage()) return rc;
+        if (call.host())  // (what comes back is the keys routed, known only after the count pass)
+            if (int rc = call.scratch(kt::AUX1, call.total * 8, &d_keys)) return rc;
         SegArgs a;
-        if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, k, &a)) return rc;
+        if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, k, &a)) return rc;
         const uint32_t grid = grid_for(ctx, a.n_seg, 8);
         hipLaunchKernelGGL(route_count_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, a, (uint32_t)n_owners, d_counts);
         hipLaunchKernelGGL(route_prefix_kernel, dim3(1), dim3(64), 0, ctx->stream, d_counts, (uint32_t)n_owners, d_cursors);
@@ -1438,49 +1338,45 @@ int kt_ctr_route(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uin
         KT_HIP(hipMemcpyAsync(owner_counts, d_counts, n_owners * 8, hipMemcpyDeviceToDevice, ctx->stream));
         return KT_OK;
     }
-    KT_HIP(hipMemcpyAsync(owner_counts, d_counts, n_owners * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
+    call.back(owner_counts, (const uint64_t *)d_counts, (uint64_t)n_owners);
+    if (int rc = call.finish()) return rc;
     uint64_t n_keys = 0;
     for (int o = 0; o < n_owners; o++) n_keys += owner_counts[o];
-    if (n_keys) KT_HIP(hipMemcpy(keys_out, d_keys, n_keys * 8, hipMemcpyDeviceToHost));
-    return KT_OK;
+    if (!n_keys) return KT_OK;
+    call.back(keys_out, (const uint64_t *)d_keys, n_keys);
+    return call.finish();
 }
 
 int kt_kmers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k, uint64_t *fwd,
              uint64_t *rev, uint8_t *valid, int mem) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_kmers: null ctx");
     if (k < 1 || k > 31) return kt::fail(KT_ERR_ARG, "kt_kmers: k must be in 1..31");
+    Call call(ctx, mem, "kt_kmers");
+    if (int rc = call.enter()) return rc;
     if (n_reads == 0) return KT_OK;
-    if (!offsets) return kt::fail(KT_ERR_ARG, "kt_kmers: null offsets");
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
+    if (!offsets) return call.fail("null offsets");
+    if (int rc = call.batch(bases, offsets, n_reads, nullptr)) return rc;
+    const uint64_t total = call.total;
     if (total == 0) return KT_OK;
-    if (!bases || !fwd || !rev || !valid) return kt::fail(KT_ERR_ARG, "kt_kmers: null buffer");
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
+    if (!bases || !fwd || !rev || !valid) return call.fail("null buffer");
+    if (int rc = call.stage()) return rc;
     uint64_t *d_fwd = fwd, *d_rev = rev;
     uint8_t *d_valid = valid;
-    if (mem == KT_MEM_HOST) {
-        if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-        if (int rc = ctx->s_out.reserve(total * 17)) return rc;
-        d_fwd = (uint64_t *)ctx->s_out.p;
+    if (call.host()) {  // fwd | rev | valid in one buffer
+        if (int rc = call.scratch(kt::OUT, total * 17, &d_fwd)) return rc;
         d_rev = d_fwd + total;
         d_valid = (uint8_t *)(d_rev + total);
+        call.back(fwd, (const uint64_t *)d_fwd, total);
+        call.back(rev, (const uint64_t *)d_rev, total);
+        call.back(valid, (const uint8_t *)d_valid, total);
     }
     KT_HIP(hipMemsetAsync(d_valid, 0, total, ctx->stream));
     SegArgs a;
-    if (int rc = make_seg_args(ctx, d_bases, d_offsets, n_reads, total, k, &a)) return rc;
+    if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, total, k, &a)) return rc;
     hipLaunchKernelGGL(kmers_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, d_fwd, d_rev,
                        d_valid);
     KT_HIP(hipGetLastError());
-    if (mem == KT_MEM_HOST) {
-        KT_HIP(hipMemcpyAsync(fwd, d_fwd, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipMemcpyAsync(rev, d_rev, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipMemcpyAsync(valid, d_valid, total, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return KT_OK;
+    return call.finish();
 }
 
 }  // extern "C"

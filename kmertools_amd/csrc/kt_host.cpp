@@ -69,6 +69,17 @@ int kt_ctx::use() {
     return KT_OK;
 }
 
+int kt_ctx::claim_bytes(kt::Buf b, size_t bytes, const char *who, void **p) {
+    static const char *const names[kt::N_BUF] = {"BASES", "OFFSETS", "OUT", "AUX0", "AUX1", "AUX2"};
+    *p = nullptr;
+    if (depth == 0) return kt::fail(KT_ERR_ARG, std::string(who) + ": scratch " + names[b] + " claimed outside a library call");
+    if (claimed >> b & 1u) return kt::fail(KT_ERR_ARG, std::string(who) + ": scratch " + names[b] + " is already held in this call");
+    if (int rc = scratch[b].reserve(bytes)) return rc;
+    claimed |= 1u << b;
+    *p = scratch[b].p;
+    return KT_OK;
+}
+
 int kt_ctx::canon_lut(int k, const uint16_t **out) {
     if (k < 1 || k > kt::KT_MAX_OLIGO_K) return kt::fail(KT_ERR_ARG, "canon_lut: k out of range");
     if (!lut_dev[k]) {
@@ -150,12 +161,7 @@ int kt_ctx_destroy(kt_ctx *ctx) {
     for (auto &p : ctx->lut32_dev)
         if (p) (void)hipFree(p);
     ctx->oligo_tune.release();
-    ctx->s_bases.release();
-    ctx->s_offsets.release();
-    ctx->s_out.release();
-    ctx->s_aux0.release();
-    ctx->s_aux1.release();
-    ctx->s_aux2.release();
+    for (auto &b : ctx->scratch) b.release();
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return KT_OK;

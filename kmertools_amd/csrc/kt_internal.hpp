@@ -29,6 +29,9 @@ struct Scratch {
 
 constexpr int KT_MAX_OLIGO_K = 7;
 
+// the context's six scratch buffers (kt_ctx::claim)
+enum Buf { BASES, OFFSETS, OUT, AUX0, AUX1, AUX2, N_BUF };
+
 }  // namespace kt
 
 struct kt_ctx {
@@ -41,7 +44,18 @@ struct kt_ctx {
     // bin's u32 counter inside a row), k = 1..7
     uint16_t *lut_dev[kt::KT_MAX_OLIGO_K + 1] = {};
     uint32_t *lut32_dev[13] = {};  // canonical rank of every k-mer, k = 1..12 (the generic oligo path, kt_oligo_generic.hip)
-    kt::Scratch s_bases, s_offsets, s_out, s_aux0, s_aux1, s_aux2;
+    // Scratch shared by everything that runs on the context.  Within one outermost library call (kt::ClaimScope) a buffer
+    // has one holder: claim() reserves it, notes the claim in `claimed` and refuses a second one - a helper cannot take a
+    // buffer behind its caller's back, and no pointer goes stale through a later reserve of the same buffer.
+    kt::Scratch scratch[kt::N_BUF];
+    uint32_t claimed = 0;  // bit b: buffer b is held
+    int depth = 0;         // library calls open on this context (an entry point that calls another one)
+    int claim_bytes(kt::Buf b, size_t bytes, const char *who, void **p);
+    template <class T>
+    int claim(kt::Buf b, size_t bytes, const char *who, T **p) { return claim_bytes(b, bytes, who, (void **)p); }
+    // gives a buffer up before the call ends: its holder has read its result back (or the next holder's work is queued
+    // behind the last kernel that touches it), and a later step of the same call takes the buffer
+    void unclaim(kt::Buf b) { claimed &= ~(1u << b); }
     struct OligoKnobs {  // KT_OLIGO_* launch tunables, read once per context (kt_oligo.hip)
         bool loaded = false, live = false;
         uint32_t shape = 104, R = 0, oversub = 0, debug = 0, pw = 7;
@@ -72,6 +86,21 @@ struct kt_ctx {
     int canon_lut(int k, const uint16_t **out);
     int canon_lut32(int k, const uint32_t **out);
 };
+
+namespace kt {
+// One library call's hold on the context's scratch: every extern "C" entry point that claims scratch, itself or through a
+// helper, opens one.  The outermost scope starts with no buffer held; an entry point called from another one keeps its
+// caller's claims and gives back its own when it returns (its results are in its caller's arrays by then).
+struct ClaimScope {
+    kt_ctx *ctx;
+    uint32_t outer;
+    explicit ClaimScope(kt_ctx *c) : ctx(c), outer(c->depth++ ? c->claimed : 0u) { ctx->claimed = outer; }
+    ClaimScope(const ClaimScope &) = delete;
+    ~ClaimScope() { reset(), ctx->depth--; }
+    // gives back what was claimed under this scope so far (a loop whose every round ends with a wait for the stream)
+    void reset() { ctx->claimed = outer; }
+};
+}  // namespace kt
 
 // where level 2 of the partition passes reads a table's level-1 buckets from: the regions of buckets 0, 1, ... (cap1 keys of
 // room each, `counts` keys used) of the level-1 output (kt_bulk.hip)
@@ -132,7 +161,7 @@ int kt_oligo_generic_launch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *o
                             int count_min, int norm, int total_step, int dt, void *out);
 
 // kt_sort.hip: (key, count) pairs in device memory into ascending key order (LSD radix sort over key_bits bits, on the
-// context's stream; scratch: the context's s_out and s_aux0)
+// context's stream; scratch: the context's OUT and AUX0)
 int kt_sort_pairs(kt_ctx *ctx, uint64_t *keys, uint32_t *counts, uint64_t n, uint32_t key_bits);
 
 namespace kt {

@@ -1,6 +1,10 @@
-// kt_launch.hpp - host-side launch helpers shared by the translation units that use the
-// segment front-end (kt_ctr.hip, kt_cov.hip, kt_correct.hip).  Defined in kt_ctr.hip.
+// kt_launch.hpp - what the host code of the extern "C" entry points shares: launch helpers of the segment front-end,
+// argument checks that several entry points make in the same words, and ktl::Call, the one path by which an entry point
+// moves its arguments between the caller's memory and the device.  Defined in kt_launch.hip.
 #pragma once
+#include <memory>
+#include <new>
+
 #include "kt_internal.hpp"
 #include "kt_segment.hpp"
 #include "kt_table.hpp"
@@ -9,17 +13,9 @@ namespace ktl {
 
 // min(work_items, n_cu * per_cu) workgroups, at least 1
 uint32_t grid_for(const kt_ctx *ctx, uint64_t work_items, uint32_t per_cu);
-// SegArgs for a device-resident CSR batch (launches seg_index_kernel into ctx scratch s_aux0)
+// SegArgs for a device-resident CSR batch (launches seg_index_kernel into the context's scratch AUX0)
 int make_seg_args(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                   uint64_t total_bases, int k, ktseg::SegArgs *out);
-// offsets[n_reads]; a device read-back for KT_MEM_DEVICE
-int total_bases_of(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, int mem, uint64_t *total);
-// copies a host CSR batch into ctx scratch (s_bases, s_offsets)
-int stage_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
-                const uint8_t **d_bases, const uint64_t **d_offsets);
-// *too_long = a read of the batch holds 2^32 bases or more (total = offsets[n_reads]; a device read-back for KT_MEM_DEVICE;
-// uses ctx scratch s_aux2).  Defined in kt_cov.hip.
-int has_read_of_2_32(kt_ctx *ctx, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int mem, bool *too_long);
 // the table's geometry as the device functions take it (kt_table.hpp)
 inline kttab::Geom geom_of(const kt_ctr *ctr) { return kttab::Geom{ctr->cap, ctr->shift, ctr->m8, ctr->kbits}; }
 // the table as the kernels that probe it take it (after table_ready: the slots hold the probing image)
@@ -28,5 +24,89 @@ inline kttab::Probed probed_of(const kt_ctr *ctr, uint32_t n_parts = 1, uint32_t
 }
 // makes the table readable: performs a deferred clear, reports KT_ERR_FULL if it overflowed
 int table_ready(kt_ctr *ctr);
+
+// One call of an entry point that takes `int mem`.  It holds the call's claim scope on the context's scratch and is the
+// only place that tells the two memory kinds apart: for KT_MEM_DEVICE every method hands the caller's pointer through
+// and nothing waits; for KT_MEM_HOST inputs go up into a claimed scratch buffer, outputs are made in one, and finish()
+// issues the copies back and waits for the stream once.
+class Call {
+public:
+    Call(kt_ctx *ctx, int mem, const char *name) : ctx_(ctx), mem_(mem), name_(name), scope_(ctx) {}
+    bool host() const { return mem_ == KT_MEM_HOST; }
+    int fail(const char *what) const { return kt::fail(KT_ERR_ARG, std::string(name_) + ": " + what); }
+    // "<name>: bad mem" unless mem is one of the two kinds; makes the context's device the current one
+    int enter() { return mem_ == KT_MEM_HOST || mem_ == KT_MEM_DEVICE ? ctx_->use() : fail("bad mem"); }
+    int check_part(uint32_t n_parts, uint32_t part) const { return part < n_parts ? KT_OK : fail("need part < n_parts"); }
+    // the entry points that need every k-mer's count in one table refuse one shard of a sharded table
+    int refuse_shard(const kt_ctr *t) const {
+        return t->n_owners > 1 ? fail("the table is one shard of a sharded table - shards are not supported "
+                                      "(a shard cannot tell a k-mer absent here from one absent everywhere)") : KT_OK;
+    }
+
+    // the CSR batch of the call, as the caller gave it until stage(): total = offsets[n_reads] (a read-back for device
+    // memory); "<name>: <null_text>" when the batch has bases and `bases` is null
+    const uint8_t *bases = nullptr;
+    const uint64_t *offsets = nullptr;
+    uint64_t n_reads = 0, total = 0;
+    int batch(const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, const char *null_text = "null bases");
+    // host: the batch into BASES and OFFSETS (offsets[0] must be 0); bases / offsets become the device copies
+    int stage();
+    // "<name>: a read of 2^32 bases or more (<why>)" when the batch holds one
+    int refuse_long_reads(const char *why);
+
+    // a scratch buffer for the call itself, whichever the memory kind
+    template <class T>
+    int scratch(kt::Buf slot, size_t bytes, T **d) { return ctx_->claim(slot, bytes, name_, d); }
+    // host: n elements of the caller's `p` to `dev`, on the stream
+    template <class T>
+    int up(T *dev, const T *p, uint64_t n) {
+        if (host() && n) KT_HIP(hipMemcpyAsync(dev, p, n * sizeof(T), hipMemcpyHostToDevice, ctx_->stream));
+        return KT_OK;
+    }
+    // host: queues n elements at `dev` for finish() to copy to the caller's `p` (null: nothing) - the elements the entry
+    // point filled, which may be fewer than it reserved
+    template <class T>
+    void back(T *p, const T *dev, uint64_t n) {
+        if (host() && p && n) copies_[n_copies_++] = Copy{p, dev, n * sizeof(T)};
+    }
+    // an input array of n elements: the caller's pointer, or its copy in `slot`
+    template <class T>
+    int in(kt::Buf slot, const T *p, uint64_t n, const T **d) {
+        T *s = const_cast<T *>(p);
+        if (host())
+            if (int rc = scratch(slot, n * sizeof(T), &s)) return rc;
+        *d = s;
+        return up(s, p, n);
+    }
+    // an output array of n elements: the caller's pointer, or `slot` and a copy back by finish()
+    template <class T>
+    int out(kt::Buf slot, T *p, uint64_t n, T **d) {
+        *d = p;
+        if (host())
+            if (int rc = scratch(slot, n * sizeof(T), d)) return rc;
+        back(p, (const T *)*d, n);
+        return KT_OK;
+    }
+    // waits for the stream and hands out a host copy of n device elements: what an entry point adds into its caller's arrays
+    template <class T>
+    int fetch(const T *dev, uint64_t n, std::unique_ptr<T[]> *h) {
+        h->reset(new (std::nothrow) T[n]);
+        return fetch_bytes(h->get(), dev, n * sizeof(T));
+    }
+    // host: the queued copies back, then one wait for the stream; device: nothing (the call stays asynchronous)
+    int finish();
+    // gives the call's scratch back (a loop whose every round ends with finish() takes it anew)
+    void release() { scope_.reset(); }
+
+private:
+    struct Copy { void *dst; const void *src; size_t bytes; };
+    int fetch_bytes(void *dst, const void *dev, size_t bytes);
+    kt_ctx *ctx_;
+    int mem_;
+    const char *name_;
+    kt::ClaimScope scope_;
+    Copy copies_[8];
+    int n_copies_ = 0;
+};
 
 }  // namespace ktl

@@ -802,13 +802,12 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // written out.  Level 2, with W = J H + R: B_J(p) = min over j < J of A0(p - j H) by doubling on the stride-H sequence
 // (log2 J elementwise passes, out[p] = min(in[p], in[p - d])), and the window's first H m-mers are A0(p - (W - H)):
 // act(p) = min(B_J(p), A0(p - (W - H))).  Windows that reach across a run's start come out wrong and are never looked at
-// (an event needs run_len >= w), exactly as inside a tile.  Three arrays of one m-mer per base, in ctx->s_aux0.
+// (an event needs run_len >= w), exactly as inside a tile.  Three arrays of one m-mer per base in `base`: the 3 * align256(total * sizeof(V)) + 256
+// bytes of the context's AUX0 that kt_minimisers claimed when it chose this path.
 template <class V>
-int wide_window_act(kt_ctx *ctx, const MinArgs &a_in, V **act_out) {
+int wide_window_act(kt_ctx *ctx, const MinArgs &a_in, char *base, V **act_out) {
     const uint64_t total = a_in.total, H = (uint64_t)MAX_HG * GRAN, W = a_in.W;
     const size_t one = align256(total * sizeof(V));
-    if (int rc = ctx->s_aux0.reserve(3 * one + 256)) return rc;
-    char *base = (char *)ctx->s_aux0.p;
     V *A0 = (V *)base, *bufs[2] = {(V *)(base + one), (V *)(base + 2 * one)};
     MinArgs a = a_in;
     a.W = (uint32_t)H;
@@ -847,7 +846,8 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
                              uint64_t *ends, uint64_t capacity, uint64_t *n_events, int mem) {
     if (!ctx || !n_events) return kt::fail(KT_ERR_ARG, "kt_minimisers: null");
     *n_events = 0;
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_minimisers: bad mem");
+    Call call(ctx, mem, "kt_minimisers");
+    if (int rc = call.enter()) return rc;
     if (msize < 1 || msize > 31) return kt::fail(KT_ERR_ARG, "kt_minimisers: msize must be in 1..31");
     if (wsize != 0 && wsize < (uint64_t)msize)
         return kt::fail(KT_ERR_ARG, "kt_minimisers: wsize must be 0 or >= msize");
@@ -861,24 +861,23 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
     if (n_reads == 0) return KT_OK;
     if (!offsets || !ev_offsets) return kt::fail(KT_ERR_ARG, "kt_minimisers: null offsets");
     if (capacity && (!kmers || !starts || !ends)) return kt::fail(KT_ERR_ARG, "kt_minimisers: null output");
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_minimisers: null bases");
-    if (two_level && ctx->s_aux0.reserve(3 * align256(total * (msize <= 16 ? 4 : 8)) + 256) != KT_OK) {
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    const uint64_t total = call.total;
+    char *act_room = nullptr;  // the two-level minimum's three arrays: claimed here, because whether there is room decides the path
+    if (two_level && call.scratch(kt::AUX0, 3 * align256(total * (msize <= 16 ? 4 : 8)) + 256, &act_room) != KT_OK) {
         kt::set_error("");  // (no room for the three arrays of the two-level minimum: the iterator needs one)
         two_level = false;
         wide = true;
     }
 
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
+    if (int rc = call.stage()) return rc;
+    const uint8_t *d_bases = call.bases;
+    const uint64_t *d_offsets = call.offsets;
     uint64_t *d_evoff = ev_offsets, *d_k = kmers, *d_s = starts, *d_e = ends;
-    if (mem == KT_MEM_HOST) {
-        if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
+    if (call.host()) {  // ev_offsets | kmers | starts | ends in one buffer
         const size_t o1 = align256((n_reads + 1) * 8), oc = align256(capacity * 8);
-        if (int rc = ctx->s_out.reserve(o1 + 3 * oc + 256)) return rc;
-        char *p = (char *)ctx->s_out.p;
+        char *p = nullptr;
+        if (int rc = call.scratch(kt::OUT, o1 + 3 * oc + 256, &p)) return rc;
         d_evoff = (uint64_t *)p;
         d_k = (uint64_t *)(p + o1);
         d_s = (uint64_t *)(p + o1 + oc);
@@ -901,8 +900,8 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
     const size_t o_rcount = off;  off += align256((wsize == 0 || wide ? n_reads + 1 : 1) * 8);
     const size_t o_part = off;    off += align256((n_scan / 1024 + 2) * 8);
     const size_t o_total = off;   off += 256;
-    if (int rc = ctx->s_aux1.reserve(off)) return rc;
-    char *ib = (char *)ctx->s_aux1.p;
+    char *ib = nullptr;
+    if (int rc = call.scratch(kt::AUX1, off, &ib)) return rc;
     uint64_t *gfirst = (uint64_t *)(ib + o_gfirst), *lastbreak = (uint64_t *)(ib + o_break);
     uint64_t *carry = (uint64_t *)(ib + o_carry), *tcount = (uint64_t *)(ib + o_tcount);
     uint64_t *tbase = (uint64_t *)(ib + o_tbase), *rcount = (uint64_t *)(ib + o_rcount);
@@ -910,8 +909,8 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
 
     uint64_t n_ev = 0;
     if (wide) {
-        if (int rc = ctx->s_aux2.reserve((total + n_reads + 1) * 8)) return rc;
-        uint64_t *ring = (uint64_t *)ctx->s_aux2.p;
+        uint64_t *ring = nullptr;
+        if (int rc = call.scratch(kt::AUX2, (total + n_reads + 1) * 8, &ring)) return rc;
         const uint32_t nb = (uint32_t)((n_reads + BLOCK - 1) / BLOCK);
         hipLaunchKernelGGL(min_serial_kernel, dim3(nb), dim3(BLOCK), 0, ctx->stream, d_bases, d_offsets, n_reads, wsize,
                            (uint32_t)msize, ring, rcount, (const uint64_t *)nullptr, (uint64_t)0, (uint64_t *)nullptr,
@@ -955,7 +954,8 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
             uint32_t *act32 = nullptr;
             uint64_t *act64 = nullptr;
             if (two_level) {
-                if (int rc = narrow ? wide_window_act<uint32_t>(ctx, a, &act32) : wide_window_act<uint64_t>(ctx, a, &act64)) return rc;
+                if (int rc = narrow ? wide_window_act<uint32_t>(ctx, a, act_room, &act32) : wide_window_act<uint64_t>(ctx, a, act_room, &act64))
+                    return rc;
             }
             Chain chain{(unsigned long long *)tcount, (unsigned long long *)(d_total + 1), d_total, n_tiles, capacity};
             if (capacity == 0) {
@@ -976,9 +976,9 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
                 KT_HIP(hipStreamSynchronize(ctx->stream));
             } else {
                 // single pass: the tiles chain their output offsets themselves (decoupled look-back)
-                if (int rc = ctx->s_aux2.reserve(align256(capacity * sizeof(Event)) + capacity + 256)) return rc;
-                Event *ev = (Event *)ctx->s_aux2.p;
-                uint8_t *ev_type = (uint8_t *)ctx->s_aux2.p + align256(capacity * sizeof(Event));
+                Event *ev = nullptr;
+                if (int rc = call.scratch(kt::AUX2, align256(capacity * sizeof(Event)) + capacity + 256, &ev)) return rc;
+                uint8_t *ev_type = (uint8_t *)ev + align256(capacity * sizeof(Event));
                 KT_HIP(hipMemsetAsync(tcount, 0, n_tiles * 8, ctx->stream));
                 KT_HIP(hipMemsetAsync(d_total, 0, 16, ctx->stream));
                 if (narrow) {
@@ -1014,15 +1014,11 @@ extern "C" int kt_minimisers(kt_ctx *ctx, const uint8_t *bases, const uint64_t *
     }
     *n_events = n_ev;
     const uint64_t n_out = n_ev < capacity ? n_ev : capacity;
-    if (mem == KT_MEM_HOST) {
-        KT_HIP(hipMemcpyAsync(ev_offsets, d_evoff, (n_reads + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_out) {
-            KT_HIP(hipMemcpyAsync(kmers, d_k, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-            KT_HIP(hipMemcpyAsync(starts, d_s, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-            KT_HIP(hipMemcpyAsync(ends, d_e, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    call.back(ev_offsets, (const uint64_t *)d_evoff, n_reads + 1);
+    call.back(kmers, (const uint64_t *)d_k, n_out);
+    call.back(starts, (const uint64_t *)d_s, n_out);
+    call.back(ends, (const uint64_t *)d_e, n_out);
+    if (int rc = call.finish()) return rc;
     if (n_ev > capacity && capacity)
         return kt::fail(KT_ERR_ARG, "kt_minimisers: capacity smaller than the number of minimisers (see *n_events)");
     return KT_OK;

@@ -39,7 +39,7 @@
 // measured and dropped (double-buffered producer/consumer wave specialisation; the per-read
 // wave loop with k-1 DPP shifts) are in the git history and DESIGN.md.
 #include "kt_device.hpp"
-#include "kt_internal.hpp"
+#include "kt_launch.hpp"
 
 #include <type_traits>
 
@@ -1160,8 +1160,9 @@ extern "C" int kt_selftest_quotient(kt_ctx *ctx, uint32_t d_lo, uint32_t d_hi, u
     if (!ctx || !n_checked || !n_mismatch || !checksum) return kt::fail(KT_ERR_ARG, "kt_selftest_quotient: null");
     if (d_lo < 1 || d_hi < d_lo) return kt::fail(KT_ERR_ARG, "kt_selftest_quotient: need 1 <= d_lo <= d_hi");
     if (int rc = ctx->use()) return rc;
-    if (int rc = ctx->s_aux2.reserve(64)) return rc;
-    uint64_t *d_out = (uint64_t *)ctx->s_aux2.p;
+    kt::ClaimScope scope(ctx);
+    uint64_t *d_out = nullptr;
+    if (int rc = ctx->claim(kt::AUX2, 64, "kt_selftest_quotient", &d_out)) return rc;
     KT_HIP(hipMemsetAsync(d_out, 0, 24, ctx->stream));
     uint32_t grid = d_hi - d_lo + 1;
     if (grid > (uint32_t)ctx->n_cu * 16) grid = (uint32_t)ctx->n_cu * 16;
@@ -1189,6 +1190,7 @@ extern "C" int kt_oligo_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t 
     if (n_reads == 0) return KT_OK;
     if (!offsets || !out) return kt::fail(KT_ERR_ARG, "kt_oligo_batch: null pointer");
     if (int rc = ctx->use()) return rc;
+    ktl::Call call(ctx, mem, "kt_oligo_batch");
 
     uint64_t bins = 0;
     kt_bins(k, count_min, &bins);
@@ -1210,28 +1212,21 @@ extern "C" int kt_oligo_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t 
     for (uint64_t r0 = 0; r0 < n_reads; r0 += slab) {
         const uint64_t nr = (n_reads - r0) < slab ? (n_reads - r0) : slab;
         const uint64_t b0 = offsets[r0], b1 = offsets[r0 + nr];
-        if (int rc = ctx->s_bases.reserve(b1 - b0 + 16)) return rc;
-        if (int rc = ctx->s_offsets.reserve((nr + 1) * 8)) return rc;
-        if (int rc = ctx->s_out.reserve(nr * row_bytes)) return rc;
-        // rebase offsets to the slab
-        uint64_t *tmp = (uint64_t *)malloc((nr + 1) * 8);
+        call.release();  // (a slab ends with a wait for the stream: the next one takes every buffer anew)
+        uint8_t *d_bases = nullptr;
+        uint64_t *d_offsets = nullptr;
+        char *d_out = nullptr;
+        if (int rc = call.scratch(kt::BASES, b1 - b0 + 16, &d_bases)) return rc;
+        if (int rc = call.scratch(kt::OFFSETS, (nr + 1) * 8, &d_offsets)) return rc;
+        if (int rc = call.scratch(kt::OUT, nr * row_bytes, &d_out)) return rc;
+        std::unique_ptr<uint64_t[]> tmp(new (std::nothrow) uint64_t[nr + 1]);  // the offsets rebased to the slab
         if (!tmp) return kt::fail(KT_ERR_NOMEM, "kt_oligo_batch: host alloc");
         for (uint64_t i = 0; i <= nr; i++) tmp[i] = offsets[r0 + i] - b0;
-        hipError_t e = hipSuccess;
-        if (b1 > b0) e = hipMemcpyAsync(ctx->s_bases.p, bases + b0, b1 - b0, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ctx->s_offsets.p, tmp, (nr + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-        int rc = KT_OK;
-        if (e == hipSuccess)
-            rc = oligo_launch(ctx, (const uint8_t *)ctx->s_bases.p, (const uint64_t *)ctx->s_offsets.p, nr, k,
-                              count_min, norm, total_step, out_dtype, ctx->s_out.p);
-        if (e == hipSuccess && rc == KT_OK)
-            e = hipMemcpyAsync((char *)out + r0 * row_bytes, ctx->s_out.p, nr * row_bytes,
-                               hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && rc == KT_OK) e = hipStreamSynchronize(ctx->stream);
-        free(tmp);
-        if (rc != KT_OK) return rc;
-        if (e != hipSuccess) return kt::fail(KT_ERR_HIP, std::string("kt_oligo_batch: ") + hipGetErrorString(e));
+        if (int rc = call.up(d_bases, bases + b0, b1 - b0)) return rc;
+        if (int rc = call.up(d_offsets, (const uint64_t *)tmp.get(), nr + 1)) return rc;
+        if (int rc = oligo_launch(ctx, d_bases, d_offsets, nr, k, count_min, norm, total_step, out_dtype, d_out)) return rc;
+        call.back((char *)out + r0 * row_bytes, (const char *)d_out, nr * row_bytes);
+        if (int rc = call.finish()) return rc;
     }
     return KT_OK;
 }

@@ -107,11 +107,10 @@ int kt_oligo_generic_launch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *o
     uint64_t slab = (1ull << 28) / bins;  // <= 1 GiB of u32 counters at a time
     if (slab < 1) slab = 1;
     if (slab > n_reads) slab = n_reads;
-    if (int rc = ctx->s_aux1.reserve(slab * bins * 4)) return rc;
-    if (int rc = ctx->s_aux2.reserve(slab * 4 + (slab + 1) * 8 + 64)) return rc;
-    uint32_t *counts = (uint32_t *)ctx->s_aux1.p;
-    uint32_t *totals = (uint32_t *)ctx->s_aux2.p;
-    uint64_t *sub_offsets = (uint64_t *)((char *)ctx->s_aux2.p + ((slab * 4 + 63) & ~(size_t)63));
+    uint32_t *counts = nullptr, *totals = nullptr;
+    if (int rc = ctx->claim(kt::AUX1, slab * bins * 4, "kt_oligo_batch", &counts)) return rc;
+    if (int rc = ctx->claim(kt::AUX2, slab * 4 + (slab + 1) * 8 + 64, "kt_oligo_batch", &totals)) return rc;
+    uint64_t *sub_offsets = (uint64_t *)((char *)totals + ((slab * 4 + 63) & ~(size_t)63));
     for (uint64_t r0 = 0; r0 < n_reads; r0 += slab) {
         const uint64_t nr = n_reads - r0 < slab ? n_reads - r0 : slab;
         uint64_t b0 = 0, b1 = 0;
@@ -125,6 +124,7 @@ int kt_oligo_generic_launch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *o
                                nr, sub_offsets);
             SegArgs a;
             if (int rc = ktl::make_seg_args(ctx, bases + b0, sub_offsets, nr, b1 - b0, k, &a)) return rc;
+            ctx->unclaim(kt::AUX0);  // (the next slab's index is written behind this slab's kernels on the stream)
             if (count_min)
                 hipLaunchKernelGGL(oligo_generic_count<true>, dim3(ktl::grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream,
                                    a, lut, bins, counts, totals);

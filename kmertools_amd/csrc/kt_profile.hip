@@ -309,8 +309,8 @@ static int stats_device(kt_ctx *ctx, const uint32_t *profile, const uint64_t *of
                         const StatsOut &o) {
     // which forms are needed: the long sequences' indices (at most total / (MID_MAX + 1) of them), whether a middle one exists
     const uint64_t list_cap = total / (MID_MAX + 1) + 1;
-    if (int rc = ctx->s_aux1.reserve(sizeof(Classes) + list_cap * 8)) return rc;
-    Classes *d_cls = (Classes *)ctx->s_aux1.p;
+    Classes *d_cls = nullptr;
+    if (int rc = ctx->claim(kt::AUX1, sizeof(Classes) + list_cap * 8, "kt_profile_stats", &d_cls)) return rc;
     uint64_t *d_list = (uint64_t *)(d_cls + 1);
     Classes cls{};
     KT_HIP(hipMemsetAsync(d_cls, 0, sizeof(Classes), ctx->stream));
@@ -331,8 +331,8 @@ static int stats_device(kt_ctx *ctx, const uint32_t *profile, const uint64_t *of
     if (!cls.n_long) return KT_OK;
 
     const uint32_t n_long = cls.n_long;
-    if (int rc = ctx->s_aux2.reserve((uint64_t)n_long * (sizeof(LongAcc) + 256 * 4))) return rc;
-    LongAcc *d_acc = (LongAcc *)ctx->s_aux2.p;
+    LongAcc *d_acc = nullptr;
+    if (int rc = ctx->claim(kt::AUX2, (uint64_t)n_long * (sizeof(LongAcc) + 256 * 4), "kt_profile_stats", &d_acc)) return rc;
     uint32_t *d_hist = (uint32_t *)(d_acc + n_long);
     KT_HIP(hipMemsetAsync(d_hist, 0, (uint64_t)n_long * 256 * 4, ctx->stream));
     hipLaunchKernelGGL(long_init_kernel, dim3((n_long + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, d_acc, n_long);
@@ -361,30 +361,27 @@ extern "C" int kt_profile_stats(kt_ctx *ctx, const uint32_t *profile, const uint
                                 uint32_t *n_present, uint32_t *min_count, uint32_t *median, uint32_t *max_count, uint64_t *sum,
                                 int mem) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_profile_stats: null ctx");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_profile_stats: bad mem");
+    Call call(ctx, mem, "kt_profile_stats");
+    if (int rc = call.enter()) return rc;
     if (n_reads == 0) return KT_OK;
-    if (!offsets) return kt::fail(KT_ERR_ARG, "kt_profile_stats: null buffer");
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && !profile) return kt::fail(KT_ERR_ARG, "kt_profile_stats: null profile");
-    bool too_long = false;
-    if (int rc = has_read_of_2_32(ctx, offsets, n_reads, total, mem, &too_long)) return rc;
-    if (too_long) return kt::fail(KT_ERR_ARG, "kt_profile_stats: a read of 2^32 bases or more (the numbers of k-mers are u32)");
+    if (!offsets) return call.fail("null buffer");
+    if (int rc = call.batch(nullptr, offsets, n_reads, nullptr)) return rc;
+    const uint64_t total = call.total;
+    if (total && !profile) return call.fail("null profile");
+    if (int rc = call.refuse_long_reads("the numbers of k-mers are u32")) return rc;
     uint32_t *const out32[5] = {n_kmers, n_present, min_count, median, max_count};
     if (!n_kmers && !n_present && !min_count && !median && !max_count && !sum) return KT_OK;
 
-    if (mem == KT_MEM_DEVICE) return stats_device(ctx, profile, offsets, n_reads, total, StatsOut{n_kmers, n_present, min_count, median, max_count, sum});
+    if (!call.host()) return stats_device(ctx, profile, offsets, n_reads, total, StatsOut{n_kmers, n_present, min_count, median, max_count, sum});
 
-    // host arrays: staged in ctx scratch, the outputs the caller asked for made there and copied back
-    if (int rc = ctx->s_bases.reserve(total * 4 + 4)) return rc;
-    if (int rc = ctx->s_offsets.reserve((n_reads + 1) * 8)) return rc;
-    if (int rc = ctx->s_out.reserve(n_reads * (8 + 5 * 4))) return rc;
-    uint32_t *d_profile = (uint32_t *)ctx->s_bases.p;
-    uint64_t *d_offsets = (uint64_t *)ctx->s_offsets.p;
-    if (total) KT_HIP(hipMemcpyAsync(d_profile, profile, total * 4, hipMemcpyHostToDevice, ctx->stream));
-    KT_HIP(hipMemcpyAsync(d_offsets, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t *d_sum = (uint64_t *)ctx->s_out.p;
+    // host arrays: the profile in BASES, the offsets in OFFSETS, sum | the five u32 outputs in OUT
+    uint32_t *d_profile = nullptr;
+    const uint64_t *d_offsets = nullptr;
+    uint64_t *d_sum = nullptr;
+    if (int rc = call.scratch(kt::BASES, total * 4 + 4, &d_profile)) return rc;
+    if (int rc = call.in(kt::OFFSETS, offsets, n_reads + 1, &d_offsets)) return rc;
+    if (int rc = call.scratch(kt::OUT, n_reads * (8 + 5 * 4), &d_sum)) return rc;
+    if (int rc = call.up(d_profile, profile, total)) return rc;
     uint32_t *d32 = (uint32_t *)(d_sum + n_reads);
     StatsOut o{n_kmers ? d32 : nullptr,
                n_present ? d32 + n_reads : nullptr,
@@ -393,9 +390,7 @@ extern "C" int kt_profile_stats(kt_ctx *ctx, const uint32_t *profile, const uint
                max_count ? d32 + 4 * n_reads : nullptr,
                sum ? d_sum : nullptr};
     if (int rc = stats_device(ctx, d_profile, d_offsets, n_reads, total, o)) return rc;
-    for (int q = 0; q < 5; q++)
-        if (out32[q]) KT_HIP(hipMemcpyAsync(out32[q], d32 + (uint64_t)q * n_reads, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (sum) KT_HIP(hipMemcpyAsync(sum, d_sum, n_reads * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    for (int q = 0; q < 5; q++) call.back(out32[q], (const uint32_t *)d32 + (uint64_t)q * n_reads, n_reads);
+    call.back(sum, (const uint64_t *)d_sum, n_reads);
+    return call.finish();
 }

@@ -815,6 +815,7 @@ int kt_sharded_add_reads(kt_sharded *s, const uint8_t *bases, const uint64_t *of
     if (!s->routed) return kt_ctr_add_reads(s->table, bases, offsets, n_reads, mem);
     kt_ctx *ctx = s->ctx;
     if (int rc = ctx->use()) return rc;
+    ktl::Call call(ctx, mem, "kt_sharded_add_reads");
     // What this rank finds wrong - with its arguments, or while it sets the batch up: a pending table that filled up in an
     // earlier batch, a failed copy - is not returned at once: a rank that left now would leave its peers waiting in the
     // exchange.  Every fallible local step comes first (the route pass among them); then the ranks tell each other in
@@ -843,7 +844,8 @@ int kt_sharded_add_reads(kt_sharded *s, const uint8_t *bases, const uint64_t *of
     if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) arg_fail("kt_sharded_add_reads: bad mem flag");
     if (my_code == KT_OK && n_reads) {
         if (!offsets) arg_fail("kt_sharded_add_reads: null offsets");
-        else if (int rc = ktl::total_bases_of(ctx, offsets, n_reads, mem, &total)) local_fail(rc);
+        else if (int rc = call.batch(bases, offsets, n_reads, nullptr)) local_fail(rc);
+        else total = call.total;
     }
     if (my_code == KT_OK && total > s->max_batch_bases) arg_fail("kt_sharded_add_reads: batch larger than max_batch_bases (split it)");
     if (my_code == KT_OK && total && !bases) arg_fail("kt_sharded_add_reads: null bases");
@@ -857,11 +859,11 @@ int kt_sharded_add_reads(kt_sharded *s, const uint8_t *bases, const uint64_t *of
         }
         s->add_calls++;
     }
-    const uint8_t *d_bases = bases;
-    const uint64_t *d_offsets = offsets;
     if (my_code == KT_OK && mem == KT_MEM_HOST && total) {
-        if (int rc = ktl::stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) local_fail(rc);
+        if (int rc = call.stage()) local_fail(rc);
     }
+    const uint8_t *d_bases = call.bases;
+    const uint64_t *d_offsets = call.offsets;
     SegArgs a{};
     if (my_code == KT_OK && total) {
         if (int rc = ktl::make_seg_args(ctx, d_bases, d_offsets, n_reads, total, s->k, &a)) local_fail(rc);

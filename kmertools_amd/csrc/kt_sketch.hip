@@ -423,12 +423,13 @@ static int sketch_device(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offs
     while ((1ull << rounds) < max_pieces) rounds++;
     const uint64_t n_slots = 2 * a.n_seg;
     const uint64_t buf_bytes = n_slots * o.s * 8, all_bytes = buf_bytes + n_slots * 4;
-    if (int rc = ctx->s_aux1.reserve(all_bytes + n_slots * 8)) return rc;
+    char *p0 = nullptr, *p1 = nullptr;  // (p1 stays null when a single round never writes the second set of slots)
+    if (int rc = ctx->claim(kt::AUX1, all_bytes + n_slots * 8, "kt_sketch_batch", &p0)) return rc;
     if (rounds >= 2)
-        if (int rc = ctx->s_aux2.reserve(all_bytes)) return rc;
-    Slots s0{(uint64_t *)ctx->s_aux1.p, (uint32_t *)((char *)ctx->s_aux1.p + buf_bytes + n_slots * 8)};
-    uint64_t *slot_rid = (uint64_t *)((char *)ctx->s_aux1.p + buf_bytes);
-    Slots s1{(uint64_t *)ctx->s_aux2.p, (uint32_t *)((char *)ctx->s_aux2.p + buf_bytes)};
+        if (int rc = ctx->claim(kt::AUX2, all_bytes, "kt_sketch_batch", &p1)) return rc;
+    Slots s0{(uint64_t *)p0, (uint32_t *)(p0 + buf_bytes + n_slots * 8)};
+    uint64_t *slot_rid = (uint64_t *)(p0 + buf_bytes);
+    Slots s1{(uint64_t *)p1, (uint32_t *)(p1 + buf_bytes)};
     const uint32_t seg_grid = (uint32_t)(a.n_seg < (1u << 20) ? a.n_seg : (1u << 20));
     hipLaunchKernelGGL(sketch_segment_kernel, dim3(seg_grid), dim3(BLOCK), 0, ctx->stream, a, seed, o, s0, slot_rid);
     KT_HIP(hipGetLastError());
@@ -446,49 +447,46 @@ extern "C" int kt_sketch_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: null ctx");
     if (k < 1 || k > 31) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: k must be in 1..31");
     if (s < 1 || s > MAX_S) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: s must be in 1..KT_SKETCH_MAX_S");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: bad mem");
+    Call call(ctx, mem, "kt_sketch_batch");
+    if (int rc = call.enter()) return rc;
     if (n_reads == 0) return KT_OK;
-    if (!offsets || !hashes || !sizes) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: null buffer");
-    if (int rc = ctx->use()) return rc;
-    uint64_t total = 0;
-    if (int rc = total_bases_of(ctx, offsets, n_reads, mem, &total)) return rc;
-    if (total && !bases) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: null bases");
+    if (!offsets || !hashes || !sizes) return call.fail("null buffer");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    const uint64_t total = call.total;
 
     uint64_t max_len = 0;
-    if (mem == KT_MEM_HOST) {
+    if (call.host()) {
         for (uint64_t i = 0; i < n_reads; i++) {
             if (offsets[i + 1] < offsets[i]) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: offsets decrease");
             const uint64_t len = offsets[i + 1] - offsets[i];
             max_len = len > max_len ? len : max_len;
         }
     } else if (total) {
-        if (int rc = ctx->s_aux2.reserve(8)) return rc;
-        uint64_t *d_max = (uint64_t *)ctx->s_aux2.p;
+        uint64_t *d_max = nullptr;
+        if (int rc = call.scratch(kt::AUX2, 8, &d_max)) return rc;
         KT_HIP(hipMemsetAsync(d_max, 0, 8, ctx->stream));
         hipLaunchKernelGGL(max_len_kernel, dim3(grid_for(ctx, (n_reads + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream, offsets,
                            n_reads, d_max);
         KT_HIP(hipGetLastError());
         KT_HIP(hipMemcpyAsync(&max_len, d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->unclaim(kt::AUX2);  // (read back: the tree's second set of slots may follow)
     }
     if (max_len >= (1ull << 32)) return kt::fail(KT_ERR_ARG, "kt_sketch_batch: a read of 2^32 bases or more (the numbers of k-mers are u32)");
 
-    if (mem == KT_MEM_DEVICE) return sketch_device(ctx, bases, offsets, n_reads, total, max_len, k, seed, BatchOut{hashes, sizes, n_kmers, s});
-
-    const uint8_t *d_bases;
-    const uint64_t *d_offsets;
-    if (int rc = stage_batch(ctx, bases, offsets, n_reads, &d_bases, &d_offsets)) return rc;
-    const uint64_t row_bytes = n_reads * (uint64_t)s * 8;
-    if (int rc = ctx->s_out.reserve(row_bytes + n_reads * 8)) return rc;
-    uint64_t *d_hashes = (uint64_t *)ctx->s_out.p;
-    uint32_t *d_sizes = (uint32_t *)((char *)ctx->s_out.p + row_bytes), *d_nk = d_sizes + n_reads;
-    if (int rc = sketch_device(ctx, d_bases, d_offsets, n_reads, total, max_len, k, seed, BatchOut{d_hashes, d_sizes, n_kmers ? d_nk : nullptr, s}))
-        return rc;
-    KT_HIP(hipMemcpyAsync(hashes, d_hashes, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipMemcpyAsync(sizes, d_sizes, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_kmers) KT_HIP(hipMemcpyAsync(n_kmers, d_nk, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    BatchOut o{hashes, sizes, n_kmers, s};
+    if (call.host()) {  // hashes | sizes | n_kmers in one buffer
+        if (int rc = call.stage()) return rc;
+        const uint64_t rows = n_reads * (uint64_t)s;
+        if (int rc = call.scratch(kt::OUT, rows * 8 + n_reads * 8, &o.hashes)) return rc;
+        o.sizes = (uint32_t *)(o.hashes + rows);
+        o.n_kmers = n_kmers ? o.sizes + n_reads : nullptr;
+        call.back(hashes, (const uint64_t *)o.hashes, rows);
+        call.back(sizes, (const uint32_t *)o.sizes, n_reads);
+        call.back(n_kmers, (const uint32_t *)o.n_kmers, n_reads);
+    }
+    if (int rc = sketch_device(ctx, call.bases, call.offsets, n_reads, total, max_len, k, seed, o)) return rc;
+    return call.finish();
 }
 
 // the merge over device arrays; max_rows = the rows of the largest group (at least 1)
@@ -501,12 +499,13 @@ static int merge_device(kt_ctx *ctx, const uint64_t *hashes, const uint32_t *siz
     uint32_t rounds = 1;
     while ((1ull << rounds) < max_rows) rounds++;
     const uint64_t buf_bytes = n * (uint64_t)s * 8;
+    char *p0 = nullptr, *p1 = nullptr;  // (null where no round writes: a group's last round writes the output row)
     if (rounds >= 2)
-        if (int rc = ctx->s_aux1.reserve(buf_bytes + n * 4)) return rc;
+        if (int rc = ctx->claim(kt::AUX1, buf_bytes + n * 4, "kt_sketch_merge", &p0)) return rc;
     if (rounds >= 3)
-        if (int rc = ctx->s_aux2.reserve(buf_bytes + n * 4)) return rc;
-    uint64_t *mh[2] = {(uint64_t *)ctx->s_aux1.p, (uint64_t *)ctx->s_aux2.p};
-    uint32_t *ms[2] = {(uint32_t *)((char *)ctx->s_aux1.p + buf_bytes), (uint32_t *)((char *)ctx->s_aux2.p + buf_bytes)};
+        if (int rc = ctx->claim(kt::AUX2, buf_bytes + n * 4, "kt_sketch_merge", &p1)) return rc;
+    uint64_t *mh[2] = {(uint64_t *)p0, (uint64_t *)p1};
+    uint32_t *ms[2] = {(uint32_t *)(p0 + buf_bytes), (uint32_t *)(p1 + buf_bytes)};
     const uint32_t grid = (uint32_t)(n < (1u << 20) ? (n ? n : 1) : (1u << 20));
     for (uint32_t r = 0; r < rounds; r++) {
         const uint64_t *in_h = r ? mh[(r - 1) & 1u] : hashes;
@@ -522,45 +521,44 @@ extern "C" int kt_sketch_merge(kt_ctx *ctx, const uint64_t *hashes, const uint32
                                const uint64_t *group_offsets, uint64_t n_groups, uint64_t *out_hashes, uint32_t *out_sizes, int mem) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_sketch_merge: null ctx");
     if (s < 1 || s > MAX_S) return kt::fail(KT_ERR_ARG, "kt_sketch_merge: s must be in 1..KT_SKETCH_MAX_S");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_sketch_merge: bad mem");
+    Call call(ctx, mem, "kt_sketch_merge");
+    if (int rc = call.enter()) return rc;
     if (n_groups == 0) return KT_OK;
-    if (!group_offsets || !out_hashes || !out_sizes || (n && (!hashes || !sizes))) return kt::fail(KT_ERR_ARG, "kt_sketch_merge: null buffer");
-    if (int rc = ctx->use()) return rc;
-    const char *bad_groups = "kt_sketch_merge: group_offsets must not decrease and must end at or below n";
+    if (!group_offsets || !out_hashes || !out_sizes || (n && (!hashes || !sizes))) return call.fail("null buffer");
+    const char *bad_groups = "group_offsets must not decrease and must end at or below n";
     uint64_t max_rows = 0;
-    if (mem == KT_MEM_DEVICE) {
-        if (int rc = ctx->s_aux2.reserve(16)) return rc;
-        uint64_t *d_chk = (uint64_t *)ctx->s_aux2.p, chk[2] = {0, 0};  // [0]: largest group, [1]: the bad flag
+    if (!call.host()) {
+        uint64_t *d_chk = nullptr, chk[2] = {0, 0};  // [0]: largest group, [1]: the bad flag
+        if (int rc = call.scratch(kt::AUX2, 16, &d_chk)) return rc;
         KT_HIP(hipMemsetAsync(d_chk, 0, 16, ctx->stream));
         hipLaunchKernelGGL(group_check_kernel, dim3(grid_for(ctx, (n_groups + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
                            group_offsets, n_groups, n, (uint32_t *)(d_chk + 1), d_chk);
         KT_HIP(hipGetLastError());
         KT_HIP(hipMemcpyAsync(chk, d_chk, 16, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
-        if (chk[1]) return kt::fail(KT_ERR_ARG, bad_groups);
+        ctx->unclaim(kt::AUX2);  // (read back: the tree's second set of rows may follow)
+        if (chk[1]) return call.fail(bad_groups);
         return merge_device(ctx, hashes, sizes, n, s, group_offsets, n_groups, chk[0], out_hashes, out_sizes);
     }
     for (uint64_t g = 0; g < n_groups; g++) {
-        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n) return kt::fail(KT_ERR_ARG, bad_groups);
+        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n) return call.fail(bad_groups);
         const uint64_t rows = group_offsets[g + 1] - group_offsets[g];
         max_rows = rows > max_rows ? rows : max_rows;
     }
     const uint64_t in_bytes = n * (uint64_t)s * 8, out_bytes = n_groups * (uint64_t)s * 8;
-    if (int rc = ctx->s_bases.reserve(in_bytes + n * 4 + 8)) return rc;
-    if (int rc = ctx->s_offsets.reserve((n_groups + 1) * 8)) return rc;
-    if (int rc = ctx->s_out.reserve(out_bytes + n_groups * 4)) return rc;
-    uint64_t *d_h = (uint64_t *)ctx->s_bases.p, *d_go = (uint64_t *)ctx->s_offsets.p, *d_oh = (uint64_t *)ctx->s_out.p;
-    uint32_t *d_sz = (uint32_t *)((char *)ctx->s_bases.p + in_bytes), *d_os = (uint32_t *)((char *)ctx->s_out.p + out_bytes);
-    if (n) {
-        KT_HIP(hipMemcpyAsync(d_h, hashes, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-        KT_HIP(hipMemcpyAsync(d_sz, sizes, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    KT_HIP(hipMemcpyAsync(d_go, group_offsets, (n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    // hashes | sizes in BASES, the groups in OFFSETS, out_hashes | out_sizes in OUT
+    uint64_t *d_h = nullptr, *d_oh = nullptr;
+    const uint64_t *d_go = nullptr;
+    if (int rc = call.scratch(kt::BASES, in_bytes + n * 4 + 8, &d_h)) return rc;
+    if (int rc = call.in(kt::OFFSETS, group_offsets, n_groups + 1, &d_go)) return rc;
+    if (int rc = call.scratch(kt::OUT, out_bytes + n_groups * 4, &d_oh)) return rc;
+    uint32_t *d_sz = (uint32_t *)((char *)d_h + in_bytes), *d_os = (uint32_t *)((char *)d_oh + out_bytes);
+    if (int rc = call.up(d_h, hashes, n * (uint64_t)s)) return rc;
+    if (int rc = call.up(d_sz, sizes, n)) return rc;
     if (int rc = merge_device(ctx, d_h, d_sz, n, s, d_go, n_groups, max_rows, d_oh, d_os)) return rc;
-    KT_HIP(hipMemcpyAsync(out_hashes, d_oh, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipMemcpyAsync(out_sizes, d_os, n_groups * 4, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    call.back(out_hashes, (const uint64_t *)d_oh, n_groups * (uint64_t)s);
+    call.back(out_sizes, (const uint32_t *)d_os, n_groups);
+    return call.finish();
 }
 
 static int pairs_device(kt_ctx *ctx, const uint64_t *a_h, const uint32_t *a_s, uint64_t n_a, const uint64_t *b_h, const uint32_t *b_s,
@@ -585,29 +583,30 @@ extern "C" int kt_sketch_pairs(kt_ctx *ctx, const uint64_t *a_hashes, const uint
                                const uint32_t *b_sizes, uint64_t n_b, uint32_t s, uint32_t *shared, uint32_t *denom, int mem) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_sketch_pairs: null ctx");
     if (s < 1 || s > MAX_S) return kt::fail(KT_ERR_ARG, "kt_sketch_pairs: s must be in 1..KT_SKETCH_MAX_S");
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return kt::fail(KT_ERR_ARG, "kt_sketch_pairs: bad mem");
+    Call call(ctx, mem, "kt_sketch_pairs");
+    if (int rc = call.enter()) return rc;
     if (n_a == 0 || n_b == 0) return KT_OK;
-    if (!a_hashes || !a_sizes || !b_hashes || !b_sizes || !shared) return kt::fail(KT_ERR_ARG, "kt_sketch_pairs: null buffer");
-    if (int rc = ctx->use()) return rc;
-    if (mem == KT_MEM_DEVICE) return pairs_device(ctx, a_hashes, a_sizes, n_a, b_hashes, b_sizes, n_b, s, shared, denom);
+    if (!a_hashes || !a_sizes || !b_hashes || !b_sizes || !shared) return call.fail("null buffer");
+    if (!call.host()) return pairs_device(ctx, a_hashes, a_sizes, n_a, b_hashes, b_sizes, n_b, s, shared, denom);
 
     const bool same = a_hashes == b_hashes && a_sizes == b_sizes && n_a == n_b;
     const uint64_t a_bytes = n_a * (uint64_t)s * 8, b_bytes = same ? 0 : n_b * (uint64_t)s * 8, cells = n_a * n_b;
-    if (int rc = ctx->s_bases.reserve(a_bytes + b_bytes + 8)) return rc;
-    if (int rc = ctx->s_offsets.reserve((n_a + n_b) * 4 + 8)) return rc;
-    if (int rc = ctx->s_out.reserve(cells * 8)) return rc;
-    uint64_t *d_a = (uint64_t *)ctx->s_bases.p, *d_b = same ? d_a : (uint64_t *)((char *)ctx->s_bases.p + a_bytes);
-    uint32_t *d_as = (uint32_t *)ctx->s_offsets.p, *d_bs = same ? d_as : d_as + n_a;
-    uint32_t *d_sh = (uint32_t *)ctx->s_out.p, *d_dn = d_sh + cells;
-    KT_HIP(hipMemcpyAsync(d_a, a_hashes, a_bytes, hipMemcpyHostToDevice, ctx->stream));
-    KT_HIP(hipMemcpyAsync(d_as, a_sizes, n_a * 4, hipMemcpyHostToDevice, ctx->stream));
+    // A's rows | B's rows in BASES, their sizes in OFFSETS, shared | denom in OUT
+    uint64_t *d_a = nullptr;
+    uint32_t *d_as = nullptr, *d_sh = nullptr;
+    if (int rc = call.scratch(kt::BASES, a_bytes + b_bytes + 8, &d_a)) return rc;
+    if (int rc = call.scratch(kt::OFFSETS, (n_a + n_b) * 4 + 8, &d_as)) return rc;
+    if (int rc = call.scratch(kt::OUT, cells * 8, &d_sh)) return rc;
+    uint64_t *d_b = same ? d_a : (uint64_t *)((char *)d_a + a_bytes);
+    uint32_t *d_bs = same ? d_as : d_as + n_a, *d_dn = d_sh + cells;
+    if (int rc = call.up(d_a, a_hashes, n_a * (uint64_t)s)) return rc;
+    if (int rc = call.up(d_as, a_sizes, n_a)) return rc;
     if (!same) {
-        KT_HIP(hipMemcpyAsync(d_b, b_hashes, b_bytes, hipMemcpyHostToDevice, ctx->stream));
-        KT_HIP(hipMemcpyAsync(d_bs, b_sizes, n_b * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = call.up(d_b, b_hashes, n_b * (uint64_t)s)) return rc;
+        if (int rc = call.up(d_bs, b_sizes, n_b)) return rc;
     }
     if (int rc = pairs_device(ctx, d_a, d_as, n_a, d_b, d_bs, n_b, s, d_sh, denom ? d_dn : nullptr)) return rc;
-    KT_HIP(hipMemcpyAsync(shared, d_sh, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (denom) KT_HIP(hipMemcpyAsync(denom, d_dn, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    call.back(shared, (const uint32_t *)d_sh, cells);
+    call.back(denom, (const uint32_t *)d_dn, cells);
+    return call.finish();
 }

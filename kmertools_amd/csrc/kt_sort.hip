@@ -144,17 +144,17 @@ __global__ __launch_bounds__(BLOCK) void sort_scatter_kernel(const uint64_t *__r
 }  // namespace
 
 // keys[0, n) / counts[0, n) (device) into ascending key order, on the context's stream; key_bits = the bits a key can
-// have set.  Scratch: the context's s_out (a second pair) and s_aux0 (the digit histograms).
+// have set.  Scratch: the context's OUT (a second pair) and AUX0 (the digit histograms).
 int kt_sort_pairs(kt_ctx *ctx, uint64_t *keys, uint32_t *counts, uint64_t n, uint32_t key_bits) {
     if (n < 2) return KT_OK;
     if (int rc = ctx->use()) return rc;
     uint32_t passes = (key_bits + 7u) / 8u;
     passes += passes & 1u;  // (even: the pairs end where they started)
     const uint64_t T = (n + WTILE - 1) / WTILE;
-    if (int rc = ctx->s_out.reserve(n * 12)) return rc;
-    if (int rc = ctx->s_aux0.reserve((256 * T + 256) * 8)) return rc;
-    uint64_t *hist = (uint64_t *)ctx->s_aux0.p, *totals = hist + 256 * T;
-    uint64_t *k_src = keys, *k_dst = (uint64_t *)ctx->s_out.p;
+    uint64_t *hist = nullptr, *k_dst = nullptr;
+    if (int rc = ctx->claim(kt::OUT, n * 12, "kt_sort_pairs", &k_dst)) return rc;
+    if (int rc = ctx->claim(kt::AUX0, (256 * T + 256) * 8, "kt_sort_pairs", &hist)) return rc;
+    uint64_t *totals = hist + 256 * T, *k_src = keys;
     uint32_t *c_src = counts, *c_dst = (uint32_t *)(k_dst + n);
     const dim3 grid((uint32_t)((T + WAVES - 1) / WAVES)), block(BLOCK);
     for (uint32_t p = 0; p < passes; p++) {
