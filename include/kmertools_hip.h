@@ -284,6 +284,43 @@ int kt_ctr_compare(kt_ctr *a, kt_ctr *b, uint64_t *matrix, uint32_t n_rows, uint
 int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32_t min_a, uint32_t max_a, uint32_t min_b, uint32_t max_b,
                  uint64_t *keys, uint32_t *counts, uint64_t max_out, uint64_t *n_out, int mem, int sorted);
 
+/* Which k-mers of the table follow which: the de Bruijn adjacency of its k-mers, the sides at which a unitig ends, and a
+ * census of the nodes (BCALM / Cuttlefish start from this; the graph-cleaning stage of a short-read assembler).
+ * A canonical k-mer u of the table is a NODE when min_count <= count(u) <= max_count ("solid"; an absent k-mer has
+ * count 0 and min_count >= 1, so it is never solid).  F = the forward string of u, the canonical word itself, F[0..k).
+ * canon(s) = the smaller of s and its reverse complement.  The node's info word, for x in 0..3 (A C G T):
+ *   bit x      (right bit x)  canon(F[1..k) + x) is solid
+ *   bit 4 + x  (left bit x)   canon(x + F[0..k-1)) is solid
+ *   bit 8      (right end)    dR != 1 || sibR != 1
+ *   bit 9      (left end)     dL != 1 || sibL != 1
+ *   bits 10..31 are 0
+ * with dR = popcount of bits 0..3, dL = popcount of bits 4..7, sibR = the number of y in 0..3 with canon(y + F[1..k))
+ * solid (y = F[0] is u itself and counts) and sibL = the number of y with canon(F[0..k-1) + y) solid.  The counts run
+ * over x and y, not over distinct k-mers, and these formulas are the whole rule: self-loops, palindromic k-mers (even k)
+ * and palindromic overlaps (hairpins) get no special case.  A side that is not an end has exactly one neighbour, whose
+ * facing side is not an end either.  An info word is never 0 (a side of degree 0 is an end).
+ * census (may be NULL): KT_GRAPH_CENSUS u64, ADDED into the caller's array, over the nodes:
+ *   [0] nodes  [1] occurrences (sum of counts)  [2] degree sum dL + dR  [3] end sides  [4] isolated (dL == 0 && dR == 0)
+ *   [5] tips (exactly one of dL, dR is 0)  [6] branching (dL > 1 || dR > 1)  [7 + 5 * dL + dR] nodes of those two degrees
+ * End sides may be odd: a hairpin joins a node's side to itself, so end sides / 2 is not a unitig count.
+ * Every node is emitted exactly once as (keys[i], info[i]); counts[i] (counts may be NULL) is its occurrences.
+ * sorted == 0: in unspecified order; sorted != 0: in ascending key order, info and counts following their keys.
+ * *n_out = the number of nodes, always exact.  max_out == 0 (the outputs may be NULL) stores nothing and still fills the
+ * census.  If 0 < max_out < *n_out, nothing past max_out is written (what is written is of no use) and the call returns
+ * KT_ERR_ARG with *n_out set and the census added, so that the caller can resize and repeat.
+ * The table's content does not change; it is probed, so it gets its probing image first, as in kt_ctr_lookup /
+ * kt_ctr_compare(a, a), and is walked in the form it then has.  An empty table gives *n_out = 0 and adds nothing.
+ * One hash partition of an out-of-core count (kt_ctr_add_reads_part) cannot be used: a node's neighbours live in other
+ * partitions, so the answers of partitions cannot be combined - the whole table must be resident (there is no n_parts).
+ * mem says where keys / info / counts / census live.  KT_MEM_HOST synchronises; KT_MEM_DEVICE writes on the context's
+ * stream, but the call still synchronises once, to learn *n_out.
+ * KT_ERR_ARG: a null table or n_out, min_count == 0, min_count > max_count, a bad mem, null keys or info with
+ * max_out > 0, a table that is one shard of a sharded table (n_owners > 1: not supported).  An overflowed table is
+ * KT_ERR_FULL as in kt_ctr_size.  On every one of these errors the output arrays and the census are untouched. */
+#define KT_GRAPH_CENSUS 32
+int kt_ctr_graph(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint64_t *keys, uint32_t *info, uint32_t *counts,
+                 uint64_t max_out, uint64_t *n_out, uint64_t *census, int mem, int sorted);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

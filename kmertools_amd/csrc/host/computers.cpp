@@ -2017,6 +2017,120 @@ std::string SetopComputer::setop() {
 }
 
 // ---------------------------------------------------------------------------------------------
+GraphComputer::GraphComputer(std::string in_path, std::string out_dir, int ksize)
+    : in_path_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
+
+GraphComputer::~GraphComputer() {
+    if (table_) kt_ctr_destroy(table_);
+}
+
+// the census names, in kt_ctr_graph's order
+static std::string graph_census_name(int j) {
+    static const char *sums[7] = {"nodes", "occurrences", "degree_sum", "end_sides", "isolated", "tips", "branching"};
+    if (j < 7) return sums[j];
+    return "degree_" + std::to_string((j - 7) / 5) + "_" + std::to_string((j - 7) % 5);
+}
+
+std::string GraphComputer::graph() {
+    if (table_) kt_ctr_destroy(table_);
+    table_ = nullptr;
+    // The table is sized as CountComputer::count sizes its own.  HBM per slot: the slot (16) + its share of the result
+    // (key, info, count: 16 bytes a node) and of the sort's second pair (12), with 1.9 slots per entry: 28 / 1.9 < 15
+    Lap setup;
+    uint64_t want = 0;
+    if (std::string e = compare_want(in_path_, ksize_, &want); !e.empty()) return e;
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
+    uint64_t free_b = 0, total_b = 0, fit = want;
+    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
+        const uint64_t reserve = TWO_TABLE_BATCH_BASES * 20 + (1ull << 30);
+        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
+        fit = usable / 10 * 9 / (16 + 15);
+    }
+    fit = std::min(fit, env_u64_host("KT_CTR_MAX_SLOTS", ~0ull));  // (tests: what forces the other commands' passes)
+    if (fit < 1024) fit = 1024;
+    const char *whole = "graph needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
+                        "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
+                        "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
+                        "memory or a smaller input";
+    if (want > fit) return std::string(whole) + " (" + std::to_string(want) + " slots wanted, room for " + std::to_string(fit) + ")";
+    if (const int rc = kt_ctr_create(dev_.ctx, ksize_, want, &table_); rc != KT_OK)
+        return rc == KT_ERR_NOMEM ? std::string(whole) + " (" + kt_last_error() + ")" : std::string(kt_last_error());
+    if (getenv("KT_CLI_TIMING")) {
+        uint64_t slots = want;
+        (void)kt_ctr_capacity(table_, &slots);
+        fprintf(stderr, "[timing] graph setup: table of %llu slots %.3f s\n", (unsigned long long)slots, setup());
+    }
+    PhaseTimer pt("graph");
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    Batch b;
+    Lap lap;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(TWO_TABLE_BATCH_BASES), cli_batch_reads(1ull << 22));
+        pt.t[0] += lap();
+        if (b.n_reads() && !b.bases.empty())
+            if (kt_ctr_add_reads(table_, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST) != KT_OK) return kt_last_error();
+        pt.t[1] += lap();
+        if (!more) break;
+    }
+    if (reader.failed()) return reader.error();
+    // what can be a node at most sizes the host arrays: one call, no counting call before it
+    uint64_t bound = 0, n = 0, census[KT_GRAPH_CENSUS] = {};
+    if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
+    if (stats_only_) bound = 0;
+    std::vector<uint64_t> keys((size_t)bound);
+    std::vector<uint32_t> info((size_t)bound), counts((size_t)bound);
+    if (kt_ctr_graph(table_, min_count_, max_count_, keys.data(), info.data(), counts.data(), bound, &n, census, KT_MEM_HOST, 1) != KT_OK)
+        return kt_last_error();
+    pt.t[1] += lap();
+    if (!stats_only_) {
+        const std::string npath = out_dir_ + "/graph.nodes";
+        FILE *out = fopen(npath.c_str(), "wb");
+        if (!out) return "Unable to write to file: " + npath;
+        // ~64 bytes of text a node, a slab at a time (TableWriter's bound)
+        uint64_t slab = (uint64_t)(memory_ceil_gb_ * (double)(1ull << 30) / 16.0 / 64.0);
+        slab = std::min<uint64_t>(std::max<uint64_t>(slab, 1ull << 16), 1ull << 20);
+        std::vector<std::string> pieces;
+        bool ok = true;
+        for (uint64_t i0 = 0; i0 < n && ok; i0 += slab) {
+            format_rows(std::min(slab, n - i0), threads_, (size_t)ksize_ + 26, pieces, [&](uint64_t r, std::string &s) {
+                const uint64_t i = i0 + r;
+                char buf[40];
+                if (acgt_) {
+                    kt_numeric_to_kmer(keys[i], ksize_, buf);
+                    s += buf;
+                } else {
+                    const auto rr = std::to_chars(buf, buf + sizeof buf, keys[i]);
+                    s.append(buf, (size_t)(rr.ptr - buf));
+                }
+                s += '\t';
+                const auto r2 = std::to_chars(buf, buf + sizeof buf, counts[i]);
+                s.append(buf, (size_t)(r2.ptr - buf));
+                s += '\t';
+                for (int x = 0; x < 4; x++) s += info[i] >> (4 + x) & 1u ? "ACGT"[x] : '.';
+                s += '\t';
+                for (int x = 0; x < 4; x++) s += info[i] >> x & 1u ? "ACGT"[x] : '.';
+                s += '\t';
+                s += info[i] & 0x200u ? 'L' : '.';
+                s += info[i] & 0x100u ? 'R' : '.';
+                s += '\n';
+            });
+            for (const auto &p : pieces) ok = ok && fwrite(p.data(), 1, p.size(), out) == p.size();
+        }
+        if (fclose(out) != 0 || !ok) return "Unable to write to file: " + npath;
+    }
+    std::string s;
+    for (int j = 0; j < KT_GRAPH_CENSUS; j++) s += graph_census_name(j) + '\t' + std::to_string(census[j]) + '\n';
+    const std::string spath = out_dir_ + "/graph.stats";
+    FILE *out = fopen(spath.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + spath;
+    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
+    pt.t[3] += lap();
+    return "";
+}
+
+// ---------------------------------------------------------------------------------------------
 // minimisers: one C-ABI call per batch; the capacity is a guess that is corrected on the first miss
 static std::string minimiser_batch(kt_ctx *ctx, Work &w, uint64_t wsize, int msize) {
     const uint64_t n = w.b.n_reads();

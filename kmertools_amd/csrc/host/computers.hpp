@@ -357,6 +357,35 @@ class SetopComputer {
     void release();
 };
 
+// `graph`: which k-mers of an input follow which - the de Bruijn adjacency of its counted k-mers, the unitig ends and the
+// node census (kt_ctr_graph, sorted).  One table, and the whole of it on the device: a node's neighbours live in other hash
+// partitions, so a count that would take several passes is refused before anything is written.  Writes
+// {out_dir}/graph.nodes ("kmer\tcount\tleft4\tright4\tends2" per node, ascending numeric key; not with stats_only) and
+// {out_dir}/graph.stats (the KT_GRAPH_CENSUS values as "name\tvalue" lines).
+class GraphComputer {
+  public:
+    GraphComputer(std::string in_path, std::string out_dir, int ksize);
+    ~GraphComputer();
+    GraphComputer(const GraphComputer &) = delete;
+    GraphComputer &operator=(const GraphComputer &) = delete;
+    void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
+    void set_acgt_output(bool a) { acgt_ = a; }
+    void set_stats_only(bool s) { stats_only_ = s; }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // the text slabs shrink with it; the table lives in HBM
+    void set_device(int d) { dev_.index = d; }
+    std::string graph();  // "" or the error message
+
+  private:
+    std::string in_path_, out_dir_;
+    int ksize_, threads_ = 0;
+    uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
+    bool acgt_ = false, stats_only_ = false;
+    double memory_ceil_gb_ = 6.0;
+    Device dev_;
+    kt_ctr *table_ = nullptr;
+};
+
 // `sketch`: bottom-s MinHash sketches of the records of an input (kt_sketch_batch), of the whole input (--single: the
 // batches' sketches merged by kt_sketch_merge) and the Mash distances between them (kt_sketch_pairs, a block of rows of the
 // matrix at a time; the formula is kt_mash_distance).  Writes {out_dir}/sketch.tsv ("id\tlength\tkmers\tsize\th0,h1,..."

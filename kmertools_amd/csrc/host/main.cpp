@@ -4,7 +4,8 @@
 // auto-derived short flags, `--flag=value`, `-k4`.  `min`: args.rs:172-205, :326-352.  `filter` (a k-mer read
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
 // and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
-// inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances).
+// inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances) and `graph` (de Bruijn adjacency of the counted
+// k-mers).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -135,6 +136,7 @@ const char *HELP_MAIN =
     "  compare Compare the k-mer counts of two inputs (matrix and set similarity)\n"
     "  profile Per-position k-mer counts and per-sequence min / median / mean / max\n"
     "  setop   Intersect, subtract, union or xor the k-mer sets of two inputs\n"
+    "  graph   De Bruijn adjacency, unitig ends and node census of the counted k-mers\n"
     "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
@@ -814,6 +816,65 @@ int cmd_setop(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_GRAPH =
+    "De Bruijn adjacency, unitig ends and node census of the counted k-mers\n\n"
+    "Counts the canonical k-mers of the input.  A k-mer is a node when min-count <= its count <= max-count.  Writes one line\n"
+    "per node to {output}/graph.nodes, in ascending order of the numeric k-mer (with --acgt too):\n"
+    "\"kmer<TAB>count<TAB>left4<TAB>right4<TAB>ends2\", the k-mer as `ctr` writes it.  Position x of right4 is \"ACGT\"[x] when the\n"
+    "k-mer's last k - 1 bases followed by that base are a node (either strand), of left4 when that base followed by its first\n"
+    "k - 1 bases are one, else \".\"; ends2 is \"L\" or \".\" followed by \"R\" or \".\": a unitig ends at that side (the side has no\n"
+    "or several neighbours, or its neighbour has several on the facing side).  {output}/graph.stats holds the census, one\n"
+    "\"name<TAB>value\" line each: nodes, occurrences, degree_sum, end_sides, isolated, tips, branching and degree_<l>_<r>, the\n"
+    "nodes with l left and r right neighbours (l, r = 0..4).  The whole table must fit the device memory: a k-mer's neighbours\n"
+    "live anywhere in it, so graph cannot count in several passes as the other commands do, and says so before it writes.\n\n"
+    "Usage: kmertools graph [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "      --min-count <N>          Lowest count of a node [default: 1]\n"
+    "      --max-count <N>          Highest count of a node [default: 4294967295]\n"
+    "      --acgt                   Output ACGT instead of numeric values\n"
+    "      --stats-only             Write graph.stats only, no graph.nodes\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (the table lives in HBM; the text is written in slabs)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_graph(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
+                                     {0, "max-count", true},   {0, "acgt", false},         {0, "stats-only", false}, {'m', "memory", true},
+                                     {'t', "threads", true},   {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_GRAPH);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work and before the output directory is made
+    const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
+    const uint64_t hi = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (lo > hi)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(lo) + " is greater than " + std::to_string(hi));
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+        fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
+        return 101;
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    GraphComputer gc(in, out, k);
+    gc.set_range((uint32_t)lo, (uint32_t)hi);
+    gc.set_acgt_output(f.count("acgt") != 0);
+    gc.set_stats_only(f.count("stats-only") != 0);
+    if (threads > 0) gc.set_threads(threads);
+    gc.set_max_memory((double)mem);
+    gc.set_device(device);
+    if (std::string e = gc.graph(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -944,5 +1005,6 @@ int main(int argc, char **argv) {
     if (cmd == "profile") return cmd_profile(argc, argv, 2);
     if (cmd == "sketch") return cmd_sketch(argc, argv, 2);
     if (cmd == "setop") return cmd_setop(argc, argv, 2);
+    if (cmd == "graph") return cmd_graph(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

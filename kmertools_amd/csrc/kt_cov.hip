@@ -342,6 +342,14 @@ extern "C" int kt_cov_batch_part(kt_ctr *table, const uint8_t *bases, const uint
     return KT_OK;
 }
 
+int ktl::lookup_counts(kt_ctr *table, const uint64_t *d_keys, uint64_t n, uint32_t *d_counts) {
+    kt_ctx *ctx = table->ctx;
+    hipLaunchKernelGGL(lookup_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
+                       probed_of(table), d_keys, n, d_counts);
+    KT_HIP(hipGetLastError());
+    return KT_OK;
+}
+
 extern "C" int kt_ctr_lookup(kt_ctr *table, const uint64_t *keys, uint64_t n, uint32_t *counts, int mem) {
     if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_lookup: null table");
     kt_ctx *ctx = table->ctx;
@@ -354,9 +362,7 @@ extern "C" int kt_ctr_lookup(kt_ctr *table, const uint64_t *keys, uint64_t n, ui
     uint32_t *d_counts = nullptr;
     if (int rc = call.in(kt::AUX1, keys, n, &d_keys)) return rc;
     if (int rc = call.out(kt::AUX2, counts, n, &d_counts)) return rc;
-    hipLaunchKernelGGL(lookup_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
-                       probed_of(table), d_keys, n, d_counts);
-    KT_HIP(hipGetLastError());
+    if (int rc = lookup_counts(table, d_keys, n, d_counts)) return rc;
     return call.finish();
 }
 

@@ -217,7 +217,7 @@ __global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__r
     }
 }
 
-// ---- a table's entries in the form they are in (view_of builds it; the walks of spectrum, compare and setop read it) ---------
+// ---- a table's entries in the form they are in (view_of builds it; the walks of spectrum, compare, setop and graph read it) ---------
 // The form is the kernels' template argument; the view holds what they read.
 enum Form { FORM_PROBE = 0, FORM_DENSE = 1, FORM_PAIRS = 2 };
 struct TableView {
@@ -604,14 +604,15 @@ struct SetShared {
 };
 
 // the workgroup's tile: entries with out[u] != 0 are kept.  Every thread of the workgroup must be here, `step` counting
-// the calls (two barriers a call; the parity keeps a step's LDS words apart from its neighbours').
-__device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)[SET_UNROLL], const uint32_t (&out)[SET_UNROLL],
-                                         SetShared &sm, uint32_t &step) {
+// the calls (two barriers a call; the parity keeps a step's LDS words apart from its neighbours').  N: the walk's unroll.
+template <uint32_t N>
+__device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)[N], const uint32_t (&out)[N], SetShared &sm,
+                                         uint32_t &step) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, par = step++ & 1u;
-    uint64_t bal[SET_UNROLL];
+    uint64_t bal[N];
     uint32_t total = 0;
 #pragma unroll
-    for (uint32_t u = 0; u < SET_UNROLL; u++) {
+    for (uint32_t u = 0; u < N; u++) {
         bal[u] = __ballot(out[u] != 0u);
         total += (uint32_t)__popcll(bal[u]);
     }
@@ -630,7 +631,7 @@ __device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)
     if (!total) return;
     uint64_t base = sm.tile_base[par] + before;
 #pragma unroll
-    for (uint32_t u = 0; u < SET_UNROLL; u++) {
+    for (uint32_t u = 0; u < N; u++) {
         if ((bal[u] >> lane) & 1ull) {
             const uint64_t pos = base + __popcll(bal[u] & ((1ull << lane) - 1ull));
             if (pos < s.max_out) {
@@ -652,6 +653,134 @@ __global__ __launch_bounds__(BLOCK) void setop_kernel(TableView w, SetArgs s) {
         s.probed.counts(key, present(key), [&](uint32_t u, uint32_t cp) { out[u] = set_decide<SECOND>(s, cw[u], cp); });
         set_emit(s, key, out, sm, step);
     });
+}
+
+// ---- de Bruijn adjacency of a table's k-mers (kt_ctr_graph) -----------------------------------------------------------
+// The table walked read-only in the form it is in (walk_entries) and probed in its own probing image: an entry whose count
+// lies in [lo, hi] is a node, and its 14 related k-mers - the 4 right and 4 left neighbours of its forward string F (the
+// canonical word itself) and the 3 + 3 other k-mers that enter those neighbours from the same side - are all functions of
+// F alone, so their home-slot loads go out together (kttab::Probed::counts, 14 x 16 bytes in flight per node).  A related
+// k-mer's reverse complement comes from R = rev_comp(F) by the mirrored shift, so one bit reversal serves all 14.  The info
+// words are compacted as setop compacts its counts (set_emit: info != 0 for every node); the census is tallied in registers
+// (the seven sums and cell (1, 1), where the nodes of a genome's unitigs fall), the other degree cells in LDS, and every
+// workgroup adds its non-zero cells to the caller's 32 once, at the end.
+// The unroll is the walk's and the emit tile's only (BLOCK x GRAPH_UNROLL entries per cursor atomic); the nodes of a step
+// are resolved one after the other, 14 loads in flight each.  The compiler reports 119 VGPRs at 2 (4 waves per SIMD) and
+// 133 at 4 (3 waves): 2 keeps the fourth wave, and at 14 probes per node the cursor is far from binding.
+#ifndef KT_GRAPH_UNROLL
+#define KT_GRAPH_UNROLL 2
+#endif
+constexpr uint32_t GRAPH_UNROLL = KT_GRAPH_UNROLL, GRAPH_KEYS = 14, GRAPH_SUMS = 7, GRAPH_CELLS = 25;
+static_assert(GRAPH_SUMS + GRAPH_CELLS == KT_GRAPH_CENSUS, "the census layout");
+
+struct GraphArgs {
+    SetArgs s;          // probed: the table itself; lo_w / hi_w: the solid range; the (key, info) output and its cursor
+    uint64_t *census;   // KT_GRAPH_CENSUS cells, added into (null: no census)
+    uint32_t k;
+};
+
+// the info word of node F (canonical, k bases): bits 0..3 right neighbours, 4..7 left neighbours, 8 right end, 9 left end
+__device__ __forceinline__ uint32_t graph_info(const GraphArgs &g, uint64_t F) {
+    const uint32_t top = 2u * g.k - 2u;                    // where a k-mer's first base sits (<= 60)
+    const uint64_t mask = (1ull << (2u * g.k)) - 1ull;     // 2k <= 62
+    const uint64_t low = mask >> 2;                        // the last k - 1 bases
+    const uint64_t R = ktd::rev_comp(F, (int)g.k);
+    const uint64_t first = F >> top, last = F & 3ull;
+    uint64_t key[GRAPH_KEYS];
+#pragma unroll
+    for (uint64_t x = 0; x < 4; x++) {
+        // F[1..k) + x and its reverse complement comp(x) + R[0..k-1)
+        const uint64_t rf = ((F << 2) & mask) | x, rr = (R >> 2) | ((3ull - x) << top);
+        // x + F[0..k-1) and R[1..k) + comp(x)
+        const uint64_t lf = (F >> 2) | (x << top), lr = ((R << 2) & mask) | (3ull - x);
+        key[x] = rf < rr ? rf : rr;
+        key[4 + x] = lf < lr ? lf : lr;
+    }
+#pragma unroll
+    for (uint64_t j = 0; j < 3; j++) {
+        // y + F[1..k) for the three y != F[0] (what else enters the right neighbours), reverse complement R[0..k-1) + comp(y)
+        const uint64_t yr = j + (j >= first ? 1ull : 0ull);
+        const uint64_t sf = (F & low) | (yr << top), sr = (R & ~3ull) | (3ull - yr);
+        // F[0..k-1) + y for the three y != F[k-1], reverse complement comp(y) + R[1..k)
+        const uint64_t yl = j + (j >= last ? 1ull : 0ull);
+        const uint64_t tf = (F & ~3ull) | yl, tr = (R & low) | ((3ull - yl) << top);
+        key[8 + j] = sf < sr ? sf : sr;
+        key[11 + j] = tf < tr ? tf : tr;
+    }
+    uint32_t solid = 0;
+    g.s.probed.counts(key, (1u << GRAPH_KEYS) - 1u, [&](uint32_t u, uint32_t c) {
+        solid |= (c >= g.s.lo_w && c <= g.s.hi_w ? 1u : 0u) << u;
+    });
+    const uint32_t dR = __popc(solid & 0xFu), dL = __popc(solid & 0xF0u);
+    const uint32_t sibR = 1u + __popc(solid & 0x700u), sibL = 1u + __popc(solid & 0x3800u);
+    return (solid & 0xFFu) | (dR != 1u || sibR != 1u ? 0x100u : 0u) | (dL != 1u || sibL != 1u ? 0x200u : 0u);
+}
+
+struct GraphTally {
+    uint32_t n = 0, deg = 0, ends = 0, isolated = 0, tips = 0, branching = 0, c11 = 0;
+    uint64_t occ = 0;
+    __device__ __forceinline__ void add(uint32_t info, uint32_t c, uint32_t *cells) {
+        const uint32_t dR = __popc(info & 0xFu), dL = __popc(info & 0xF0u);
+        n++;
+        occ += c;
+        deg += dL + dR;
+        ends += __popc(info & 0x300u);
+        isolated += dL == 0u && dR == 0u;
+        tips += (dL == 0u) != (dR == 0u);
+        branching += dL > 1u || dR > 1u;
+        if (dL == 1u && dR == 1u) c11++;
+        else atomicAdd(&cells[5u * dL + dR], 1u);  // (no-return ds_add)
+    }
+};
+
+// w: the table's view, FORM = its form
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void graph_kernel(TableView w, GraphArgs g) {
+    __shared__ SetShared sm;
+    __shared__ uint32_t cells[GRAPH_CELLS];
+    __shared__ unsigned long long sums[GRAPH_SUMS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (tid < GRAPH_CELLS) cells[tid] = 0u;
+    if (tid < GRAPH_SUMS) sums[tid] = 0ull;
+    ktd::lds_barrier();
+    GraphTally t;
+    uint32_t step = 0;
+    walk_entries<FORM, GRAPH_UNROLL, true>(w, [&](const uint64_t (&key)[GRAPH_UNROLL], const uint32_t (&cw)[GRAPH_UNROLL]) {
+        uint32_t out[GRAPH_UNROLL] = {};
+#pragma unroll
+        for (uint32_t u = 0; u < GRAPH_UNROLL; u++) {
+            // (a lane without an entry, or whose entry is not a node, issues no probe)
+            if (key[u] != KT_EMPTY_KEY && cw[u] >= g.s.lo_w && cw[u] <= g.s.hi_w) {
+                out[u] = graph_info(g, key[u]);
+                t.add(out[u], cw[u], cells);
+            }
+        }
+        set_emit(g.s, key, out, sm, step);
+    });
+    if (!g.census) return;
+    // the register tallies: one wave reduction each, lane 0 adds the wave's sums to the workgroup's
+    {
+        uint64_t v[GRAPH_SUMS] = {t.n, t.occ, t.deg, t.ends, t.isolated, t.tips, t.branching};
+        uint32_t c11 = t.c11;
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+            for (uint32_t j = 0; j < GRAPH_SUMS; j++) v[j] += __shfl_down(v[j], o, 64);
+            c11 += __shfl_down(c11, o, 64);
+        }
+        if (lane == 0 && v[0]) {
+#pragma unroll
+            for (uint32_t j = 0; j < GRAPH_SUMS; j++)
+                if (v[j]) atomicAdd(&sums[j], (unsigned long long)v[j]);
+            if (c11) atomicAdd(&cells[5u * 1u + 1u], c11);
+        }
+    }
+    ktd::lds_barrier();
+    if (tid < GRAPH_SUMS) {
+        if (const unsigned long long v = sums[tid]) atomicAdd(reinterpret_cast<unsigned long long *>(g.census + tid), v);
+    } else if (tid < GRAPH_SUMS + GRAPH_CELLS) {
+        if (const uint32_t v = cells[tid - GRAPH_SUMS])
+            atomicAdd(reinterpret_cast<unsigned long long *>(g.census + tid), (unsigned long long)v);
+    }
 }
 
 __global__ __launch_bounds__(BLOCK) void route_count_kernel(SegArgs a, uint32_t n_owners,
@@ -1284,6 +1413,66 @@ extern "C" int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32
     call.back(counts, (const uint32_t *)d_counts, written);
     if (int rc = call.finish()) return rc;
     if (max_out && n > max_out) return call.fail("max_out smaller than the result (*n_out entries)");
+    return KT_OK;
+}
+
+extern "C" int kt_ctr_graph(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint64_t *keys, uint32_t *info,
+                            uint32_t *counts, uint64_t max_out, uint64_t *n_out, uint64_t *census, int mem, int sorted) {
+    if (!table || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_graph: null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, mem, "kt_ctr_graph");
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (min_count == 0) return call.fail("min_count must be >= 1");
+    if (min_count > max_count) return call.fail("min_count > max_count");
+    if (int rc = call.enter()) return rc;
+    if (max_out && (!keys || !info)) return call.fail("null output");
+    uint64_t n_t = 0;
+    if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    *n_out = 0;
+    if (!n_t) return KT_OK;
+    // the table is probed: its probing image first; its form is read only after that (it is walked as it is now)
+    if (int rc = table_ready(table)) return rc;
+    // host: this call's results are made in scratch - AUX1: keys | census, AUX2: info | counts
+    uint64_t *d_keys = keys, *d_census = census;
+    uint32_t *d_info = info, *d_counts = counts;
+    if (call.host()) {
+        if (int rc = call.scratch(kt::AUX1, (max_out + KT_GRAPH_CENSUS) * 8, &d_keys)) return rc;
+        d_census = census ? d_keys + max_out : nullptr;
+        if (census) KT_HIP(hipMemsetAsync(d_census, 0, KT_GRAPH_CENSUS * 8, ctx->stream));
+        if (max_out) {
+            if (int rc = call.scratch(kt::AUX2, max_out * 8, &d_info)) return rc;
+            d_counts = counts ? d_info + max_out : nullptr;
+        }
+    }
+    uint64_t *cursor = table->cursor;
+    KT_HIP(hipMemsetAsync(cursor, 0, 8, ctx->stream));
+    const GraphArgs g{SetArgs{probed_of(table), 0u, 0u, min_count, max_count, 1u, 0xFFFFFFFFu, d_keys, d_info, max_out, cursor},
+                      d_census, (uint32_t)table->k};
+    const TableWalk w = view_of(table, n_t);
+    if (int rc = launch_walk(ctx, w, w.v.n, (uint64_t)BLOCK * GRAPH_UNROLL, [&](auto form, dim3 grid) {
+            hipLaunchKernelGGL(graph_kernel<decltype(form)::value>, grid, dim3(BLOCK), 0, ctx->stream, w.v, g);
+        }))
+        return rc;
+    uint64_t n = 0;
+    KT_HIP(hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KT_HIP(hipStreamSynchronize(ctx->stream));
+    *n_out = n;
+    const uint64_t written = n < max_out ? n : max_out;
+    if (sorted && written == n)  // (a result that did not fit is not a result: the caller repeats the call)
+        if (int rc = kt_sort_pairs(ctx, d_keys, d_info, n, 2u * (uint32_t)table->k)) return rc;
+    // the counts of the emitted keys, in the order they are left in: they need not ride through the sort
+    if (d_counts && written)
+        if (int rc = lookup_counts(table, d_keys, written, d_counts)) return rc;
+    call.back(keys, (const uint64_t *)d_keys, written);
+    call.back(info, (const uint32_t *)d_info, written);
+    call.back(counts, (const uint32_t *)d_counts, written);
+    if (call.host() && census) {
+        std::unique_ptr<uint64_t[]> h;
+        if (int rc = call.fetch((const uint64_t *)d_census, (uint64_t)KT_GRAPH_CENSUS, &h)) return rc;
+        for (int j = 0; j < KT_GRAPH_CENSUS; j++) census[j] += h[j];
+    }
+    if (int rc = call.finish()) return rc;
+    if (max_out && n > max_out) return call.fail("max_out smaller than the result (*n_out nodes)");
     return KT_OK;
 }
 

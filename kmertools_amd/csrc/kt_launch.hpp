@@ -24,6 +24,9 @@ inline kttab::Probed probed_of(const kt_ctr *ctr, uint32_t n_parts = 1, uint32_t
 }
 // makes the table readable: performs a deferred clear, reports KT_ERR_FULL if it overflowed
 int table_ready(kt_ctr *ctr);
+// d_counts[i] = occurrences of d_keys[i] in the table (0: absent), n > 0 device keys, on the context's stream; the table
+// holds its probing image (table_ready).  kt_cov.hip's lookup_kernel.
+int lookup_counts(kt_ctr *table, const uint64_t *d_keys, uint64_t n, uint32_t *d_counts);
 
 // One call of an entry point that takes `int mem`.  It holds the call's claim scope on the context's scratch and is the
 // only place that tells the two memory kinds apart: for KT_MEM_DEVICE every method hands the caller's pointer through

@@ -93,6 +93,20 @@ def mash_distance(shared, denom, k):
     return float(_lib.lib().kt_mash_distance(int(shared), int(denom), int(k)))
 
 
+# the cells of Counter.graph's census, in order (kt_ctr_graph): degree_<dL>_<dR> = nodes with those two degrees
+GRAPH_CENSUS_NAMES = ("nodes", "occurrences", "degree_sum", "end_sides", "isolated", "tips", "branching") + tuple(
+    "degree_%d_%d" % (dl, dr) for dl in range(5) for dr in range(5))
+
+
+def graph_info_text(info):
+    """an info word of Counter.graph as (left4, right4, ends2), `kmertools graph`'s rendering: position x of left4 /
+    right4 is "ACGT"[x] when that neighbour is a node, else "."; ends2 is "L" or "." followed by "R" or "." """
+    info = int(info)
+    right = "".join("ACGT"[x] if info >> x & 1 else "." for x in range(4))
+    left = "".join("ACGT"[x] if info >> (4 + x) & 1 else "." for x in range(4))
+    return left, right, ("L" if info & 0x200 else ".") + ("R" if info & 0x100 else ".")
+
+
 def to_csr(seqs):
     """list[str|bytes] -> (bases u8[total], offsets u64[n+1])"""
     bs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
@@ -654,6 +668,34 @@ class Counter:
         n = C.c_uint64()
         check(_lib.lib().kt_ctr_setop(self._h, other._h, *args, _ptr(keys), _ptr(counts), int(max_out), C.byref(n),
                                       KT_MEM_DEVICE, int(bool(sort))))
+        return n.value
+
+    def graph(self, min_count=1, max_count=None, sort=True, census=False):
+        """The de Bruijn adjacency of the table's k-mers with min_count <= count <= max_count (the nodes; None: no upper
+        bound) as numpy (keys u64, info u32, counts u32), ascending by key with sort.  info: bit x = right neighbour
+        F[1..k) + "ACGT"[x] is a node, bit 4 + x = left neighbour "ACGT"[x] + F[0..k-1) is one, bit 8 / 9 = a unitig ends
+        at the right / left side (F: the canonical k-mer itself).  census=True: also the KT_GRAPH_CENSUS u64 cells named
+        by GRAPH_CENSUS_NAMES.  A count-only call, then one call sized by it (kt_ctr_graph)."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        n = C.c_uint64()
+        cen = np.zeros(_lib.KT_GRAPH_CENSUS, np.uint64)
+        check(_lib.lib().kt_ctr_graph(self._h, int(min_count), hi, None, None, None, 0, C.byref(n), _ptr(cen), KT_MEM_HOST, 0))
+        keys = np.zeros(n.value, np.uint64)
+        info = np.zeros(n.value, np.uint32)
+        counts = np.zeros(n.value, np.uint32)
+        if n.value:
+            check(_lib.lib().kt_ctr_graph(self._h, int(min_count), hi, _ptr(keys), _ptr(info), _ptr(counts), n.value,
+                                          C.byref(n), None, KT_MEM_HOST, int(bool(sort))))
+        return (keys, info, counts, cen) if census else (keys, info, counts)
+
+    def graph_device(self, keys, info, counts, max_out, min_count=1, max_count=None, sort=True, census=None):
+        """graph into device tensors of max_out entries (keys u64 / info, counts u32 bit patterns; counts may be None;
+        None, None, None, 0 only counts the nodes) and, added, into `census` (KT_GRAPH_CENSUS u64 on the device, or None);
+        returns the number of nodes.  Raises KmertoolsError (KT_ERR_ARG) when 0 < max_out < that number."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        n = C.c_uint64()
+        check(_lib.lib().kt_ctr_graph(self._h, int(min_count), hi, _ptr(keys), _ptr(info), _ptr(counts), int(max_out),
+                                      C.byref(n), _ptr(census), KT_MEM_DEVICE, int(bool(sort))))
         return n.value
 
     def export_stage_range(self, min_count=1, max_count=None):
