@@ -212,7 +212,10 @@ int kt_ctr_export(kt_ctr *ctr, uint64_t *keys, uint32_t *counts, uint64_t max_ou
  * kt_ctr_export_stage gathers the entries on the DEVICE (a staging area of the library; a table counted into an export
  * target has them there already) and returns their number; kt_ctr_export_fetch then copies entries
  * [first, first + count) to host arrays, any number of times, in any order.  The staged entries stay valid until the table
- * is changed (kt_ctr_clear, adds) or another export / cov call uses the context's scratch. */
+ * is changed (kt_ctr_clear, adds), staged again or given another export target - and, for a table counted into an export
+ * target, until a call that probes the table (kt_ctr_lookup, kt_cov_batch, kt_ctr_profile, kt_ctr_graph, a kt_ctr_compare /
+ * kt_ctr_setop that probes it, ...): such a call gives the target's arrays back to the caller.  After any of these
+ * kt_ctr_export_fetch is KT_ERR_ARG until the entries are staged again. */
 int kt_ctr_export_stage(kt_ctr *ctr, uint64_t *n_out);
 int kt_ctr_export_fetch(kt_ctr *ctr, uint64_t first, uint64_t count, uint64_t *keys_host, uint32_t *counts_host);
 

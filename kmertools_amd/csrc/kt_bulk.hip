@@ -3743,6 +3743,9 @@ int kt_table_image(kt_ctr *ctr) {
     if (ctr->dense_ext) {  // the entries are the caller's export arrays: back into an empty table, as (key, count) pairs
         ctr->dense = false;
         ctr->dense_ext = false;
+        // entries that kt_ctr_export_stage staged by pointing at those arrays go with them: from here on they are the
+        // caller's to reuse, and a fetch must not hand out what it has put there (kt_ctr_export_fetch says "stage first")
+        if (ctr->stage_keys == ctr->xt_keys) ctr->stage_n = 0;
         return kt_ctr_reload_pairs(ctr, ctr->xt_keys, ctr->xt_counts);
     }
     kt_ctx *ctx = ctr->ctx;
