@@ -1,9 +1,12 @@
 """Read batches for the tests, as plain helpers (no test in here): the CSR `Batch`, the noisy ragged reads and the buffer
-views / guard bands that tests/test_buffer_views.py introduced, and the seeded batch families of
+views / guard bands that tests/test_buffer_views.py introduced, the seeded batch families of
 tests/test_read_boundaries.py - reads far shorter than a 16-base lane, long runs of empty reads, read ends placed on the
 kernels' structural constants, reads of one length - with the numbers that say, from the offsets alone, that a batch
-has the shape it is meant to have.  Also the per-read oracle answers as flat arrays, a pure-Python brute force of "the
-k-mers of a read" that shares no code with the oracle, and the text that says where a result differs.
+has the shape it is meant to have, and the content families of tests/test_read_content.py - every byte value at every
+position of a 32-base item, with and without a raw code next to it, and reads of nothing but the 14 valid bytes - with
+the check that says, from the bytes and offsets alone, that every (value, position) pair is there.  Also the per-read
+oracle answers as flat arrays, a pure-Python brute force of "the k-mers of a read" that shares no code with the oracle,
+and the text that says where a result differs.
 
 Vocabulary (kmertools_amd/csrc): a *lane* is 16 consecutive bases starting at a multiple of 16 (one thread's load in
 kt_oligo.hip, one thread's positions in kt_min.hip); a *segment* is 8192 bases starting at a multiple of 8192 (one
@@ -15,6 +18,8 @@ SLACK = 4096
 GUARD = 0xA5
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 LETTERS = np.frombuffer(b"ACGTUacgtu", np.uint8)      # everything kt_cgr_points accepts
+VALID = np.frombuffer(b"ACGTUacgtu\x00\x01\x02\x03", np.uint8)   # every byte that is a nucleotide: the letters and the raw codes
+ALPHA_LEN, ALPHA_FIRST, ALPHA_STEP, ALPHA_TIMES = 1104, 32, 33, 32   # alphabet_batch: a read, its first occurrence, their distance
 LANE, SEG = 16, 8192
 EMPTY_RUNS = (1, 63, 64, 65, 256, 257, 5000)
 LATTICE = (16, 32, 64, 128, 256, 1008, 1024, 2048, 4096, 7168, 8192)   # 256: kt_sketch.hip's chunks, 2048: a wave's span of a segment
@@ -348,6 +353,156 @@ def mixed_tiles_batch(seed, R):
     lens.append(25)
     bases = _sprinkle(rng, _random_bases(rng, int(np.sum(lens)), False))
     return Batch.of_lens("mixed_tiles(seed=%d,R=%d)" % (seed, R), bases, lens, tiles=kinds)
+
+
+# ---- what the bytes are: every value at every position of an item ------------------------------------------------------------
+
+def alphabet_batch(seed, raw_neighbour=False, ragged=False, values=range(256)):
+    """one read per byte value v: 1104 random ACGT bases (69 lanes, more than the oligo kernel's 1008-byte chunk) with v at the
+    read positions 32 + 33 i, i = 0..31 - 33 apart, so that their batch positions take 32 consecutive residues modulo 32 (every
+    byte of a dword, every dword of a lane's 16-byte load, both lanes of a 32-base item), with 32 valid bases between two of
+    them and at both read ends (valid windows of 31 on both sides of each).  raw_neighbour: a raw code (v + i) & 3 sits
+    1 + (v + i) % 15 bases behind each occurrence - in the same item or the next lane, always in the same wave.  That puts v
+    and the letters around it on the oligo kernel's per-byte path at every position, and on the per-item one of
+    kt_segment.hpp where the raw code shares v's 32-base item: always at the positions 0..16 mod 32, never at 31, in between
+    as the distance has it (check_alphabet says for which positions).  ragged: v % 7 more valid bases in front of each read -
+    the reads differ in length (the oligo kernel's general path) and the items are no longer aligned with them.  meta["values"]: read i is
+    byte values[i]"""
+    rng = np.random.default_rng(seed)
+    values = [int(v) for v in values]
+    lens = np.array([ALPHA_LEN + (v % 7 if ragged else 0) for v in values], np.int64)
+    bases = _random_bases(rng, int(lens.sum()), False)
+    start = np.concatenate(([0], np.cumsum(lens)))[:-1]
+    for v, s, L in zip(values, start.tolist(), lens.tolist()):
+        first = s + L - ALPHA_LEN + ALPHA_FIRST
+        for i in range(ALPHA_TIMES):
+            p = first + ALPHA_STEP * i
+            bases[p] = v
+            if raw_neighbour:
+                bases[p + 1 + (v + i) % 15] = (v + i) & 3
+    return Batch.of_lens("alphabet(seed=%d,raw_neighbour=%s,ragged=%s,%d values)" % (seed, raw_neighbour, ragged, len(values)),
+                         bases, lens, values=values)
+
+
+def valid_mix_batch(seed, n, alphabet=VALID, min_len=0):
+    """n ragged reads of 0..400 bases, every byte drawn uniformly from the 14 valid ones (ACGTUacgtu and the raw codes 0..3):
+    every window is a k-mer, and nearly every item and wave is on the per-byte path with letters in it.  alphabet=LETTERS:
+    the letters alone (for kt_cgr_points); min_len: no read is shorter (callers that define nothing for a shorter one)"""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(min_len, 401, size=n)
+    lens[:4] = (min_len, 400, min_len + 1, min_len)
+    total = int(lens.sum())
+    assert total <= 600_000, total
+    alphabet = np.asarray(alphabet, np.uint8)
+    bases = alphabet[rng.integers(0, len(alphabet), size=total)].copy()
+    return Batch.of_lens("valid_mix(seed=%d,n=%d,%d byte values,min_len=%d)" % (seed, n, len(alphabet), min_len), bases, lens)
+
+
+def _valid_runs(bases, offsets):
+    """-> (left, right): the valid nucleotide bytes directly in front of / behind each base, inside its read"""
+    total = len(bases)
+    pos = np.arange(total, dtype=np.int64)
+    ok = np.isin(bases, VALID)
+    o = np.asarray(offsets, np.int64)
+    rid = np.searchsorted(o, pos, side="right") - 1
+    last_bad = np.maximum.accumulate(np.where(ok, -1, pos))            # the last invalid byte at or before pos
+    prev_bad = np.concatenate(([-1], last_bad[:-1]))                   # ... before pos
+    left = pos - np.maximum(prev_bad + 1, o[rid])
+    next_bad = np.minimum.accumulate(np.where(ok, total, pos)[::-1])[::-1]
+    next_bad = np.concatenate((next_bad[1:], [total]))                 # the first invalid byte behind pos
+    right = np.minimum(next_bad, o[rid + 1]) - 1 - pos
+    return left, right
+
+
+def check_alphabet(batch, raw_neighbour, values=range(256)):
+    """from the bytes and offsets alone: for every value v and every residue q in 0..31 an occurrence of v at a batch position
+    = q mod 32 with at least 31 valid nucleotide bytes on either side inside its read and, with raw_neighbour, a raw code
+    1..15 bases behind it; without, none (v itself apart) within 32 bases on either side: it is v alone that chooses the
+    encoder.  With raw_neighbour, batch.meta["same_item"][v] is the set of positions mod 32 at which that raw code lies in
+    v's own 32-base item (asserted: all of 0..16, and 20 of the 32 at least).  -> the number of such occurrences"""
+    bases = batch.bases
+    total = len(bases)
+    left, right = _valid_runs(bases, batch.offsets)
+    good = (left >= 31) & (right >= 31)
+    c = np.concatenate(([0], np.cumsum(bases < 4)))
+    pos = np.arange(total, dtype=np.int64)
+    near = c[np.minimum(pos + 16, total)] - c[np.minimum(pos + 1, total)] > 0       # (right >= 31: those 15 are in the read)
+    if raw_neighbour:
+        good &= near
+    else:
+        good &= c[np.minimum(pos + 33, total)] - c[np.minimum(pos + 1, total)] + c[pos] - c[np.maximum(pos - 32, 0)] == 0
+    values = np.array([int(v) for v in values], np.int64)
+    seen = np.unique(bases[good].astype(np.int64) * 32 + pos[good] % 32)
+    want = (values[:, None] * 32 + np.arange(32)[None, :]).ravel()
+    missing = np.setdiff1d(want, seen)
+    assert not len(missing), (batch.name, "byte %#04x never at a position = %d mod 32 with valid windows on both sides%s" % (
+        missing[0] // 32, missing[0] % 32, " and a raw code behind it" if raw_neighbour else ""), len(missing))
+    if raw_neighbour:
+        rest = 31 - pos % 32                                                # bases of the item behind pos
+        c_item = c[np.minimum(pos + 1 + np.minimum(rest, 15), total)] - c[np.minimum(pos + 1, total)] > 0
+        shared = good & c_item & np.isin(bases, values)
+        same = {int(v): set() for v in values}
+        for v, q in zip(bases[shared].tolist(), (pos[shared] % 32).tolist()):
+            same[v].add(q)
+        assert all(set(range(17)) <= qs and 31 not in qs and len(qs) >= 20 for qs in same.values()), batch.name
+        batch.meta["same_item"] = same
+    return int(np.isin(bases[good], values).sum())
+
+
+def check_valid_mix(batch, alphabet=VALID, min_len=0):
+    """all of the alphabet's bytes occur, and no other; the shortest and the longest reads are there; with raw codes in the
+    alphabet next to no 32-base item is without one"""
+    assert np.array_equal(np.unique(batch.bases), np.sort(np.asarray(alphabet, np.uint8))), batch.name
+    lens = batch.lens
+    assert (lens == min_len).any() and (lens == 400).any() and (lens < min_len + 16).any() and lens.min() == min_len, batch.name
+    assert batch.total <= 600_000, (batch.name, batch.total)
+    if (np.asarray(alphabet) < 4).any():
+        items = (batch.bases[:batch.total // 32 * 32].reshape(-1, 32) < 4).any(axis=1)
+        assert items.mean() > 0.99, (batch.name, items.mean())
+
+
+def long_stretch_batch(seed, stretch, n_long=6, gap=24):
+    """for the windows wider than the reads of the other content batches: n_long reads, each a stretch of `stretch` bytes
+    drawn from the 14 valid ones, then its share of the 256 byte values, each followed by `gap` valid bytes, then another
+    such stretch; between them a read shorter than the window, an empty one and one of a single stretch.  meta["planted"]:
+    the position of each byte value"""
+    rng = np.random.default_rng(seed)
+    draw = lambda n: VALID[rng.integers(0, len(VALID), size=n)]   # noqa: E731
+    parts, lens, planted, pos = [], [], {}, 0
+    share = np.array_split(np.arange(256), n_long)
+    for j in range(n_long):
+        read = [draw(stretch)]
+        at = pos + stretch
+        for v in share[j].tolist():
+            planted[v] = at
+            read += [np.array([v], np.uint8), draw(gap)]
+            at += 1 + gap
+        read.append(draw(stretch))
+        parts += read
+        lens.append(sum(len(x) for x in read))
+        pos += lens[-1]
+        for extra in ((300, 0, stretch) if j == 0 else ()):
+            parts.append(draw(extra))
+            lens.append(extra)
+            pos += extra
+    b = Batch.of_lens("long_stretch(seed=%d,stretch=%d,n_long=%d,gap=%d)" % (seed, stretch, n_long, gap),
+                      np.concatenate(parts), lens, planted=planted)
+    return b
+
+
+def check_long_stretch(batch, window):
+    """every byte value is planted once, with `gap` valid bytes behind it and a valid one in front; every read of more than
+    two windows begins and ends with more than `window` valid bytes; all 14 valid bytes occur in them"""
+    left, right = _valid_runs(batch.bases, batch.offsets)
+    at = np.array([batch.meta["planted"][v] for v in range(256)], np.int64)
+    assert (batch.bases[at] == np.arange(256)).all() and (left[at] >= 1).all() and (right[at] >= 1).all(), batch.name
+    o = batch.offsets.astype(np.int64)
+    long_reads = np.flatnonzero(batch.lens > 2 * window)
+    assert len(long_reads) >= 2, batch.name
+    for i in long_reads.tolist():
+        assert right[o[i]] >= window and left[o[i + 1] - 1] >= window, (batch.name, i)
+        assert len(np.unique(batch.bases[o[i]:o[i] + window])) == len(VALID), (batch.name, i)
+    assert (batch.lens == 0).any() and ((batch.lens > 0) & (batch.lens < window)).any(), batch.name
 
 
 # ---- what a batch looks like, from its offsets alone --------------------------------------------------------------------------

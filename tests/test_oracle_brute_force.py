@@ -2,8 +2,12 @@
 it holds a byte that is no nucleotide, min(forward, reverse complement) taken - so that the oracle and the kernels cannot
 share one misreading of "a k-mer may not span a read start".  3000 reads of family A (tests/read_batches.py: reads of
 0..8, 0..2k and 12..34 bases with N, lower case, U, raw codes and IUPAC letters), k = 3, 5, 7: the k-mers of every read,
-the oligo rows (raw and canonical) and the count table.  At the end: the comparisons the GPU tests report with
-(first_flat_diff, first_row_diff, table_diff) on doctored arrays - one bit, one ulp, one element or key missing or added."""
+the oligo rows (raw and canonical) and the count table.  Then the content families of tests/test_read_content.py - every
+byte value at every position of an item, alone and with a raw code behind it, and reads of the 14 valid bytes - at
+k = 4, 16, 17, 31 on every 37th read and the reads of the bytes that are most like a nucleotide: what entitles the GPU
+tests to take the oracle as their reference for bytes that no fixture of the reference holds.  At the end: the comparisons
+the GPU tests report with (first_flat_diff, first_row_diff, table_diff) on doctored arrays - one bit, one ulp, one element
+or key missing or added."""
 import numpy as np
 import pytest
 
@@ -55,6 +59,74 @@ def test_oracle_count_table_equals_the_brute_force(oracle, sample, k):
     keys, counts = oracle.count_reads(b.bases, b.offsets, k)
     want = rb.brute_table(b.seqs, k)
     assert dict(zip(keys.tolist(), counts.tolist())) == want and len(keys) == len(want)
+
+
+# ---- the content families: every byte value, with and without a raw code next to it -----------------------------------------
+
+# the bytes one bit, a case fold or a sign away from a nucleotide, the raw codes, load_guarded's 0xFF
+NEAR_NUCLEOTIDES = sorted({0, 1, 2, 3, 4, 0x14, 0x21, 0x40, 0x60, 0x7B, 0x80, 0x83, 0xFF} | set(b"ACGTUacgtuBEFVWNnRSsdw")
+                          | {x | 0x80 for x in b"ACGTUacgtu"})
+CONTENT = ("alphabet", "alphabet_ragged", "alphabet_raw", "alphabet_raw_ragged", "valid_mix")
+
+
+@pytest.fixture(scope="module")
+def content_sample():
+    out = {}
+    for j, name in enumerate(CONTENT):
+        if name == "valid_mix":
+            b = rb.valid_mix_batch(0xb17e, 1400)
+            rb.check_valid_mix(b)
+            pick = list(range(j, b.n, 37))
+        else:
+            raw = "raw" in name
+            b = rb.alphabet_batch(0xb17e + j, raw_neighbour=raw, ragged="ragged" in name)
+            assert rb.check_alphabet(b, raw) >= 256 * 32
+            pick = sorted(set(range(j, b.n, 37)) | set(NEAR_NUCLEOTIDES))
+        out[name] = rb.Batch("%s[%d of them]" % (b.name, len(pick)), [b.seqs[i] for i in pick])
+        out[name].meta["picked"] = pick
+    return out
+
+
+@pytest.mark.parametrize("k", [4, 16, 17, 31])
+@pytest.mark.parametrize("name", CONTENT)
+def test_oracle_equals_the_brute_force_on_every_byte_value(oracle, content_sample, name, k):
+    b = content_sample[name]
+    flat = []
+    for i, (s, o) in enumerate(zip(b.seqs, b.offsets[:-1])):
+        f, r, e = oracle.kmers(s, k)
+        want = rb.brute_kmers(s, k)
+        assert list(zip(f.tolist(), r.tolist(), e.tolist())) == want, (name, k, "read %d" % b.meta["picked"][i], rb.where(b, i))
+        flat += [(f_, r_, e_ + int(o)) for f_, r_, e_ in want]
+    if name != "valid_mix":                                   # 32 occurrences of an invalid byte leave 33 stretches of 32 bases
+        assert len(flat) > 33 * max(0, 33 - k) * 20
+    else:
+        assert len(flat) == int(np.maximum(b.lens - k + 1, 0).sum()) > 1000      # every window is a k-mer
+    wf, wr, we = rb.oracle_kmers_flat(oracle, b, k)
+    assert list(zip(wf.tolist(), wr.tolist(), we.tolist())) == flat
+    keys, counts = oracle.count_reads(b.bases, b.offsets, k)
+    table = rb.brute_table(b.seqs, k)
+    assert dict(zip(keys.tolist(), counts.tolist())) == table and len(keys) == len(table)
+
+
+def test_alphabet_check_notices_a_missing_pair():
+    """check_alphabet on doctored batches: one occurrence replaced, its neighbourhood spoiled, its raw code taken away"""
+    for raw in (False, True):
+        b = rb.alphabet_batch(5, raw_neighbour=raw)
+        assert rb.check_alphabet(b, raw) >= 256 * 32
+        v, i = 0x56, 7
+        p = v * rb.ALPHA_LEN + rb.ALPHA_FIRST + rb.ALPHA_STEP * i
+        assert b.bases[p] == v
+        spoil = ((p + 1 + (v + i) % 15, ord("C")),) if raw else ((p - 32, 2), (p + 32, 1))
+        for at, byte in ((p, ord("A")), (p - 31, ord("N")), (p + 31, ord("N"))) + spoil:
+            doctored = rb.Batch.of_lens(b.name, b.bases.copy(), b.lens)
+            doctored.bases[at] = byte
+            with pytest.raises(AssertionError):
+                rb.check_alphabet(doctored, raw)
+    b = rb.alphabet_batch(5, ragged=True, values=rb.LETTERS)
+    assert b.n == 10 and len(set(b.lens)) > 1 and np.isin(b.bases, rb.LETTERS).all()
+    assert rb.check_alphabet(b, False, rb.LETTERS) >= 10 * 32
+    with pytest.raises(AssertionError):
+        rb.check_alphabet(b, False)
 
 
 # ---- the comparisons of tests/test_read_boundaries.py notice a doctored answer and say where -------------------------------
