@@ -324,6 +324,42 @@ int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32_t min_a, u
 int kt_ctr_graph(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint64_t *keys, uint32_t *info, uint32_t *counts,
                  uint64_t max_out, uint64_t *n_out, uint64_t *census, int mem, int sorted);
 
+/* The maximal unitigs of that graph: the sequences of the compacted de Bruijn graph (what BCALM / Cuttlefish write as
+ * unitigs.fa), spelled on the device.  Nodes, F, canon, the info word and "solid" are exactly kt_ctr_graph's, for the same
+ * (min_count, max_count).  A side of node u (R or L) is JOINED when all of these hold:
+ *   - its end bit is clear; it then has exactly one neighbour string s = F[1..k) + x (right) or x + F[0..k-1) (left);
+ *   - canon(s) != F (no self-links: the homopolymer loop and the hairpin are ends);
+ *   - s is not its own reverse complement, and F is not its own reverse complement (both only matter for even k).
+ * The facing side of v = canon(s) is v's left side if u's right side leads to s == v, v's right side if it leads to
+ * rc(s) == v (mirrored for u's left side), and that side is joined back to u.  Joined sides pair up sides of distinct
+ * nodes, at most one pair per side, so the nodes fall into simple PATHS and simple CYCLES, each node in exactly one:
+ * the unitigs.  A unitig of n nodes is a string of n + k - 1 bases:
+ *   path   its two terminals are the nodes with an unjoined side (a single node is both).  It is spelled from the terminal
+ *          with the smaller canonical k-mer, oriented so that its unjoined side comes first (a single node: as F), through
+ *          the joins to the other terminal; every further node adds one base.
+ *   cycle  (no unjoined side anywhere) linearised at its node with the smallest canonical k-mer: it starts with that
+ *          node's F, leaves through its right side and goes once around, so the last k - 1 bases repeat the first k - 1;
+ *          flag KT_UNITIG_CIRCULAR is set.
+ * The unitigs ascend by the canonical k-mer of their start node (the smaller terminal, the smallest node of a cycle): the
+ * result is a function of the table's content and the count range alone.
+ * bases: ASCII ACGT, concatenated, no separators; offsets: max_unitigs + 1 entries, unitig i = bases[offsets[i] ..
+ * offsets[i + 1]); count_sums[i] (may be NULL) = the sum of its nodes' counts; flags[i] (may be NULL) = KT_UNITIG_* bits.
+ * *n_unitigs and *n_bases are always exact.  max_unitigs == 0 && max_bases == 0 only counts (the outputs may be NULL).
+ * When either room is too small, nothing is written and the call returns KT_ERR_ARG with both numbers set, so that the
+ * caller can resize and repeat.  The table's content does not change; it gets its probing image first, as in
+ * kt_ctr_graph.  An empty table, or a range with no nodes, gives 0 / 0 and offsets[0] = 0 (unless the call only counts).
+ * The whole table must be resident (there is no n_parts, for kt_ctr_graph's reason).
+ * KT_MEM_HOST synchronises; KT_MEM_DEVICE writes on the context's stream and synchronises only to learn the sizes.
+ * KT_ERR_ARG: a null table or null size pointers, min_count == 0, min_count > max_count, a bad mem, null bases with
+ * max_bases > 0, null offsets with any room > 0, a table that is one shard of a sharded table, a table of more than
+ * 2^31 - 2 entries (a node's two oriented states, 2 * index + side, are u32).  An overflowed table is KT_ERR_FULL.  On every
+ * one of these errors the outputs are untouched.  Device scratch: 16 bytes per table entry and 64 per node, 48 more per node when
+ * the graph has cycles, besides kt_ctr_graph's sort. */
+#define KT_UNITIG_CIRCULAR 1u
+int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
+                   uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
+                   uint64_t *n_bases, int mem);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

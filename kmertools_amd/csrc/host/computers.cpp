@@ -2131,6 +2131,124 @@ std::string GraphComputer::graph() {
 }
 
 // ---------------------------------------------------------------------------------------------
+UnitigComputer::UnitigComputer(std::string in_path, std::string out_dir, int ksize)
+    : in_path_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
+
+UnitigComputer::~UnitigComputer() {
+    if (table_) kt_ctr_destroy(table_);
+}
+
+std::string UnitigComputer::unitigs() {
+    if (table_) kt_ctr_destroy(table_);
+    table_ = nullptr;
+    // The table is sized as GraphComputer::graph sizes its own.  HBM per slot: the slot (16) + its share of what
+    // kt_ctr_unitigs keeps when every entry is a node (16 + 64 bytes, 48 more on cycles, the sort's second pair 12), with 1.9 slots per entry:
+    // 140 / 1.9 < 74
+    Lap setup;
+    uint64_t want = 0;
+    if (std::string e = compare_want(in_path_, ksize_, &want); !e.empty()) return e;
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
+    uint64_t free_b = 0, total_b = 0, fit = want;
+    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
+        const uint64_t reserve = TWO_TABLE_BATCH_BASES * 20 + (1ull << 30);
+        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
+        fit = usable / 10 * 9 / (16 + 74);
+    }
+    fit = std::min(fit, env_u64_host("KT_CTR_MAX_SLOTS", ~0ull));  // (tests: what forces the other commands' passes)
+    if (fit < 1024) fit = 1024;
+    const char *whole = "unitigs needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
+                        "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
+                        "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
+                        "memory or a smaller input";
+    if (want > fit) return std::string(whole) + " (" + std::to_string(want) + " slots wanted, room for " + std::to_string(fit) + ")";
+    if (const int rc = kt_ctr_create(dev_.ctx, ksize_, want, &table_); rc != KT_OK)
+        return rc == KT_ERR_NOMEM ? std::string(whole) + " (" + kt_last_error() + ")" : std::string(kt_last_error());
+    if (getenv("KT_CLI_TIMING")) {
+        uint64_t slots = want;
+        (void)kt_ctr_capacity(table_, &slots);
+        fprintf(stderr, "[timing] unitigs setup: table of %llu slots %.3f s\n", (unsigned long long)slots, setup());
+    }
+    PhaseTimer pt("unitigs");
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    Batch b;
+    Lap lap;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(TWO_TABLE_BATCH_BASES), cli_batch_reads(1ull << 22));
+        pt.t[0] += lap();
+        if (b.n_reads() && !b.bases.empty())
+            if (kt_ctr_add_reads(table_, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST) != KT_OK) return kt_last_error();
+        pt.t[1] += lap();
+        if (!more) break;
+    }
+    if (reader.failed()) return reader.error();
+    // a count-only call, then one call sized by it
+    uint64_t nu = 0, nb = 0;
+    if (kt_ctr_unitigs(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, KT_MEM_HOST) != KT_OK)
+        return kt_last_error();
+    std::vector<uint8_t> bases((size_t)nb);
+    std::vector<uint64_t> offsets((size_t)nu + 1), sums((size_t)nu);
+    std::vector<uint32_t> flags((size_t)nu);
+    if (nu && kt_ctr_unitigs(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(), nu, &nu, &nb,
+                             KT_MEM_HOST) != KT_OK)
+        return kt_last_error();
+    pt.t[1] += lap();
+    const uint64_t overlap = (uint64_t)ksize_ - 1;
+    if (!stats_only_) {
+        const std::string fpath = out_dir_ + "/unitigs.fa";
+        FILE *out = fopen(fpath.c_str(), "wb");
+        if (!out) return "Unable to write to file: " + fpath;
+        std::string s;
+        bool ok = true;
+        for (uint64_t i = 0; i < nu && ok; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            char head[160];
+            const int h = snprintf(head, sizeof head, ">%llu LN:i:%llu KC:i:%llu km:f:%.1f%s\n", (unsigned long long)i,
+                                   (unsigned long long)len, (unsigned long long)sums[i], (double)sums[i] / (double)(len - overlap),
+                                   flags[i] & KT_UNITIG_CIRCULAR ? " CL:i:1" : "");
+            s.append(head, (size_t)h);
+            s.append((const char *)bases.data() + offsets[i], (size_t)len);
+            s += '\n';
+            if (s.size() >= (1u << 22) || i + 1 == nu) {
+                ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+                s.clear();
+            }
+        }
+        if (fclose(out) != 0 || !ok) return "Unable to write to file: " + fpath;
+    }
+    // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
+    std::vector<uint64_t> lens((size_t)nu);
+    uint64_t occ = 0, circular = 0, singletons = 0, longest = 0, n50 = 0;
+    for (uint64_t i = 0; i < nu; i++) {
+        lens[i] = offsets[i + 1] - offsets[i];
+        occ += sums[i];
+        circular += flags[i] & KT_UNITIG_CIRCULAR ? 1 : 0;
+        singletons += lens[i] == overlap + 1;
+        longest = std::max(longest, lens[i]);
+    }
+    std::sort(lens.begin(), lens.end(), std::greater<uint64_t>());
+    for (uint64_t i = 0, run = 0; i < nu; i++) {
+        run += lens[i];
+        if (2 * run >= nb) {
+            n50 = lens[i];
+            break;
+        }
+    }
+    const std::pair<const char *, uint64_t> rows[8] = {{"unitigs", nu},           {"bases", nb},           {"nodes", nb - nu * overlap},
+                                                      {"occurrences", occ},      {"circular", circular},  {"singletons", singletons},
+                                                      {"longest", longest},      {"n50", n50}};
+    std::string s;
+    for (const auto &r : rows) s += std::string(r.first) + '\t' + std::to_string(r.second) + '\n';
+    const std::string spath = out_dir_ + "/unitigs.stats";
+    FILE *out = fopen(spath.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + spath;
+    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
+    pt.t[3] += lap();
+    return "";
+}
+
+// ---------------------------------------------------------------------------------------------
 // minimisers: one C-ABI call per batch; the capacity is a guess that is corrected on the first miss
 static std::string minimiser_batch(kt_ctx *ctx, Work &w, uint64_t wsize, int msize) {
     const uint64_t n = w.b.n_reads();

@@ -386,6 +386,30 @@ class GraphComputer {
     kt_ctr *table_ = nullptr;
 };
 
+// `unitigs`: the maximal unitigs of the de Bruijn graph of an input's counted k-mers (kt_ctr_unitigs): one table, the whole of
+// it on the device, as for `graph`.  Writes {out_dir}/unitigs.fa (">{i} LN:i:{bases} KC:i:{count sum} km:f:{count sum / nodes}"
+// and " CL:i:1" on a cycle, then the sequence on one line; not with stats_only) and {out_dir}/unitigs.stats ("name\tvalue":
+// unitigs, bases, nodes, occurrences, circular, singletons, longest, n50).
+class UnitigComputer {
+  public:
+    UnitigComputer(std::string in_path, std::string out_dir, int ksize);
+    ~UnitigComputer();
+    UnitigComputer(const UnitigComputer &) = delete;
+    UnitigComputer &operator=(const UnitigComputer &) = delete;
+    void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
+    void set_stats_only(bool s) { stats_only_ = s; }
+    void set_device(int d) { dev_.index = d; }
+    std::string unitigs();  // "" or the error message
+
+  private:
+    std::string in_path_, out_dir_;
+    int ksize_;
+    uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
+    bool stats_only_ = false;
+    Device dev_;
+    kt_ctr *table_ = nullptr;
+};
+
 // `sketch`: bottom-s MinHash sketches of the records of an input (kt_sketch_batch), of the whole input (--single: the
 // batches' sketches merged by kt_sketch_merge) and the Mash distances between them (kt_sketch_pairs, a block of rows of the
 // matrix at a time; the formula is kt_mash_distance).  Writes {out_dir}/sketch.tsv ("id\tlength\tkmers\tsize\th0,h1,..."

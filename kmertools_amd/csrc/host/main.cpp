@@ -5,7 +5,7 @@
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
 // and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
 // inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances) and `graph` (de Bruijn adjacency of the counted
-// k-mers).
+// k-mers) and `unitigs` (that graph's maximal unitigs).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -137,6 +137,7 @@ const char *HELP_MAIN =
     "  profile Per-position k-mer counts and per-sequence min / median / mean / max\n"
     "  setop   Intersect, subtract, union or xor the k-mer sets of two inputs\n"
     "  graph   De Bruijn adjacency, unitig ends and node census of the counted k-mers\n"
+    "  unitigs Maximal unitigs of the de Bruijn graph of the counted k-mers\n"
     "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
@@ -875,6 +876,60 @@ int cmd_graph(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_UNITIGS =
+    "Maximal unitigs of the de Bruijn graph of the counted k-mers\n\n"
+    "Counts the canonical k-mers of the input.  A k-mer is a node when min-count <= its count <= max-count; nodes are chained\n"
+    "through the sides at which `graph` reports no unitig end (a k-mer that follows itself, a hairpin and a k-mer that is its\n"
+    "own reverse complement end a chain as well).  Every chain is one unitig of nodes + k - 1 bases: a path is written from its\n"
+    "end with the smaller canonical k-mer, a cycle from its smallest canonical k-mer, once around.  {output}/unitigs.fa holds, in\n"
+    "ascending order of that first k-mer, \">{i} LN:i:{bases} KC:i:{sum of the k-mers' counts} km:f:{that sum / k-mers}\" (and\n"
+    "\" CL:i:1\" on a cycle), then the sequence on one line.  {output}/unitigs.stats holds one \"name<TAB>value\" line each:\n"
+    "unitigs, bases, nodes, occurrences, circular, singletons, longest, n50.  The whole table must fit the device memory, as\n"
+    "for `graph`: unitigs cannot count in several passes, and says so before it writes.\n\n"
+    "Usage: kmertools unitigs [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "      --min-count <N>          Lowest count of a node [default: 1]\n"
+    "      --max-count <N>          Highest count of a node [default: 4294967295]\n"
+    "      --stats-only             Write unitigs.stats only, no unitigs.fa\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_unitigs(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
+                                     {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
+                                     {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work and before the output directory is made
+    const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
+    const uint64_t hi = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (lo > hi)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(lo) + " is greater than " + std::to_string(hi));
+    (void)ranged(f, "memory", 6, 128, false, 6);
+    (void)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+        fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
+        return 101;
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    UnitigComputer uc(in, out, k);
+    uc.set_range((uint32_t)lo, (uint32_t)hi);
+    uc.set_stats_only(f.count("stats-only") != 0);
+    uc.set_device(device);
+    if (std::string e = uc.unitigs(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -1006,5 +1061,6 @@ int main(int argc, char **argv) {
     if (cmd == "sketch") return cmd_sketch(argc, argv, 2);
     if (cmd == "setop") return cmd_setop(argc, argv, 2);
     if (cmd == "graph") return cmd_graph(argc, argv, 2);
+    if (cmd == "unitigs") return cmd_unitigs(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

@@ -1,0 +1,453 @@
+// kt_unitig.hip - the maximal unitigs of a table's de Bruijn graph (kt_ctr_unitigs): the nodes of kt_ctr_graph, sorted, are
+// chained through their joined sides, ranked along their chains by pointer doubling and spelled into one base array.
+//
+// Stages, every one a plain launch over nodes or over ORIENTED STATES (state 2i + e = node i entered through side e, R = 0,
+// L = 1; it leaves through side 1 - e):
+//   a. nodes     kt_ctr_graph(KT_MEM_DEVICE, sorted, counts) into this call's scratch: node index = rank of the key
+//   b. links     link[2i + side] = 2j + facing side of the one neighbour across a joined side (binary search of the sorted
+//                keys), NIL for an unjoined side; a second launch checks that every link is answered (link[link[x]] == x)
+//   c. ranking   (next, dist) per state, a terminal state (its exit side unjoined) points at itself with dist 0;
+//                rounds of next = next[next], dist += dist[next] between two buffers.  The number of rounds is a function of
+//                n computed on the host (ceil(log2 2n) + 1); no launch waits for convergence.  States that do not end at
+//                a terminal after that lie on cycles (counted, one read-back: no cycle, no cycle stages): those get a second
+//                doubling of (smallest state index in the window ahead, distance to it) - the smallest state of a directed
+//                cycle is the one of its smallest node - for ceil(log2 n) rounds.
+//   d. placing   a path node takes the direction whose origin terminal has the smaller index (index order is key order), a
+//                cycle node the direction that meets its smallest node entered from the left; both give (start node,
+//                position, orientation).  Start nodes carry their unitig's length; an exclusive scan of (is start, bases)
+//                over node index numbers the unitigs in start-key order and lays out their bases.
+//   e. spelling  every node writes the last base of its oriented k-mer at offset + position + k - 1, a start node its first
+//                k - 1 bases, the offset and the flags as well; count sums by integer atomics.
+// Anything the rule excludes (a link without an answer, a neighbour that is no node, a chain that is neither a path nor a
+// cycle) raises a bit in the call's error word and comes back as an error: nothing spins.
+#include "kt_device.hpp"
+#include "kt_launch.hpp"
+
+namespace {
+
+using namespace ktl;
+
+constexpr int BLOCK = 256, WAVES = BLOCK / 64;
+constexpr uint32_t NIL = 0xFFFFFFFFu;
+constexpr uint32_t SCAN_ITEMS = 4, SCAN_TILE = BLOCK * SCAN_ITEMS;
+constexpr uint32_t CIRC = 0x80000000u;  // in slen: the unitig is a cycle; in place.y: the node is spelled forward
+constexpr uint32_t ERR_DEGREE = 1u, ERR_SEARCH = 2u, ERR_MUTUAL = 4u, ERR_CHAIN = 8u, ERR_CYCLE = 16u;
+
+// the call's device words, zeroed on the stream before the first kernel
+struct Words {
+    uint32_t err, pad;
+    unsigned long long unresolved, n_unitigs, n_bases;
+};
+
+__device__ __forceinline__ uint64_t pack(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+__device__ __forceinline__ uint32_t lo32(uint64_t v) { return (uint32_t)v; }
+__device__ __forceinline__ uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
+
+// ---- b. links --------------------------------------------------------------------------------------------------------
+
+// one thread per node side
+__global__ __launch_bounds__(BLOCK) void unitig_link_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ info,
+                                                            uint64_t n, uint32_t k, uint32_t *__restrict__ link,
+                                                            Words *__restrict__ w) {
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= 2 * n) return;
+    const uint64_t i = t >> 1;
+    const uint32_t side = (uint32_t)t & 1u;
+    const uint32_t inf = info[i];
+    uint32_t out = NIL;
+    if (!(inf & (0x100u << side))) {
+        const uint32_t bits = (inf >> (4u * side)) & 0xFu;
+        if (__popc(bits) != 1) {
+            atomicOr(&w->err, ERR_DEGREE);
+        } else {
+            const uint64_t x = (uint64_t)(__ffs((int)bits) - 1);
+            const uint32_t top = 2u * k - 2u;
+            const uint64_t mask = (1ull << (2u * k)) - 1ull;
+            const uint64_t F = keys[i], R = ktd::rev_comp(F, (int)k);
+            // right: F[1..k) + x, reverse complement comp(x) + R[0..k-1); left: x + F[0..k-1), R[1..k) + comp(x)
+            const uint64_t s = side == 0u ? ((F << 2) & mask) | x : (F >> 2) | (x << top);
+            const uint64_t rs = side == 0u ? (R >> 2) | ((3ull - x) << top) : ((R << 2) & mask) | (3ull - x);
+            const uint64_t v = s < rs ? s : rs;
+            if (v != F && s != rs && F != R) {
+                uint64_t lo = 0, hi = n;  // the first key >= v
+                while (lo < hi) {
+                    const uint64_t mid = lo + ((hi - lo) >> 1);
+                    if (keys[mid] < v) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < n && keys[lo] == v) out = (uint32_t)(2 * lo) + (s == v ? side ^ 1u : side);
+                else atomicOr(&w->err, ERR_SEARCH);
+            }
+        }
+    }
+    link[t] = out;
+}
+
+// ---- c. ranking ------------------------------------------------------------------------------------------------------
+
+// every link is answered; state s starts at its successor, or at itself when its exit side is unjoined
+__global__ __launch_bounds__(BLOCK) void unitig_rank_init_kernel(const uint32_t *__restrict__ link, uint64_t m,
+                                                                 uint64_t *__restrict__ cur, Words *__restrict__ w) {
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= m) return;
+    const uint32_t l = link[s];
+    if (l != NIL && (l >= m || link[l] != (uint32_t)s)) atomicOr(&w->err, ERR_MUTUAL);
+    const uint32_t x = link[s ^ 1ull];
+    cur[s] = x == NIL || x >= m ? pack((uint32_t)s, 0u) : pack(x, 1u);
+}
+
+__global__ __launch_bounds__(BLOCK) void unitig_rank_jump_kernel(const uint64_t *__restrict__ cur, uint64_t m,
+                                                                 uint64_t *__restrict__ out) {
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= m) return;
+    const uint64_t p = cur[s], q = cur[lo32(p)];
+    out[s] = pack(lo32(q), hi32(p) + hi32(q));
+}
+
+// the state that `res` says s ends at is a terminal
+__device__ __forceinline__ bool resolved(const uint64_t *__restrict__ res, const uint32_t *__restrict__ link, uint64_t s) {
+    return link[lo32(res[s]) ^ 1u] == NIL;
+}
+
+__global__ __launch_bounds__(BLOCK) void unitig_unresolved_kernel(const uint64_t *__restrict__ res, const uint32_t *__restrict__ link,
+                                                                  uint64_t m, Words *__restrict__ w) {
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool open = s < m && !resolved(res, link, s);
+    const uint64_t b = __ballot(open);
+    if (b && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)b) - 1)) atomicAdd(&w->unresolved, (unsigned long long)__popcll(b));
+}
+
+// cycle states: val = (smallest state index among the next `hop` states, this one included) << 32 | distance to it
+__global__ __launch_bounds__(BLOCK) void unitig_cycle_init_kernel(const uint64_t *__restrict__ res, const uint32_t *__restrict__ link,
+                                                                  uint64_t m, uint64_t *__restrict__ val, uint32_t *__restrict__ nxt) {
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= m) return;
+    const bool path = resolved(res, link, s);
+    val[s] = path ? ~0ull : (uint64_t)s << 32;
+    nxt[s] = path ? NIL : link[s ^ 1ull];
+}
+
+__global__ __launch_bounds__(BLOCK) void unitig_cycle_jump_kernel(const uint64_t *__restrict__ val, const uint32_t *__restrict__ nxt,
+                                                                  uint64_t m, uint64_t hop, uint64_t *__restrict__ val_out,
+                                                                  uint32_t *__restrict__ nxt_out) {
+    const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= m) return;
+    const uint32_t a = nxt[s];
+    uint64_t v = val[s];
+    uint32_t b = NIL;
+    if (a != NIL && a < m) {
+        const uint64_t c = val[a] + hop;  // (distance < hop, so the sum stays in the low word)
+        v = c < v ? c : v;
+        b = nxt[a];
+    }
+    val_out[s] = v;
+    nxt_out[s] = b;
+}
+
+// ---- d. placing ------------------------------------------------------------------------------------------------------
+
+// place[i] = (start node, position | forward << 31); slen[i] = the unitig's nodes (| CIRC) at its start node, else 0
+__global__ __launch_bounds__(BLOCK) void unitig_place_kernel(const uint64_t *__restrict__ res, const uint32_t *__restrict__ link,
+                                                             const uint64_t *__restrict__ cval, uint64_t n, uint2 *__restrict__ place,
+                                                             uint32_t *__restrict__ slen, Words *__restrict__ w) {
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t p0 = res[2 * i], p1 = res[2 * i + 1];
+    const bool r0 = link[lo32(p0) ^ 1u] == NIL, r1 = link[lo32(p1) ^ 1u] == NIL;
+    uint32_t start = (uint32_t)i, pos = 0, fwd = 1, len = 1, err = 0;
+    if (r0 && r1) {
+        // state (i, e) runs to terminal a_e in d_e steps; walking the other way, a_e is where direction 1 - e comes from
+        const uint32_t a0 = lo32(p0) >> 1, a1 = lo32(p1) >> 1, d0 = hi32(p0), d1 = hi32(p1);
+        fwd = a0 <= a1;
+        start = fwd ? a0 : a1;
+        pos = fwd ? d0 : d1;
+        len = d0 + d1 + 1u;
+        if (a0 == a1 && len != 1u) err = ERR_CHAIN;
+    } else if (!r0 && !r1 && cval) {
+        const uint64_t v0 = cval[2 * i], v1 = cval[2 * i + 1];
+        const uint32_t m0 = hi32(v0), m1 = hi32(v1);  // the smallest states of the two directed cycles: one node, two entries
+        fwd = m1 & 1u;
+        const uint32_t d = lo32(fwd ? v1 : v0);
+        start = m0 >> 1;
+        const uint32_t after = start < n ? link[2ull * start] : NIL;  // the state behind (start, entered left): c - 1 from it
+        if ((m0 ^ m1) != 1u || after == NIL || after >= 2 * n) {
+            err = ERR_CYCLE;
+            start = (uint32_t)i;
+        } else {
+            len = lo32(cval[after]) + 1u;
+            pos = d ? len - d : 0u;
+            if (d >= len || (hi32(cval[after]) | 1u) != (m0 | 1u)) err = ERR_CYCLE, pos = 0;
+            len |= CIRC;
+        }
+    } else {
+        err = ERR_CHAIN;
+    }
+    if (err) {
+        atomicOr(&w->err, err);
+        start = (uint32_t)i, pos = 0, len = 1;
+    }
+    place[i] = make_uint2(start, pos | (fwd << 31));
+    slen[i] = pos == 0u && start == (uint32_t)i ? len : 0u;
+}
+
+// inclusive prefix sums of a and b over the workgroup's threads; *ta, *tb = the sums
+__device__ __forceinline__ void block_scan2(uint64_t &a, uint64_t &b, uint64_t (*wsum)[2], uint64_t *ta, uint64_t *tb) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t ua = __shfl_up(a, off, 64), ub = __shfl_up(b, off, 64);
+        if (lane >= (uint32_t)off) a += ua, b += ub;
+    }
+    if (lane == 63u) wsum[wave][0] = a, wsum[wave][1] = b;
+    ktd::lds_barrier();
+    uint64_t pa = 0, pb = 0, sa = 0, sb = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < (uint32_t)WAVES; x++) {
+        const uint64_t xa = wsum[x][0], xb = wsum[x][1];
+        if (x < wave) pa += xa, pb += xb;
+        sa += xa, sb += xb;
+    }
+    ktd::lds_barrier();  // (wsum is rewritten by the next call)
+    a += pa, b += pb;
+    *ta = sa, *tb = sb;
+}
+
+// a start node's unitig: 1 unitig, nodes + k - 1 bases
+__device__ __forceinline__ uint64_t bases_of(uint32_t sl, uint32_t k) { return sl ? (uint64_t)(sl & ~CIRC) + k - 1u : 0ull; }
+
+// tile t (SCAN_TILE nodes) -> tiles[2t] = its unitigs, tiles[2t + 1] = its bases
+__global__ __launch_bounds__(BLOCK) void unitig_tile_sum_kernel(const uint32_t *__restrict__ slen, uint64_t n, uint32_t k,
+                                                                uint64_t *__restrict__ tiles) {
+    __shared__ uint64_t wsum[WAVES][2];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+    uint64_t a = 0, b = 0, ta, tb;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
+        const uint32_t sl = base + j < n ? slen[base + j] : 0u;
+        a += sl != 0u;
+        b += bases_of(sl, k);
+    }
+    block_scan2(a, b, wsum, &ta, &tb);
+    if (threadIdx.x == 0) tiles[2ull * blockIdx.x] = ta, tiles[2ull * blockIdx.x + 1] = tb;
+}
+
+// one workgroup: the tiles' sums into their exclusive prefixes, the totals into the call's words
+__global__ __launch_bounds__(BLOCK) void unitig_tile_scan_kernel(uint64_t *__restrict__ tiles, uint64_t T, Words *__restrict__ w) {
+    __shared__ uint64_t wsum[WAVES][2];
+    uint64_t ca = 0, cb = 0;
+    for (uint64_t c0 = 0; c0 < T; c0 += BLOCK) {
+        const uint64_t t = c0 + threadIdx.x;
+        const uint64_t va = t < T ? tiles[2 * t] : 0, vb = t < T ? tiles[2 * t + 1] : 0;
+        uint64_t a = va, b = vb, ta, tb;
+        block_scan2(a, b, wsum, &ta, &tb);
+        if (t < T) tiles[2 * t] = ca + a - va, tiles[2 * t + 1] = cb + b - vb;
+        ca += ta, cb += tb;
+    }
+    if (threadIdx.x == 0) w->n_unitigs = ca, w->n_bases = cb;
+}
+
+// ex_id[i], ex_off[i] = unitigs and bases that start at nodes before i
+__global__ __launch_bounds__(BLOCK) void unitig_scan_apply_kernel(const uint32_t *__restrict__ slen, uint64_t n, uint32_t k,
+                                                                  const uint64_t *__restrict__ tiles, uint32_t *__restrict__ ex_id,
+                                                                  uint64_t *__restrict__ ex_off) {
+    __shared__ uint64_t wsum[WAVES][2];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+    uint32_t sl[SCAN_ITEMS];
+    uint64_t a = 0, b = 0, ta, tb;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
+        sl[j] = base + j < n ? slen[base + j] : 0u;
+        a += sl[j] != 0u;
+        b += bases_of(sl[j], k);
+    }
+    const uint64_t own_a = a, own_b = b;
+    block_scan2(a, b, wsum, &ta, &tb);
+    uint64_t ra = tiles[2ull * blockIdx.x] + a - own_a, rb = tiles[2ull * blockIdx.x + 1] + b - own_b;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
+        if (base + j < n) ex_id[base + j] = (uint32_t)ra, ex_off[base + j] = rb;
+        ra += sl[j] != 0u;
+        rb += bases_of(sl[j], k);
+    }
+}
+
+// ---- e. spelling -----------------------------------------------------------------------------------------------------
+
+struct SpellArgs {
+    const uint64_t *keys;
+    const uint32_t *counts;
+    const uint2 *place;
+    const uint32_t *slen, *ex_id;
+    const uint64_t *ex_off;
+    uint64_t n;
+    uint32_t k;
+    uint8_t *bases;
+    uint64_t *offsets, *count_sums;
+    uint32_t *flags;
+    uint64_t max_bases, max_unitigs;  // (the host launches this only when everything fits: these guard the stores all the same)
+    const Words *w;
+};
+
+__device__ __forceinline__ uint8_t letter(uint64_t code) { return (uint8_t)((0x54474341u >> (8u * (uint32_t)(code & 3ull))) & 0xFFu); }  // "ACGT"
+
+__global__ __launch_bounds__(BLOCK) void unitig_spell_kernel(SpellArgs s) {
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i == 0 && s.w->n_unitigs <= s.max_unitigs) s.offsets[s.w->n_unitigs] = s.w->n_bases;
+    if (i >= s.n) return;
+    const uint2 pl = s.place[i];
+    const uint32_t start = pl.x, pos = pl.y & ~CIRC, k = s.k;
+    const bool fwd = pl.y & CIRC;
+    const uint64_t uid = s.ex_id[start], off = s.ex_off[start];
+    if (uid >= s.max_unitigs) return;
+    const uint64_t F = s.keys[i];
+    // the node's k-mer as the unitig reads it
+    const uint64_t S = fwd ? F : ktd::rev_comp(F, (int)k);
+    const uint64_t at = off + pos + k - 1u;
+    if (at < s.max_bases) s.bases[at] = letter(S);
+    if (s.count_sums) atomicAdd(reinterpret_cast<unsigned long long *>(s.count_sums + uid), (unsigned long long)s.counts[i]);
+    if (start == (uint32_t)i && pos == 0u) {
+        for (uint32_t j = 0; j + 1u < k; j++)
+            if (off + j < s.max_bases) s.bases[off + j] = letter(S >> (2u * (k - 1u - j)));
+        s.offsets[uid] = off;
+        if (s.flags) s.flags[uid] = s.slen[i] & CIRC ? KT_UNITIG_CIRCULAR : 0u;
+    }
+}
+
+uint32_t ceil_log2(uint64_t x) {  // the smallest r with 2^r >= x
+    uint32_t r = 0;
+    while (r < 63u && (1ull << r) < x) r++;
+    return r;
+}
+
+dim3 blocks_for(uint64_t items, uint64_t per_block = BLOCK) { return dim3((uint32_t)((items + per_block - 1) / per_block)); }
+
+size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+}  // namespace
+
+extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
+                              uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
+                              uint64_t *n_bases, int mem) {
+    if (!table || !n_unitigs || !n_bases) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs: null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, mem, "kt_ctr_unitigs");
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (min_count == 0) return call.fail("min_count must be >= 1");
+    if (min_count > max_count) return call.fail("min_count > max_count");
+    if (int rc = call.enter()) return rc;
+    const bool store = max_bases || max_unitigs;
+    if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
+    uint64_t n_t = 0;
+    if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    if (n_t > 0x7FFFFFFEull) return call.fail("a table of more than 2^31 - 2 entries (the oriented node states are u32)");
+    hipStream_t st = ctx->stream;
+    // no node: no unitig, and offsets[0] = 0 where there is room for it
+    auto nothing = [&]() -> int {
+        *n_unitigs = 0, *n_bases = 0;
+        if (!store) return KT_OK;
+        if (call.host()) offsets[0] = 0;
+        else KT_HIP(hipMemsetAsync(offsets, 0, 8, st));
+        return KT_OK;
+    };
+    if (!n_t) return nothing();
+
+    // a. the nodes, ascending by key, in this call's AUX1, with room for every entry of the table: 16 bytes an entry
+    // (kt_ctr_graph's sort takes OUT and AUX0)
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += align16(bytes); return o; };
+    const size_t o_keys = take(n_t * 8), o_info = take(n_t * 4), o_counts = take(n_t * 4);
+    uint8_t *A = nullptr;
+    if (int rc = call.scratch(kt::AUX1, at, &A)) return rc;
+    uint64_t *keys = (uint64_t *)(A + o_keys);
+    uint32_t *info = (uint32_t *)(A + o_info), *counts = (uint32_t *)(A + o_counts);
+    uint64_t n = 0;
+    if (int rc = kt_ctr_graph(table, min_count, max_count, keys, info, counts, n_t, &n, nullptr, KT_MEM_DEVICE, 1)) return rc;
+    if (!n) return nothing();
+    // what the later stages keep per node, in AUX2: 64 bytes a node (the cycle stages: 48 more, in BASES)
+    const uint64_t T_n = (n + SCAN_TILE - 1) / SCAN_TILE;
+    at = 0;
+    const size_t o_words = take(sizeof(Words)), o_link = take(n * 8), o_ra = take(n * 16), o_rb = take(n * 16), o_place = take(n * 8),
+                 o_slen = take(n * 4), o_exid = take(n * 4), o_exoff = take(n * 8), o_tiles = take(T_n * 16);
+    uint8_t *S = nullptr;
+    if (int rc = call.scratch(kt::AUX2, at, &S)) return rc;
+    Words *w = (Words *)(S + o_words);
+    uint64_t *ra = (uint64_t *)(S + o_ra), *rb = (uint64_t *)(S + o_rb), *ex_off = (uint64_t *)(S + o_exoff),
+             *tiles = (uint64_t *)(S + o_tiles);
+    uint32_t *link = (uint32_t *)(S + o_link), *slen = (uint32_t *)(S + o_slen), *ex_id = (uint32_t *)(S + o_exid);
+    uint2 *place = (uint2 *)(S + o_place);
+    const uint64_t m = 2 * n, T = (n + SCAN_TILE - 1) / SCAN_TILE;
+    const uint32_t k = (uint32_t)table->k;
+    KT_HIP(hipMemsetAsync(w, 0, sizeof(Words), st));
+
+    // b. links
+    hipLaunchKernelGGL(unitig_link_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)keys, (const uint32_t *)info, n, k, link, w);
+    // c. ranking: a number of rounds fixed by n
+    hipLaunchKernelGGL(unitig_rank_init_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint32_t *)link, m, ra, w);
+    const uint32_t rounds = ceil_log2(m) + 1u;
+    for (uint32_t r = 0; r < rounds; r++) {
+        hipLaunchKernelGGL(unitig_rank_jump_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)ra, m, rb);
+        uint64_t *t = ra;
+        ra = rb, rb = t;
+    }
+    hipLaunchKernelGGL(unitig_unresolved_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link, m, w);
+    KT_HIP(hipGetLastError());
+    Words h;
+    KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    uint64_t *cval = nullptr;
+    if (h.unresolved && !h.err) {  // cycles: the smallest state of each, and every state's distance to it
+        uint8_t *C = nullptr;
+        if (int rc = call.scratch(kt::BASES, align16(m * 8) * 2 + align16(m * 4) * 2, &C)) return rc;
+        uint64_t *va = (uint64_t *)C, *vb = (uint64_t *)(C + align16(m * 8));
+        uint32_t *na = (uint32_t *)(C + 2 * align16(m * 8)), *nc = (uint32_t *)(C + 2 * align16(m * 8) + align16(m * 4));
+        hipLaunchKernelGGL(unitig_cycle_init_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link, m, va, na);
+        const uint32_t crounds = ceil_log2(n);
+        for (uint32_t r = 0; r < crounds; r++) {
+            hipLaunchKernelGGL(unitig_cycle_jump_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)va, (const uint32_t *)na, m,
+                               1ull << r, vb, nc);
+            uint64_t *tv = va;
+            va = vb, vb = tv;
+            uint32_t *tn = na;
+            na = nc, nc = tn;
+        }
+        cval = va;
+    }
+    // d. placing, ids and offsets
+    hipLaunchKernelGGL(unitig_place_kernel, blocks_for(n), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link,
+                       (const uint64_t *)cval, n, place, slen, w);
+    hipLaunchKernelGGL(unitig_tile_sum_kernel, dim3((uint32_t)T), dim3(BLOCK), 0, st, (const uint32_t *)slen, n, k, tiles);
+    hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), dim3(BLOCK), 0, st, tiles, T, w);
+    hipLaunchKernelGGL(unitig_scan_apply_kernel, dim3((uint32_t)T), dim3(BLOCK), 0, st, (const uint32_t *)slen, n, k,
+                       (const uint64_t *)tiles, ex_id, ex_off);
+    KT_HIP(hipGetLastError());
+    KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    if (h.err)
+        return kt::fail(KT_ERR_HIP, "kt_ctr_unitigs: internal: the nodes' links do not form paths and cycles (error bits " +
+                                        std::to_string(h.err) + ")");
+    *n_unitigs = h.n_unitigs, *n_bases = h.n_bases;
+    if (!store) return KT_OK;
+    if (h.n_unitigs > max_unitigs || h.n_bases > max_bases)
+        return call.fail("max_unitigs or max_bases smaller than the result (*n_unitigs, *n_bases)");
+
+    // e. spelling (host: into OFFSETS = offsets | count sums | flags | bases, copied back by finish())
+    const uint64_t nu = h.n_unitigs;
+    uint8_t *d_bases = bases;
+    uint64_t *d_offsets = offsets, *d_sums = count_sums;
+    uint32_t *d_flags = flags;
+    if (call.host()) {
+        if (int rc = call.scratch(kt::OFFSETS, (nu + 1) * 8 + nu * 8 + align16(nu * 4) + h.n_bases, &d_offsets)) return rc;
+        d_sums = count_sums ? d_offsets + nu + 1 : nullptr;
+        d_flags = flags ? (uint32_t *)(d_offsets + 2 * nu + 1) : nullptr;
+        d_bases = (uint8_t *)(d_offsets + 2 * nu + 1) + align16(nu * 4);
+    }
+    if (d_sums) KT_HIP(hipMemsetAsync(d_sums, 0, nu * 8, st));
+    const SpellArgs sp{keys, counts, place, slen, ex_id, ex_off, n, k, d_bases, d_offsets, d_sums, d_flags, h.n_bases, nu, w};
+    hipLaunchKernelGGL(unitig_spell_kernel, blocks_for(n), dim3(BLOCK), 0, st, sp);
+    KT_HIP(hipGetLastError());
+    call.back(bases, (const uint8_t *)d_bases, h.n_bases);
+    call.back(offsets, (const uint64_t *)d_offsets, nu + 1);
+    call.back(count_sums, (const uint64_t *)d_sums, nu);
+    call.back(flags, (const uint32_t *)d_flags, nu);
+    return call.finish();
+}

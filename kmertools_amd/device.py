@@ -98,6 +98,9 @@ GRAPH_CENSUS_NAMES = ("nodes", "occurrences", "degree_sum", "end_sides", "isolat
     "degree_%d_%d" % (dl, dr) for dl in range(5) for dr in range(5))
 
 
+UNITIG_CIRCULAR = 1  # Counter.unitigs' flag bit (KT_UNITIG_CIRCULAR): the unitig is a cycle, linearised at its smallest k-mer
+
+
 def graph_info_text(info):
     """an info word of Counter.graph as (left4, right4, ends2), `kmertools graph`'s rendering: position x of left4 /
     right4 is "ACGT"[x] when that neighbour is a node, else "."; ends2 is "L" or "." followed by "R" or "." """
@@ -697,6 +700,34 @@ class Counter:
         check(_lib.lib().kt_ctr_graph(self._h, int(min_count), hi, _ptr(keys), _ptr(info), _ptr(counts), int(max_out),
                                       C.byref(n), _ptr(census), KT_MEM_DEVICE, int(bool(sort))))
         return n.value
+
+    def unitigs(self, min_count=1, max_count=None):
+        """The maximal unitigs of the de Bruijn graph of the table's k-mers with min_count <= count <= max_count (None: no
+        upper bound) as numpy (bases u8: ASCII ACGT, concatenated; offsets u64: unitig i = bases[offsets[i]:offsets[i + 1]];
+        count_sums u64: the sum of its k-mers' counts; flags u32: UNITIG_CIRCULAR), ascending by the canonical k-mer of
+        their start node.  A count-only call, then one call sized by it (kt_ctr_unitigs)."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        nu, nb = C.c_uint64(), C.c_uint64()
+        check(_lib.lib().kt_ctr_unitigs(self._h, int(min_count), hi, None, 0, None, None, None, 0, C.byref(nu), C.byref(nb),
+                                        KT_MEM_HOST))
+        bases = np.zeros(nb.value, np.uint8)
+        offsets = np.zeros(nu.value + 1, np.uint64)
+        sums = np.zeros(nu.value, np.uint64)
+        flags = np.zeros(nu.value, np.uint32)
+        if nu.value:
+            check(_lib.lib().kt_ctr_unitigs(self._h, int(min_count), hi, _ptr(bases), nb.value, _ptr(offsets), _ptr(sums),
+                                            _ptr(flags), nu.value, C.byref(nu), C.byref(nb), KT_MEM_HOST))
+        return bases, offsets, sums, flags
+
+    def unitigs_device(self, bases, max_bases, offsets, count_sums, flags, max_unitigs, min_count=1, max_count=None):
+        """unitigs into device tensors (bases u8 of max_bases, offsets u64 bit patterns of max_unitigs + 1, count_sums u64 /
+        flags u32 of max_unitigs or None; None, 0, None, None, None, 0 only counts); returns (n_unitigs, n_bases).  Raises
+        KmertoolsError (KT_ERR_ARG) when either room is too small."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        nu, nb = C.c_uint64(), C.c_uint64()
+        check(_lib.lib().kt_ctr_unitigs(self._h, int(min_count), hi, _ptr(bases), int(max_bases), _ptr(offsets), _ptr(count_sums),
+                                        _ptr(flags), int(max_unitigs), C.byref(nu), C.byref(nb), KT_MEM_DEVICE))
+        return nu.value, nb.value
 
     def export_stage_range(self, min_count=1, max_count=None):
         """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
