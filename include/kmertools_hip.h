@@ -360,6 +360,34 @@ int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_
                    uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
                    uint64_t *n_bases, int mem);
 
+/* Those unitigs and the edges between them: the compacted de Bruijn graph whole (what BCALM / Cuttlefish write as L:
+ * fields, GFA as L lines).  The unitigs are exactly kt_ctr_unitigs's, for the same (min_count, max_count): the same
+ * numbering, the same strings, and bases / offsets / count_sums / flags as that call fills them.
+ * An ORIENTED unitig (u, +) is unitig u's string U; (u, -) is the reverse complement of U.  There is a directed LINK
+ * (u, su) -> (v, sv) exactly when the last k - 1 bases of oriented (u, su) equal the first k - 1 bases of oriented (v, sv);
+ * for k = 1 every pair is linked.  No pair is excluded, u == v included.  The graph is node-centric, so this is the same as:
+ * the first k-mer of (v, sv) is a solid neighbour, on the outward side, of the last k-mer of (u, su).  It follows that
+ *   - every link has its mirror (v, !sv) -> (u, !su); a hairpin (u, +) -> (u, -) is its own mirror;
+ *   - a circular unitig has exactly the two links (u, +) -> (u, +) and (u, -) -> (u, -);
+ *   - a k-mer that follows itself gives (u, +) -> (u, +);
+ *   - a unitig that is its own reverse complement is a single palindromic node (even k only) and is linked under both signs;
+ *   - an end has at most 5 links: one per set neighbour bit of its terminal node's outward nibble and one more where that
+ *     neighbour is such a palindrome (odd k: at most 4).
+ * END e = 2 * u + (su is '-') owns link_to[link_offsets[e] .. link_offsets[e + 1]); each value is 2 * v + (sv is '-'),
+ * ascending within an end (unitig numbers are below 2^31).  link_offsets: 2 * max_unitigs + 1 entries; link_to: max_links.
+ * *n_links = the number of directed links, always exact, as *n_unitigs and *n_bases are.  max_bases == 0 && max_unitigs == 0
+ * && max_links == 0 only counts (the outputs may be NULL).  When any of the three rooms is too small, nothing is written and
+ * the call returns KT_ERR_ARG with all three numbers set.  No nodes: 0 / 0 / 0 and offsets[0] = link_offsets[0] = 0 (unless
+ * the call only counts).  KT_MEM_HOST synchronises; KT_MEM_DEVICE writes on the context's stream and synchronises to learn the
+ * sizes and, after the links are written, that every neighbour stood at an end of its unitig (if not: KT_ERR_HIP).
+ * KT_ERR_ARG: what kt_ctr_unitigs refuses (a room > 0 includes max_links), a null n_links, null link_offsets with any room
+ * > 0, null link_to with max_links > 0, max_links > 0 with max_unitigs == 0.  On every one of these errors the outputs are
+ * untouched.  Device scratch: kt_ctr_unitigs's and 8 bytes per unitig. */
+int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
+                          uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
+                          uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to, uint64_t max_links, uint64_t *n_links,
+                          int mem);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

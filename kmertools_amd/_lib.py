@@ -65,6 +65,8 @@ SYMBOLS = {
     "kt_ctr_setop": (_i, [_vp, _vp, _i, _i, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64), _i, _i]),
     "kt_ctr_graph": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _i, _i]),
     "kt_ctr_unitigs": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _i]),
+    "kt_ctr_unitigs_linked": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _u64,
+                                   C.POINTER(_u64), _i]),
     "kt_cgr_points": (_i, [_vp, _vp, _vp, _u64, C.c_double, _vp, _vp, _i]),
     "kt_minimisers": (_i, [_vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _i]),
     "kt_cov_batch": (_i, [_vp, _vp, _vp, _u64, _u64, _u64, _i, _i, _vp, _i]),

@@ -2182,15 +2182,20 @@ std::string UnitigComputer::unitigs() {
         if (!more) break;
     }
     if (reader.failed()) return reader.error();
-    // a count-only call, then one call sized by it
-    uint64_t nu = 0, nb = 0;
-    if (kt_ctr_unitigs(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, KT_MEM_HOST) != KT_OK)
+    // a count-only call, then one call sized by it; with the links only where a file asks for them
+    const bool linked = gfa_ || fa_links_;
+    uint64_t nu = 0, nb = 0, nl = 0;
+    if ((linked ? kt_ctr_unitigs_linked(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, nullptr,
+                                        nullptr, 0, &nl, KT_MEM_HOST)
+                : kt_ctr_unitigs(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, KT_MEM_HOST)) != KT_OK)
         return kt_last_error();
     std::vector<uint8_t> bases((size_t)nb);
-    std::vector<uint64_t> offsets((size_t)nu + 1), sums((size_t)nu);
-    std::vector<uint32_t> flags((size_t)nu);
-    if (nu && kt_ctr_unitigs(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(), nu, &nu, &nb,
-                             KT_MEM_HOST) != KT_OK)
+    std::vector<uint64_t> offsets((size_t)nu + 1), sums((size_t)nu), loff(linked ? 2 * (size_t)nu + 1 : 0);
+    std::vector<uint32_t> flags((size_t)nu), lto((size_t)nl);
+    if (nu && (linked ? kt_ctr_unitigs_linked(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(),
+                                              nu, &nu, &nb, loff.data(), lto.data(), nl, &nl, KT_MEM_HOST)
+                      : kt_ctr_unitigs(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(), nu,
+                                       &nu, &nb, KT_MEM_HOST)) != KT_OK)
         return kt_last_error();
     pt.t[1] += lap();
     const uint64_t overlap = (uint64_t)ksize_ - 1;
@@ -2203,10 +2208,17 @@ std::string UnitigComputer::unitigs() {
         for (uint64_t i = 0; i < nu && ok; i++) {
             const uint64_t len = offsets[i + 1] - offsets[i];
             char head[160];
-            const int h = snprintf(head, sizeof head, ">%llu LN:i:%llu KC:i:%llu km:f:%.1f%s\n", (unsigned long long)i,
+            const int h = snprintf(head, sizeof head, ">%llu LN:i:%llu KC:i:%llu km:f:%.1f%s", (unsigned long long)i,
                                    (unsigned long long)len, (unsigned long long)sums[i], (double)sums[i] / (double)(len - overlap),
                                    flags[i] & KT_UNITIG_CIRCULAR ? " CL:i:1" : "");
             s.append(head, (size_t)h);
+            if (fa_links_)
+                for (uint64_t e = 2 * i; e < 2 * i + 2; e++)
+                    for (uint64_t j = loff[e]; j < loff[e + 1]; j++) {
+                        const int l = snprintf(head, sizeof head, " L:%c:%u:%c", e & 1 ? '-' : '+', lto[j] >> 1, lto[j] & 1 ? '-' : '+');
+                        s.append(head, (size_t)l);
+                    }
+            s += '\n';
             s.append((const char *)bases.data() + offsets[i], (size_t)len);
             s += '\n';
             if (s.size() >= (1u << 22) || i + 1 == nu) {
@@ -2215,6 +2227,66 @@ std::string UnitigComputer::unitigs() {
             }
         }
         if (fclose(out) != 0 || !ok) return "Unable to write to file: " + fpath;
+    }
+    if (linked) {
+        // of a link e -> f and its mirror (f ^ 1) -> (e ^ 1), the GFA takes the one that is not the larger as (u, su is '-',
+        // v, sv is '-'), which is the order of (e, f) as pairs of numbers; a link that is its own mirror is there once
+        uint64_t edges = 0, dead = 0, isolated = 0, self = 0, max_deg = 0;
+        for (uint64_t e = 0; e < 2 * nu; e++) {
+            const uint64_t d = loff[e + 1] - loff[e];
+            dead += d == 0;
+            isolated += (e & 1) && d == 0 && loff[e] == loff[e - 1];
+            max_deg = std::max(max_deg, d);
+            for (uint64_t j = loff[e]; j < loff[e + 1]; j++) {
+                const uint64_t f = lto[j], me = f ^ 1, mf = e ^ 1;
+                self += (f >> 1) == (e >> 1);
+                edges += e < me || (e == me && f <= mf);
+            }
+        }
+        if (gfa_) {
+            const std::string gpath = out_dir_ + "/unitigs.gfa";
+            FILE *out = fopen(gpath.c_str(), "wb");
+            if (!out) return "Unable to write to file: " + gpath;
+            std::string s = "H\tVN:Z:1.0\n";
+            char line[160];
+            bool ok = true;
+            auto flush = [&](bool last) {
+                if (ok && (last || s.size() >= (1u << 22))) {
+                    ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+                    s.clear();
+                }
+            };
+            for (uint64_t i = 0; i < nu; i++) {
+                const uint64_t len = offsets[i + 1] - offsets[i];
+                s += "S\t" + std::to_string(i) + '\t';
+                s.append((const char *)bases.data() + offsets[i], (size_t)len);
+                const int h = snprintf(line, sizeof line, "\tLN:i:%llu\tKC:i:%llu\tkm:f:%.1f%s\n", (unsigned long long)len,
+                                       (unsigned long long)sums[i], (double)sums[i] / (double)(len - overlap),
+                                       flags[i] & KT_UNITIG_CIRCULAR ? "\tCL:i:1" : "");
+                s.append(line, (size_t)h);
+                flush(false);
+            }
+            for (uint64_t e = 0; e < 2 * nu; e++)
+                for (uint64_t j = loff[e]; j < loff[e + 1]; j++) {
+                    const uint64_t f = lto[j], me = f ^ 1, mf = e ^ 1;
+                    if (!(e < me || (e == me && f <= mf))) continue;
+                    const int h = snprintf(line, sizeof line, "L\t%llu\t%c\t%llu\t%c\t%lluM\n", (unsigned long long)(e >> 1),
+                                           e & 1 ? '-' : '+', (unsigned long long)(f >> 1), f & 1 ? '-' : '+', (unsigned long long)overlap);
+                    s.append(line, (size_t)h);
+                    flush(false);
+                }
+            flush(true);
+            if (fclose(out) != 0 || !ok) return "Unable to write to file: " + gpath;
+        }
+        const std::pair<const char *, uint64_t> rows[6] = {{"links", nl},          {"edges", edges},     {"dead_ends", dead},
+                                                          {"isolated", isolated}, {"self_links", self}, {"max_end_degree", max_deg}};
+        std::string s;
+        for (const auto &r : rows) s += std::string(r.first) + '\t' + std::to_string(r.second) + '\n';
+        const std::string lpath = out_dir_ + "/unitigs.links.stats";
+        FILE *out = fopen(lpath.c_str(), "wb");
+        if (!out) return "Unable to write to file: " + lpath;
+        const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
+        if (fclose(out) != 0 || !ok) return "Unable to write to file: " + lpath;
     }
     // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
     std::vector<uint64_t> lens((size_t)nu);

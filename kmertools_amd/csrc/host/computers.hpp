@@ -389,7 +389,11 @@ class GraphComputer {
 // `unitigs`: the maximal unitigs of the de Bruijn graph of an input's counted k-mers (kt_ctr_unitigs): one table, the whole of
 // it on the device, as for `graph`.  Writes {out_dir}/unitigs.fa (">{i} LN:i:{bases} KC:i:{count sum} km:f:{count sum / nodes}"
 // and " CL:i:1" on a cycle, then the sequence on one line; not with stats_only) and {out_dir}/unitigs.stats ("name\tvalue":
-// unitigs, bases, nodes, occurrences, circular, singletons, longest, n50).
+// unitigs, bases, nodes, occurrences, circular, singletons, longest, n50).  With set_links (kt_ctr_unitigs_linked instead):
+// gfa writes {out_dir}/unitigs.gfa ("H\tVN:Z:1.0", "S\t{i}\t{seq}\tLN:i:\tKC:i:\tkm:f:" and "\tCL:i:1" on a cycle,
+// "L\t{u}\t{su}\t{v}\t{sv}\t{k-1}M" for every link that is not larger than its mirror as (u, su is '-', v, sv is '-')), fa_links
+// appends " L:{su}:{v}:{sv}" per directed link to the header lines of unitigs.fa; either one writes
+// {out_dir}/unitigs.links.stats (links, edges, dead_ends, isolated, self_links, max_end_degree).
 class UnitigComputer {
   public:
     UnitigComputer(std::string in_path, std::string out_dir, int ksize);
@@ -398,6 +402,7 @@ class UnitigComputer {
     UnitigComputer &operator=(const UnitigComputer &) = delete;
     void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
     void set_stats_only(bool s) { stats_only_ = s; }
+    void set_links(bool gfa, bool fa_links) { gfa_ = gfa, fa_links_ = fa_links; }
     void set_device(int d) { dev_.index = d; }
     std::string unitigs();  // "" or the error message
 
@@ -405,7 +410,7 @@ class UnitigComputer {
     std::string in_path_, out_dir_;
     int ksize_;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
-    bool stats_only_ = false;
+    bool stats_only_ = false, gfa_ = false, fa_links_ = false;
     Device dev_;
     kt_ctr *table_ = nullptr;
 };

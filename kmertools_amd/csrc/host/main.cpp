@@ -886,6 +886,13 @@ const char *HELP_UNITIGS =
     "\" CL:i:1\" on a cycle), then the sequence on one line.  {output}/unitigs.stats holds one \"name<TAB>value\" line each:\n"
     "unitigs, bases, nodes, occurrences, circular, singletons, longest, n50.  The whole table must fit the device memory, as\n"
     "for `graph`: unitigs cannot count in several passes, and says so before it writes.\n\n"
+    "The edges of the compacted graph: unitig u read as written is (u, +), its reverse complement (u, -); (u, su) links to\n"
+    "(v, sv) when the last k - 1 bases of the one are the first k - 1 of the other (u = v included; every link has a mirror\n"
+    "(v, !sv) -> (u, !su)).  --links appends \" L:{su}:{v}:{sv}\" for every link of the unitig to its header line in unitigs.fa\n"
+    "(BCALM's form).  --gfa writes {output}/unitigs.gfa: \"H<TAB>VN:Z:1.0\", one\n"
+    "\"S<TAB>{i}<TAB>{sequence}<TAB>LN:i:<TAB>KC:i:<TAB>km:f:\" line per unitig (and \"<TAB>CL:i:1\" on a cycle) and one\n"
+    "\"L<TAB>{u}<TAB>{su}<TAB>{v}<TAB>{sv}<TAB>{k-1}M\" line per link, a link and its mirror written once.  Either flag also\n"
+    "writes {output}/unitigs.links.stats: links, edges (L lines), dead_ends, isolated, self_links, max_end_degree.\n\n"
     "Usage: kmertools unitigs [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
     "Options:\n"
     "  -i, --input <INPUT>          Input file path\n"
@@ -894,6 +901,8 @@ const char *HELP_UNITIGS =
     "      --min-count <N>          Lowest count of a node [default: 1]\n"
     "      --max-count <N>          Highest count of a node [default: 4294967295]\n"
     "      --stats-only             Write unitigs.stats only, no unitigs.fa\n"
+    "      --gfa                    Also write unitigs.gfa (S and L lines) and unitigs.links.stats\n"
+    "      --links                  Append L:{su}:{v}:{sv} fields to the header lines of unitigs.fa; also unitigs.links.stats\n"
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
@@ -902,7 +911,7 @@ const char *HELP_UNITIGS =
 int cmd_unitigs(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
-                                     {0, "device", true}};
+                                     {0, "device", true},      {0, "gfa", false},          {0, "links", false}};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -914,12 +923,16 @@ int cmd_unitigs(int argc, char **argv, int from) {
     (void)ranged(f, "memory", 6, 128, false, 6);
     (void)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const bool gfa = f.count("gfa") != 0, links = f.count("links") != 0;
+    if (f.count("stats-only") && gfa) usage_error("the argument '--stats-only' cannot be used with '--gfa'");
+    if (f.count("stats-only") && links) usage_error("the argument '--stats-only' cannot be used with '--links'");
     if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
     UnitigComputer uc(in, out, k);
+    uc.set_links(gfa, links);
     uc.set_range((uint32_t)lo, (uint32_t)hi);
     uc.set_stats_only(f.count("stats-only") != 0);
     uc.set_device(device);

@@ -18,6 +18,14 @@
 //                over node index numbers the unitigs in start-key order and lays out their bases.
 //   e. spelling  every node writes the last base of its oriented k-mer at offset + position + k - 1, a start node its first
 //                k - 1 bases, the offset and the flags as well; count sums by integer atomics.
+// kt_ctr_unitigs_linked adds the edges of the compacted graph (only then: kt_ctr_unitigs launches and claims what it did):
+//   f. degrees   one thread per node side; a side that is a unitig end (position 0: the - end, position len - 1: the + end,
+//                outward side from the orientation bit) counts the set bits of its outward nibble, one more where a
+//                neighbour string is its own reverse complement; a cycle's start node 1 per end.  deg[2 * unitig + end],
+//                an exclusive scan of it (the same tile sums / one workgroup / apply) = link_offsets and the total.
+//   g. emit      the same threads: every neighbour's index by stage b's search, its place and its unitig's length give
+//                (v, sv); the neighbour has to be first (+) or last (-) in a unitig that is no cycle, else ERR_LINK; the at
+//                most 5 values, sorted in registers, go to the end's offset.
 // Anything the rule excludes (a link without an answer, a neighbour that is no node, a chain that is neither a path nor a
 // cycle) raises a bit in the call's error word and comes back as an error: nothing spins.
 #include "kt_device.hpp"
@@ -31,7 +39,7 @@ constexpr int BLOCK = 256, WAVES = BLOCK / 64;
 constexpr uint32_t NIL = 0xFFFFFFFFu;
 constexpr uint32_t SCAN_ITEMS = 4, SCAN_TILE = BLOCK * SCAN_ITEMS;
 constexpr uint32_t CIRC = 0x80000000u;  // in slen: the unitig is a cycle; in place.y: the node is spelled forward
-constexpr uint32_t ERR_DEGREE = 1u, ERR_SEARCH = 2u, ERR_MUTUAL = 4u, ERR_CHAIN = 8u, ERR_CYCLE = 16u;
+constexpr uint32_t ERR_DEGREE = 1u, ERR_SEARCH = 2u, ERR_MUTUAL = 4u, ERR_CHAIN = 8u, ERR_CYCLE = 16u, ERR_LINK = 32u;
 
 // the call's device words, zeroed on the stream before the first kernel
 struct Words {
@@ -42,6 +50,26 @@ struct Words {
 __device__ __forceinline__ uint64_t pack(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 __device__ __forceinline__ uint32_t lo32(uint64_t v) { return (uint32_t)v; }
 __device__ __forceinline__ uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
+
+// the index of the first of the n ascending keys that is >= v
+__device__ __forceinline__ uint64_t first_key_not_below(const uint64_t *__restrict__ keys, uint64_t n, uint64_t v) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the neighbour string of F (reverse complement R) through `side` with base x: right F[1..k) + x, reverse complement
+// comp(x) + R[0..k-1); left x + F[0..k-1), reverse complement R[1..k) + comp(x)
+__device__ __forceinline__ void neighbour(uint64_t F, uint64_t R, uint32_t side, uint64_t x, uint32_t k, uint64_t *s, uint64_t *rs) {
+    const uint32_t top = 2u * k - 2u;
+    const uint64_t mask = (1ull << (2u * k)) - 1ull;
+    *s = side == 0u ? ((F << 2) & mask) | x : (F >> 2) | (x << top);
+    *rs = side == 0u ? (R >> 2) | ((3ull - x) << top) : ((R << 2) & mask) | (3ull - x);
+}
 
 // ---- b. links --------------------------------------------------------------------------------------------------------
 
@@ -61,20 +89,12 @@ __global__ __launch_bounds__(BLOCK) void unitig_link_kernel(const uint64_t *__re
             atomicOr(&w->err, ERR_DEGREE);
         } else {
             const uint64_t x = (uint64_t)(__ffs((int)bits) - 1);
-            const uint32_t top = 2u * k - 2u;
-            const uint64_t mask = (1ull << (2u * k)) - 1ull;
             const uint64_t F = keys[i], R = ktd::rev_comp(F, (int)k);
-            // right: F[1..k) + x, reverse complement comp(x) + R[0..k-1); left: x + F[0..k-1), R[1..k) + comp(x)
-            const uint64_t s = side == 0u ? ((F << 2) & mask) | x : (F >> 2) | (x << top);
-            const uint64_t rs = side == 0u ? (R >> 2) | ((3ull - x) << top) : ((R << 2) & mask) | (3ull - x);
+            uint64_t s, rs;
+            neighbour(F, R, side, x, k, &s, &rs);
             const uint64_t v = s < rs ? s : rs;
             if (v != F && s != rs && F != R) {
-                uint64_t lo = 0, hi = n;  // the first key >= v
-                while (lo < hi) {
-                    const uint64_t mid = lo + ((hi - lo) >> 1);
-                    if (keys[mid] < v) lo = mid + 1;
-                    else hi = mid;
-                }
+                const uint64_t lo = first_key_not_below(keys, n, v);
                 if (lo < n && keys[lo] == v) out = (uint32_t)(2 * lo) + (s == v ? side ^ 1u : side);
                 else atomicOr(&w->err, ERR_SEARCH);
             }
@@ -231,8 +251,10 @@ __global__ __launch_bounds__(BLOCK) void unitig_tile_sum_kernel(const uint32_t *
     if (threadIdx.x == 0) tiles[2ull * blockIdx.x] = ta, tiles[2ull * blockIdx.x + 1] = tb;
 }
 
-// one workgroup: the tiles' sums into their exclusive prefixes, the totals into the call's words
-__global__ __launch_bounds__(BLOCK) void unitig_tile_scan_kernel(uint64_t *__restrict__ tiles, uint64_t T, Words *__restrict__ w) {
+// one workgroup: the tiles' sums into their exclusive prefixes, the totals into *sum_a and *sum_b
+__global__ __launch_bounds__(BLOCK) void unitig_tile_scan_kernel(uint64_t *__restrict__ tiles, uint64_t T,
+                                                                 unsigned long long *__restrict__ sum_a,
+                                                                 unsigned long long *__restrict__ sum_b) {
     __shared__ uint64_t wsum[WAVES][2];
     uint64_t ca = 0, cb = 0;
     for (uint64_t c0 = 0; c0 < T; c0 += BLOCK) {
@@ -243,7 +265,7 @@ __global__ __launch_bounds__(BLOCK) void unitig_tile_scan_kernel(uint64_t *__res
         if (t < T) tiles[2 * t] = ca + a - va, tiles[2 * t + 1] = cb + b - vb;
         ca += ta, cb += tb;
     }
-    if (threadIdx.x == 0) w->n_unitigs = ca, w->n_bases = cb;
+    if (threadIdx.x == 0) *sum_a = ca, *sum_b = cb;
 }
 
 // ex_id[i], ex_off[i] = unitigs and bases that start at nodes before i
@@ -313,6 +335,139 @@ __global__ __launch_bounds__(BLOCK) void unitig_spell_kernel(SpellArgs s) {
     }
 }
 
+// ---- f, g. the links between unitig ends -----------------------------------------------------------------------------
+
+// the call's link words (in the link scratch: Words stays what kt_ctr_unitigs reads back)
+struct LinkWords {
+    unsigned long long n_links, unused;
+};
+
+struct LinkArgs {
+    const uint64_t *keys;
+    const uint32_t *info;
+    const uint2 *place;
+    const uint32_t *slen, *ex_id;
+    uint64_t n, n_ends;  // n_ends = 2 * unitigs
+    uint32_t k;
+    uint32_t *deg;                 // f: deg[end]
+    const uint64_t *link_offsets;  // g: where each end's links start, n_ends + 1 entries
+    uint32_t *link_to;
+    uint64_t max_links;  // (the host launches g only when everything fits: this guards the stores all the same)
+    Words *w;
+};
+
+// puts v into the ascending a[0..5) (unused places hold NIL) - fixed indices only, so that a[] stays in registers
+__device__ __forceinline__ void insert5(uint32_t (&a)[5], uint32_t v) {
+#pragma unroll
+    for (int t = 0; t < 5; t++) {
+        const uint32_t lo = v < a[t] ? v : a[t];
+        v = v < a[t] ? a[t] : v;
+        a[t] = lo;
+    }
+}
+
+// Thread t = side t & 1 of node t >> 1.  The side is the outward side of a unitig end when the node is first in its unitig
+// (the - end: the string read backwards leaves through it) or last (the + end); a cycle has no such side, and its two
+// closing links are given by its start node.  EMIT false: deg[2 * unitig + end] = the end's links.  EMIT true: the links.
+template <bool EMIT>
+__device__ __forceinline__ void unitig_end_links(const LinkArgs &a) {
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= 2 * a.n) return;
+    const uint64_t i = t >> 1;
+    const uint32_t side = (uint32_t)t & 1u, k = a.k;
+    const uint2 pl = a.place[i];
+    const uint32_t start = pl.x, pos = pl.y & ~CIRC, fwd = pl.y >> 31;
+    const uint32_t sl = a.slen[start], len = sl & ~CIRC;
+    // forward node: its right side ends the + string, its left side the - string; spelled backwards: the other way round
+    const uint32_t end = sl & CIRC ? side : (uint32_t)(side == fwd);
+    if (sl & CIRC ? start != (uint32_t)i : pos != (end ? 0u : len - 1u)) return;
+    const uint64_t e = 2ull * a.ex_id[start] + end;
+    if (e >= a.n_ends) return;
+    uint32_t val[5] = {NIL, NIL, NIL, NIL, NIL};
+    uint32_t cnt = 0, err = 0;
+    if (sl & CIRC) {  // (u, +) -> (u, +) and (u, -) -> (u, -): the last k - 1 bases repeat the first
+        cnt = 1;
+        val[0] = (uint32_t)e;
+    } else {
+        const uint32_t bits = (a.info[i] >> (4u * side)) & 0xFu;
+        const uint64_t F = a.keys[i], R = ktd::rev_comp(F, (int)k);
+#pragma unroll
+        for (uint32_t x = 0; x < 4u; x++) {
+            if (!(bits >> x & 1u)) continue;
+            uint64_t s, rs;
+            neighbour(F, R, side, (uint64_t)x, k, &s, &rs);
+            const bool twice = s == rs;  // its own reverse complement: a single node that begins both of its orientations
+            cnt += twice ? 2u : 1u;
+            if (!EMIT) continue;
+            const uint64_t v = s < rs ? s : rs;
+            const uint64_t j = first_key_not_below(a.keys, a.n, v);
+            if (j >= a.n || a.keys[j] != v) {
+                err |= ERR_SEARCH;
+                continue;
+            }
+            const uint2 pj = a.place[j];
+            const uint32_t sj = a.slen[pj.x], lenj = sj & ~CIRC, posj = pj.y & ~CIRC;
+            const uint32_t to = 2u * a.ex_id[pj.x];
+            // the end's string goes on as s through the right side, as rs through the left: the neighbour reads that way in
+            // (v, +) when it is spelled as it is met, and then has to come first; else in (v, -), where it has to come last
+            const bool plus = ((side == 0u ? s : rs) == v) == (bool)(pj.y >> 31);
+            if ((sj & CIRC) || posj != (plus ? 0u : lenj - 1u) || (twice && lenj != 1u)) err |= ERR_LINK;
+            if (twice) insert5(val, to), insert5(val, to + 1u);
+            else insert5(val, to + (plus ? 0u : 1u));
+        }
+    }
+    if (!EMIT) {
+        a.deg[e] = cnt;
+        return;
+    }
+    if (err) atomicOr(&a.w->err, err);
+    const uint64_t at = a.link_offsets[e];
+    if (cnt > 5u || at + cnt > a.max_links) return;
+#pragma unroll
+    for (uint32_t c = 0; c < 5u; c++)
+        if (c < cnt) a.link_to[at + c] = val[c];
+}
+
+__global__ __launch_bounds__(BLOCK) void unitig_end_degree_kernel(LinkArgs a) { unitig_end_links<false>(a); }
+__global__ __launch_bounds__(BLOCK) void unitig_end_emit_kernel(LinkArgs a) { unitig_end_links<true>(a); }
+
+// tile t (SCAN_TILE ends) -> tiles[2t] = its links (tiles[2t + 1] = 0: the tile scan is stage d's)
+__global__ __launch_bounds__(BLOCK) void unitig_end_tile_sum_kernel(const uint32_t *__restrict__ deg, uint64_t n_ends,
+                                                                    uint64_t *__restrict__ tiles) {
+    __shared__ uint64_t wsum[WAVES][2];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+    uint64_t a = 0, b = 0, ta, tb;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) a += base + j < n_ends ? deg[base + j] : 0u;
+    block_scan2(a, b, wsum, &ta, &tb);
+    if (threadIdx.x == 0) tiles[2ull * blockIdx.x] = ta, tiles[2ull * blockIdx.x + 1] = tb;
+}
+
+// link_offsets[e] = the links of the ends before e; link_offsets[n_ends] = all of them
+__global__ __launch_bounds__(BLOCK) void unitig_end_scan_apply_kernel(const uint32_t *__restrict__ deg, uint64_t n_ends,
+                                                                      const uint64_t *__restrict__ tiles,
+                                                                      const LinkWords *__restrict__ lw,
+                                                                      uint64_t *__restrict__ link_offsets) {
+    __shared__ uint64_t wsum[WAVES][2];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+    uint32_t d[SCAN_ITEMS];
+    uint64_t a = 0, b = 0, ta, tb;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
+        d[j] = base + j < n_ends ? deg[base + j] : 0u;
+        a += d[j];
+    }
+    const uint64_t own = a;
+    block_scan2(a, b, wsum, &ta, &tb);
+    uint64_t r = tiles[2ull * blockIdx.x] + a - own;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
+        if (base + j < n_ends) link_offsets[base + j] = r;
+        r += d[j];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) link_offsets[n_ends] = lw->n_links;
+}
+
 uint32_t ceil_log2(uint64_t x) {  // the smallest r with 2^r >= x
     uint32_t r = 0;
     while (r < 63u && (1ull << r) < x) r++;
@@ -323,30 +478,34 @@ dim3 blocks_for(uint64_t items, uint64_t per_block = BLOCK) { return dim3((uint3
 
 size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
-}  // namespace
-
-extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
-                              uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
-                              uint64_t *n_bases, int mem) {
-    if (!table || !n_unitigs || !n_bases) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs: null");
+// both entry points; n_links null: kt_ctr_unitigs, which has no link outputs and runs no link stage
+int unitigs_body(const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
+                 uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
+                 uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to, uint64_t max_links, uint64_t *n_links, int mem) {
+    const bool linked = n_links != nullptr;
     kt_ctx *ctx = table->ctx;
-    Call call(ctx, mem, "kt_ctr_unitigs");
+    Call call(ctx, mem, name);
     if (int rc = call.refuse_shard(table)) return rc;
     if (min_count == 0) return call.fail("min_count must be >= 1");
     if (min_count > max_count) return call.fail("min_count > max_count");
     if (int rc = call.enter()) return rc;
-    const bool store = max_bases || max_unitigs;
+    const bool store = max_bases || max_unitigs || max_links;
     if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
+    if (linked && ((store && !link_offsets) || (max_links && !link_to))) return call.fail("null link output");
+    if (max_links && !max_unitigs) return call.fail("max_links > 0 with max_unitigs == 0");
     uint64_t n_t = 0;
     if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
     if (n_t > 0x7FFFFFFEull) return call.fail("a table of more than 2^31 - 2 entries (the oriented node states are u32)");
     hipStream_t st = ctx->stream;
-    // no node: no unitig, and offsets[0] = 0 where there is room for it
+    // no node: no unitig and no link, and offsets[0] = link_offsets[0] = 0 where there is room for them
     auto nothing = [&]() -> int {
         *n_unitigs = 0, *n_bases = 0;
+        if (linked) *n_links = 0;
         if (!store) return KT_OK;
         if (call.host()) offsets[0] = 0;
         else KT_HIP(hipMemsetAsync(offsets, 0, 8, st));
+        if (linked && call.host()) link_offsets[0] = 0;
+        else if (linked) KT_HIP(hipMemsetAsync(link_offsets, 0, 8, st));
         return KT_OK;
     };
     if (!n_t) return nothing();
@@ -416,30 +575,59 @@ extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_co
     hipLaunchKernelGGL(unitig_place_kernel, blocks_for(n), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link,
                        (const uint64_t *)cval, n, place, slen, w);
     hipLaunchKernelGGL(unitig_tile_sum_kernel, dim3((uint32_t)T), dim3(BLOCK), 0, st, (const uint32_t *)slen, n, k, tiles);
-    hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), dim3(BLOCK), 0, st, tiles, T, w);
+    hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), dim3(BLOCK), 0, st, tiles, T, &w->n_unitigs, &w->n_bases);
     hipLaunchKernelGGL(unitig_scan_apply_kernel, dim3((uint32_t)T), dim3(BLOCK), 0, st, (const uint32_t *)slen, n, k,
                        (const uint64_t *)tiles, ex_id, ex_off);
     KT_HIP(hipGetLastError());
     KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
     if (h.err)
-        return kt::fail(KT_ERR_HIP, "kt_ctr_unitigs: internal: the nodes' links do not form paths and cycles (error bits " +
+        return kt::fail(KT_ERR_HIP, std::string(name) + ": internal: the nodes' links do not form paths and cycles (error bits " +
                                         std::to_string(h.err) + ")");
+    const uint64_t nu = h.n_unitigs;
+    // f. the ends' degrees and their sum, in AUX0 (the graph's sort has given it back): 8 bytes a unitig
+    const uint64_t n_ends = 2 * nu, T_e = (n_ends + SCAN_TILE - 1) / SCAN_TILE;
+    LinkArgs la{keys, info, place, slen, ex_id, n, n_ends, k, nullptr, nullptr, nullptr, 0, w};
+    uint64_t *ltiles = nullptr;
+    LinkWords *lw = nullptr;
+    LinkWords hl{0, 0};
+    if (linked) {
+        at = 0;
+        const size_t o_lw = take(sizeof(LinkWords)), o_deg = take(n_ends * 4), o_lt = take(T_e * 16);
+        uint8_t *D = nullptr;
+        if (int rc = call.scratch(kt::AUX0, at, &D)) return rc;
+        lw = (LinkWords *)(D + o_lw), la.deg = (uint32_t *)(D + o_deg), ltiles = (uint64_t *)(D + o_lt);
+        KT_HIP(hipMemsetAsync(D, 0, o_lt, st));
+        hipLaunchKernelGGL(unitig_end_degree_kernel, blocks_for(m), dim3(BLOCK), 0, st, la);
+        hipLaunchKernelGGL(unitig_end_tile_sum_kernel, dim3((uint32_t)T_e), dim3(BLOCK), 0, st, (const uint32_t *)la.deg, n_ends, ltiles);
+        hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), dim3(BLOCK), 0, st, ltiles, T_e, &lw->n_links, &lw->unused);
+        KT_HIP(hipGetLastError());
+        KT_HIP(hipMemcpyAsync(&hl, lw, sizeof(LinkWords), hipMemcpyDeviceToHost, st));
+        KT_HIP(hipStreamSynchronize(st));
+        *n_links = hl.n_links;
+    }
     *n_unitigs = h.n_unitigs, *n_bases = h.n_bases;
     if (!store) return KT_OK;
+    if (linked && (h.n_unitigs > max_unitigs || h.n_bases > max_bases || hl.n_links > max_links))
+        return call.fail("max_unitigs, max_bases or max_links smaller than the result (*n_unitigs, *n_bases, *n_links)");
     if (h.n_unitigs > max_unitigs || h.n_bases > max_bases)
         return call.fail("max_unitigs or max_bases smaller than the result (*n_unitigs, *n_bases)");
 
-    // e. spelling (host: into OFFSETS = offsets | count sums | flags | bases, copied back by finish())
-    const uint64_t nu = h.n_unitigs;
+    // e. spelling (host: into OFFSETS = offsets | count sums | flags | bases | link offsets | links, copied back by finish())
     uint8_t *d_bases = bases;
     uint64_t *d_offsets = offsets, *d_sums = count_sums;
     uint32_t *d_flags = flags;
+    uint64_t *d_loff = link_offsets;
+    uint32_t *d_lto = link_to;
     if (call.host()) {
-        if (int rc = call.scratch(kt::OFFSETS, (nu + 1) * 8 + nu * 8 + align16(nu * 4) + h.n_bases, &d_offsets)) return rc;
+        const size_t unlinked = (nu + 1) * 8 + nu * 8 + align16(nu * 4) + h.n_bases;
+        const size_t all = linked ? align16(unlinked) + (n_ends + 1) * 8 + hl.n_links * 4 : unlinked;
+        if (int rc = call.scratch(kt::OFFSETS, all, &d_offsets)) return rc;
         d_sums = count_sums ? d_offsets + nu + 1 : nullptr;
         d_flags = flags ? (uint32_t *)(d_offsets + 2 * nu + 1) : nullptr;
         d_bases = (uint8_t *)(d_offsets + 2 * nu + 1) + align16(nu * 4);
+        d_loff = (uint64_t *)((uint8_t *)d_offsets + align16(unlinked));
+        d_lto = (uint32_t *)(d_loff + n_ends + 1);
     }
     if (d_sums) KT_HIP(hipMemsetAsync(d_sums, 0, nu * 8, st));
     const SpellArgs sp{keys, counts, place, slen, ex_id, ex_off, n, k, d_bases, d_offsets, d_sums, d_flags, h.n_bases, nu, w};
@@ -449,5 +637,40 @@ extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_co
     call.back(offsets, (const uint64_t *)d_offsets, nu + 1);
     call.back(count_sums, (const uint64_t *)d_sums, nu);
     call.back(flags, (const uint32_t *)d_flags, nu);
+    if (linked) {
+        // g. the offsets from the degrees, then the links; the one thing left to learn is whether every neighbour stood
+        // where the rule puts it
+        la.link_offsets = d_loff, la.link_to = d_lto, la.max_links = hl.n_links;
+        hipLaunchKernelGGL(unitig_end_scan_apply_kernel, dim3((uint32_t)T_e), dim3(BLOCK), 0, st, (const uint32_t *)la.deg, n_ends,
+                           (const uint64_t *)ltiles, (const LinkWords *)lw, d_loff);
+        if (hl.n_links) hipLaunchKernelGGL(unitig_end_emit_kernel, blocks_for(m), dim3(BLOCK), 0, st, la);
+        KT_HIP(hipGetLastError());
+        KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
+        KT_HIP(hipStreamSynchronize(st));
+        if (h.err)
+            return kt::fail(KT_ERR_HIP, std::string(name) + ": internal: a unitig end's neighbour is not at an end of its own "
+                                                            "unitig (error bits " + std::to_string(h.err) + ")");
+        call.back(link_offsets, (const uint64_t *)d_loff, n_ends + 1);
+        call.back(link_to, (const uint32_t *)d_lto, hl.n_links);
+    }
     return call.finish();
+}
+
+}  // namespace
+
+extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
+                              uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
+                              uint64_t *n_bases, int mem) {
+    if (!table || !n_unitigs || !n_bases) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs: null");
+    return unitigs_body("kt_ctr_unitigs", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags, max_unitigs,
+                        n_unitigs, n_bases, nullptr, nullptr, 0, nullptr, mem);
+}
+
+extern "C" int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
+                                     uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs,
+                                     uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to,
+                                     uint64_t max_links, uint64_t *n_links, int mem) {
+    if (!table || !n_unitigs || !n_bases || !n_links) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs_linked: null");
+    return unitigs_body("kt_ctr_unitigs_linked", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags,
+                        max_unitigs, n_unitigs, n_bases, link_offsets, link_to, max_links, n_links, mem);
 }

@@ -729,6 +729,39 @@ class Counter:
                                         _ptr(flags), int(max_unitigs), C.byref(nu), C.byref(nb), KT_MEM_DEVICE))
         return nu.value, nb.value
 
+    def unitig_links(self, min_count=1, max_count=None):
+        """unitigs() and the links between the unitigs' ends (kt_ctr_unitigs_linked): returns (bases, offsets, count_sums,
+        flags, link_offsets u64, link_to u32).  End e = 2 * u + (the sign is '-') of unitig u owns
+        link_to[link_offsets[e]:link_offsets[e + 1]]; each value is 2 * v + (the sign is '-'), ascending: the end's last
+        k - 1 bases are the first k - 1 of that oriented unitig.  A count-only call, then one call sized by it."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        nu, nb, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(_lib.lib().kt_ctr_unitigs_linked(self._h, int(min_count), hi, None, 0, None, None, None, 0, C.byref(nu), C.byref(nb),
+                                               None, None, 0, C.byref(nl), KT_MEM_HOST))
+        bases = np.zeros(nb.value, np.uint8)
+        offsets = np.zeros(nu.value + 1, np.uint64)
+        sums = np.zeros(nu.value, np.uint64)
+        flags = np.zeros(nu.value, np.uint32)
+        link_offsets = np.zeros(2 * nu.value + 1, np.uint64)
+        link_to = np.zeros(nl.value, np.uint32)
+        if nu.value:
+            check(_lib.lib().kt_ctr_unitigs_linked(self._h, int(min_count), hi, _ptr(bases), nb.value, _ptr(offsets), _ptr(sums),
+                                                   _ptr(flags), nu.value, C.byref(nu), C.byref(nb), _ptr(link_offsets),
+                                                   _ptr(link_to), nl.value, C.byref(nl), KT_MEM_HOST))
+        return bases, offsets, sums, flags, link_offsets, link_to
+
+    def unitigs_linked_device(self, bases, max_bases, offsets, count_sums, flags, max_unitigs, link_offsets, link_to, max_links,
+                              min_count=1, max_count=None):
+        """unitigs_device with the links: link_offsets (u64 bit patterns of 2 * max_unitigs + 1) and link_to (u32 bit patterns
+        of max_links) are device tensors as well (None, 0, None, None, None, 0, None, None, 0 only counts); returns
+        (n_unitigs, n_bases, n_links).  Raises KmertoolsError (KT_ERR_ARG) when any room is too small."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        nu, nb, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(_lib.lib().kt_ctr_unitigs_linked(self._h, int(min_count), hi, _ptr(bases), int(max_bases), _ptr(offsets),
+                                               _ptr(count_sums), _ptr(flags), int(max_unitigs), C.byref(nu), C.byref(nb),
+                                               _ptr(link_offsets), _ptr(link_to), int(max_links), C.byref(nl), KT_MEM_DEVICE))
+        return nu.value, nb.value, nl.value
+
     def export_stage_range(self, min_count=1, max_count=None):
         """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
         n = C.c_uint64()
