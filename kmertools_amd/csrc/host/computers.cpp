@@ -302,10 +302,12 @@ class AsyncWriter {
 
 // Batch limits can be lowered from the environment (KT_CLI_BATCH_READS / KT_CLI_BATCH_BASES): the tests use it to
 // push a small file through many batches (the rotating work items, the ordered writer, several table adds).
-static uint64_t env_cap(const char *name, uint64_t v) {
-    const char *e = getenv(name);
-    if (!e || !*e) return v;
-    const uint64_t c = strtoull(e, nullptr, 10);
+static uint64_t env_u64_host(const char *name, uint64_t dflt) {  // unset or empty: dflt; "0" is a value
+    const char *v = getenv(name);
+    return v && *v ? strtoull(v, nullptr, 10) : dflt;
+}
+static uint64_t env_cap(const char *name, uint64_t v) {  // lowers v only: unset, empty, 0 and anything above v leave it
+    const uint64_t c = env_u64_host(name, 0);
     return c && c < v ? c : v;
 }
 static uint64_t cli_batch_reads(uint64_t v) { return env_cap("KT_CLI_BATCH_READS", v); }
@@ -369,6 +371,104 @@ static uint64_t batch_bases(uint64_t memory) {
 }
 
 static const uint8_t *bases_ptr(const Batch &b) { return b.bases.empty() ? (const uint8_t *)"" : b.bases.data(); }
+
+// ---- what the table commands share: small text files, the input walk, values kept across passes ------------------
+// a whole small file from a string: "" or the error message
+static std::string write_text_file(const std::string &path, const std::string &text) {
+    FILE *out = fopen(path.c_str(), "wb");
+    if (!out) return "Unable to write to file: " + path;
+    const bool ok = fwrite(text.data(), 1, text.size(), out) == text.size();
+    return fclose(out) == 0 && ok ? "" : "Unable to write to file: " + path;
+}
+
+// "name\tvalue\n" lines (the *.stats files)
+static void append_stats_rows(std::string &s, const char *const *names, const uint64_t *values, size_t n) {
+    for (size_t j = 0; j < n; j++) s += std::string(names[j]) + '\t' + std::to_string(values[j]) + '\n';
+}
+
+// one FASTA / FASTQ record: header line, `len` bases on one line, for FASTQ "+" and `len` quality bytes
+static void append_record(std::string &out, bool fastq, const std::string &header, const uint8_t *bases, const uint8_t *quals,
+                          uint64_t len) {
+    out += fastq ? '@' : '>';
+    out += header;
+    out += '\n';
+    out.append((const char *)bases, len);
+    out += '\n';
+    if (fastq) {
+        out += "+\n";
+        out.append((const char *)quals, len);
+        out += '\n';
+    }
+}
+
+// a k-mer as its letters (counter/src/lib.rs:221-226) or as its number
+static void append_kmer(std::string &s, uint64_t key, int k, bool acgt) {
+    char buf[40];
+    if (acgt) {
+        kt_numeric_to_kmer(key, k, buf);
+        s += buf;
+    } else {
+        const auto r = std::to_chars(buf, buf + sizeof buf, key);
+        s.append(buf, (size_t)(r.ptr - buf));
+    }
+}
+
+static void append_uint(std::string &out, uint64_t v) {
+    char buf[24];
+    const auto e = std::to_chars(buf, buf + sizeof buf, v);
+    out.append(buf, (size_t)(e.ptr - buf));
+}
+
+// The input walk of every command that does not go through run_pipeline: batches of at most max_bases / max_reads
+// (lowered by KT_CLI_BATCH_*, here and nowhere else) until the reader has no more, fn(b, at) for every batch with reads -
+// `at`: the reads and bases in front of the batch -, nothing more after the first error, the reader's or fn's.  The
+// reader and the batch are the caller's: whether they live across passes (count, compare, setop: one of each, rewound) or
+// per pass (the pass hooks) is the caller's choice, and so is what fn does with a batch without bases.  pt / lap: the
+// time of next_batch is booked as read time; fn books its own.  *end: the whole input's reads and bases.
+template <class F>
+static std::string walk(SeqReader &reader, Batch &b, uint64_t max_bases, uint64_t max_reads, bool keep_records, PhaseTimer *pt,
+                        Lap *lap, Cursor *end, F fn) {
+    max_bases = cli_batch_bases(max_bases);
+    max_reads = cli_batch_reads(max_reads);
+    Cursor at;
+    for (;;) {
+        const bool more = reader.next_batch(b, max_bases, max_reads, false, keep_records);
+        if (pt) pt->t[0] += (*lap)();
+        if (const uint64_t n = b.n_reads()) {
+            if (std::string e = fn(b, at); !e.empty()) return e;
+            at.reads += n;
+            at.bases += b.offsets[n];
+        }
+        if (!more) break;
+    }
+    if (reader.failed()) return reader.error();
+    if (end) *end = at;
+    return "";
+}
+static const uint64_t TABLE_BATCH_BASES = 256ull << 20;  // of every walk; the table plan's reserve is a multiple of it
+
+std::string KeptAcrossPasses::inside(const Cursor &at, const Batch &b) const {
+    const uint64_t n = b.n_reads();
+    return at.reads + n > seen.reads || at.bases + b.offsets[n] > seen.bases ? changed() : "";
+}
+
+std::string KeptAcrossPasses::finish(bool first, const Cursor &end) {
+    if (first) seen = end;
+    else if (end.reads != seen.reads || end.bases != seen.bases) return changed();
+    return "";
+}
+
+std::string KeptAcrossPasses::over_ceiling(uint64_t bases, unsigned bytes_per_base, const char *what, uint32_t passes,
+                                           double ceil_gb) const {
+    const double bytes = (double)bases * (double)bytes_per_base;
+    if (!(bytes > ceil_gb * (double)(1ull << 30))) return "";
+    char msg[320];
+    snprintf(msg, sizeof msg,
+             "%s: the table takes %u passes, and the %s of the input kept across them (%u bytes per base, more than %.1f GB) do "
+             "not fit the memory ceiling of %.0f GB: raise -m or split the input",
+             cmd, passes, what, bytes_per_base, bytes / (double)(1ull << 30), ceil_gb);
+    return msg;
+}
 
 // writes `rows` (n x bins) as delimited text: {:.6} when normalised, Display otherwise
 static void emit_matrix(AsyncWriter &writer, const Work &w, uint64_t bins, bool norm, const std::string &delim, int threads,
@@ -747,17 +847,9 @@ class TableWriter {
     std::string emit(FILE *out, const uint64_t *keys, const uint32_t *counts, uint64_t m) {
         // "{kmer}\t{count}\n" (or the ACGT form), counter/src/lib.rs:220-230
         format_rows(m, threads_, acgt_ ? (size_t)k_ + 13 : 32, pieces_, [&](uint64_t i, std::string &s) {
-            char buf[40];
-            if (acgt_) {
-                kt_numeric_to_kmer(keys[i], k_, buf);  // counter/src/lib.rs:221-226
-                s += buf;
-            } else {
-                const auto rr = std::to_chars(buf, buf + sizeof buf, keys[i]);
-                s.append(buf, (size_t)(rr.ptr - buf));
-            }
+            append_kmer(s, keys[i], k_, acgt_);
             s += '\t';
-            const auto r2 = std::to_chars(buf, buf + sizeof buf, counts[i]);
-            s.append(buf, (size_t)(r2.ptr - buf));
+            append_uint(s, counts[i]);
             s += '\n';
         });
         const uint64_t h = heap_in_use_kb();  // with a slab's pairs and its text in hand: the writer's high point
@@ -784,9 +876,6 @@ std::string CountComputer::add_spectrum(kt_ctr *t) {
 
 // {out_dir}/kmers.histo: "c\tn" for c = 1..H, zeros included, the last line the k-mers with H or more occurrences
 std::string CountComputer::write_histo() const {
-    const std::string path = out_dir_ + "/kmers.histo";
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + path;
     std::string s;
     for (uint32_t c = 1; c <= histo_max_; c++) {
         s += std::to_string(c);
@@ -794,72 +883,119 @@ std::string CountComputer::write_histo() const {
         s += std::to_string(c < histo_.size() ? histo_[c] : 0);
         s += '\n';
     }
-    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-    return fclose(out) == 0 && ok ? "" : "Unable to write to file: " + path;
+    return write_text_file(out_dir_ + "/kmers.histo", s);
 }
 
-static uint64_t env_u64_host(const char *name, uint64_t dflt) {
-    const char *v = getenv(name);
-    return v && *v ? strtoull(v, nullptr, 10) : dflt;
+// ---- the table plan ----------------------------------------------------------------------------------------------
+// What an input can hold: an upper bound of its bases - a plain file gives one without being read: its size (FASTA), or
+// half of it (FASTQ: as many quality bytes as bases); compressed input takes the pre-pass, which counts the records too -,
+// of its distinct k-mers (at most the canonical k-mers of k <= 15), and the slots wanted for them: 1.9 per possible key =
+// load factor ~0.5 at worst (the library rounds up to m * 2^j, m in 5..8)
+struct InputBound {
+    uint64_t n_seq = 0, bases = 0, max_distinct = 0, want = 0;  // n_seq: 0 when the pre-pass was skipped
+};
+static std::string slots_wanted(const std::string &path, int k, InputBound *in) {
+    std::string err;
+    struct stat st;
+    const bool plain = !(path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) && stat(path.c_str(), &st) == 0 &&
+                       S_ISREG(st.st_mode);
+    in->n_seq = 0;
+    if (plain) in->bases = format_from_path(path) == SeqFormat::Fastq ? (uint64_t)st.st_size / 2 : (uint64_t)st.st_size;
+    else if (!SeqReader::seq_stats(path, in->n_seq, in->bases, err)) return err;
+    in->max_distinct = in->bases;
+    if (k <= 15) {
+        const uint64_t n4k = 1ull << (2 * k);
+        const uint64_t canon = (k & 1) ? n4k / 2 : (n4k + (1ull << k)) / 2;
+        if (canon < in->max_distinct) in->max_distinct = canon;
+    }
+    in->want = in->max_distinct + in->max_distinct / 10 * 9;
+    if (in->want < 1024) in->want = 1024;
+    return "";
+}
+
+// How many passes the tables of a command take.  The reference bounds its memory with -m: chunks of the input, partitions
+// spilled to disk, merged partition by partition (counter/src/lib.rs:114-118, 151-167, 188-231).  Here the bound is the
+// HBM next to the build's buffers (two key arrays + the staging of a batch: the reserve), `bytes_per_slot` for every slot
+// of every table; tables that cannot hold every distinct k-mer are filled in `passes` passes over the input, pass p
+// counting hash partition p only (kt_ctr_add_reads_part).  KT_CTR_MAX_SLOTS (tests: force the passes) comes in one of two
+// ways, which the commands' tests rely on: for `ctr` it REPLACES the fit - a value above what the HBM holds is taken and
+// left to create_tables -; for the others it bounds every single table next to the fit (default: no bound).
+struct TablePlan {
+    int n = 1;                   // tables, on one device
+    uint64_t want[2] = {0, 0};
+    uint64_t room = 0;           // slots a pass may hold (of one table, where KT_CTR_MAX_SLOTS bounds that more tightly)
+    uint32_t passes = 1;
+    // a partition's share of the keys varies a little: 1 / passes + 5 sigma of room
+    uint64_t capacity(int i) const { return passes == 1 ? want[i] : want[i] / passes + want[i] / passes / 16 + 4096; }
+    void plan(kt_ctx *ctx, uint64_t bytes_per_slot, bool env_replaces_fit) {
+        uint64_t sum = 0;
+        for (int i = 0; i < n; i++) sum += want[i];
+        uint64_t free_b = 0, total_b = 0, fit = sum, each = ~0ull;
+        if (kt_device_memory(ctx, &free_b, &total_b) == KT_OK) {
+            const uint64_t reserve = TABLE_BATCH_BASES * 20 + (1ull << 30);
+            const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
+            fit = usable / 10 * 9 / bytes_per_slot;
+        }
+        if (env_replaces_fit) fit = env_u64_host("KT_CTR_MAX_SLOTS", fit);
+        else each = env_u64_host("KT_CTR_MAX_SLOTS", ~0ull);
+        if (fit < 1024 * (uint64_t)n) fit = 1024 * (uint64_t)n;
+        if (each < 1024) each = 1024;
+        uint64_t p = (sum + fit - 1) / fit;
+        for (int i = 0; i < n; i++) p = std::max(p, (want[i] + each - 1) / each);
+        passes = (uint32_t)std::max<uint64_t>(p, 1);
+        room = std::min(fit, each);
+    }
+};
+
+// The plan's tables, created.  The library rounds a request up (to m * 2^j, at most 1.25x), so tables sized to the edge of
+// the free HBM may not fit after all: more passes then, with none of the tables left in between.
+static std::string create_tables(kt_ctx *ctx, int k, TablePlan &plan, kt_ctr **const *tables) {
+    for (;; plan.passes++) {
+        int rc = KT_OK;
+        for (int i = 0; i < plan.n && rc == KT_OK; i++) rc = kt_ctr_create(ctx, k, plan.capacity(i), tables[i]);
+        if (rc == KT_OK) return "";
+        for (int i = 0; i < plan.n; i++) {
+            if (*tables[i]) kt_ctr_destroy(*tables[i]);
+            *tables[i] = nullptr;
+        }
+        if (rc != KT_ERR_NOMEM || plan.passes >= 4096) return kt_last_error();
+    }
+}
+
+// One walk over an input into a table: add(b) is the library's call (kt_ctr_add_reads, kt_ctr_add_reads_part); a batch
+// whose reads have no bases is not passed on.
+template <class Add>
+static std::string fill_table(SeqReader &reader, Batch &b, PhaseTimer &pt, Lap &lap, Add add) {
+    return walk(reader, b, TABLE_BATCH_BASES, 1ull << 22, false, &pt, &lap, nullptr, [&](const Batch &bb, const Cursor &) -> std::string {
+        if (!bb.bases.empty() && add(bb) != KT_OK) return kt_last_error();
+        pt.t[1] += lap();
+        return "";
+    });
 }
 
 std::string CountComputer::count() {
     // init(): pre-pass for record count and total length (counter/src/lib.rs:236-249); here it
     // sizes the HBM table instead of the reference's partition count
-    std::string err;
     Lap setup;
     if (in_path_ == "-") return "ctr reads its input more than once and cannot take stdin";  // (the reference panics
                                                                                             // on SeqFormat::get("-"))
-    // An upper bound of the number of bases is all the sizing needs.  A plain file gives one without being read:
-    // its size (FASTA), or half of it (FASTQ: as many quality bytes as bases).  Compressed input keeps the pre-pass.
-    struct stat st;
-    const bool plain = !(in_path_.size() > 3 && in_path_.compare(in_path_.size() - 3, 3, ".gz") == 0) &&
-                       stat(in_path_.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-    if (plain) {
-        seq_count_ = 0;
-        total_length_ = format_from_path(in_path_) == SeqFormat::Fastq ? (uint64_t)st.st_size / 2 : (uint64_t)st.st_size;
-    } else if (!SeqReader::seq_stats(in_path_, seq_count_, total_length_, err)) {
-        return err;
-    }
+    InputBound in;
+    if (std::string e = slots_wanted(in_path_, ksize_, &in); !e.empty()) return e;
+    seq_count_ = in.n_seq;
+    total_length_ = in.bases;
     const double t_stats = setup();
-    uint64_t max_distinct = total_length_;
-    if (ksize_ <= 15) {
-        const uint64_t n4k = 1ull << (2 * ksize_);
-        const uint64_t canon = (ksize_ & 1) ? n4k / 2 : (n4k + (1ull << ksize_)) / 2;
-        if (canon < max_distinct) max_distinct = canon;
-    }
-    if (n_devices_ > 1) return count_sharded(max_distinct);
+    if (n_devices_ > 1) return count_sharded(in.max_distinct);
     if (std::string e = dev_.ensure(); !e.empty()) return e;
     const double t_dev = setup();
-    // 1.9 slots per possible key = load factor ~0.5 at worst (the library rounds up to m * 2^j, m in 5..8)
-    uint64_t want = max_distinct + max_distinct / 10 * 9;
-    if (want < 1024) want = 1024;
-    // The reference bounds its memory with -m: chunks of the input, partitions spilled to disk, merged partition by
-    // partition (counter/src/lib.rs:114-118, 151-167, 188-231).  Here the bound is the HBM next to the build's
-    // buffers; a table that cannot hold every distinct k-mer is filled in `passes` passes over the input, pass p
-    // counting hash partition p only (kt_ctr_add_reads_part), each pass's table written out and cleared.
-    const uint64_t batch_bases = 256ull << 20;
-    uint64_t free_b = 0, total_b = 0, fit = want;
-    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
-        const uint64_t reserve = batch_bases * 20 + (1ull << 30);  // two key arrays + staging of a batch
-        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
-        fit = usable / 10 * 9 / 16;
-    }
-    fit = env_u64_host("KT_CTR_MAX_SLOTS", fit);  // (tests: force the out-of-core passes)
-    if (fit < 1024) fit = 1024;
-    passes_ = (uint32_t)((want + fit - 1) / fit);
-    if (passes_ < 1) passes_ = 1;
-    // a partition's share of the keys varies a little: 1 / passes + 5 sigma of room.  The library rounds the request up
-    // (to m * 2^j, at most 1.25x), so a table sized to the edge of the free HBM may not fit after all: more passes then.
-    uint64_t cap = 0;
-    for (;; passes_++) {
-        cap = passes_ == 1 ? want : want / passes_ + want / passes_ / 16 + 4096;
-        const int rc = kt_ctr_create(dev_.ctx, ksize_, cap, &ctr_);
-        if (rc == KT_OK) break;
-        if (rc != KT_ERR_NOMEM || passes_ >= 4096) return kt_last_error();
-    }
+    // one table, 16 bytes a slot; each pass's table is written out and cleared
+    TablePlan plan;
+    plan.want[0] = in.want;
+    plan.plan(dev_.ctx, 16, true);
+    kt_ctr **const tables[1] = {&ctr_};
+    if (std::string e = create_tables(dev_.ctx, ksize_, plan, tables); !e.empty()) return e;
+    passes_ = plan.passes;
     if (getenv("KT_CLI_TIMING")) {
-        uint64_t slots = cap;
+        uint64_t slots = plan.capacity(0);
         (void)kt_ctr_capacity(ctr_, &slots);
         fprintf(stderr, "[timing] ctr setup: sizing (pre-pass only for compressed input) %.3f s, device init %.3f s, table of %llu slots, %u pass(es) %.3f s\n",
                 t_stats, t_dev, (unsigned long long)slots, passes_, setup());
@@ -880,17 +1016,11 @@ std::string CountComputer::count() {
     for (uint32_t pass = 0; pass < passes_; pass++) {
         if (pass && !reader.rewind()) return reader.error();
         Lap lap;
-        for (;;) {
-            const bool more = reader.next_batch(b, cli_batch_bases(batch_bases), cli_batch_reads(1ull << 22));
-            pt.t[0] += lap();
-            if (b.n_reads() && !b.bases.empty()) {
-                if (kt_ctr_add_reads_part(ctr_, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST, passes_, pass) != KT_OK)
-                    return kt_last_error();
-            }
-            pt.t[1] += lap();
-            if (!more) break;
-        }
-        if (reader.failed()) return reader.error();
+        if (std::string e = fill_table(reader, b, pt, lap, [&](const Batch &bb) {
+                return kt_ctr_add_reads_part(ctr_, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST, passes_, pass);
+            });
+            !e.empty())
+            return e;
         if (passes_ == 1) break;  // the table stays resident: merge() (and cov) read it
         // out of core: this partition is complete - whoever needs to look k-mers up does it now (cov) -
         if (pass_hook_)
@@ -1146,30 +1276,24 @@ CovComputer::~CovComputer() { delete ctr_; }
 std::string CovComputer::cov_pass(uint32_t pass, uint32_t passes, kt_ctr *table) {
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    Batch b;
-    uint64_t at = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(bin_count_ >= 2048 ? 8192 : 1ull << 19));
+    Batch batch;
+    Cursor end;
+    const std::string e = walk(reader, batch, TABLE_BATCH_BASES, bin_count_ >= 2048 ? 8192 : 1ull << 19, false, nullptr, nullptr, &end,
+                               [&](const Batch &b, const Cursor &at) -> std::string {
         const uint64_t n = b.n_reads();
-        if (n) {
-            if (pass == 0) acc_rows_.resize((at + n) * bin_count_, 0u);
-            else if ((at + n) * bin_count_ > acc_rows_.size()) return "cov: the input changed between the passes";
-            if (kt_cov_batch_part(table, bases_ptr(b), b.offsets.data(), n, bin_size_, bin_count_, acc_rows_.data() + at * bin_count_,
-                                  KT_MEM_HOST, passes, pass) != KT_OK)
-                return kt_last_error();
-            at += n;
-        }
-        if (!more) break;
-    }
-    if (reader.failed()) return reader.error();
-    acc_reads_ = at;
-    return "";
+        if (std::string c = kept_.claim(pass == 0, acc_rows_, (at.reads + n) * bin_count_, 0u); !c.empty()) return c;
+        if (kt_cov_batch_part(table, bases_ptr(b), b.offsets.data(), n, bin_size_, bin_count_, acc_rows_.data() + at.reads * bin_count_,
+                              KT_MEM_HOST, passes, pass) != KT_OK)
+            return kt_last_error();
+        return "";
+    });
+    return e.empty() ? kept_.finish(pass == 0, end) : e;
 }
 
 std::string CovComputer::build_table() {
     delete ctr_;
     acc_rows_.clear();
-    acc_reads_ = 0;
+    kept_.seen = Cursor();
     ctr_ = new CountComputer(in_path_kmer_, out_dir_, ksize_);
     ctr_->set_threads(threads_);
     ctr_->set_max_memory(memory_ceil_gb_);
@@ -1192,10 +1316,10 @@ std::string CovComputer::compute_coverages() {
         PhaseTimer pt("cov (rows summed over the passes)");
         AsyncWriter writer(out, pt);
         std::vector<std::string> pieces;
-        const uint64_t bins = bin_count_, slab = bins >= 2048 ? 8192 : 1ull << 19;
+        const uint64_t bins = bin_count_, slab = bins >= 2048 ? 8192 : 1ull << 19, acc_reads = kept_.seen.reads;
         Work w;
-        for (uint64_t r0 = 0; r0 < acc_reads_; r0 += slab) {
-            const uint64_t n = acc_reads_ - r0 < slab ? acc_reads_ - r0 : slab;
+        for (uint64_t r0 = 0; r0 < acc_reads; r0 += slab) {
+            const uint64_t n = acc_reads - r0 < slab ? acc_reads - r0 : slab;
             w.b.clear();
             w.b.offsets.assign(n + 1, 0);  // (emit_matrix only needs the number of reads)
             w.resize_rows(n * bins);
@@ -1315,29 +1439,21 @@ static constexpr uint32_t NO_WEAK = 0xFFFFFFFFu;  // first_weak of a read withou
 std::string FilterComputer::filter_pass(uint32_t pass, uint32_t passes, kt_ctr *table) {
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    Batch b;
-    uint64_t at = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20));
-        const uint64_t n = b.n_reads();
-        if (n) {
-            if (pass == 0) {
-                acc_n_.resize(at + n, 0u);
-                acc_s_.resize(at + n, 0u);
-                if (trim_) acc_w_.resize(at + n, NO_WEAK);
-            } else if (at + n > acc_n_.size()) {
-                return "filter: the input changed between the passes";
-            }
-            if (kt_ctr_read_solidity(table, bases_ptr(b), b.offsets.data(), n, min_count_, max_count_, acc_n_.data() + at,
-                                     acc_s_.data() + at, trim_ ? acc_w_.data() + at : nullptr, KT_MEM_HOST, passes, pass) != KT_OK)
-                return kt_last_error();
-            at += n;
-        }
-        if (!more) break;
-    }
-    if (reader.failed()) return reader.error();
-    acc_reads_ = at;
-    return "";
+    Batch batch;
+    Cursor end;
+    const std::string e = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, false, nullptr, nullptr, &end,
+                               [&](const Batch &b, const Cursor &at) -> std::string {
+        const uint64_t n = b.n_reads(), to = at.reads + n;
+        std::string c = kept_.claim(pass == 0, acc_n_, to, 0u);
+        if (c.empty()) c = kept_.claim(pass == 0, acc_s_, to, 0u);
+        if (c.empty() && trim_) c = kept_.claim(pass == 0, acc_w_, to, NO_WEAK);
+        if (!c.empty()) return c;
+        if (kt_ctr_read_solidity(table, bases_ptr(b), b.offsets.data(), n, min_count_, max_count_, acc_n_.data() + at.reads,
+                                 acc_s_.data() + at.reads, trim_ ? acc_w_.data() + at.reads : nullptr, KT_MEM_HOST, passes, pass) != KT_OK)
+            return kt_last_error();
+        return "";
+    });
+    return e.empty() ? kept_.finish(pass == 0, end) : e;
 }
 
 void FilterComputer::emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const {
@@ -1352,17 +1468,21 @@ void FilterComputer::emit(const Batch &b, const uint32_t *n, const uint32_t *s, 
         } else if (!((double)s[i] >= min_solid_ * (double)n[i])) {
             continue;
         }
-        out += fastq ? '@' : '>';
-        out += b.headers[i];
-        out += '\n';
-        out.append((const char *)b.bases.data() + o, keep);
-        out += '\n';
-        if (fastq) {
-            out += "+\n";
-            out.append((const char *)b.quals.data() + o, keep);
-            out += '\n';
-        }
+        append_record(out, fastq, b.headers[i], b.bases.data() + o, fastq ? b.quals.data() + o : nullptr, keep);
     }
+}
+
+// the table a read-level command looks its k-mers up in: counted as by `ctr`, no kmers.histo and no kmers.counts, `hook`
+// for every complete pass of an out-of-core count
+static CountComputer *make_lookup_counter(const std::string &in, int k, int threads, double memory_ceil_gb, int device,
+                                          std::function<std::string(uint32_t, uint32_t, kt_ctr *)> hook) {
+    CountComputer *c = new CountComputer(in, ".", k);
+    c->set_threads(threads);
+    c->set_max_memory(memory_ceil_gb);
+    c->set_device(device);
+    c->set_histo(0, true);
+    c->set_pass_hook(std::move(hook));
+    return c;
 }
 
 std::string FilterComputer::filter() {
@@ -1370,13 +1490,9 @@ std::string FilterComputer::filter() {
     acc_n_.clear();
     acc_s_.clear();
     acc_w_.clear();
-    acc_reads_ = 0;
-    ctr_ = new CountComputer(in_path_kmer_, ".", ksize_);
-    ctr_->set_threads(threads_);
-    ctr_->set_max_memory(memory_ceil_gb_);
-    ctr_->set_device(device_);
-    ctr_->set_histo(0, true);  // no kmers.histo and no kmers.counts: the table is only looked up
-    ctr_->set_pass_hook([this](uint32_t pass, uint32_t passes, kt_ctr *t) { return filter_pass(pass, passes, t); });
+    kept_.seen = Cursor();
+    ctr_ = make_lookup_counter(in_path_kmer_, ksize_, threads_, memory_ceil_gb_, device_,
+                               [this](uint32_t pass, uint32_t passes, kt_ctr *t) { return filter_pass(pass, passes, t); });
     if (std::string e = ctr_->count(); !e.empty()) return e;
     const bool resident = ctr_->passes() == 1;  // else: the numbers were combined pass by pass (filter_pass)
     if (resident && !ctr_->table()) return "filter: no table";
@@ -1387,48 +1503,34 @@ std::string FilterComputer::filter() {
     if (!out) return "Unable to write to file: " + out_path_;
     PhaseTimer pt("filter");
     Lap lap;
-    Batch b;
-    std::string text, err;
+    Batch batch;
+    std::string text;
     std::vector<uint32_t> nk, ns, fw;
-    uint64_t at = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
-        pt.t[0] += lap();
+    Cursor end;
+    std::string err = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, true, &pt, &lap, &end, [&](const Batch &b, const Cursor &at) -> std::string {
         const uint64_t n = b.n_reads();
-        if (n) {
-            const uint32_t *pn, *ps, *pw;
-            if (resident) {
-                nk.assign(n, 0u);
-                ns.assign(n, 0u);
-                fw.assign(trim_ ? n : 0, NO_WEAK);
-                if (kt_ctr_read_solidity(ctr_->table(), bases_ptr(b), b.offsets.data(), n, min_count_, max_count_, nk.data(),
-                                         ns.data(), trim_ ? fw.data() : nullptr, KT_MEM_HOST, 1, 0) != KT_OK) {
-                    err = kt_last_error();
-                    break;
-                }
-                pn = nk.data(), ps = ns.data(), pw = fw.data();
-            } else {
-                if (at + n > acc_reads_) {
-                    err = "filter: the input changed between the passes";
-                    break;
-                }
-                pn = acc_n_.data() + at, ps = acc_s_.data() + at, pw = trim_ ? acc_w_.data() + at : nullptr;
-            }
-            pt.t[1] += lap();
-            text.clear();
-            emit(b, pn, ps, pw, fastq, text);
-            pt.t[2] += lap();
-            if (fwrite(text.data(), 1, text.size(), out) != text.size()) {
-                err = "Unable to write to file: " + out_path_;
-                break;
-            }
-            pt.t[3] += lap();
-            at += n;
+        const uint32_t *pn, *ps, *pw;
+        if (resident) {
+            nk.assign(n, 0u);
+            ns.assign(n, 0u);
+            fw.assign(trim_ ? n : 0, NO_WEAK);
+            if (kt_ctr_read_solidity(ctr_->table(), bases_ptr(b), b.offsets.data(), n, min_count_, max_count_, nk.data(), ns.data(),
+                                     trim_ ? fw.data() : nullptr, KT_MEM_HOST, 1, 0) != KT_OK)
+                return kt_last_error();
+            pn = nk.data(), ps = ns.data(), pw = fw.data();
+        } else {
+            if (std::string c = kept_.inside(at, b); !c.empty()) return c;
+            pn = acc_n_.data() + at.reads, ps = acc_s_.data() + at.reads, pw = trim_ ? acc_w_.data() + at.reads : nullptr;
         }
-        if (!more) break;
-    }
-    if (err.empty() && reader.failed()) err = reader.error();
-    if (err.empty() && !resident && at != acc_reads_) err = "filter: the input changed between the passes";
+        pt.t[1] += lap();
+        text.clear();
+        emit(b, pn, ps, pw, fastq, text);
+        pt.t[2] += lap();
+        if (fwrite(text.data(), 1, text.size(), out) != text.size()) return "Unable to write to file: " + out_path_;
+        pt.t[3] += lap();
+        return "";
+    });
+    if (err.empty() && !resident) err = kept_.finish(false, end);
     if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path_;
     return err;
 }
@@ -1443,44 +1545,19 @@ ProfileComputer::~ProfileComputer() { delete ctr_; }
 std::string ProfileComputer::profile_pass(uint32_t pass, uint32_t passes, kt_ctr *table) {
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    const double ceil_bytes = memory_ceil_gb_ * (double)(1ull << 30);
-    Batch b;
-    uint64_t at = 0, base = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20));
-        const uint64_t n = b.n_reads();
-        if (n) {
-            const uint64_t total = b.offsets[n];
-            if (pass == 0) {
-                if ((double)(base + total) * 4.0 > ceil_bytes) {
-                    char msg[256];
-                    snprintf(msg, sizeof msg,
-                             "profile: the table takes %u passes, and the per-base counts of the input kept across them (4 bytes "
-                             "per base, more than %.1f GB) do not fit the memory ceiling of %.0f GB: raise -m or split the input",
-                             passes, (double)(base + total) * 4.0 / (double)(1ull << 30), memory_ceil_gb_);
-                    return msg;
-                }
-                acc_.resize(base + total, KT_NO_KMER);
-            } else if (base + total > acc_.size()) {
-                return "profile: the input changed between the passes";
-            }
-            if (total && kt_ctr_profile(table, bases_ptr(b), b.offsets.data(), n, acc_.data() + base, KT_MEM_HOST, passes, pass) != KT_OK)
-                return kt_last_error();
-            at += n;
-            base += total;
-        }
-        if (!more) break;
-    }
-    if (reader.failed()) return reader.error();
-    if (pass && (at != acc_reads_ || base != acc_.size())) return "profile: the input changed between the passes";
-    acc_reads_ = at;
-    return "";
-}
-
-static void append_uint(std::string &out, uint64_t v) {
-    char buf[24];
-    const auto e = std::to_chars(buf, buf + sizeof buf, v);
-    out.append(buf, (size_t)(e.ptr - buf));
+    Batch batch;
+    Cursor end;
+    const std::string e = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, false, nullptr, nullptr, &end,
+                               [&](const Batch &b, const Cursor &at) -> std::string {
+        const uint64_t n = b.n_reads(), total = b.offsets[n];
+        if (pass == 0)
+            if (std::string c = kept_.over_ceiling(at.bases + total, 4, "per-base counts", passes, memory_ceil_gb_); !c.empty()) return c;
+        if (std::string c = kept_.claim(pass == 0, acc_, at.bases + total, (uint32_t)KT_NO_KMER); !c.empty()) return c;
+        if (total && kt_ctr_profile(table, bases_ptr(b), b.offsets.data(), n, acc_.data() + at.bases, KT_MEM_HOST, passes, pass) != KT_OK)
+            return kt_last_error();
+        return "";
+    });
+    return e.empty() ? kept_.finish(pass == 0, end) : e;
 }
 
 // a record's name: its header up to the first white space
@@ -1494,13 +1571,9 @@ std::string ProfileComputer::profile() {
     delete ctr_;
     acc_.clear();
     acc_.shrink_to_fit();
-    acc_reads_ = 0;
-    ctr_ = new CountComputer(in_path_kmer_, ".", ksize_);
-    ctr_->set_threads(threads_);
-    ctr_->set_max_memory(memory_ceil_gb_);
-    ctr_->set_device(device_);
-    ctr_->set_histo(0, true);  // no kmers.histo and no kmers.counts: the table is only looked up
-    ctr_->set_pass_hook([this](uint32_t pass, uint32_t passes, kt_ctr *t) { return profile_pass(pass, passes, t); });
+    kept_.seen = Cursor();
+    ctr_ = make_lookup_counter(in_path_kmer_, ksize_, threads_, memory_ceil_gb_, device_,
+                               [this](uint32_t pass, uint32_t passes, kt_ctr *t) { return profile_pass(pass, passes, t); });
     if (std::string e = ctr_->count(); !e.empty()) return e;
     const bool resident = ctr_->passes() == 1;  // else: the positions were filled pass by pass (profile_pass)
     if (resident && !ctr_->table()) return "profile: no table";
@@ -1518,86 +1591,71 @@ std::string ProfileComputer::profile() {
     }
     PhaseTimer pt("profile");
     Lap lap;
-    Batch b;
-    std::string text = "#name\tlength\tkmers\tpresent\tmin\tmedian\tmean\tmax\n", err;
+    Batch batch;
+    std::string text = "#name\tlength\tkmers\tpresent\tmin\tmedian\tmean\tmax\n";
     std::vector<std::string> pieces;
     std::vector<uint32_t> prof, st;
     std::vector<uint64_t> sum;
-    uint64_t at = 0, base = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
-        pt.t[0] += lap();
-        const uint64_t n = b.n_reads();
-        if (n) {
-            const uint64_t total = b.offsets[n];
-            const uint32_t *p;
-            if (resident) {
-                prof.assign(total, KT_NO_KMER);
-                if (total && kt_ctr_profile(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), KT_MEM_HOST, 1, 0) != KT_OK) {
-                    err = kt_last_error();
-                    break;
-                }
-                p = prof.data();
-            } else {
-                if (at + n > acc_reads_ || base + total > acc_.size()) {
-                    err = "profile: the input changed between the passes";
-                    break;
-                }
-                p = acc_.data() + base;
-            }
-            st.resize(n * 5);
-            sum.resize(n);
-            uint32_t *nk = st.data(), *np = nk + n, *mn = np + n, *md = mn + n, *mx = md + n;
-            if (kt_profile_stats(ctx, p, b.offsets.data(), n, nk, np, mn, md, mx, sum.data(), KT_MEM_HOST) != KT_OK) {
-                err = kt_last_error();
-                break;
-            }
-            pt.t[1] += lap();
-            for (uint64_t i = 0; i < n; i++) {
-                append_name(text, b.headers[i]);
-                text += '\t';
-                append_uint(text, b.offsets[i + 1] - b.offsets[i]);
-                for (const uint32_t *col : {nk, np, mn, md}) {
-                    text += '\t';
-                    append_uint(text, col[i]);
-                }
-                text += '\t';
-                append_fixed6(text, (double)sum[i] / (double)(nk[i] ? nk[i] : 1u));
-                text += '\t';
-                append_uint(text, mx[i]);
-                text += '\n';
-            }
-            if (fc)
-                format_rows(n, threads_, 512, pieces, [&](uint64_t i, std::string &s) {
-                    s += '>';
-                    append_name(s, b.headers[i]);
-                    s += '\n';
-                    for (uint64_t g = b.offsets[i]; g < b.offsets[i + 1]; g++) {
-                        if (g != b.offsets[i]) s += ' ';
-                        if (p[g] == KT_NO_KMER) s += "-1";
-                        else append_uint(s, p[g]);
-                    }
-                    s += '\n';
-                });
-            pt.t[2] += lap();
-            bool ok = fwrite(text.data(), 1, text.size(), fs) == text.size();
-            text.clear();
-            if (fc)
-                for (const std::string &piece : pieces) ok = ok && fwrite(piece.data(), 1, piece.size(), fc) == piece.size();
-            if (!ok) {
-                err = "Unable to write to directory: " + out_dir_;
-                break;
-            }
-            pt.t[3] += lap();
-            at += n;
-            base += total;
+    Cursor end;
+    bool in_batch = false;  // stays set when a batch ends with an error
+    std::string err = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, true, &pt, &lap, &end, [&](const Batch &b, const Cursor &at) -> std::string {
+        in_batch = true;
+        const uint64_t n = b.n_reads(), total = b.offsets[n];
+        const uint32_t *p;
+        if (resident) {
+            prof.assign(total, KT_NO_KMER);
+            if (total && kt_ctr_profile(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), KT_MEM_HOST, 1, 0) != KT_OK)
+                return kt_last_error();
+            p = prof.data();
+        } else {
+            if (std::string c = kept_.inside(at, b); !c.empty()) return c;
+            p = acc_.data() + at.bases;
         }
-        if (!more) break;
-    }
-    if (err.empty() && !text.empty() && fwrite(text.data(), 1, text.size(), fs) != text.size())  // (an input without records: the header line)
+        st.resize(n * 5);
+        sum.resize(n);
+        uint32_t *nk = st.data(), *np = nk + n, *mn = np + n, *md = mn + n, *mx = md + n;
+        if (kt_profile_stats(ctx, p, b.offsets.data(), n, nk, np, mn, md, mx, sum.data(), KT_MEM_HOST) != KT_OK) return kt_last_error();
+        pt.t[1] += lap();
+        for (uint64_t i = 0; i < n; i++) {
+            append_name(text, b.headers[i]);
+            text += '\t';
+            append_uint(text, b.offsets[i + 1] - b.offsets[i]);
+            for (const uint32_t *col : {nk, np, mn, md}) {
+                text += '\t';
+                append_uint(text, col[i]);
+            }
+            text += '\t';
+            append_fixed6(text, (double)sum[i] / (double)(nk[i] ? nk[i] : 1u));
+            text += '\t';
+            append_uint(text, mx[i]);
+            text += '\n';
+        }
+        if (fc)
+            format_rows(n, threads_, 512, pieces, [&](uint64_t i, std::string &s) {
+                s += '>';
+                append_name(s, b.headers[i]);
+                s += '\n';
+                for (uint64_t g = b.offsets[i]; g < b.offsets[i + 1]; g++) {
+                    if (g != b.offsets[i]) s += ' ';
+                    if (p[g] == KT_NO_KMER) s += "-1";
+                    else append_uint(s, p[g]);
+                }
+                s += '\n';
+            });
+        pt.t[2] += lap();
+        bool ok = fwrite(text.data(), 1, text.size(), fs) == text.size();
+        text.clear();
+        if (fc)
+            for (const std::string &piece : pieces) ok = ok && fwrite(piece.data(), 1, piece.size(), fc) == piece.size();
+        if (!ok) return "Unable to write to directory: " + out_dir_;
+        pt.t[3] += lap();
+        in_batch = false;
+        return "";
+    });
+    // (an input without records - or none before the reader failed: the header line)
+    if (!in_batch && !text.empty() && fwrite(text.data(), 1, text.size(), fs) != text.size() && err.empty())
         err = "Unable to write to file: " + spath;
-    if (err.empty() && reader.failed()) err = reader.error();
-    if (err.empty() && !resident && (at != acc_reads_ || base != acc_.size())) err = "profile: the input changed between the passes";
+    if (err.empty() && !resident) err = kept_.finish(false, end);
     if (fclose(fs) != 0 && err.empty()) err = "Unable to write to file: " + spath;
     if (fc && fclose(fc) != 0 && err.empty()) err = "Unable to write to file: " + cpath;
     return err;
@@ -1614,53 +1672,32 @@ CorrectComputer::~CorrectComputer() { delete ctr_; }
 std::string CorrectComputer::table_pass(bool support, uint32_t pass, uint32_t passes, kt_ctr *table) {
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    const double ceil_bytes = memory_ceil_gb_ * (double)(1ull << 30);
-    Batch b;
-    uint64_t at = 0, base = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20));
-        const uint64_t n = b.n_reads();
-        if (n) {
-            const uint64_t total = b.offsets[n];
-            if (!support && pass == 0) {
-                if ((double)(base + total) * 8.0 > ceil_bytes) {
-                    char msg[320];
-                    snprintf(msg, sizeof msg,
-                             "correct: the table takes %u passes, and the per-base counts and supports of the input kept across "
-                             "them (8 bytes per base, more than %.1f GB) do not fit the memory ceiling of %.0f GB: raise -m or "
-                             "split the input",
-                             passes, (double)(base + total) * 8.0 / (double)(1ull << 30), memory_ceil_gb_);
-                    return msg;
-                }
-                acc_prof_.resize(base + total, KT_NO_KMER);
-            } else if (base + total > acc_prof_.size()) {
-                return "correct: the input changed between the passes";
-            }
-            if (total) {
-                const int rc = support ? kt_ctr_correct_support(table, bases_ptr(b), b.offsets.data(), n, acc_prof_.data() + base, min_count_,
-                                                                max_count_, acc_sup_.data() + base, KT_MEM_HOST, passes, pass)
-                                       : kt_ctr_profile(table, bases_ptr(b), b.offsets.data(), n, acc_prof_.data() + base, KT_MEM_HOST, passes, pass);
-                if (rc != KT_OK) return kt_last_error();
-            }
-            at += n;
-            base += total;
+    const bool first = !support && pass == 0;
+    Batch batch;
+    Cursor end;
+    const std::string e = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, false, nullptr, nullptr, &end,
+                               [&](const Batch &b, const Cursor &at) -> std::string {
+        const uint64_t n = b.n_reads(), total = b.offsets[n];
+        if (first)
+            if (std::string c = kept_.over_ceiling(at.bases + total, 8, "per-base counts and supports", passes, memory_ceil_gb_); !c.empty())
+                return c;
+        if (std::string c = kept_.claim(first, acc_prof_, at.bases + total, (uint32_t)KT_NO_KMER); !c.empty()) return c;
+        if (total) {
+            uint32_t *prof = acc_prof_.data() + at.bases;
+            const int rc = support ? kt_ctr_correct_support(table, bases_ptr(b), b.offsets.data(), n, prof, min_count_, max_count_,
+                                                            acc_sup_.data() + at.bases, KT_MEM_HOST, passes, pass)
+                                   : kt_ctr_profile(table, bases_ptr(b), b.offsets.data(), n, prof, KT_MEM_HOST, passes, pass);
+            if (rc != KT_OK) return kt_last_error();
         }
-        if (!more) break;
-    }
-    if (reader.failed()) return reader.error();
-    if ((support || pass) && (at != acc_reads_ || base != acc_prof_.size())) return "correct: the input changed between the passes";
-    acc_reads_ = at;
-    return "";
+        return "";
+    });
+    return e.empty() ? kept_.finish(first, end) : e;
 }
 
 CountComputer *CorrectComputer::new_counter(bool support) {
-    CountComputer *c = new CountComputer(in_path_kmer_, ".", ksize_);
-    c->set_threads(threads_);
-    c->set_max_memory(memory_ceil_gb_);
-    c->set_device(device_);
-    c->set_histo(0, true);  // no kmers.histo and no kmers.counts: the table is only looked up
-    c->set_pass_hook([this, support](uint32_t pass, uint32_t passes, kt_ctr *t) { return table_pass(support, pass, passes, t); });
-    return c;
+    return make_lookup_counter(in_path_kmer_, ksize_, threads_, memory_ceil_gb_, device_, [this, support](uint32_t pass, uint32_t passes, kt_ctr *t) {
+        return table_pass(support, pass, passes, t);
+    });
 }
 
 std::string CorrectComputer::correct() {
@@ -1670,7 +1707,7 @@ std::string CorrectComputer::correct() {
     acc_prof_.shrink_to_fit();
     acc_sup_.clear();
     acc_sup_.shrink_to_fit();
-    acc_reads_ = 0;
+    kept_.seen = Cursor();
     ctr_ = new_counter(false);
     if (std::string e = ctr_->count(); !e.empty()) return e;
     const bool resident = ctr_->passes() == 1;
@@ -1692,84 +1729,55 @@ std::string CorrectComputer::correct() {
     if (!out) return "Unable to write to file: " + out_path_;
     PhaseTimer pt("correct");
     Lap lap;
-    Batch b;
-    std::string text, err;
+    Batch batch;
+    std::string text;
     std::vector<uint32_t> prof, sup, ns, na;
     std::vector<uint8_t> fixed;
-    uint64_t at = 0, base = 0;
+    Cursor end;
     uint64_t reads_corrected = 0, bases_corrected = 0, ambiguous = 0, over_limit = 0;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
-        pt.t[0] += lap();
-        const uint64_t n = b.n_reads();
-        if (n) {
-            const uint64_t total = b.offsets[n];
-            const uint32_t *s;
-            if (resident) {
-                prof.assign(total, KT_NO_KMER);
-                sup.assign(total, 0u);
-                if (total && (kt_ctr_profile(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), KT_MEM_HOST, 1, 0) != KT_OK ||
-                              kt_ctr_correct_support(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), min_count_, max_count_,
-                                                     sup.data(), KT_MEM_HOST, 1, 0) != KT_OK)) {
-                    err = kt_last_error();
-                    break;
-                }
-                s = sup.data();
-            } else {
-                if (at + n > acc_reads_ || base + total > acc_sup_.size()) {
-                    err = "correct: the input changed between the passes";
-                    break;
-                }
-                s = acc_sup_.data() + base;
-            }
-            fixed.resize(total);
-            ns.resize(n);
-            na.resize(n);
-            if (kt_correct_apply(ctx, bases_ptr(b), b.offsets.data(), n, s, min_support_, max_corrections_, fixed.data(), ns.data(),
-                                 na.data(), KT_MEM_HOST) != KT_OK) {
-                err = kt_last_error();
-                break;
-            }
-            pt.t[1] += lap();
-            text.clear();
-            for (uint64_t i = 0; i < n; i++) {
-                const uint64_t o = b.offsets[i], len = b.offsets[i + 1] - o;
-                ambiguous += na[i];
-                if (max_corrections_ && ns[i] > max_corrections_) over_limit++;
-                else if (ns[i]) reads_corrected++, bases_corrected += ns[i];
-                text += fastq ? '@' : '>';
-                text += b.headers[i];
-                text += '\n';
-                text.append((const char *)fixed.data() + o, len);
-                text += '\n';
-                if (fastq) {
-                    text += "+\n";
-                    text.append((const char *)b.quals.data() + o, len);
-                    text += '\n';
-                }
-            }
-            pt.t[2] += lap();
-            if (fwrite(text.data(), 1, text.size(), out) != text.size()) {
-                err = "Unable to write to file: " + out_path_;
-                break;
-            }
-            pt.t[3] += lap();
-            at += n;
-            base += total;
+    std::string err = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, true, &pt, &lap, &end, [&](const Batch &b, const Cursor &at) -> std::string {
+        const uint64_t n = b.n_reads(), total = b.offsets[n];
+        const uint32_t *s;
+        if (resident) {
+            prof.assign(total, KT_NO_KMER);
+            sup.assign(total, 0u);
+            if (total && (kt_ctr_profile(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), KT_MEM_HOST, 1, 0) != KT_OK ||
+                          kt_ctr_correct_support(ctr_->table(), bases_ptr(b), b.offsets.data(), n, prof.data(), min_count_, max_count_,
+                                                 sup.data(), KT_MEM_HOST, 1, 0) != KT_OK))
+                return kt_last_error();
+            s = sup.data();
+        } else {
+            if (std::string c = kept_.inside(at, b); !c.empty()) return c;
+            s = acc_sup_.data() + at.bases;
         }
-        if (!more) break;
-    }
-    if (err.empty() && reader.failed()) err = reader.error();
-    if (err.empty() && !resident && (at != acc_reads_ || base != acc_sup_.size())) err = "correct: the input changed between the passes";
+        fixed.resize(total);
+        ns.resize(n);
+        na.resize(n);
+        if (kt_correct_apply(ctx, bases_ptr(b), b.offsets.data(), n, s, min_support_, max_corrections_, fixed.data(), ns.data(), na.data(),
+                             KT_MEM_HOST) != KT_OK)
+            return kt_last_error();
+        pt.t[1] += lap();
+        text.clear();
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t o = b.offsets[i], len = b.offsets[i + 1] - o;
+            ambiguous += na[i];
+            if (max_corrections_ && ns[i] > max_corrections_) over_limit++;
+            else if (ns[i]) reads_corrected++, bases_corrected += ns[i];
+            append_record(text, fastq, b.headers[i], fixed.data() + o, fastq ? b.quals.data() + o : nullptr, len);
+        }
+        pt.t[2] += lap();
+        if (fwrite(text.data(), 1, text.size(), out) != text.size()) return "Unable to write to file: " + out_path_;
+        pt.t[3] += lap();
+        return "";
+    });
+    if (err.empty() && !resident) err = kept_.finish(false, end);
     if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path_;
     if (err.empty() && !stats_path_.empty()) {
-        FILE *fs = fopen(stats_path_.c_str(), "wb");
-        if (!fs) return "Unable to write to file: " + stats_path_;
-        const int w = fprintf(fs, "reads\t%llu\nbases\t%llu\nreads_corrected\t%llu\nbases_corrected\t%llu\npositions_ambiguous\t%llu\n"
-                                  "reads_over_limit\t%llu\n",
-                              (unsigned long long)at, (unsigned long long)base, (unsigned long long)reads_corrected,
-                              (unsigned long long)bases_corrected, (unsigned long long)ambiguous, (unsigned long long)over_limit);
-        if ((fclose(fs) != 0 || w < 0) && err.empty()) err = "Unable to write to file: " + stats_path_;
+        static const char *names[6] = {"reads", "bases", "reads_corrected", "bases_corrected", "positions_ambiguous", "reads_over_limit"};
+        const uint64_t values[6] = {end.reads, end.bases, reads_corrected, bases_corrected, ambiguous, over_limit};
+        std::string s;
+        append_stats_rows(s, names, values, 6);
+        err = write_text_file(stats_path_, s);
     }
     return err;
 }
@@ -1786,28 +1794,6 @@ void CompareComputer::release() {
     ta_ = tb_ = nullptr;
 }
 
-// slots for the distinct k-mers of one input, as CountComputer::count sizes its table: an upper bound of the bases (a
-// plain file's size, half of it for FASTQ; the pre-pass for compressed input), at most the canonical k-mers of k <= 15,
-// 1.9 slots per possible key
-static std::string compare_want(const std::string &path, int k, uint64_t *want) {
-    uint64_t total = 0, n_seq = 0;
-    std::string err;
-    struct stat st;
-    const bool plain = !(path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) && stat(path.c_str(), &st) == 0 &&
-                       S_ISREG(st.st_mode);
-    if (plain) total = format_from_path(path) == SeqFormat::Fastq ? (uint64_t)st.st_size / 2 : (uint64_t)st.st_size;
-    else if (!SeqReader::seq_stats(path, n_seq, total, err)) return err;
-    uint64_t max_distinct = total;
-    if (k <= 15) {
-        const uint64_t n4k = 1ull << (2 * k);
-        const uint64_t canon = (k & 1) ? n4k / 2 : (n4k + (1ull << k)) / 2;
-        if (canon < max_distinct) max_distinct = canon;
-    }
-    *want = max_distinct + max_distinct / 10 * 9;
-    if (*want < 1024) *want = 1024;
-    return "";
-}
-
 std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_t *tot) const {
     const uint32_t R = max_a_ + 1, C = max_b_ + 1;
     std::string s;
@@ -1819,15 +1805,11 @@ std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_
             s.append(buf, (size_t)(e.ptr - buf));
             s += c + 1 < C ? '\t' : '\n';
         }
-    const std::string mpath = out_dir_ + "/compare.matrix", spath = out_dir_ + "/compare.stats";
-    FILE *out = fopen(mpath.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + mpath;
-    bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + mpath;
+    if (std::string e = write_text_file(out_dir_ + "/compare.matrix", s); !e.empty()) return e;
     // distinct_a, distinct_b, shared, occurrences_a, occurrences_b, shared_min; then the ratios (0 over a zero denominator)
     static const char *names[6] = {"distinct_a", "distinct_b", "shared", "occurrences_a", "occurrences_b", "shared_min"};
     s.clear();
-    for (int j = 0; j < 6; j++) s += std::string(names[j]) + '\t' + std::to_string(tot[j]) + '\n';
+    append_stats_rows(s, names, tot, 6);
     auto ratio = [&](const char *name, uint64_t num, uint64_t den) {
         char b[FIXED6_BUF + 64];
         snprintf(b, sizeof b, "%s\t%.6f\n", name, den ? (double)num / (double)den : 0.0);
@@ -1838,53 +1820,27 @@ std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_
     ratio("containment_a", sh, da);
     ratio("containment_b", sh, db);
     ratio("weighted_jaccard", smin, oa + ob - smin);
-    out = fopen(spath.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + spath;
-    ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
-    return "";
+    return write_text_file(out_dir_ + "/compare.stats", s);
 }
 
-// What `compare` and `setop` share.  Both tables of a pass live on one device next to the build's buffers
-// (CountComputer::count's reserve), `bytes_per_slot` of HBM for every slot of either (16: the slot itself); when they cannot,
-// or KT_CTR_MAX_SLOTS bounds a table (tests: force the out-of-core passes), the inputs are counted in *passes passes,
-// pass p holding hash partition p of both.  Creates the tables; on an error none is left.
-static const uint64_t TWO_TABLE_BATCH_BASES = 256ull << 20;
+// What `compare` and `setop` share: both tables of a pass on one device, `bytes_per_slot` of HBM for every slot of either
+// (16: the slot itself), pass p holding hash partition p of both.  Creates the tables; on an error none is left.
 static std::string two_tables_setup(Device &dev, const std::string &in_a, const std::string &in_b, int k, uint64_t bytes_per_slot,
                                     const char *what, uint32_t *passes, kt_ctr **ta, kt_ctr **tb) {
     Lap setup;
-    uint64_t want_a = 0, want_b = 0;
-    if (std::string e = compare_want(in_a, k, &want_a); !e.empty()) return e;
-    if (std::string e = compare_want(in_b, k, &want_b); !e.empty()) return e;
+    InputBound a, b;
+    if (std::string e = slots_wanted(in_a, k, &a); !e.empty()) return e;
+    if (std::string e = slots_wanted(in_b, k, &b); !e.empty()) return e;
     if (std::string e = dev.ensure(); !e.empty()) return e;
-    uint64_t free_b = 0, total_b = 0, fit_both = want_a + want_b;
-    if (kt_device_memory(dev.ctx, &free_b, &total_b) == KT_OK) {
-        const uint64_t reserve = TWO_TABLE_BATCH_BASES * 20 + (1ull << 30);
-        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
-        fit_both = usable / 10 * 9 / bytes_per_slot;
-    }
-    if (fit_both < 2048) fit_both = 2048;
-    uint64_t fit_each = env_u64_host("KT_CTR_MAX_SLOTS", ~0ull);
-    if (fit_each < 1024) fit_each = 1024;
-    uint64_t p = (want_a + want_b + fit_both - 1) / fit_both;
-    p = std::max(p, (want_a + fit_each - 1) / fit_each);
-    p = std::max(p, (want_b + fit_each - 1) / fit_each);
-    *passes = (uint32_t)std::max<uint64_t>(p, 1);
-    // a partition's share of the keys varies a little: 1 / passes + 5 sigma of room; more passes when the tables do not fit
-    uint64_t cap_a = 0, cap_b = 0;
-    for (;; ++*passes) {
-        cap_a = *passes == 1 ? want_a : want_a / *passes + want_a / *passes / 16 + 4096;
-        cap_b = *passes == 1 ? want_b : want_b / *passes + want_b / *passes / 16 + 4096;
-        int rc = kt_ctr_create(dev.ctx, k, cap_a, ta);
-        if (rc == KT_OK) rc = kt_ctr_create(dev.ctx, k, cap_b, tb);
-        if (rc == KT_OK) break;
-        if (*ta) kt_ctr_destroy(*ta);
-        if (*tb) kt_ctr_destroy(*tb);
-        *ta = *tb = nullptr;
-        if (rc != KT_ERR_NOMEM || *passes >= 4096) return kt_last_error();
-    }
+    TablePlan plan;
+    plan.n = 2;
+    plan.want[0] = a.want, plan.want[1] = b.want;
+    plan.plan(dev.ctx, bytes_per_slot, false);
+    kt_ctr **const tables[2] = {ta, tb};
+    if (std::string e = create_tables(dev.ctx, k, plan, tables); !e.empty()) return e;
+    *passes = plan.passes;
     if (getenv("KT_CLI_TIMING")) {
-        uint64_t sa = cap_a, sb = cap_b;
+        uint64_t sa = plan.capacity(0), sb = plan.capacity(1);
         (void)kt_ctr_capacity(*ta, &sa);
         (void)kt_ctr_capacity(*tb, &sb);
         fprintf(stderr, "[timing] %s setup: tables of %llu + %llu slots, %u pass(es) %.3f s\n", what, (unsigned long long)sa,
@@ -1899,16 +1855,12 @@ static std::string two_tables_count(uint32_t pass, uint32_t passes, SeqReader &r
     if (pass && (kt_ctr_clear(ta) != KT_OK || kt_ctr_clear(tb) != KT_OK)) return kt_last_error();
     for (auto [reader, table] : {std::make_pair(&ra, ta), std::make_pair(&rb, tb)}) {
         if (pass && !reader->rewind()) return reader->error();
-        for (;;) {
-            const bool more = reader->next_batch(b, cli_batch_bases(TWO_TABLE_BATCH_BASES), cli_batch_reads(1ull << 22));
-            pt.t[0] += lap();
-            if (b.n_reads() && !b.bases.empty())
-                if (kt_ctr_add_reads_part(table, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST, passes, pass) != KT_OK)
-                    return kt_last_error();
-            pt.t[1] += lap();
-            if (!more) break;
-        }
-        if (reader->failed()) return reader->error();
+        kt_ctr *t = table;  // (a structured binding cannot be captured)
+        if (std::string e = fill_table(*reader, b, pt, lap, [&](const Batch &bb) {
+                return kt_ctr_add_reads_part(t, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST, passes, pass);
+            });
+            !e.empty())
+            return e;
     }
     return "";
 }
@@ -2008,12 +1960,8 @@ std::string SetopComputer::setop() {
     if (fclose(out) != 0) return "Unable to write to file: " + cpath;
     static const char *names[6] = {"distinct_a", "distinct_b", "in_a", "in_b", "emitted", "emitted_occurrences"};
     std::string s;
-    for (int j = 0; j < 6; j++) s += std::string(names[j]) + '\t' + std::to_string(tot[j]) + '\n';
-    out = fopen(spath.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + spath;
-    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
-    return "";
+    append_stats_rows(s, names, tot, 6);
+    return write_text_file(spath, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2031,49 +1979,51 @@ static std::string graph_census_name(int j) {
     return "degree_" + std::to_string((j - 7) / 5) + "_" + std::to_string((j - 7) % 5);
 }
 
+// What `graph` and `unitigs` share: one table, and the whole of it on the device - a plan of several passes is refused
+// before anything is counted or written.  whole_table plans and creates it (`name`: the command, in the texts - its
+// PhaseTimer starts only afterwards, so a refusal prints no phase line), fill_whole_table counts the input into it.
+static std::string whole_table(Device &dev, const std::string &path, int k, uint64_t bytes_per_slot, const char *name, kt_ctr **table) {
+    Lap setup;
+    InputBound in;
+    if (std::string e = slots_wanted(path, k, &in); !e.empty()) return e;
+    if (std::string e = dev.ensure(); !e.empty()) return e;
+    TablePlan plan;
+    plan.want[0] = in.want;
+    plan.plan(dev.ctx, bytes_per_slot, false);
+    const std::string whole = std::string(name) +
+                              " needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
+                              "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
+                              "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
+                              "memory or a smaller input";
+    if (plan.passes > 1) return whole + " (" + std::to_string(in.want) + " slots wanted, room for " + std::to_string(plan.room) + ")";
+    if (const int rc = kt_ctr_create(dev.ctx, k, in.want, table); rc != KT_OK)
+        return rc == KT_ERR_NOMEM ? whole + " (" + kt_last_error() + ")" : std::string(kt_last_error());
+    if (getenv("KT_CLI_TIMING")) {
+        uint64_t slots = in.want;
+        (void)kt_ctr_capacity(*table, &slots);
+        fprintf(stderr, "[timing] %s setup: table of %llu slots %.3f s\n", name, (unsigned long long)slots, setup());
+    }
+    return "";
+}
+// (the reader and the batch stay the caller's, alive until the command is done, as the table's other users keep theirs)
+static std::string fill_whole_table(kt_ctr *table, SeqReader &reader, Batch &b, PhaseTimer &pt, Lap &lap) {
+    return fill_table(reader, b, pt, lap, [&](const Batch &bb) {
+        return kt_ctr_add_reads(table, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST);
+    });
+}
+
 std::string GraphComputer::graph() {
     if (table_) kt_ctr_destroy(table_);
     table_ = nullptr;
-    // The table is sized as CountComputer::count sizes its own.  HBM per slot: the slot (16) + its share of the result
-    // (key, info, count: 16 bytes a node) and of the sort's second pair (12), with 1.9 slots per entry: 28 / 1.9 < 15
-    Lap setup;
-    uint64_t want = 0;
-    if (std::string e = compare_want(in_path_, ksize_, &want); !e.empty()) return e;
-    if (std::string e = dev_.ensure(); !e.empty()) return e;
-    uint64_t free_b = 0, total_b = 0, fit = want;
-    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
-        const uint64_t reserve = TWO_TABLE_BATCH_BASES * 20 + (1ull << 30);
-        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
-        fit = usable / 10 * 9 / (16 + 15);
-    }
-    fit = std::min(fit, env_u64_host("KT_CTR_MAX_SLOTS", ~0ull));  // (tests: what forces the other commands' passes)
-    if (fit < 1024) fit = 1024;
-    const char *whole = "graph needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
-                        "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
-                        "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
-                        "memory or a smaller input";
-    if (want > fit) return std::string(whole) + " (" + std::to_string(want) + " slots wanted, room for " + std::to_string(fit) + ")";
-    if (const int rc = kt_ctr_create(dev_.ctx, ksize_, want, &table_); rc != KT_OK)
-        return rc == KT_ERR_NOMEM ? std::string(whole) + " (" + kt_last_error() + ")" : std::string(kt_last_error());
-    if (getenv("KT_CLI_TIMING")) {
-        uint64_t slots = want;
-        (void)kt_ctr_capacity(table_, &slots);
-        fprintf(stderr, "[timing] graph setup: table of %llu slots %.3f s\n", (unsigned long long)slots, setup());
-    }
+    // HBM per slot: the slot (16) + its share of the result (key, info, count: 16 bytes a node) and of the sort's second
+    // pair (12), with 1.9 slots per entry: 28 / 1.9 < 15
+    if (std::string e = whole_table(dev_, in_path_, ksize_, 16 + 15, "graph", &table_); !e.empty()) return e;
     PhaseTimer pt("graph");
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     Lap lap;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(TWO_TABLE_BATCH_BASES), cli_batch_reads(1ull << 22));
-        pt.t[0] += lap();
-        if (b.n_reads() && !b.bases.empty())
-            if (kt_ctr_add_reads(table_, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST) != KT_OK) return kt_last_error();
-        pt.t[1] += lap();
-        if (!more) break;
-    }
-    if (reader.failed()) return reader.error();
+    if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
     // what can be a node at most sizes the host arrays: one call, no counting call before it
     uint64_t bound = 0, n = 0, census[KT_GRAPH_CENSUS] = {};
     if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
@@ -2095,17 +2045,9 @@ std::string GraphComputer::graph() {
         for (uint64_t i0 = 0; i0 < n && ok; i0 += slab) {
             format_rows(std::min(slab, n - i0), threads_, (size_t)ksize_ + 26, pieces, [&](uint64_t r, std::string &s) {
                 const uint64_t i = i0 + r;
-                char buf[40];
-                if (acgt_) {
-                    kt_numeric_to_kmer(keys[i], ksize_, buf);
-                    s += buf;
-                } else {
-                    const auto rr = std::to_chars(buf, buf + sizeof buf, keys[i]);
-                    s.append(buf, (size_t)(rr.ptr - buf));
-                }
+                append_kmer(s, keys[i], ksize_, acgt_);
                 s += '\t';
-                const auto r2 = std::to_chars(buf, buf + sizeof buf, counts[i]);
-                s.append(buf, (size_t)(r2.ptr - buf));
+                append_uint(s, counts[i]);
                 s += '\t';
                 for (int x = 0; x < 4; x++) s += info[i] >> (4 + x) & 1u ? "ACGT"[x] : '.';
                 s += '\t';
@@ -2121,11 +2063,7 @@ std::string GraphComputer::graph() {
     }
     std::string s;
     for (int j = 0; j < KT_GRAPH_CENSUS; j++) s += graph_census_name(j) + '\t' + std::to_string(census[j]) + '\n';
-    const std::string spath = out_dir_ + "/graph.stats";
-    FILE *out = fopen(spath.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + spath;
-    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
+    if (std::string e = write_text_file(out_dir_ + "/graph.stats", s); !e.empty()) return e;
     pt.t[3] += lap();
     return "";
 }
@@ -2141,47 +2079,15 @@ UnitigComputer::~UnitigComputer() {
 std::string UnitigComputer::unitigs() {
     if (table_) kt_ctr_destroy(table_);
     table_ = nullptr;
-    // The table is sized as GraphComputer::graph sizes its own.  HBM per slot: the slot (16) + its share of what
-    // kt_ctr_unitigs keeps when every entry is a node (16 + 64 bytes, 48 more on cycles, the sort's second pair 12), with 1.9 slots per entry:
-    // 140 / 1.9 < 74
-    Lap setup;
-    uint64_t want = 0;
-    if (std::string e = compare_want(in_path_, ksize_, &want); !e.empty()) return e;
-    if (std::string e = dev_.ensure(); !e.empty()) return e;
-    uint64_t free_b = 0, total_b = 0, fit = want;
-    if (kt_device_memory(dev_.ctx, &free_b, &total_b) == KT_OK) {
-        const uint64_t reserve = TWO_TABLE_BATCH_BASES * 20 + (1ull << 30);
-        const uint64_t usable = free_b > 2 * reserve ? free_b - reserve : free_b / 2;
-        fit = usable / 10 * 9 / (16 + 74);
-    }
-    fit = std::min(fit, env_u64_host("KT_CTR_MAX_SLOTS", ~0ull));  // (tests: what forces the other commands' passes)
-    if (fit < 1024) fit = 1024;
-    const char *whole = "unitigs needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
-                        "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
-                        "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
-                        "memory or a smaller input";
-    if (want > fit) return std::string(whole) + " (" + std::to_string(want) + " slots wanted, room for " + std::to_string(fit) + ")";
-    if (const int rc = kt_ctr_create(dev_.ctx, ksize_, want, &table_); rc != KT_OK)
-        return rc == KT_ERR_NOMEM ? std::string(whole) + " (" + kt_last_error() + ")" : std::string(kt_last_error());
-    if (getenv("KT_CLI_TIMING")) {
-        uint64_t slots = want;
-        (void)kt_ctr_capacity(table_, &slots);
-        fprintf(stderr, "[timing] unitigs setup: table of %llu slots %.3f s\n", (unsigned long long)slots, setup());
-    }
+    // HBM per slot: the slot (16) + its share of what kt_ctr_unitigs keeps when every entry is a node (16 + 64 bytes, 48 more
+    // on cycles, the sort's second pair 12), with 1.9 slots per entry: 140 / 1.9 < 74
+    if (std::string e = whole_table(dev_, in_path_, ksize_, 16 + 74, "unitigs", &table_); !e.empty()) return e;
     PhaseTimer pt("unitigs");
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     Lap lap;
-    for (;;) {
-        const bool more = reader.next_batch(b, cli_batch_bases(TWO_TABLE_BATCH_BASES), cli_batch_reads(1ull << 22));
-        pt.t[0] += lap();
-        if (b.n_reads() && !b.bases.empty())
-            if (kt_ctr_add_reads(table_, b.bases.data(), b.offsets.data(), b.n_reads(), KT_MEM_HOST) != KT_OK) return kt_last_error();
-        pt.t[1] += lap();
-        if (!more) break;
-    }
-    if (reader.failed()) return reader.error();
+    if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
     // a count-only call, then one call sized by it; with the links only where a file asks for them
     const bool linked = gfa_ || fa_links_;
     uint64_t nu = 0, nb = 0, nl = 0;
@@ -2278,15 +2184,11 @@ std::string UnitigComputer::unitigs() {
             flush(true);
             if (fclose(out) != 0 || !ok) return "Unable to write to file: " + gpath;
         }
-        const std::pair<const char *, uint64_t> rows[6] = {{"links", nl},          {"edges", edges},     {"dead_ends", dead},
-                                                          {"isolated", isolated}, {"self_links", self}, {"max_end_degree", max_deg}};
+        static const char *names[6] = {"links", "edges", "dead_ends", "isolated", "self_links", "max_end_degree"};
+        const uint64_t values[6] = {nl, edges, dead, isolated, self, max_deg};
         std::string s;
-        for (const auto &r : rows) s += std::string(r.first) + '\t' + std::to_string(r.second) + '\n';
-        const std::string lpath = out_dir_ + "/unitigs.links.stats";
-        FILE *out = fopen(lpath.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + lpath;
-        const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-        if (fclose(out) != 0 || !ok) return "Unable to write to file: " + lpath;
+        append_stats_rows(s, names, values, 6);
+        if (std::string e = write_text_file(out_dir_ + "/unitigs.links.stats", s); !e.empty()) return e;
     }
     // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
     std::vector<uint64_t> lens((size_t)nu);
@@ -2306,16 +2208,11 @@ std::string UnitigComputer::unitigs() {
             break;
         }
     }
-    const std::pair<const char *, uint64_t> rows[8] = {{"unitigs", nu},           {"bases", nb},           {"nodes", nb - nu * overlap},
-                                                      {"occurrences", occ},      {"circular", circular},  {"singletons", singletons},
-                                                      {"longest", longest},      {"n50", n50}};
+    static const char *names[8] = {"unitigs", "bases", "nodes", "occurrences", "circular", "singletons", "longest", "n50"};
+    const uint64_t values[8] = {nu, nb, nb - nu * overlap, occ, circular, singletons, longest, n50};
     std::string s;
-    for (const auto &r : rows) s += std::string(r.first) + '\t' + std::to_string(r.second) + '\n';
-    const std::string spath = out_dir_ + "/unitigs.stats";
-    FILE *out = fopen(spath.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + spath;
-    const bool ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-    if (fclose(out) != 0 || !ok) return "Unable to write to file: " + spath;
+    append_stats_rows(s, names, values, 8);
+    if (std::string e = write_text_file(out_dir_ + "/unitigs.stats", s); !e.empty()) return e;
     pt.t[3] += lap();
     return "";
 }

@@ -38,6 +38,30 @@ struct Device {  // one kt_ctx per computer, created on first use
     std::string ensure();  // "" or error message
 };
 
+struct Cursor {  // a place in an input: the reads and the bases in front of it
+    uint64_t reads = 0, bases = 0;
+};
+
+// What a read-level command (cov, filter, profile, correct) keeps of its input across the passes of an out-of-core table:
+// arrays indexed by read or by base.  The first walk over the input grows them and notes its reads and bases; every
+// later walk - the other passes, the output loop - must stay inside them and end at the same totals.
+struct KeptAcrossPasses {
+    const char *cmd;  // in front of the error texts
+    Cursor seen;      // the input as the first walk saw it
+    explicit KeptAcrossPasses(const char *c) : cmd(c) {}
+    std::string changed() const { return std::string(cmd) + ": the input changed between the passes"; }
+    template <class T>
+    std::string claim(bool first, std::vector<T> &v, uint64_t size, T init) const {  // v holds `size` values from here on
+        if (first) v.resize(size, init);
+        else if (size > v.size()) return changed();
+        return "";
+    }
+    std::string inside(const Cursor &at, const Batch &b) const;  // the batch at `at` lies inside what the first walk saw
+    std::string finish(bool first, const Cursor &end);           // after a walk: note the totals, or compare them
+    // profile and correct keep bytes_per_base of `what` per base of the whole input: refused above the memory ceiling (-m)
+    std::string over_ceiling(uint64_t bases, unsigned bytes_per_base, const char *what, uint32_t passes, double ceil_gb) const;
+};
+
 class OligoComputer {
   public:
     OligoComputer(std::string in_path, std::string out_path, int ksize, bool count_min);
@@ -177,7 +201,7 @@ class CovComputer {
     // a table that needed several passes (the k-mers do not fit the HBM): the reads' raw bin counts, summed over the
     // passes as each pass's table is complete (kt_cov_batch_part), normalised and written at the end
     std::vector<uint32_t> acc_rows_;
-    uint64_t acc_reads_ = 0;
+    KeptAcrossPasses kept_{"cov"};
     std::string cov_pass(uint32_t pass, uint32_t passes, kt_ctr *table);
 
   public:
@@ -217,7 +241,7 @@ class FilterComputer {
     CountComputer *ctr_ = nullptr;
     // out of core: the reads' numbers, combined over the passes as each pass's table is complete (filter_pass)
     std::vector<uint32_t> acc_n_, acc_s_, acc_w_;
-    uint64_t acc_reads_ = 0;
+    KeptAcrossPasses kept_{"filter"};
     std::string filter_pass(uint32_t pass, uint32_t passes, kt_ctr *table);
     // appends the kept records of batch b (its numbers: n, s, w) to `out`
     void emit(const Batch &b, const uint32_t *n, const uint32_t *s, const uint32_t *w, bool fastq, std::string &out) const;
@@ -255,7 +279,7 @@ class CorrectComputer {
     CountComputer *ctr_ = nullptr;
     // out of core: the whole input's per-base counts (first pass loop) and supports (second), filled as each pass's table is complete
     std::vector<uint32_t> acc_prof_, acc_sup_;
-    uint64_t acc_reads_ = 0;
+    KeptAcrossPasses kept_{"correct"};
     std::string table_pass(bool support, uint32_t pass, uint32_t passes, kt_ctr *table);
     CountComputer *new_counter(bool support);
 };
@@ -290,7 +314,7 @@ class ProfileComputer {
     CountComputer *ctr_ = nullptr;
     // out of core: the whole input's per-base counts, filled over the passes as each pass's table is complete
     std::vector<uint32_t> acc_;
-    uint64_t acc_reads_ = 0;
+    KeptAcrossPasses kept_{"profile"};
     std::string profile_pass(uint32_t pass, uint32_t passes, kt_ctr *table);
 };
 
