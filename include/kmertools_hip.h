@@ -198,6 +198,20 @@ int kt_ctr_add_reads_part(kt_ctr *ctr, const uint8_t *bases, const uint64_t *off
 int kt_ctr_add_pairs(kt_ctr *ctr, const uint64_t *keys, const uint32_t *counts, uint64_t n,
                      int mem);
 
+/* Removes k-mers from the table in place: every canonical k-mer of keys[0, n) that the table holds.  Afterwards an erased
+ * k-mer is absent for every reader (its count reads 0, kt_ctr_size drops; lookup, cov, profile, spectrum, compare, setop,
+ * graph, unitigs and the exports see the reduced content), and a later add of it starts from 0.  Keys the table does not
+ * hold, duplicates in keys, KT_EMPTY_KEY entries and values >= 4^k are ignored.  *n_erased (may be NULL) = the entries
+ * removed, exact.  n == 0 is KT_OK and leaves the table as it is.  The table may be in any form (dense after a bulk build,
+ * the probing image, counted into an export target - whose arrays are the caller's again afterwards, as after any call that
+ * probes); what kt_ctr_export_stage staged is invalidated, as by an add.  A key cannot simply be taken out of its slot (the
+ * keys behind it in its probe chain would be cut off): the survivors are compacted and the probing image is built again
+ * from them, so the cost is one export plus one reload of the table whatever n is - erase in batches.  Any error leaves the
+ * content exactly as it was.  KT_MEM_HOST synchronises; KT_MEM_DEVICE reads keys on the context's stream and synchronises
+ * once to learn *n_erased.  KT_ERR_ARG: a null table, null keys with n > 0, a bad mem, one shard of a sharded table;
+ * KT_ERR_FULL: an overflowed table.  Device scratch: 12 bytes per entry and one bit per slot. */
+int kt_ctr_erase(kt_ctr *table, const uint64_t *keys, uint64_t n, uint64_t *n_erased, int mem);
+
 /* number of distinct k-mers in the table (synchronises). KT_ERR_FULL if an insert overflowed. */
 int kt_ctr_size(kt_ctr *ctr, uint64_t *distinct);
 
@@ -387,6 +401,53 @@ int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t max_count,
                           uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
                           uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to, uint64_t max_links, uint64_t *n_links,
                           int mem);
+
+/* Which of those unitigs are TIPS - the short dead ends that sequencing errors leave hanging off the true path (what
+ * Bifrost -i clips and -d deletes, what BCALM / minia remove before compacting again).  One round, read-only: marks[u] is
+ * for unitig u of kt_ctr_unitigs's numbering for the same (min_count, max_count).  The rule reads kt_ctr_unitigs_linked's
+ * outputs alone, so it holds for every k.  n_u = unitig u's nodes (bases - k + 1), c_u = its count sum; end e = 2u + (sign is
+ * '-') owns the links links[e] with values f = 2v + (sv is '-'); a link e -> f arrives at end f ^ 1 of unitig f >> 1, and its
+ * mirror is (f ^ 1) -> (e ^ 1).  u is SHORT when it is not circular and n_u <= max_tip_nodes.
+ *   - a short u with no link at either end: KT_TIP_ISOLATED;
+ *   - a short u with no link at exactly one end is a CANDIDATE, e its live end;
+ *   - w BEATS a candidate u when w is no candidate, or w is one and c_w / n_w > c_u / n_u, or the two are equal and w < u
+ *     (compared exactly, as 128-bit products);
+ *   - a candidate u is KT_TIP_TIP when for EVERY link f of its live end, end g = f ^ 1 has a link h != e ^ 1 whose unitig
+ *     h >> 1 beats u;
+ *   - everything else: KT_TIP_KEEP.
+ * So at a fork whose branches are all short dead ends the best one (highest mean count, then lowest number) stays, an end
+ * that had links keeps at least one of them among the unmarked unitigs, and a trunk that is itself a short dead end is not
+ * clipped by its own branches.
+ * tally (may be NULL; KT_TIP_TALLY values, overwritten): [0] tips, [1] their nodes, [2] isolated short unitigs, [3] their
+ * nodes.  *n_unitigs is always exact.  max_unitigs == 0 only counts (marks may be NULL) and still fills tally; when
+ * 0 < max_unitigs < *n_unitigs nothing is written and the call returns KT_ERR_ARG with the number set.  The table is not
+ * changed (it gets its probing image first, as in kt_ctr_graph).  KT_MEM_HOST synchronises; KT_MEM_DEVICE writes marks and
+ * tally on the context's stream and synchronises to learn the sizes.  KT_ERR_ARG: what kt_ctr_unitigs_linked refuses,
+ * max_tip_nodes == 0, a null n_unitigs, null marks with max_unitigs > 0; KT_ERR_FULL: an overflowed table.  On every error the
+ * outputs are untouched.  Device scratch: kt_ctr_unitigs_linked's with 20 + 4 * links / unitigs bytes per unitig in place
+ * of the base array, and 2 bytes per unitig. */
+#define KT_TIP_KEEP 0
+#define KT_TIP_TIP 1
+#define KT_TIP_ISOLATED 2
+#define KT_TIP_TALLY 4
+int kt_ctr_unitig_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint8_t *marks,
+                       uint64_t max_unitigs, uint64_t *n_unitigs, uint64_t *tally, int mem);
+
+/* Clip, recompact, repeat.  Each round takes the marks of kt_ctr_unitig_tips and erases from the table (kt_ctr_erase, the
+ * keys listed on the device: no trip to the host) the nodes of every KT_TIP_TIP unitig and, with KT_CLIP_ISOLATED in flags,
+ * of every KT_TIP_ISOLATED one; the next round sees the unitigs of what is left, so that a tip on a tip goes in two rounds.
+ * The call stops after the first round that erases nothing, or after max_rounds rounds (1..1024).  Entries outside
+ * [min_count, max_count] are no nodes and are never touched.
+ * stats (host memory, may be NULL; KT_CLIP_STATS values, overwritten): [0] rounds that erased something, [1] tips clipped,
+ * [2] tip nodes erased, [3] isolated unitigs dropped, [4] isolated nodes erased, [5] occurrences erased, [6] 1 if the last
+ * round still erased something (stopped by max_rounds: another call may find more), else 0, [7] 0.
+ * An error in round r leaves the table as rounds 0 .. r - 1 left it, and stats describes those rounds.  Synchronises.
+ * KT_ERR_ARG: what kt_ctr_unitig_tips refuses, max_rounds outside 1..1024, flags other than KT_CLIP_ISOLATED.  Device
+ * scratch: kt_ctr_unitig_tips's and 8 bytes per node for the list, then kt_ctr_erase's. */
+#define KT_CLIP_ISOLATED 1u
+#define KT_CLIP_STATS 8
+int kt_ctr_clip_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint32_t max_rounds,
+                     uint32_t flags, uint64_t *stats);
 
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a

@@ -417,7 +417,9 @@ class GraphComputer {
 // gfa writes {out_dir}/unitigs.gfa ("H\tVN:Z:1.0", "S\t{i}\t{seq}\tLN:i:\tKC:i:\tkm:f:" and "\tCL:i:1" on a cycle,
 // "L\t{u}\t{su}\t{v}\t{sv}\t{k-1}M" for every link that is not larger than its mirror as (u, su is '-', v, sv is '-')), fa_links
 // appends " L:{su}:{v}:{sv}" per directed link to the header lines of unitigs.fa; either one writes
-// {out_dir}/unitigs.links.stats (links, edges, dead_ends, isolated, self_links, max_end_degree).
+// {out_dir}/unitigs.links.stats (links, edges, dead_ends, isolated, self_links, max_end_degree).  With set_clip the counted
+// table is clipped first (kt_ctr_clip_tips), every file describes the clipped graph, and {out_dir}/unitigs.clip.stats holds
+// rounds, tips, tip_nodes, isolated, isolated_nodes, occurrences, converged.
 class UnitigComputer {
   public:
     UnitigComputer(std::string in_path, std::string out_dir, int ksize);
@@ -427,6 +429,11 @@ class UnitigComputer {
     void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
     void set_stats_only(bool s) { stats_only_ = s; }
     void set_links(bool gfa, bool fa_links) { gfa_ = gfa, fa_links_ = fa_links; }
+    // before anything is written, the tips of at most tip_nodes k-mers (drop_isolated: the isolated unitigs that short, too)
+    // are erased from the table, for at most `rounds` rounds
+    void set_clip(uint32_t tip_nodes, uint32_t rounds, bool drop_isolated) {
+        clip_ = true, tip_nodes_ = tip_nodes, clip_rounds_ = rounds, drop_isolated_ = drop_isolated;
+    }
     void set_device(int d) { dev_.index = d; }
     std::string unitigs();  // "" or the error message
 
@@ -435,6 +442,8 @@ class UnitigComputer {
     int ksize_;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
     bool stats_only_ = false, gfa_ = false, fa_links_ = false;
+    bool clip_ = false, drop_isolated_ = false;
+    uint32_t tip_nodes_ = 0, clip_rounds_ = 8;
     Device dev_;
     kt_ctr *table_ = nullptr;
 };

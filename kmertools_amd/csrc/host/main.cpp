@@ -893,6 +893,13 @@ const char *HELP_UNITIGS =
     "\"S<TAB>{i}<TAB>{sequence}<TAB>LN:i:<TAB>KC:i:<TAB>km:f:\" line per unitig (and \"<TAB>CL:i:1\" on a cycle) and one\n"
     "\"L<TAB>{u}<TAB>{su}<TAB>{v}<TAB>{sv}<TAB>{k-1}M\" line per link, a link and its mirror written once.  Either flag also\n"
     "writes {output}/unitigs.links.stats: links, edges (L lines), dead_ends, isolated, self_links, max_end_degree.\n\n"
+    "--clip-tips cleans the graph before anything is written, so that every file describes the clipped graph.  A unitig of at\n"
+    "most --tip-nodes k-mers that is no cycle and has links at one end only is a tip when every end it links to has another\n"
+    "link to a unitig that is no such dead end, or is one with a higher mean count (then: a lower number).  The tips' k-mers are\n"
+    "erased from the table and the unitigs made again, for --clip-rounds rounds or until a round finds no tip;\n"
+    "--drop-isolated erases the unitigs that short without a link at either end as well.  {output}/unitigs.clip.stats holds\n"
+    "rounds, tips, tip_nodes, isolated, isolated_nodes, occurrences (all erased) and converged (1: the last round found\n"
+    "nothing, 0: stopped by --clip-rounds).\n\n"
     "Usage: kmertools unitigs [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
     "Options:\n"
     "  -i, --input <INPUT>          Input file path\n"
@@ -903,6 +910,10 @@ const char *HELP_UNITIGS =
     "      --stats-only             Write unitigs.stats only, no unitigs.fa\n"
     "      --gfa                    Also write unitigs.gfa (S and L lines) and unitigs.links.stats\n"
     "      --links                  Append L:{su}:{v}:{sv} fields to the header lines of unitigs.fa; also unitigs.links.stats\n"
+    "      --clip-tips              Erase the tips from the table before the unitigs are written; also unitigs.clip.stats\n"
+    "      --tip-nodes <N>          Longest tip, in k-mers [default: k] (needs --clip-tips)\n"
+    "      --clip-rounds <R>        Most rounds of clipping, 1..1024 [default: 8] (needs --clip-tips)\n"
+    "      --drop-isolated          Erase the isolated unitigs of at most --tip-nodes k-mers too (needs --clip-tips)\n"
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
@@ -911,7 +922,9 @@ const char *HELP_UNITIGS =
 int cmd_unitigs(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
-                                     {0, "device", true},      {0, "gfa", false},          {0, "links", false}};
+                                     {0, "device", true},      {0, "gfa", false},          {0, "links", false},
+                                     {0, "clip-tips", false},  {0, "tip-nodes", true},     {0, "clip-rounds", true},
+                                     {0, "drop-isolated", false}};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -926,6 +939,12 @@ int cmd_unitigs(int argc, char **argv, int from) {
     const bool gfa = f.count("gfa") != 0, links = f.count("links") != 0;
     if (f.count("stats-only") && gfa) usage_error("the argument '--stats-only' cannot be used with '--gfa'");
     if (f.count("stats-only") && links) usage_error("the argument '--stats-only' cannot be used with '--links'");
+    const bool clip = f.count("clip-tips") != 0;
+    const uint64_t tip_nodes = ranged(f, "tip-nodes", 1, 0x7FFFFFFEull, false, (uint64_t)k);
+    const uint64_t clip_rounds = ranged(f, "clip-rounds", 1, 1024, false, 8);
+    for (const char *needs : {"tip-nodes", "clip-rounds", "drop-isolated"})
+        if (f.count(needs) && !clip)
+            usage_error(std::string("the argument '--") + needs + "' requires '--clip-tips'");
     if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
@@ -933,6 +952,7 @@ int cmd_unitigs(int argc, char **argv, int from) {
     if (int rc = make_out_dir(out)) return rc;
     UnitigComputer uc(in, out, k);
     uc.set_links(gfa, links);
+    if (clip) uc.set_clip((uint32_t)tip_nodes, (uint32_t)clip_rounds, f.count("drop-isolated") != 0);
     uc.set_range((uint32_t)lo, (uint32_t)hi);
     uc.set_stats_only(f.count("stats-only") != 0);
     uc.set_device(device);

@@ -217,6 +217,68 @@ __global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__r
     }
 }
 
+// ---- kt_ctr_erase: flag the slots of the keys to remove, compact the others, build the image again from them -------------
+// A slot cannot simply be freed: the keys behind it in its probe chain (which may wrap at the end of the range) would be cut
+// off, and a stored count has no spare value for a tombstone.  So the slots to drop are flagged in a bitmask beside the
+// table (bit s of dead[]: slot s goes), the surviving pairs are compacted into scratch and the image is made anew from them.
+
+// one thread per erase key: the key's slot in the probing image, if it has one, is flagged; the first to flag a slot counts it
+__global__ __launch_bounds__(BLOCK) void erase_flag_kernel(const uint64_t *__restrict__ keys, uint64_t n, kttab::Probed t,
+                                                           uint64_t key_limit, uint32_t *__restrict__ dead,
+                                                           uint64_t *__restrict__ n_erased) {
+    uint32_t hit = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t key = keys[i];
+        if (key == KT_EMPTY_KEY || key >= key_limit) continue;
+        kttab::Probe p = kttab::probe_of(key, t.g);
+        for (uint32_t probe = 0; probe < p.rs; probe++) {
+            const uint64_t s = p.slot();
+            const uint64_t cur = t.slots[s].key;
+            if (cur == KT_EMPTY_KEY) break;
+            if (cur == key) {
+                const uint32_t bit = 1u << (uint32_t)(s & 31u);
+                hit += !(atomicOr(dead + (s >> 5), bit) & bit);
+                break;
+            }
+            p.next();
+        }
+    }
+    publish_fresh(hit, n_erased);
+}
+
+// table_export_kernel over the slots whose bit in dead[] is clear
+__global__ __launch_bounds__(BLOCK) void erase_survivors_kernel(const Slot *__restrict__ slots, uint64_t cap,
+                                                                const uint32_t *__restrict__ dead, uint64_t *__restrict__ out_keys,
+                                                                uint32_t *__restrict__ out_counts, uint64_t max_out,
+                                                                uint64_t *__restrict__ cursor) {
+    __shared__ TileShared sm;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint64_t n_tiles = (cap + XTILE - 1) / XTILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        uint4 v[XPT];
+        uint64_t bal[XPT];
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++) {
+            const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
+            v[j] = i < cap ? reinterpret_cast<const uint4 *>(slots)[i] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+            const bool gone = i < cap && (dead[i >> 5] >> (uint32_t)(i & 31u) & 1u);
+            bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu && !gone);
+        }
+        const uint64_t base = sm.reserve(bal, cursor);
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++) {
+            if ((bal[j] >> lane) & 1ull) {
+                const uint64_t pos = sm.pos(base, bal[j], j);
+                if (pos < max_out) {
+                    out_keys[pos] = ((uint64_t)v[j].y << 32) | v[j].x;
+                    out_counts[pos] = v[j].z + 1u;  // stored value is occurrences - 1
+                }
+            }
+        }
+        ktd::lds_barrier();  // the reservation's LDS is rewritten by the next tile
+    }
+}
+
 // ---- a table's entries in the form they are in (view_of builds it; the walks of spectrum, compare, setop and graph read it) ---------
 // The form is the kernels' template argument; the view holds what they read.
 enum Form { FORM_PROBE = 0, FORM_DENSE = 1, FORM_PAIRS = 2 };
@@ -1060,6 +1122,67 @@ int kt_ctr_reload_pairs(kt_ctr *ctr, const uint64_t *d_keys, const uint32_t *d_c
     hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
                        d_keys, d_counts, n, t, ctr->distinct);
     KT_HIP(hipGetLastError());
+    return KT_OK;
+}
+
+// Scratch: AUX1 = the surviving pairs (12 bytes an entry of the table), AUX2 = the bitmask (one bit a slot), host keys in
+// OFFSETS - all claimed before the first write into the table.  One wait for the stream tells how many slots were flagged;
+// none: the table is left as it is.
+extern "C" int kt_ctr_erase(kt_ctr *ctr, const uint64_t *keys, uint64_t n, uint64_t *n_erased, int mem) {
+    if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_erase: null table");
+    kt_ctx *ctx = ctr->ctx;
+    Call call(ctx, mem, "kt_ctr_erase");
+    if (int rc = call.refuse_shard(ctr)) return rc;
+    if (int rc = call.enter()) return rc;
+    if (n && !keys) return call.fail("null keys");
+    uint64_t n_t = 0;
+    if (int rc = kt_ctr_size(ctr, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    // the keys are looked up by probing: the probing image first (a dense table is imaged, an export target's pairs are
+    // loaded and its arrays are the caller's again, whatever n is) - the content stays what it was
+    if (int rc = table_ready(ctr)) return rc;
+    if (n == 0 || n_t == 0) {
+        if (n_erased) *n_erased = 0;
+        return KT_OK;
+    }
+    const uint64_t words = (ctr->cap + 31) / 32;
+    const size_t o_counts = (n_t * 8 + 15) & ~(size_t)15;
+    uint8_t *pairs = nullptr;
+    uint32_t *dead = nullptr;
+    const uint64_t *d_keys = nullptr;
+    if (int rc = call.scratch(kt::AUX1, o_counts + n_t * 4, &pairs)) return rc;
+    if (int rc = call.scratch(kt::AUX2, words * 4, &dead)) return rc;
+    if (int rc = call.in(kt::OFFSETS, keys, n, &d_keys)) return rc;
+    uint64_t *live_keys = (uint64_t *)pairs;
+    uint32_t *live_counts = (uint32_t *)(pairs + o_counts);
+    hipStream_t st = ctx->stream;
+    uint64_t *cursor = ctr->cursor;  // [0]: flagged slots, [1]: the survivors' cursor
+    KT_HIP(hipMemsetAsync(cursor, 0, 16, st));
+    KT_HIP(hipMemsetAsync(dead, 0, words * 4, st));
+    hipLaunchKernelGGL(erase_flag_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, st, d_keys, n,
+                       probed_of(ctr), 1ull << (2 * ctr->k), dead, cursor);
+    KT_HIP(hipGetLastError());
+    uint64_t gone = 0;
+    KT_HIP(hipMemcpyAsync(&gone, cursor, 8, hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    if (gone > n_t) return kt::fail(KT_ERR_HIP, "kt_ctr_erase: internal: more slots flagged than the table holds");
+    if (gone) {
+        hipLaunchKernelGGL(erase_survivors_kernel, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0, st,
+                           (const Slot *)ctr->slots, ctr->cap, (const uint32_t *)dead, live_keys, live_counts, n_t - gone, cursor + 1);
+        KT_HIP(hipGetLastError());
+        // from here on the table changes: what kt_ctr_export_stage staged is no longer the table
+        ctr->stage_n = 0;
+        hipLaunchKernelGGL(table_clear_kernel, dim3(grid_for(ctx, (ctr->cap + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, st,
+                           (Slot *)ctr->slots, ctr->cap);
+        KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, st));
+        if (n_t - gone) {
+            TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
+            hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(ctx, (n_t - gone + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, st,
+                               (const uint64_t *)live_keys, (const uint32_t *)live_counts, n_t - gone, t, ctr->distinct);
+        }
+        KT_HIP(hipGetLastError());
+    }
+    if (int rc = call.finish()) return rc;
+    if (n_erased) *n_erased = gone;
     return KT_OK;
 }
 

@@ -26,6 +26,16 @@
 //   g. emit      the same threads: every neighbour's index by stage b's search, its place and its unitig's length give
 //                (v, sv); the neighbour has to be first (+) or last (-) in a unitig that is no cycle, else ERR_LINK; the at
 //                most 5 values, sorted in registers, go to the end's offset.
+// kt_ctr_unitig_tips and kt_ctr_clip_tips run the linked stages into this call's scratch (offsets, count sums, flags and links;
+// no base is written) and go on:
+//   h. classes   one thread per unitig: short (no cycle, at most max_tip_nodes nodes) and dead at both ends (isolated), at one
+//                end (a candidate, and which end lives), or neither
+//   i. marks     the same threads: a candidate is a tip when every link of its live end arrives at an end that has another
+//                link to a unitig that beats it (no candidate, or a higher mean count as 128-bit products, then the lower
+//                number): at most 5 x 5 links; the tally summed per wave, one atomic per word
+//   j. list      kt_ctr_clip_tips only, one thread per node: its key where its unitig (stage d's place, ex_id) is marked
+//                for erasing, else KT_EMPTY_KEY - kt_ctr_erase skips those, so the list is not compacted; it goes to
+//                kt_ctr_erase as device memory, and the next round starts at stage a on what is left
 // Anything the rule excludes (a link without an answer, a neighbour that is no node, a chain that is neither a path nor a
 // cycle) raises a bit in the call's error word and comes back as an error: nothing spins.
 #include "kt_device.hpp"
@@ -478,21 +488,152 @@ dim3 blocks_for(uint64_t items, uint64_t per_block = BLOCK) { return dim3((uint3
 
 size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
-// both entry points; n_links null: kt_ctr_unitigs, which has no link outputs and runs no link stage
-int unitigs_body(const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
-                 uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
-                 uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to, uint64_t max_links, uint64_t *n_links, int mem) {
+// ---- h, i, j. tips ---------------------------------------------------------------------------------------------------
+
+// what the rule reads: the outputs of the linked run, on the device
+struct TipArgs {
+    const uint64_t *offsets, *count_sums;
+    const uint32_t *flags;
+    const uint64_t *link_offsets;
+    const uint32_t *link_to;
+    uint64_t nu;
+    uint32_t k, max_tip_nodes;
+};
+
+// the round's device words: tally[0..4) as kt_ctr_unitig_tips gives them, [4] the tips' and [5] the isolated unitigs' occurrences
+constexpr int TIP_WORDS = 6;
+constexpr uint8_t CLS_NONE = 0, CLS_LIVE_PLUS = 1, CLS_LIVE_MINUS = 2, CLS_ISOLATED = 3;
+
+// one tip round, as its callers ask for it and as it comes back
+struct TipRun {
+    uint32_t max_tip_nodes;
+    uint32_t erase_marks;           // kt_ctr_clip_tips: the marks (bits) whose nodes stage j lists; 0: no stage j
+    uint64_t nu = 0;                // unitigs
+    uint64_t tally[TIP_WORDS] = {};
+    const uint8_t *d_marks = nullptr;  // nu marks, in OUT
+    const uint64_t *d_words = nullptr; // the tally on the device
+    const uint64_t *d_list = nullptr;  // stage j: n_list keys, KT_EMPTY_KEY for a node that stays, in OUT
+    uint64_t n_list = 0;
+};
+
+__device__ __forceinline__ uint64_t nodes_of(const TipArgs &a, uint64_t u) { return a.offsets[u + 1] - a.offsets[u] - (a.k - 1u); }
+
+// h. one thread per unitig: short and dead at both ends (isolated), at one end (a candidate, and which end lives), or neither
+__global__ __launch_bounds__(BLOCK) void unitig_tip_class_kernel(TipArgs a, uint8_t *__restrict__ cls) {
+    const uint64_t u = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (u >= a.nu) return;
+    const bool is_short = !(a.flags[u] & KT_UNITIG_CIRCULAR) && nodes_of(a, u) <= (uint64_t)a.max_tip_nodes;
+    const uint64_t l0 = a.link_offsets[2 * u], l1 = a.link_offsets[2 * u + 1], l2 = a.link_offsets[2 * u + 2];
+    const bool plus = l1 > l0, minus = l2 > l1;
+    cls[u] = !is_short || (plus && minus) ? CLS_NONE : plus ? CLS_LIVE_PLUS : minus ? CLS_LIVE_MINUS : CLS_ISOLATED;
+}
+
+// w beats the candidate u: it is no candidate, or its mean count is higher (c_w / n_w > c_u / n_u as c_w n_u > c_u n_w in
+// 128 bits), or the means are equal and its number is lower
+__device__ __forceinline__ bool tip_beats(const TipArgs &a, const uint8_t *__restrict__ cls, uint64_t w, uint64_t u, uint64_t c_u,
+                                          uint64_t n_u) {
+    const uint8_t cw = cls[w];
+    if (cw != CLS_LIVE_PLUS && cw != CLS_LIVE_MINUS) return true;
+    const uint64_t c_w = a.count_sums[w], n_w = nodes_of(a, w);
+    const uint64_t lh = __umul64hi(c_w, n_u), ll = c_w * n_u, rh = __umul64hi(c_u, n_w), rl = c_u * n_w;
+    if (lh != rh) return lh > rh;
+    if (ll != rl) return ll > rl;
+    return w < u;
+}
+
+// i. one thread per unitig: a candidate is a tip when every link f of its live end e arrives at an end f ^ 1 that has
+// another link (not the mirror e ^ 1) to a unitig that beats it; marks and the tally
+__global__ __launch_bounds__(BLOCK) void unitig_tip_mark_kernel(TipArgs a, const uint8_t *__restrict__ cls, uint8_t *__restrict__ marks,
+                                                                unsigned long long *__restrict__ words) {
+    const uint64_t u = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint8_t c = u < a.nu ? cls[u] : CLS_NONE;  // (every lane stays for the wave's sums)
+    uint8_t mark = KT_TIP_KEEP;
+    if (c == CLS_ISOLATED) {
+        mark = KT_TIP_ISOLATED;
+    } else if (c != CLS_NONE) {
+        const uint64_t e = 2 * u + (c == CLS_LIVE_MINUS), c_u = a.count_sums[u], n_u = nodes_of(a, u);
+        bool tip = true;
+        for (uint64_t x = a.link_offsets[e]; tip && x < a.link_offsets[e + 1]; x++) {
+            const uint64_t g = (uint64_t)a.link_to[x] ^ 1ull;
+            bool beaten = false;
+            if (g < 2 * a.nu)
+                for (uint64_t y = a.link_offsets[g]; !beaten && y < a.link_offsets[g + 1]; y++) {
+                    const uint64_t h = a.link_to[y];
+                    beaten = h != (e ^ 1ull) && (h >> 1) < a.nu && tip_beats(a, cls, h >> 1, u, c_u, n_u);
+                }
+            tip = beaten;
+        }
+        if (tip) mark = KT_TIP_TIP;
+    }
+    if (u < a.nu) marks[u] = mark;
+    // the tally: summed over the wave, one atomic per word and wave that has something to add
+    const bool tipped = mark == KT_TIP_TIP, alone = mark == KT_TIP_ISOLATED;
+    const uint64_t nodes = mark != KT_TIP_KEEP ? nodes_of(a, u) : 0, occ = mark != KT_TIP_KEEP ? a.count_sums[u] : 0;
+    uint64_t v[TIP_WORDS] = {tipped, tipped ? nodes : 0, alone, alone ? nodes : 0, tipped ? occ : 0, alone ? occ : 0};
+#pragma unroll
+    for (int j = 0; j < TIP_WORDS; j++) {
+        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_down(v[j], o, 64);
+        if ((threadIdx.x & 63) == 0 && v[j]) atomicAdd(words + j, (unsigned long long)v[j]);
+    }
+}
+
+// j. one thread per node: its key where its unitig's mark is one of `erase_marks`, else KT_EMPTY_KEY (which kt_ctr_erase
+// skips: the list needs no compaction)
+__global__ __launch_bounds__(BLOCK) void unitig_tip_list_kernel(const uint64_t *__restrict__ keys, const uint2 *__restrict__ place,
+                                                                const uint32_t *__restrict__ ex_id, uint64_t n,
+                                                                const uint8_t *__restrict__ marks, uint64_t nu, uint32_t erase_marks,
+                                                                uint64_t *__restrict__ list) {
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t start = place[i].x;
+    const uint64_t u = start < n ? ex_id[start] : nu;
+    list[i] = u < nu && (marks[u] & erase_marks) ? keys[i] : KT_EMPTY_KEY;
+}
+
+// stages h to j behind a linked run, in OUT (the graph's sort has given it back): words | classes | marks | list
+int tip_stages(Call &call, kt_ctx *ctx, const TipArgs &a, const uint64_t *keys, const uint2 *place, const uint32_t *ex_id,
+               uint64_t n, TipRun *tr) {
+    hipStream_t st = ctx->stream;
+    const uint64_t nu = a.nu;
+    const size_t o_cls = align16(TIP_WORDS * 8), o_marks = o_cls + align16(nu), o_list = o_marks + align16(nu);
+    uint8_t *T = nullptr;
+    if (int rc = call.scratch(kt::OUT, o_list + (tr->erase_marks ? n * 8 : 0), &T)) return rc;
+    unsigned long long *words = (unsigned long long *)T;
+    uint8_t *cls = T + o_cls, *marks = T + o_marks;
+    uint64_t *list = (uint64_t *)(T + o_list);
+    KT_HIP(hipMemsetAsync(words, 0, TIP_WORDS * 8, st));
+    hipLaunchKernelGGL(unitig_tip_class_kernel, blocks_for(nu), dim3(BLOCK), 0, st, a, cls);
+    hipLaunchKernelGGL(unitig_tip_mark_kernel, blocks_for(nu), dim3(BLOCK), 0, st, a, (const uint8_t *)cls, marks, words);
+    if (tr->erase_marks)
+        hipLaunchKernelGGL(unitig_tip_list_kernel, blocks_for(n), dim3(BLOCK), 0, st, keys, place, ex_id, n, (const uint8_t *)marks, nu,
+                           tr->erase_marks, list);
+    KT_HIP(hipGetLastError());
+    KT_HIP(hipMemcpyAsync(tr->tally, words, TIP_WORDS * 8, hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    tr->nu = nu, tr->d_marks = marks, tr->d_words = (const uint64_t *)words;
+    if (tr->erase_marks) tr->d_list = list, tr->n_list = n;
+    return KT_OK;
+}
+
+// The entry points' one run of the stages, under the caller's `call`.  n_links null: kt_ctr_unitigs, which has no link outputs
+// and runs no link stage.  tr set (the tip calls; call is a device call, the output pointers are null): the linked run with
+// offsets, count sums, flags and links made in OFFSETS and no base written, then stages h to j.
+int unitigs_run(Call &call, const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases,
+                uint64_t max_bases, uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs,
+                uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to, uint64_t max_links,
+                uint64_t *n_links, TipRun *tr) {
     const bool linked = n_links != nullptr;
     kt_ctx *ctx = table->ctx;
-    Call call(ctx, mem, name);
     if (int rc = call.refuse_shard(table)) return rc;
     if (min_count == 0) return call.fail("min_count must be >= 1");
     if (min_count > max_count) return call.fail("min_count > max_count");
     if (int rc = call.enter()) return rc;
-    const bool store = max_bases || max_unitigs || max_links;
-    if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
-    if (linked && ((store && !link_offsets) || (max_links && !link_to))) return call.fail("null link output");
-    if (max_links && !max_unitigs) return call.fail("max_links > 0 with max_unitigs == 0");
+    const bool store = tr || max_bases || max_unitigs || max_links;
+    if (!tr) {
+        if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
+        if (linked && ((store && !link_offsets) || (max_links && !link_to))) return call.fail("null link output");
+        if (max_links && !max_unitigs) return call.fail("max_links > 0 with max_unitigs == 0");
+    }
     uint64_t n_t = 0;
     if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
     if (n_t > 0x7FFFFFFEull) return call.fail("a table of more than 2^31 - 2 entries (the oriented node states are u32)");
@@ -501,7 +642,7 @@ int unitigs_body(const char *name, kt_ctr *table, uint32_t min_count, uint32_t m
     auto nothing = [&]() -> int {
         *n_unitigs = 0, *n_bases = 0;
         if (linked) *n_links = 0;
-        if (!store) return KT_OK;
+        if (!store || tr) return KT_OK;
         if (call.host()) offsets[0] = 0;
         else KT_HIP(hipMemsetAsync(offsets, 0, 8, st));
         if (linked && call.host()) link_offsets[0] = 0;
@@ -608,9 +749,10 @@ int unitigs_body(const char *name, kt_ctr *table, uint32_t min_count, uint32_t m
     }
     *n_unitigs = h.n_unitigs, *n_bases = h.n_bases;
     if (!store) return KT_OK;
-    if (linked && (h.n_unitigs > max_unitigs || h.n_bases > max_bases || hl.n_links > max_links))
+    if (tr) max_unitigs = nu, max_links = hl.n_links;  // (everything is made, in this call's scratch; max_bases stays 0)
+    if (!tr && linked && (h.n_unitigs > max_unitigs || h.n_bases > max_bases || hl.n_links > max_links))
         return call.fail("max_unitigs, max_bases or max_links smaller than the result (*n_unitigs, *n_bases, *n_links)");
-    if (h.n_unitigs > max_unitigs || h.n_bases > max_bases)
+    if (!tr && (h.n_unitigs > max_unitigs || h.n_bases > max_bases))
         return call.fail("max_unitigs or max_bases smaller than the result (*n_unitigs, *n_bases)");
 
     // e. spelling (host: into OFFSETS = offsets | count sums | flags | bases | link offsets | links, copied back by finish())
@@ -619,18 +761,19 @@ int unitigs_body(const char *name, kt_ctr *table, uint32_t min_count, uint32_t m
     uint32_t *d_flags = flags;
     uint64_t *d_loff = link_offsets;
     uint32_t *d_lto = link_to;
-    if (call.host()) {
-        const size_t unlinked = (nu + 1) * 8 + nu * 8 + align16(nu * 4) + h.n_bases;
+    const uint64_t spelled = tr ? 0 : h.n_bases;  // a tip run reads lengths, count sums, flags and links: it writes no base
+    if (call.host() || tr) {
+        const size_t unlinked = (nu + 1) * 8 + nu * 8 + align16(nu * 4) + spelled;
         const size_t all = linked ? align16(unlinked) + (n_ends + 1) * 8 + hl.n_links * 4 : unlinked;
         if (int rc = call.scratch(kt::OFFSETS, all, &d_offsets)) return rc;
-        d_sums = count_sums ? d_offsets + nu + 1 : nullptr;
-        d_flags = flags ? (uint32_t *)(d_offsets + 2 * nu + 1) : nullptr;
+        d_sums = count_sums || tr ? d_offsets + nu + 1 : nullptr;
+        d_flags = flags || tr ? (uint32_t *)(d_offsets + 2 * nu + 1) : nullptr;
         d_bases = (uint8_t *)(d_offsets + 2 * nu + 1) + align16(nu * 4);
         d_loff = (uint64_t *)((uint8_t *)d_offsets + align16(unlinked));
         d_lto = (uint32_t *)(d_loff + n_ends + 1);
     }
     if (d_sums) KT_HIP(hipMemsetAsync(d_sums, 0, nu * 8, st));
-    const SpellArgs sp{keys, counts, place, slen, ex_id, ex_off, n, k, d_bases, d_offsets, d_sums, d_flags, h.n_bases, nu, w};
+    const SpellArgs sp{keys, counts, place, slen, ex_id, ex_off, n, k, d_bases, d_offsets, d_sums, d_flags, spelled, nu, w};
     hipLaunchKernelGGL(unitig_spell_kernel, blocks_for(n), dim3(BLOCK), 0, st, sp);
     KT_HIP(hipGetLastError());
     call.back(bases, (const uint8_t *)d_bases, h.n_bases);
@@ -653,6 +796,7 @@ int unitigs_body(const char *name, kt_ctr *table, uint32_t min_count, uint32_t m
         call.back(link_offsets, (const uint64_t *)d_loff, n_ends + 1);
         call.back(link_to, (const uint32_t *)d_lto, hl.n_links);
     }
+    if (tr) return tip_stages(call, ctx, TipArgs{d_offsets, d_sums, d_flags, d_loff, d_lto, nu, k, tr->max_tip_nodes}, keys, place, ex_id, n, tr);
     return call.finish();
 }
 
@@ -662,8 +806,9 @@ extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_co
                               uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs, uint64_t *n_unitigs,
                               uint64_t *n_bases, int mem) {
     if (!table || !n_unitigs || !n_bases) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs: null");
-    return unitigs_body("kt_ctr_unitigs", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags, max_unitigs,
-                        n_unitigs, n_bases, nullptr, nullptr, 0, nullptr, mem);
+    Call call(table->ctx, mem, "kt_ctr_unitigs");
+    return unitigs_run(call, "kt_ctr_unitigs", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags, max_unitigs,
+                       n_unitigs, n_bases, nullptr, nullptr, 0, nullptr, nullptr);
 }
 
 extern "C" int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
@@ -671,6 +816,79 @@ extern "C" int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t
                                      uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to,
                                      uint64_t max_links, uint64_t *n_links, int mem) {
     if (!table || !n_unitigs || !n_bases || !n_links) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs_linked: null");
-    return unitigs_body("kt_ctr_unitigs_linked", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags,
-                        max_unitigs, n_unitigs, n_bases, link_offsets, link_to, max_links, n_links, mem);
+    Call call(table->ctx, mem, "kt_ctr_unitigs_linked");
+    return unitigs_run(call, "kt_ctr_unitigs_linked", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags,
+                       max_unitigs, n_unitigs, n_bases, link_offsets, link_to, max_links, n_links, nullptr);
+}
+
+extern "C" int kt_ctr_unitig_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint8_t *marks,
+                                  uint64_t max_unitigs, uint64_t *n_unitigs, uint64_t *tally, int mem) {
+    if (!table || !n_unitigs) return kt::fail(KT_ERR_ARG, "kt_ctr_unitig_tips: null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, mem, "kt_ctr_unitig_tips");
+    if (int rc = call.enter()) return rc;
+    if (max_tip_nodes == 0) return call.fail("max_tip_nodes must be >= 1");
+    if (max_unitigs && !marks) return call.fail("null marks");
+    // the run works in device memory whatever `mem` is: only the marks and the tally go to the caller
+    Call run(ctx, KT_MEM_DEVICE, "kt_ctr_unitig_tips");
+    TipRun tr{max_tip_nodes, 0u};
+    uint64_t nu = 0, nb = 0, nl = 0;
+    if (int rc = unitigs_run(run, "kt_ctr_unitig_tips", table, min_count, max_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb,
+                             nullptr, nullptr, 0, &nl, &tr))
+        return rc;
+    *n_unitigs = tr.nu;
+    if (max_unitigs && max_unitigs < tr.nu) return call.fail("max_unitigs smaller than the result (*n_unitigs)");
+    if (call.host()) {
+        if (max_unitigs) call.back(marks, tr.d_marks, tr.nu);
+        if (tally)
+            for (int j = 0; j < KT_TIP_TALLY; j++) tally[j] = tr.tally[j];
+        return call.finish();
+    }
+    if (max_unitigs && tr.nu) KT_HIP(hipMemcpyAsync(marks, tr.d_marks, tr.nu, hipMemcpyDeviceToDevice, ctx->stream));
+    if (tally) {
+        if (tr.d_words) KT_HIP(hipMemcpyAsync(tally, tr.d_words, KT_TIP_TALLY * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        else KT_HIP(hipMemsetAsync(tally, 0, KT_TIP_TALLY * 8, ctx->stream));
+    }
+    return KT_OK;
+}
+
+extern "C" int kt_ctr_clip_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint32_t max_rounds,
+                                uint32_t flags, uint64_t *stats) {
+    if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_clip_tips: null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, KT_MEM_DEVICE, "kt_ctr_clip_tips");
+    if (max_tip_nodes == 0) return call.fail("max_tip_nodes must be >= 1");
+    if (max_rounds < 1 || max_rounds > 1024) return call.fail("max_rounds must be in 1..1024");
+    if (flags & ~KT_CLIP_ISOLATED) return call.fail("unknown flags");
+    const bool drop = flags & KT_CLIP_ISOLATED;
+    uint64_t s[KT_CLIP_STATS] = {};
+    auto leave = [&](int rc) {
+        if (stats)
+            for (int j = 0; j < KT_CLIP_STATS; j++) stats[j] = s[j];
+        return rc;
+    };
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        TipRun tr{max_tip_nodes, (uint32_t)KT_TIP_TIP | (drop ? (uint32_t)KT_TIP_ISOLATED : 0u)};
+        uint64_t nu = 0, nb = 0, nl = 0;
+        if (int rc = unitigs_run(call, "kt_ctr_clip_tips", table, min_count, max_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu,
+                                 &nb, nullptr, nullptr, 0, &nl, &tr))
+            return r ? leave(rc) : rc;  // (an argument the first round refuses leaves stats untouched, as every refusal does)
+        const uint64_t want = tr.tally[1] + (drop ? tr.tally[3] : 0);
+        if (!want) {
+            s[6] = 0;
+            break;
+        }
+        // the list (in OUT) is all the erase reads: the run's other buffers are its to take, behind the run's kernels on the stream
+        for (kt::Buf b : {kt::BASES, kt::OFFSETS, kt::AUX0, kt::AUX1, kt::AUX2}) ctx->unclaim(b);
+        uint64_t gone = 0;
+        if (int rc = kt_ctr_erase(table, tr.d_list, tr.n_list, &gone, KT_MEM_DEVICE)) return leave(rc);
+        s[0]++, s[1] += tr.tally[0], s[2] += tr.tally[1], s[5] += tr.tally[4];
+        if (drop) s[3] += tr.tally[2], s[4] += tr.tally[3], s[5] += tr.tally[5];
+        s[6] = 1;
+        if (gone != want)
+            return leave(kt::fail(KT_ERR_HIP, "kt_ctr_clip_tips: internal: the table held " + std::to_string(gone) + " of the " +
+                                                  std::to_string(want) + " nodes to erase"));
+        call.release();
+    }
+    return leave(KT_OK);
 }

@@ -18,6 +18,9 @@ from ._lib import KT_F32, KT_F64, KT_MEM_DEVICE, KT_MEM_HOST, KT_U32, check
 _DT = {"f64": KT_F64, "f32": KT_F32, "u32": KT_U32, np.float64: KT_F64, np.float32: KT_F32, np.uint32: KT_U32}
 _NP = {KT_F64: np.float64, KT_F32: np.float32, KT_U32: np.uint32}
 NO_KMER = 0xFFFFFFFF  # KT_NO_KMER: the entry of a profile where no k-mer starts
+TIP_KEEP, TIP_TIP, TIP_ISOLATED = 0, 1, 2  # Counter.unitig_tips' marks (KT_TIP_*)
+CLIP_ISOLATED = 1  # Counter.clip_tips(drop_isolated=True) (KT_CLIP_ISOLATED)
+CLIP_STATS_NAMES = ("rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "occurrences", "converged")
 
 
 def _ptr(x):
@@ -471,6 +474,18 @@ class Counter:
         if len(keys):
             self.add_pairs(keys, counts, len(keys), KT_MEM_HOST)
 
+    def erase(self, keys):
+        """removes the canonical k-mers `keys` (host u64) from the table in place; returns how many entries went
+        (kt_ctr_erase: absent keys, duplicates, KT_EMPTY_KEY and values >= 4^k are ignored)"""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        return self.erase_device(keys, len(keys), KT_MEM_HOST)
+
+    def erase_device(self, keys, n, mem=KT_MEM_DEVICE):
+        """erase() with the n keys in a device tensor (u64 bit patterns)"""
+        gone = C.c_uint64()
+        check(_lib.lib().kt_ctr_erase(self._h, _ptr(keys) if n else None, int(n), C.byref(gone), mem))
+        return gone.value
+
     def size(self):
         n = C.c_uint64()
         check(_lib.lib().kt_ctr_size(self._h, C.byref(n)))
@@ -761,6 +776,43 @@ class Counter:
                                                _ptr(count_sums), _ptr(flags), int(max_unitigs), C.byref(nu), C.byref(nb),
                                                _ptr(link_offsets), _ptr(link_to), int(max_links), C.byref(nl), KT_MEM_DEVICE))
         return nu.value, nb.value, nl.value
+
+    def unitig_tips(self, max_tip_nodes=None, min_count=1, max_count=None):
+        """One round of the tip rule over unitigs()' numbering (kt_ctr_unitig_tips; the table is not changed): returns (marks u8:
+        TIP_KEEP / TIP_TIP / TIP_ISOLATED per unitig, tally u64[4]: tips, their nodes, isolated short unitigs, their nodes).
+        max_tip_nodes None: k nodes.  A count-only call, then one call sized by it."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        tip = self.k if max_tip_nodes is None else int(max_tip_nodes)
+        nu = C.c_uint64()
+        tally = np.zeros(_lib.KT_TIP_TALLY, np.uint64)
+        check(_lib.lib().kt_ctr_unitig_tips(self._h, int(min_count), hi, tip, None, 0, C.byref(nu), _ptr(tally), KT_MEM_HOST))
+        marks = np.zeros(nu.value, np.uint8)
+        if nu.value:
+            check(_lib.lib().kt_ctr_unitig_tips(self._h, int(min_count), hi, tip, _ptr(marks), nu.value, C.byref(nu), _ptr(tally),
+                                                KT_MEM_HOST))
+        return marks, tally
+
+    def unitig_tips_device(self, marks, max_unitigs, tally=None, max_tip_nodes=None, min_count=1, max_count=None):
+        """unitig_tips into device tensors (marks u8 of max_unitigs, tally u64 bit patterns of 4 or None; None, 0 only counts
+        and still fills tally); returns n_unitigs.  Raises KmertoolsError (KT_ERR_ARG) when the room is too small."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        tip = self.k if max_tip_nodes is None else int(max_tip_nodes)
+        nu = C.c_uint64()
+        check(_lib.lib().kt_ctr_unitig_tips(self._h, int(min_count), hi, tip, _ptr(marks), int(max_unitigs), C.byref(nu),
+                                            _ptr(tally), KT_MEM_DEVICE))
+        return nu.value
+
+    def clip_tips(self, max_tip_nodes=None, max_rounds=8, drop_isolated=False, min_count=1, max_count=None):
+        """Clips the tips of the table's de Bruijn graph in place, round after round until a round finds none or max_rounds
+        are done (kt_ctr_clip_tips): the k-mers of every tip - with drop_isolated, of every isolated short unitig too - are
+        erased from the table.  max_tip_nodes None: k nodes.  Returns the stats as a dict (CLIP_STATS_NAMES)."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        tip = self.k if max_tip_nodes is None else int(max_tip_nodes)
+        stats = np.zeros(_lib.KT_CLIP_STATS, np.uint64)
+        check(_lib.lib().kt_ctr_clip_tips(self._h, int(min_count), hi, tip, int(max_rounds), CLIP_ISOLATED if drop_isolated else 0,
+                                          _ptr(stats)))
+        stats[6] = 1 - stats[6]  # (the call says whether the last round still erased something)
+        return {name: int(v) for name, v in zip(CLIP_STATS_NAMES, stats)}
 
     def export_stage_range(self, min_count=1, max_count=None):
         """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
