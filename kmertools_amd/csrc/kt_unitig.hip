@@ -38,6 +38,8 @@
 //                kt_ctr_erase as device memory, and the next round starts at stage a on what is left
 // Anything the rule excludes (a link without an answer, a neighbour that is no node, a chain that is neither a path nor a
 // cycle) raises a bit in the call's error word and comes back as an error: nothing spins.
+// On the host a call is a Run: its methods are the stages - nodes (a), chains (b to d), degrees (f), spell (e), emit (g),
+// tips (h to j) - and every entry point says which of them it runs, and into which Outputs.
 #include "kt_device.hpp"
 #include "kt_launch.hpp"
 
@@ -245,18 +247,31 @@ __device__ __forceinline__ void block_scan2(uint64_t &a, uint64_t &b, uint64_t (
 // a start node's unitig: 1 unitig, nodes + k - 1 bases
 __device__ __forceinline__ uint64_t bases_of(uint32_t sl, uint32_t k) { return sl ? (uint64_t)(sl & ~CIRC) + k - 1u : 0ull; }
 
-// tile t (SCAN_TILE nodes) -> tiles[2t] = its unitigs, tiles[2t + 1] = its bases
-__global__ __launch_bounds__(BLOCK) void unitig_tile_sum_kernel(const uint32_t *__restrict__ slen, uint64_t n, uint32_t k,
-                                                                uint64_t *__restrict__ tiles) {
+// The exclusive scan over n items, two sums at once, is written once over a functor F: word(i) is item i's one u32,
+// add(word, a, b) what it contributes to the two sums (word 0, the filler past n, contributes nothing), put(i, a, b) takes
+// the sums over the items before i, total() is thread 0's after the last put.  Three launches: the tiles' sums, one
+// workgroup over those, and the tiles again.
+
+// stage d, over nodes: (is start, bases) -> ex_id[i], ex_off[i] = unitigs and bases that start at nodes before i
+struct NodeScan {
+    const uint32_t *slen;
+    uint32_t k;
+    uint32_t *ex_id;
+    uint64_t *ex_off;
+    __device__ __forceinline__ uint32_t word(uint64_t i) const { return slen[i]; }
+    __device__ __forceinline__ void add(uint32_t sl, uint64_t &a, uint64_t &b) const { a += sl != 0u, b += bases_of(sl, k); }
+    __device__ __forceinline__ void put(uint64_t i, uint64_t a, uint64_t b) const { ex_id[i] = (uint32_t)a, ex_off[i] = b; }
+    __device__ __forceinline__ void total() const {}
+};
+
+// tile t (SCAN_TILE items) -> tiles[2t], tiles[2t + 1] = its two sums
+template <class F>
+__global__ __launch_bounds__(BLOCK) void unitig_tile_sum_kernel(F f, uint64_t n, uint64_t *__restrict__ tiles) {
     __shared__ uint64_t wsum[WAVES][2];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
     uint64_t a = 0, b = 0, ta, tb;
 #pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        const uint32_t sl = base + j < n ? slen[base + j] : 0u;
-        a += sl != 0u;
-        b += bases_of(sl, k);
-    }
+    for (uint32_t j = 0; j < SCAN_ITEMS; j++) f.add(base + j < n ? f.word(base + j) : 0u, a, b);
     block_scan2(a, b, wsum, &ta, &tb);
     if (threadIdx.x == 0) tiles[2ull * blockIdx.x] = ta, tiles[2ull * blockIdx.x + 1] = tb;
 }
@@ -278,29 +293,27 @@ __global__ __launch_bounds__(BLOCK) void unitig_tile_scan_kernel(uint64_t *__res
     if (threadIdx.x == 0) *sum_a = ca, *sum_b = cb;
 }
 
-// ex_id[i], ex_off[i] = unitigs and bases that start at nodes before i
-__global__ __launch_bounds__(BLOCK) void unitig_scan_apply_kernel(const uint32_t *__restrict__ slen, uint64_t n, uint32_t k,
-                                                                  const uint64_t *__restrict__ tiles, uint32_t *__restrict__ ex_id,
-                                                                  uint64_t *__restrict__ ex_off) {
+// every item's put(), from its tile's exclusive prefix in `tiles`
+template <class F>
+__global__ __launch_bounds__(BLOCK) void unitig_scan_apply_kernel(F f, uint64_t n, const uint64_t *__restrict__ tiles) {
     __shared__ uint64_t wsum[WAVES][2];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t sl[SCAN_ITEMS];
+    uint32_t v[SCAN_ITEMS];
     uint64_t a = 0, b = 0, ta, tb;
 #pragma unroll
     for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        sl[j] = base + j < n ? slen[base + j] : 0u;
-        a += sl[j] != 0u;
-        b += bases_of(sl[j], k);
+        v[j] = base + j < n ? f.word(base + j) : 0u;
+        f.add(v[j], a, b);
     }
     const uint64_t own_a = a, own_b = b;
     block_scan2(a, b, wsum, &ta, &tb);
     uint64_t ra = tiles[2ull * blockIdx.x] + a - own_a, rb = tiles[2ull * blockIdx.x + 1] + b - own_b;
 #pragma unroll
     for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        if (base + j < n) ex_id[base + j] = (uint32_t)ra, ex_off[base + j] = rb;
-        ra += sl[j] != 0u;
-        rb += bases_of(sl[j], k);
+        if (base + j < n) f.put(base + j, ra, rb);
+        f.add(v[j], ra, rb);
     }
+    if (blockIdx.x == 0 && threadIdx.x == 0) f.total();
 }
 
 // ---- e. spelling -----------------------------------------------------------------------------------------------------
@@ -441,42 +454,18 @@ __device__ __forceinline__ void unitig_end_links(const LinkArgs &a) {
 __global__ __launch_bounds__(BLOCK) void unitig_end_degree_kernel(LinkArgs a) { unitig_end_links<false>(a); }
 __global__ __launch_bounds__(BLOCK) void unitig_end_emit_kernel(LinkArgs a) { unitig_end_links<true>(a); }
 
-// tile t (SCAN_TILE ends) -> tiles[2t] = its links (tiles[2t + 1] = 0: the tile scan is stage d's)
-__global__ __launch_bounds__(BLOCK) void unitig_end_tile_sum_kernel(const uint32_t *__restrict__ deg, uint64_t n_ends,
-                                                                    uint64_t *__restrict__ tiles) {
-    __shared__ uint64_t wsum[WAVES][2];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t a = 0, b = 0, ta, tb;
-#pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) a += base + j < n_ends ? deg[base + j] : 0u;
-    block_scan2(a, b, wsum, &ta, &tb);
-    if (threadIdx.x == 0) tiles[2ull * blockIdx.x] = ta, tiles[2ull * blockIdx.x + 1] = tb;
-}
-
-// link_offsets[e] = the links of the ends before e; link_offsets[n_ends] = all of them
-__global__ __launch_bounds__(BLOCK) void unitig_end_scan_apply_kernel(const uint32_t *__restrict__ deg, uint64_t n_ends,
-                                                                      const uint64_t *__restrict__ tiles,
-                                                                      const LinkWords *__restrict__ lw,
-                                                                      uint64_t *__restrict__ link_offsets) {
-    __shared__ uint64_t wsum[WAVES][2];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t d[SCAN_ITEMS];
-    uint64_t a = 0, b = 0, ta, tb;
-#pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        d[j] = base + j < n_ends ? deg[base + j] : 0u;
-        a += d[j];
-    }
-    const uint64_t own = a;
-    block_scan2(a, b, wsum, &ta, &tb);
-    uint64_t r = tiles[2ull * blockIdx.x] + a - own;
-#pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        if (base + j < n_ends) link_offsets[base + j] = r;
-        r += d[j];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) link_offsets[n_ends] = lw->n_links;
-}
+// stage f / g, over ends: the degree -> link_offsets[e] = the links of the ends before e, link_offsets[n_ends] = all of them.
+// The second sum stays 0: block_scan2 and the one-workgroup tile scan are stage d's, and carry two.
+struct EndScan {
+    const uint32_t *deg;
+    uint64_t n_ends;
+    const LinkWords *lw;
+    uint64_t *link_offsets;
+    __device__ __forceinline__ uint32_t word(uint64_t e) const { return deg[e]; }
+    __device__ __forceinline__ void add(uint32_t d, uint64_t &a, uint64_t &) const { a += d; }
+    __device__ __forceinline__ void put(uint64_t e, uint64_t a, uint64_t) const { link_offsets[e] = a; }
+    __device__ __forceinline__ void total() const { link_offsets[n_ends] = lw->n_links; }
+};
 
 uint32_t ceil_log2(uint64_t x) {  // the smallest r with 2^r >= x
     uint32_t r = 0;
@@ -487,6 +476,23 @@ uint32_t ceil_log2(uint64_t x) {  // the smallest r with 2^r >= x
 dim3 blocks_for(uint64_t items, uint64_t per_block = BLOCK) { return dim3((uint32_t)((items + per_block - 1) / per_block)); }
 
 size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+// carve(call, buf, &a, count_a, &b, count_b, ...): one claim of a scratch buffer, cut into typed arrays that each take a
+// multiple of 16 bytes.  carve_parts: their bytes, and from `at`, where it is set, their places.
+size_t carve_parts(uint8_t *) { return 0; }
+template <class T, class... More>
+size_t carve_parts(uint8_t *at, T **p, uint64_t count, More... more) {
+    const size_t bytes = align16(count * sizeof(T));
+    if (at) *p = (T *)at;
+    return bytes + carve_parts(at ? at + bytes : at, more...);
+}
+template <class... Parts>
+int carve(Call &call, kt::Buf buf, Parts... parts) {
+    uint8_t *b = nullptr;
+    if (int rc = call.scratch(buf, carve_parts(nullptr, parts...), &b)) return rc;
+    carve_parts(b, parts...);
+    return KT_OK;
+}
 
 // ---- h, i, j. tips ---------------------------------------------------------------------------------------------------
 
@@ -510,9 +516,9 @@ struct TipRun {
     uint32_t erase_marks;           // kt_ctr_clip_tips: the marks (bits) whose nodes stage j lists; 0: no stage j
     uint64_t nu = 0;                // unitigs
     uint64_t tally[TIP_WORDS] = {};
-    const uint8_t *d_marks = nullptr;  // nu marks, in OUT
-    const uint64_t *d_words = nullptr; // the tally on the device
-    const uint64_t *d_list = nullptr;  // stage j: n_list keys, KT_EMPTY_KEY for a node that stays, in OUT
+    uint8_t *d_marks = nullptr;             // nu marks, in OUT
+    unsigned long long *d_words = nullptr;  // the tally on the device
+    uint64_t *d_list = nullptr;             // stage j: n_list keys, KT_EMPTY_KEY for a node that stays, in OUT
     uint64_t n_list = 0;
 };
 
@@ -590,214 +596,200 @@ __global__ __launch_bounds__(BLOCK) void unitig_tip_list_kernel(const uint64_t *
     list[i] = u < nu && (marks[u] & erase_marks) ? keys[i] : KT_EMPTY_KEY;
 }
 
-// stages h to j behind a linked run, in OUT (the graph's sort has given it back): words | classes | marks | list
-int tip_stages(Call &call, kt_ctx *ctx, const TipArgs &a, const uint64_t *keys, const uint2 *place, const uint32_t *ex_id,
-               uint64_t n, TipRun *tr) {
-    hipStream_t st = ctx->stream;
-    const uint64_t nu = a.nu;
-    const size_t o_cls = align16(TIP_WORDS * 8), o_marks = o_cls + align16(nu), o_list = o_marks + align16(nu);
-    uint8_t *T = nullptr;
-    if (int rc = call.scratch(kt::OUT, o_list + (tr->erase_marks ? n * 8 : 0), &T)) return rc;
-    unsigned long long *words = (unsigned long long *)T;
-    uint8_t *cls = T + o_cls, *marks = T + o_marks;
-    uint64_t *list = (uint64_t *)(T + o_list);
-    KT_HIP(hipMemsetAsync(words, 0, TIP_WORDS * 8, st));
-    hipLaunchKernelGGL(unitig_tip_class_kernel, blocks_for(nu), dim3(BLOCK), 0, st, a, cls);
-    hipLaunchKernelGGL(unitig_tip_mark_kernel, blocks_for(nu), dim3(BLOCK), 0, st, a, (const uint8_t *)cls, marks, words);
-    if (tr->erase_marks)
-        hipLaunchKernelGGL(unitig_tip_list_kernel, blocks_for(n), dim3(BLOCK), 0, st, keys, place, ex_id, n, (const uint8_t *)marks, nu,
-                           tr->erase_marks, list);
-    KT_HIP(hipGetLastError());
-    KT_HIP(hipMemcpyAsync(tr->tally, words, TIP_WORDS * 8, hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    tr->nu = nu, tr->d_marks = marks, tr->d_words = (const uint64_t *)words;
-    if (tr->erase_marks) tr->d_list = list, tr->n_list = n;
-    return KT_OK;
-}
+// ---- the stages on the host -------------------------------------------------------------------------------------------
 
-// The entry points' one run of the stages, under the caller's `call`.  n_links null: kt_ctr_unitigs, which has no link outputs
-// and runs no link stage.  tr set (the tip calls; call is a device call, the output pointers are null): the linked run with
-// offsets, count sums, flags and links made in OFFSETS and no base written, then stages h to j.
-int unitigs_run(Call &call, const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases,
-                uint64_t max_bases, uint64_t *offsets, uint64_t *count_sums, uint32_t *flags, uint64_t max_unitigs,
-                uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *link_offsets, uint32_t *link_to, uint64_t max_links,
-                uint64_t *n_links, TipRun *tr) {
-    const bool linked = n_links != nullptr;
-    kt_ctx *ctx = table->ctx;
-    if (int rc = call.refuse_shard(table)) return rc;
-    if (min_count == 0) return call.fail("min_count must be >= 1");
-    if (min_count > max_count) return call.fail("min_count > max_count");
-    if (int rc = call.enter()) return rc;
-    const bool store = tr || max_bases || max_unitigs || max_links;
-    if (!tr) {
-        if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
-        if (linked && ((store && !link_offsets) || (max_links && !link_to))) return call.fail("null link output");
-        if (max_links && !max_unitigs) return call.fail("max_links > 0 with max_unitigs == 0");
-    }
-    uint64_t n_t = 0;
-    if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
-    if (n_t > 0x7FFFFFFEull) return call.fail("a table of more than 2^31 - 2 entries (the oriented node states are u32)");
-    hipStream_t st = ctx->stream;
-    // no node: no unitig and no link, and offsets[0] = link_offsets[0] = 0 where there is room for them
-    auto nothing = [&]() -> int {
-        *n_unitigs = 0, *n_bases = 0;
-        if (linked) *n_links = 0;
-        if (!store || tr) return KT_OK;
-        if (call.host()) offsets[0] = 0;
-        else KT_HIP(hipMemsetAsync(offsets, 0, 8, st));
-        if (linked && call.host()) link_offsets[0] = 0;
-        else if (linked) KT_HIP(hipMemsetAsync(link_offsets, 0, 8, st));
-        return KT_OK;
-    };
-    if (!n_t) return nothing();
-
-    // a. the nodes, ascending by key, in this call's AUX1, with room for every entry of the table: 16 bytes an entry
-    // (kt_ctr_graph's sort takes OUT and AUX0)
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align16(bytes); return o; };
-    const size_t o_keys = take(n_t * 8), o_info = take(n_t * 4), o_counts = take(n_t * 4);
-    uint8_t *A = nullptr;
-    if (int rc = call.scratch(kt::AUX1, at, &A)) return rc;
-    uint64_t *keys = (uint64_t *)(A + o_keys);
-    uint32_t *info = (uint32_t *)(A + o_info), *counts = (uint32_t *)(A + o_counts);
-    uint64_t n = 0;
-    if (int rc = kt_ctr_graph(table, min_count, max_count, keys, info, counts, n_t, &n, nullptr, KT_MEM_DEVICE, 1)) return rc;
-    if (!n) return nothing();
-    // what the later stages keep per node, in AUX2: 64 bytes a node (the cycle stages: 48 more, in BASES)
-    const uint64_t T_n = (n + SCAN_TILE - 1) / SCAN_TILE;
-    at = 0;
-    const size_t o_words = take(sizeof(Words)), o_link = take(n * 8), o_ra = take(n * 16), o_rb = take(n * 16), o_place = take(n * 8),
-                 o_slen = take(n * 4), o_exid = take(n * 4), o_exoff = take(n * 8), o_tiles = take(T_n * 16);
-    uint8_t *S = nullptr;
-    if (int rc = call.scratch(kt::AUX2, at, &S)) return rc;
-    Words *w = (Words *)(S + o_words);
-    uint64_t *ra = (uint64_t *)(S + o_ra), *rb = (uint64_t *)(S + o_rb), *ex_off = (uint64_t *)(S + o_exoff),
-             *tiles = (uint64_t *)(S + o_tiles);
-    uint32_t *link = (uint32_t *)(S + o_link), *slen = (uint32_t *)(S + o_slen), *ex_id = (uint32_t *)(S + o_exid);
-    uint2 *place = (uint2 *)(S + o_place);
-    const uint64_t m = 2 * n, T = (n + SCAN_TILE - 1) / SCAN_TILE;
-    const uint32_t k = (uint32_t)table->k;
-    KT_HIP(hipMemsetAsync(w, 0, sizeof(Words), st));
-
-    // b. links
-    hipLaunchKernelGGL(unitig_link_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)keys, (const uint32_t *)info, n, k, link, w);
-    // c. ranking: a number of rounds fixed by n
-    hipLaunchKernelGGL(unitig_rank_init_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint32_t *)link, m, ra, w);
-    const uint32_t rounds = ceil_log2(m) + 1u;
-    for (uint32_t r = 0; r < rounds; r++) {
-        hipLaunchKernelGGL(unitig_rank_jump_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)ra, m, rb);
-        uint64_t *t = ra;
-        ra = rb, rb = t;
-    }
-    hipLaunchKernelGGL(unitig_unresolved_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link, m, w);
-    KT_HIP(hipGetLastError());
-    Words h;
-    KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    uint64_t *cval = nullptr;
-    if (h.unresolved && !h.err) {  // cycles: the smallest state of each, and every state's distance to it
-        uint8_t *C = nullptr;
-        if (int rc = call.scratch(kt::BASES, align16(m * 8) * 2 + align16(m * 4) * 2, &C)) return rc;
-        uint64_t *va = (uint64_t *)C, *vb = (uint64_t *)(C + align16(m * 8));
-        uint32_t *na = (uint32_t *)(C + 2 * align16(m * 8)), *nc = (uint32_t *)(C + 2 * align16(m * 8) + align16(m * 4));
-        hipLaunchKernelGGL(unitig_cycle_init_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link, m, va, na);
-        const uint32_t crounds = ceil_log2(n);
-        for (uint32_t r = 0; r < crounds; r++) {
-            hipLaunchKernelGGL(unitig_cycle_jump_kernel, blocks_for(m), dim3(BLOCK), 0, st, (const uint64_t *)va, (const uint32_t *)na, m,
-                               1ull << r, vb, nc);
-            uint64_t *tv = va;
-            va = vb, vb = tv;
-            uint32_t *tn = na;
-            na = nc, nc = tn;
-        }
-        cval = va;
-    }
-    // d. placing, ids and offsets
-    hipLaunchKernelGGL(unitig_place_kernel, blocks_for(n), dim3(BLOCK), 0, st, (const uint64_t *)ra, (const uint32_t *)link,
-                       (const uint64_t *)cval, n, place, slen, w);
-    hipLaunchKernelGGL(unitig_tile_sum_kernel, dim3((uint32_t)T), dim3(BLOCK), 0, st, (const uint32_t *)slen, n, k, tiles);
-    hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), dim3(BLOCK), 0, st, tiles, T, &w->n_unitigs, &w->n_bases);
-    hipLaunchKernelGGL(unitig_scan_apply_kernel, dim3((uint32_t)T), dim3(BLOCK), 0, st, (const uint32_t *)slen, n, k,
-                       (const uint64_t *)tiles, ex_id, ex_off);
-    KT_HIP(hipGetLastError());
-    KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    if (h.err)
-        return kt::fail(KT_ERR_HIP, std::string(name) + ": internal: the nodes' links do not form paths and cycles (error bits " +
-                                        std::to_string(h.err) + ")");
-    const uint64_t nu = h.n_unitigs;
-    // f. the ends' degrees and their sum, in AUX0 (the graph's sort has given it back): 8 bytes a unitig
-    const uint64_t n_ends = 2 * nu, T_e = (n_ends + SCAN_TILE - 1) / SCAN_TILE;
-    LinkArgs la{keys, info, place, slen, ex_id, n, n_ends, k, nullptr, nullptr, nullptr, 0, w};
-    uint64_t *ltiles = nullptr;
-    LinkWords *lw = nullptr;
-    LinkWords hl{0, 0};
-    if (linked) {
-        at = 0;
-        const size_t o_lw = take(sizeof(LinkWords)), o_deg = take(n_ends * 4), o_lt = take(T_e * 16);
-        uint8_t *D = nullptr;
-        if (int rc = call.scratch(kt::AUX0, at, &D)) return rc;
-        lw = (LinkWords *)(D + o_lw), la.deg = (uint32_t *)(D + o_deg), ltiles = (uint64_t *)(D + o_lt);
-        KT_HIP(hipMemsetAsync(D, 0, o_lt, st));
-        hipLaunchKernelGGL(unitig_end_degree_kernel, blocks_for(m), dim3(BLOCK), 0, st, la);
-        hipLaunchKernelGGL(unitig_end_tile_sum_kernel, dim3((uint32_t)T_e), dim3(BLOCK), 0, st, (const uint32_t *)la.deg, n_ends, ltiles);
-        hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), dim3(BLOCK), 0, st, ltiles, T_e, &lw->n_links, &lw->unused);
-        KT_HIP(hipGetLastError());
-        KT_HIP(hipMemcpyAsync(&hl, lw, sizeof(LinkWords), hipMemcpyDeviceToHost, st));
-        KT_HIP(hipStreamSynchronize(st));
-        *n_links = hl.n_links;
-    }
-    *n_unitigs = h.n_unitigs, *n_bases = h.n_bases;
-    if (!store) return KT_OK;
-    if (tr) max_unitigs = nu, max_links = hl.n_links;  // (everything is made, in this call's scratch; max_bases stays 0)
-    if (!tr && linked && (h.n_unitigs > max_unitigs || h.n_bases > max_bases || hl.n_links > max_links))
-        return call.fail("max_unitigs, max_bases or max_links smaller than the result (*n_unitigs, *n_bases, *n_links)");
-    if (!tr && (h.n_unitigs > max_unitigs || h.n_bases > max_bases))
-        return call.fail("max_unitigs or max_bases smaller than the result (*n_unitigs, *n_bases)");
-
-    // e. spelling (host: into OFFSETS = offsets | count sums | flags | bases | link offsets | links, copied back by finish())
-    uint8_t *d_bases = bases;
-    uint64_t *d_offsets = offsets, *d_sums = count_sums;
-    uint32_t *d_flags = flags;
-    uint64_t *d_loff = link_offsets;
-    uint32_t *d_lto = link_to;
-    const uint64_t spelled = tr ? 0 : h.n_bases;  // a tip run reads lengths, count sums, flags and links: it writes no base
-    if (call.host() || tr) {
+// where stages e and g write, on the device; max_bases = the bases there is room for (0: none is spelled)
+struct Outputs {
+    uint8_t *bases;
+    uint64_t *offsets, *count_sums;
+    uint32_t *flags;
+    uint64_t *link_offsets;
+    uint32_t *link_to;
+    uint64_t max_bases;
+    // all six made in OFFSETS = offsets | count sums | flags | bases | link offsets | links (n_ends 0: no link arrays)
+    int carve(Call &call, uint64_t nu, uint64_t spelled, uint64_t n_ends, uint64_t n_links) {
         const size_t unlinked = (nu + 1) * 8 + nu * 8 + align16(nu * 4) + spelled;
-        const size_t all = linked ? align16(unlinked) + (n_ends + 1) * 8 + hl.n_links * 4 : unlinked;
-        if (int rc = call.scratch(kt::OFFSETS, all, &d_offsets)) return rc;
-        d_sums = count_sums || tr ? d_offsets + nu + 1 : nullptr;
-        d_flags = flags || tr ? (uint32_t *)(d_offsets + 2 * nu + 1) : nullptr;
-        d_bases = (uint8_t *)(d_offsets + 2 * nu + 1) + align16(nu * 4);
-        d_loff = (uint64_t *)((uint8_t *)d_offsets + align16(unlinked));
-        d_lto = (uint32_t *)(d_loff + n_ends + 1);
+        if (int rc = call.scratch(kt::OFFSETS, n_ends ? align16(unlinked) + (n_ends + 1) * 8 + n_links * 4 : unlinked, &offsets)) return rc;
+        count_sums = offsets + nu + 1;
+        flags = (uint32_t *)(offsets + 2 * nu + 1);
+        bases = (uint8_t *)flags + align16(nu * 4);
+        link_offsets = (uint64_t *)((uint8_t *)offsets + align16(unlinked));
+        link_to = (uint32_t *)(link_offsets + n_ends + 1);
+        max_bases = spelled;
+        return KT_OK;
     }
-    if (d_sums) KT_HIP(hipMemsetAsync(d_sums, 0, nu * 8, st));
-    const SpellArgs sp{keys, counts, place, slen, ex_id, ex_off, n, k, d_bases, d_offsets, d_sums, d_flags, spelled, nu, w};
-    hipLaunchKernelGGL(unitig_spell_kernel, blocks_for(n), dim3(BLOCK), 0, st, sp);
-    KT_HIP(hipGetLastError());
-    call.back(bases, (const uint8_t *)d_bases, h.n_bases);
-    call.back(offsets, (const uint64_t *)d_offsets, nu + 1);
-    call.back(count_sums, (const uint64_t *)d_sums, nu);
-    call.back(flags, (const uint32_t *)d_flags, nu);
-    if (linked) {
-        // g. the offsets from the degrees, then the links; the one thing left to learn is whether every neighbour stood
-        // where the rule puts it
-        la.link_offsets = d_loff, la.link_to = d_lto, la.max_links = hl.n_links;
-        hipLaunchKernelGGL(unitig_end_scan_apply_kernel, dim3((uint32_t)T_e), dim3(BLOCK), 0, st, (const uint32_t *)la.deg, n_ends,
-                           (const uint64_t *)ltiles, (const LinkWords *)lw, d_loff);
-        if (hl.n_links) hipLaunchKernelGGL(unitig_end_emit_kernel, blocks_for(m), dim3(BLOCK), 0, st, la);
+};
+
+// One run of the stages under an entry point's `call`: a method is a stage, and leaves here and on the device what the later
+// ones read.  The entry points below say which stages they run.
+struct Run {
+    Call &call;
+    const char *name;
+    kt_ctr *table;
+    uint32_t min_count, max_count;
+    hipStream_t st = table->ctx->stream;
+    uint32_t k = (uint32_t)table->k;
+    // a: the nodes, ascending by key, in AUX1 (16 bytes an entry of the table)
+    uint64_t *keys = nullptr, n = 0;
+    uint32_t *info = nullptr, *counts = nullptr;
+    // b to d: what the later stages keep per node, in AUX2 (64 bytes a node), and the call's words as last read back
+    Words *w = nullptr, h{};
+    uint32_t *link = nullptr, *slen = nullptr, *ex_id = nullptr;
+    uint2 *place = nullptr;
+    uint64_t *ex_off = nullptr, *tiles = nullptr, nu = 0, n_bases = 0;
+    // f: the link words, the ends' degrees and their tiles, in AUX0 (8 bytes a unitig)
+    LinkWords *lw = nullptr;
+    uint32_t *deg = nullptr;
+    uint64_t *ltiles = nullptr, n_ends = 0, n_links = 0;
+
+    // the checks every entry point makes first
+    int begin() {
+        if (int rc = call.refuse_shard(table)) return rc;
+        if (min_count == 0) return call.fail("min_count must be >= 1");
+        if (min_count > max_count) return call.fail("min_count > max_count");
+        return call.enter();
+    }
+    // a read-back behind everything queued so far, and a wait for it
+    int fetch(void *host, const void *dev, size_t bytes) {
         KT_HIP(hipGetLastError());
-        KT_HIP(hipMemcpyAsync(&h, w, sizeof(Words), hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
         KT_HIP(hipStreamSynchronize(st));
-        if (h.err)
-            return kt::fail(KT_ERR_HIP, std::string(name) + ": internal: a unitig end's neighbour is not at an end of its own "
-                                                            "unitig (error bits " + std::to_string(h.err) + ")");
-        call.back(link_offsets, (const uint64_t *)d_loff, n_ends + 1);
-        call.back(link_to, (const uint32_t *)d_lto, hl.n_links);
+        return KT_OK;
     }
-    if (tr) return tip_stages(call, ctx, TipArgs{d_offsets, d_sums, d_flags, d_loff, d_lto, nu, k, tr->max_tip_nodes}, keys, place, ex_id, n, tr);
-    return call.finish();
+    // ... of the words: an error bit in them is the call's error, `what` its text
+    int check_words(const char *what) {
+        if (int rc = fetch(&h, w, sizeof(Words))) return rc;
+        return h.err ? kt::fail(KT_ERR_HIP, std::string(name) + ": internal: " + what + " (error bits " + std::to_string(h.err) + ")") : KT_OK;
+    }
+    // a. n = 0: no node, and for an empty table nothing claimed or launched (kt_ctr_graph's sort takes OUT and AUX0)
+    int nodes() {
+        uint64_t n_t = 0;
+        if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
+        if (n_t > 0x7FFFFFFEull) return call.fail("a table of more than 2^31 - 2 entries (the oriented node states are u32)");
+        if (!n_t) return KT_OK;
+        if (int rc = carve(call, kt::AUX1, &keys, n_t, &info, n_t, &counts, n_t)) return rc;
+        return kt_ctr_graph(table, min_count, max_count, keys, info, counts, n_t, &n, nullptr, KT_MEM_DEVICE, 1);
+    }
+    // b to d, for n > 0: nu and n_bases
+    int chains() {
+        const uint64_t m = 2 * n;
+        const dim3 M = blocks_for(m), T = blocks_for(n, SCAN_TILE), B(BLOCK);
+        uint64_t *ra = nullptr, *rb = nullptr;
+        if (int rc = carve(call, kt::AUX2, &w, 1, &link, m, &ra, m, &rb, m, &place, n, &slen, n, &ex_id, n, &ex_off, n, &tiles, 2ull * T.x))
+            return rc;
+        KT_HIP(hipMemsetAsync(w, 0, sizeof(Words), st));
+        // b. links
+        hipLaunchKernelGGL(unitig_link_kernel, M, B, 0, st, keys, info, n, k, link, w);
+        // c. ranking: a number of rounds fixed by n
+        hipLaunchKernelGGL(unitig_rank_init_kernel, M, B, 0, st, link, m, ra, w);
+        for (uint32_t r = 0, rounds = ceil_log2(m) + 1u; r < rounds; r++) {
+            hipLaunchKernelGGL(unitig_rank_jump_kernel, M, B, 0, st, ra, m, rb);
+            std::swap(ra, rb);
+        }
+        hipLaunchKernelGGL(unitig_unresolved_kernel, M, B, 0, st, ra, link, m, w);
+        if (int rc = fetch(&h, w, sizeof(Words))) return rc;
+        uint64_t *cval = nullptr;
+        if (h.unresolved && !h.err) {  // cycles: the smallest state of each, and every state's distance to it, in BASES (48 bytes a node)
+            uint64_t *vb = nullptr;
+            uint32_t *na = nullptr, *nc = nullptr;
+            if (int rc = carve(call, kt::BASES, &cval, m, &vb, m, &na, m, &nc, m)) return rc;
+            hipLaunchKernelGGL(unitig_cycle_init_kernel, M, B, 0, st, ra, link, m, cval, na);
+            for (uint32_t r = 0, rounds = ceil_log2(n); r < rounds; r++) {
+                hipLaunchKernelGGL(unitig_cycle_jump_kernel, M, B, 0, st, cval, na, m, 1ull << r, vb, nc);
+                std::swap(cval, vb), std::swap(na, nc);
+            }
+        }
+        // d. placing, ids and offsets
+        hipLaunchKernelGGL(unitig_place_kernel, blocks_for(n), B, 0, st, ra, link, cval, n, place, slen, w);
+        const NodeScan scan{slen, k, ex_id, ex_off};
+        hipLaunchKernelGGL(unitig_tile_sum_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
+        hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), B, 0, st, tiles, (uint64_t)T.x, &w->n_unitigs, &w->n_bases);
+        hipLaunchKernelGGL(unitig_scan_apply_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
+        if (int rc = check_words("the nodes' links do not form paths and cycles")) return rc;
+        nu = h.n_unitigs, n_bases = h.n_bases;
+        return KT_OK;
+    }
+    // f. the ends' degrees and their sum (the graph's sort has given AUX0 back): n_ends and n_links
+    int degrees() {
+        n_ends = 2 * nu;
+        const dim3 T = blocks_for(n_ends, SCAN_TILE), B(BLOCK);
+        if (int rc = carve(call, kt::AUX0, &lw, 1, &deg, n_ends, &ltiles, 2ull * T.x)) return rc;
+        KT_HIP(hipMemsetAsync(lw, 0, (uint8_t *)ltiles - (uint8_t *)lw, st));
+        hipLaunchKernelGGL(unitig_end_degree_kernel, blocks_for(2 * n), B, 0, st, link_args(Outputs{}));
+        hipLaunchKernelGGL(unitig_tile_sum_kernel<EndScan>, T, B, 0, st, EndScan{deg, n_ends, lw, nullptr}, n_ends, ltiles);
+        hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), B, 0, st, ltiles, (uint64_t)T.x, &lw->n_links, &lw->unused);
+        return fetch(&n_links, &lw->n_links, 8);
+    }
+    LinkArgs link_args(const Outputs &o) const {  // (f writes deg and reads no output; max_links guards g's stores)
+        return LinkArgs{keys, info, place, slen, ex_id, n, n_ends, k, deg, o.link_offsets, o.link_to, n_links, w};
+    }
+    // host: e and g write into arrays made in OFFSETS instead of the caller's (*o as it comes), the optional ones only where the
+    // caller has one, and finish() copies them there
+    int stage(Outputs *o) {
+        if (!call.host()) return KT_OK;
+        const Outputs user = *o;
+        if (int rc = o->carve(call, nu, n_bases, n_ends, n_links)) return rc;
+        if (!user.count_sums) o->count_sums = nullptr;
+        if (!user.flags) o->flags = nullptr;
+        call.back(user.bases, o->bases, n_bases), call.back(user.offsets, o->offsets, nu + 1);
+        call.back(user.count_sums, o->count_sums, nu), call.back(user.flags, o->flags, nu);
+        call.back(user.link_offsets, o->link_offsets, n_ends + 1), call.back(user.link_to, o->link_to, n_links);
+        return KT_OK;
+    }
+    // e. spelling (max_bases and nu guard the stores: the entry points launch this only when everything fits)
+    int spell(const Outputs &o) {
+        if (o.count_sums) KT_HIP(hipMemsetAsync(o.count_sums, 0, nu * 8, st));
+        const SpellArgs sp{keys, counts, place, slen, ex_id, ex_off, n, k, o.bases, o.offsets, o.count_sums, o.flags, o.max_bases, nu, w};
+        hipLaunchKernelGGL(unitig_spell_kernel, blocks_for(n), dim3(BLOCK), 0, st, sp);
+        KT_HIP(hipGetLastError());
+        return KT_OK;
+    }
+    // g. the offsets from the degrees, then the links; the one thing left to learn is whether every neighbour stood where the
+    // rule puts it
+    int emit(const Outputs &o) {
+        const EndScan scan{deg, n_ends, lw, o.link_offsets};
+        hipLaunchKernelGGL(unitig_scan_apply_kernel<EndScan>, blocks_for(n_ends, SCAN_TILE), dim3(BLOCK), 0, st, scan, n_ends, ltiles);
+        if (n_links) hipLaunchKernelGGL(unitig_end_emit_kernel, blocks_for(2 * n), dim3(BLOCK), 0, st, link_args(o));
+        return check_words("a unitig end's neighbour is not at an end of its own unitig");
+    }
+    // no node: offsets[0] and link_offsets[0] = 0, in a call that has room for them
+    int zero(std::initializer_list<uint64_t *> firsts) {
+        for (uint64_t *first : firsts)
+            if (call.host()) *first = 0;
+            else KT_HIP(hipMemsetAsync(first, 0, 8, st));
+        return KT_OK;
+    }
+    // h to j behind e and g, in OUT (the graph's sort has given it back): words | classes | marks | list
+    int tips(const Outputs &o, TipRun *tip) {
+        const TipArgs a{o.offsets, o.count_sums, o.flags, o.link_offsets, o.link_to, nu, k, tip->max_tip_nodes};
+        const dim3 U = blocks_for(nu), B(BLOCK);
+        uint8_t *cls = nullptr;
+        tip->nu = nu, tip->n_list = tip->erase_marks ? n : 0;
+        if (int rc = carve(call, kt::OUT, &tip->d_words, TIP_WORDS, &cls, nu, &tip->d_marks, nu, &tip->d_list, tip->n_list)) return rc;
+        KT_HIP(hipMemsetAsync(tip->d_words, 0, TIP_WORDS * 8, st));
+        hipLaunchKernelGGL(unitig_tip_class_kernel, U, B, 0, st, a, cls);
+        hipLaunchKernelGGL(unitig_tip_mark_kernel, U, B, 0, st, a, cls, tip->d_marks, tip->d_words);
+        if (tip->n_list)
+            hipLaunchKernelGGL(unitig_tip_list_kernel, blocks_for(n), B, 0, st, keys, place, ex_id, n, tip->d_marks, nu, tip->erase_marks,
+                               tip->d_list);
+        return fetch(tip->tally, tip->d_words, TIP_WORDS * 8);
+    }
+};
+
+// One tip round under the device call `call`: the linked stages with offsets, count sums, flags and links made in OFFSETS and
+// no base written, then h to j.  No node: *tip as it came.
+int tip_round(Call &call, const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, TipRun *tip) {
+    Run r{call, name, table, min_count, max_count};
+    if (int rc = r.begin()) return rc;
+    if (int rc = r.nodes()) return rc;
+    if (!r.n) return KT_OK;
+    if (int rc = r.chains()) return rc;
+    if (int rc = r.degrees()) return rc;
+    Outputs o{};
+    if (int rc = o.carve(call, r.nu, 0, r.n_ends, r.n_links)) return rc;
+    if (int rc = r.spell(o)) return rc;
+    if (int rc = r.emit(o)) return rc;
+    return r.tips(o, tip);
 }
 
 }  // namespace
@@ -807,8 +799,22 @@ extern "C" int kt_ctr_unitigs(kt_ctr *table, uint32_t min_count, uint32_t max_co
                               uint64_t *n_bases, int mem) {
     if (!table || !n_unitigs || !n_bases) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs: null");
     Call call(table->ctx, mem, "kt_ctr_unitigs");
-    return unitigs_run(call, "kt_ctr_unitigs", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags, max_unitigs,
-                       n_unitigs, n_bases, nullptr, nullptr, 0, nullptr, nullptr);
+    Run r{call, "kt_ctr_unitigs", table, min_count, max_count};
+    if (int rc = r.begin()) return rc;
+    const bool store = max_bases || max_unitigs;
+    if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
+    if (int rc = r.nodes()) return rc;
+    if (r.n)
+        if (int rc = r.chains()) return rc;
+    *n_unitigs = r.nu, *n_bases = r.n_bases;
+    if (!store) return KT_OK;
+    if (!r.n) return r.zero({offsets});
+    if (r.nu > max_unitigs || r.n_bases > max_bases)
+        return call.fail("max_unitigs or max_bases smaller than the result (*n_unitigs, *n_bases)");
+    Outputs o{bases, offsets, count_sums, flags, nullptr, nullptr, r.n_bases};
+    if (int rc = r.stage(&o)) return rc;
+    if (int rc = r.spell(o)) return rc;
+    return call.finish();
 }
 
 extern "C" int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint8_t *bases, uint64_t max_bases,
@@ -817,8 +823,27 @@ extern "C" int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t
                                      uint64_t max_links, uint64_t *n_links, int mem) {
     if (!table || !n_unitigs || !n_bases || !n_links) return kt::fail(KT_ERR_ARG, "kt_ctr_unitigs_linked: null");
     Call call(table->ctx, mem, "kt_ctr_unitigs_linked");
-    return unitigs_run(call, "kt_ctr_unitigs_linked", table, min_count, max_count, bases, max_bases, offsets, count_sums, flags,
-                       max_unitigs, n_unitigs, n_bases, link_offsets, link_to, max_links, n_links, nullptr);
+    Run r{call, "kt_ctr_unitigs_linked", table, min_count, max_count};
+    if (int rc = r.begin()) return rc;
+    const bool store = max_bases || max_unitigs || max_links;
+    if ((max_bases && !bases) || (store && !offsets)) return call.fail("null output");
+    if ((store && !link_offsets) || (max_links && !link_to)) return call.fail("null link output");
+    if (max_links && !max_unitigs) return call.fail("max_links > 0 with max_unitigs == 0");
+    if (int rc = r.nodes()) return rc;
+    if (r.n) {
+        if (int rc = r.chains()) return rc;
+        if (int rc = r.degrees()) return rc;
+    }
+    *n_unitigs = r.nu, *n_bases = r.n_bases, *n_links = r.n_links;
+    if (!store) return KT_OK;
+    if (!r.n) return r.zero({offsets, link_offsets});
+    if (r.nu > max_unitigs || r.n_bases > max_bases || r.n_links > max_links)
+        return call.fail("max_unitigs, max_bases or max_links smaller than the result (*n_unitigs, *n_bases, *n_links)");
+    Outputs o{bases, offsets, count_sums, flags, link_offsets, link_to, r.n_bases};
+    if (int rc = r.stage(&o)) return rc;
+    if (int rc = r.spell(o)) return rc;
+    if (int rc = r.emit(o)) return rc;
+    return call.finish();
 }
 
 extern "C" int kt_ctr_unitig_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint8_t *marks,
@@ -832,10 +857,7 @@ extern "C" int kt_ctr_unitig_tips(kt_ctr *table, uint32_t min_count, uint32_t ma
     // the run works in device memory whatever `mem` is: only the marks and the tally go to the caller
     Call run(ctx, KT_MEM_DEVICE, "kt_ctr_unitig_tips");
     TipRun tr{max_tip_nodes, 0u};
-    uint64_t nu = 0, nb = 0, nl = 0;
-    if (int rc = unitigs_run(run, "kt_ctr_unitig_tips", table, min_count, max_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb,
-                             nullptr, nullptr, 0, &nl, &tr))
-        return rc;
+    if (int rc = tip_round(run, "kt_ctr_unitig_tips", table, min_count, max_count, &tr)) return rc;
     *n_unitigs = tr.nu;
     if (max_unitigs && max_unitigs < tr.nu) return call.fail("max_unitigs smaller than the result (*n_unitigs)");
     if (call.host()) {
@@ -869,9 +891,7 @@ extern "C" int kt_ctr_clip_tips(kt_ctr *table, uint32_t min_count, uint32_t max_
     };
     for (uint32_t r = 0; r < max_rounds; r++) {
         TipRun tr{max_tip_nodes, (uint32_t)KT_TIP_TIP | (drop ? (uint32_t)KT_TIP_ISOLATED : 0u)};
-        uint64_t nu = 0, nb = 0, nl = 0;
-        if (int rc = unitigs_run(call, "kt_ctr_clip_tips", table, min_count, max_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu,
-                                 &nb, nullptr, nullptr, 0, &nl, &tr))
+        if (int rc = tip_round(call, "kt_ctr_clip_tips", table, min_count, max_count, &tr))
             return r ? leave(rc) : rc;  // (an argument the first round refuses leaves stats untouched, as every refusal does)
         const uint64_t want = tr.tally[1] + (drop ? tr.tally[3] : 0);
         if (!want) {

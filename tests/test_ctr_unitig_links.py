@@ -3,8 +3,8 @@ test_ctr_unitig_links_cli_args.py pins, on the CPU, to worked answers and to its
 kinds - the worked answers, every k that takes another path with several count ranges, small k where palindromes, ends of 5
 links and links that are their own mirror occur, unitig counts on either side of one scan tile and of the one-workgroup tile
 scan's first round, one path and one cycle longer than any tile, every table form, the shapes and argument errors of the
-call between guards, the unitigs byte for byte kt_ctr_unitigs's, the scratch claims between other entry points; and
-`kmertools unitigs --gfa --links` end to end.  Every comparison is exact."""
+call between guards, the unitigs byte for byte kt_ctr_unitigs's, the scratch claims between other entry points, the three
+entry points that share the stages back to back in two orders; and `kmertools unitigs --gfa --links` end to end.  Every comparison is exact."""
 import ctypes as C
 import json
 import os
@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import graph_ref as gr  # noqa: E402
 import test_ctr_unitigs as tu  # noqa: E402  (its table builders, buffers and guards: the same tables, the same forms)
+import tip_ref as tr  # noqa: E402
 import unitig_link_ref as lr  # noqa: E402
 import unitig_ref as ur  # noqa: E402
 
@@ -480,6 +481,60 @@ def test_links_same_unitigs_and_scratch_claims(torch_mod, ctx, oracle):
             s2 = c.spectrum_host(64)
             assert all(np.array_equal(x, y) for x, y in zip(spec, s2))
         assert first_difference(reference(tu.strings_table(tk, tc, k), k), first) is None
+    finally:
+        c.close()
+
+
+def test_links_three_entry_points_share_stages(torch_mod, ctx):
+    """kt_ctr_unitig_tips, kt_ctr_unitigs and kt_ctr_unitigs_linked run the same stages into the same scratch: on one table,
+    back to back in two orders and through both memory kinds, every call answers the same each time it is made.  The table at
+    k = 11 is a cycle of 40 nodes, a path seen twice with a branch of 3 nodes seen once (a tip), and single 11-mers that touch
+    nothing, up to 1025 unitigs: the scan over nodes, the scan over ends and the tip kernels all cross a tile."""
+    torch = torch_mod
+    k, mt, NU = 11, 11, 1025
+    rng = np.random.default_rng(NU)
+    word = lambda n: "".join(rng.choice(list("ACGT"), size=n))
+    cyc, G = word(40), word(80)
+    branch = G[30:30 + k - 1] + ("A" if G[30 + k - 1] != "A" else "C") + word(2)
+    table = gr.count_strings([cyc + cyc[:k - 1], G, G, branch], k)
+    short = NU - len(ur.unitigs(table, k))
+    while short:
+        s = word(k)
+        if not any(gr.canon_s(x) in table for b in "ACGT" for x in (s, s[1:] + b, b + s[:-1])):
+            table[gr.canon_s(s)] = int(rng.integers(1, 5))
+            short -= 1
+    # the input's shape, on the CPU
+    us, ls, wm, wt = tr.marks(table, k, mt)
+    assert len(us) == NU and sum(1 for u in us if u[2] & ur.CIRCULAR) == 1 and wt[0] >= 1 and wt[2] >= NU - 10, wt
+    want = tu.as_arrays(us) + lr.as_arrays(ls)
+    nu, nb, nl = NU, len(want[0]), len(want[5])
+    tk, tc = tu.sorted_table([gr.key_of(s) for s in table], list(table.values()))
+    c = tu.pairs_counter(ctx, k, tk, tc)
+
+    def tips_dev():
+        dm = torch.zeros(nu, dtype=torch.uint8, device="cuda")
+        dt = torch.zeros(4, dtype=torch.int64, device="cuda")
+        assert c.unitig_tips_device(dm, nu, dt, mt, 1, None) == nu
+        torch.cuda.synchronize()
+        return dm.cpu().numpy(), dt.cpu().numpy().view(np.uint64)
+
+    calls = {"tips": (lambda: c.unitig_tips(mt, 1, None), tips_dev),
+             "unitigs": (lambda: c.unitigs(1, None), lambda: tu.unitigs_dev(torch, c, 1, None, nu, nb)),
+             "linked": (lambda: c.unitig_links(1, None), lambda: links_dev(torch, c, 1, None, nu, nb, nl))}
+    try:
+        first = {}
+        for order in (("tips", "unitigs", "linked", "tips"), ("tips", "linked", "unitigs", "tips")):
+            for name in order:
+                for mode, fn in zip(("host", "device"), calls[name]):
+                    got = tuple(np.asarray(a).copy() for a in fn())
+                    was = first.setdefault(name, got)
+                    assert len(got) == len(was) and all(g.dtype == w.dtype and np.array_equal(g, w) for g, w in zip(got, was)), \
+                        (order, name, mode)
+        assert tu.same(first["unitigs"], first["linked"][:4])
+        assert first_difference(first["linked"], want) is None, first_difference(first["linked"], want)
+        am, at = tr.marks_of_arrays(*first["linked"][1:], k, mt)
+        assert np.array_equal(first["tips"][0], am) and np.array_equal(first["tips"][1], at)
+        assert np.array_equal(am, np.asarray(wm, np.uint8)) and at.tolist() == list(wt)
     finally:
         c.close()
 

@@ -1,5 +1,5 @@
-"""Times tip clipping on the device: one round and the whole of kt_ctr_clip_tips, beside kt_ctr_unitigs_linked, the read-only
-kt_ctr_unitig_tips and the count of the same table.  The table is bench.py's genome-sampled ctr_k31 (reads of 150 bases
+"""Times tip clipping on the device: one round and the whole of kt_ctr_clip_tips, beside kt_ctr_unitigs_linked, kt_ctr_unitigs,
+the read-only kt_ctr_unitig_tips and the count of the same table.  The table is bench.py's genome-sampled ctr_k31 (reads of 150 bases
 sampled by kt_synth_reads from a random genome, both strands, 1 % substitutions, 3.75-fold coverage, k = 31, every k-mer a
 node), scaled: bench.py's 25 M reads from 1 Gbp hold more than the 2^31 - 2 entries the unitig calls take.  One process,
 events on the context's stream round each call.  A clip changes the table, so a round is measured once: the first round as
@@ -88,6 +88,7 @@ def main():
     lo_ = torch.empty(2 * nu + 1, dtype=torch.int64, device="cuda")
     lt = torch.empty(nl, dtype=torch.int32, device="cuda")
     r["unitigs_linked"] = timed(lambda: t.unitigs_linked_device(ub, nb, uo, us, uf, nu, lo_, lt, nl), 1, args.reps)
+    r["unitigs_unlinked"] = timed(lambda: t.unitigs_device(ub, nb, uo, us, uf, nu), 1, args.reps)
     del ub, uo, us, uf, lo_, lt
     if args.linked_only:
         r["library"] = str(_lib.LIB_PATH)
