@@ -6,27 +6,43 @@
 // (one CAS or atomic add per k-mer, kt_ctr.hip) cannot exceed ~20 G k-mers/s.  A batch can instead go through
 // streaming passes (a job: kt_bulk_begin, level 1 over one or more sources, kt_bulk_finish):
 //
-//   scatter1x persistent workgroups (one per CU, four 256-thread groups) run a source's units (8192-base segments of
-//             reads, or 8192 keys of an array that another GPU routed here), four at a time; a round's 16 K keys
-//             (32 K 32-bit ones) are counting-sorted in LDS by d1 = top b1 bits of khash(key) and every d1 run is
-//             appended to the bucket's fixed region of the key array - its place taken with one atomic per run on the
-//             cursor the workgroups of an XCD share (whole cache lines leave the L2), written in 16-byte groups.
-//             64-bit keys are stored as khash(key) from here on (to_stored / from_stored).
-//   part2     one workgroup per level-1 bucket: the bucket is read in 16384-key chunks, each chunk
-//             counting-sorted in LDS by d2 (next b2 hash bits) and its runs appended to the fine buckets, which
-//             own fixed shares of the bucket's region; a bucket whose keys do not spread that evenly is noticed
-//             during the pass and redone with exact fine boundaries (see part2_kernel)
-//   build     one workgroup per fine bucket (d1,d2) = one range of the table (kt_table.hpp): its keys are inserted
-//             into the range's image in LDS - on top of what the range already holds when the table has data - and
-//             the range is written out: its occupied entries only, packed (a fresh table: the "dense" state), or the
-//             whole image with 16-byte coalesced stores, empty slots included (see build_kernel)
+//   pack      (read batches) one pass turns the reads into 16-byte items of 32 bases - codes, invalid-base mask, read-start
+//             mask - so that level 1 stages nothing through LDS (pack_segments_kernel; KT_BULK_PACK=0, the hash partitions
+//             of an out-of-core count and record / key sources: level 1 reads its source itself)
+//   level 1   persistent workgroups run a source's units (8192-base segments of reads, 8192 keys of an array that another
+//             GPU routed here, blocks of records); a round's keys are counting-sorted in LDS by d1 = top b1 bits of
+//             khash(key) and every d1 run is appended to the bucket's fixed region of the key array - its place taken with
+//             one atomic per run on the cursor that the workgroups of an XCD share (whole cache lines leave the L2), written
+//             in 16-byte groups.  scatter1y_kernel: 1024 threads, two sort buffers, a round's copy-out spread over the next
+//             round; scatter1x_kernel: one buffer, a round copied out before the next begins - for the shapes whose two
+//             buffers do not fit the LDS, and KT_S1Y=0.  64-bit keys are stored as khash(key) from here on (to_stored / from_stored).
+//   tails     xcd_tails_kernel pads what the cursor sets' fills differ by with the empty key and leaves every bucket's
+//             extent; behind it the host reads one word: did every bucket fit its region?
+//   level 2   one workgroup per level-1 bucket sorts it by d2 (the next b2 hash bits) into its fine buckets, which own
+//             fixed shares of the bucket's region in the second key array.  part2_swwc_kernel (fan-outs of 512 and more):
+//             one line per fine bucket in LDS, whole aligned lines written; part2_fast_kernel (below that): chunks of 16384
+//             keys counting-sorted in LDS, their runs appended.  A bucket whose keys do not spread that evenly is noticed
+//             during the pass, raises its word of fail[], and the launch behind - part2_exact_kernel over those buckets
+//             only, none normally - redoes it with exact fine boundaries from a histogram of the bucket.
+//   build     one workgroup per fine bucket (d1,d2) = one range of the table (kt_table.hpp): its keys are inserted into
+//             the range's image in LDS and the range is written out (build_kernel), as one of
+//               merge       on top of what the range already holds (a table with data), the whole image written
+//               image       a fresh table, the whole image with 16-byte coalesced stores, empty slots included (KT_BULK_DENSE=0)
+//               dense       a fresh table, the range's occupied entries only, packed: the "dense" state
+//               direct      dense for a table of exactly 4^k slots, k <= 16: the image is counters alone, no key is stored
+//               dense-ext,  the packed entries go straight to the export arrays the caller named (kt_ctr_export_target) in
+//               direct-ext  blocks per workgroup; ext_scan_kernel and ext_patch_kernel close the holes between the blocks.
+//                           Where they did not fit (one read by the host) the ranges are built again as dense / direct.
+//             Keys of a range that holds more distinct keys than slots go to a spill list; a build that leaves the
+//             probing image (merge, image) inserts them by probing afterwards (spill_insert_kernel).
 //
 // Fixed regions assume the hash spreads the batch; a batch dominated by a few k-mers overflows a level-1 region,
-// is noticed (one 4-byte read by the host), and is redone from its sources with exact offsets:
+// is noticed (the read behind the tails), and is redone from its sources with exact offsets - for this job and every
+// later one of the table:
 //   hist1     a front-end pass that counts k-mers per (workgroup, d1)          (LDS counters)
 //   scan1     exact output offset of every (workgroup, d1) pair
 //   scatter1  one 256-thread workgroup per unit, every run copied to its exact place
-//   part2     first histograms the whole bucket by d2 (a second read) to get the fine boundaries
+//   level 2   part2_exact_kernel over every bucket: the fine buckets own no fixed room then
 //
 // Traffic ~ 1 B/base + 8 B/k-mer x 4 + 12 B per distinct k-mer (dense) or 16 B/slot (image), all streaming.  The
 // intermediate key arrays and the LDS sort / insert arrays hold 32-bit keys when k <= 16 (template parameter K): half
@@ -122,7 +138,7 @@ struct Meta {           // device arrays carved from ctr->b_meta
     uint64_t spill_cap;
 };
 
-// (both digits lie in the hash's high word - 1 <= b1, b1 + b2 <= 21: plan_job - so they are 32-bit shifts; written on the 64-bit
+// (both digits lie in the hash's high word - 1 <= b1, b1 + b2 <= 21: split_bits - so they are 32-bit shifts; written on the 64-bit
 // value, with a shift the compiler does not know to be >= 32, each is a 64-bit shift: per key, in every pass)
 __device__ __forceinline__ uint32_t digit1h(uint64_t h, const Plan &p) { return (uint32_t)(h >> 32) >> (32 - p.b1); }
 __device__ __forceinline__ uint32_t digit2h(uint64_t h, const Plan &p) {
@@ -148,7 +164,7 @@ template <class K>
 __device__ __forceinline__ uint64_t hash_of_stored(K s, const Plan &p) {
     if constexpr (stores_hash<K>()) return (uint64_t)s;
     else if constexpr (sizeof(K) == 4) return (uint64_t)ktd::nhash_top((uint32_t)s, p.kbits) << 32;  // (k <= 16: kbits = 2k, never 0 -
-    else return ktd::khash_k((uint64_t)s, p.kbits);  // khash_k's test of it is a branch per key and pass: plan_job)
+    else return ktd::khash_k((uint64_t)s, p.kbits);  // khash_k's test of it is a branch per key and pass: kt_bulk_job::plan)
 }
 template <class K>
 __device__ __forceinline__ uint64_t from_stored(K s) {
@@ -1186,7 +1202,7 @@ __global__ __launch_bounds__(T, 4) void scatter1y_kernel(Source src, Plan p, uns
     constexpr bool CARRY = KT_S1Y_CARRY && GK == 2;
     uint32_t rs_prev = 0, rc_prev = 0;  // this thread's bucket in the round before: where its run starts in sorted[], its keys
     constexpr uint32_t LSH1 = sizeof(K) == 8 ? 4 : 5;  // keys per 128-byte line (xcd_place)
-    const uint32_t cap1_32 = (uint32_t)p.cap1, cap_lines = (uint32_t)(p.cap1 >> LSH1);  // (plan_job: a region is < 2^31 bytes)
+    const uint32_t cap1_32 = (uint32_t)p.cap1, cap_lines = (uint32_t)(p.cap1 >> LSH1);  // (kt_bulk_job::plan: a region is < 2^31 bytes)
     // group u of this thread's share of the round before: out to its place, or - nothing there, or no room - to the dump line
     auto emit = [&](int u, uint32_t tl, uint32_t pp) {
         uint32_t m = tl + (uint32_t)u * T;
@@ -1441,19 +1457,9 @@ struct Part2Shared {
     }
 };
 
-// FIXED (with paged level 1): every fine bucket owns cap2 keys of room in keys2, so the whole-bucket histogram
-// pass (a second read of keys1) is not needed - as long as the bucket's keys spread over its fine buckets the way
-// a hash spreads distinct keys.  They do not when few distinct k-mers make up the batch (deep coverage of a small
-// genome, repeats): the attempt watches every fine bucket's fill against the fraction of the level-1 bucket
-// processed so far, and as soon as one is heading past its room it stops placing keys, finishes the pass counting
-// only (which is exactly the histogram), and the bucket is redone with the exact boundaries - the price of a
-// wrong guess is the part of the pass done before it was noticed.
-// Where part2 reads a bucket from: its region of the level-1 output - bucket jl = srcs[0].keys + jl * cap1,
+// Where level 2 reads a bucket from: its region of the level-1 output - bucket jl = srcs[0].keys + jl * cap1,
 // min(srcs[0].counts[jl], cap1) keys, empty keys in the gaps (the kernels walk a list of such sources; a job has one).
 // (exact level 1, srcs == nullptr: keys1 is dense, bucket j = [bstart[j], bstart[j + 1]).)
-#ifndef KT_P2_LOAD16
-#define KT_P2_LOAD16 0  // two keys per 16-byte load in part2: measured 16.0 against 15.5 ms (k=31) - off
-#endif
 struct P2In {
     const void *keys1;
     const uint64_t *bstart;
@@ -1462,8 +1468,12 @@ struct P2In {
     __device__ __forceinline__ uint64_t out_of(uint32_t jl, uint64_t room1) const { return (uint64_t)jl * room1; }
 };
 
-template <class K, bool FIXED, bool BIG, bool L16 = false>
-__global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) void part2_kernel(P2In in, Plan p,
+// Level 2 with exact fine boundaries: a histogram of the whole bucket by d2 (a first read of it), the boundaries from its
+// scan, then the pass that places the keys.  It runs for every bucket when the fine buckets own no fixed room (cap2 = 0:
+// exact level 1, KT_BULK_FIXED2=0), and behind part2_swwc_kernel / part2_fast_kernel for the buckets whose word in `only`
+// they raised.
+template <class K, bool BIG>
+__global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) void part2_exact_kernel(P2In in, Plan p,
                                                       K *__restrict__ keys2, uint64_t *__restrict__ fstart,
                                                       uint64_t *__restrict__ fend, const uint32_t *__restrict__ only) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1475,7 +1485,7 @@ __global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) v
     const uint32_t tid = threadIdx.x;
     const uint32_t nd = p.B1;
     for (uint32_t jl = blockIdx.x; jl < nd; jl += gridDim.x) {
-        if (only && !only[jl]) continue;  // (the redo pass behind part2_fast_kernel: only the buckets whose attempt failed)
+        if (only && !only[jl]) continue;  // (the redo pass: only the buckets that did not fit their fixed fine regions)
         // the bucket's segments, and where the bucket lives in keys2
         const uint32_t n_seg = in.srcs ? in.n_src : 1u;
         auto segment = [&](uint32_t sidx, const K *&base, uint64_t &n) {
@@ -1489,182 +1499,113 @@ __global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) v
                 n = in.bstart[jl + 1] - in.bstart[jl];
             }
         };
-        uint64_t total = 0;
-        for (uint32_t sidx = 0; sidx < n_seg; sidx++) {
-            const K *b;
-            uint64_t n;
-            segment(sidx, b, n);
-            total += n;
-        }
         const uint64_t lo = in.srcs ? in.out_of(jl, p.room1) : in.bstart[jl];
         auto load_chunk = [&](const K *base, uint64_t n, uint64_t c0, K (&dst)[PER]) {
-            if constexpr (sizeof(K) == 8 && L16) {  // two keys per load (regions are 16-byte aligned: paged level 1)
-                typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                for (int u = 0; u < PER / 2; u++) {
-                    const uint64_t i = c0 + ((uint64_t)u * P2T + tid) * 2;
-                    u64x2 v = {(unsigned long long)EMPTY, (unsigned long long)EMPTY};
-                    if (i + 1 < n) v = *reinterpret_cast<const u64x2 *>(base + i);
-                    else if (i < n) v.x = base[i];
-                    dst[2 * u] = (K)v.x;
-                    dst[2 * u + 1] = (K)v.y;
-                }
-                return;
-            }
 #pragma unroll
             for (int u = 0; u < PER; u++) {
                 const uint64_t i = c0 + (uint64_t)u * P2T + tid;
                 dst[u] = i < n ? base[i] : EMPTY;
             }
         };
+        // whole-bucket histogram of d2
+        for (uint32_t i = tid; i < p.B2; i += P2T) sm.cnt[i] = 0;
+        ktd::lds_barrier();
+        for (uint32_t sidx = 0; sidx < n_seg; sidx++) {
+            const K *base;
+            uint64_t n;
+            segment(sidx, base, n);
+            for (uint64_t i0 = tid; i0 < n; i0 += (uint64_t)P2T * 8) {  // 8 loads in flight per thread
+                K kk[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint64_t i = i0 + (uint64_t)u * P2T;
+                    kk[u] = i < n ? base[i] : EMPTY;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (kk[u] != EMPTY) atomicAdd(&sm.cnt[digit2h(hash_of_stored<K>(kk[u], p), p)], 1u);
+            }
+        }
+        ktd::lds_barrier();
+        // fine bucket boundaries from the sizes (a level-1 bucket of > 4 G keys is not supported)
+        block_excl_scan<P2T>(sm.cnt, sm.start, p.B2, sm.tmp);
+        for (uint32_t i = tid; i < p.B2; i += P2T) {
+            const uint64_t pos = lo + sm.start[i];
+            sm.cur[i] = sm.start[i];
+            fstart[(uint64_t)jl * p.B2 + i] = pos;
+            fend[(uint64_t)jl * p.B2 + i] = pos + sm.cnt[i];
+        }
+        ktd::lds_barrier();
         // one pass over the bucket in chunks of chunk2<K, BIG>() keys, segment after segment: counting sort in LDS, runs
         // appended at the fine buckets' cursors.  The next chunk's keys are loaded while the current one is sorted.
-        // attempt = fixed fine regions (cursors may run past their room: then nothing is stored any more)
-        auto run_pass = [&](const bool attempt) {
-            // One set of key registers: the next chunk's loads are issued once the current chunk's keys have been placed in
-            // LDS (they are dead then) and travel during the copy-out.  (Holding the prefetched chunk beside the current one
-            // - 64 registers of keys - spilled a quarter of them at the 128 registers a 16-wave workgroup gets.)
-            K kcur[PER];
-            bool counting_only = false;
-            uint64_t seen_keys = 0;
-            // Five barriers per chunk (it was seven): the chunks alternate between two count arrays, each zeroed a chunk
-            // ahead, so a wave that has copied its share of the sorted chunk out goes straight on to the cursor update
-            // and the next chunk's count while the others are still copying.
-            uint32_t par = 0;
-            for (uint32_t i = tid; i < 2 * p.B2; i += P2T) sm.cnt[i] = 0;
-            ktd::lds_barrier();
-            for (uint32_t sidx = 0; sidx < n_seg; sidx++) {
-                const K *base;
-                uint64_t n;
-                segment(sidx, base, n);
-                if (n) load_chunk(base, n, 0, kcur);
-                for (uint64_t c0 = 0; c0 < n; c0 += CH, par ^= 1u) {
-                    uint32_t *const cntc = sm.cnt + par * p.B2, *const cntn = sm.cnt + (par ^ 1u) * p.B2;
+        // One set of key registers: the next chunk's loads are issued once the current chunk's keys have been placed in
+        // LDS (they are dead then) and travel during the copy-out.  (Holding the prefetched chunk beside the current one
+        // - 64 registers of keys - spilled a quarter of them at the 128 registers a 16-wave workgroup gets.)
+        K kcur[PER];
+        // Five barriers per chunk (it was seven): the chunks alternate between two count arrays, each zeroed a chunk ahead, so a wave
+        // that has copied its share of the sorted chunk out goes straight on to the cursor update and the next chunk's
+        // count while the others are still copying.
+        uint32_t par = 0;
+        for (uint32_t i = tid; i < 2 * p.B2; i += P2T) sm.cnt[i] = 0;
+        ktd::lds_barrier();
+        for (uint32_t sidx = 0; sidx < n_seg; sidx++) {
+            const K *base;
+            uint64_t n;
+            segment(sidx, base, n);
+            if (n) load_chunk(base, n, 0, kcur);
+            for (uint64_t c0 = 0; c0 < n; c0 += CH, par ^= 1u) {
+                uint32_t *const cntc = sm.cnt + par * p.B2, *const cntn = sm.cnt + (par ^ 1u) * p.B2;
 #pragma unroll
-                    for (int u = 0; u < PER; u++) {
-                        const uint32_t d = digit2h(hash_of_stored<K>(kcur[u], p), p);
-                        if (kcur[u] != EMPTY) atomicAdd(&cntc[d], 1u);
-                    }
-                    ktd::lds_barrier();
-                    if (attempt) counting_only = *sm.flag != 0;  // (raised in a cursor update before the barrier above)
-                    if (!counting_only) {
-                        const uint32_t nc = block_excl_scan<P2T>(cntc, sm.start, p.B2, sm.tmp);  // keys in the chunk
-                        // (cntc has been summed: from here to the cursor update it holds cur - start, what the copy-out
-                        // adds to a sorted key's index to get its place in the level-1 bucket; the other array - last
-                        // read by the previous chunk's cursor update, before the barrier above - is zeroed for the next)
-                        for (uint32_t i = tid; i < p.B2; i += P2T) {
-                            cntc[i] = sm.cur[i] - sm.start[i];
-                            cntn[i] = 0;
-                        }
-                        ktd::lds_barrier();
-#pragma unroll
-                        for (int u = 0; u < PER; u++) {
-                            if (kcur[u] != EMPTY) {
-                                const uint32_t d = digit2h(hash_of_stored<K>(kcur[u], p), p);
-                                const uint32_t pos = atomicAdd(&sm.start[d], 1u);
-                                sm.sorted[pos] = kcur[u];
-                                if constexpr (p2_sdig<K, BIG>()) sm.sdig[pos] = (uint16_t)d;
-                            }
-                        }
-                        if (c0 + CH < n) load_chunk(base, n, c0 + CH, kcur);  // the next chunk travels during the copy-out
-                        ktd::lds_barrier();
-                        for (uint32_t i = tid; i < nc; i += P2T) {
-                            const K key = sm.sorted[i];
-                            uint32_t d;
-                            if constexpr (p2_sdig<K, BIG>()) d = sm.sdig[i];
-                            else d = digit2h(hash_of_stored<K>(key, p), p);
-                            const uint64_t pos = lo + (uint32_t)(cntc[d] + i);
-                            if (!attempt || pos < lo + (uint64_t)(d + 1) * p.cap2) keys2[pos] = key;
-                        }
-                    } else {
-                        if (c0 + CH < n) load_chunk(base, n, c0 + CH, kcur);
-                        for (uint32_t i = tid; i < p.B2; i += P2T) cntn[i] = 0;
-                    }
-                    // cursors move on (no barrier: nothing the copy-out of the other waves reads is written here); during
-                    // an attempt every fine bucket's fill is held against its room scaled to the part of the level-1
-                    // bucket seen so far (+ 6 sigma): hashed distinct keys never get there
-                    float allowed = 0.f;
-                    if (attempt) {
-                        const float seen = (float)(seen_keys + c0 + CH) / (float)total;
-                        // (the bucket may hold fewer keys than its room: what counts is the share of a fine bucket)
-                        const float room = (float)p.cap2 * (seen < 1.f ? seen : 1.f);
-                        allowed = 0.93f * room + 6.f * sqrtf(room) + 32.f;
-                    }
-                    for (uint32_t i = tid; i < p.B2; i += P2T) {
-                        // placed: start[] stands at the runs' ends, so start + (cur - start at their beginnings) = cur + count
-                        const uint32_t c = counting_only ? sm.cur[i] + cntc[i] : sm.start[i] + cntc[i];
-                        sm.cur[i] = c;
-                        if (attempt && !counting_only && (float)(c - i * (uint32_t)p.cap2) > allowed) *sm.flag = 1;
-                    }
-                    if (counting_only) ktd::lds_barrier();  // (the zeroing above against the next chunk's count)
+                for (int u = 0; u < PER; u++) {
+                    const uint32_t d = digit2h(hash_of_stored<K>(kcur[u], p), p);
+                    if (kcur[u] != EMPTY) atomicAdd(&cntc[d], 1u);
                 }
-                seen_keys += n;
-            }
-            ktd::lds_barrier();
-        };
-
-        bool exact = !FIXED;
-        if constexpr (FIXED) {
-            for (uint32_t i = tid; i < p.B2; i += P2T) sm.cur[i] = i * (uint32_t)p.cap2;  // (room1 = B2 * cap2 < 2^32)
-            if (tid == 0) *sm.flag = 0;
-            ktd::lds_barrier();
-            run_pass(true);
-            // did every fine bucket stay inside its room?  (the running check is a prediction; this is the fact)
-            for (uint32_t i = tid; i < p.B2; i += P2T)
-                if (sm.cur[i] - i * (uint32_t)p.cap2 > p.cap2) *sm.flag = 1;
-            ktd::lds_barrier();
-            if (*sm.flag == 0) {
+                ktd::lds_barrier();
+                const uint32_t nc = block_excl_scan<P2T>(cntc, sm.start, p.B2, sm.tmp);  // keys in the chunk
+                // (cntc has been summed: from here to the cursor update it holds cur - start, what the copy-out
+                // adds to a sorted key's index to get its place in the level-1 bucket; the other array - last
+                // read by the previous chunk's cursor update, before the barrier above - is zeroed for the next)
                 for (uint32_t i = tid; i < p.B2; i += P2T) {
-                    fstart[(uint64_t)jl * p.B2 + i] = lo + (uint64_t)i * p.cap2;
-                    fend[(uint64_t)jl * p.B2 + i] = lo + sm.cur[i];
+                    cntc[i] = sm.cur[i] - sm.start[i];
+                    cntn[i] = 0;
                 }
-            } else {  // no: the cursors hold the exact sizes now
-                for (uint32_t i = tid; i < p.B2; i += P2T) sm.cnt[i] = sm.cur[i] - i * (uint32_t)p.cap2;
-                exact = true;
-            }
-            ktd::lds_barrier();
-        } else {
-            // whole-bucket histogram of d2
-            for (uint32_t i = tid; i < p.B2; i += P2T) sm.cnt[i] = 0;
-            ktd::lds_barrier();
-            for (uint32_t sidx = 0; sidx < n_seg; sidx++) {
-                const K *base;
-                uint64_t n;
-                segment(sidx, base, n);
-                for (uint64_t i0 = tid; i0 < n; i0 += (uint64_t)P2T * 8) {  // 8 loads in flight per thread
-                    K kk[8];
+                ktd::lds_barrier();
 #pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        const uint64_t i = i0 + (uint64_t)u * P2T;
-                        kk[u] = i < n ? base[i] : EMPTY;
+                for (int u = 0; u < PER; u++) {
+                    if (kcur[u] != EMPTY) {
+                        const uint32_t d = digit2h(hash_of_stored<K>(kcur[u], p), p);
+                        const uint32_t pos = atomicAdd(&sm.start[d], 1u);
+                        sm.sorted[pos] = kcur[u];
+                        if constexpr (p2_sdig<K, BIG>()) sm.sdig[pos] = (uint16_t)d;
                     }
-#pragma unroll
-                    for (int u = 0; u < 8; u++)
-                        if (kk[u] != EMPTY) atomicAdd(&sm.cnt[digit2h(hash_of_stored<K>(kk[u], p), p)], 1u);
                 }
+                if (c0 + CH < n) load_chunk(base, n, c0 + CH, kcur);  // the next chunk travels during the copy-out
+                ktd::lds_barrier();
+                for (uint32_t i = tid; i < nc; i += P2T) {
+                    const K key = sm.sorted[i];
+                    uint32_t d;
+                    if constexpr (p2_sdig<K, BIG>()) d = sm.sdig[i];
+                    else d = digit2h(hash_of_stored<K>(key, p), p);
+                    keys2[lo + (uint32_t)(cntc[d] + i)] = key;
+                }
+                // cursors move on (no barrier: nothing the copy-out of the other waves reads is written here).
+                // placed: start[] stands at the runs' ends, so start + (cur - start at their beginnings) = cur + count
+                for (uint32_t i = tid; i < p.B2; i += P2T) sm.cur[i] = sm.start[i] + cntc[i];
             }
-            ktd::lds_barrier();
         }
-        if (exact) {
-            // fine bucket boundaries from the sizes (a level-1 bucket of > 4 G keys is not supported)
-            block_excl_scan<P2T>(sm.cnt, sm.start, p.B2, sm.tmp);
-            for (uint32_t i = tid; i < p.B2; i += P2T) {
-                const uint64_t pos = lo + sm.start[i];
-                sm.cur[i] = sm.start[i];
-                fstart[(uint64_t)jl * p.B2 + i] = pos;
-                fend[(uint64_t)jl * p.B2 + i] = pos + sm.cnt[i];
-            }
-            ktd::lds_barrier();
-            run_pass(false);
-        }
+        ktd::lds_barrier();
     }
 }
 
 // ---- part2, the kernel the bulk path runs (round 4): fixed fine regions, nothing else --------------------------------
-// part2_kernel<.., FIXED> with everything that is not the common case taken out: one attempt with fixed fine regions
-// per bucket; a bucket whose keys do not spread like hashed distinct keys raises fail[jl] and is left to a second launch of
-// the general kernel (exact boundaries from a histogram pass), which skips every other bucket.  What round 3's ISA and
-// ablations showed about the old loop, and what this one does about it:
+// With paged level 1 every fine bucket owns cap2 keys of room in keys2, so the whole-bucket histogram pass (a second read
+// of keys1) is not needed - as long as the bucket's keys spread over its fine buckets the way a hash spreads distinct
+// keys.  They do not when few distinct k-mers make up the batch (deep coverage of a small genome, repeats): the attempt
+// watches every fine bucket's fill against the fraction of the level-1 bucket processed so far, and as soon as one is
+// heading past its room it gives the bucket up - the price of a wrong guess is the part of the pass done before it was
+// noticed.  One attempt per bucket, nothing that is not the common case: a bucket given up raises fail[jl] and is left to
+// a second launch of part2_exact_kernel (exact boundaries from a histogram pass), which skips every other bucket.  What
+// round 3's ISA and ablations showed about the old loop, and what this one does about it:
 //  * the wave waited for every LDS round trip on its own: sixteen times "ds_add_rtn, s_waitcnt lgkmcnt(0), ds_write_b64"
 //    in the placement, a rolled "ds_read_b64, wait, ds_read_b32, wait, store" in the copy-out - with 4 waves per SIMD
 //    nothing hid those ~50 round trips per chunk.  Now ONE LDS atomic per key: the count's atomic returns the key's rank
@@ -1675,7 +1616,7 @@ __global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) v
 //    drained its stores once per chunk, and the one workgroup of a CU does nothing else meanwhile.  Now loads and stores
 //    are issued out of the compiler's sight (buf_load8_async / buf_store_async) and the wait is vmcnt(PER): the loads are in,
 //    this chunk's stores drain while the next chunk is counted, scanned and placed.
-//  * registers: 512 threads x 32 keys (64-bit keys) in a 256-register budget, the general kernel's other paths gone, the
+//  * registers: 512 threads x 32 keys (64-bit keys) in a 256-register budget, the exact kernel's histogram pass gone, the
 //    scan with a compile-time number of counters per thread (PB), the thread index made opaque per chunk - the hot loop
 //    must not touch scratch: a reload is a vmcnt(0).
 template <class K, bool BIG, int PB>
@@ -1866,8 +1807,8 @@ __global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) v
                 fend[(uint64_t)jl * B2 + i] = lo + sm.cur[i];
             }
         } else if (tid == 0) {
-            fail[jl] = 1u;  // redone by part2_kernel<K, false, BIG> (exact fine boundaries) in the launch behind this one
-            atomicAdd(&fail[p.B1], 1u);  // (how many of the job's buckets: finish_typed reports it, kt_shard.hip sizes its next job by it)
+            fail[jl] = 1u;  // redone by part2_exact_kernel<K, BIG> (exact fine boundaries) in the launch behind this one
+            atomicAdd(&fail[p.B1], 1u);  // (how many of the job's buckets: kt_bulk_job::build_to_target reads it, kt_shard.hip sizes its next job by it)
         }
         ktd::lds_barrier();
     }
@@ -1887,7 +1828,7 @@ __global__ __launch_bounds__((p2t<K, BIG>()), (p2t<K, BIG>() == 1024 ? 4 : 2)) v
 // the lines is carried into the next chunk).  What a bucket
 // still holds when its input ends goes out as one partial line.
 // Same contract as part2_fast_kernel: fixed fine regions (cap2 keys each, a multiple of LK so that every region starts on
-// a line), a bucket that outgrows one raises fail[jl] and is redone by the general kernel.
+// a line), a bucket that outgrows one raises fail[jl] and is redone by part2_exact_kernel.
 template <class K>
 struct SwwcShared {
     K *buf;             // [B2][LK] the buckets' lines
@@ -2121,7 +2062,7 @@ __global__ __launch_bounds__((swwc_t<K>()), (swwc_t<K>() / 256)) void part2_swwc
         }
         ktd::lds_barrier();
         if ((failed || sm.flags[2] != 0) && tid == 0) {
-            fail[jl] = 1u;  // redone by part2_kernel<K, false, BIG> in the launch behind this one
+            fail[jl] = 1u;  // redone by part2_exact_kernel<K, BIG> in the launch behind this one
             atomicAdd(&fail[p.B1], 1u);
         }
         ktd::lds_barrier();
@@ -2189,7 +2130,7 @@ struct lds_word<uint32_t> { using type = unsigned int; };
 // Positions are "virtual": [0, max) is the caller's arrays, [max, max + ovf_cap) the library's scratch behind them,
 // because blocks + holes reach past n even when n <= max (the caller's arrays may be exactly n long).  Keys that are
 // NOT spread evenly over the workgroups (an adversarial input) can push the extent past the scratch: ext_scan_kernel
-// raises flag 4 and the host builds the ranges again the ordinary way (finish_typed).
+// raises flag 4 and the host builds the ranges again the ordinary way (kt_bulk_job::build).
 // The table keeps no per-range record of where entries went: whatever needs the probing image afterwards re-inserts
 // the exported pairs (kt_table_image).
 constexpr uint32_t XBLK = 8192;  // >= the slots of a range: a range spans at most two blocks
@@ -2234,7 +2175,7 @@ struct ExtOut {
 #ifndef KT_BUILD_SGPRS
 #define KT_BUILD_SGPRS 80
 #endif
-// DIRECT (32-bit keys, a fresh dense build of a table with exactly 4^k slots, i.e. n = 2k hash bits: plan_job): the
+// DIRECT (32-bit keys, a fresh dense build of a table with exactly 4^k slots, i.e. n = 2k hash bits: kt_bulk_job::build_variant): the
 // table's hash is a bijection of the k-mers onto the slots (ktd::nhash), so a range's image is its COUNTERS alone - a key
 // is one LDS add at the low 13 bits of its hash, no key stored, no compare, no probe chain, no lane waiting for another
 // lane's chain - and the entries come out of the counters that are not zero: key = nhash_inv(range's bits | index).
@@ -3020,6 +2961,8 @@ uint64_t env_u64(const char *name, uint64_t dflt) {
 }  // namespace
 
 // ---- host side: a job = plan + buffers + level 1 over one or more sources + level 2 + range build ----------------
+using ktl::launch;
+
 enum SourceKind { SRC_READS, SRC_KEYS, SRC_RECORDS, SRC_PACKED };
 struct SourceRec {  // what level 1 ran over (kept so that a skewed batch can be redone with exact offsets)
     SourceKind kind;
@@ -3042,7 +2985,7 @@ static int with_source(const SourceRec &r, F &&f) {
 
 struct BulkKnobs {  // the KT_BULK_* / KT_S1_* / KT_P2_* / KT_BUILD_* environment, read once per job (kt_bulk_begin)
     uint64_t bulk, min_bases, merge_div, g_mult, paged, fixed2, p2_big64, p2_big32, build_wgs, dense,
-        verbose, ext_ovf_blocks, build_wgs_ext, direct, pack, p2_fast, p2_grid, p2_swwc, b1, build_lists, s1y;
+        verbose, ext_ovf_blocks, build_wgs_ext, direct, pack, p2_grid, p2_swwc, b1, build_lists, s1y;
 };
 static BulkKnobs read_knobs() {
     BulkKnobs k;
@@ -3058,314 +3001,16 @@ static BulkKnobs read_knobs() {
     k.p2_grid = env_u64("KT_P2_GRID", 0);  // workgroups of the level-2 launch (0: one per bucket)
     k.b1 = env_u64("KT_BULK_B1", 0);
     k.p2_swwc = env_u64("KT_P2_SWWC", 1);  // level 2 with one line per fine bucket in LDS, whole lines written (0: sort buffer)
-    k.p2_fast = env_u64("KT_P2_FAST", 1);  // 0: the general level-2 kernel also for fixed fine regions (A/B, tests)
     k.build_wgs = env_u64("KT_BUILD_WGS", 64);
     k.build_wgs_ext = env_u64("KT_BUILD_WGS_EXT", 16);
     k.build_lists = env_u64("KT_BUILD_LISTS", 1);  // 0: the dense build packs the image instead of keeping claim lists (A/B)
     k.dense = env_u64("KT_BULK_DENSE", 1);
-    k.direct = env_u64("KT_BUILD_DIRECT", 1);
-    k.pack = env_u64("KT_BULK_PACK", 1);  // 0: level 1 stages the reads itself (ReadsSource) instead of reading packed items  // 0: tables of exactly 4^k slots are built by probing too (A/B, tests)
+    k.direct = env_u64("KT_BUILD_DIRECT", 1);  // 0: tables of exactly 4^k slots are built by probing too (A/B, tests)
+    k.pack = env_u64("KT_BULK_PACK", 1);  // 0: level 1 stages the reads itself (ReadsSource) instead of reading packed items
     k.verbose = env_u64("KT_BULK_VERBOSE", 0);
     k.ext_ovf_blocks = env_u64("KT_EXT_OVF_BLOCKS", 0);  // tests: n + 1 = blocks of scratch behind the export target
     return k;
 }
-
-struct kt_bulk_job {
-    Plan p{};
-    BulkKnobs kn{};
-    Meta m{};
-    bool narrow = false;  // 32-bit keys through the partition passes (k <= 16)
-    bool paged = false, merge = false, open = false;
-    bool xcd = false;  // paged level 1 appends through per-XCD cursors (scatter1x_kernel + xcd_tails_kernel)
-    uint64_t max_keys = 0, added_bound = 0;
-    std::vector<SourceRec> srcs;
-    kt_seg_src p2_src{};  // where part2 reads every bucket from: the level-1 output (host copy of its one device entry)
-    // record sources (kt_bulk_add_records): their descriptors on the device (ctr->b_desc), the host copies the uploads read
-    size_t desc_used = 0;
-    std::vector<std::vector<uint64_t>> desc_host;
-    size_t ksz() const { return narrow ? 4 : 8; }
-};
-
-void kt_bulk_job_free(kt_bulk_job *job) { delete job; }
-
-namespace {
-
-template <class K>
-int level1_paged(kt_ctr *ctr, kt_bulk_job &j, const SourceRec &r) {
-    kt_ctx *ctx = ctr->ctx;
-    K *keys1 = (K *)ctr->b_keys1.p;
-    if (!j.xcd) return kt::fail(KT_ERR_ARG, "bulk build: paged level 1 without its cursors");
-    unsigned long long *xcur = j.m.xcur;
-    const Plan p = j.p;
-    uint32_t *const ovf = j.m.ovf;
-    unsigned long long *const dump = j.m.dump;
-    // two sort buffers, the copy-out spread over the next round - or, a shape that does not fit the LDS, one buffer
-    const bool two = j.kn.s1y && Scatter1YShared<K, 1024>::bytes(j.p.B1) <= 160 * 1024;
-    const uint32_t mult = (uint32_t)(j.kn.g_mult ? j.kn.g_mult : 1);
-    const uint32_t cus = (uint32_t)ctx->n_cu > 2 * ctr->l1_spare_cus ? (uint32_t)ctx->n_cu - ctr->l1_spare_cus : (uint32_t)ctx->n_cu;
-    return with_source(r, [&](const auto &src) -> int {
-        using S = std::decay_t<decltype(src)>;
-        if (two) {
-            constexpr int T = 1024;
-            const size_t lds = Scatter1YShared<K, T>::bytes(p.B1);
-            auto kern = scatter1y_kernel<S, K, T>;
-            KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(cus * mult), dim3(T), lds, ctx->stream, src, p, xcur, ovf, keys1, dump);
-        } else {
-            constexpr int T = KT_S1X_T;
-            const size_t lds = sizeof(Scatter1XShared<K, T>);
-            auto kern = scatter1x_kernel<S, K, T>;
-            KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(cus * (1024 / T) * mult), dim3(T), lds, ctx->stream, src, p, xcur, ovf, keys1, dump);
-        }
-        KT_HIP(hipGetLastError());
-        return KT_OK;
-    });
-}
-
-template <class K>
-int level1_exact(kt_ctr *ctr, kt_bulk_job &j) {  // hist1 over every source, scan1, scatter1 over every source
-    kt_ctx *ctx = ctr->ctx;
-    K *keys1 = (K *)ctr->b_keys1.p;
-    const Plan p = j.p;
-    const Meta m = j.m;
-    KT_HIP(hipMemsetAsync(m.H, 0, (size_t)p.G * p.B1 * 4, ctx->stream));
-    for (const SourceRec &r : j.srcs) {
-        const int rc = with_source(r, [&](const auto &src) -> int {
-            using S = std::decay_t<decltype(src)>;
-            hipLaunchKernelGGL(hist1_kernel<S>, dim3(p.G), dim3(BLOCK), 0, ctx->stream, src, p, m.H);
-            return KT_OK;
-        });
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(scan1_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.H, p, m.O, m.bstart);
-    for (const SourceRec &r : j.srcs) {
-        const int rc = with_source(r, [&](const auto &src) -> int {
-            using S = std::decay_t<decltype(src)>;
-            auto kern = scatter1_kernel<S, K>;
-            KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)sizeof(Scatter1Shared<K>)));
-            hipLaunchKernelGGL(kern, dim3(p.G), dim3(BLOCK), sizeof(Scatter1Shared<K>), ctx->stream, src, p, m.O, keys1);
-            return KT_OK;
-        });
-        if (rc) return rc;
-    }
-    KT_HIP(hipGetLastError());
-    return KT_OK;
-}
-
-template <class K>
-int finish_typed(kt_ctr *ctr, kt_bulk_job &j) {
-    kt_ctx *ctx = ctr->ctx;
-    Plan &p = j.p;
-    Meta &m = j.m;
-    K *keys1 = (K *)ctr->b_keys1.p, *keys2 = (K *)ctr->b_keys2.p;
-    if (j.paged) {
-        hipLaunchKernelGGL(xcd_tails_kernel<K>, dim3(p.B1), dim3(BLOCK), 0, ctx->stream, p, (const unsigned long long *)m.xcur, m.gcur, keys1);
-        // the one host round trip of the build: did every bucket fit its region?
-        uint32_t ovf = 0;
-        KT_HIP(hipMemcpyAsync(&ovf, m.ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-        if (ovf) {  // skewed batch: exact offsets after all, and no more paged attempts on this table
-            j.paged = false;
-            ctr->paged_failed = true;
-            p.cap1 = 0;
-            p.cap2 = 0;
-            if (j.added_bound > ctr->b_keys1.cap / sizeof(K)) {  // (the paged room is always the larger)
-                return kt::fail(KT_ERR_NOMEM, "bulk build: key buffers too small for the exact layout");
-            }
-            if (int rc = level1_exact<K>(ctr, j)) return rc;
-        }
-    }
-    // where part2 finds every bucket: the level-1 output
-    P2In in{keys1, m.bstart, nullptr, 0};
-    if (j.paged) {
-        j.p2_src = kt_seg_src{keys1, m.gcur, p.cap1};
-        KT_HIP(hipMemcpyAsync(m.srcs, &j.p2_src, sizeof(kt_seg_src), hipMemcpyHostToDevice, ctx->stream));
-        in.srcs = m.srcs;
-        in.n_src = 1;
-    }
-    const uint32_t nd = p.B1;
-    // one level-2 launch: `pp` says which hash bits it sorts by and how many buckets it reads, `src` where from
-    // (`fail`: one word per bucket of the launch - zeroed here)
-    auto run_part2 = [&](const Plan &pp, const P2In &src, K *out, uint64_t *fs, uint64_t *fe, uint32_t *fail) -> int {
-        // (one line per fine bucket wants about a line's worth of keys per bucket and chunk: fan-outs below 512 keep the sort buffer)
-        if (pp.cap2 && src.srcs && j.kn.p2_swwc && pp.B2 >= 512 && SwwcShared<K>::bytes(pp.B2) <= 160 * 1024) {
-            // fixed fine regions, whole lines only (part2_swwc_kernel); then the general kernel over the buckets that did not
-            // fit their regions (none, normally)
-            const size_t lds = SwwcShared<K>::bytes(pp.B2);
-            KT_HIP(hipMemsetAsync(fail, 0, ((size_t)pp.B1 + 1) * 4, ctx->stream));
-            auto swwc = part2_swwc_kernel<K>;
-            KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(swwc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            uint32_t grid = pp.B1;
-            if (j.kn.p2_grid && grid > j.kn.p2_grid) grid = (uint32_t)j.kn.p2_grid;
-            hipLaunchKernelGGL(swwc, dim3(grid), dim3(swwc_t<K>()), lds, ctx->stream, src, pp, out, fs, fe, fail);
-            KT_HIP(hipGetLastError());
-            const bool bigr = (sizeof(K) == 8 ? j.kn.p2_big64 : j.kn.p2_big32) != 0 && Part2Shared<K, true>::bytes(pp.B2) <= 160 * 1024;
-            auto redo_launch = [&](auto big) -> int {
-                constexpr bool BIG = decltype(big)::value;
-                const size_t rl = Part2Shared<K, BIG>::bytes(pp.B2);
-                auto redo = part2_kernel<K, false, BIG>;
-                KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(redo), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl));
-                hipLaunchKernelGGL(redo, dim3(pp.B1), dim3(p2t<K, BIG>()), rl, ctx->stream, src, pp, out, fs, fe,
-                                   (const uint32_t *)fail);
-                KT_HIP(hipGetLastError());
-                return KT_OK;
-            };
-            return bigr ? redo_launch(std::true_type{}) : redo_launch(std::false_type{});
-        }
-        const bool big2 = (sizeof(K) == 8 ? j.kn.p2_big64 : j.kn.p2_big32) != 0 &&
-                          Part2Shared<K, true>::bytes(pp.B2) <= 160 * 1024;
-        auto launch = [&](auto big) -> int {
-            constexpr bool BIG = decltype(big)::value;
-            const size_t part2_lds = Part2Shared<K, BIG>::bytes(pp.B2);
-            constexpr uint32_t P2T = (uint32_t)p2t<K, BIG>();
-            if (pp.cap2 && src.srcs && j.kn.p2_fast && pp.B2 <= 4 * P2T) {
-                // fixed fine regions: the lean kernel, then the general one over the buckets that did not fit (none, normally)
-                KT_HIP(hipMemsetAsync(fail, 0, ((size_t)pp.B1 + 1) * 4, ctx->stream));
-                auto go = [&](auto pb) -> int {
-                    constexpr int PB = decltype(pb)::value;
-                    auto fast = part2_fast_kernel<K, BIG, PB>;
-                    KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fast), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)part2_lds));
-                    uint32_t grid = pp.B1;
-                    if (j.kn.p2_grid && grid > j.kn.p2_grid) grid = (uint32_t)j.kn.p2_grid;
-                    hipLaunchKernelGGL(fast, dim3(grid), dim3(P2T), part2_lds, ctx->stream, src, pp, out, fs, fe, fail);
-                    KT_HIP(hipGetLastError());
-                    return KT_OK;
-                };
-                const int rc = pp.B2 <= P2T       ? go(std::integral_constant<int, 1>{})
-                               : pp.B2 <= 2 * P2T ? go(std::integral_constant<int, 2>{})
-                                                  : go(std::integral_constant<int, 4>{});
-                if (rc) return rc;
-                auto redo = part2_kernel<K, false, BIG>;
-                KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(redo), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)part2_lds));
-                hipLaunchKernelGGL(redo, dim3(pp.B1), dim3(P2T), part2_lds, ctx->stream, src, pp, out, fs, fe,
-                                   (const uint32_t *)fail);
-                KT_HIP(hipGetLastError());
-                return KT_OK;
-            }
-            // (16-byte loads where every region starts on a 16-byte boundary: paged level-1 outputs)
-            const bool l16 = KT_P2_LOAD16 && sizeof(K) == 8 && pp.cap2 && src.srcs;
-            auto part2 = !pp.cap2 ? part2_kernel<K, false, BIG> : l16 ? part2_kernel<K, true, BIG, true> : part2_kernel<K, true, BIG>;
-            KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(part2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)part2_lds));
-            hipLaunchKernelGGL(part2, dim3(pp.B1), dim3(P2T), part2_lds, ctx->stream, src, pp, out, fs, fe,
-                               (const uint32_t *)nullptr);
-            KT_HIP(hipGetLastError());
-            return KT_OK;
-        };
-        return big2 ? launch(std::true_type{}) : launch(std::false_type{});
-    };
-    if (int rc = run_part2(p, in, keys2, m.fstart, m.fend, m.fail)) return rc;
-    const uint64_t n_fine = (uint64_t)nd * p.B2;
-    // workgroups per CU over the launch; up to two are resident per CU.  Each takes ranges b, b + grid, ... with the next
-    // one's bounds and first keys prefetched, so a few ranges per workgroup are enough - and a smaller static share evens
-    // out what the compute units get (k=31: 2 / 4 / 8 / 16 / 32 / 128 per CU = 19.4 / 19.0 / 18.6 / 18.2 / 18.0 / 17.9 ms)
-    const bool dense = !j.merge && j.kn.dense != 0;
-    bool ext = dense && ctr->xt_keys && ctr->xt_counts;  // the packed entries go straight to the export arrays
-    // (ext: the scratch behind the caller's arrays is sized by the number of workgroups - 16 per CU there: 18.2 against
-    // 17.9 ms)
-    uint64_t gb = (uint64_t)ctx->n_cu * (ext ? j.kn.build_wgs_ext : j.kn.build_wgs);
-    if (gb > n_fine) gb = n_fine;
-    size_t build_lds = (size_t)(p.m8 << (LOG2_S - 3)) * (sizeof(K) + 4);
-    // the dense build's claim lists ride behind the image where that does not cost the CU its second workgroup
-    p.lists = dense && j.kn.build_lists && build_lds + LIST_KEYS * 2 + 256 <= 80 * 1024 ? 1u : 0u;
-    if (p.lists) build_lds += LIST_KEYS * 2;
-    // (ctr k=31: dense build 29.0 ms + dense export 17.4 ms against image build 22-23.5 ms + export 27.5 ms; k=15: 13.8 +
-    // 3.2 against 12.5 + 4.7 ms; profiles/r2_build_sweep.txt.  KT_BULK_DENSE=0 builds the probing image at once.)
-    auto launch_build = [&](bool to_ext, const ExtOut &xo) -> int {
-        auto build = j.merge ? build_kernel<K, true, false>
-                     : to_ext ? build_kernel<K, false, true, true>
-                     : dense  ? build_kernel<K, false, true>
-                              : build_kernel<K, false, false>;
-        if constexpr (sizeof(K) == 4) {
-            // a table of exactly 4^k slots: the hash is a bijection onto them, the ranges' images are counters alone
-            if (dense && !j.merge && j.kn.direct && p.kbits && p.n == p.kbits && p.m8 == 8)
-                build = to_ext ? build_kernel<K, false, true, true, true> : build_kernel<K, false, true, false, true>;
-        }
-        KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(build), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)build_lds));
-        hipLaunchKernelGGL(build, dim3((uint32_t)gb), dim3(BUILD_T), build_lds, ctx->stream, (const K *)keys2, m.fstart,
-                           m.fend, p, (Slot *)ctr->slots, m.spill_n, m.spill_keys, m.spill_counts, m.spill_cap, ctr->flags,
-                           ctr->distinct, ctr->range_counts, xo);
-        KT_HIP(hipGetLastError());
-        return KT_OK;
-    };
-    if (ext) {
-        // scratch behind the caller's arrays (blocks + holes reach past the packed length), the blocks' fill, the holes' prefix.
-        // Holes: about half a block per workgroup; the rest of the scratch is the tolerance for workgroups that need more
-        // blocks than the average (KT_EXT_OVF_BLOCKS: tests make it too small on purpose).
-        const uint64_t ovf_cap = (j.kn.ext_ovf_blocks ? j.kn.ext_ovf_blocks - 1 : 2 * gb + 2) * XBLK;
-        const uint64_t max_blocks = (ctr->xt_max + ovf_cap) / XBLK + 2;
-        size_t off = 0;
-        const size_t off_fill = off;  off += (max_blocks * 4 + 255) & ~(size_t)255;
-        const size_t off_hpre = off;  off += ((max_blocks + 1) * 8 + 255) & ~(size_t)255;
-        const size_t off_info = off;  off += ((8 + XSCAN_WGS + 1) * 8 + 255) & ~(size_t)255;
-        const size_t off_ok = off;    off += (ovf_cap * 8 + 255) & ~(size_t)255;
-        const size_t off_oc = off;    off += (ovf_cap * 4 + 255) & ~(size_t)255;
-        if (int rc = ctr->b_ext.reserve(off)) return rc;
-        char *xb = (char *)ctr->b_ext.p;
-        uint64_t *hpre = (uint64_t *)(xb + off_hpre), *xinfo = (uint64_t *)(xb + off_info);
-        const ExtOut xo{ctr->xt_keys, ctr->xt_counts, ctr->xt_max, (uint64_t *)(xb + off_ok), (uint32_t *)(xb + off_oc),
-                        ovf_cap,      ctr->cursor,    (uint32_t *)(xb + off_fill), max_blocks};
-        KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-        KT_HIP(hipMemsetAsync(xo.fill, 0, max_blocks * 4, ctx->stream));
-        if (int rc = launch_build(true, xo)) return rc;
-        // close the holes: the entries beyond the packed length move into them
-        const uint64_t patch_grid = ovf_cap / XBLK + 3;
-        KT_HIP(hipMemsetAsync(xinfo, 0, (8 + XSCAN_WGS + 1) * 8, ctx->stream));  // (the scan's tickets)
-        hipLaunchKernelGGL(ext_scan_kernel, dim3(XSCAN_WGS), dim3(1024), 0, ctx->stream, xo, hpre, max_blocks, patch_grid, xinfo, ctr->flags);
-        hipLaunchKernelGGL(ext_patch_kernel, dim3((uint32_t)patch_grid), dim3(256), 0, ctx->stream, xo,
-                           (const uint64_t *)hpre, (const uint64_t *)xinfo, (const uint32_t *)ctr->flags);
-        KT_HIP(hipGetLastError());
-        // did the blocks fit (flag 4: keys spread too unevenly over the workgroups)?  One 4-byte read; the caller's
-        // next step - kt_ctr_size, kt_ctr_export - waits for these kernels anyway.
-        uint32_t fl = 0, l2_redone = 0;
-        KT_HIP(hipMemcpyAsync(&fl, ctr->flags, 4, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipMemcpyAsync(&l2_redone, m.fail + p.B1, 4, hipMemcpyDeviceToHost, ctx->stream));  // (rides on the same round trip)
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-        ctr->l2_redone = l2_redone;
-        ctr->l2_buckets = p.B1;
-        if (fl & 6u) {
-            // 4: the blocks did not fit (or could not all be patched): the ranges are built the ordinary way and
-            //    kt_ctr_export copies them out.
-            // 2: the caller's arrays are smaller than the table: the same, so that the table is NOT lost - the counts
-            //    stay in the table's own slots, kt_ctr_size / kt_ctr_export into large enough arrays work - and the
-            //    call that counted reports KT_ERR_ARG once the build is done.
-            if (fl & 2u) ctr->xt_too_small = true;
-            fl &= ~6u;
-            KT_HIP(hipMemcpyAsync(ctr->flags, &fl, 4, hipMemcpyHostToDevice, ctx->stream));
-            KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, ctx->stream));  // (a dense build starts from an empty table)
-            KT_HIP(hipStreamSynchronize(ctx->stream));                 // (fl lives on this stack frame)
-            ext = false;
-            if (j.kn.verbose) fprintf(stderr, "[bulk] export-target build redone into the table (%s)\n",
-                                      ctr->xt_too_small ? "arrays too small" : "uneven blocks");
-        }
-    }
-    if (!ext)
-        if (int rc = launch_build(false, ExtOut{})) return rc;
-    ctr->dense = dense;
-    ctr->dense_ext = ext;
-    if (!dense) {
-        TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
-        hipLaunchKernelGGL(spill_insert_kernel, dim3(ctx->n_cu), dim3(BLOCK), 0, ctx->stream, m.spill_n, m.spill_keys,
-                           m.spill_counts, m.spill_cap, t, ctr->distinct);
-    }
-    KT_HIP(hipGetLastError());
-    if (j.kn.verbose) {
-        uint64_t spilled = 0;
-        KT_HIP(hipMemcpyAsync(&spilled, m.spill_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-        fprintf(stderr, "[bulk] k=%d keys<=%llu level1=%s level2=%s %s spilled=%llu\n", ctr->k,
-                (unsigned long long)j.max_keys, j.paged ? "paged" : "exact", p.cap2 ? "fixed" : "exact",
-                j.merge ? "merge" : "build", (unsigned long long)spilled);
-    }
-    return KT_OK;
-}
-
-}  // namespace
 
 // The cursor sets of scatter1x: one per XCD that runs workgroups of this context's device.  A census launch (once per
 // context) notes which XCC_IDs there are; id -> set is their rank, the number of sets the next power of two (a device
@@ -3375,8 +3020,7 @@ static int xcc_sets(kt_ctx *ctx, uint32_t *nxs, uint32_t *xmap) {
         uint32_t *mask = nullptr, h = 0;
         if (int rc = ctx->claim(kt::AUX2, 256, "xcc_sets", &mask)) return rc;
         KT_HIP(hipMemsetAsync(mask, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(xcc_census_kernel, dim3((uint32_t)ctx->n_cu * 4), dim3(64), 0, ctx->stream, mask);
-        KT_HIP(hipGetLastError());
+        if (int rc = launch(xcc_census_kernel, dim3((uint32_t)ctx->n_cu * 4), dim3(64), 0, ctx->stream, mask)) return rc;
         KT_HIP(hipMemcpyAsync(&h, mask, 4, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
         ctx->unclaim(kt::AUX2);  // (read back: whoever plans the job may hold AUX2 next)
@@ -3406,165 +3050,436 @@ static int xcc_sets(kt_ctx *ctx, uint32_t *nxs, uint32_t *xmap) {
     return KT_OK;
 }
 
-// Plans the partition of at most `max_keys` k-mers into the table's ranges and reserves the buffers.  *eligible = 0:
-// the table shape or the batch does not suit the bulk path (or HBM is short) and the caller uses the probing path.
 // keys of room of a level-1 region for at most max_keys k-mers in B1 buckets: the bucket's share + 1/8 (the hash's own spread
 // and the cursor sets' uneven fills) + 16 lines per set, a multiple of 256
 static uint64_t region_room(uint64_t max_keys, uint32_t B1) {
     return (max_keys / B1 + max_keys / B1 / 8 + 16 * 256 + 255) / 256 * 256;
 }
 
-static int plan_job(kt_ctr *ctr, uint64_t max_keys, int *eligible) {
+// How the n hash bits that address the table split between the levels: b1 + b2 + LOG2_S == n.  False: the passes do not
+// suit a table of that size (fewer than four ranges, or more bits than two passes resolve).
+static bool split_bits(uint32_t n, const BulkKnobs &kn, uint32_t *b1, uint32_t *b2) {
+    if (n < LOG2_S + 2 || n > LOG2_S + 21) return false;
+    const uint32_t fb = n - LOG2_S;
+    *b1 = (fb + 1) / 2;
+    if (*b1 > 10) *b1 = 10;  // level 1 keeps its per-digit LDS arrays at 1024 entries
+    // level 2's write-combining kernel wants a fan-out of 512 or 1024 (one line per fine bucket; below that the sort-buffer
+    // kernel runs): tables of 2^16 .. 2^17 ranges give level 2 nine bits instead of eight (ctr k=15, 2^17 ranges: level 1 with
+    // 256 instead of 512 buckets 23.7 -> 23.3 ms, level 2 14.4 -> 13.8 ms)
+    if (fb >= 16 && fb - *b1 < 9) *b1 = fb - 9;
+    if (kn.b1 && kn.b1 <= 10 && kn.b1 < fb && fb - kn.b1 <= 11) *b1 = (uint32_t)kn.b1;  // (KT_BULK_B1: the split between the levels, experiments)
+    *b2 = fb - *b1;
+    return *b2 <= 11;  // (a pass resolves at most 10 (level 1) / 11 (level 2) hash bits)
+}
+
+// the record descriptors as RecordSource reads them: n_runs x {blocks, n_rec}, then n_runs + 1 cumulative block counts.
+// Returns the blocks of all the runs.
+static uint64_t record_descriptors(const ktsk::RecRun *runs, uint32_t n_runs, std::vector<uint64_t> *h) {
+    h->assign((size_t)n_runs * 3 + 1, 0);
+    uint64_t blocks = 0;
+    for (uint32_t i = 0; i < n_runs; i++) {
+        (*h)[2 * (size_t)i] = (uint64_t)(uintptr_t)runs[i].blocks;
+        (*h)[2 * (size_t)i + 1] = runs[i].n_rec;
+        (*h)[2 * (size_t)n_runs + i] = blocks;
+        blocks += (runs[i].n_rec + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS;
+    }
+    (*h)[3 * (size_t)n_runs] = blocks;
+    return blocks;
+}
+
+// what a job launched, by name in the verbose line (report)
+enum Level1 { L1_EXACT, L1_SCATTER1X, L1_SCATTER1Y };
+enum Level2 { L2_GENERAL, L2_FAST, L2_SWWC };
+enum Build { BUILD_MERGE, BUILD_IMAGE, BUILD_DENSE, BUILD_DENSE_EXT, BUILD_DIRECT, BUILD_DIRECT_EXT };
+static const char *const LEVEL1_NAMES[] = {"exact", "scatter1x", "scatter1y"};
+static const char *const LEVEL2_NAMES[] = {"general", "fast", "swwc"};
+static const char *const BUILD_NAMES[] = {"merge", "image", "dense", "dense-ext", "direct", "direct-ext"};
+
+// One job of a table: a method is a stage, and leaves here and on the device what the later ones read.  kt_bulk_begin
+// plans, the kt_bulk_add_* entry points add sources (with paged level 1 each source is scattered as it is added),
+// kt_bulk_finish runs close_level1, level2, build and report.
+struct kt_bulk_job {
+    kt_ctr *ctr = nullptr;
+    kt_ctx *ctx = nullptr;
+    Plan p{};
+    BulkKnobs kn{};
+    Meta m{};
+    bool narrow = false;  // 32-bit keys through the partition passes (k <= 16)
+    bool paged = false, merge = false, open = false;
+    uint64_t max_keys = 0, added_bound = 0;
+    std::vector<SourceRec> srcs;
+    kt_seg_src p2_src{};  // where part2 reads every bucket from: the level-1 output (host copy of its one device entry)
+    // record sources (kt_bulk_add_records): their descriptors on the device (ctr->b_desc), the host copies the uploads read
+    size_t desc_used = 0;
+    std::vector<std::vector<uint64_t>> desc_host;
+    // the kernels the stages chose
+    Level1 l1 = L1_EXACT;
+    Level2 l2 = L2_GENERAL;
+    Build built = BUILD_MERGE;
+    uint32_t build_grid = 0;  // the build's launch: workgroups, dynamic LDS
+    size_t build_lds = 0;
+    size_t ksz() const { return narrow ? 4 : 8; }
+
+    // the arrays of the metadata buffer: their bytes, and from `at`, where it is set, their places in m
+    size_t carve_meta(uint8_t *at) {
+        const uint64_t per_wg = (uint64_t)p.G * p.B1, fine = (uint64_t)p.B1 * p.B2 + 1;
+        return ktl::carve_parts<256>(at, &m.H, per_wg, &m.O, per_wg, &m.bstart, p.B1 + 1, &m.fstart, fine, &m.fend, fine, &m.gcur, p.B1,
+                                     &m.xcur, 8 * p.B1, &m.dump, 1024 * 2, &m.srcs, 1, &m.ovf, 1, &m.fail, p.B1 + 2, &m.spill_n, 1,
+                                     &m.spill_keys, m.spill_cap, &m.spill_counts, m.spill_cap);
+    }
+    // the two key arrays (the level-1 output, keys2) + the metadata.  The paged layout wants 1/8 more room than the keys:
+    // where HBM is short the exact one is tried before giving up.  False: not enough HBM for the bulk buffers.
+    bool reserve(uint64_t cap1) {
+        const size_t meta = carve_meta(nullptr);
+        auto all = [&](uint64_t keys) {
+            return ctr->b_keys1.reserve(keys * ksz()) == KT_OK && ctr->b_keys2.reserve(keys * ksz()) == KT_OK &&
+                   ctr->b_meta.reserve(meta) == KT_OK;
+        };
+        bool have = all(paged ? cap1 * p.B1 : max_keys);
+        if (!have && paged) {
+            paged = false;
+            have = all(max_keys);
+            if (have) kt::set_error("");
+        }
+        if (!have) {
+            ctr->b_keys1.release();
+            ctr->b_keys2.release();
+            ctr->b_meta.release();
+            kt::set_error("");
+        }
+        return have;
+    }
+    // paged level 1 (no hist1): the regions' room in the plan, the cursors zeroed, the cursor sets
+    int arm_paged(uint64_t cap1) {
+        p.cap1 = cap1;
+        p.room1 = cap1;
+        p.cap2 = kn.fixed2 ? cap1 / p.B2 / (128 / ksz()) * (128 / ksz()) : 0;  // (whole cache lines: every fine region starts on one)
+        KT_HIP(hipMemsetAsync(m.gcur, 0, (size_t)p.B1 * 8, ctx->stream));
+        KT_HIP(hipMemsetAsync(m.ovf, 0, 8, ctx->stream));
+        // (per-XCD cursors: no pages; the room beyond the keys' share covers the sets' uneven fills - every set's lines reach as
+        // far as the fullest set's - and the same 1/8 for the hash's own spread; a multiple of 8 sets x 32 keys)
+        if (int rc = xcc_sets(ctx, &p.nxs, &p.xmap)) return rc;
+        // (a batch of a few dozen units does not spread evenly over the XCDs - a handful of workgroups, some XCDs with
+        // one more than others - and a set's share of a region is only an eighth of it: such batches append through
+        // one set; what the sets buy, whole lines out of the L2, is nothing they would notice)
+        if (max_keys < (16ull << 20) && !getenv("KT_S1X_SETS")) {
+            p.nxs = 0;
+            p.xmap = 0;
+        }
+        KT_HIP(hipMemsetAsync(m.xcur, 0, (size_t)8 * p.B1 * 8, ctx->stream));
+        return KT_OK;
+    }
+
+    // Plans the partition of at most `max_keys` k-mers into the table's ranges and reserves the buffers.  *eligible = 0:
+    // the table shape or the batch does not suit the bulk path (or HBM is short) and the caller uses the probing path.
+    int plan(kt_ctr *table, const BulkKnobs &knobs, uint64_t keys_bound, int *eligible) {
+        ctr = table;
+        ctx = table->ctx;
+        kn = knobs;
+        ctr->stage_n = 0;  // (a job changes the table: kt_ctr_export_stage's entries are stale)
+        open = false;
+        srcs.clear();
+        merge = !ctr->empty;  // the table holds data: every range is rebuilt from what it has + the batch
+        if (merge)
+            if (int rc = kt_table_image(ctr)) return rc;  // (a densely packed table gets its probing image first)
+        narrow = ctr->k <= 16 && ctr->kbits != 0;  // (kt_ctr_create: every table of k <= 16 hashes with ktd::nhash)
+        max_keys = keys_bound;
+        added_bound = 0;
+        p = Plan{};
+        p.n = 64 - ctr->shift;
+        p.kbits = ctr->kbits;
+        p.m8 = ctr->m8;
+#if KT_ABLATION
+        p.dbg = (uint32_t)env_u64("KT_BUILD_DBG", 0);  // bits 0-7: build_kernel, 8-11: part2, 12-15: scatter1x
+#endif
+        if (!split_bits(p.n, kn, &p.b1, &p.b2)) return KT_OK;
+        // a rebuild moves the whole table: small batches are cheaper through the atomics
+        if (merge && max_keys < ctr->cap / (kn.merge_div ? kn.merge_div : 1)) return KT_OK;
+        p.B1 = 1u << p.b1;
+        p.B2 = 1u << p.b2;
+        // persistent level-1 workgroups (the same for every source of the job): two per CU for the per-unit kernels; the wide
+        // kernel launches G / 2 of them, one resident per CU (KT_BULK_G_MULT > 1: more, shorter-lived workgroups)
+        p.G = (uint32_t)ctx->n_cu * 2 * (uint32_t)(kn.g_mult ? kn.g_mult : 1);
+        // paged level 1: room per bucket = its share of the most keys there can be + 1/8 (region_room), every region
+        // starting on a cache line whatever the key size
+        paged = kn.paged != 0 && !ctr->paged_failed;
+        const uint64_t cap1 = region_room(max_keys, p.B1);
+        if (cap1 * ksz() >= (1ull << 31)) paged = false;  // (part2 addresses a bucket's fixed regions through 32-bit buffer offsets)
+        // spill list: keys of ranges that hold more distinct keys than slots (they fail in the probing path: table full)
+        m = Meta{};
+        m.spill_cap = 1u << 20;
+        if (!reserve(cap1)) return KT_OK;  // incremental path
+        carve_meta((uint8_t *)ctr->b_meta.p);
+        KT_HIP(hipMemsetAsync(m.spill_n, 0, 8, ctx->stream));
+        if (paged)
+            if (int rc = arm_paged(cap1)) return rc;
+        desc_used = 0;
+        desc_host.clear();
+        l1 = L1_EXACT;
+        open = true;
+        *eligible = 1;
+        return KT_OK;
+    }
+
+    // one more source of the job; with paged level 1 it is scattered now (exact offsets: in close_level1, over all the sources)
+    int add(const SourceRec &r, uint64_t bound);
+
+    template <class K>
+    int level1_paged(const SourceRec &r) {
+        K *keys1 = (K *)ctr->b_keys1.p;
+        // two sort buffers, the copy-out spread over the next round - or, a shape that does not fit the LDS, one buffer
+        l1 = kn.s1y && Scatter1YShared<K, 1024>::bytes(p.B1) <= 160 * 1024 ? L1_SCATTER1Y : L1_SCATTER1X;
+        const uint32_t mult = (uint32_t)(kn.g_mult ? kn.g_mult : 1);
+        const uint32_t cus = (uint32_t)ctx->n_cu > 2 * ctr->l1_spare_cus ? (uint32_t)ctx->n_cu - ctr->l1_spare_cus : (uint32_t)ctx->n_cu;
+        return with_source(r, [&](const auto &src) -> int {
+            using S = std::decay_t<decltype(src)>;
+            if (l1 == L1_SCATTER1Y)
+                return launch(scatter1y_kernel<S, K, 1024>, dim3(cus * mult), dim3(1024), Scatter1YShared<K, 1024>::bytes(p.B1),
+                              ctx->stream, src, p, m.xcur, m.ovf, keys1, m.dump);
+            constexpr int T = KT_S1X_T;
+            return launch(scatter1x_kernel<S, K, T>, dim3(cus * (1024 / T) * mult), dim3(T), sizeof(Scatter1XShared<K, T>),
+                          ctx->stream, src, p, m.xcur, m.ovf, keys1, m.dump);
+        });
+    }
+
+    template <class K>
+    int level1_exact() {  // hist1 over every source, scan1, scatter1 over every source
+        K *keys1 = (K *)ctr->b_keys1.p;
+        l1 = L1_EXACT;
+        KT_HIP(hipMemsetAsync(m.H, 0, (size_t)p.G * p.B1 * 4, ctx->stream));
+        for (const SourceRec &r : srcs) {
+            const int rc = with_source(r, [&](const auto &src) -> int {
+                using S = std::decay_t<decltype(src)>;
+                return launch(hist1_kernel<S>, dim3(p.G), dim3(BLOCK), 0, ctx->stream, src, p, m.H);
+            });
+            if (rc) return rc;
+        }
+        if (int rc = launch(scan1_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.H, p, m.O, m.bstart)) return rc;
+        for (const SourceRec &r : srcs) {
+            const int rc = with_source(r, [&](const auto &src) -> int {
+                using S = std::decay_t<decltype(src)>;
+                return launch(scatter1_kernel<S, K>, dim3(p.G), dim3(BLOCK), sizeof(Scatter1Shared<K>), ctx->stream, src, p, m.O, keys1);
+            });
+            if (rc) return rc;
+        }
+        return KT_OK;
+    }
+
+    // Level 1 is complete behind this.  Paged: the regions' tails, then the one host round trip of the build - did every
+    // bucket fit its region?  A skewed batch is redone from its sources with exact offsets.
+    template <class K>
+    int close_level1() {
+        if (!paged) return level1_exact<K>();
+        if (int rc = launch(xcd_tails_kernel<K>, dim3(p.B1), dim3(BLOCK), 0, ctx->stream, p, m.xcur, m.gcur, (K *)ctr->b_keys1.p)) return rc;
+        uint32_t ovf = 0;
+        KT_HIP(hipMemcpyAsync(&ovf, m.ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        if (!ovf) return KT_OK;
+        // skewed batch: exact offsets after all, and no more paged attempts on this table
+        paged = false;
+        ctr->paged_failed = true;
+        p.cap1 = 0;
+        p.cap2 = 0;
+        if (added_bound > ctr->b_keys1.cap / sizeof(K))  // (the paged room is always the larger)
+            return kt::fail(KT_ERR_NOMEM, "bulk build: key buffers too small for the exact layout");
+        return level1_exact<K>();
+    }
+
+    // Level 2: every level-1 bucket into its B2 fine buckets in keys2, m.fstart / m.fend their bounds.  Where the fine
+    // buckets own fixed room (paged level 1) one attempt runs with them - whole lines out of LDS (swwc) where the fan-out
+    // gives every fine bucket about a line's worth of keys per chunk, the sort buffer (fast) below that - and raises
+    // m.fail[bucket] for a bucket that outgrows its room; the exact kernel behind it takes those buckets (none, normally).
+    // Without fixed room it takes them all.
+    template <class K>
+    int level2() {
+        P2In in{ctr->b_keys1.p, m.bstart, nullptr, 0};  // where part2 finds every bucket: the level-1 output
+        if (paged) {
+            p2_src = kt_seg_src{ctr->b_keys1.p, m.gcur, p.cap1};
+            KT_HIP(hipMemcpyAsync(m.srcs, &p2_src, sizeof(kt_seg_src), hipMemcpyHostToDevice, ctx->stream));
+            in.srcs = m.srcs;
+            in.n_src = 1;
+        }
+        l2 = !(p.cap2 && in.srcs)                                                              ? L2_GENERAL
+             : kn.p2_swwc && p.B2 >= 512 && SwwcShared<K>::bytes(p.B2) <= 160 * 1024 ? L2_SWWC
+                                                                                         : L2_FAST;
+        const bool big = (sizeof(K) == 8 ? kn.p2_big64 : kn.p2_big32) != 0 && Part2Shared<K, true>::bytes(p.B2) <= 160 * 1024;
+        return big ? launch_level2<K, true>(in) : launch_level2<K, false>(in);
+    }
+    template <class K, bool BIG>
+    int launch_level2(const P2In &in) {
+        K *keys2 = (K *)ctr->b_keys2.p;
+        constexpr uint32_t P2T = (uint32_t)p2t<K, BIG>();
+        const size_t lds = Part2Shared<K, BIG>::bytes(p.B2);
+        uint32_t grid = p.B1;
+        if (kn.p2_grid && grid > kn.p2_grid) grid = (uint32_t)kn.p2_grid;
+        if (l2 != L2_GENERAL) KT_HIP(hipMemsetAsync(m.fail, 0, ((size_t)p.B1 + 1) * 4, ctx->stream));
+        if (l2 == L2_SWWC) {
+            if (int rc = launch(part2_swwc_kernel<K>, dim3(grid), dim3(swwc_t<K>()), SwwcShared<K>::bytes(p.B2), ctx->stream, in, p,
+                                keys2, m.fstart, m.fend, m.fail))
+                return rc;
+        } else if (l2 == L2_FAST) {  // (PB: fine buckets per thread of the scan)
+            auto fast = p.B2 <= P2T       ? part2_fast_kernel<K, BIG, 1>
+                        : p.B2 <= 2 * P2T ? part2_fast_kernel<K, BIG, 2>
+                                          : part2_fast_kernel<K, BIG, 4>;
+            if (int rc = launch(fast, dim3(grid), dim3(P2T), lds, ctx->stream, in, p, keys2, m.fstart, m.fend, m.fail)) return rc;
+        }
+        return launch(part2_exact_kernel<K, BIG>, dim3(p.B1), dim3(P2T), lds, ctx->stream, in, p, keys2, m.fstart, m.fend,
+                      l2 == L2_GENERAL ? nullptr : m.fail);
+    }
+
+    // which build a job runs: a table with data is merged range by range; a fresh one is left densely packed (`dense`; `ext`:
+    // packed into the caller's export arrays) or, KT_BULK_DENSE=0, as its probing image at once
+    // (ctr k=31: dense build 29.0 ms + dense export 17.4 ms against image build 22-23.5 ms + export 27.5 ms; k=15: 13.8 +
+    // 3.2 against 12.5 + 4.7 ms; profiles/r2_build_sweep.txt)
+    template <class K>
+    Build build_variant(bool dense, bool ext) const {
+        if (merge) return BUILD_MERGE;
+        if (!dense) return BUILD_IMAGE;
+        // a table of exactly 4^k slots: the hash is a bijection onto them, the ranges' images are counters alone
+        if (sizeof(K) == 4 && kn.direct && p.kbits && p.n == p.kbits && p.m8 == 8) return ext ? BUILD_DIRECT_EXT : BUILD_DIRECT;
+        return ext ? BUILD_DENSE_EXT : BUILD_DENSE;
+    }
+    template <class K>
+    int launch_build(Build b, const ExtOut &xo) {
+        auto kern = b == BUILD_MERGE       ? build_kernel<K, true, false>
+                    : b == BUILD_IMAGE     ? build_kernel<K, false, false>
+                    : b == BUILD_DENSE_EXT ? build_kernel<K, false, true, true>
+                                           : build_kernel<K, false, true>;
+        if constexpr (sizeof(K) == 4) {
+            if (b == BUILD_DIRECT) kern = build_kernel<K, false, true, false, true>;
+            if (b == BUILD_DIRECT_EXT) kern = build_kernel<K, false, true, true, true>;
+        }
+        return launch(kern, dim3(build_grid), dim3(BUILD_T), build_lds, ctx->stream, (const K *)ctr->b_keys2.p, m.fstart, m.fend, p,
+                      (Slot *)ctr->slots, m.spill_n, m.spill_keys, m.spill_counts, m.spill_cap, ctr->flags, ctr->distinct,
+                      ctr->range_counts, xo);
+    }
+
+    // The build `b` with the packed entries sent straight to the export target, the holes between the workgroups' blocks
+    // closed behind it.  *delivered = false: the target holds nothing and the table is as before the build - the caller
+    // builds the ranges the ordinary way and kt_ctr_export copies them out.
+    template <class K>
+    int build_to_target(Build b, bool *delivered) {
+        // scratch behind the caller's arrays (blocks + holes reach past the packed length), the blocks' fill, the holes' prefix.
+        // Holes: about half a block per workgroup; the rest of the scratch is the tolerance for workgroups that need more
+        // blocks than the average (KT_EXT_OVF_BLOCKS: tests make it too small on purpose).
+        const uint64_t ovf_cap = (kn.ext_ovf_blocks ? kn.ext_ovf_blocks - 1 : 2 * (uint64_t)build_grid + 2) * XBLK;
+        const uint64_t max_blocks = (ctr->xt_max + ovf_cap) / XBLK + 2, n_info = 8 + XSCAN_WGS + 1;
+        ExtOut xo{ctr->xt_keys, ctr->xt_counts, ctr->xt_max, nullptr, nullptr, ovf_cap, ctr->cursor, nullptr, max_blocks};
+        uint64_t *hpre = nullptr, *xinfo = nullptr;
+        auto parts = [&](uint8_t *at) {
+            return ktl::carve_parts<256>(at, &xo.fill, max_blocks, &hpre, max_blocks + 1, &xinfo, n_info, &xo.ovf_keys, ovf_cap,
+                                         &xo.ovf_counts, ovf_cap);
+        };
+        if (int rc = ctr->b_ext.reserve(parts(nullptr))) return rc;
+        parts((uint8_t *)ctr->b_ext.p);
+        KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
+        KT_HIP(hipMemsetAsync(xo.fill, 0, max_blocks * 4, ctx->stream));
+        if (int rc = launch_build<K>(b, xo)) return rc;
+        // close the holes: the entries beyond the packed length move into them
+        const uint64_t patch_grid = ovf_cap / XBLK + 3;
+        KT_HIP(hipMemsetAsync(xinfo, 0, n_info * 8, ctx->stream));  // (the scan's tickets)
+        if (int rc = launch(ext_scan_kernel, dim3(XSCAN_WGS), dim3(1024), 0, ctx->stream, xo, hpre, max_blocks, patch_grid, xinfo, ctr->flags))
+            return rc;
+        if (int rc = launch(ext_patch_kernel, dim3((uint32_t)patch_grid), dim3(256), 0, ctx->stream, xo, hpre, xinfo, ctr->flags)) return rc;
+        // did the blocks fit (flag 4: keys spread too unevenly over the workgroups)?  One 4-byte read; the caller's
+        // next step - kt_ctr_size, kt_ctr_export - waits for these kernels anyway.
+        uint32_t fl = 0, l2_redone = 0;
+        KT_HIP(hipMemcpyAsync(&fl, ctr->flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipMemcpyAsync(&l2_redone, m.fail + p.B1, 4, hipMemcpyDeviceToHost, ctx->stream));  // (rides on the same round trip)
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        ctr->l2_redone = l2_redone;
+        ctr->l2_buckets = p.B1;
+        *delivered = !(fl & 6u);
+        if (*delivered) return KT_OK;
+        // 4: the blocks did not fit (or could not all be patched).
+        // 2: the caller's arrays are smaller than the table: the table is NOT lost - the counts stay in the table's own
+        //    slots, kt_ctr_size / kt_ctr_export into large enough arrays work - and the call that counted reports
+        //    KT_ERR_ARG once the build is done.
+        if (fl & 2u) ctr->xt_too_small = true;
+        fl &= ~6u;
+        KT_HIP(hipMemcpyAsync(ctr->flags, &fl, 4, hipMemcpyHostToDevice, ctx->stream));
+        KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, ctx->stream));  // (a dense build starts from an empty table)
+        KT_HIP(hipStreamSynchronize(ctx->stream));                 // (fl lives on this stack frame)
+        if (kn.verbose) fprintf(stderr, "[bulk] export-target build redone into the table (%s)\n",
+                                ctr->xt_too_small ? "arrays too small" : "uneven blocks");
+        return KT_OK;
+    }
+
+    // The range builds: one workgroup per fine bucket = range of the table, over keys2.  With an export target: try the
+    // build into it, read the flags, redo into the table where it did not fit.
+    template <class K>
+    int build() {
+        const uint64_t n_fine = (uint64_t)p.B1 * p.B2;
+        const bool dense = !merge && kn.dense != 0;
+        bool ext = dense && ctr->xt_keys && ctr->xt_counts;  // the packed entries go straight to the export arrays
+        // workgroups per CU over the launch; up to two are resident per CU.  Each takes ranges b, b + grid, ... with the next
+        // one's bounds and first keys prefetched, so a few ranges per workgroup are enough - and a smaller static share evens
+        // out what the compute units get (k=31: 2 / 4 / 8 / 16 / 32 / 128 per CU = 19.4 / 19.0 / 18.6 / 18.2 / 18.0 / 17.9 ms)
+        // (ext: the scratch behind the caller's arrays is sized by the number of workgroups - 16 per CU there: 18.2 against
+        // 17.9 ms)
+        const uint64_t gb = (uint64_t)ctx->n_cu * (ext ? kn.build_wgs_ext : kn.build_wgs);
+        build_grid = (uint32_t)(gb > n_fine ? n_fine : gb);
+        build_lds = (size_t)(p.m8 << (LOG2_S - 3)) * (sizeof(K) + 4);
+        // the dense build's claim lists ride behind the image where that does not cost the CU its second workgroup
+        p.lists = dense && kn.build_lists && build_lds + LIST_KEYS * 2 + 256 <= 80 * 1024 ? 1u : 0u;
+        if (p.lists) build_lds += LIST_KEYS * 2;
+        built = build_variant<K>(dense, ext);
+        if (ext) {
+            if (int rc = build_to_target<K>(built, &ext)) return rc;
+            if (!ext) built = build_variant<K>(dense, false);
+        }
+        if (!ext)
+            if (int rc = launch_build<K>(built, ExtOut{})) return rc;
+        ctr->dense = dense;
+        ctr->dense_ext = ext;
+        if (dense) return KT_OK;
+        TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
+        return launch(spill_insert_kernel, dim3(ctx->n_cu), dim3(BLOCK), 0, ctx->stream, m.spill_n, m.spill_keys, m.spill_counts,
+                      m.spill_cap, t, ctr->distinct);
+    }
+
+    // KT_BULK_VERBOSE: one line per job - what it was planned for, and which kernels the stages above chose
+    int report() {
+        if (!kn.verbose) return KT_OK;
+        uint64_t spilled = 0;
+        KT_HIP(hipMemcpyAsync(&spilled, m.spill_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        fprintf(stderr, "[bulk] k=%d keys<=%llu level1=%s level2=%s %s spilled=%llu l1=%s l2=%s build=%s\n", ctr->k,
+                (unsigned long long)max_keys, paged ? "paged" : "exact", p.cap2 ? "fixed" : "exact", merge ? "merge" : "build",
+                (unsigned long long)spilled, LEVEL1_NAMES[l1], LEVEL2_NAMES[l2], BUILD_NAMES[built]);
+        return KT_OK;
+    }
+};
+
+void kt_bulk_job_free(kt_bulk_job *job) { delete job; }
+
+// f(a value of the type the job's keys travel as through the partition passes)
+template <class F>
+static int with_key_type(const kt_bulk_job &j, F &&f) {
+    return j.narrow ? f(uint32_t{}) : f(uint64_t{});
+}
+
+int kt_bulk_job::add(const SourceRec &r, uint64_t bound) {
+    if (added_bound + bound > max_keys) return kt::fail(KT_ERR_ARG, "bulk build: more keys than the job was planned for");
+    added_bound += bound;
+    srcs.push_back(r);
+    if (!paged) return KT_OK;
+    return with_key_type(*this, [&](auto key) { return level1_paged<decltype(key)>(r); });
+}
+
+static int job_add(kt_ctr *ctr, const SourceRec &r, uint64_t bound) {
+    if (!ctr->job || !ctr->job->open) return kt::fail(KT_ERR_ARG, "bulk build: no open job");
+    return ctr->job->add(r, bound);
+}
+
+int kt_bulk_begin(kt_ctr *ctr, uint64_t max_keys, int *eligible) {
     *eligible = 0;
-    kt_ctx *ctx = ctr->ctx;
     const BulkKnobs kn = read_knobs();
     if (kn.bulk == 0) return KT_OK;
     if (max_keys < kn.min_bases) return KT_OK;  // small batches: atomics are fine
     if (!ctr->job) ctr->job = new (std::nothrow) kt_bulk_job();
     if (!ctr->job) return kt::fail(KT_ERR_NOMEM, "bulk build: host alloc");
-    kt_bulk_job &j = *ctr->job;
-    ctr->stage_n = 0;  // (a job changes the table: kt_ctr_export_stage's entries are stale)
-    j.kn = kn;
-    j.open = false;
-    j.srcs.clear();
-    j.merge = !ctr->empty;  // the table holds data: every range is rebuilt from what it has + the batch
-    if (j.merge)
-        if (int rc = kt_table_image(ctr)) return rc;  // (a densely packed table gets its probing image first)
-    j.narrow = ctr->k <= 16 && ctr->kbits != 0;  // (kt_ctr_create: every table of k <= 16 hashes with ktd::nhash)
-    j.max_keys = max_keys;
-    j.added_bound = 0;
-    const size_t ksz = j.narrow ? 4 : 8;
-    Plan p{};
-    p.n = 64 - ctr->shift;
-    p.kbits = ctr->kbits;
-    p.m8 = ctr->m8;
-#if KT_ABLATION
-    p.dbg = (uint32_t)env_u64("KT_BUILD_DBG", 0);  // bits 0-7: build_kernel, 8-11: part2, 12-15: scatter1x
-#endif
-    if (p.n < LOG2_S + 2 || p.n > LOG2_S + 21) return KT_OK;
-    // a rebuild moves the whole table: small batches are cheaper through the atomics
-    if (j.merge && max_keys < ctr->cap / (kn.merge_div ? kn.merge_div : 1)) return KT_OK;
-    const uint32_t fb = p.n - LOG2_S;
-    p.b1 = (fb + 1) / 2;
-    if (p.b1 > 10) p.b1 = 10;  // level 1 keeps its per-digit LDS arrays at 1024 entries
-    // level 2's write-combining kernel wants a fan-out of 512 or 1024 (one line per fine bucket; below that the sort-buffer
-    // kernel runs): tables of 2^16 .. 2^17 ranges give level 2 nine bits instead of eight (ctr k=15, 2^17 ranges: level 1 with
-    // 256 instead of 512 buckets 23.7 -> 23.3 ms, level 2 14.4 -> 13.8 ms)
-    if (fb >= 16 && fb - p.b1 < 9) p.b1 = fb - 9;
-    if (kn.b1 && kn.b1 <= 10 && kn.b1 < fb && fb - kn.b1 <= 11) p.b1 = (uint32_t)kn.b1;  // (KT_BULK_B1: the split between the levels, experiments)
-    p.b2 = fb - p.b1;
-    if (p.b2 > 11) return KT_OK;  // (a pass resolves at most 10 (level 1) / 11 (level 2) hash bits)
-    p.B1 = 1u << p.b1;
-    p.B2 = 1u << p.b2;
-    const uint32_t nd = p.B1;
-    // persistent level-1 workgroups (the same for every source of the job): two per CU for the per-unit kernels; the wide
-    // kernel launches G / 2 of them, one resident per CU (KT_BULK_G_MULT > 1: more, shorter-lived workgroups)
-    p.G = (uint32_t)ctx->n_cu * 2 * (uint32_t)(kn.g_mult ? kn.g_mult : 1);
-    // paged level 1 (no hist1): room per bucket = its share of the most keys there can be + 1/8 + a page per
-    // workgroup (every workgroup leaves at most one partly used page per bucket)
-    bool paged = kn.paged != 0 && !ctr->paged_failed;
-    // (rounded to a multiple of 128 keys: every region starts on a cache line, whatever the key size)
-    // (per-XCD cursors: no pages; the room beyond the keys' share covers the sets' uneven fills - every set's lines reach as
-    // far as the fullest set's - and the same 1/8 for the hash's own spread; a multiple of 8 sets x 32 keys)
-    const bool xcd = paged;
-    const uint64_t cap1 = region_room(max_keys, p.B1), room1 = cap1;
-    if (room1 * ksz >= (1ull << 31)) paged = false;  // (part2 addresses a bucket's fixed regions through 32-bit buffer offsets)
-    uint64_t room_in = paged ? cap1 * p.B1 : max_keys;  // the level-1 output
-    uint64_t room_out = paged ? room1 * nd : max_keys;  // keys2
-
-    // buffers: two key arrays + metadata; if HBM is short, fall back to the incremental path
-    // spill list: keys of ranges that hold more distinct keys than slots (they fail in the probing path: table full)
-    const uint64_t spill_cap = 1u << 20;
-    size_t meta = 0;
-    const size_t off_H = meta;       meta += ((size_t)p.G * p.B1 * 4 + 255) & ~(size_t)255;
-    const size_t off_O = meta;       meta += ((size_t)p.G * p.B1 * 8 + 255) & ~(size_t)255;
-    const size_t off_bs = meta;      meta += ((size_t)(p.B1 + 1) * 8 + 255) & ~(size_t)255;
-    const size_t off_fs = meta;      meta += (((size_t)nd * p.B2 + 1) * 8 + 255) & ~(size_t)255;
-    const size_t off_fe = meta;      meta += (((size_t)nd * p.B2 + 1) * 8 + 255) & ~(size_t)255;
-    const size_t off_gc = meta;      meta += ((size_t)p.B1 * 8 + 255) & ~(size_t)255;
-    const size_t off_xc = meta + 0;  meta += ((size_t)8 * p.B1 * 8 + 255) & ~(size_t)255;
-    const size_t off_du = meta;      meta += 1024 * 16;
-    const size_t off_sr = meta;      meta += 256;
-    const size_t off_ov = meta;      meta += 256;
-    const size_t off_fl = meta;      meta += (((size_t)nd + 2) * 4 + 255) & ~(size_t)255;
-    const size_t off_sn = meta;      meta += 256;
-    const size_t off_sk = meta;      meta += (spill_cap * 8 + 255) & ~(size_t)255;
-    const size_t off_sc = meta;      meta += (spill_cap * 4 + 255) & ~(size_t)255;
-    auto reserve_all = [&]() {
-        return ctr->b_keys1.reserve(room_in * ksz) == KT_OK && ctr->b_keys2.reserve(room_out * ksz) == KT_OK &&
-               ctr->b_meta.reserve(meta) == KT_OK;
-    };
-    bool have = reserve_all();
-    if (!have && paged) {  // the paged layout wants 1/8 more room than the keys: try the exact one before giving up
-        paged = false;
-        room_in = room_out = max_keys;
-        have = reserve_all();
-        if (have) kt::set_error("");
-    }
-    if (!have) {
-        ctr->b_keys1.release();
-        ctr->b_keys2.release();
-        ctr->b_meta.release();
-        kt::set_error("");
-        return KT_OK;  // not enough HBM for the bulk buffers: incremental path
-    }
-    char *mb = (char *)ctr->b_meta.p;
-    Meta m{};
-    m.H = (uint32_t *)(mb + off_H);
-    m.O = (uint64_t *)(mb + off_O);
-    m.bstart = (uint64_t *)(mb + off_bs);
-    m.fstart = (uint64_t *)(mb + off_fs);
-    m.fend = (uint64_t *)(mb + off_fe);
-    m.gcur = (uint64_t *)(mb + off_gc);
-    m.srcs = (kt_seg_src *)(mb + off_sr);
-    m.xcur = (unsigned long long *)(mb + off_xc);
-    m.dump = (unsigned long long *)(mb + off_du);
-    m.ovf = (uint32_t *)(mb + off_ov);
-    m.fail = (uint32_t *)(mb + off_fl);
-    m.spill_n = (uint64_t *)(mb + off_sn);
-    m.spill_keys = (uint64_t *)(mb + off_sk);
-    m.spill_counts = (uint32_t *)(mb + off_sc);
-    m.spill_cap = spill_cap;
-    KT_HIP(hipMemsetAsync(m.spill_n, 0, 8, ctx->stream));
-    if (paged) {
-        p.cap1 = cap1;
-        p.room1 = room1;
-        p.cap2 = kn.fixed2 ? room1 / p.B2 / (128 / ksz) * (128 / ksz) : 0;  // (whole cache lines: every fine region starts on one)
-        KT_HIP(hipMemsetAsync(m.gcur, 0, (size_t)p.B1 * 8, ctx->stream));
-        KT_HIP(hipMemsetAsync(m.ovf, 0, 8, ctx->stream));
-        if (xcd) {
-            if (int rc = xcc_sets(ctx, &p.nxs, &p.xmap)) return rc;
-            // (a batch of a few dozen units does not spread evenly over the XCDs - a handful of workgroups, some XCDs with
-            // one more than others - and a set's share of a region is only an eighth of it: such batches append through
-            // one set; what the sets buy, whole lines out of the L2, is nothing they would notice)
-            if (max_keys < (16ull << 20) && !getenv("KT_S1X_SETS")) {
-                p.nxs = 0;
-                p.xmap = 0;
-            }
-            KT_HIP(hipMemsetAsync(m.xcur, 0, (size_t)8 * p.B1 * 8, ctx->stream));
-        }
-    }
-    j.xcd = paged && xcd;
-    j.desc_used = 0;
-    j.desc_host.clear();
-    j.p = p;
-    j.m = m;
-    j.paged = paged;
-    j.open = true;
-    *eligible = 1;
-    return KT_OK;
-}
-
-int kt_bulk_begin(kt_ctr *ctr, uint64_t max_keys, int *eligible) { return plan_job(ctr, max_keys, eligible); }
-
-static int job_add(kt_ctr *ctr, const SourceRec &r, uint64_t bound) {
-    kt_bulk_job *job = ctr->job;
-    if (!job || !job->open) return kt::fail(KT_ERR_ARG, "bulk build: no open job");
-    if (job->added_bound + bound > job->max_keys) return kt::fail(KT_ERR_ARG, "bulk build: more keys than the job was planned for");
-    job->added_bound += bound;
-    job->srcs.push_back(r);
-    if (!job->paged) return KT_OK;  // exact offsets: level 1 runs in finish, over all the sources
-    return job->narrow ? level1_paged<uint32_t>(ctr, *job, r) : level1_paged<uint64_t>(ctr, *job, r);
+    return ctr->job->plan(ctr, kn, max_keys, eligible);
 }
 
 // level 1 over the k-mers that start in segments [seg_lo, seg_hi) of a read batch (seg_first: ktseg::seg_index_kernel)
@@ -3602,16 +3517,8 @@ int kt_bulk_add_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs, 
     kt_bulk_job *job = ctr->job;
     if (!job || !job->open) return kt::fail(KT_ERR_ARG, "bulk build: no open job");
     if (!n_runs) return KT_OK;
-    // the descriptors: n_runs x {blocks, n_rec}, then n_runs + 1 cumulative block counts
-    std::vector<uint64_t> h((size_t)n_runs * 3 + 1);
-    uint64_t blocks = 0;
-    for (uint32_t i = 0; i < n_runs; i++) {
-        h[2 * (size_t)i] = (uint64_t)(uintptr_t)runs[i].blocks;
-        h[2 * (size_t)i + 1] = runs[i].n_rec;
-        h[2 * (size_t)n_runs + i] = blocks;
-        blocks += (runs[i].n_rec + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS;
-    }
-    h[3 * (size_t)n_runs] = blocks;
+    std::vector<uint64_t> h;
+    const uint64_t blocks = record_descriptors(runs, n_runs, &h);
     if (!blocks) return KT_OK;
     const size_t bytes = (h.size() * 8 + 255) & ~(size_t)255;
     if (job->desc_used + bytes > DESC_BYTES) return kt::fail(KT_ERR_ARG, "bulk build: too many record sources in one job");
@@ -3630,22 +3537,15 @@ int kt_bulk_add_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs, 
     r.rc.k = (uint32_t)ctr->k;
     r.rc.n_blocks = blocks;
     r.n_units = blocks;
-    return job_add(ctr, r, kmers_bound);
+    return job->add(r, kmers_bound);
 }
 
 // the same records, one table_add per k-mer (kt_shard.hip, when kt_bulk_begin says the batch does not suit the passes)
 int kt_ctr_count_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs) {
     kt_ctx *ctx = ctr->ctx;
     if (!n_runs) return KT_OK;
-    std::vector<uint64_t> h((size_t)n_runs * 3 + 1);
-    uint64_t blocks = 0;
-    for (uint32_t i = 0; i < n_runs; i++) {
-        h[2 * (size_t)i] = (uint64_t)(uintptr_t)runs[i].blocks;
-        h[2 * (size_t)i + 1] = runs[i].n_rec;
-        h[2 * (size_t)n_runs + i] = blocks;
-        blocks += (runs[i].n_rec + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS;
-    }
-    h[3 * (size_t)n_runs] = blocks;
+    std::vector<uint64_t> h;
+    const uint64_t blocks = record_descriptors(runs, n_runs, &h);
     if (!blocks) return KT_OK;
     ctr->stage_n = 0;
     if (int rc = ktl::table_ready(ctr)) return rc;  // (a dense table gets its probing image, a deferred clear happens now)
@@ -3656,9 +3556,7 @@ int kt_ctr_count_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs)
     KT_HIP(hipStreamSynchronize(ctx->stream));  // (h lives on this frame)
     RecordSource src{(const ktsk::RecRun *)d, (const uint64_t *)d + 2 * (size_t)n_runs, n_runs, (uint32_t)ctr->k, blocks};
     TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
-    hipLaunchKernelGGL(count_records_kernel, dim3(ktl::grid_for(ctx, blocks, 8)), dim3(BLOCK), 0, ctx->stream, src, t, ctr->distinct);
-    KT_HIP(hipGetLastError());
-    return KT_OK;
+    return launch(count_records_kernel, dim3(ktl::grid_for(ctx, blocks, 8)), dim3(BLOCK), 0, ctx->stream, src, t, ctr->distinct);
 }
 
 // level 2 + the range builds; the sources must still be readable (a skewed batch is redone from them)
@@ -3666,10 +3564,13 @@ int kt_bulk_finish(kt_ctr *ctr) {
     kt_bulk_job *job = ctr->job;
     if (!job || !job->open) return kt::fail(KT_ERR_ARG, "bulk build: no open job");
     job->open = false;
-    if (!job->paged) {
-        if (int rc = job->narrow ? level1_exact<uint32_t>(ctr, *job) : level1_exact<uint64_t>(ctr, *job)) return rc;
-    }
-    int rc = job->narrow ? finish_typed<uint32_t>(ctr, *job) : finish_typed<uint64_t>(ctr, *job);
+    int rc = with_key_type(*job, [&](auto key) -> int {
+        using K = decltype(key);
+        if (int rc = job->close_level1<K>()) return rc;
+        if (int rc = job->level2<K>()) return rc;
+        if (int rc = job->build<K>()) return rc;
+        return job->report();
+    });
     job->srcs.clear();
     if (rc == KT_OK) {
         ctr->empty = false;
@@ -3694,8 +3595,9 @@ int kt_bulk_build(kt_ctr *ctr, const uint8_t *d_bases, const uint64_t *d_offsets
     // the segment index (seg_first) lives in ctx scratch; same helper kernel as the other paths
     uint64_t *seg_first = nullptr;
     if (int rc = ctx->claim(kt::AUX0, (n_seg + 2) * sizeof(uint64_t), "kt_bulk_build", &seg_first)) return rc;
-    hipLaunchKernelGGL(ktseg::seg_index_kernel, dim3((uint32_t)((n_reads + 1 + 255) / 256)), dim3(256), 0, ctx->stream,
-                       d_offsets, n_reads, seg_first, n_seg);
+    if (int rc = launch(ktseg::seg_index_kernel, dim3((uint32_t)((n_reads + 1 + 255) / 256)), dim3(256), 0, ctx->stream, d_offsets,
+                        n_reads, seg_first, n_seg))
+        return rc;
     // A pass of its own packs the reads (16 bytes per 32 bases: codes, invalid-base mask, read-start mask - what stage_segment
     // makes of them) and level 1 reads the packed items: it stages nothing through LDS and has no barrier of its own per unit.
     // ctr k=31: pack 1.5 + level 1 11.0 ms against 13.2-13.4 with the staging inside level 1; k=15: 3.1 + 14.7 against 18.3.
@@ -3708,9 +3610,9 @@ int kt_bulk_build(kt_ctr *ctr, const uint8_t *d_bases, const uint64_t *d_offsets
     }
     if (packed) {
         SegArgs a{d_bases, d_offsets, seg_first, n_reads, n_seg, (uint32_t)ctr->k};
-        hipLaunchKernelGGL(pack_segments_kernel, dim3(ktl::grid_for(ctx, n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, (uint64_t)0, n_seg,
-                           (uint4 *)ctr->b_pack.p);
-        KT_HIP(hipGetLastError());
+        if (int rc = launch(pack_segments_kernel, dim3(ktl::grid_for(ctx, n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, (uint64_t)0, n_seg,
+                            (uint4 *)ctr->b_pack.p))
+            return rc;
         SourceRec r{};
         r.kind = SRC_PACKED;
         r.ps = PackedSource{(const uint4 *)ctr->b_pack.p, 0, n_seg, (uint32_t)ctr->k};
@@ -3751,14 +3653,11 @@ int kt_table_image(kt_ctr *ctr) {
     kt_ctx *ctx = ctr->ctx;
     const uint32_t RS = ctr->m8 << (LOG2_S - 3);
     const uint64_t n_ranges = ctr->cap / RS;
-    const size_t lds = (size_t)RS * 12;
-    KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(materialize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
     uint64_t g = (uint64_t)ctx->n_cu * 4;
     if (g > n_ranges) g = n_ranges;
-    hipLaunchKernelGGL(materialize_kernel, dim3((uint32_t)g), dim3(BUILD_T), lds, ctx->stream, (Slot *)ctr->slots, RS, n_ranges,
-                       ctr->shift, ctr->m8, ctr->kbits, ctr->range_counts);
-    KT_HIP(hipGetLastError());
+    if (int rc = launch(materialize_kernel, dim3((uint32_t)g), dim3(BUILD_T), (size_t)RS * 12, ctx->stream, (Slot *)ctr->slots, RS,
+                        n_ranges, ctr->shift, ctr->m8, ctr->kbits, ctr->range_counts))
+        return rc;
     ctr->dense = false;
     return KT_OK;
 }
@@ -3781,12 +3680,12 @@ int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uin
     const uint64_t n_ranges = ctr->cap / RS, n_tiles = (n_ranges + XT - 1) / XT;
     uint64_t *tiles = nullptr;
     if (int rc = ctx->claim(kt::AUX0, (n_tiles + 1) * 8, "kt_table_dense_export", &tiles)) return rc;
-    hipLaunchKernelGGL(tile_sums_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, ctr->range_counts, n_ranges, tiles);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles);
+    if (int rc = launch(tile_sums_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, ctr->range_counts, n_ranges, tiles)) return rc;
+    if (int rc = launch(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles)) return rc;
     if (max_out)
-        hipLaunchKernelGGL(dense_export_kernel<false>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
-                           n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, nullptr, 1u, 0xFFFFFFFFu);
-    KT_HIP(hipGetLastError());
+        if (int rc = launch(dense_export_kernel<false>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
+                            n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, nullptr, 1u, 0xFFFFFFFFu))
+            return rc;
     KT_HIP(hipMemcpyAsync(n, tiles + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
     KT_HIP(hipStreamSynchronize(ctx->stream));
     return KT_OK;
@@ -3803,13 +3702,14 @@ int kt_table_dense_export_range(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_count
     uint64_t *tiles = nullptr;
     if (int rc = ctx->claim(kt::AUX0, (n_tiles + 1) * 8 + n_ranges * 4, "kt_table_dense_export_range", &tiles)) return rc;
     uint32_t *kept = (uint32_t *)(tiles + n_tiles + 1);
-    hipLaunchKernelGGL(dense_kept_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS, n_ranges,
-                       ctr->range_counts, lo, hi, kept, tiles);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles);
+    if (int rc = launch(dense_kept_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS, n_ranges,
+                        ctr->range_counts, lo, hi, kept, tiles))
+        return rc;
+    if (int rc = launch(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles)) return rc;
     if (max_out)
-        hipLaunchKernelGGL(dense_export_kernel<true>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
-                           n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, kept, lo, hi);
-    KT_HIP(hipGetLastError());
+        if (int rc = launch(dense_export_kernel<true>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
+                            n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, kept, lo, hi))
+            return rc;
     KT_HIP(hipMemcpyAsync(n, tiles + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
     KT_HIP(hipStreamSynchronize(ctx->stream));
     return KT_OK;

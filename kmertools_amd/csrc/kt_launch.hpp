@@ -1,6 +1,7 @@
 // kt_launch.hpp - what the host code of the extern "C" entry points shares: launch helpers of the segment front-end,
-// argument checks that several entry points make in the same words, and ktl::Call, the one path by which an entry point
-// moves its arguments between the caller's memory and the device.  Defined in kt_launch.hip.
+// argument checks that several entry points make in the same words, ktl::launch and ktl::carve_parts (one kernel launch;
+// typed arrays cut from one buffer), and ktl::Call, the one path by which an entry point moves its arguments between the
+// caller's memory and the device.  Defined in kt_launch.hip, the templates here.
 #pragma once
 #include <memory>
 #include <new>
@@ -27,6 +28,27 @@ int table_ready(kt_ctr *ctr);
 // d_counts[i] = occurrences of d_keys[i] in the table (0: absent), n > 0 device keys, on the context's stream; the table
 // holds its probing image (table_ready).  kt_cov.hip's lookup_kernel.
 int lookup_counts(kt_ctr *table, const uint64_t *d_keys, uint64_t n, uint32_t *d_counts);
+
+// One kernel launch: where it asks for dynamic LDS, the kernel's limit is raised to that first (at every launch, not once
+// per process: two builds of the library may be loaded side by side), and the launch's own error is the status.
+template <class... P, class... A>
+int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A &&...args) {
+    if (lds) KT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, static_cast<P>(args)...);
+    KT_HIP(hipGetLastError());
+    return KT_OK;
+}
+
+// carve_parts<ALIGN>(at, &a, count_a, &b, count_b, ...): typed arrays cut from one buffer in the order given, each taking
+// a multiple of ALIGN bytes.  Returns their bytes; with `at` set it also puts the arrays there (null: the size alone).
+template <size_t ALIGN>
+size_t carve_parts(uint8_t *) { return 0; }
+template <size_t ALIGN, class T, class... More>
+size_t carve_parts(uint8_t *at, T **p, uint64_t count, More... more) {
+    const size_t bytes = (count * sizeof(T) + ALIGN - 1) & ~(ALIGN - 1);
+    if (at) *p = (T *)at;
+    return bytes + carve_parts<ALIGN>(at ? at + bytes : at, more...);
+}
 
 // One call of an entry point that takes `int mem`.  It holds the call's claim scope on the context's scratch and is the
 // only place that tells the two memory kinds apart: for KT_MEM_DEVICE every method hands the caller's pointer through

@@ -439,7 +439,8 @@ class Counter:
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            _lib.lib().kt_ctr_destroy(self._h)
+            if self.ctx._h.value:   # (a table that outlives its context is not destroyed: kt_ctr_destroy waits for the context's stream)
+                _lib.lib().kt_ctr_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

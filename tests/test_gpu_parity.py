@@ -836,15 +836,16 @@ def test_ctr_level1_over_packed_reads_and_over_staged_reads(hctx, oracle, monkey
 
 
 @pytest.mark.parametrize("k", [8, 10, 12, 13])
-def test_ctr_direct_addressed_tables(torch_mod, ctx, oracle, monkeypatch, k):
+def test_ctr_direct_addressed_tables(torch_mod, ctx, oracle, monkeypatch, capfd, k):
     """a table of exactly 4^k slots (k <= 15: the hash of a k-mer is a bijection onto the slots - ktd::nhash - and the bulk
     build's ranges are counters alone, keys coming back from the slots' indices): the oracle's table from ragged noisy
     reads with repeats, into the table and into an export target; look-ups, cov and a second batch on top (the dense table
     becomes a probing image under the same hash, the rebuild merges into it); the same with KT_BUILD_DIRECT=0 (probing
-    build of the same geometry)"""
+    build of the same geometry).  The job's verbose line names the build that ran."""
     torch = torch_mod
     from kmertools_amd import device
     monkeypatch.setenv("KT_BULK_MIN_BASES", "0")
+    monkeypatch.setenv("KT_BULK_VERBOSE", "1")
     rng = np.random.default_rng(k)
     seqs = ragged_reads(900 + k, 3000) + [b"ACGT" * 400, b"A" * 3000]
     bases, offsets = device.to_csr(seqs)
@@ -857,7 +858,10 @@ def test_ctr_direct_addressed_tables(torch_mod, ctx, oracle, monkeypatch, k):
         monkeypatch.setenv("KT_BUILD_DIRECT", direct)
         ctr = device.Counter(ctx, k, 4 ** k)
         assert ctr.capacity() == 4 ** k
+        capfd.readouterr()
         ctr.add_reads_host(bases, offsets)
+        lines = _bulk_lines(capfd)
+        assert len(lines) == 1 and _field(lines[0], "build") == ("direct" if direct == "1" else "dense"), lines
         gk, gc = ctr.export_host()
         assert np.array_equal(gk, wk) and np.array_equal(gc, wc), (k, direct)
         assert np.array_equal(ctr.lookup_host(probe), want_probe)
@@ -873,7 +877,10 @@ def test_ctr_direct_addressed_tables(torch_mod, ctx, oracle, monkeypatch, k):
         c2.export_target(xk, xc, len(wk) + 5)
         db = torch.from_numpy(bases).cuda()
         do = torch.from_numpy(offsets.astype(np.int64)).cuda()
+        capfd.readouterr()
         c2.add_reads(db, do, len(seqs))
+        lines = _bulk_lines(capfd)
+        assert len(lines) == 1 and _field(lines[0], "build") == ("direct-ext" if direct == "1" else "dense-ext"), lines
         d = c2.size()
         assert d == len(wk) and c2.export(xk, xc, len(wk) + 5) == d
         gk2 = xk[:d].cpu().numpy().view(np.uint64)
@@ -917,9 +924,34 @@ def test_ctr_bulk_build_matches_oracle(hctx, oracle, monkeypatch, k, log2cap, pa
     ctr.close()
 
 
+def _bulk_lines(capfd):
+    """the jobs' lines of KT_BULK_VERBOSE=1 since the last read of stderr, one per job"""
+    return [l for l in capfd.readouterr().err.splitlines() if l.startswith("[bulk] k=")]
+
+
+def _field(line, name):
+    """the value of ` name=value` in a [bulk] line"""
+    return dict(f.split("=", 1) for f in line.split() if "=" in f)[name]
+
+
+def _level1_kernel(k, log2_slots, s1y=True):
+    """the level-1 kernel a paged job launches, by the code's own rule (kt_bulk.hip, kt_bulk_job::level1_paged): scatter1y
+    where KT_S1Y is on and Scatter1YShared<K, 1024>::bytes(B1) fits 160 KB of LDS, else scatter1x.  B1 as split_bits
+    gives it without KT_BULK_B1: 13 hash bits per range, the rest halved between the levels."""
+    key = 4 if k <= 16 else 8
+    fb = log2_slots - 13
+    b1 = min((fb + 1) // 2, 10)
+    if fb >= 16 and fb - b1 < 9:
+        b1 = fb - 9
+    half_per = (32 if key == 4 else 16) // 2                      # half_per<K>(): keys per thread and round
+    slots = (1024 * half_per + (1 << b1) * (16 // key - 1) + 63) // 64 * 64
+    lds = 2 * slots * key + 1024 * (2 if key == 8 else 4) + 3 * 1024 * 4 + 16 * 4 + 16
+    return "scatter1y" if s1y and lds <= 160 * 1024 else "scatter1x"
+
+
 @pytest.mark.parametrize("k", [31, 15])
 @pytest.mark.parametrize("shape", ["wide", "sets8", "sets2", "one_buffer", "one_buffer_sets8", "part2_small", "image"])
-def test_ctr_bulk_kernel_shapes_and_odd_batches(hctx, oracle, monkeypatch, k, shape):
+def test_ctr_bulk_kernel_shapes_and_odd_batches(hctx, oracle, monkeypatch, capfd, k, shape):
     """every shape of the partition kernels on batches that do not fill them: one short read, a batch of less than one
     segment, segments in numbers that are not a multiple of the four a level-1 workgroup takes, a read that ends a
     segment exactly, N runs, an empty read - and an empty batch.  wide = scatter1y (two sort buffers, the copy-out of a round
@@ -928,9 +960,19 @@ def test_ctr_bulk_kernel_shapes_and_odd_batches(hctx, oracle, monkeypatch, k, sh
     round-robin to the sets, tails padded, a set that runs out of its eighth of a region falls back to exact offsets),
     one_buffer = scatter1x (KT_S1Y=0: the shape 32-bit keys with 1024 buckets keep, whose two buffers do not fit the LDS),
     part2_small = the 512-thread level 2 for 64-bit keys, image = the
-    probing image written at once instead of the dense state"""
+    probing image written at once instead of the dense state.  The job's verbose line names the kernels that ran: the
+    level-1 kernel of the shape, the build of the shape, the sort-buffer level 2 (a fan-out of 4)."""
     from kmertools_amd import device
     monkeypatch.setenv("KT_BULK_MIN_BASES", "0")
+    monkeypatch.setenv("KT_BULK_VERBOSE", "1")
+    want_l1 = _level1_kernel(k, 18, s1y=not shape.startswith("one_buffer"))
+    if k == 31:
+        assert want_l1 == ("scatter1x" if shape.startswith("one_buffer") else "scatter1y")
+
+    def l1_of(line):
+        # forced cursor sets leave a set an eighth (a half) of a small batch's region: where one runs out, the job says
+        # level1=exact - it has redone level 1 with exact offsets, and the table stays with them - and l1 must say the same
+        return "exact" if "sets" in shape and "level1=exact" in line else want_l1
     if shape.startswith("one_buffer"):
         monkeypatch.setenv("KT_S1Y", "0")
     if "sets" in shape:
@@ -957,11 +999,21 @@ def test_ctr_bulk_kernel_shapes_and_odd_batches(hctx, oracle, monkeypatch, k, sh
         bases, offsets = device.to_csr(seqs)
         wk, wc = oracle.count_reads(bases, offsets, k)
         ctr = device.Counter(hctx, k, 1 << 18)
+        assert ctr.capacity() == 1 << 18
+        capfd.readouterr()
         ctr.add_reads_host(bases, offsets)
+        lines = _bulk_lines(capfd)
+        assert len(lines) == 1, lines
+        assert _field(lines[0], "l1") == l1_of(lines[0])
+        assert _field(lines[0], "build") == ("image" if shape == "image" else "dense")
+        if shape == "part2_small":
+            assert _field(lines[0], "l2") == "fast"
         assert ctr.size() == len(wk)
         gk, gc = ctr.export_host()
         assert np.array_equal(gk, wk) and np.array_equal(gc, wc)
         ctr.add_reads_host(bases, offsets)                    # and on top of itself (merge or probing path)
+        for line in _bulk_lines(capfd):                       # (merge: the bulk path again)
+            assert _field(line, "l1") == l1_of(line) and _field(line, "build") == "merge"
         gk, gc = ctr.export_host()
         assert np.array_equal(gk, wk) and np.array_equal(gc, 2 * wc)
         ctr.close()
@@ -1011,6 +1063,50 @@ def test_ctr_bulk_build_heavy_hitters_in_fixed_regions(hctx, oracle, monkeypatch
     assert len(lines) == 1
     if repeat == 600:
         assert "level1=paged level2=fixed" in lines[0]
+    ctr.close()
+
+
+@pytest.mark.parametrize("k", [31, 15])
+@pytest.mark.parametrize("mix", ["uniform", "heavy"])
+def test_ctr_level2_write_combining_small(hctx, oracle, monkeypatch, capfd, k, mix):
+    """part2_swwc_kernel, and behind it part2_exact_kernel over the buckets it gave up, at the smallest shape that selects
+    it: level 2 writes whole lines out of LDS only for fan-outs of 512 and more, which the default split of the hash bits
+    reaches at 2^31 slots.  KT_BULK_B1=1 on a table of 2^23 slots (128 MB) gives 10 fine bits, b1 = 1, b2 = 9: B1 = 2,
+    B2 = 512.  (B1 = 2 is within what the kernels take: scatter1y / scatter1x mask a digit with B1 - 1 and guard their
+    per-bucket work with d < B1, their scan takes any count of buckets, xcd_tails and level 2 loop over B1 buckets, and
+    digit1h needs b1 >= 1 only - a power of two is all they ask.)
+    uniform: 300 random reads of 1000 bases, about 285 keys for each fine bucket's 336 keys of room.  heavy: four reads of
+    one 40-mer 600 times on top, so that some fine buckets outgrow their room and their level-1 buckets are redone with
+    exact boundaries - still the swwc choice, the redo is part of it.  Then the same batch on top: a merge."""
+    from kmertools_amd import device
+    monkeypatch.setenv("KT_BULK_MIN_BASES", "0")
+    monkeypatch.setenv("KT_BULK_VERBOSE", "1")
+    monkeypatch.setenv("KT_BULK_B1", "1")
+    monkeypatch.setenv("KT_BULK_MERGE_DIV", "1000000000")   # (the second batch rebuilds the ranges whatever its size)
+    rng = np.random.default_rng(300 + k)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    seqs = [bytes(rng.choice(acgt, size=1000)) for _ in range(300)]
+    if mix == "heavy":
+        seqs += [bytes(rng.choice(acgt, size=40)) * 600 for _ in range(4)]
+    bases, offsets = device.to_csr(seqs)
+    wk, wc = oracle.count_reads(bases, offsets, k)
+    assert (wc.max() > 500) == (mix == "heavy")
+    ctr = device.Counter(hctx, k, 1 << 23)
+    assert ctr.capacity() == 1 << 23
+    capfd.readouterr()
+    ctr.add_reads_host(bases, offsets)
+    lines = _bulk_lines(capfd)
+    assert len(lines) == 1, lines
+    assert _field(lines[0], "l2") == "swwc" and _field(lines[0], "build") == "dense"
+    assert ctr.size() == len(wk)
+    gk, gc = ctr.export_host()
+    assert np.array_equal(gk, wk) and np.array_equal(gc, wc)
+    ctr.add_reads_host(bases, offsets)
+    lines = _bulk_lines(capfd)
+    assert len(lines) == 1, lines
+    assert _field(lines[0], "l2") == "swwc" and _field(lines[0], "build") == "merge"
+    gk, gc = ctr.export_host()
+    assert np.array_equal(gk, wk) and np.array_equal(gc, 2 * wc)
     ctr.close()
 
 
@@ -1176,14 +1272,16 @@ def test_ctr_dense_table_state(hctx, oracle, monkeypatch, k):
 
 
 @pytest.mark.parametrize("k", [31, 15, 21])
-def test_ctr_export_target(torch_mod, ctx, oracle, monkeypatch, k):
+def test_ctr_export_target(torch_mod, ctx, oracle, monkeypatch, capfd, k):
     """kt_ctr_export_target: the range build writes its packed (key, count) pairs straight into the caller's device
     arrays (no export pass); the table stays usable - size, export to the same or to other arrays, cov, further adds
     (probing path and range rebuild) first rebuild the probing image from those arrays; a target that is too small is
-    reported, not silently truncated; the target is sticky across clears"""
+    reported, not silently truncated; the target is sticky across clears.  The job's verbose line names the build that
+    produced the table: into the target, or - redone - into the table's own slots."""
     from kmertools_amd import device, _lib
     torch = torch_mod
     monkeypatch.setenv("KT_BULK_MIN_BASES", "0")
+    monkeypatch.setenv("KT_BULK_VERBOSE", "1")
     seqs = ragged_reads(19 + k, 500) + _random_reads(k + 1, 400) + [b"C" * 2500] + _random_reads(k + 1, 50)
     hb, ho = device.to_csr(seqs)
     wk, wc = oracle.count_reads(hb, ho, k)
@@ -1209,7 +1307,10 @@ def test_ctr_export_target(torch_mod, ctx, oracle, monkeypatch, k):
         for rep in range(2):            # sticky: the second round (after a clear) takes the same road
             xk.fill_(-1)
             ctr.clear()
+            capfd.readouterr()
             ctr.add_reads(bases, offsets, n)
+            lines = _bulk_lines(capfd)
+            assert len(lines) == 1 and _field(lines[0], "build") == ("dense" if after == "uneven" else "dense-ext"), lines
             assert ctr.size() == len(wk)
             got = ctr.export(xk, xc, room)
             assert got == len(wk)
@@ -1273,7 +1374,10 @@ def test_ctr_export_target(torch_mod, ctx, oracle, monkeypatch, k):
     bc = torch.zeros(big, dtype=torch.int32, device="cuda")
     ctr = device.Counter(ctx, k, 1 << 18)
     ctr.export_target(bk, bc, big)
+    capfd.readouterr()
     ctr.add_reads(bases, offsets, n)
+    lines = _bulk_lines(capfd)
+    assert len(lines) == 1 and _field(lines[0], "build") == "dense", lines
     assert ctr.size() == len(wk)
     gk, gc = ctr.export_host()
     assert np.array_equal(gk, wk) and np.array_equal(gc, wc)

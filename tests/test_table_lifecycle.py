@@ -655,12 +655,12 @@ def test_one_table_through_its_whole_life(torch_mod, oracle, monkeypatch, capfd,
         capfd.readouterr()
         add_device(R, c, "bulk1")
         lines = bulk_lines(capfd)
-        assert len(lines) == 1 and lines[0].split()[-2] == "build", (tag(6), lines)
+        assert len(lines) == 1 and lines[0].split()[5] == "build", (tag(6), lines)  # (k, keys, level1, level2, build | merge, ...)
         check_all(R, c, S[6], order, tag(6))
         # 7. a second batch merged in place by the bulk path
         add_device(R, c, "bulk2")
         lines = bulk_lines(capfd)
-        assert len(lines) == 1 and lines[0].split()[-2] == "merge", (tag(7), lines)
+        assert len(lines) == 1 and lines[0].split()[5] == "merge", (tag(7), lines)
         check_all(R, c, S[7], order, tag(7))
         # 8. a small batch by the probing path on top of the rebuilt ranges
         env_probing(monkeypatch)
@@ -676,7 +676,7 @@ def test_one_table_through_its_whole_life(torch_mod, oracle, monkeypatch, capfd,
         c.clear()
         add_device(R, c, "bulk2")
         lines = bulk_lines(capfd)
-        assert len(lines) == 1 and lines[0].split()[-2] == "build", (tag(9), lines)  # (no "redone into the table" line)
+        assert len(lines) == 1 and lines[0].split()[5] == "build", (tag(9), lines)  # (no "redone into the table" line)
         check_all(R, c, S[9], order, tag(9), only=WALKERS)
         R.after()
         n = S[9].m.size
@@ -707,7 +707,7 @@ def test_one_table_through_its_whole_life(torch_mod, oracle, monkeypatch, capfd,
         capfd.readouterr()
         add_device(R, c, "bulk1")
         lines = bulk_lines(capfd)
-        assert len(lines) == 1 and lines[0].split()[-2] == "build", (tag(12), lines)
+        assert len(lines) == 1 and lines[0].split()[5] == "build", (tag(12), lines)
         n = S[12].m.size
         hk, hc = by_key(u64(xk)[:n], u32(xc)[:n])  # (what the arrays hold beyond the entries is unspecified)
         assert same(hk, S[12].m.keys) and same(hc, S[12].m.counts), tag(12)
