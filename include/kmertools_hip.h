@@ -180,7 +180,10 @@ int kt_ctr_clear(kt_ctr *ctr);
 int kt_ctr_capacity(kt_ctr *ctr, uint64_t *slots);
 
 /* replaces: the hot loop of count_chunk, counter/src/lib.rs:119-131:
- * for every k-mer of every read: table[min(fwd,rev)] += 1.  Repeatable (= chunks). */
+ * for every k-mer of every read: table[min(fwd,rev)] += 1.  Repeatable (= chunks).
+ * A count is a u32 and is exact while a k-mer's occurrences, over every call that adds to the table (reads, pairs, bulk
+ * merges), stay <= 0xFFFFFFFF; 0xFFFFFFFF itself is reached and read back exactly.  Beyond that the result is unspecified
+ * (nothing saturates; the reference's u32 wraps silently). */
 int kt_ctr_add_reads(kt_ctr *ctr, const uint8_t *bases, const uint64_t *offsets,
                      uint64_t n_reads, int mem);
 
@@ -194,7 +197,9 @@ int kt_ctr_add_reads_part(kt_ctr *ctr, const uint8_t *bases, const uint64_t *off
                           uint32_t n_parts, uint32_t part);
 
 /* replaces: merge's arithmetic, counter/src/lib.rs:201-210: table[keys[i]] += counts[i]
- * (counts == NULL means 1 each: raw canonical k-mers routed from another GPU). */
+ * (counts == NULL means 1 each: raw canonical k-mers routed from another GPU).
+ * A pair with count 0 adds nothing, exactly like a KT_EMPTY_KEY entry: a key the table does not hold stays absent,
+ * kt_ctr_size does not grow and a later kt_ctr_erase of that key removes nothing. */
 int kt_ctr_add_pairs(kt_ctr *ctr, const uint64_t *keys, const uint32_t *counts, uint64_t n,
                      int mem);
 
@@ -535,7 +540,10 @@ int kt_cov_batch_part(kt_ctr *table, const uint8_t *bases, const uint64_t *offse
  * then skipped).  `mem` says where bases, offsets and the three arrays live; KT_MEM_HOST synchronises.
  * KT_ERR_ARG: min_count == 0, min_count > max_count, part >= n_parts, a bad mem, a null buffer with n_reads > 0, a read
  * of 2^32 bases or more (positions are u32), or a table that is one shard of a sharded table (n_owners > 1: a shard
- * cannot tell a k-mer absent here from one absent everywhere - shards are not supported). */
+ * cannot tell a k-mer absent here from one absent everywhere - shards are not supported).
+ * The count compared is the table's own: a k-mer with 0xFFFFFFFF occurrences is solid for max_count == 0xFFFFFFFF, also
+ * with min_count == 0xFFFFFFFF.  (kt_ctr_profile caps what it writes at 0xFFFFFFFE; kt_ctr_correct_support's "covered"
+ * reads that profile and so differs for exactly this k-mer - see there.) */
 int kt_ctr_read_solidity(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                          uint32_t min_count, uint32_t max_count, uint32_t *n_kmers, uint32_t *n_solid,
                          uint32_t *first_weak, int mem, uint32_t n_parts, uint32_t part);
@@ -588,7 +596,11 @@ int kt_profile_stats(kt_ctx *ctx, const uint32_t *profile, const uint64_t *offse
  *             carries into the next.  Entries of covered bases and of reads shorter than k are not written.
  * `mem` says where bases, offsets, profile and support live; KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the
  * context's stream.  KT_ERR_ARG: min_count == 0, min_count > max_count, part >= n_parts, a bad mem, a null buffer with
- * n_reads > 0, or a table that is one shard of a sharded table (as for the read solidity call). */
+ * n_reads > 0, or a table that is one shard of a sharded table (as for the read solidity call).
+ * The two ends of u32: KT_NO_KMER is 0xFFFFFFFF, so a k-mer with 0xFFFFFFFF occurrences reads as 0xFFFFFFFE in a profile.
+ * "covered" sees that value: with max_count == 0xFFFFFFFF the k-mer covers for every min_count <= 0xFFFFFFFE, and with
+ * min_count == 0xFFFFFFFF it does not cover - although it is solid for kt_ctr_read_solidity and, in `support`, for the
+ * substituted k-mers, which are probed in the table and compared with their real count. */
 int kt_ctr_correct_support(kt_ctr *table, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                            const uint32_t *profile, uint32_t min_count, uint32_t max_count, uint32_t *support, int mem,
                            uint32_t n_parts, uint32_t part);

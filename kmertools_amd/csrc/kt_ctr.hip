@@ -60,7 +60,7 @@ __global__ __launch_bounds__(BLOCK) void add_pairs_kernel(const uint64_t *__rest
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) {
         const uint64_t key = keys[i];
         const uint32_t c = counts ? counts[i] : 1u;
-        if (key == KT_EMPTY_KEY) continue;
+        if (key == KT_EMPTY_KEY || c == 0u) continue;  // adding 0 adds nothing: a claimed slot would mean "seen once"
         const uint32_t st = table_add(t, key, c);
         if (st == 0u) atomicOr(t.flags, 1u);
         fresh += st == 2u;

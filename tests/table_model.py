@@ -45,7 +45,8 @@ class Model:
         uk, inv = np.unique(keys, return_inverse=True)
         uc = np.zeros(len(uk), np.uint64)
         np.add.at(uc, inv, counts)
-        assert (uc <= U32).all(), "the model does not restate saturation"
+        assert (uc <= U32).all(), ("more than 0xFFFFFFFF occurrences of a k-mer: past the exactness limit the result is "
+                                   "unspecified (include/kmertools_hip.h, kt_ctr_add_reads)")
         self.keys, self.counts = uk, uc.astype(np.uint32)
 
     def add_reads(self, bases, offsets):
@@ -53,9 +54,9 @@ class Model:
         self._merge(*kt_oracle.count_reads(np.ascontiguousarray(bases, np.uint8), np.ascontiguousarray(offsets, np.uint64), self.k))
 
     def add_pairs(self, keys, counts):
-        counts = np.asarray(counts, np.uint32)
-        assert (counts >= 1).all(), "a pair with count 0 is unspecified"
-        self._merge(keys, counts)
+        keys, counts = np.asarray(keys, np.uint64), np.asarray(counts, np.uint32)
+        some = counts >= 1  # (a pair with count 0 adds nothing: its key stays absent if the table does not hold it)
+        self._merge(keys[some], counts[some])
 
     def clear(self):
         self.keys, self.counts = np.zeros(0, np.uint64), np.zeros(0, np.uint32)
