@@ -454,6 +454,50 @@ int kt_ctr_unitig_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, ui
 int kt_ctr_clip_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint32_t max_rounds,
                      uint32_t flags, uint64_t *stats);
 
+/* Which of those unitigs are the weaker sides of BUBBLES - the short parallel paths that a SNP, a small indel or a repeated
+ * sequencing error leaves between the same two points (Velvet's tour bus, minia's and SPAdes' bulge removal, Bifrost's
+ * simplification).  One round, read-only, in kt_ctr_unitig_tips' vocabulary: n_u, c_u, end e = 2u + (sign is '-') and its
+ * links f = 2v + (sv is '-'); a link e -> f arrives at end f ^ 1 of unitig f >> 1, its mirror is (f ^ 1) -> (e ^ 1).  The
+ * rule reads kt_ctr_unitigs_linked's outputs alone, so it holds for every k.
+ *   - u is a BRANCH when it is not circular, n_u <= max_bubble_nodes, end 2u has exactly one link a, end 2u + 1 has exactly
+ *     one link b, and a >> 1 != u and b >> 1 != u;
+ *   - branches u != w are PARALLEL when the unordered pairs {a_u, b_u} and {a_w, b_w} are equal (unordered: w may lie the
+ *     other way round between the same two ends).  Parallel is an equivalence: a branch is in exactly one class;
+ *   - w OUTRANKS u when c_w / n_w > c_u / n_u, or the two are equal and w < u (compared exactly, as 128-bit products);
+ *   - a branch is KT_BUBBLE_POP when some parallel branch outranks it; everything else is 0.
+ * So exactly one branch of every class stays, and it keeps both anchors joined.  An anchor end (a ^ 1, b ^ 1) of a class of
+ * two or more has at least two links, so an anchor is never a branch and is never popped.  A popped unitig has links at both
+ * ends, so it is never a tip candidate, and an anchor that is a tip candidate is never a tip: the branch end that faces it
+ * has no other link that could beat it.  KT_BUBBLE_POP is a bit of its own beside KT_TIP_TIP and KT_TIP_ISOLATED, one mark
+ * byte carries both rules, and the tips' invariant holds for the union of both marks: an end of an unmarked unitig that had
+ * links keeps at least one of them among the unmarked unitigs.
+ * The search is one-sided: branch u looks through the at most 5 links h of end a ^ 1; w = h >> 1 != u is parallel exactly
+ * when it is a branch and the single link of its end h equals b (its end h ^ 1 links to a, the mirror of h).
+ * tally (may be NULL; KT_BUBBLE_TALLY values, overwritten): [0] popped unitigs, [1] their nodes, [2] bubbles (classes of two
+ * or more), [3] occurrences popped.  Shapes, the count-only form, KT_ERR_ARG cases, untouched outputs on error, KT_MEM_HOST and
+ * KT_MEM_DEVICE: exactly as in kt_ctr_unitig_tips, with max_bubble_nodes == 0 refused.  Device scratch: kt_ctr_unitig_tips'
+ * less one byte per unitig (the rule keeps no class array). */
+#define KT_BUBBLE_POP 4
+#define KT_BUBBLE_TALLY 4
+int kt_ctr_unitig_bubbles(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_bubble_nodes, uint8_t *marks,
+                          uint64_t max_unitigs, uint64_t *n_unitigs, uint64_t *tally, int mem);
+
+/* Clip tips and pop bubbles in the same rounds.  Each round is one linked run whose unitigs are marked by the tip rule when
+ * max_tip_nodes > 0 and by the bubble rule when max_bubble_nodes > 0 (both 0: KT_ERR_ARG); one list and one kt_ctr_erase take
+ * the nodes of every KT_TIP_TIP and KT_BUBBLE_POP unitig and, with KT_CLIP_ISOLATED in flags (valid only with
+ * max_tip_nodes > 0), of every KT_TIP_ISOLATED one.  The next round sees the unitigs of what is left: a bubble behind a tip
+ * pops in the round after the tip went.  The call stops as kt_ctr_clip_tips does.
+ * stats (host memory, may be NULL; KT_SIMPLIFY_STATS values, overwritten): [0] rounds that erased something, [1] tips,
+ * [2] tip nodes, [3] isolated unitigs, [4] isolated nodes, [5] unitigs popped, [6] their nodes, [7] bubbles, [8] occurrences
+ * erased, [9] 1 if the last round still erased something (stopped by max_rounds), else 0, [10], [11] 0.
+ * With max_bubble_nodes == 0 the table afterwards and stats [0..4], [8], [9] are kt_ctr_clip_tips' table and stats [0..4],
+ * [5], [6] for the same arguments.  Errors as in kt_ctr_clip_tips: an error in round r leaves the table as rounds 0 .. r - 1
+ * left it and stats describes those rounds; a refusal in round 0 leaves stats untouched.  Synchronises.  Device scratch:
+ * kt_ctr_clip_tips'. */
+#define KT_SIMPLIFY_STATS 12
+int kt_ctr_simplify(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint32_t max_bubble_nodes,
+                    uint32_t max_rounds, uint32_t flags, uint64_t *stats);
+
 /* Where the table's entries are wanted - told BEFORE counting, so that counting can deliver them there.
  * replaces: the same map.scan as kt_ctr_export (counter/src/lib.rs:162-165, :220-230), for the usual life of a
  * table: filled once, written out once.  keys_dev / counts_dev are DEVICE arrays of max_out entries owned by the

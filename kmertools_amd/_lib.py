@@ -22,6 +22,7 @@ KT_SETCNT_FIRST, KT_SETCNT_MIN, KT_SETCNT_MAX, KT_SETCNT_SUM = 0, 1, 2, 3
 KT_GRAPH_CENSUS = 32
 KT_TIP_KEEP, KT_TIP_TIP, KT_TIP_ISOLATED, KT_TIP_TALLY = 0, 1, 2, 4
 KT_CLIP_ISOLATED, KT_CLIP_STATS = 1, 8
+KT_BUBBLE_POP, KT_BUBBLE_TALLY, KT_SIMPLIFY_STATS = 4, 4, 12
 
 # every symbol include/kmertools_hip.h declares: name -> (restype, argtypes)
 _vp, _u64, _u32, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -71,6 +72,8 @@ SYMBOLS = {
                                    C.POINTER(_u64), _i]),
     "kt_ctr_unitig_tips": (_i, [_vp, _u32, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp, _i]),
     "kt_ctr_clip_tips": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "kt_ctr_unitig_bubbles": (_i, [_vp, _u32, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp, _i]),
+    "kt_ctr_simplify": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "kt_ctr_erase": (_i, [_vp, _vp, _u64, C.POINTER(_u64), _i]),
     "kt_cgr_points": (_i, [_vp, _vp, _vp, _u64, C.c_double, _vp, _vp, _i]),
     "kt_minimisers": (_i, [_vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _i]),

@@ -2084,15 +2084,26 @@ std::string UnitigComputer::unitigs() {
     // Clipping (kt_ctr_clip_tips) adds, per entry when every entry is a single-node unitig: its offset, count sum, flags and
     // two link offsets in place of bases the run does not write (36), its class and mark (2) - the list of keys to erase (8 a
     // node) lies where the sort's keys lay, the erase's surviving pairs (12) where the nodes lay - and per slot one bit of the
-    // erase's mask: 38 / 1.9 + 1 / 8 < 21
-    if (std::string e = whole_table(dev_, in_path_, ksize_, clip_ ? 16 + 74 + 21 : 16 + 74, "unitigs", &table_); !e.empty()) return e;
+    // erase's mask: 38 / 1.9 + 1 / 8 < 21.  Popping bubbles (kt_ctr_simplify) claims no more than that.
+    if (std::string e = whole_table(dev_, in_path_, ksize_, clip_ || pop_ ? 16 + 74 + 21 : 16 + 74, "unitigs", &table_); !e.empty()) return e;
     PhaseTimer pt("unitigs");
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     Lap lap;
     if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
-    if (clip_) {  // the table is clipped in place: everything below describes the clipped graph
+    if (pop_) {  // the table is simplified in place, tips (with clip_) and bubbles in the same rounds
+        uint64_t st[KT_SIMPLIFY_STATS] = {};
+        if (kt_ctr_simplify(table_, min_count_, max_count_, clip_ ? tip_nodes_ : 0u, bubble_nodes_, clip_rounds_,
+                            drop_isolated_ ? KT_CLIP_ISOLATED : 0u, st) != KT_OK)
+            return kt_last_error();
+        static const char *names[10] = {"rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "popped", "popped_nodes", "bubbles",
+                                        "occurrences", "converged"};
+        const uint64_t values[10] = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9] ? 0ull : 1ull};
+        std::string s;
+        append_stats_rows(s, names, values, 10);
+        if (std::string e = write_text_file(out_dir_ + "/unitigs.simplify.stats", s); !e.empty()) return e;
+    } else if (clip_) {  // the table is clipped in place: everything below describes the clipped graph
         uint64_t st[KT_CLIP_STATS] = {};
         if (kt_ctr_clip_tips(table_, min_count_, max_count_, tip_nodes_, clip_rounds_, drop_isolated_ ? KT_CLIP_ISOLATED : 0u, st) != KT_OK)
             return kt_last_error();

@@ -419,7 +419,10 @@ class GraphComputer {
 // appends " L:{su}:{v}:{sv}" per directed link to the header lines of unitigs.fa; either one writes
 // {out_dir}/unitigs.links.stats (links, edges, dead_ends, isolated, self_links, max_end_degree).  With set_clip the counted
 // table is clipped first (kt_ctr_clip_tips), every file describes the clipped graph, and {out_dir}/unitigs.clip.stats holds
-// rounds, tips, tip_nodes, isolated, isolated_nodes, occurrences, converged.
+// rounds, tips, tip_nodes, isolated, isolated_nodes, occurrences, converged.  With set_bubbles the table is simplified by
+// kt_ctr_simplify instead - bubbles popped, and tips clipped in the same rounds when set_clip is given too - and
+// {out_dir}/unitigs.simplify.stats holds rounds, tips, tip_nodes, isolated, isolated_nodes, popped, popped_nodes, bubbles,
+// occurrences, converged (and no unitigs.clip.stats is written).
 class UnitigComputer {
   public:
     UnitigComputer(std::string in_path, std::string out_dir, int ksize);
@@ -434,6 +437,9 @@ class UnitigComputer {
     void set_clip(uint32_t tip_nodes, uint32_t rounds, bool drop_isolated) {
         clip_ = true, tip_nodes_ = tip_nodes, clip_rounds_ = rounds, drop_isolated_ = drop_isolated;
     }
+    // before anything is written, of the branches of at most bubble_nodes k-mers between the same two ends all but the best
+    // are erased, for at most `rounds` rounds - the rounds of set_clip, where both are given
+    void set_bubbles(uint32_t bubble_nodes, uint32_t rounds) { pop_ = true, bubble_nodes_ = bubble_nodes, clip_rounds_ = rounds; }
     void set_device(int d) { dev_.index = d; }
     std::string unitigs();  // "" or the error message
 
@@ -442,8 +448,8 @@ class UnitigComputer {
     int ksize_;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
     bool stats_only_ = false, gfa_ = false, fa_links_ = false;
-    bool clip_ = false, drop_isolated_ = false;
-    uint32_t tip_nodes_ = 0, clip_rounds_ = 8;
+    bool clip_ = false, drop_isolated_ = false, pop_ = false;
+    uint32_t tip_nodes_ = 0, clip_rounds_ = 8, bubble_nodes_ = 0;
     Device dev_;
     kt_ctr *table_ = nullptr;
 };

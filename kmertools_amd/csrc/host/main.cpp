@@ -900,6 +900,13 @@ const char *HELP_UNITIGS =
     "--drop-isolated erases the unitigs that short without a link at either end as well.  {output}/unitigs.clip.stats holds\n"
     "rounds, tips, tip_nodes, isolated, isolated_nodes, occurrences (all erased) and converged (1: the last round found\n"
     "nothing, 0: stopped by --clip-rounds).\n\n"
+    "--pop-bubbles removes the short parallel paths that a SNP, a small indel or a repeated error leaves: of the unitigs of at\n"
+    "most --bubble-nodes k-mers that are no cycles and have exactly one link at either end, to the same two ends of other\n"
+    "unitigs, only the one with the highest mean count (then: the lowest number) stays.  The others' k-mers are erased and the\n"
+    "unitigs made again, for --clip-rounds rounds or until a round finds nothing; with --clip-tips both rules mark the unitigs\n"
+    "of every round, so that a bubble behind a tip pops in the round after the tip went.  {output}/unitigs.simplify.stats then\n"
+    "holds rounds, tips, tip_nodes, isolated, isolated_nodes, popped, popped_nodes, bubbles, occurrences (all erased) and\n"
+    "converged, and takes the place of unitigs.clip.stats.\n\n"
     "Usage: kmertools unitigs [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
     "Options:\n"
     "  -i, --input <INPUT>          Input file path\n"
@@ -912,8 +919,11 @@ const char *HELP_UNITIGS =
     "      --links                  Append L:{su}:{v}:{sv} fields to the header lines of unitigs.fa; also unitigs.links.stats\n"
     "      --clip-tips              Erase the tips from the table before the unitigs are written; also unitigs.clip.stats\n"
     "      --tip-nodes <N>          Longest tip, in k-mers [default: k] (needs --clip-tips)\n"
-    "      --clip-rounds <R>        Most rounds of clipping, 1..1024 [default: 8] (needs --clip-tips)\n"
+    "      --clip-rounds <R>        Most rounds of clipping, 1..1024 [default: 8] (needs --clip-tips or --pop-bubbles)\n"
     "      --drop-isolated          Erase the isolated unitigs of at most --tip-nodes k-mers too (needs --clip-tips)\n"
+    "      --pop-bubbles            Erase all but the best of parallel branches before the unitigs are written; also\n"
+    "                               unitigs.simplify.stats\n"
+    "      --bubble-nodes <N>       Longest branch of a bubble, in k-mers [default: 2k] (needs --pop-bubbles)\n"
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
@@ -924,7 +934,7 @@ int cmd_unitigs(int argc, char **argv, int from) {
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
                                      {0, "device", true},      {0, "gfa", false},          {0, "links", false},
                                      {0, "clip-tips", false},  {0, "tip-nodes", true},     {0, "clip-rounds", true},
-                                     {0, "drop-isolated", false}};
+                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -942,9 +952,12 @@ int cmd_unitigs(int argc, char **argv, int from) {
     const bool clip = f.count("clip-tips") != 0;
     const uint64_t tip_nodes = ranged(f, "tip-nodes", 1, 0x7FFFFFFEull, false, (uint64_t)k);
     const uint64_t clip_rounds = ranged(f, "clip-rounds", 1, 1024, false, 8);
+    const bool pop = f.count("pop-bubbles") != 0;
+    const uint64_t bubble_nodes = ranged(f, "bubble-nodes", 1, 0x7FFFFFFEull, false, 2 * (uint64_t)k);
     for (const char *needs : {"tip-nodes", "clip-rounds", "drop-isolated"})
-        if (f.count(needs) && !clip)
+        if (f.count(needs) && !clip && !(pop && std::string(needs) == "clip-rounds"))
             usage_error(std::string("the argument '--") + needs + "' requires '--clip-tips'");
+    if (f.count("bubble-nodes") && !pop) usage_error("the argument '--bubble-nodes' requires '--pop-bubbles'");
     if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
@@ -953,6 +966,7 @@ int cmd_unitigs(int argc, char **argv, int from) {
     UnitigComputer uc(in, out, k);
     uc.set_links(gfa, links);
     if (clip) uc.set_clip((uint32_t)tip_nodes, (uint32_t)clip_rounds, f.count("drop-isolated") != 0);
+    if (pop) uc.set_bubbles((uint32_t)bubble_nodes, (uint32_t)clip_rounds);
     uc.set_range((uint32_t)lo, (uint32_t)hi);
     uc.set_stats_only(f.count("stats-only") != 0);
     uc.set_device(device);

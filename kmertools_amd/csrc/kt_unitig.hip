@@ -36,10 +36,16 @@
 //   j. list      kt_ctr_clip_tips only, one thread per node: its key where its unitig (stage d's place, ex_id) is marked
 //                for erasing, else KT_EMPTY_KEY - kt_ctr_erase skips those, so the list is not compacted; it goes to
 //                kt_ctr_erase as device memory, and the next round starts at stage a on what is left
+// kt_ctr_unitig_bubbles and kt_ctr_simplify run the same round with one more rule, alone or behind stage i on the stream:
+//   k. bubbles   one thread per unitig: a branch (no cycle, at most max_bubble_nodes nodes, exactly one link at either end,
+//                neither to itself) looks through the at most 5 links of the end its + link arrives at for branches between
+//                the same two ends, and is popped when one of them outranks it (a higher mean count as 128-bit products,
+//                then the lower number); its bit is ORed into the unitig's mark, so that stage j lists tips and popped
+//                branches in one pass; no class array - the predicate is a handful of loads, made again for a neighbour
 // Anything the rule excludes (a link without an answer, a neighbour that is no node, a chain that is neither a path nor a
 // cycle) raises a bit in the call's error word and comes back as an error: nothing spins.
 // On the host a call is a Run: its methods are the stages - nodes (a), chains (b to d), degrees (f), spell (e), emit (g),
-// tips (h to j) - and every entry point says which of them it runs, and into which Outputs.
+// marks (h to k) - and every entry point says which of them it runs, and into which Outputs.
 #include "kt_device.hpp"
 #include "kt_launch.hpp"
 
@@ -501,14 +507,17 @@ struct TipArgs {
 
 // the round's device words: tally[0..4) as kt_ctr_unitig_tips gives them, [4] the tips' and [5] the isolated unitigs' occurrences
 constexpr int TIP_WORDS = 6;
+// ... and behind them, in a round with the bubble rule: tally[0..4) as kt_ctr_unitig_bubbles gives them
+constexpr int BUBBLE_WORDS = 4, ROUND_WORDS = TIP_WORDS + BUBBLE_WORDS;
 constexpr uint8_t CLS_NONE = 0, CLS_LIVE_PLUS = 1, CLS_LIVE_MINUS = 2, CLS_ISOLATED = 3;
 
-// one tip round, as its callers ask for it and as it comes back
+// one marking round, as its callers ask for it and as it comes back
 struct TipRun {
-    uint32_t max_tip_nodes;
-    uint32_t erase_marks;           // kt_ctr_clip_tips: the marks (bits) whose nodes stage j lists; 0: no stage j
+    uint32_t max_tip_nodes;         // 0: no tip rule (no stages h and i)
+    uint32_t erase_marks;           // kt_ctr_clip_tips, kt_ctr_simplify: the marks (bits) whose nodes stage j lists; 0: no stage j
+    uint32_t max_bubble_nodes = 0;  // 0: no bubble rule (no stage k)
     uint64_t nu = 0;                // unitigs
-    uint64_t tally[TIP_WORDS] = {};
+    uint64_t tally[ROUND_WORDS] = {};  // (the bubble words stay 0 in a round without the rule)
     uint8_t *d_marks = nullptr;             // nu marks, in OUT
     unsigned long long *d_words = nullptr;  // the tally on the device
     uint64_t *d_list = nullptr;             // stage j: n_list keys, KT_EMPTY_KEY for a node that stays, in OUT
@@ -571,6 +580,50 @@ __global__ __launch_bounds__(BLOCK) void unitig_tip_mark_kernel(TipArgs a, const
     uint64_t v[TIP_WORDS] = {tipped, tipped ? nodes : 0, alone, alone ? nodes : 0, tipped ? occ : 0, alone ? occ : 0};
 #pragma unroll
     for (int j = 0; j < TIP_WORDS; j++) {
+        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_down(v[j], o, 64);
+        if ((threadIdx.x & 63) == 0 && v[j]) atomicAdd(words + j, (unsigned long long)v[j]);
+    }
+}
+
+// k. u is a branch: *la, *lb = the one link of its + end and of its - end
+__device__ __forceinline__ bool bubble_branch(const TipArgs &a, uint32_t max_bubble_nodes, uint64_t u, uint32_t *la, uint32_t *lb) {
+    if ((a.flags[u] & KT_UNITIG_CIRCULAR) || nodes_of(a, u) > (uint64_t)max_bubble_nodes) return false;
+    const uint64_t l0 = a.link_offsets[2 * u], l1 = a.link_offsets[2 * u + 1], l2 = a.link_offsets[2 * u + 2];
+    if (l1 - l0 != 1 || l2 - l1 != 1) return false;
+    *la = a.link_to[l0], *lb = a.link_to[l1];
+    return (*la >> 1) != u && (*lb >> 1) != u;
+}
+
+// k. one thread per unitig: a branch u with links a and b looks at the links h of end a ^ 1 (its own mirror 2u + 1 among them);
+// w = h >> 1 is parallel when it is a branch whose end h ^ 1 links to a (the mirror of h) and whose end h links to b; u is
+// popped when a parallel w outranks it, and counts the bubble when it has a parallel branch and none outranks it.  ORs
+// KT_BUBBLE_POP into marks[u]; words = the round's bubble words
+__global__ __launch_bounds__(BLOCK) void unitig_bubble_mark_kernel(TipArgs a, uint32_t max_bubble_nodes, uint8_t *__restrict__ marks,
+                                                                   unsigned long long *__restrict__ words) {
+    const uint64_t u = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    bool found = false, popped = false;  // (every lane stays for the wave's sums)
+    uint32_t la = 0, lb = 0;
+    uint64_t c_u = 0, n_u = 0;
+    if (u < a.nu && bubble_branch(a, max_bubble_nodes, u, &la, &lb) && (la ^ 1u) < 2 * a.nu) {
+        c_u = a.count_sums[u], n_u = nodes_of(a, u);
+        const uint64_t g = la ^ 1u;
+        for (uint64_t y = a.link_offsets[g]; y < a.link_offsets[g + 1]; y++) {
+            const uint32_t h = a.link_to[y];
+            const uint64_t w = h >> 1;
+            uint32_t wa, wb;
+            if (w == u || w >= a.nu || !bubble_branch(a, max_bubble_nodes, w, &wa, &wb)) continue;
+            if ((h & 1u ? wa : wb) != la || (h & 1u ? wb : wa) != lb) continue;  // the links of ends h ^ 1 and h
+            found = true;
+            const uint64_t c_w = a.count_sums[w], n_w = nodes_of(a, w);
+            const uint64_t lh = __umul64hi(c_w, n_u), ll = c_w * n_u, rh = __umul64hi(c_u, n_w), rl = c_u * n_w;
+            popped = popped || (lh != rh ? lh > rh : ll != rl ? ll > rl : w < u);
+        }
+    }
+    if (popped) marks[u] |= KT_BUBBLE_POP;
+    // the tally: summed over the wave, one atomic per word and wave that has something to add
+    uint64_t v[BUBBLE_WORDS] = {popped, popped ? n_u : 0, found && !popped, popped ? c_u : 0};
+#pragma unroll
+    for (int j = 0; j < BUBBLE_WORDS; j++) {
         for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_down(v[j], o, 64);
         if ((threadIdx.x & 63) == 0 && v[j]) atomicAdd(words + j, (unsigned long long)v[j]);
     }
@@ -752,25 +805,34 @@ struct Run {
             else KT_HIP(hipMemsetAsync(first, 0, 8, st));
         return KT_OK;
     }
-    // h to j behind e and g, in OUT (the graph's sort has given it back): words | classes | marks | list
-    int tips(const Outputs &o, TipRun *tip) {
+    // h to k behind e and g, in OUT (the graph's sort has given it back): words | classes | marks | list.  The tip rule (h, i)
+    // where tip->max_tip_nodes, the bubble rule (k) where tip->max_bubble_nodes - behind i on the stream, or over zeroed marks -
+    // and one list (j) of the union; the tip rule alone claims and launches what it always did
+    int marks(const Outputs &o, TipRun *tip) {
         const TipArgs a{o.offsets, o.count_sums, o.flags, o.link_offsets, o.link_to, nu, k, tip->max_tip_nodes};
         const dim3 U = blocks_for(nu), B(BLOCK);
+        const bool tips = tip->max_tip_nodes != 0, bubbles = tip->max_bubble_nodes != 0;
+        const uint64_t words = bubbles ? ROUND_WORDS : TIP_WORDS;
         uint8_t *cls = nullptr;
         tip->nu = nu, tip->n_list = tip->erase_marks ? n : 0;
-        if (int rc = carve(call, kt::OUT, &tip->d_words, TIP_WORDS, &cls, nu, &tip->d_marks, nu, &tip->d_list, tip->n_list)) return rc;
-        KT_HIP(hipMemsetAsync(tip->d_words, 0, TIP_WORDS * 8, st));
-        hipLaunchKernelGGL(unitig_tip_class_kernel, U, B, 0, st, a, cls);
-        hipLaunchKernelGGL(unitig_tip_mark_kernel, U, B, 0, st, a, cls, tip->d_marks, tip->d_words);
+        if (int rc = carve(call, kt::OUT, &tip->d_words, words, &cls, tips ? nu : 0, &tip->d_marks, nu, &tip->d_list, tip->n_list)) return rc;
+        KT_HIP(hipMemsetAsync(tip->d_words, 0, words * 8, st));
+        if (tips) {
+            hipLaunchKernelGGL(unitig_tip_class_kernel, U, B, 0, st, a, cls);
+            hipLaunchKernelGGL(unitig_tip_mark_kernel, U, B, 0, st, a, cls, tip->d_marks, tip->d_words);
+        } else {
+            KT_HIP(hipMemsetAsync(tip->d_marks, 0, nu, st));
+        }
+        if (bubbles) hipLaunchKernelGGL(unitig_bubble_mark_kernel, U, B, 0, st, a, tip->max_bubble_nodes, tip->d_marks, tip->d_words + TIP_WORDS);
         if (tip->n_list)
             hipLaunchKernelGGL(unitig_tip_list_kernel, blocks_for(n), B, 0, st, keys, place, ex_id, n, tip->d_marks, nu, tip->erase_marks,
                                tip->d_list);
-        return fetch(tip->tally, tip->d_words, TIP_WORDS * 8);
+        return fetch(tip->tally, tip->d_words, words * 8);
     }
 };
 
-// One tip round under the device call `call`: the linked stages with offsets, count sums, flags and links made in OFFSETS and
-// no base written, then h to j.  No node: *tip as it came.
+// One marking round under the device call `call`: the linked stages with offsets, count sums, flags and links made in OFFSETS
+// and no base written, then h to k as *tip asks.  No node: *tip as it came.
 int tip_round(Call &call, const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, TipRun *tip) {
     Run r{call, name, table, min_count, max_count};
     if (int rc = r.begin()) return rc;
@@ -782,7 +844,72 @@ int tip_round(Call &call, const char *name, kt_ctr *table, uint32_t min_count, u
     if (int rc = o.carve(call, r.nu, 0, r.n_ends, r.n_links)) return rc;
     if (int rc = r.spell(o)) return rc;
     if (int rc = r.emit(o)) return rc;
-    return r.tips(o, tip);
+    return r.marks(o, tip);
+}
+
+// kt_ctr_unitig_tips and kt_ctr_unitig_bubbles: one round of the one rule `tr` asks for, read-only; the marks and the
+// `count` words from `first` of the round's words go to the caller.  `refusal`: what is wrong with the rule's argument, or null.
+int mark_call(const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, TipRun tr, const char *refusal, int first,
+              int count, uint8_t *marks, uint64_t max_unitigs, uint64_t *n_unitigs, uint64_t *tally, int mem) {
+    if (!table || !n_unitigs) return kt::fail(KT_ERR_ARG, std::string(name) + ": null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, mem, name);
+    if (int rc = call.enter()) return rc;
+    if (refusal) return call.fail(refusal);
+    if (max_unitigs && !marks) return call.fail("null marks");
+    // the run works in device memory whatever `mem` is: only the marks and the tally go to the caller
+    Call run(ctx, KT_MEM_DEVICE, name);
+    if (int rc = tip_round(run, name, table, min_count, max_count, &tr)) return rc;
+    *n_unitigs = tr.nu;
+    if (max_unitigs && max_unitigs < tr.nu) return call.fail("max_unitigs smaller than the result (*n_unitigs)");
+    if (call.host()) {
+        if (max_unitigs) call.back(marks, tr.d_marks, tr.nu);
+        if (tally)
+            for (int j = 0; j < count; j++) tally[j] = tr.tally[first + j];
+        return call.finish();
+    }
+    if (max_unitigs && tr.nu) KT_HIP(hipMemcpyAsync(marks, tr.d_marks, tr.nu, hipMemcpyDeviceToDevice, ctx->stream));
+    if (tally) {
+        if (tr.d_words) KT_HIP(hipMemcpyAsync(tally, tr.d_words + first, count * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        else KT_HIP(hipMemsetAsync(tally, 0, count * 8, ctx->stream));
+    }
+    return KT_OK;
+}
+
+// kt_ctr_clip_tips and kt_ctr_simplify: mark, list, erase, again - under the caller's `call`, its arguments checked.  s: the
+// stats as kt_ctr_simplify gives them.  *told = s describes what was done (not so when round 0 refuses its arguments).
+int erase_rounds(Call &call, const char *name, kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes,
+                 uint32_t max_bubble_nodes, uint32_t max_rounds, bool drop, uint64_t *s, bool *told) {
+    kt_ctx *ctx = table->ctx;
+    *told = true;
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        TipRun tr{max_tip_nodes, (max_tip_nodes ? (uint32_t)KT_TIP_TIP : 0u) | (drop ? (uint32_t)KT_TIP_ISOLATED : 0u) |
+                                     (max_bubble_nodes ? (uint32_t)KT_BUBBLE_POP : 0u),
+                  max_bubble_nodes};
+        if (int rc = tip_round(call, name, table, min_count, max_count, &tr)) {
+            *told = r != 0;  // (an argument the first round refuses leaves stats untouched, as every refusal does)
+            return rc;
+        }
+        const uint64_t *t = tr.tally, *b = tr.tally + TIP_WORDS;
+        const uint64_t want = t[1] + (drop ? t[3] : 0) + b[1];
+        if (!want) {
+            s[9] = 0;
+            break;
+        }
+        // the list (in OUT) is all the erase reads: the run's other buffers are its to take, behind the run's kernels on the stream
+        for (kt::Buf buf : {kt::BASES, kt::OFFSETS, kt::AUX0, kt::AUX1, kt::AUX2}) ctx->unclaim(buf);
+        uint64_t gone = 0;
+        if (int rc = kt_ctr_erase(table, tr.d_list, tr.n_list, &gone, KT_MEM_DEVICE)) return rc;
+        s[0]++, s[1] += t[0], s[2] += t[1], s[8] += t[4] + b[3];
+        if (drop) s[3] += t[2], s[4] += t[3], s[8] += t[5];
+        s[5] += b[0], s[6] += b[1], s[7] += b[2];
+        s[9] = 1;
+        if (gone != want)
+            return kt::fail(KT_ERR_HIP, std::string(name) + ": internal: the table held " + std::to_string(gone) + " of the " +
+                                            std::to_string(want) + " nodes to erase");
+        call.release();
+    }
+    return KT_OK;
 }
 
 }  // namespace
@@ -841,67 +968,48 @@ extern "C" int kt_ctr_unitigs_linked(kt_ctr *table, uint32_t min_count, uint32_t
 
 extern "C" int kt_ctr_unitig_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint8_t *marks,
                                   uint64_t max_unitigs, uint64_t *n_unitigs, uint64_t *tally, int mem) {
-    if (!table || !n_unitigs) return kt::fail(KT_ERR_ARG, "kt_ctr_unitig_tips: null");
-    kt_ctx *ctx = table->ctx;
-    Call call(ctx, mem, "kt_ctr_unitig_tips");
-    if (int rc = call.enter()) return rc;
-    if (max_tip_nodes == 0) return call.fail("max_tip_nodes must be >= 1");
-    if (max_unitigs && !marks) return call.fail("null marks");
-    // the run works in device memory whatever `mem` is: only the marks and the tally go to the caller
-    Call run(ctx, KT_MEM_DEVICE, "kt_ctr_unitig_tips");
-    TipRun tr{max_tip_nodes, 0u};
-    if (int rc = tip_round(run, "kt_ctr_unitig_tips", table, min_count, max_count, &tr)) return rc;
-    *n_unitigs = tr.nu;
-    if (max_unitigs && max_unitigs < tr.nu) return call.fail("max_unitigs smaller than the result (*n_unitigs)");
-    if (call.host()) {
-        if (max_unitigs) call.back(marks, tr.d_marks, tr.nu);
-        if (tally)
-            for (int j = 0; j < KT_TIP_TALLY; j++) tally[j] = tr.tally[j];
-        return call.finish();
-    }
-    if (max_unitigs && tr.nu) KT_HIP(hipMemcpyAsync(marks, tr.d_marks, tr.nu, hipMemcpyDeviceToDevice, ctx->stream));
-    if (tally) {
-        if (tr.d_words) KT_HIP(hipMemcpyAsync(tally, tr.d_words, KT_TIP_TALLY * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        else KT_HIP(hipMemsetAsync(tally, 0, KT_TIP_TALLY * 8, ctx->stream));
-    }
-    return KT_OK;
+    return mark_call("kt_ctr_unitig_tips", table, min_count, max_count, TipRun{max_tip_nodes, 0u},
+                     max_tip_nodes == 0 ? "max_tip_nodes must be >= 1" : nullptr, 0, KT_TIP_TALLY, marks, max_unitigs, n_unitigs, tally, mem);
+}
+
+extern "C" int kt_ctr_unitig_bubbles(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_bubble_nodes, uint8_t *marks,
+                                     uint64_t max_unitigs, uint64_t *n_unitigs, uint64_t *tally, int mem) {
+    return mark_call("kt_ctr_unitig_bubbles", table, min_count, max_count, TipRun{0u, 0u, max_bubble_nodes},
+                     max_bubble_nodes == 0 ? "max_bubble_nodes must be >= 1" : nullptr, TIP_WORDS, KT_BUBBLE_TALLY, marks, max_unitigs,
+                     n_unitigs, tally, mem);
 }
 
 extern "C" int kt_ctr_clip_tips(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint32_t max_rounds,
                                 uint32_t flags, uint64_t *stats) {
     if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_clip_tips: null");
-    kt_ctx *ctx = table->ctx;
-    Call call(ctx, KT_MEM_DEVICE, "kt_ctr_clip_tips");
+    Call call(table->ctx, KT_MEM_DEVICE, "kt_ctr_clip_tips");
     if (max_tip_nodes == 0) return call.fail("max_tip_nodes must be >= 1");
     if (max_rounds < 1 || max_rounds > 1024) return call.fail("max_rounds must be in 1..1024");
     if (flags & ~KT_CLIP_ISOLATED) return call.fail("unknown flags");
-    const bool drop = flags & KT_CLIP_ISOLATED;
-    uint64_t s[KT_CLIP_STATS] = {};
-    auto leave = [&](int rc) {
-        if (stats)
-            for (int j = 0; j < KT_CLIP_STATS; j++) stats[j] = s[j];
-        return rc;
-    };
-    for (uint32_t r = 0; r < max_rounds; r++) {
-        TipRun tr{max_tip_nodes, (uint32_t)KT_TIP_TIP | (drop ? (uint32_t)KT_TIP_ISOLATED : 0u)};
-        if (int rc = tip_round(call, "kt_ctr_clip_tips", table, min_count, max_count, &tr))
-            return r ? leave(rc) : rc;  // (an argument the first round refuses leaves stats untouched, as every refusal does)
-        const uint64_t want = tr.tally[1] + (drop ? tr.tally[3] : 0);
-        if (!want) {
-            s[6] = 0;
-            break;
-        }
-        // the list (in OUT) is all the erase reads: the run's other buffers are its to take, behind the run's kernels on the stream
-        for (kt::Buf b : {kt::BASES, kt::OFFSETS, kt::AUX0, kt::AUX1, kt::AUX2}) ctx->unclaim(b);
-        uint64_t gone = 0;
-        if (int rc = kt_ctr_erase(table, tr.d_list, tr.n_list, &gone, KT_MEM_DEVICE)) return leave(rc);
-        s[0]++, s[1] += tr.tally[0], s[2] += tr.tally[1], s[5] += tr.tally[4];
-        if (drop) s[3] += tr.tally[2], s[4] += tr.tally[3], s[5] += tr.tally[5];
-        s[6] = 1;
-        if (gone != want)
-            return leave(kt::fail(KT_ERR_HIP, "kt_ctr_clip_tips: internal: the table held " + std::to_string(gone) + " of the " +
-                                                  std::to_string(want) + " nodes to erase"));
-        call.release();
+    uint64_t s[KT_SIMPLIFY_STATS] = {};
+    bool told = false;
+    const int rc = erase_rounds(call, "kt_ctr_clip_tips", table, min_count, max_count, max_tip_nodes, 0u, max_rounds,
+                                flags & KT_CLIP_ISOLATED, s, &told);
+    if (stats && told) {
+        for (int j = 0; j < 5; j++) stats[j] = s[j];
+        stats[5] = s[8], stats[6] = s[9], stats[7] = 0;
     }
-    return leave(KT_OK);
+    return rc;
+}
+
+extern "C" int kt_ctr_simplify(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint32_t max_tip_nodes, uint32_t max_bubble_nodes,
+                               uint32_t max_rounds, uint32_t flags, uint64_t *stats) {
+    if (!table) return kt::fail(KT_ERR_ARG, "kt_ctr_simplify: null");
+    Call call(table->ctx, KT_MEM_DEVICE, "kt_ctr_simplify");
+    if (max_tip_nodes == 0 && max_bubble_nodes == 0) return call.fail("max_tip_nodes and max_bubble_nodes are both 0");
+    if (max_rounds < 1 || max_rounds > 1024) return call.fail("max_rounds must be in 1..1024");
+    if (flags & ~KT_CLIP_ISOLATED) return call.fail("unknown flags");
+    if ((flags & KT_CLIP_ISOLATED) && max_tip_nodes == 0) return call.fail("KT_CLIP_ISOLATED needs max_tip_nodes >= 1");
+    uint64_t s[KT_SIMPLIFY_STATS] = {};
+    bool told = false;
+    const int rc = erase_rounds(call, "kt_ctr_simplify", table, min_count, max_count, max_tip_nodes, max_bubble_nodes, max_rounds,
+                                flags & KT_CLIP_ISOLATED, s, &told);
+    if (stats && told)
+        for (int j = 0; j < KT_SIMPLIFY_STATS; j++) stats[j] = s[j];
+    return rc;
 }

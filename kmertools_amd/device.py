@@ -21,6 +21,9 @@ NO_KMER = 0xFFFFFFFF  # KT_NO_KMER: the entry of a profile where no k-mer starts
 TIP_KEEP, TIP_TIP, TIP_ISOLATED = 0, 1, 2  # Counter.unitig_tips' marks (KT_TIP_*)
 CLIP_ISOLATED = 1  # Counter.clip_tips(drop_isolated=True) (KT_CLIP_ISOLATED)
 CLIP_STATS_NAMES = ("rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "occurrences", "converged")
+BUBBLE_POP = 4  # Counter.unitig_bubbles' mark (KT_BUBBLE_POP): a bit beside TIP_TIP and TIP_ISOLATED
+SIMPLIFY_STATS_NAMES = ("rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "popped", "popped_nodes", "bubbles", "occurrences",
+                        "converged")
 
 
 def _ptr(x):
@@ -814,6 +817,44 @@ class Counter:
                                           _ptr(stats)))
         stats[6] = 1 - stats[6]  # (the call says whether the last round still erased something)
         return {name: int(v) for name, v in zip(CLIP_STATS_NAMES, stats)}
+
+    def unitig_bubbles(self, max_bubble_nodes=None, min_count=1, max_count=None):
+        """One round of the bubble rule over unitigs()' numbering (kt_ctr_unitig_bubbles; the table is not changed): returns
+        (marks u8: 0 or BUBBLE_POP per unitig, tally u64[4]: popped unitigs, their nodes, bubbles, occurrences popped).
+        max_bubble_nodes None: 2k nodes.  A count-only call, then one call sized by it."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        mb = 2 * self.k if max_bubble_nodes is None else int(max_bubble_nodes)
+        nu = C.c_uint64()
+        tally = np.zeros(_lib.KT_BUBBLE_TALLY, np.uint64)
+        check(_lib.lib().kt_ctr_unitig_bubbles(self._h, int(min_count), hi, mb, None, 0, C.byref(nu), _ptr(tally), KT_MEM_HOST))
+        marks = np.zeros(nu.value, np.uint8)
+        if nu.value:
+            check(_lib.lib().kt_ctr_unitig_bubbles(self._h, int(min_count), hi, mb, _ptr(marks), nu.value, C.byref(nu), _ptr(tally),
+                                                   KT_MEM_HOST))
+        return marks, tally
+
+    def unitig_bubbles_device(self, marks, max_unitigs, tally=None, max_bubble_nodes=None, min_count=1, max_count=None):
+        """unitig_bubbles into device tensors (marks u8 of max_unitigs, tally u64 bit patterns of 4 or None; None, 0 only counts
+        and still fills tally); returns n_unitigs.  Raises KmertoolsError (KT_ERR_ARG) when the room is too small."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        mb = 2 * self.k if max_bubble_nodes is None else int(max_bubble_nodes)
+        nu = C.c_uint64()
+        check(_lib.lib().kt_ctr_unitig_bubbles(self._h, int(min_count), hi, mb, _ptr(marks), int(max_unitigs), C.byref(nu),
+                                               _ptr(tally), KT_MEM_DEVICE))
+        return nu.value
+
+    def simplify(self, max_tip_nodes=None, max_bubble_nodes=None, max_rounds=8, drop_isolated=False, min_count=1, max_count=None):
+        """Clips the tips and pops the bubbles of the table's de Bruijn graph in place, both rules in every round, until a round
+        finds nothing or max_rounds are done (kt_ctr_simplify).  max_tip_nodes None: k nodes, max_bubble_nodes None: 2k nodes;
+        0 switches a rule off.  Returns the stats as a dict (SIMPLIFY_STATS_NAMES)."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        tip = self.k if max_tip_nodes is None else int(max_tip_nodes)
+        mb = 2 * self.k if max_bubble_nodes is None else int(max_bubble_nodes)
+        stats = np.zeros(_lib.KT_SIMPLIFY_STATS, np.uint64)
+        check(_lib.lib().kt_ctr_simplify(self._h, int(min_count), hi, tip, mb, int(max_rounds), CLIP_ISOLATED if drop_isolated else 0,
+                                         _ptr(stats)))
+        stats[9] = 1 - stats[9]  # (the call says whether the last round still erased something)
+        return {name: int(v) for name, v in zip(SIMPLIFY_STATS_NAMES, stats)}
 
     def export_stage_range(self, min_count=1, max_count=None):
         """stages the entries with min_count <= count <= max_count on the device; returns how many (export_fetch reads them)"""
