@@ -705,6 +705,46 @@ int kt_sketch_pairs(kt_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_siz
  * denom == 0); 1 when j == 0, else min(1, -ln(2j / (1 + j)) / k); j == 1 gives 0. */
 double kt_mash_distance(uint32_t shared, uint32_t denom, int k);
 
+/* HyperLogLog registers of the distinct canonical k-mers of a batch (`kmertools card`, `--estimate-size`; what ntCard, KMC's
+ * estimator and Jellyfish's size hint give their users).  replaces: nothing - the reference has no such operation.  No
+ * table is involved.
+ *   m = 2^p registers of one byte, q = 64 - p.
+ *   A read's k-mers are its valid windows, canonical, as for every other k-mer walk here (1 <= k <= 31).
+ *   h = mix64(kmer ^ seed), the formula printed above kt_sketch_batch.
+ *   Register index j = h >> q.
+ *   Rank r = 1 + (number of leading zeros of the low q bits of h, taken as a q-bit word): r = q + 1 when those bits are all
+ *   zero, and r lies in 1..q+1.
+ *   registers[j] = max(registers[j], r).
+ * Like kt_ctr_spectrum the call combines into what the caller passes: the caller zeroes the array once; batches,
+ * hash-partition passes and files accumulate into one array; a batch added in two calls, in either order, gives the
+ * registers of one call with both.  *n_kmers (may be NULL) += the windows, with multiplicity.
+ * `mem` says where bases, offsets, registers and n_kmers live; KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the
+ * context's stream.  n_reads == 0 is KT_OK and touches nothing.
+ * KT_ERR_ARG: k outside 1..31, p outside KT_CARD_MIN_P..KT_CARD_MAX_P, a bad mem, a null buffer with n_reads > 0, a read of
+ * 2^32 bases or more. */
+#define KT_CARD_MIN_P 4
+#define KT_CARD_MAX_P 16
+int kt_card_add_reads(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k, int p,
+                      uint64_t seed, uint8_t *registers, uint64_t *n_kmers, int mem);
+
+/* into[j] = max(into[j], from[j]) for the 2^p registers of two host arrays: the registers of the union of what the two
+ * arrays have seen (same k, p and seed).  KT_ERR_ARG: p outside KT_CARD_MIN_P..KT_CARD_MAX_P, a null array. */
+int kt_card_merge(uint8_t *into, const uint8_t *from, int p);
+
+/* The number of distinct k-mers behind 2^p registers (a host array): Ertl's improved raw estimator, which needs no bias
+ * tables, evaluated in doubles in exactly this order.  C[v] = number of registers equal to v, for v = 0..q+1 (a register
+ * above q + 1 is KT_ERR_ARG), m = 2^p:
+ *   z = m * tau(1 - C[q+1]/m);  for v = q down to 1: z = 0.5 * (z + C[v]);  z += m * sigma(C[0]/m)
+ *   estimate = (m*m / (2 ln 2)) / z
+ *   sigma(x): x == 1 -> +inf; y = 1, z = x; repeat { x *= x; z' = z; z += x*y; y += y } until z' == z
+ *   tau(x):   x == 0 or x == 1 -> 0; y = 1, z = 1 - x; repeat { x = sqrt(x); z' = z; y *= 0.5; z -= (1-x)^2 * y } until z' == z;
+ *             return z/3
+ * All-zero registers give 0.  *zero_registers (may be NULL) = C[0].  KT_ERR_ARG also: p out of range, a null array. */
+int kt_card_estimate(const uint8_t *registers, int p, double *estimate, uint64_t *zero_registers);
+
+/* the estimator's relative standard error, 1.04 / sqrt(2^p) */
+double kt_card_rel_error(int p);
+
 /* Multi-GPU routing step (the reference's `min_mer % n_parts` partitioning,
  * counter/src/lib.rs:127, re-expressed as hash-prefix ownership):
  * writes every canonical k-mer of the reads into keys_out grouped by owner

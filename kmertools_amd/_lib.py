@@ -17,6 +17,7 @@ KT_MEM_HOST, KT_MEM_DEVICE = 0, 1
 KT_F64, KT_F32, KT_U32 = 0, 1, 2
 KT_EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
 KT_SKETCH_MAX_S = 16384
+KT_CARD_MIN_P, KT_CARD_MAX_P = 4, 16
 KT_SET_INTERSECT, KT_SET_SUBTRACT, KT_SET_UNION, KT_SET_XOR = 0, 1, 2, 3
 KT_SETCNT_FIRST, KT_SETCNT_MIN, KT_SETCNT_MAX, KT_SETCNT_SUM = 0, 1, 2, 3
 KT_GRAPH_CENSUS = 32
@@ -89,6 +90,10 @@ SYMBOLS = {
     "kt_sketch_merge": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _vp, _i]),
     "kt_sketch_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _i]),
     "kt_mash_distance": (C.c_double, [_u32, _u32, _i]),
+    "kt_card_add_reads": (_i, [_vp, _vp, _vp, _u64, _i, _i, _u64, _vp, _vp, _i]),
+    "kt_card_merge": (_i, [_vp, _vp, _i]),
+    "kt_card_estimate": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_u64)]),
+    "kt_card_rel_error": (C.c_double, [_i]),
     "kt_ctr_route": (_i, [_vp, _vp, _vp, _u64, _i, _i, _vp, _vp, _i]),
     "kt_owner_of": (_u32, [_u64, _u32]),
     "kt_rccl_unique_id": (_i, [_vp]),

@@ -894,7 +894,43 @@ std::string CountComputer::write_histo() const {
 struct InputBound {
     uint64_t n_seq = 0, bases = 0, max_distinct = 0, want = 0;  // n_seq: 0 when the pre-pass was skipped
 };
-static std::string slots_wanted(const std::string &path, int k, InputBound *in) {
+
+// --estimate-size (set_estimate_size): the plan's `want` comes down to what the input's distinct k-mers need
+static struct {
+    bool on = false;
+    int p = 14;
+    uint64_t taken = 0;  // the sum of the estimates used so far
+} g_estimate;
+void set_estimate_size(bool on, int precision) { g_estimate.on = on, g_estimate.p = precision; }
+uint64_t estimate_size_taken() { return g_estimate.taken; }
+// (the library's text for KT_ERR_FULL, kt_ctr_size: the computers hand a failed call's message on, not its code)
+bool table_overflowed(const std::string &err) { return err.find("k-mer table is full") != std::string::npos; }
+
+// One walk over an input into HyperLogLog registers (2^p bytes, combined into; `card` and the estimate of the table plan)
+static std::string card_walk(kt_ctx *ctx, const std::string &path, int k, int p, uint64_t seed, std::vector<uint8_t> &registers,
+                             uint64_t *n_kmers, Cursor *end) {
+    SeqReader reader;
+    if (!reader.open(path, false)) return reader.error();
+    Batch b;
+    return walk(reader, b, TABLE_BATCH_BASES, 1ull << 22, false, nullptr, nullptr, end, [&](const Batch &bb, const Cursor &) -> std::string {
+        if (!bb.bases.empty() &&
+            kt_card_add_reads(ctx, bb.bases.data(), bb.offsets.data(), bb.n_reads(), k, p, seed, registers.data(), n_kmers, KT_MEM_HOST) != KT_OK)
+            return kt_last_error();
+        return "";
+    });
+}
+
+// slots for E distinct k-mers: 5 sigma on top of the estimate (its tails are somewhat heavier than Gaussian; the 1.9 slots
+// per key leave far more), then the 1.9 per key of every plan
+static uint64_t slots_for_estimate(double estimate, int p) {
+    const double e5 = ceil(estimate * (1.0 + 5.0 * kt_card_rel_error(p)));
+    if (!(e5 < 9.0e18)) return ~0ull;
+    const uint64_t e = (uint64_t)e5, want = e + e / 10 * 9;
+    return want < 1024 ? 1024 : want;
+}
+
+// `dev`: the device of the estimate's walk, with --estimate-size (not used without it)
+static std::string slots_wanted(const std::string &path, int k, InputBound *in, Device &dev) {
     std::string err;
     struct stat st;
     const bool plain = !(path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) && stat(path.c_str(), &st) == 0 &&
@@ -910,6 +946,22 @@ static std::string slots_wanted(const std::string &path, int k, InputBound *in) 
     }
     in->want = in->max_distinct + in->max_distinct / 10 * 9;
     if (in->want < 1024) in->want = 1024;
+    if (!g_estimate.on) return "";
+    // one extra walk: the distinct k-mers of this input, estimated (KT_CARD_SCALE, tests: a wrong estimate)
+    Lap lap;
+    if (std::string e = dev.ensure(); !e.empty()) return e;
+    std::vector<uint8_t> registers((size_t)1 << g_estimate.p, 0);
+    if (std::string e = card_walk(dev.ctx, path, k, g_estimate.p, 0, registers, nullptr, nullptr); !e.empty()) return e;
+    double estimate = 0.0;
+    if (kt_card_estimate(registers.data(), g_estimate.p, &estimate, nullptr) != KT_OK) return kt_last_error();
+    if (const char *s = getenv("KT_CARD_SCALE"); s && *s) estimate *= strtod(s, nullptr);
+    const uint64_t bound = in->want;
+    in->want = std::min(bound, slots_for_estimate(estimate, g_estimate.p));
+    const uint64_t shown = estimate < 9.0e18 ? (uint64_t)(estimate + 0.5) : ~0ull;
+    g_estimate.taken += shown;
+    if (getenv("KT_CLI_TIMING"))
+        fprintf(stderr, "[timing] card pre-pass: %.3f s, estimate %llu, slots wanted %llu (bound: %llu)\n", lap(), (unsigned long long)shown,
+                (unsigned long long)in->want, (unsigned long long)bound);
     return "";
 }
 
@@ -980,7 +1032,7 @@ std::string CountComputer::count() {
     if (in_path_ == "-") return "ctr reads its input more than once and cannot take stdin";  // (the reference panics
                                                                                             // on SeqFormat::get("-"))
     InputBound in;
-    if (std::string e = slots_wanted(in_path_, ksize_, &in); !e.empty()) return e;
+    if (std::string e = slots_wanted(in_path_, ksize_, &in, dev_); !e.empty()) return e;
     seq_count_ = in.n_seq;
     total_length_ = in.bases;
     const double t_stats = setup();
@@ -1829,8 +1881,8 @@ static std::string two_tables_setup(Device &dev, const std::string &in_a, const 
                                     const char *what, uint32_t *passes, kt_ctr **ta, kt_ctr **tb) {
     Lap setup;
     InputBound a, b;
-    if (std::string e = slots_wanted(in_a, k, &a); !e.empty()) return e;
-    if (std::string e = slots_wanted(in_b, k, &b); !e.empty()) return e;
+    if (std::string e = slots_wanted(in_a, k, &a, dev); !e.empty()) return e;
+    if (std::string e = slots_wanted(in_b, k, &b, dev); !e.empty()) return e;
     if (std::string e = dev.ensure(); !e.empty()) return e;
     TablePlan plan;
     plan.n = 2;
@@ -1985,7 +2037,7 @@ static std::string graph_census_name(int j) {
 static std::string whole_table(Device &dev, const std::string &path, int k, uint64_t bytes_per_slot, const char *name, kt_ctr **table) {
     Lap setup;
     InputBound in;
-    if (std::string e = slots_wanted(path, k, &in); !e.empty()) return e;
+    if (std::string e = slots_wanted(path, k, &in, dev); !e.empty()) return e;
     if (std::string e = dev.ensure(); !e.empty()) return e;
     TablePlan plan;
     plan.want[0] = in.want;
@@ -2585,6 +2637,68 @@ std::string SketchComputer::sketch() {
         if (std::string e = sketch_input(alt_path_, out_dir_ + "/sketch.alt.tsv", b, dist_); !e.empty()) return e;
     if (dist_) return write_dist(a, alt_path_.empty() ? nullptr : &b);
     return "";
+}
+
+// ---- card ------------------------------------------------------------------------------------------------------------
+CardComputer::CardComputer(std::string in_path, std::string out_dir, int ksize, int precision)
+    : in_path_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize), p_(precision) {}
+
+static void append_fixed6_row(std::string &s, const std::string &name, double x) {
+    s += name;
+    s += '\t';
+    append_fixed6(s, x);
+    s += '\n';
+}
+
+std::string CardComputer::card() {
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
+    const size_t m = (size_t)1 << p_;
+    std::vector<uint8_t> regs[2];
+    double est[2] = {0.0, 0.0};
+    std::string s;
+    const int n_in = alt_path_.empty() ? 1 : 2;
+    for (int i = 0; i < n_in; i++) {
+        const std::string &path = i ? alt_path_ : in_path_;
+        const std::string pre = i ? "alt_" : "";
+        regs[i].assign(m, 0);
+        uint64_t n_kmers = 0, zeros = 0;
+        Cursor end;
+        if (std::string e = card_walk(dev_.ctx, path, ksize_, p_, seed_, regs[i], &n_kmers, &end); !e.empty()) return e;
+        if (kt_card_estimate(regs[i].data(), p_, &est[i], &zeros) != KT_OK) return kt_last_error();
+        // what the table plan of this input would ask for with --estimate-size: never more than the input's bound
+        InputBound in;
+        if (std::string e = slots_wanted(path, ksize_, &in, dev_); !e.empty()) return e;
+        const std::string names[7] = {pre + "sequences", pre + "bases", pre + "kmers", pre + "precision", pre + "registers",
+                                      pre + "zero_registers", pre + "distinct_estimate"};
+        const uint64_t values[7] = {end.reads, end.bases, n_kmers, (uint64_t)p_, (uint64_t)m, zeros, (uint64_t)floor(est[i] + 0.5)};
+        for (int j = 0; j < 7; j++) {
+            const char *name = names[j].c_str();
+            append_stats_rows(s, &name, &values[j], 1);
+        }
+        append_fixed6_row(s, pre + "rel_std_error", kt_card_rel_error(p_));
+        const std::string wn = pre + "slots_wanted";
+        const char *name = wn.c_str();
+        const uint64_t want = std::min(in.want, slots_for_estimate(est[i], p_));
+        append_stats_rows(s, &name, &want, 1);
+
+        std::string r = std::to_string(p_) + '\t' + std::to_string(seed_) + '\t' + std::to_string(ksize_) + '\n';
+        for (size_t j = 0; j < m; j++) {
+            append_uint(r, regs[i][j]);
+            r += '\n';
+        }
+        if (std::string e = write_text_file(out_dir_ + (i ? "/card.alt.registers" : "/card.registers"), r); !e.empty()) return e;
+    }
+    if (n_in == 2) {
+        if (kt_card_merge(regs[0].data(), regs[1].data(), p_) != KT_OK) return kt_last_error();
+        double uni = 0.0;
+        if (kt_card_estimate(regs[0].data(), p_, &uni, nullptr) != KT_OK) return kt_last_error();
+        const double inter = est[0] + est[1] - uni > 0.0 ? est[0] + est[1] - uni : 0.0;
+        const char *names[2] = {"union_estimate", "intersection_estimate"};
+        const uint64_t values[2] = {(uint64_t)floor(uni + 0.5), (uint64_t)floor(inter + 0.5)};
+        append_stats_rows(s, names, values, 2);
+        append_fixed6_row(s, "jaccard_estimate", uni > 0.0 ? inter / uni : 0.0);
+    }
+    return write_text_file(out_dir_ + "/card.stats", s);
 }
 
 }  // namespace kthost

@@ -487,4 +487,33 @@ class SketchComputer {
     std::string write_dist(const Set &a, const Set *b);
 };
 
+// `card`: the HyperLogLog registers of the distinct canonical k-mers of an input (kt_card_add_reads over the input walk) and
+// their estimate (kt_card_estimate).  Writes {out_dir}/card.stats ("name\tvalue": sequences, bases, kmers, precision,
+// registers, zero_registers, distinct_estimate, rel_std_error, slots_wanted; with a second input the same rows with an
+// alt_ prefix, then union_estimate, intersection_estimate and jaccard_estimate from the merged registers) and
+// {out_dir}/card.registers ("p\tseed\tk", then one register per line; card.alt.registers for the second input).
+class CardComputer {
+  public:
+    CardComputer(std::string in_path, std::string out_dir, int ksize, int precision);
+    void set_seed(uint64_t seed) { seed_ = seed; }
+    void set_alt_path(std::string p) { alt_path_ = std::move(p); }
+    void set_threads(int t) { threads_ = t; }
+    void set_device(int d) { dev_.index = d; }
+    std::string card();  // "" or the error message
+
+  private:
+    std::string in_path_, alt_path_, out_dir_;
+    int ksize_, p_, threads_ = 0;
+    uint64_t seed_ = 0;
+    Device dev_;
+};
+
+// --estimate-size of the table commands: with it on, the table plan takes the distinct k-mers of the input it counts from
+// one extra walk (kt_card_add_reads into 2^precision registers) instead of from the input's size alone.  The dispatcher
+// sets it before it runs a command; when the command then fails with a full table (table_overflowed: the estimate was too
+// small) it says so, switches it off and runs the command once more - with the plan of a run without the flag.
+void set_estimate_size(bool on, int precision);
+uint64_t estimate_size_taken();                  // the sum of the estimates the plans of this process have used
+bool table_overflowed(const std::string &err);   // `err` is a command's error for a table that took more keys than slots
+
 }  // namespace kthost

@@ -5,7 +5,8 @@
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
 // and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
 // inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances) and `graph` (de Bruijn adjacency of the counted
-// k-mers) and `unitigs` (that graph's maximal unitigs).
+// k-mers) and `unitigs` (that graph's maximal unitigs) and `card` (a HyperLogLog estimate of the distinct k-mers, which
+// also sizes the tables of the others: --estimate-size).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -121,6 +122,57 @@ std::string required_str(const std::map<std::string, std::string> &f, const char
     return it->second;
 }
 
+// ---- --estimate-size [--estimate-precision P] of the commands that make a k-mer table ---------------------------------
+#define SPEC_ESTIMATE_SIZE {0, "estimate-size", false}
+#define SPEC_ESTIMATE_P {0, "estimate-precision", true}
+#define HELP_ESTIMATE_(sharded)                                                                                              \
+    "      --estimate-size          Size the table from an estimate of the distinct k-mers of the input it is counted\n"    \
+    "                               from (one extra walk over that input: HyperLogLog registers on the GPU) instead of\n"   \
+    "                               from the input's size alone.  An estimate that proves too small costs one more run\n"   \
+    "                               with the input's bound.\n" sharded                                                       \
+    "      --estimate-precision <P> The estimate's 2^P registers, 4..16 [default: 14] (needs --estimate-size)\n"
+#define HELP_ESTIMATE HELP_ESTIMATE_("")
+// (the commands that have --devices)
+#define HELP_ESTIMATE_SHARDED \
+    HELP_ESTIMATE_("                               Not with --devices above 1: the sharded table keeps its bound.\n")
+
+struct EstimateFlags {
+    bool on = false;
+    int p = 14;
+};
+
+// checked with the command's other flags, before any device work
+EstimateFlags estimate_flags(const std::map<std::string, std::string> &f) {
+    EstimateFlags est;
+    est.on = f.count("estimate-size") != 0;
+    bool has_p = false;
+    est.p = (int)ranged(f, "estimate-precision", KT_CARD_MIN_P, KT_CARD_MAX_P, false, 14, &has_p);
+    if (has_p && !est.on) usage_error("the argument '--estimate-precision <P>' requires '--estimate-size'");
+    if (est.on && ranged(f, "devices", 1, 64, false, 1) > 1)
+        usage_error("the argument '--estimate-size' cannot be used with '--devices <N>' above 1");
+    return est;
+}
+
+// Runs a table command (run() makes the command's computer and returns its error, "" for none) under the estimate flags.
+// An estimate that was too small shows as a full table somewhere in the command: the command then runs once more, from
+// the start and in this process, with the plan of a run without the flag - its files are written anew.
+template <class Run>
+int run_table_command(const EstimateFlags &est, Run run) {
+    set_estimate_size(est.on, est.p);
+    std::string e = run();
+    if (est.on && table_overflowed(e)) {
+        fprintf(stderr, "[card] estimate %llu was too small for this input: counting again with the input's bound\n",
+                (unsigned long long)estimate_size_taken());
+        set_estimate_size(false, est.p);
+        e = run();
+    }
+    if (!e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 const char *HELP_MAIN =
     "kmertools: DNA vectorisation\n\n"
     "k-mer based vectorisation for DNA sequences for\nmetagenomics and AI/ML applications\n"
@@ -139,6 +191,7 @@ const char *HELP_MAIN =
     "  graph   De Bruijn adjacency, unitig ends and node census of the counted k-mers\n"
     "  unitigs Maximal unitigs of the de Bruijn graph of the counted k-mers\n"
     "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
+    "  card    Estimate the number of distinct k-mers (HyperLogLog), sizes tables\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
 
@@ -189,6 +242,7 @@ const char *HELP_CTR =
     "                           (lines \"count<TAB>k-mers\", count = 1..H; the last line counts H or more)\n"
     "      --histo-max <H>      Highest count of kmers.histo [default: 10000]\n"
     "      --histo-only         Write kmers.histo and no kmers.counts (implies --histo)\n"
+    HELP_ESTIMATE_SHARDED
     "  -h, --help               Print help\n";
 
 const char *HELP_COV =
@@ -207,6 +261,7 @@ const char *HELP_COV =
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
     "      --devices <N>            Shard the table over N GPUs, --device .. --device + N - 1 [default: 1]\n"
+    HELP_ESTIMATE_SHARDED
     "  -h, --help                   Print help\n";
 
 int make_out_dir(const std::string &out) {
@@ -225,7 +280,7 @@ int cmd_cov(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},    {'a', "alt-input", true}, {'o', "output", true},
                                      {'k', "k-size", true},   {'p', "preset", true},    {'s', "bin-size", true},
                                      {'c', "bin-count", true}, {'m', "memory", true},   {0, "counts", false},
-                                     {'t', "threads", true},  {0, "device", true},      {0, "devices", true}};
+                                     {'t', "threads", true},  {0, "device", true},      {0, "devices", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_COV);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 7, 31, false, 15);
@@ -236,6 +291,7 @@ int cmd_cov(int argc, char **argv, int from) {
     std::string preset = f.count("preset") ? f.at("preset") : "spc";
     if (preset != "csv" && preset != "tsv" && preset != "spc")
         usage_error("invalid value '" + preset + "' for '--preset <PRESET>'\n  [possible values: csv, tsv, spc]");
+    const EstimateFlags est = estimate_flags(f);
     if (int rc = make_out_dir(out)) return rc;
     const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
     for (const std::string &p : {in, kin}) {
@@ -244,21 +300,20 @@ int cmd_cov(int argc, char **argv, int from) {
             return 101;  // SeqFormat::get(...).unwrap()
         }
     }
-    CovComputer cov(in, out, k, bin_size, bin_count);
-    if (threads > 0) cov.set_threads(threads);
-    if (f.count("alt-input")) cov.set_kmer_path(kin);
-    if (f.count("counts")) cov.set_norm(false);
-    cov.set_max_memory((double)mem);
-    cov.set_delim(preset == "csv" ? "," : preset == "tsv" ? "\t" : " ");
-    cov.set_device((int)ranged(f, "device", 0, 63, false, 0));
-    cov.set_devices((int)ranged(f, "devices", 1, 64, false, 1));
-    std::string e = cov.build_table();
-    if (e.empty()) e = cov.compute_coverages();
-    if (!e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;  // build_table().unwrap() / unwraps inside compute_coverages
-    }
-    return 0;
+    const int device = (int)ranged(f, "device", 0, 63, false, 0), devices = (int)ranged(f, "devices", 1, 64, false, 1);
+    return run_table_command(est, [&]() -> std::string {  // (101: build_table().unwrap() / unwraps inside compute_coverages)
+        CovComputer cov(in, out, k, bin_size, bin_count);
+        if (threads > 0) cov.set_threads(threads);
+        if (f.count("alt-input")) cov.set_kmer_path(kin);
+        if (f.count("counts")) cov.set_norm(false);
+        cov.set_max_memory((double)mem);
+        cov.set_delim(preset == "csv" ? "," : preset == "tsv" ? "\t" : " ");
+        cov.set_device(device);
+        cov.set_devices(devices);
+        std::string e = cov.build_table();
+        if (e.empty()) e = cov.compute_coverages();
+        return e;
+    });
 }
 
 const char *HELP_MIN =
@@ -368,7 +423,7 @@ int cmd_ctr(int argc, char **argv, int from) {
                                      {'m', "memory", true}, {'a', "acgt", false},  {'t', "threads", true},
                                      {0, "device", true},   {0, "devices", true},
                                      {0, "min-count", true}, {0, "max-count", true}, {0, "histo", false},
-                                     {0, "histo-max", true}, {0, "histo-only", false}};
+                                     {0, "histo-max", true}, {0, "histo-only", false}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_CTR);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -382,27 +437,27 @@ int cmd_ctr(int argc, char **argv, int from) {
                     std::to_string(max_count));
     const uint64_t histo_max = ranged(f, "histo-max", 1, (1u << 24) - 1, false, 10000);
     const bool histo_only = f.count("histo-only") != 0, histo = histo_only || f.count("histo") != 0;
+    const EstimateFlags est = estimate_flags(f);
     if (int rc = make_out_dir(out)) return rc;
     if (format_from_path(in) == SeqFormat::Unknown) {
         // CountComputer::new unwraps SeqFormat::get (counter/src/lib.rs:38): unknown extension - "-" included - panics
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
-    CountComputer ctr(in, out, k);
-    ctr.set_devices((int)ranged(f, "devices", 1, 64, false, 1));
-    if (threads > 0) ctr.set_threads(threads);
-    if (f.count("acgt")) ctr.set_acgt_output(true);
-    ctr.set_max_memory((double)mem);
-    ctr.set_device((int)ranged(f, "device", 0, 63, false, 0));
-    ctr.set_count_range((uint32_t)min_count, (uint32_t)max_count);
-    if (histo) ctr.set_histo((uint32_t)histo_max, histo_only);
-    std::string e = ctr.count();
-    if (e.empty()) e = ctr.merge(true);
-    if (!e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;  // count()/merge() unwrap in the reference
-    }
-    return 0;
+    const int devices = (int)ranged(f, "devices", 1, 64, false, 1), device = (int)ranged(f, "device", 0, 63, false, 0);
+    return run_table_command(est, [&]() -> std::string {  // (101: count()/merge() unwrap in the reference)
+        CountComputer ctr(in, out, k);
+        ctr.set_devices(devices);
+        if (threads > 0) ctr.set_threads(threads);
+        if (f.count("acgt")) ctr.set_acgt_output(true);
+        ctr.set_max_memory((double)mem);
+        ctr.set_device(device);
+        ctr.set_count_range((uint32_t)min_count, (uint32_t)max_count);
+        if (histo) ctr.set_histo((uint32_t)histo_max, histo_only);
+        std::string e = ctr.count();
+        if (e.empty()) e = ctr.merge(true);
+        return e;
+    });
 }
 
 const char *HELP_FILTER =
@@ -424,13 +479,14 @@ const char *HELP_FILTER =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_filter(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},      {'o', "output", true},     {'k', "k-size", true},
                                      {'a', "alt-input", true},  {0, "min-count", true},    {0, "max-count", true},
                                      {0, "min-solid", true},    {0, "trim", false},        {'m', "memory", true},
-                                     {'t', "threads", true},    {0, "device", true}};
+                                     {'t', "threads", true},    {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_FILTER);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -452,6 +508,7 @@ int cmd_filter(int argc, char **argv, int from) {
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
     const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
     for (const std::string &p : {in, kin}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
@@ -459,19 +516,17 @@ int cmd_filter(int argc, char **argv, int from) {
             return 101;
         }
     }
-    FilterComputer flt(in, out, k);
-    if (threads > 0) flt.set_threads(threads);
-    flt.set_kmer_path(kin);
-    flt.set_count_range((uint32_t)min_count, (uint32_t)max_count);
-    flt.set_min_solid(min_solid);
-    flt.set_trim(trim);
-    flt.set_max_memory((double)mem);
-    flt.set_device(device);
-    if (std::string e = flt.filter(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        FilterComputer flt(in, out, k);
+        if (threads > 0) flt.set_threads(threads);
+        flt.set_kmer_path(kin);
+        flt.set_count_range((uint32_t)min_count, (uint32_t)max_count);
+        flt.set_min_solid(min_solid);
+        flt.set_trim(trim);
+        flt.set_max_memory((double)mem);
+        flt.set_device(device);
+        return flt.filter();
+    });
 }
 
 const char *HELP_CORRECT =
@@ -500,13 +555,14 @@ const char *HELP_CORRECT =
     "                               kept across the passes of an out-of-core count)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_correct(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},       {'o', "output", true},          {'k', "k-size", true},
                                      {'a', "alt-input", true},   {0, "min-count", true},         {0, "max-count", true},
                                      {0, "min-support", true},   {0, "max-corrections", true},   {0, "stats", true},
-                                     {'m', "memory", true},      {'t', "threads", true},         {0, "device", true}};
+                                     {'m', "memory", true},      {'t', "threads", true},         {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_CORRECT);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -521,6 +577,7 @@ int cmd_correct(int argc, char **argv, int from) {
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
     const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
     for (const std::string &p : {in, kin}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
@@ -528,20 +585,18 @@ int cmd_correct(int argc, char **argv, int from) {
             return 101;
         }
     }
-    CorrectComputer cor(in, out, k);
-    if (threads > 0) cor.set_threads(threads);
-    cor.set_kmer_path(kin);
-    cor.set_count_range((uint32_t)min_count, (uint32_t)max_count);
-    cor.set_min_support((uint32_t)min_support);
-    cor.set_max_corrections((uint32_t)max_corrections);
-    if (f.count("stats")) cor.set_stats_path(f.at("stats"));
-    cor.set_max_memory((double)mem);
-    cor.set_device(device);
-    if (std::string e = cor.correct(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        CorrectComputer cor(in, out, k);
+        if (threads > 0) cor.set_threads(threads);
+        cor.set_kmer_path(kin);
+        cor.set_count_range((uint32_t)min_count, (uint32_t)max_count);
+        cor.set_min_support((uint32_t)min_support);
+        cor.set_max_corrections((uint32_t)max_corrections);
+        if (f.count("stats")) cor.set_stats_path(f.at("stats"));
+        cor.set_max_memory((double)mem);
+        cor.set_device(device);
+        return cor.correct();
+    });
 }
 
 const char *HELP_COMPARE =
@@ -563,12 +618,13 @@ const char *HELP_COMPARE =
     "                               hold every distinct k-mer, the inputs are counted in several passes)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_compare(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},  {'a', "alt-input", true}, {'o', "output", true},
                                      {'k', "k-size", true}, {0, "max-a", true},       {0, "max-b", true},
-                                     {'m', "memory", true}, {'t', "threads", true},   {0, "device", true}};
+                                     {'m', "memory", true}, {'t', "threads", true},   {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_COMPARE);
     const std::string in = required_str(f, "input"), alt = required_str(f, "alt-input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -581,6 +637,7 @@ int cmd_compare(int argc, char **argv, int from) {
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
     if (int rc = make_out_dir(out)) return rc;
     for (const std::string &p : {in, alt}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
@@ -588,16 +645,14 @@ int cmd_compare(int argc, char **argv, int from) {
             return 101;
         }
     }
-    CompareComputer cmp(in, alt, out, k);
-    cmp.set_max_counts((uint32_t)max_a, (uint32_t)max_b);
-    if (threads > 0) cmp.set_threads(threads);
-    cmp.set_max_memory((double)mem);
-    cmp.set_device(device);
-    if (std::string e = cmp.compare(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        CompareComputer cmp(in, alt, out, k);
+        cmp.set_max_counts((uint32_t)max_a, (uint32_t)max_b);
+        if (threads > 0) cmp.set_threads(threads);
+        cmp.set_max_memory((double)mem);
+        cmp.set_device(device);
+        return cmp.compare();
+    });
 }
 
 const char *HELP_PROFILE =
@@ -622,12 +677,13 @@ const char *HELP_PROFILE =
     "                               kept across the passes of an out-of-core count)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_profile(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},  {'k', "k-size", true},
                                      {'a', "alt-input", true}, {0, "positions", false}, {'m', "memory", true},
-                                     {'t', "threads", true},   {0, "device", true}};
+                                     {'t', "threads", true},   {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_PROFILE);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 1, 31, true, 0);
@@ -635,6 +691,7 @@ int cmd_profile(int argc, char **argv, int from) {
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
     const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
     for (const std::string &p : {in, kin}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
@@ -643,17 +700,15 @@ int cmd_profile(int argc, char **argv, int from) {
         }
     }
     if (int rc = make_out_dir(out)) return rc;
-    ProfileComputer prof(in, out, k);
-    if (threads > 0) prof.set_threads(threads);
-    prof.set_kmer_path(kin);
-    prof.set_positions(f.count("positions") != 0);
-    prof.set_max_memory((double)mem);
-    prof.set_device(device);
-    if (std::string e = prof.profile(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        ProfileComputer prof(in, out, k);
+        if (threads > 0) prof.set_threads(threads);
+        prof.set_kmer_path(kin);
+        prof.set_positions(f.count("positions") != 0);
+        prof.set_max_memory((double)mem);
+        prof.set_device(device);
+        return prof.profile();
+    });
 }
 
 const char *HELP_SKETCH =
@@ -725,6 +780,61 @@ int cmd_sketch(int argc, char **argv, int from) {
     return 0;
 }
 
+const char *HELP_CARD =
+    "Estimate the number of distinct k-mers (HyperLogLog), sizes tables\n\n"
+    "One walk over the input: every canonical k-mer (windows over a non-ACGT base are none) is hashed, hash = splitmix64\n"
+    "finaliser of (k-mer xor --seed); its top --precision bits pick one of 2^precision registers, which keeps the largest\n"
+    "rank (1 + leading zeros of the other bits) it has seen.  Writes {output}/card.stats, one \"name<TAB>value\" line each:\n"
+    "sequences, bases, kmers, precision, registers, zero_registers, distinct_estimate (Ertl's improved estimator, rounded),\n"
+    "rel_std_error (1.04 / sqrt(registers), six decimals) and slots_wanted (the table --estimate-size would ask for: 1.9 slots\n"
+    "for the estimate plus five standard errors, never more than the input's size allows), and {output}/card.registers: the\n"
+    "line \"precision<TAB>seed<TAB>k\", then one register per line - registers of the same three numbers merge by taking the\n"
+    "larger of every pair.  With --alt-input the second input's rows follow with an alt_ prefix, then union_estimate (from\n"
+    "the merged registers), intersection_estimate (the two estimates minus the union's, at least 0) and jaccard_estimate (six\n"
+    "decimals, 0 when the union is 0); its registers go to {output}/card.alt.registers.\n\n"
+    "Usage: kmertools card [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size (1..31)\n"
+    "  -p, --precision <P>          2^P registers (4..16) [default: 14]\n"
+    "      --seed <SEED>            Hash seed [default: 0]\n"
+    "  -a, --alt-input <ALT_INPUT>  Second input: its estimate, and the union, intersection and Jaccard estimates\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    "  -h, --help                   Print help\n";
+
+int cmd_card(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true}, {'o', "output", true},    {'k', "k-size", true},  {'p', "precision", true},
+                                     {0, "seed", true},    {'a', "alt-input", true}, {'t', "threads", true}, {0, "device", true}};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_CARD);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    // everything is checked before any device work and before the output directory is made
+    const int k = (int)ranged(f, "k-size", 1, 31, true, 0);
+    const int p = (int)ranged(f, "precision", KT_CARD_MIN_P, KT_CARD_MAX_P, false, 14);
+    const uint64_t seed = ranged(f, "seed", 0, UINT64_MAX, false, 0);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const std::string alt = f.count("alt-input") ? f.at("alt-input") : "";
+    for (const std::string &path : f.count("alt-input") ? std::vector<std::string>{in, alt} : std::vector<std::string>{in}) {
+        if (format_from_path(path) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", path.c_str());
+            return 101;
+        }
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    CardComputer card(in, out, k, p);
+    card.set_seed(seed);
+    card.set_alt_path(alt);
+    if (threads > 0) card.set_threads(threads);
+    card.set_device(device);
+    if (std::string e = card.card(); !e.empty()) {
+        fprintf(stderr, "Error: %s\n", e.c_str());
+        return 101;
+    }
+    return 0;
+}
+
 const char *HELP_SETOP =
     "Intersect, subtract, union or xor the k-mer sets of two inputs\n\n"
     "Counts the canonical k-mers of both inputs.  A k-mer is in the input when min-a <= its count there <= max-a, in the alt\n"
@@ -753,6 +863,7 @@ const char *HELP_SETOP =
     "                               fit, the inputs are counted in several passes; the text is written in slabs)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 // the index of flag `name`'s value among `values` (clap's possible values)
@@ -775,7 +886,7 @@ int cmd_setop(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},  {'a', "alt-input", true}, {'o', "output", true}, {'k', "k-size", true},
                                      {0, "op", true},       {0, "count", true},       {0, "min-a", true},    {0, "max-a", true},
                                      {0, "min-b", true},    {0, "max-b", true},       {0, "acgt", false},    {'m', "memory", true},
-                                     {'t', "threads", true}, {0, "device", true}};
+                                     {'t', "threads", true}, {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_SETOP);
     const std::string in = required_str(f, "input"), alt = required_str(f, "alt-input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -796,6 +907,7 @@ int cmd_setop(int argc, char **argv, int from) {
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
     for (const std::string &p : {in, alt}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
@@ -803,18 +915,16 @@ int cmd_setop(int argc, char **argv, int from) {
         }
     }
     if (int rc = make_out_dir(out)) return rc;
-    SetopComputer so(in, alt, out, k);
-    so.set_op(op, rule);
-    so.set_ranges((uint32_t)lo[0], (uint32_t)hi[0], (uint32_t)lo[1], (uint32_t)hi[1]);
-    so.set_acgt_output(f.count("acgt") != 0);
-    if (threads > 0) so.set_threads(threads);
-    so.set_max_memory((double)mem);
-    so.set_device(device);
-    if (std::string e = so.setop(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        SetopComputer so(in, alt, out, k);
+        so.set_op(op, rule);
+        so.set_ranges((uint32_t)lo[0], (uint32_t)hi[0], (uint32_t)lo[1], (uint32_t)hi[1]);
+        so.set_acgt_output(f.count("acgt") != 0);
+        if (threads > 0) so.set_threads(threads);
+        so.set_max_memory((double)mem);
+        so.set_device(device);
+        return so.setop();
+    });
 }
 
 const char *HELP_GRAPH =
@@ -840,12 +950,13 @@ const char *HELP_GRAPH =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (the table lives in HBM; the text is written in slabs)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_graph(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
                                      {0, "max-count", true},   {0, "acgt", false},         {0, "stats-only", false}, {'m', "memory", true},
-                                     {'t', "threads", true},   {0, "device", true}};
+                                     {'t', "threads", true},   {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_GRAPH);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -857,23 +968,22 @@ int cmd_graph(int argc, char **argv, int from) {
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
     if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
-    GraphComputer gc(in, out, k);
-    gc.set_range((uint32_t)lo, (uint32_t)hi);
-    gc.set_acgt_output(f.count("acgt") != 0);
-    gc.set_stats_only(f.count("stats-only") != 0);
-    if (threads > 0) gc.set_threads(threads);
-    gc.set_max_memory((double)mem);
-    gc.set_device(device);
-    if (std::string e = gc.graph(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        GraphComputer gc(in, out, k);
+        gc.set_range((uint32_t)lo, (uint32_t)hi);
+        gc.set_acgt_output(f.count("acgt") != 0);
+        gc.set_stats_only(f.count("stats-only") != 0);
+        if (threads > 0) gc.set_threads(threads);
+        gc.set_max_memory((double)mem);
+        gc.set_device(device);
+        return gc.graph();
+    });
 }
 
 const char *HELP_UNITIGS =
@@ -927,6 +1037,7 @@ const char *HELP_UNITIGS =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_unitigs(int argc, char **argv, int from) {
@@ -934,7 +1045,7 @@ int cmd_unitigs(int argc, char **argv, int from) {
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
                                      {0, "device", true},      {0, "gfa", false},          {0, "links", false},
                                      {0, "clip-tips", false},  {0, "tip-nodes", true},     {0, "clip-rounds", true},
-                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}};
+                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -958,23 +1069,22 @@ int cmd_unitigs(int argc, char **argv, int from) {
         if (f.count(needs) && !clip && !(pop && std::string(needs) == "clip-rounds"))
             usage_error(std::string("the argument '--") + needs + "' requires '--clip-tips'");
     if (f.count("bubble-nodes") && !pop) usage_error("the argument '--bubble-nodes' requires '--pop-bubbles'");
+    const EstimateFlags est = estimate_flags(f);
     if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
-    UnitigComputer uc(in, out, k);
-    uc.set_links(gfa, links);
-    if (clip) uc.set_clip((uint32_t)tip_nodes, (uint32_t)clip_rounds, f.count("drop-isolated") != 0);
-    if (pop) uc.set_bubbles((uint32_t)bubble_nodes, (uint32_t)clip_rounds);
-    uc.set_range((uint32_t)lo, (uint32_t)hi);
-    uc.set_stats_only(f.count("stats-only") != 0);
-    uc.set_device(device);
-    if (std::string e = uc.unitigs(); !e.empty()) {
-        fprintf(stderr, "Error: %s\n", e.c_str());
-        return 101;
-    }
-    return 0;
+    return run_table_command(est, [&]() -> std::string {
+        UnitigComputer uc(in, out, k);
+        uc.set_links(gfa, links);
+        if (clip) uc.set_clip((uint32_t)tip_nodes, (uint32_t)clip_rounds, f.count("drop-isolated") != 0);
+        if (pop) uc.set_bubbles((uint32_t)bubble_nodes, (uint32_t)clip_rounds);
+        uc.set_range((uint32_t)lo, (uint32_t)hi);
+        uc.set_stats_only(f.count("stats-only") != 0);
+        uc.set_device(device);
+        return uc.unitigs();
+    });
 }
 
 // hidden: parse a file and print its records (CPU-only reader tests)
@@ -1106,6 +1216,7 @@ int main(int argc, char **argv) {
     if (cmd == "compare") return cmd_compare(argc, argv, 2);
     if (cmd == "profile") return cmd_profile(argc, argv, 2);
     if (cmd == "sketch") return cmd_sketch(argc, argv, 2);
+    if (cmd == "card") return cmd_card(argc, argv, 2);
     if (cmd == "setop") return cmd_setop(argc, argv, 2);
     if (cmd == "graph") return cmd_graph(argc, argv, 2);
     if (cmd == "unitigs") return cmd_unitigs(argc, argv, 2);

@@ -99,6 +99,40 @@ def mash_distance(shared, denom, k):
     return float(_lib.lib().kt_mash_distance(int(shared), int(denom), int(k)))
 
 
+def _card_p(registers):
+    """the precision of a register array: its length is 2^p"""
+    m = int(registers.size)
+    if m < 1 or m & (m - 1):
+        raise ValueError("a register array holds 2^p registers, not %d" % m)
+    return m.bit_length() - 1
+
+
+def card_estimate(registers):
+    """-> (estimate, zero_registers): the distinct k-mers behind HyperLogLog registers (u8[2^p], host), by Ertl's improved
+    raw estimator (kt_card_estimate)"""
+    registers = np.ascontiguousarray(registers, np.uint8)
+    est, zeros = C.c_double(), C.c_uint64()
+    check(_lib.lib().kt_card_estimate(_ptr(registers), _card_p(registers), C.byref(est), C.byref(zeros)))
+    return est.value, zeros.value
+
+
+def card_merge(into, other):
+    """into[j] = max(into[j], other[j]) in place (u8[2^p] host arrays of one k, p and seed): the registers of the union
+    (kt_card_merge); returns into"""
+    other = np.ascontiguousarray(other, np.uint8)
+    if not (isinstance(into, np.ndarray) and into.dtype == np.uint8 and into.flags.c_contiguous and into.flags.writeable):
+        raise ValueError("card_merge: into must be a writable contiguous uint8 array")
+    if into.size != other.size:
+        raise ValueError("card_merge: %d registers into %d" % (other.size, into.size))
+    check(_lib.lib().kt_card_merge(_ptr(into), _ptr(other), _card_p(into)))
+    return into
+
+
+def card_rel_error(p):
+    """the estimator's relative standard error, 1.04 / sqrt(2^p) (kt_card_rel_error)"""
+    return float(_lib.lib().kt_card_rel_error(int(p)))
+
+
 # the cells of Counter.graph's census, in order (kt_ctr_graph): degree_<dL>_<dR> = nodes with those two degrees
 GRAPH_CENSUS_NAMES = ("nodes", "occurrences", "degree_sum", "end_sides", "isolated", "tips", "branching") + tuple(
     "degree_%d_%d" % (dl, dr) for dl in range(5) for dr in range(5))
@@ -424,6 +458,23 @@ class Context:
         denom = np.zeros_like(shared)
         self.sketch_pairs(a_hashes, a_sizes, len(a_sizes), b_hashes, b_sizes, len(b_sizes), s, shared, denom, KT_MEM_HOST)
         return shared, denom
+
+    # -- card: HyperLogLog registers of the distinct canonical k-mers ----------------------------
+    def card_add(self, bases, offsets, n_reads, k, registers, p=14, seed=0, n_kmers=None, mem=KT_MEM_DEVICE):
+        """registers (u8, 2^p, zeroed once by the caller) are raised by the k-mers of the batch: register
+        mix64(canonical k-mer ^ seed) >> (64 - p) to 1 + the leading zeros of the hash's low 64 - p bits; n_kmers (one u64,
+        may be None) += the windows (kt_card_add_reads)"""
+        check(_lib.lib().kt_card_add_reads(self._h, _ptr(bases), _ptr(offsets), int(n_reads), int(k), int(p), int(seed),
+                                           _ptr(registers), _ptr(n_kmers), mem))
+
+    def card_host(self, bases, offsets, k, p=14, seed=0):
+        """-> (registers u8[2^p], n_kmers) of a host batch"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        registers, n_kmers = np.zeros(1 << int(p), np.uint8), np.zeros(1, np.uint64)
+        self.card_add(bases if bases.size else np.zeros(1, np.uint8), offsets, n, k, registers, p, seed, n_kmers, KT_MEM_HOST)
+        return registers, int(n_kmers[0])
 
     def synth_reads(self, seed, n_reads, read_len, bases_dev, offsets_dev=None, noise=False, genome_len=0,
                     first_read=0):
