@@ -26,6 +26,7 @@
 // status - a rank that cannot take part (a batch larger than agreed, a full pending table, a failed copy) still enters
 // it, and then either all ranks move data or ALL return an error; nobody is left waiting for a peer that went home.
 #include <dlfcn.h>
+#include <limits.h>
 #include <rccl/rccl.h>
 #include <stdlib.h>
 #include <string.h>
@@ -450,10 +451,39 @@ struct kt_sharded {
     uint64_t exchanged_bytes = 0;  // sent to other ranks so far (statistics; a forced single rank: what would have left)
     uint64_t add_calls = 0;        // kt_sharded_add_reads calls so far (tests: KT_SHARD_FAIL_LOCAL)
     std::vector<uint64_t> last_records, last_kmers;  // what the last batch's route pass put into every owner's region
+    std::vector<void *> owned;  // the device allocations behind the pointers above: six large buffers, one for the small arrays
     uint64_t *region(uint64_t *buf, int o) const { return buf + (uint64_t)o * region_words; }
 };
 
 namespace {
+
+constexpr uint64_t FIN_WORDS = HDR_U64 + FIN_CAP + FIN_CAP / 2;  // u64 words of a finalize message: header, keys, counts
+
+// The environment's knobs, each read by the one function that uses it, when it uses it (tests set them before they make
+// a counter, or between two calls).
+struct Knobs {
+    static long long number(const char *name, long long unset) {
+        const char *e = getenv(name);
+        return e ? atoll(e) : unset;
+    }
+    static long long positive(const char *name, long long otherwise, long long most = LLONG_MAX) {
+        const long long v = number(name, 0);
+        return v <= 0 ? otherwise : v < most ? v : most;
+    }
+    static int slices() { return (int)positive("KT_SHARD_SLICES", 4, 64); }  // creation: the pieces the regions leave in
+    // creation; tests: the routed path with a single rank too, into n owners' regions - and regions of that many blocks
+    static int force() { return (int)positive("KT_SHARD_FORCE", 0, MAX_RANKS); }
+    static uint64_t room_blocks() { return (uint64_t)positive("KT_SHARD_ROOM_BLOCKS", 0); }
+    // kt_sharded_connect_rccl: the CUs level 1 leaves to the exchange's kernels; per call: workgroups of the route pass per CU
+    static uint32_t comm_cus() { return (uint32_t)number("KT_SHARD_COMM_CUS", 16); }
+    static uint32_t route_grid() { return (uint32_t)positive("KT_ROUTE_GRID", 16, INT_MAX); }
+    // per call; tests: KT_SHARD_FAIL_LOCAL=<rank>:<call> - that rank's call number <call> (0-based, per counter) fails locally
+    static bool fail_local(int rank, uint64_t call) {
+        const char *inj = getenv("KT_SHARD_FAIL_LOCAL");
+        int r = -1, c = -1;
+        return inj && sscanf(inj, "%d:%d", &r, &c) == 2 && r == rank && (uint64_t)c == call;
+    }
+};
 
 // One piece per peer each way: piece p of the send list goes to rank p, piece p of the receive list comes from rank p
 // (this rank's own entries are ignored: what a rank keeps for itself it reads where it lies).  Pieces may differ in
@@ -553,43 +583,45 @@ uint64_t region_room(uint64_t max_batch_bases, uint32_t w, int n_owners) {
 }
 
 int sharded_alloc(kt_sharded *s) {
-    kt_ctx *ctx = s->ctx;
-    if (int rc = ctx->use()) return rc;
-    const uint64_t fin_u64 = HDR_U64 + FIN_CAP + FIN_CAP / 2;
+    if (int rc = s->ctx->use()) return rc;
     // the pending table: DISTINCT k-mers that overflow their regions (a batch may be one k-mer a billion times over - one
     // entry); a batch whose overflow has more distinct k-mers than this is not skewed, it is larger than agreed
     uint64_t pend_slots = s->max_batch_bases / 64;
     if (pend_slots < (1u << 20)) pend_slots = 1u << 20;
-    if (int rc = kt_ctr_create(ctx, s->k, pend_slots, &s->pend)) return rc;
+    if (int rc = kt_ctr_create(s->ctx, s->k, pend_slots, &s->pend)) return rc;
     if (int rc = kt_ctr_capacity(s->pend, &s->pend_cap)) return rc;
     s->room = region_room(s->max_batch_bases, s->w, s->n_owners);
-    if (const char *e = getenv("KT_SHARD_ROOM_BLOCKS"))  // tests: regions of that many blocks (a flood that overflows them)
-        if (atoll(e) > 0) s->room = (uint64_t)atoll(e) * ktsk::BLOCK_RECS;
+    if (const uint64_t blocks = Knobs::room_blocks()) s->room = blocks * ktsk::BLOCK_RECS;
     if (s->room >= 0xFFF00000ull)  // (the route pass keeps a record's place in its owner's stream in 32 bits)
         return kt::fail(KT_ERR_ARG, "kt_sharded_create: max_batch_bases too large for the exchange regions");
     s->region_words = s->room / ktsk::BLOCK_RECS * ktsk::BLOCK_WORDS;
-    hipError_t e = hipMalloc((void **)&s->send, s->region_words * 8 * (size_t)s->n_owners);
-    if (e == hipSuccess && s->n_ranks > 1) e = hipMalloc((void **)&s->recv, s->region_words * 8 * (size_t)s->n_ranks);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->cursors, 2 * ktsk::MAX_OWNERS * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->go_send, (size_t)s->n_ranks * GO_WORDS * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->go_recv, (size_t)s->n_ranks * GO_WORDS * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->go_cannot, GO_WORDS * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->fin_send, fin_u64 * 8 * s->n_ranks);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->fin_recv, fin_u64 * 8 * s->n_ranks);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->pend_keys, s->pend_cap * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->pend_counts, s->pend_cap * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->fin_left, 256);
+    // the large buffers (GBs at cfg4) are allocations of their own - one request for all could fail where six succeed -
+    // and the small arrays are parts of one
+    const uint64_t n = (uint64_t)s->n_ranks;
+    auto small_at = [&](uint8_t *at) {
+        return ktl::carve_parts<256>(at, &s->cursors, 2 * ktsk::MAX_OWNERS, &s->go_send, n * GO_WORDS, &s->go_recv, n * GO_WORDS,
+                                     &s->go_cannot, GO_WORDS, &s->fin_left, 1);
+    };
+    uint8_t *small = nullptr;
+    const struct { void **p; size_t bytes; } bufs[] = {
+        {(void **)&s->send, s->region_words * 8 * (size_t)s->n_owners},
+        {(void **)&s->recv, s->n_ranks > 1 ? s->region_words * 8 * (size_t)s->n_ranks : 0},
+        {(void **)&s->fin_send, FIN_WORDS * 8 * n},       {(void **)&s->fin_recv, FIN_WORDS * 8 * n},
+        {(void **)&s->pend_keys, s->pend_cap * 8},        {(void **)&s->pend_counts, s->pend_cap * 4},
+        {(void **)&small, small_at(nullptr)}};
+    hipError_t e = hipSuccess;
+    for (const auto &b : bufs)
+        if (e == hipSuccess && b.bytes && (e = hipMalloc(b.p, b.bytes)) == hipSuccess) s->owned.push_back(*b.p);
     if (e == hipSuccess) {
+        small_at(small);
         uint64_t wd[GO_WORDS] = {};
         wd[0] = 1;  // status: cannot go on
         e = hipMemcpy(s->go_cannot, wd, sizeof wd, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return kt::fail(KT_ERR_NOMEM, std::string("sharded counter: hipMalloc: ") + hipGetErrorString(e));
-    {   // the exchange should start the moment its piece is ready, whatever the main stream is running
-        int lo = 0, hi = 0;
-        KT_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        KT_HIP(hipStreamCreateWithPriority(&s->comm_stream, hipStreamNonBlocking, hi));
-    }
+    int lo = 0, hi = 0;  // the exchange should start the moment its piece is ready, whatever the main stream is running
+    KT_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    KT_HIP(hipStreamCreateWithPriority(&s->comm_stream, hipStreamNonBlocking, hi));
     KT_HIP(hipEventCreateWithFlags(&s->ev_main, hipEventDisableTiming));
     s->ev_recv.resize((size_t)s->n_slices);
     for (auto &ev : s->ev_recv) KT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -613,13 +645,10 @@ int sharded_new(kt_ctx *ctx, int k, uint64_t capacity_slots, uint64_t max_batch_
     s->n_ranks = n_ranks;
     s->rank = rank;
     s->max_batch_bases = max_batch_bases;
-    const char *env = getenv("KT_SHARD_SLICES");
-    s->n_slices = env && atoi(env) > 0 ? atoi(env) : 4;
-    if (s->n_slices > 64) s->n_slices = 64;
-    const char *force = getenv("KT_SHARD_FORCE");  // tests: the routed path with a single rank too, into n owners' regions
-    const int forced = force ? atoi(force) : 0;
+    s->n_slices = Knobs::slices();
+    const int forced = Knobs::force();
     s->routed = n_ranks > 1 || forced > 0;
-    s->n_owners = n_ranks > 1 ? n_ranks : forced > 1 ? (forced > MAX_RANKS ? MAX_RANKS : forced) : 1;
+    s->n_owners = n_ranks > 1 ? n_ranks : forced > 1 ? forced : 1;
     int rc = kt_ctr_create(ctx, k, capacity_slots, &s->table);
     if (rc == KT_OK) {
         s->table->n_owners = (uint32_t)n_ranks;  // (kt_cov_batch_part: the k-mers of the other ranks are not absent, they are elsewhere)
@@ -632,6 +661,271 @@ int sharded_new(kt_ctx *ctx, int k, uint64_t capacity_slots, uint64_t max_batch_
     }
     *out = s;
     return KT_OK;
+}
+
+// ---- one batch ------------------------------------------------------------------------------------------------------
+using Source = ktsk::RecRun;  // a region of records and how many of them it holds
+struct Blocks { uint64_t lo, hi; };
+// the blocks of a region of n_rec records that piece i of P holds; the most blocks any one piece of it has
+Blocks piece_of(uint64_t n_rec, int i, int P) {
+    const uint64_t nb = (n_rec + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS;
+    return Blocks{nb * (uint64_t)i / (uint64_t)P, nb * (uint64_t)(i + 1) / (uint64_t)P};
+}
+uint64_t largest_piece(uint64_t n_rec, int P) {  // (the pieces have floor or ceil of nb / P blocks, and sum to nb)
+    return ((n_rec + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS + (uint64_t)P - 1) / (uint64_t)P;
+}
+// ... and the records in those blocks (the last block of a region may be part full)
+ktsk::RecRun run_of(const Source &src, Blocks b) {
+    if (b.hi <= b.lo) return ktsk::RecRun{src.blocks, 0};
+    const uint64_t n = b.hi * ktsk::BLOCK_RECS < src.n_rec ? (b.hi - b.lo) * ktsk::BLOCK_RECS : src.n_rec - b.lo * ktsk::BLOCK_RECS;
+    return ktsk::RecRun{src.blocks + b.lo * ktsk::BLOCK_WORDS, n};
+}
+
+// One call of kt_sharded_add_reads; its methods are the stages, in the order the entry point lists them.  What this rank
+// finds wrong - its arguments, a pending table that filled up in an earlier batch, a failed copy - is not returned at
+// once: a rank that left now would leave its peers waiting in the exchange.  So the local stages, check and route, return
+// nothing: their steps run through step(), which skips them once the batch is refused, and refuse() keeps the first
+// status.  agree() is the first stage with a status: all ranks move data or none does.
+struct Batch {
+    kt_sharded *const s;
+    kt_ctx *const ctx;
+    const int mem, P, N, V, me;
+    ktl::Call call;
+    int code = KT_OK;  // the local status: what this rank returns once every rank knows of it
+    std::string error;
+    uint64_t total = 0;  // bases (0 once refused)
+    SegArgs a{};
+    std::vector<uint64_t> fill, kmers;        // [V] records in every owner's region (at most its room), their k-mers
+    std::vector<uint64_t> from_rec, from_km;  // [N] what every peer will send
+    uint64_t max_piece = 0;                   // the most records any rank sends any other
+    std::vector<Source> src;                  // [0] this rank's own region, then what the others sent (forced: its other regions)
+    int eligible = 0;                         // the bulk path takes the batch
+    std::vector<ktsk::RecRun> late;           // otherwise: every run, for the probing path behind the last piece
+
+    Batch(kt_sharded *s_, int mem_)
+        : s(s_), ctx(s_->ctx), mem(mem_), P(s_->n_slices), N(s_->n_ranks), V(s_->n_owners), me(s_->rank),
+          call(s_->ctx, mem_, "kt_sharded_add_reads"), fill((size_t)V, 0), kmers((size_t)V, 0), from_rec((size_t)N, 0), from_km((size_t)N, 0) {}
+
+    void refuse(int rc, const std::string &text) {
+        if (code == KT_OK) code = rc, error = text;
+        total = 0;
+    }
+    template <class F>
+    void step(F f) {
+        if (code != KT_OK) return;
+        if (int rc = f()) refuse(rc, kt_last_error());
+    }
+    int status() const { return code == KT_OK ? KT_OK : kt::fail(code, error); }
+
+    // ---- check: the arguments, the batch on the device, its segments, the pending table ready
+    void check(const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads) {
+        step([&] { return arguments(bases, offsets, n_reads); });
+        if (Knobs::fail_local(me, s->add_calls++))
+            step([] { return kt::fail(KT_ERR_FULL, "kt_sharded_add_reads: injected local failure (KT_SHARD_FAIL_LOCAL)"); });
+        step([&] {
+            if (!total) return (int)KT_OK;
+            if (int rc = call.stage()) return rc;
+            if (int rc = ktl::make_seg_args(ctx, call.bases, call.offsets, n_reads, total, s->k, &a)) return rc;
+            return ktl::table_ready(s->pend);  // (a deferred clear happens now; a full table is reported)
+        });
+    }
+    int arguments(const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads) {
+        if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) return call.fail("bad mem flag");
+        if (!n_reads) return KT_OK;
+        if (!offsets) return call.fail("null offsets");
+        if (int rc = call.batch(bases, offsets, n_reads, nullptr)) return rc;
+        total = call.total;
+        if (total > s->max_batch_bases) return call.fail("batch larger than max_batch_bases (split it)");
+        return total && !bases ? call.fail("null bases") : KT_OK;
+    }
+
+    // ---- route: the route pass over this rank's reads, one region of records per owner; the regions' fills come back
+    void route() {
+        std::vector<unsigned long long> h_cur(2 * ktsk::MAX_OWNERS, 0ull);
+        step([&] { return total ? route_pass(h_cur.data()) : (int)KT_OK; });
+        s->last_records.assign(h_cur.begin(), h_cur.begin() + V);  // (statistics: kt_sharded_route_stats)
+        s->last_kmers = kmers;
+    }
+    int route_pass(unsigned long long *h_cur) {
+        s->pend->empty = false;
+        s->pend_touched = true;
+        const PendRef pend{(Slot *)s->pend->slots, ktl::geom_of(s->pend), s->pend->flags, s->pend->distinct};
+        const RouteArgs ra{a, 0, a.n_seg, s->m, s->w, (uint32_t)V, s->send, s->region_words, s->room, s->cursors, s->cursors + ktsk::MAX_OWNERS, pend};
+        auto checked = [](hipError_t e) {
+            return e == hipSuccess ? (int)KT_OK : kt::fail(KT_ERR_HIP, std::string("kt_sharded_add_reads: the route pass: ") + hipGetErrorString(e));
+        };
+        const size_t bytes = 2 * ktsk::MAX_OWNERS * 8;
+        if (int rc = checked(hipMemsetAsync(s->cursors, 0, bytes, ctx->stream))) return rc;
+        if (int rc = ktl::launch(route_kernel, dim3(ktl::grid_for(ctx, a.n_seg, Knobs::route_grid())), dim3(BLOCK), 0, ctx->stream, ra))
+            return rc;
+        if (int rc = checked(hipMemcpyAsync(h_cur, s->cursors, bytes, hipMemcpyDeviceToHost, ctx->stream))) return rc;
+        if (int rc = checked(hipStreamSynchronize(ctx->stream))) return rc;
+        for (size_t o = 0; o < (size_t)V; o++) {
+            fill[o] = h_cur[o] < s->room ? h_cur[o] : s->room;
+            kmers[o] = h_cur[ktsk::MAX_OWNERS + o];
+        }
+        return KT_OK;
+    }
+
+    // ---- agree (ranks > 1): can everybody go on, and how much will each send each?  go word p -> rank p: [0] status
+    // (0 = fine), [1] records for rank p, [2] their k-mers at most, [3] the room of a region here (all ranks must have made
+    // their counters alike), [4] the most records this rank sends any peer (the host transport's equal blocks: every rank
+    // takes the largest).  The call's status: this rank's own, or that a peer cannot go on, or that the counters differ.
+    int agree() {
+        if (int rc = send_go()) return rc;  // (a transport that fails fails for everybody)
+        KT_HIP(hipStreamSynchronize(s->comm_stream));
+        std::vector<uint64_t> got((size_t)N * GO_WORDS, 0);
+        KT_HIP(hipMemcpy(got.data(), s->go_recv, got.size() * 8, hipMemcpyDeviceToHost));
+        bool peer = false, unlike = false;
+        for (int p = 0; p < N; p++) {
+            const uint64_t *wd = &got[(size_t)p * GO_WORDS];
+            if (p == me) continue;
+            peer |= wd[0] != 0;
+            if (wd[0] != 0) continue;
+            // (every rank compares every peer's room with its own: a mismatch is seen by both ends, in this same round)
+            unlike |= wd[3] != s->room || wd[1] > s->room;
+            from_rec[(size_t)p] = wd[1];
+            from_km[(size_t)p] = wd[2];
+            if (wd[4] > max_piece) max_piece = wd[4];
+        }
+        if (code != KT_OK) return status();
+        if (peer)
+            return kt::fail(KT_ERR_ARG, "kt_sharded_add_reads: another rank could not take part (its batch was refused or its set-up failed); nothing was counted");
+        if (unlike)
+            return kt::fail(KT_ERR_ARG, "kt_sharded_add_reads: the ranks' counters differ (max_batch_bases / k must be the same on every rank); nothing was counted");
+        return KT_OK;
+    }
+    int send_go() {
+        std::vector<uint64_t> h((size_t)N * GO_WORDS, 0);
+        for (int p = 0; p < N; p++)
+            if (p != me && fill[(size_t)p] > max_piece) max_piece = fill[(size_t)p];
+        for (int p = 0; p < N; p++) {
+            const uint64_t wd[GO_WORDS] = {code != KT_OK ? 1u : 0u, fill[(size_t)p], kmers[(size_t)p], s->room, max_piece};
+            memcpy(&h[(size_t)p * GO_WORDS], wd, sizeof wd);
+        }
+        // (a rank that cannot even put its words on the device still enters the exchange - leaving here would leave the peers
+        // waiting in it - and sends "cannot" from go_cannot: device words written at creation, which no copy of this call reaches)
+        bool words_ok = hipMemcpyAsync(s->go_send, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+        if (words_ok) words_ok = hipStreamSynchronize(ctx->stream) == hipSuccess;  // (h lives on this frame; the comm stream must see the words)
+        if (!words_ok) {
+            (void)hipGetLastError();
+            refuse(KT_ERR_HIP, "kt_sharded_add_reads: the status words could not be copied to the device");
+        }
+        std::vector<Piece> pc((size_t)N);
+        for (int p = 0; p < N; p++)
+            if (p != me)
+                pc[p] = Piece{words_ok ? s->go_send + (size_t)p * GO_WORDS : s->go_cannot, GO_WORDS * 8, s->go_recv + (size_t)p * GO_WORDS, GO_WORDS * 8};
+        return exchange_v(s, pc);
+    }
+
+    // ---- plan: what this rank will count - its own region (read where it lies) and what the peers send, or, a single rank
+    // made to take this path, all of its own regions - and the job for it
+    int plan() {
+        const bool peers = N > 1;  // (otherwise a single rank forced onto this path: every region is its own)
+        uint64_t all_km = kmers[(size_t)me], all_rec = fill[(size_t)me];
+        src.push_back(Source{s->region(s->send, me), fill[(size_t)me]});
+        for (int o = 0; o < V; o++) {
+            if (o == me) continue;
+            src.push_back(peers ? Source{s->region(s->recv, o), from_rec[(size_t)o]} : Source{s->region(s->send, o), fill[(size_t)o]});
+            all_km += peers ? from_km[(size_t)o] : kmers[(size_t)o];
+            all_rec += src.back().n_rec;
+        }
+        if (!all_rec) return KT_OK;
+        // The job is planned for the k-mers that will arrive (the ranks announced them): level 1 runs 0.8 ms faster into
+        // regions of that size than into the quarter more a job over reads gets by being planned for one k-mer per BASE.  But
+        // the k-mers of a genome's repeats do not fit fine regions that tight - a fifth of the buckets went through the exact
+        // pass, +2.8 ms per step on genome-sampled reads: once a job has had more than 2 % of its buckets redone the counter
+        // plans the quarter more from then on.
+        if (s->table->l2_buckets && s->table->l2_redone * 50u > s->table->l2_buckets) s->roomy = true;
+        return kt_bulk_begin(s->table, all_km + (s->roomy ? all_km / 4 : 0) + 1, &eligible);
+    }
+
+    // ---- move_and_count: source 0 whole - with peers, under the first pieces' flight - then every piece of the others as
+    // it is there: level 1 queued per piece, or the runs kept for the probing path
+    int move_and_count() {
+        const bool peers = N > 1;
+        if (peers) {
+            KT_HIP(hipEventRecord(s->ev_main, ctx->stream));
+            KT_HIP(hipStreamWaitEvent(s->comm_stream, s->ev_main, 0));  // (the route pass has long finished: the host read its cursors)
+        }
+        std::vector<ktsk::RecRun> runs;
+        if (src[0].n_rec) runs.push_back(src[0]);
+        if (int rc = count_runs(runs)) return rc;
+        // (the host transport's equal blocks: the largest piece any rank sends any other)
+        const size_t block_all = (size_t)largest_piece(max_piece, P) * ktsk::BLOCK_BYTES;
+        for (int i = 0; i < P; i++) {
+            if (peers)
+                if (int rc = exchange_piece(i, block_all)) return rc;
+            runs.clear();
+            for (size_t j = 1; j < src.size(); j++) {
+                const Blocks b = piece_of(src[j].n_rec, i, P);
+                const ktsk::RecRun r = run_of(src[j], b);
+                if (r.n_rec) runs.push_back(r);
+                if (!peers) s->exchanged_bytes += (b.hi - b.lo) * ktsk::BLOCK_BYTES;  // (what a rank of V would have sent)
+            }
+            if (int rc = count_runs(runs)) return rc;
+        }
+        return KT_OK;
+    }
+    // piece i of every peer's region leaves, piece i of what every peer sends arrives; the main stream waits for it
+    int exchange_piece(int i, size_t block_all) {
+        std::vector<Piece> pc((size_t)N);
+        for (int p = 0; p < N; p++) {
+            if (p == me) continue;
+            const Blocks sb = piece_of(fill[(size_t)p], i, P), rb = piece_of(from_rec[(size_t)p], i, P);
+            pc[p] = Piece{s->region(s->send, p) + sb.lo * ktsk::BLOCK_WORDS, (size_t)(sb.hi - sb.lo) * ktsk::BLOCK_BYTES,
+                          s->region(s->recv, p) + rb.lo * ktsk::BLOCK_WORDS, (size_t)(rb.hi - rb.lo) * ktsk::BLOCK_BYTES};
+        }
+        if (int rc = exchange_v(s, pc, block_all)) return rc;
+        KT_HIP(hipEventRecord(s->ev_recv[(size_t)i], s->comm_stream));
+        KT_HIP(hipStreamWaitEvent(ctx->stream, s->ev_recv[(size_t)i], 0));
+        return KT_OK;
+    }
+    int count_runs(const std::vector<ktsk::RecRun> &runs) {
+        if (!eligible) late.insert(late.end(), runs.begin(), runs.end());
+        return eligible && !runs.empty() ? kt_bulk_add_records(s->table, runs.data(), (uint32_t)runs.size(), 0) : (int)KT_OK;
+    }
+
+    // ---- finish: level 2 and the range builds - or the probing path, which counts everything behind the last piece
+    int finish() {
+        if (int rc = eligible ? kt_bulk_finish(s->table) : late.empty() ? (int)KT_OK : kt_ctr_count_records(s->table, late.data(), (uint32_t)late.size()))
+            return rc;
+        if (mem == KT_MEM_HOST) KT_HIP(hipStreamSynchronize(ctx->stream));
+        return KT_OK;
+    }
+};
+
+// ---- kt_sharded_finalize's steps ------------------------------------------------------------------------------------
+// the pending table's pairs, once: the rounds send them FIN_CAP per owner at a time.  A table that filled up is this
+// rank's failure - told to every rank in the round's headers, so that all of them return it after the exchange (a rank
+// that left here would leave the others waiting).
+int fin_pending(kt_sharded *s, uint64_t *n_pend, bool *overflowed) {
+    uint64_t n = 0;
+    const int rc = kt_ctr_size(s->pend, &n);
+    *overflowed = rc == KT_ERR_FULL;
+    *n_pend = 0;
+    if (rc != KT_OK && !*overflowed) return rc;
+    if (!*overflowed && n)
+        if (int rc2 = kt_ctr_export(s->pend, s->pend_keys, s->pend_counts, s->pend_cap, n_pend, KT_MEM_DEVICE)) return rc2;
+    kt::set_error("");
+    return KT_OK;
+}
+// the headers of the round's messages back: has any rank pairs left, has any failed
+int fin_headers(kt_sharded *s, uint64_t *hdr, bool *more, bool *failed) {
+    for (int p = 0; p < s->n_ranks; p++)
+        KT_HIP(hipMemcpyAsync(hdr + (size_t)p * HDR_U64, s->fin_recv + (uint64_t)p * FIN_WORDS, HDR_U64 * 8, hipMemcpyDeviceToHost, s->comm_stream));
+    KT_HIP(hipStreamSynchronize(s->comm_stream));
+    for (int p = 0; p < s->n_ranks; p++) {
+        *more |= hdr[(size_t)p * HDR_U64 + 1] != 0;
+        *failed |= hdr[(size_t)p * HDR_U64 + 2] != 0;
+    }
+    return KT_OK;
+}
+// message p's pairs (its header's count may exceed the message's room: the rest stayed at the sender) into the table
+int fin_deliver(kt_sharded *s, int p, uint64_t sent) {
+    const uint64_t *msg = s->fin_recv + (uint64_t)p * FIN_WORDS + HDR_U64;
+    const uint64_t n = sent < FIN_CAP ? sent : FIN_CAP;
+    return n ? kt_ctr_add_pairs(s->table, msg, reinterpret_cast<const uint32_t *>(msg + FIN_CAP), n, KT_MEM_DEVICE) : (int)KT_OK;
 }
 
 }  // namespace
@@ -666,14 +960,11 @@ int kt_sharded_connect_rccl(kt_sharded *s, const uint8_t *id128) {
     else r = s->rccl->GetUniqueId(&id);  // (a single rank made to take the routed path: tests)
     if (r == ncclSuccess) r = s->rccl->CommInitRank(&s->comm, s->n_ranks, id, s->rank);
     if (r != ncclSuccess) return kt::fail(KT_ERR_HIP, std::string("ncclCommInitRank: ") + s->rccl->GetErrorString(r));
-    if (s->n_ranks > 1) {
-        // The pieces travel (RCCL's send / receive kernels, comm stream) while level 1 counts the pieces before them - and a
-        // level-1 workgroup holds a whole CU's LDS for the length of its launch: on a chip that level 1 fills, the exchange's
-        // kernels would wait for a launch to end.  Level 1 leaves a few CUs free (KT_SHARD_COMM_CUS, default 16 of 256: +6 %
-        // of level 1's 11.5 ms, against an exchange that would otherwise not overlap at all).  NOT measured: no multi-GPU box.
-        const char *e = getenv("KT_SHARD_COMM_CUS");
-        s->table->l1_spare_cus = e ? (uint32_t)atoi(e) : 16u;
-    }
+    // The pieces travel (RCCL's send / receive kernels, comm stream) while level 1 counts the pieces before them - and a
+    // level-1 workgroup holds a whole CU's LDS for the length of its launch: on a chip that level 1 fills, the exchange's
+    // kernels would wait for a launch to end.  Level 1 leaves a few CUs free (KT_SHARD_COMM_CUS, default 16 of 256: +6 %
+    // of level 1's 11.5 ms, against an exchange that would otherwise not overlap at all).  NOT measured: no multi-GPU box.
+    if (s->n_ranks > 1) s->table->l1_spare_cus = Knobs::comm_cus();
     return KT_OK;
 }
 
@@ -702,10 +993,8 @@ int kt_sharded_create_host(kt_ctx *ctx, int k, uint64_t capacity_slots, uint64_t
     if (!fn) return kt::fail(KT_ERR_ARG, "kt_sharded_create_host: null all-to-all function");
     kt_sharded *s = nullptr;
     if (int rc = sharded_new(ctx, k, capacity_slots, max_batch_bases, n_ranks, rank, &s)) return rc;
-    s->fn = fn;
-    s->fn_user = user;
     *out = s;
-    return KT_OK;
+    return kt_sharded_connect_host(s, fn, user);
 }
 
 int kt_sharded_destroy(kt_sharded *s) {
@@ -719,17 +1008,7 @@ int kt_sharded_destroy(kt_sharded *s) {
     if (s->ev_main) (void)hipEventDestroy(s->ev_main);
     for (auto ev : s->ev_recv)
         if (ev) (void)hipEventDestroy(ev);
-    if (s->send) (void)hipFree(s->send);
-    if (s->recv) (void)hipFree(s->recv);
-    if (s->cursors) (void)hipFree(s->cursors);
-    if (s->go_send) (void)hipFree(s->go_send);
-    if (s->go_recv) (void)hipFree(s->go_recv);
-    if (s->go_cannot) (void)hipFree(s->go_cannot);
-    if (s->fin_send) (void)hipFree(s->fin_send);
-    if (s->fin_recv) (void)hipFree(s->fin_recv);
-    if (s->pend_keys) (void)hipFree(s->pend_keys);
-    if (s->pend_counts) (void)hipFree(s->pend_counts);
-    if (s->fin_left) (void)hipFree(s->fin_left);
+    for (void *p : s->owned) (void)hipFree(p);
     if (s->pend) kt_ctr_destroy(s->pend);
     if (s->h_send) (void)hipHostFree(s->h_send);
     if (s->h_recv) (void)hipHostFree(s->h_recv);
@@ -813,258 +1092,14 @@ int kt_sharded_owner_of(kt_sharded *s, uint64_t kmer, uint32_t *owner) {
 int kt_sharded_add_reads(kt_sharded *s, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int mem) {
     if (!s) return kt::fail(KT_ERR_ARG, "kt_sharded_add_reads: null");
     if (!s->routed) return kt_ctr_add_reads(s->table, bases, offsets, n_reads, mem);
-    kt_ctx *ctx = s->ctx;
-    if (int rc = ctx->use()) return rc;
-    ktl::Call call(ctx, mem, "kt_sharded_add_reads");
-    // What this rank finds wrong - with its arguments, or while it sets the batch up: a pending table that filled up in an
-    // earlier batch, a failed copy - is not returned at once: a rank that left now would leave its peers waiting in the
-    // exchange.  Every fallible local step comes first (the route pass among them); then the ranks tell each other in
-    // one small exchange whether they can go on, and either all of them move data or none does.
-    std::string my_error;
-    int my_code = KT_OK;
-    uint64_t total = 0;
-    auto local_fail = [&](int rc) {
-        if (my_code == KT_OK) {
-            my_code = rc;
-            my_error = kt_last_error();
-        }
-        total = 0;
-    };
-    auto arg_fail = [&](const char *what) {
-        if (my_code == KT_OK) {
-            my_code = KT_ERR_ARG;
-            my_error = what;
-        }
-        total = 0;
-    };
-    auto hip_fail = [&](const char *what, hipError_t e) {
-        kt::set_error(std::string("kt_sharded_add_reads: ") + what + ": " + hipGetErrorString(e));
-        local_fail(KT_ERR_HIP);
-    };
-    if (mem != KT_MEM_HOST && mem != KT_MEM_DEVICE) arg_fail("kt_sharded_add_reads: bad mem flag");
-    if (my_code == KT_OK && n_reads) {
-        if (!offsets) arg_fail("kt_sharded_add_reads: null offsets");
-        else if (int rc = call.batch(bases, offsets, n_reads, nullptr)) local_fail(rc);
-        else total = call.total;
-    }
-    if (my_code == KT_OK && total > s->max_batch_bases) arg_fail("kt_sharded_add_reads: batch larger than max_batch_bases (split it)");
-    if (my_code == KT_OK && total && !bases) arg_fail("kt_sharded_add_reads: null bases");
-    {
-        // tests: KT_SHARD_FAIL_LOCAL=<rank>:<call> - that rank's call number <call> (0-based, per counter) fails locally here
-        const char *inj = getenv("KT_SHARD_FAIL_LOCAL");
-        int r = -1, c = -1;
-        if (inj && sscanf(inj, "%d:%d", &r, &c) == 2 && r == s->rank && (uint64_t)c == s->add_calls) {
-            kt::set_error("kt_sharded_add_reads: injected local failure (KT_SHARD_FAIL_LOCAL)");
-            local_fail(KT_ERR_FULL);
-        }
-        s->add_calls++;
-    }
-    if (my_code == KT_OK && mem == KT_MEM_HOST && total) {
-        if (int rc = call.stage()) local_fail(rc);
-    }
-    const uint8_t *d_bases = call.bases;
-    const uint64_t *d_offsets = call.offsets;
-    SegArgs a{};
-    if (my_code == KT_OK && total) {
-        if (int rc = ktl::make_seg_args(ctx, d_bases, d_offsets, n_reads, total, s->k, &a)) local_fail(rc);
-    }
-    const int P = s->n_slices, N = s->n_ranks, V = s->n_owners, me = s->rank;
-    // ---- the route pass over this rank's reads: one region of records per owner
-    std::vector<unsigned long long> h_cur(2 * ktsk::MAX_OWNERS, 0ull);
-    if (my_code == KT_OK && total) {
-        if (int rc = ktl::table_ready(s->pend)) local_fail(rc);  // (a deferred clear happens now; a full table is reported)
-    }
-    if (my_code == KT_OK && total) {
-        s->pend->empty = false;
-        s->pend_touched = true;
-        RouteArgs ra{};
-        ra.a = a;
-        ra.seg_lo = 0;
-        ra.seg_hi = a.n_seg;
-        ra.m = s->m;
-        ra.w = s->w;
-        ra.n_owners = (uint32_t)V;
-        ra.regions = s->send;
-        ra.region_words = s->region_words;
-        ra.room = s->room;
-        ra.cursors = s->cursors;
-        ra.kmers = s->cursors + ktsk::MAX_OWNERS;
-        ra.pend = PendRef{(Slot *)s->pend->slots, ktl::geom_of(s->pend), s->pend->flags, s->pend->distinct};
-        hipError_t e = hipMemsetAsync(s->cursors, 0, 2 * ktsk::MAX_OWNERS * 8, ctx->stream);
-        if (e == hipSuccess) {
-            const char *ge = getenv("KT_ROUTE_GRID");  // (experiments: workgroups per CU)
-            const uint32_t per_cu = ge && atoi(ge) > 0 ? (uint32_t)atoi(ge) : 16u;
-            hipLaunchKernelGGL(route_kernel, dim3(ktl::grid_for(ctx, a.n_seg, per_cu)), dim3(BLOCK), 0, ctx->stream, ra);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cur.data(), s->cursors, 2 * ktsk::MAX_OWNERS * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) hip_fail("the route pass", e);
-    }
-    std::vector<uint64_t> fill((size_t)V, 0), kmers((size_t)V, 0);
-    if (my_code == KT_OK)
-        for (int o = 0; o < V; o++) {
-            fill[(size_t)o] = h_cur[(size_t)o] < s->room ? h_cur[(size_t)o] : s->room;
-            kmers[(size_t)o] = h_cur[ktsk::MAX_OWNERS + (size_t)o];
-        }
-    s->last_records.assign(h_cur.begin(), h_cur.begin() + V);  // (statistics: kt_sharded_route_stats)
-    s->last_kmers = kmers;
-    // ---- can everybody go on, and how much will each send each?  go word p -> rank p: [0] status (0 = fine), [1] records for
-    // rank p, [2] their k-mers at most, [3] the room of a region here (all ranks must have made their counters alike),
-    // [4] the most records this rank sends any peer (the host transport's equal blocks: every rank takes the largest)
-    std::vector<uint64_t> from_rec((size_t)N, 0), from_km((size_t)N, 0);
-    uint64_t max_piece = 0;
-    if (N > 1) {
-        std::vector<uint64_t> h((size_t)N * GO_WORDS, 0);
-        uint64_t my_max = 0;
-        for (int p = 0; p < N; p++)
-            if (p != me && fill[(size_t)p] > my_max) my_max = fill[(size_t)p];
-        for (int p = 0; p < N; p++) {
-            uint64_t *wd = &h[(size_t)p * GO_WORDS];
-            wd[0] = my_code != KT_OK ? 1u : 0u;
-            wd[1] = fill[(size_t)p];
-            wd[2] = kmers[(size_t)p];
-            wd[3] = s->room;
-            wd[4] = my_max;
-        }
-        // (a rank that cannot even put its words on the device still enters the exchange - leaving here would leave the peers
-        // waiting in it - and sends "cannot" from go_cannot: device words written at creation, which no copy of this call has
-        // to reach)
-        bool words_ok = hipMemcpyAsync(s->go_send, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-        if (words_ok) words_ok = hipStreamSynchronize(ctx->stream) == hipSuccess;  // (h lives on this frame; the comm stream must see the words)
-        if (!words_ok) {
-            (void)hipGetLastError();
-            kt::set_error("kt_sharded_add_reads: the status words could not be copied to the device");
-            local_fail(KT_ERR_HIP);
-        }
-        std::vector<Piece> pc((size_t)N);
-        for (int p = 0; p < N; p++)
-            if (p != me)
-                pc[p] = Piece{words_ok ? s->go_send + (size_t)p * GO_WORDS : s->go_cannot, GO_WORDS * 8, s->go_recv + (size_t)p * GO_WORDS, GO_WORDS * 8};
-        if (int rc = exchange_v(s, pc)) return rc;  // (a transport that fails fails for everybody)
-        KT_HIP(hipStreamSynchronize(s->comm_stream));
-        std::vector<uint64_t> got((size_t)N * GO_WORDS, 0);
-        KT_HIP(hipMemcpy(got.data(), s->go_recv, got.size() * 8, hipMemcpyDeviceToHost));
-        bool peer = false, unlike = false;
-        max_piece = my_max;
-        for (int p = 0; p < N; p++) {
-            if (p == me) continue;
-            const uint64_t *wd = &got[(size_t)p * GO_WORDS];
-            peer |= wd[0] != 0;
-            if (wd[0] != 0) continue;
-            // (every rank compares every peer's room with its own: a mismatch is seen by both ends, in this same round)
-            unlike |= wd[3] != s->room || wd[1] > s->room;
-            from_rec[(size_t)p] = wd[1];
-            from_km[(size_t)p] = wd[2];
-            if (wd[4] > max_piece) max_piece = wd[4];
-        }
-        if (my_code != KT_OK) return kt::fail(my_code, my_error);
-        if (peer)
-            return kt::fail(KT_ERR_ARG, "kt_sharded_add_reads: another rank could not take part (its batch was refused or its "
-                                        "set-up failed); nothing was counted");
-        if (unlike)
-            return kt::fail(KT_ERR_ARG, "kt_sharded_add_reads: the ranks' counters differ (max_batch_bases / k must be the same on "
-                                        "every rank); nothing was counted");
-    } else if (my_code != KT_OK) {
-        return kt::fail(my_code, my_error);
-    }
-    // ---- what this rank will count: its own region (read where it lies) and what the peers send - or, a single rank made
-    // to take this path, all of its own regions
-    uint64_t all_km = 0, all_rec = 0;
-    if (N > 1) {
-        all_km = kmers[(size_t)me];
-        all_rec = fill[(size_t)me];
-        for (int p = 0; p < N; p++)
-            if (p != me) {
-                all_km += from_km[(size_t)p];
-                all_rec += from_rec[(size_t)p];
-            }
-    } else {
-        for (int o = 0; o < V; o++) {
-            all_km += kmers[(size_t)o];
-            all_rec += fill[(size_t)o];
-        }
-    }
-    // blocks [lo, hi) of a region of n_rec records that piece i of P holds
-    auto piece_of = [&](uint64_t n_rec, int i, uint64_t *lo, uint64_t *hi) {
-        const uint64_t nb = (n_rec + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS;
-        *lo = nb * (uint64_t)i / (uint64_t)P;
-        *hi = nb * (uint64_t)(i + 1) / (uint64_t)P;
-    };
-    auto run_of = [&](const uint64_t *region, uint64_t n_rec, uint64_t lo, uint64_t hi) {
-        uint64_t n = hi * ktsk::BLOCK_RECS < n_rec ? (hi - lo) * ktsk::BLOCK_RECS : n_rec - lo * ktsk::BLOCK_RECS;
-        if (hi <= lo) n = 0;
-        return ktsk::RecRun{region + lo * ktsk::BLOCK_WORDS, n};
-    };
-    int eligible = 0;
-    if (all_rec) {
-        // The job is planned for the k-mers that will arrive (the ranks announced them): level 1 runs 0.8 ms faster into
-        // regions of that size than into the quarter more a job over reads gets by being planned for one k-mer per BASE.  But
-        // the k-mers of a genome's repeats do not fit fine regions that tight - a fifth of the buckets went through the exact
-        // pass, +2.8 ms per step on genome-sampled reads: once a job has had more than 2 % of its buckets redone the counter
-        // plans the quarter more from then on.
-        if (s->table->l2_buckets && s->table->l2_redone * 50u > s->table->l2_buckets) s->roomy = true;
-        if (int rc = kt_bulk_begin(s->table, all_km + (s->roomy ? all_km / 4 : 0) + 1, &eligible)) return rc;
-    }
-    std::vector<ktsk::RecRun> late;  // (the probing path counts everything behind the last piece)
-    auto count_runs = [&](const std::vector<ktsk::RecRun> &runs) -> int {
-        if (runs.empty()) return KT_OK;
-        if (eligible) return kt_bulk_add_records(s->table, runs.data(), (uint32_t)runs.size(), 0);
-        late.insert(late.end(), runs.begin(), runs.end());
-        return KT_OK;
-    };
-    if (N > 1) {
-        // this rank's own region at once, under the first pieces' flight
-        KT_HIP(hipEventRecord(s->ev_main, ctx->stream));
-        KT_HIP(hipStreamWaitEvent(s->comm_stream, s->ev_main, 0));  // (the route pass has long finished: the host read its cursors)
-        if (fill[(size_t)me]) {
-            std::vector<ktsk::RecRun> own{ktsk::RecRun{s->region(s->send, me), fill[(size_t)me]}};
-            if (int rc = count_runs(own)) return rc;
-        }
-        uint64_t mlo = 0, mhi = 0, piece_blocks = 0;
-        for (int i = 0; i < P; i++) {  // (the host transport's equal blocks: the largest piece any rank sends any other)
-            piece_of(max_piece, i, &mlo, &mhi);
-            if (mhi - mlo > piece_blocks) piece_blocks = mhi - mlo;
-        }
-        for (int i = 0; i < P; i++) {
-            std::vector<Piece> pc((size_t)N);
-            std::vector<ktsk::RecRun> runs;
-            for (int p = 0; p < N; p++) {
-                if (p == me) continue;
-                uint64_t slo, shi, rlo, rhi;
-                piece_of(fill[(size_t)p], i, &slo, &shi);
-                piece_of(from_rec[(size_t)p], i, &rlo, &rhi);
-                pc[p] = Piece{s->region(s->send, p) + slo * ktsk::BLOCK_WORDS, (size_t)(shi - slo) * ktsk::BLOCK_BYTES,
-                              s->region(s->recv, p) + rlo * ktsk::BLOCK_WORDS, (size_t)(rhi - rlo) * ktsk::BLOCK_BYTES};
-                const ktsk::RecRun r = run_of(s->region(s->recv, p), from_rec[(size_t)p], rlo, rhi);
-                if (r.n_rec) runs.push_back(r);
-            }
-            if (int rc = exchange_v(s, pc, (size_t)piece_blocks * ktsk::BLOCK_BYTES)) return rc;
-            KT_HIP(hipEventRecord(s->ev_recv[(size_t)i], s->comm_stream));
-            KT_HIP(hipStreamWaitEvent(ctx->stream, s->ev_recv[(size_t)i], 0));
-            if (int rc = count_runs(runs)) return rc;
-        }
-    } else {
-        // a single rank: the same launches over its own regions - region 0 whole, the others piece by piece
-        for (int i = -1; i < P; i++) {
-            std::vector<ktsk::RecRun> runs;
-            for (int o = (i < 0 ? 0 : 1); o < (i < 0 ? 1 : V); o++) {
-                uint64_t lo = 0, hi = (fill[(size_t)o] + ktsk::BLOCK_RECS - 1) / ktsk::BLOCK_RECS;
-                if (i >= 0) piece_of(fill[(size_t)o], i, &lo, &hi);
-                const ktsk::RecRun r = run_of(s->region(s->send, o), fill[(size_t)o], lo, hi);
-                if (r.n_rec) runs.push_back(r);
-                if (i >= 0) s->exchanged_bytes += (hi - lo) * ktsk::BLOCK_BYTES;  // (what a rank of V would have sent)
-            }
-            if (int rc = count_runs(runs)) return rc;
-        }
-    }
-    if (eligible) {
-        if (int rc = kt_bulk_finish(s->table)) return rc;
-    } else if (!late.empty()) {
-        if (int rc = kt_ctr_count_records(s->table, late.data(), (uint32_t)late.size())) return rc;
-    }
-    if (mem == KT_MEM_HOST) KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
+    if (int rc = s->ctx->use()) return rc;
+    Batch b(s, mem);
+    b.check(bases, offsets, n_reads);  // (the local stages: no status comes back from them, no rank leaves before agree)
+    b.route();
+    if (int rc = s->n_ranks > 1 ? b.agree() : b.status()) return rc;
+    if (int rc = b.plan()) return rc;
+    if (int rc = b.move_and_count()) return rc;
+    return b.finish();
 }
 
 int kt_sharded_finalize(kt_sharded *s) {
@@ -1072,72 +1107,38 @@ int kt_sharded_finalize(kt_sharded *s) {
     if (!s->routed) return KT_OK;
     kt_ctx *ctx = s->ctx;
     if (int rc = ctx->use()) return rc;
-    const uint64_t words = HDR_U64 + FIN_CAP + FIN_CAP / 2, all_words = words * (uint64_t)s->n_ranks;
-    std::vector<uint64_t> hdr(all_words ? (size_t)s->n_ranks * HDR_U64 : 0);
-    // the pending table's pairs, once: the rounds below send them FIN_CAP per owner at a time.  A table that filled up
-    // is this rank's failure - told to every rank in the round's headers, so that all of them return it after the
-    // exchange (a rank that left here would leave the others waiting).
+    std::vector<uint64_t> hdr((size_t)s->n_ranks * HDR_U64);
     uint64_t n_pend = 0;
     bool overflowed = false;
-    {
-        const int rc = kt_ctr_size(s->pend, &n_pend);
-        if (rc == KT_ERR_FULL) overflowed = true;
-        else if (rc != KT_OK) return rc;
-        if (!overflowed && n_pend) {
-            uint64_t got = 0;
-            if (int rc2 = kt_ctr_export(s->pend, s->pend_keys, s->pend_counts, s->pend_cap, &got, KT_MEM_DEVICE)) return rc2;
-            n_pend = got;
-        } else {
-            n_pend = 0;
-        }
-        kt::set_error("");
-    }
+    if (int rc = fin_pending(s, &n_pend, &overflowed)) return rc;
     for (int round = 0; round < 1 << 20; round++) {
         for (int p = 0; p < s->n_ranks; p++)
-            KT_HIP(hipMemsetAsync(s->fin_send + (uint64_t)p * words, 0, HDR_U64 * 8, ctx->stream));
+            KT_HIP(hipMemsetAsync(s->fin_send + (uint64_t)p * FIN_WORDS, 0, HDR_U64 * 8, ctx->stream));
         KT_HIP(hipMemsetAsync(s->fin_left, 0, 8, ctx->stream));
-        if (n_pend) {
-            hipLaunchKernelGGL(pack_pending_kernel, dim3(ktl::grid_for(ctx, (n_pend + BLOCK - 1) / BLOCK, 4)), dim3(BLOCK), 0,
-                               ctx->stream, s->pend_keys, (const uint32_t *)s->pend_counts, n_pend, (uint32_t)s->n_ranks,
-                               (uint32_t)s->k, words, s->fin_send, s->fin_left);
-        }
-        hipLaunchKernelGGL(stamp_left_kernel, dim3(1), dim3(64), 0, ctx->stream, s->fin_send, (uint32_t)s->n_ranks, words,
-                           s->fin_left, (uint64_t)(overflowed ? 1 : 0));
-        KT_HIP(hipGetLastError());
+        if (n_pend)
+            if (int rc = ktl::launch(pack_pending_kernel, dim3(ktl::grid_for(ctx, (n_pend + BLOCK - 1) / BLOCK, 4)), dim3(BLOCK), 0,
+                                     ctx->stream, s->pend_keys, s->pend_counts, n_pend, s->n_ranks, s->k, FIN_WORDS, s->fin_send, s->fin_left))
+                return rc;
+        if (int rc = ktl::launch(stamp_left_kernel, dim3(1), dim3(64), 0, ctx->stream, s->fin_send, s->n_ranks, FIN_WORDS, s->fin_left,
+                                 overflowed ? 1 : 0))
+            return rc;
         KT_HIP(hipEventRecord(s->ev_main, ctx->stream));
         KT_HIP(hipStreamWaitEvent(s->comm_stream, s->ev_main, 0));
-        if (int rc = exchange(s, s->fin_send, s->fin_recv, words)) return rc;
+        if (int rc = exchange(s, s->fin_send, s->fin_recv, FIN_WORDS)) return rc;
         // the headers decide whether another round is needed: every rank sees every rank's remainder and status
-        for (int p = 0; p < s->n_ranks; p++)
-            KT_HIP(hipMemcpyAsync(hdr.data() + (size_t)p * HDR_U64, s->fin_recv + (uint64_t)p * words, HDR_U64 * 8,
-                                  hipMemcpyDeviceToHost, s->comm_stream));
-        KT_HIP(hipStreamSynchronize(s->comm_stream));
         bool more = false, failed = false;
-        for (int p = 0; p < s->n_ranks; p++) {
-            more |= hdr[(size_t)p * HDR_U64 + 1] != 0;
-            failed |= hdr[(size_t)p * HDR_U64 + 2] != 0;
-        }
+        if (int rc = fin_headers(s, hdr.data(), &more, &failed)) return rc;
         if (failed)
             return kt::fail(KT_ERR_FULL, overflowed ? "sharded counter: too many distinct k-mers did not fit their exchange regions (batch larger than max_batch_bases allows?)"
                                                     : "sharded counter: another rank's pending table overflowed");
-        for (int p = 0; p < s->n_ranks; p++) {
-            const uint64_t n = hdr[(size_t)p * HDR_U64] < FIN_CAP ? hdr[(size_t)p * HDR_U64] : FIN_CAP;
-            if (n)
-                if (int rc = kt_ctr_add_pairs(s->table, s->fin_recv + (uint64_t)p * words + HDR_U64,
-                                              reinterpret_cast<const uint32_t *>(s->fin_recv + (uint64_t)p * words + HDR_U64 + FIN_CAP),
-                                              n, KT_MEM_DEVICE))
-                    return rc;
-        }
+        for (int p = 0; p < s->n_ranks; p++)
+            if (int rc = fin_deliver(s, p, hdr[(size_t)p * HDR_U64])) return rc;
+        KT_HIP(hipStreamSynchronize(ctx->stream));  // (fin_recv is reused by the next round, or the next finalize)
         if (!more) {
-            KT_HIP(hipStreamSynchronize(ctx->stream));  // (fin_recv is reused by the next finalize)
-            if (!n_pend && !overflowed) {               // nothing was pending: the table is as clean as it was
-                s->pend_touched = false;
-                return KT_OK;
-            }
             s->pend_touched = false;
-            return kt_ctr_clear(s->pend);               // everything pending has been delivered
+            // nothing was pending: the table is as clean as it was; otherwise everything pending has been delivered
+            return !n_pend && !overflowed ? (int)KT_OK : kt_ctr_clear(s->pend);
         }
-        KT_HIP(hipStreamSynchronize(ctx->stream));
     }
     return kt::fail(KT_ERR_HIP, "sharded counter: finalize did not converge");
 }

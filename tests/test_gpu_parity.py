@@ -759,6 +759,82 @@ def test_sharded_single_rank_through_rccl(torch_mod, ctx, oracle, monkeypatch, o
     sh.close()
 
 
+_PIECE_K = 31
+_piece_cache = {}
+
+
+def _piece_batches(oracle):
+    """the batches of test_sharded_piece_arithmetic_edges with the oracle's table of each - made once, never changed:
+    zero reads; one read shorter than k (bases, no record); 40 ragged reads (less than a block of records per owner: most
+    pieces are empty); 800 reads of 150 bases (a handful of blocks per owner); and, for the flood case, mostly poly-A (owner 0
+    of 2) with (AC)n (owner 1 of 2: the region whose overflow the room cuts off what leaves)"""
+    from kmertools_amd import device
+    if not _piece_cache:
+        rng = np.random.default_rng(20260)
+        alpha = np.frombuffer(b"ACGT", np.uint8)
+        lists = {"edges": [[], [b"ACGTTGCAAC"], ragged_reads(97, 40, max_len=120, special=False), _random_reads(98, 800)],
+                 "flood": [[b"A" * 150] * 500 + [b"AC" * 75] * 400 + _random_reads(99, 100) +
+                           [alpha[rng.integers(0, 4, size=int(n))].tobytes() for n in rng.integers(31, 90, size=50)]]}
+        for name, seq_lists in lists.items():
+            out = []
+            for seqs in seq_lists:
+                bases, offsets = device.to_csr(seqs) if seqs else (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+                wk, wc = oracle.count_reads(bases, offsets, _PIECE_K) if seqs else (np.zeros(0, np.uint64), np.zeros(0, np.uint32))
+                out.append((bases, offsets, wk, wc))
+            _piece_cache[name] = out
+    return _piece_cache
+
+
+def _tables_added(ak, ac, bk, bc):
+    """the sorted (k-mer, count) table of two such tables' sum"""
+    keys, inv = np.unique(np.concatenate([ak, bk]), return_inverse=True)
+    counts = np.zeros(len(keys), np.uint64)
+    np.add.at(counts, inv, np.concatenate([ac, bc]).astype(np.uint64))
+    return keys, counts.astype(np.uint32)
+
+
+def _add_and_check(sh, batches, room):
+    """every batch in turn into the counter `sh`: after each, what left (exchanged_bytes) is every block of the owners >= 1
+    exactly once, the route pass saw the oracle's k-mers, and the finalized table is the oracle's of everything so far"""
+    have_k, have_c = sh.table.export_host()
+    for bases, offsets, wk, wc in batches:
+        before = sh.exchanged_bytes()
+        sh.add_reads_host(bases, offsets)
+        rec, km = sh.route_stats()
+        blocks = [-(-min(int(r), room) // 1024) for r in rec[1:]]
+        assert sh.exchanged_bytes() - before == 10240 * sum(blocks), (rec, blocks)
+        assert int(km.sum()) == int(wc.astype(np.uint64).sum())
+        sh.finalize()
+        have_k, have_c = _tables_added(have_k, have_c, wk, wc)
+        gk, gc = sh.table.export_host()
+        assert np.array_equal(gk, have_k) and np.array_equal(gc, have_c)
+    return rec
+
+
+@pytest.mark.parametrize("owners,slices,room_blocks", [(o, p, 0) for o in (1, 2, 7) for p in (1, 3, 64)] + [(2, 4, 2)])
+def test_sharded_piece_arithmetic_edges(ctx, oracle, monkeypatch, owners, slices, room_blocks):
+    """the pieces the regions are counted in, at the edges of their arithmetic (one process, KT_SHARD_FORCE): 1, 3 and 64
+    pieces - 64 is the clamp, more pieces than any region here has blocks - of 1, 2 and 7 owners' regions that hold no
+    record, less than a block, a few blocks; through the range build (KT_BULK_MIN_BASES=0) and then, on the same counter,
+    through the probing path, which counts every run behind the last piece.  Regions hold 65 blocks at least: nothing
+    overflows, min(records, room) is the records - but in the last case, regions of two blocks that a batch of mostly
+    poly-A overflows: what leaves is the room's two blocks, the rest is counted aside and delivered by finalize."""
+    from kmertools_amd import device
+    batches = _piece_batches(oracle)["flood" if room_blocks else "edges"]
+    room = (room_blocks or 65) * 1024
+    monkeypatch.setenv("KT_SHARD_FORCE", str(owners))
+    monkeypatch.setenv("KT_SHARD_SLICES", str(slices))
+    if room_blocks:
+        monkeypatch.setenv("KT_SHARD_ROOM_BLOCKS", str(room_blocks))
+    sh = device.Sharded(ctx, _PIECE_K, 1 << 21, max(int(b[1][-1]) for b in batches), 1, 0, None)
+    monkeypatch.setenv("KT_BULK_MIN_BASES", "0")
+    rec = _add_and_check(sh, batches, room)
+    assert len(rec) == owners and (int(rec[1]) > room if room_blocks else int(rec.max()) < room)
+    monkeypatch.delenv("KT_BULK_MIN_BASES")
+    _add_and_check(sh, batches, room)
+    sh.close()
+
+
 def test_route_pass_records_match_restatement(torch_mod, ctx, oracle, monkeypatch):
     """the route pass over ragged reads (N runs, lower case, raw codes, reads shorter than k, a 9000-base read, poly-A and
     ACGT-repeat reads longer than a segment - runs of one owner that span whole threads and segments) into 1 .. 7 owners'
