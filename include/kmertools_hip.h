@@ -343,6 +343,54 @@ int kt_ctr_setop(kt_ctr *a, kt_ctr *b, int op, int count_rule, uint32_t min_a, u
 int kt_ctr_graph(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint64_t *keys, uint32_t *info, uint32_t *counts,
                  uint64_t max_out, uint64_t *n_out, uint64_t *census, int mem, int sorted);
 
+/* The heterozygous k-mer pairs of the table: the pairs of solid k-mers that differ in exactly one base and have no other
+ * such partner (Smudgeplot's hetkmers; the plot of their coverages, minor against major, shows ploidy and genome structure).
+ * A node is a canonical k-mer u of the table with min_count <= count(u) <= max_count ("solid").  F = its forward string,
+ * the canonical word itself; canon(s) = the smaller of s and its reverse complement: exactly kt_ctr_graph's definitions.
+ * The positions P depend on `positions`:
+ *   KT_HET_ALL     every i in 0..k
+ *   KT_HET_MIDDLE  only i = (k - 1) / 2; odd k only, KT_ERR_ARG for even k (Smudgeplot's --middle)
+ * Both sets are symmetric under i -> k - 1 - i, which is what makes the relation below symmetric.
+ * N(u) is a SET: { canon(F with base i replaced by b) : i in P, b != F[i] } with u itself removed, and only its solid
+ * members kept.  deg(u) = |N(u)|.  Three consequences:
+ *   1. self-substitution: a substitution can lead back to u.  For odd k, F = X m rc(X) with m in {A, C} has rc(F) = F with
+ *      the middle complemented.  Such a candidate is not a neighbour.
+ *   2. double reach: two substitutions can reach the same neighbour, because both v and rc(v) can lie at distance 1 from
+ *      F.  k = 5: N(ACCGT) = {ACAGT} - ACAGT is reached by C->A and by C->T (ACTGT = rc(ACAGT)), and C->G gives rc(ACCGT),
+ *      which is ACCGT itself - so deg(ACCGT) is 1, not 2 or 3.
+ *   3. symmetry: v in N(u) if and only if u in N(v).
+ * A PAIR is {u, v} with N(u) = {v} and N(v) = {u}.  It is emitted exactly once, as (a, b) with a < b as canonical words;
+ * each node is in at most one pair, so a is a unique sort key.  A neighbour present in the table but outside the count
+ * range is not a neighbour.
+ * Pair i is (keys_a[i], keys_b[i]) with occurrences counts_a[i], counts_b[i] (either counts array may be NULL).
+ * sorted != 0: ascending keys_a; otherwise the order is unspecified.  *n_out = the number of pairs, always exact.
+ * max_out == 0 only counts (the outputs may be NULL) and still fills matrix / census.  If 0 < max_out < *n_out, nothing
+ * past max_out is written (what is written is of no use) and the call returns KT_ERR_ARG with *n_out set and matrix /
+ * census added to, so that the caller can resize and repeat: kt_ctr_graph's convention.
+ * matrix (may be NULL): n_rows x n_cols u64, row-major, ADDED into: cell [r * n_cols + c] += the pairs with
+ * min(minor, n_rows - 1) == r and min(major, n_cols - 1) == c, minor <= major the pair's two counts (the smudge plot
+ * itself).  n_rows >= 2, n_cols >= 2, n_rows * n_cols <= 2^24, as in kt_ctr_compare.
+ * census (may be NULL): KT_HET_CENSUS u64, ADDED into:
+ *   [0] nodes  [1] occurrences of the nodes  [2] nodes with deg == 0  [3] deg == 1  [4] deg >= 2  [5] pairs
+ *   [6] sum of the minor counts over the pairs  [7] sum of the major counts (exact u64; 0xFFFFFFFF is an ordinary count)
+ * The table's content does not change; it is probed, so it gets its probing image first, as in kt_ctr_graph, and is
+ * walked in the form it then has.  An empty table gives *n_out = 0 and adds nothing.  The whole table must be resident
+ * (there is no n_parts, for kt_ctr_graph's reason).
+ * mem says where the outputs, matrix and census live.  KT_MEM_HOST synchronises; KT_MEM_DEVICE writes on the context's
+ * stream, but the call still synchronises once, to learn *n_out.
+ * KT_ERR_ARG: a null table or n_out, min_count == 0, min_count > max_count, unknown positions, KT_HET_MIDDLE with an even
+ * k, a bad mem, null keys_a or keys_b with max_out > 0, a bad matrix shape when matrix is given, a table that is one
+ * shard of a sharded table, sorted output (max_out > 0) from a table of 2^33 entries or more (the sort carries a pair's
+ * index as u32).  An overflowed table is KT_ERR_FULL as in kt_ctr_size.  On every one of these errors the outputs, the
+ * matrix and the census are untouched.  Device scratch: 24 bytes per table entry (the nodes' keys and the candidate pairs)
+ * and, when sorted, 12 bytes per pair of room, besides kt_ctr_graph's sort. */
+#define KT_HET_ALL 0
+#define KT_HET_MIDDLE 1
+#define KT_HET_CENSUS 8
+int kt_ctr_hetmers(kt_ctr *table, uint32_t min_count, uint32_t max_count, int positions, uint64_t *keys_a, uint64_t *keys_b,
+                   uint32_t *counts_a, uint32_t *counts_b, uint64_t max_out, uint64_t *n_out, uint64_t *matrix,
+                   uint32_t n_rows, uint32_t n_cols, uint64_t *census, int mem, int sorted);
+
 /* The maximal unitigs of that graph: the sequences of the compacted de Bruijn graph (what BCALM / Cuttlefish write as
  * unitigs.fa), spelled on the device.  Nodes, F, canon, the info word and "solid" are exactly kt_ctr_graph's, for the same
  * (min_count, max_count).  A side of node u (R or L) is JOINED when all of these hold:

@@ -21,6 +21,7 @@ KT_CARD_MIN_P, KT_CARD_MAX_P = 4, 16
 KT_SET_INTERSECT, KT_SET_SUBTRACT, KT_SET_UNION, KT_SET_XOR = 0, 1, 2, 3
 KT_SETCNT_FIRST, KT_SETCNT_MIN, KT_SETCNT_MAX, KT_SETCNT_SUM = 0, 1, 2, 3
 KT_GRAPH_CENSUS = 32
+KT_HET_ALL, KT_HET_MIDDLE, KT_HET_CENSUS = 0, 1, 8
 KT_TIP_KEEP, KT_TIP_TIP, KT_TIP_ISOLATED, KT_TIP_TALLY = 0, 1, 2, 4
 KT_CLIP_ISOLATED, KT_CLIP_STATS = 1, 8
 KT_BUBBLE_POP, KT_BUBBLE_TALLY, KT_SIMPLIFY_STATS = 4, 4, 12
@@ -68,6 +69,7 @@ SYMBOLS = {
     "kt_ctr_compare": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _i]),
     "kt_ctr_setop": (_i, [_vp, _vp, _i, _i, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64), _i, _i]),
     "kt_ctr_graph": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _i, _i]),
+    "kt_ctr_hetmers": (_i, [_vp, _u32, _u32, _i, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _u32, _u32, _vp, _i, _i]),
     "kt_ctr_unitigs": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _i]),
     "kt_ctr_unitigs_linked": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _u64,
                                    C.POINTER(_u64), _i]),

@@ -2121,6 +2121,113 @@ std::string GraphComputer::graph() {
 }
 
 // ---------------------------------------------------------------------------------------------
+HetmerComputer::HetmerComputer(std::string in_path, std::string out_dir, int ksize)
+    : in_path_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
+
+HetmerComputer::~HetmerComputer() {
+    if (table_) kt_ctr_destroy(table_);
+}
+
+std::string HetmerComputer::hetmers() {
+    if (table_) kt_ctr_destroy(table_);
+    table_ = nullptr;
+    // HBM per slot: the slot (16) + its share of the nodes and candidates (24 bytes an entry), and of the result and the sort
+    // (at most one pair per two entries: 24 + 12 + 12 bytes a pair), with 1.9 slots per entry: 48 / 1.9 < 26
+    if (std::string e = whole_table(dev_, in_path_, ksize_, 16 + 26, "hetmers", &table_); !e.empty()) return e;
+    PhaseTimer pt("hetmers");
+    SeqReader reader;
+    if (!reader.open(in_path_, false)) return reader.error();
+    Batch b;
+    Lap lap;
+    if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    // every k-mer is in at most one pair: half the entries size the host arrays, one call, no counting call before it
+    uint64_t bound = 0, n = 0, census[KT_HET_CENSUS] = {};
+    if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
+    bound = stats_only_ ? 0 : bound / 2;
+    const uint32_t R = max_minor_ + 1, C = max_major_ + 1;
+    std::vector<uint64_t> ka((size_t)bound), kb((size_t)bound), m((size_t)R * C);
+    std::vector<uint32_t> ca((size_t)bound), cb((size_t)bound);
+    if (kt_ctr_hetmers(table_, min_count_, max_count_, middle_ ? KT_HET_MIDDLE : KT_HET_ALL, ka.data(), kb.data(), ca.data(), cb.data(),
+                       bound, &n, m.data(), R, C, census, KT_MEM_HOST, 1) != KT_OK)
+        return kt_last_error();
+    pt.t[1] += lap();
+    if (!stats_only_) {
+        const std::string ppath = out_dir_ + "/hetmers.pairs", cpath = out_dir_ + "/hetmers.cov";
+        FILE *outp = fopen(ppath.c_str(), "wb");
+        if (!outp) return "Unable to write to file: " + ppath;
+        FILE *outc = fopen(cpath.c_str(), "wb");
+        if (!outc) {
+            fclose(outp);
+            return "Unable to write to file: " + cpath;
+        }
+        // B as written: the strand of b that differs from A at one allowed position, and that position.  Where both strands
+        // do (double reach) it is b's forward strand, the lower position first.
+        const uint32_t p_lo = middle_ ? (uint32_t)(ksize_ - 1) / 2u : 0u, p_hi = middle_ ? p_lo + 1u : (uint32_t)ksize_;
+        auto one_sub = [&](uint64_t x, uint32_t *pos) {
+            for (uint32_t i = p_lo; i < p_hi; i++)
+                if ((x & ~(3ull << 2u * ((uint32_t)ksize_ - 1u - i))) == 0) {
+                    *pos = i;
+                    return true;
+                }
+            return false;
+        };
+        constexpr uint64_t slab = 1ull << 18;
+        std::vector<std::string> pieces;
+        bool okp = true, okc = true;
+        for (uint64_t i0 = 0; i0 < n && okp && okc; i0 += slab) {
+            format_rows(std::min(slab, n - i0), threads_, 2 * (size_t)ksize_ + 30, pieces, [&](uint64_t r, std::string &s) {
+                const uint64_t i = i0 + r;
+                uint64_t bw = kb[i];
+                uint32_t pos = 0;
+                if (!one_sub(ka[i] ^ bw, &pos)) {
+                    bw = kt_rev_comp(kb[i], ksize_);
+                    (void)one_sub(ka[i] ^ bw, &pos);
+                }
+                append_kmer(s, ka[i], ksize_, true);
+                s += '\t';
+                append_kmer(s, bw, ksize_, true);
+                s += '\t';
+                append_uint(s, pos);
+                s += '\t';
+                append_uint(s, ca[i]);
+                s += '\t';
+                append_uint(s, cb[i]);
+                s += '\n';
+            });
+            for (const auto &p : pieces) okp = okp && fwrite(p.data(), 1, p.size(), outp) == p.size();
+            format_rows(std::min(slab, n - i0), threads_, 24, pieces, [&](uint64_t r, std::string &s) {
+                const uint64_t i = i0 + r;
+                append_uint(s, std::min(ca[i], cb[i]));
+                s += '\t';
+                append_uint(s, std::max(ca[i], cb[i]));
+                s += '\n';
+            });
+            for (const auto &p : pieces) okc = okc && fwrite(p.data(), 1, p.size(), outc) == p.size();
+        }
+        if (fclose(outp) != 0 || !okp) {
+            fclose(outc);
+            return "Unable to write to file: " + ppath;
+        }
+        if (fclose(outc) != 0 || !okc) return "Unable to write to file: " + cpath;
+    }
+    std::string s;
+    s.reserve((size_t)R * C * 2);
+    for (uint32_t r = 0; r < R; r++)
+        for (uint32_t c = 0; c < C; c++) {
+            append_uint(s, m[(size_t)r * C + c]);
+            s += c + 1 < C ? '\t' : '\n';
+        }
+    if (std::string e = write_text_file(out_dir_ + "/hetmers.matrix", s); !e.empty()) return e;
+    static const char *names[KT_HET_CENSUS] = {"nodes", "occurrences", "degree_0", "degree_1", "degree_2_or_more", "pairs", "minor_sum", "major_sum"};
+    s = "k\t" + std::to_string(ksize_) + "\nmin_count\t" + std::to_string(min_count_) + "\nmax_count\t" + std::to_string(max_count_) +
+        "\npositions\t" + (middle_ ? "middle" : "all") + "\n";
+    for (int j = 0; j < KT_HET_CENSUS; j++) s += std::string(names[j]) + '\t' + std::to_string(census[j]) + '\n';
+    if (std::string e = write_text_file(out_dir_ + "/hetmers.stats", s); !e.empty()) return e;
+    pt.t[3] += lap();
+    return "";
+}
+
+// ---------------------------------------------------------------------------------------------
 UnitigComputer::UnitigComputer(std::string in_path, std::string out_dir, int ksize)
     : in_path_(std::move(in_path)), out_dir_(std::move(out_dir)), ksize_(ksize) {}
 

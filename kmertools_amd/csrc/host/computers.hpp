@@ -410,6 +410,38 @@ class GraphComputer {
     kt_ctr *table_ = nullptr;
 };
 
+// `hetmers`: the heterozygous k-mer pairs of an input's counted k-mers (kt_ctr_hetmers, sorted) and the matrix of their
+// coverages, minor against major (Smudgeplot's hetkmers and its plot): one table, the whole of it on the device, as for
+// `graph`.  Writes {out_dir}/hetmers.pairs ("A\tB\tpos\tcount_a\tcount_b" per pair, ascending numeric A, B on the strand on
+// which it differs from A at position pos) and {out_dir}/hetmers.cov ("minor\tmajor" per pair, the same order) - neither
+// with stats_only, which moves no pairs to the host -, {out_dir}/hetmers.matrix ((max_minor + 1) lines of max_major + 1
+// tab-separated counts, compare.matrix's layout) and {out_dir}/hetmers.stats ("name\tvalue" lines: k, the count range, the
+// positions, the KT_HET_CENSUS values).
+class HetmerComputer {
+  public:
+    HetmerComputer(std::string in_path, std::string out_dir, int ksize);
+    ~HetmerComputer();
+    HetmerComputer(const HetmerComputer &) = delete;
+    HetmerComputer &operator=(const HetmerComputer &) = delete;
+    void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
+    void set_middle(bool m) { middle_ = m; }
+    void set_max_counts(uint32_t max_minor, uint32_t max_major) { max_minor_ = max_minor, max_major_ = max_major; }
+    void set_stats_only(bool s) { stats_only_ = s; }
+    void set_threads(int t) { threads_ = t; }
+    void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // (accepted; the table lives in HBM)
+    void set_device(int d) { dev_.index = d; }
+    std::string hetmers();  // "" or the error message
+
+  private:
+    std::string in_path_, out_dir_;
+    int ksize_, threads_ = 0;
+    uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu, max_minor_ = 500, max_major_ = 1000;
+    bool middle_ = false, stats_only_ = false;
+    double memory_ceil_gb_ = 6.0;
+    Device dev_;
+    kt_ctr *table_ = nullptr;
+};
+
 // `unitigs`: the maximal unitigs of the de Bruijn graph of an input's counted k-mers (kt_ctr_unitigs): one table, the whole of
 // it on the device, as for `graph`.  Writes {out_dir}/unitigs.fa (">{i} LN:i:{bases} KC:i:{count sum} km:f:{count sum / nodes}"
 // and " CL:i:1" on a cycle, then the sequence on one line; not with stats_only) and {out_dir}/unitigs.stats ("name\tvalue":

@@ -5,7 +5,7 @@
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
 // and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
 // inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances) and `graph` (de Bruijn adjacency of the counted
-// k-mers) and `unitigs` (that graph's maximal unitigs) and `card` (a HyperLogLog estimate of the distinct k-mers, which
+// k-mers) and `unitigs` (that graph's maximal unitigs) and `hetmers` (the heterozygous k-mer pairs) and `card` (a HyperLogLog estimate of the distinct k-mers, which
 // also sizes the tables of the others: --estimate-size).
 #include <math.h>
 #include <stdio.h>
@@ -190,6 +190,7 @@ const char *HELP_MAIN =
     "  setop   Intersect, subtract, union or xor the k-mer sets of two inputs\n"
     "  graph   De Bruijn adjacency, unitig ends and node census of the counted k-mers\n"
     "  unitigs Maximal unitigs of the de Bruijn graph of the counted k-mers\n"
+    "  hetmers Heterozygous k-mer pairs of the counted k-mers and their coverage matrix\n"
     "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
     "  card    Estimate the number of distinct k-mers (HyperLogLog), sizes tables\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
@@ -986,6 +987,82 @@ int cmd_graph(int argc, char **argv, int from) {
     });
 }
 
+const char *HELP_HETMERS =
+    "Heterozygous k-mer pairs of the counted k-mers and their coverage matrix\n\n"
+    "Counts the canonical k-mers of the input.  A k-mer is solid when min-count <= its count <= max-count.  Two solid k-mers\n"
+    "are a pair when they differ in exactly one base (either strand) and neither has another solid k-mer at one substitution:\n"
+    "the two alleles of an isolated heterozygous site (Smudgeplot's hetkmers).  Writes, in ascending order of the numeric\n"
+    "smaller k-mer A of each pair:\n"
+    "  {output}/hetmers.pairs   \"A<TAB>B<TAB>pos<TAB>count_a<TAB>count_b\": both k-mers as letters, B on the strand on which it\n"
+    "                           differs from A at the one 0-based position pos\n"
+    "  {output}/hetmers.cov     \"minor<TAB>major\": the smaller and the larger of the pair's two counts, in the same order\n"
+    "  {output}/hetmers.matrix  line r (r = 0..max-minor) holds max-major + 1 tab-separated numbers: the pairs whose minor\n"
+    "                           count is r and whose major count is the column; the last row and column count theirs or more\n"
+    "  {output}/hetmers.stats   one \"name<TAB>value\" line each: k, min_count, max_count, positions (all or middle), nodes,\n"
+    "                           occurrences, degree_0, degree_1, degree_2_or_more (solid k-mers with that many solid k-mers\n"
+    "                           at one substitution), pairs, minor_sum, major_sum\n"
+    "The whole table must fit the device memory, as for `graph`: a k-mer's partners live anywhere in it, so hetmers cannot\n"
+    "count in several passes, and says so before it writes.\n\n"
+    "Usage: kmertools hetmers [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          Input file path\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "      --min-count <N>          Lowest count of a solid k-mer [default: 1]\n"
+    "      --max-count <N>          Highest count of a solid k-mer [default: 4294967295]\n"
+    "      --middle                 Substitutions of the middle base only (odd k)\n"
+    "      --max-minor <N>          Highest minor count of the rows; the last row counts N or more [default: 500]\n"
+    "      --max-major <N>          Highest major count of the columns; the last column counts N or more [default: 1000]\n"
+    "      --stats-only             Write hetmers.matrix and hetmers.stats only, no hetmers.pairs and hetmers.cov\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_ESTIMATE
+    "  -h, --help                   Print help\n";
+
+int cmd_hetmers(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},   {'o', "output", true},    {'k', "k-size", true},    {0, "min-count", true},
+                                     {0, "max-count", true}, {0, "middle", false},     {0, "max-minor", true},   {0, "max-major", true},
+                                     {0, "stats-only", false}, {'m', "memory", true},  {'t', "threads", true},   {0, "device", true},
+                                     SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_HETMERS);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work and before the output directory is made
+    const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
+    const uint64_t hi = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (lo > hi)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(lo) + " is greater than " + std::to_string(hi));
+    const bool middle = f.count("middle") != 0;
+    if (middle && k % 2 == 0)
+        usage_error("invalid value '" + std::to_string(k) + "' for '--k-size <K_SIZE>' with '--middle': an even k has no middle base");
+    const uint64_t max_minor = ranged(f, "max-minor", 1, (1u << 24) - 1, false, 500);
+    const uint64_t max_major = ranged(f, "max-major", 1, (1u << 24) - 1, false, 1000);
+    if ((max_minor + 1) * (max_major + 1) > (1ull << 24))
+        usage_error("invalid values for '--max-minor' and '--max-major': (" + std::to_string(max_minor) + " + 1) x (" +
+                    std::to_string(max_major) + " + 1) cells is more than 16777216");
+    const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
+    const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
+    if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+        fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
+        return 101;
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    return run_table_command(est, [&]() -> std::string {
+        HetmerComputer hc(in, out, k);
+        hc.set_range((uint32_t)lo, (uint32_t)hi);
+        hc.set_middle(middle);
+        hc.set_max_counts((uint32_t)max_minor, (uint32_t)max_major);
+        hc.set_stats_only(f.count("stats-only") != 0);
+        if (threads > 0) hc.set_threads(threads);
+        hc.set_max_memory((double)mem);
+        hc.set_device(device);
+        return hc.hetmers();
+    });
+}
+
 const char *HELP_UNITIGS =
     "Maximal unitigs of the de Bruijn graph of the counted k-mers\n\n"
     "Counts the canonical k-mers of the input.  A k-mer is a node when min-count <= its count <= max-count; nodes are chained\n"
@@ -1220,5 +1297,6 @@ int main(int argc, char **argv) {
     if (cmd == "setop") return cmd_setop(argc, argv, 2);
     if (cmd == "graph") return cmd_graph(argc, argv, 2);
     if (cmd == "unitigs") return cmd_unitigs(argc, argv, 2);
+    if (cmd == "hetmers") return cmd_hetmers(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

@@ -279,7 +279,7 @@ __global__ __launch_bounds__(BLOCK) void erase_survivors_kernel(const Slot *__re
     }
 }
 
-// ---- a table's entries in the form they are in (view_of builds it; the walks of spectrum, compare, setop and graph read it) ---------
+// ---- a table's entries in the form they are in (view_of builds it; the walks of spectrum, compare, setop, graph and hetmers read it) ---------
 // The form is the kernels' template argument; the view holds what they read.
 enum Form { FORM_PROBE = 0, FORM_DENSE = 1, FORM_PAIRS = 2 };
 struct TableView {
@@ -665,17 +665,18 @@ struct SetShared {
     uint64_t tile_base[2];
 };
 
-// the workgroup's tile: entries with out[u] != 0 are kept.  Every thread of the workgroup must be here, `step` counting
-// the calls (two barriers a call; the parity keeps a step's LDS words apart from its neighbours').  N: the walk's unroll.
-template <uint32_t N>
-__device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)[N], const uint32_t (&out)[N], SetShared &sm,
-                                         uint32_t &step) {
+// the workgroup's tile: the entries whose bit is set in `keep` are kept, store(u, pos) writes entry u to its place `pos` of the
+// output (the payload is the caller's: setop's and graph's u32, hetmers' second key).  Every thread of the workgroup must be
+// here, `step` counting the calls (two barriers a call; the parity keeps a step's LDS words apart from its neighbours').
+// N: the walk's unroll.
+template <uint32_t N, class Store>
+__device__ __forceinline__ void tile_emit(uint64_t *cursor, uint32_t keep, SetShared &sm, uint32_t &step, Store &&store) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, par = step++ & 1u;
     uint64_t bal[N];
     uint32_t total = 0;
 #pragma unroll
     for (uint32_t u = 0; u < N; u++) {
-        bal[u] = __ballot(out[u] != 0u);
+        bal[u] = __ballot((keep >> u) & 1u);
         total += (uint32_t)__popcll(bal[u]);
     }
     if (lane == 0) sm.wave_total[par][wave] = total;
@@ -688,21 +689,30 @@ __device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)
         all += t;
     }
     if (threadIdx.x == 0 && all)
-        sm.tile_base[par] = atomicAdd(reinterpret_cast<unsigned long long *>(s.cursor), (unsigned long long)all);
+        sm.tile_base[par] = atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)all);
     ktd::lds_barrier();
     if (!total) return;
     uint64_t base = sm.tile_base[par] + before;
 #pragma unroll
     for (uint32_t u = 0; u < N; u++) {
-        if ((bal[u] >> lane) & 1ull) {
-            const uint64_t pos = base + __popcll(bal[u] & ((1ull << lane) - 1ull));
-            if (pos < s.max_out) {
-                s.out_keys[pos] = key[u];
-                s.out_counts[pos] = out[u];
-            }
-        }
+        if ((bal[u] >> lane) & 1ull) store(u, base + __popcll(bal[u] & ((1ull << lane) - 1ull)));
         base += (uint32_t)__popcll(bal[u]);
     }
+}
+
+// ... with a u32 payload: entries with out[u] != 0 are kept as (key[u], out[u]), nothing at or past s.max_out is written
+template <uint32_t N>
+__device__ __forceinline__ void set_emit(const SetArgs &s, const uint64_t (&key)[N], const uint32_t (&out)[N], SetShared &sm,
+                                         uint32_t &step) {
+    uint32_t keep = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < N; u++) keep |= (out[u] != 0u ? 1u : 0u) << u;
+    tile_emit<N>(s.cursor, keep, sm, step, [&](uint32_t u, uint64_t pos) {
+        if (pos < s.max_out) {
+            s.out_keys[pos] = key[u];
+            s.out_counts[pos] = out[u];
+        }
+    });
 }
 
 // w: the walked table's view, FORM = its form
@@ -843,6 +853,222 @@ __global__ __launch_bounds__(BLOCK) void graph_kernel(TableView w, GraphArgs g) 
         if (const uint32_t v = cells[tid - GRAPH_SUMS])
             atomicAdd(reinterpret_cast<unsigned long long *>(g.census + tid), (unsigned long long)v);
     }
+}
+
+// ---- heterozygous k-mer pairs of a table (kt_ctr_hetmers) -------------------------------------------------------------
+// The rule is in the header.  Three kernels, so that every lane that probes has a k-mer to probe for:
+//   nodes   the table walked read-only in the form it is in (walk_entries), its nodes compacted into an array of keys by
+//           tile_emit, one cursor atomic per workgroup tile; nodes and their occurrences tallied.  A first version scanned
+//           in this walk, as graph_kernel does its 14 probes: with counts from 2 up on a 30x read set one slot in 19 holds a
+//           node, and the few lanes of a wave that had one went through up to 93 probes while the others stood idle - 0.11 ns
+//           per probe against 0.035 with every entry a node.  Whether the graph's 14 probes would pay for a
+//           compaction nobody has measured; these 3k do.
+//   scan    one lane per node, probing the table's probing image.  A node's 3 |P| one-substitution variants are functions of F
+//           alone: with R = rev_comp(F), the variant
+//           of position i and d in 1..3 is min(F ^ (d << 2(k-1-i)), R ^ (d << 2i)) - the complement of a substituted base is
+//           the same XOR at the mirrored position, so one bit reversal serves them all.  They go through Probed::counts in
+//           groups of HET_POS positions (below); the lane keeps the first solid neighbour n1 and one flag, "a solid variant other
+//           than n1 was seen" (deg >= 2), and stops issuing groups at the flag: the census needs the classes 0 / 1 / >= 2 only.
+//           A variant equal to F is not probed (self-substitution); one equal to n1 does not raise the flag (double reach).
+//           Lanes with deg == 1 and F < n1 are compacted as candidates (F, n1) by tile_emit, one cursor atomic per tile.
+//   verify  one lane per candidate runs the same scan from n1, with F already in hand as its first neighbour: the flag is
+//           then "n1 has a solid neighbour other than F".  (F itself turns up by the rule's symmetry; were the table changed
+//           under the call it might not, and the pair would still be reported - there is no device assert for that.)
+//           Survivors are compacted into the output; their two counts are probed here for the sums and the matrix.
+// The numbers of nodes and candidates stay on the device: scan and verify read the cursor of the kernel before them and run
+// on a grid of the device's size, every workgroup taking the same number of steps over it, so that all reach the emit's
+// barriers.  The group is HET_POS = 5 positions = 15 keys in flight per lane, one more than graph_kernel's 14: the compiler
+// reports 120 VGPRs for het_scan_kernel and 125 for het_verify_kernel (4 waves per SIMD; graph_kernel: 119); 4 positions
+// take 98 / 104, which is still 4 waves, and 6 take 141 / 146 and cost the fourth.  So 5 it is, from the register report
+// alone: 4 against 5 on the clock nobody has measured (-DKT_HET_POS=4 builds the
+// other).  A group is also the grain of the early stop: a lane whose flag rises issues no further group.  The census classes
+// are tallied in registers and reduced as in graph_kernel.  The pairs' matrix cells are plain 64-bit global atomics, one per
+// pair: pairs are a small share of the nodes and spread over the smudges' cells, but nobody has measured a table where they
+// are not; the three pair sums are register tallies.
+#ifndef KT_HET_POS
+#define KT_HET_POS 5
+#endif
+constexpr uint32_t HET_UNROLL = 4, HET_POS = KT_HET_POS, HET_KEYS = 3 * HET_POS, HET_NODE_SUMS = 2, HET_DEG_SUMS = 3, HET_PAIR_SUMS = 3;
+static_assert(HET_NODE_SUMS + HET_DEG_SUMS + HET_PAIR_SUMS == KT_HET_CENSUS, "the census layout");
+
+struct HetArgs {
+    kttab::Probed probed;       // the table itself
+    uint32_t lo, hi;            // the solid range
+    uint32_t k, p_lo, p_hi;     // the positions [p_lo, p_hi): 0..k, or the middle one
+    uint64_t *nodes;            // the nodes' keys, room for every entry of the table
+    uint64_t *n_nodes;          // their cursor
+    uint64_t *cand_a, *cand_b;  // the candidates (F, n1), room for every entry of the table
+    uint64_t *n_cand;           // their cursor
+    uint64_t *census;           // KT_HET_CENSUS cells, added into (null: no census)
+};
+
+struct HetScan {
+    uint64_t n1;       // the first solid neighbour
+    bool have, multi;  // n1 is set; a solid neighbour other than n1 was seen
+};
+
+// the solid neighbours of node F, into `s` (stops at s.multi)
+__device__ __forceinline__ void het_scan(const HetArgs &h, uint64_t F, HetScan &s) {
+    const uint64_t R = ktd::rev_comp(F, (int)h.k);
+    const uint32_t top = 2u * h.k - 2u;  // where a k-mer's first base sits (<= 60)
+    for (uint32_t i0 = h.p_lo; i0 < h.p_hi && !s.multi; i0 += HET_POS) {
+        uint64_t key[HET_KEYS];
+        uint32_t want = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < HET_POS; j++) {
+            const bool in = i0 + j < h.p_hi;
+            const uint32_t sr = in ? 2u * (i0 + j) : 0u, sf = top - sr;  // position i in R's word and in F's
+#pragma unroll
+            for (uint32_t d = 1; d <= 3u; d++) {
+                const uint64_t f = F ^ ((uint64_t)d << sf), r = R ^ ((uint64_t)d << sr);
+                const uint64_t c = f < r ? f : r;
+                key[3u * j + d - 1u] = c;
+                want |= (in && c != F ? 1u : 0u) << (3u * j + d - 1u);
+            }
+        }
+        h.probed.counts(key, want, [&](uint32_t u, uint32_t c) {
+            if (c >= h.lo && c <= h.hi) {
+                if (!s.have) s.n1 = key[u], s.have = true;
+                else if (key[u] != s.n1) s.multi = true;
+            }
+        });
+    }
+}
+
+// the lanes' tallies v[M] into the caller's cells: one wave reduction each, the workgroup's sums in LDS (zeroed, M cells),
+// one global atomic per non-zero cell.  Every thread of the workgroup must be here.
+template <uint32_t M>
+__device__ __forceinline__ void het_add_sums(uint64_t (&v)[M], unsigned long long *sums, uint64_t *cells) {
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (uint32_t j = 0; j < M; j++) v[j] += __shfl_down(v[j], o, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < M; j++)
+            if (v[j]) atomicAdd(&sums[j], (unsigned long long)v[j]);
+    }
+    ktd::lds_barrier();
+    if (threadIdx.x < M)
+        if (const unsigned long long t = sums[threadIdx.x]) atomicAdd(reinterpret_cast<unsigned long long *>(cells + threadIdx.x), t);
+}
+
+// w: the table's view, FORM = its form
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void het_nodes_kernel(TableView w, HetArgs h) {
+    __shared__ SetShared sm;
+    __shared__ unsigned long long sums[HET_NODE_SUMS];
+    if (threadIdx.x < HET_NODE_SUMS) sums[threadIdx.x] = 0ull;
+    ktd::lds_barrier();
+    uint32_t n = 0, step = 0;
+    uint64_t occ = 0;
+    walk_entries<FORM, HET_UNROLL, true>(w, [&](const uint64_t (&key)[HET_UNROLL], const uint32_t (&cw)[HET_UNROLL]) {
+        uint32_t keep = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < HET_UNROLL; u++) {
+            if (key[u] != KT_EMPTY_KEY && cw[u] >= h.lo && cw[u] <= h.hi) {
+                keep |= 1u << u;
+                n++;
+                occ += cw[u];
+            }
+        }
+        // (the nodes' room is the table's entries: every position is inside it)
+        tile_emit<HET_UNROLL>(h.n_nodes, keep, sm, step, [&](uint32_t u, uint64_t pos) { h.nodes[pos] = key[u]; });
+    });
+    if (!h.census) return;
+    uint64_t v[HET_NODE_SUMS] = {n, occ};
+    het_add_sums(v, sums, h.census);
+}
+
+// one lane per node, grid-stride by workgroup tiles; *h.n_nodes is het_nodes_kernel's
+__global__ __launch_bounds__(BLOCK) void het_scan_kernel(HetArgs h) {
+    __shared__ SetShared sm;
+    __shared__ unsigned long long sums[HET_DEG_SUMS];
+    if (threadIdx.x < HET_DEG_SUMS) sums[threadIdx.x] = 0ull;
+    ktd::lds_barrier();
+    const uint64_t n = *h.n_nodes;  // (the same for every thread: the loop is uniform, all reach the emit's barriers)
+    uint32_t d0 = 0, d1 = 0, d2 = 0, step = 0;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK; i0 < n; i0 += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint64_t F = 0ull;
+        HetScan s{0ull, false, false};
+        uint32_t keep = 0;
+        if (i < n) {
+            F = h.nodes[i];
+            het_scan(h, F, s);
+            d0 += !s.have;
+            d1 += s.have && !s.multi;
+            d2 += s.multi;
+            keep = s.have && !s.multi && F < s.n1 ? 1u : 0u;
+        }
+        // (the candidates' room is the table's entries: every position is inside it)
+        tile_emit<1>(h.n_cand, keep, sm, step, [&](uint32_t, uint64_t pos) {
+            h.cand_a[pos] = F;
+            h.cand_b[pos] = s.n1;
+        });
+    }
+    if (!h.census) return;
+    uint64_t v[HET_DEG_SUMS] = {d0, d1, d2};
+    het_add_sums(v, sums, h.census + HET_NODE_SUMS);
+}
+
+struct HetOut {
+    uint64_t *keys_a, *keys_b;  // the pairs, a < b
+    uint32_t *index;            // index[pos] = pos, for the sort to carry (null: unsorted)
+    uint64_t max_out;
+    uint64_t *cursor;           // pairs so far
+    uint64_t *matrix;           // n_rows x n_cols, added into (null: no matrix)
+    uint32_t n_rows, n_cols;
+};
+
+// one lane per candidate, grid-stride by workgroup tiles; *h.n_cand is het_scan_kernel's
+__global__ __launch_bounds__(BLOCK) void het_verify_kernel(HetArgs h, HetOut o) {
+    __shared__ SetShared sm;
+    __shared__ unsigned long long sums[HET_PAIR_SUMS];
+    if (threadIdx.x < HET_PAIR_SUMS) sums[threadIdx.x] = 0ull;
+    ktd::lds_barrier();
+    const uint64_t n = *h.n_cand;  // (the same for every thread: the loop is uniform, all reach the emit's barriers)
+    uint64_t pairs = 0, minor = 0, major = 0;
+    uint32_t step = 0;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK; i0 < n; i0 += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint64_t ab[2] = {0ull, 0ull};
+        uint32_t keep = 0;
+        if (i < n) {
+            ab[0] = h.cand_a[i], ab[1] = h.cand_b[i];
+            HetScan s{ab[0], true, false};
+            het_scan(h, ab[1], s);
+            if (!s.multi) {
+                uint32_t c[2] = {0u, 0u};
+                h.probed.counts(ab, 3u, [&](uint32_t u, uint32_t cc) { c[u] = cc; });
+                const uint32_t mn = c[0] < c[1] ? c[0] : c[1], mx = c[0] < c[1] ? c[1] : c[0];
+                keep = 1u;
+                pairs++;
+                minor += mn;
+                major += mx;
+                if (o.matrix) {
+                    const uint32_t r = mn < o.n_rows - 1u ? mn : o.n_rows - 1u, cl = mx < o.n_cols - 1u ? mx : o.n_cols - 1u;
+                    atomicAdd(reinterpret_cast<unsigned long long *>(o.matrix + (uint64_t)r * o.n_cols + cl), 1ull);
+                }
+            }
+        }
+        tile_emit<1>(o.cursor, keep, sm, step, [&](uint32_t, uint64_t pos) {
+            if (pos < o.max_out) {
+                o.keys_a[pos] = ab[0];
+                o.keys_b[pos] = ab[1];
+                if (o.index) o.index[pos] = (uint32_t)pos;
+            }
+        });
+    }
+    if (!h.census) return;
+    uint64_t v[HET_PAIR_SUMS] = {pairs, minor, major};
+    het_add_sums(v, sums, h.census + HET_NODE_SUMS + HET_DEG_SUMS);
+}
+
+// dst[i] = src[index[i]]: the second keys follow the sort of the first
+__global__ __launch_bounds__(BLOCK) void het_gather_kernel(const uint64_t *__restrict__ src, const uint32_t *__restrict__ index,
+                                                           uint64_t n, uint64_t *__restrict__ dst) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) dst[i] = src[index[i]];
 }
 
 __global__ __launch_bounds__(BLOCK) void route_count_kernel(SegArgs a, uint32_t n_owners,
@@ -1596,6 +1822,106 @@ extern "C" int kt_ctr_graph(kt_ctr *table, uint32_t min_count, uint32_t max_coun
     }
     if (int rc = call.finish()) return rc;
     if (max_out && n > max_out) return call.fail("max_out smaller than the result (*n_out nodes)");
+    return KT_OK;
+}
+
+extern "C" int kt_ctr_hetmers(kt_ctr *table, uint32_t min_count, uint32_t max_count, int positions, uint64_t *keys_a,
+                              uint64_t *keys_b, uint32_t *counts_a, uint32_t *counts_b, uint64_t max_out, uint64_t *n_out,
+                              uint64_t *matrix, uint32_t n_rows, uint32_t n_cols, uint64_t *census, int mem, int sorted) {
+    if (!table || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_hetmers: null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, mem, "kt_ctr_hetmers");
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (min_count == 0) return call.fail("min_count must be >= 1");
+    if (min_count > max_count) return call.fail("min_count > max_count");
+    if (positions != KT_HET_ALL && positions != KT_HET_MIDDLE) return call.fail("unknown positions");
+    if (positions == KT_HET_MIDDLE && table->k % 2 == 0) return call.fail("KT_HET_MIDDLE needs an odd k");
+    if (matrix) {
+        if (n_rows < 2 || n_cols < 2) return call.fail("n_rows and n_cols must be >= 2");
+        if ((uint64_t)n_rows * n_cols > (1ull << 24)) return call.fail("n_rows * n_cols must be <= 2^24");
+    }
+    if (int rc = call.enter()) return rc;
+    if (max_out && (!keys_a || !keys_b)) return call.fail("null output");
+    uint64_t n_t = 0;
+    if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    // every node is in at most one pair, and the sort carries a pair's index as its u32 payload
+    const bool sort = sorted && max_out;
+    if (sort && n_t / 2 > 0xFFFFFFFFull) return call.fail("a table of 2^33 entries or more cannot be sorted");
+    *n_out = 0;
+    if (!n_t) return KT_OK;
+    // the table is probed: its probing image first; its form is read only after that (it is walked as it is now)
+    if (int rc = table_ready(table)) return rc;
+    // scratch - BASES: the nodes' keys | the candidates' two keys; OFFSETS: the two cursors | sorted: the second keys before
+    // the gather | the index; host: this call's results - AUX1: keys_a | keys_b | census | matrix, AUX2: counts_a | counts_b
+    const uint64_t cells = matrix ? (uint64_t)n_rows * n_cols : 0;
+    uint64_t *nodes = nullptr, *words = nullptr;
+    if (int rc = call.scratch(kt::BASES, n_t * 24, &nodes)) return rc;
+    if (int rc = call.scratch(kt::OFFSETS, 16 + (sort ? max_out * 12 : 0), &words)) return rc;
+    uint64_t *n_cand = words, *n_nodes = words + 1, *b_unsorted = words + 2;
+    uint32_t *index = sort ? reinterpret_cast<uint32_t *>(b_unsorted + max_out) : nullptr;
+    uint64_t *d_a = keys_a, *d_b = keys_b, *d_census = census, *d_matrix = matrix;
+    uint32_t *d_ca = counts_a, *d_cb = counts_b;
+    if (call.host()) {
+        if (int rc = call.scratch(kt::AUX1, (2 * max_out + KT_HET_CENSUS + cells) * 8, &d_a)) return rc;
+        d_b = d_a + max_out;
+        uint64_t *sums = d_b + max_out;
+        KT_HIP(hipMemsetAsync(sums, 0, (KT_HET_CENSUS + cells) * 8, ctx->stream));
+        d_census = census ? sums : nullptr;
+        d_matrix = matrix ? sums + KT_HET_CENSUS : nullptr;
+        if (max_out) {
+            if (int rc = call.scratch(kt::AUX2, max_out * 8, &d_ca)) return rc;
+            d_cb = counts_b ? d_ca + max_out : nullptr;
+            if (!counts_a) d_ca = nullptr;
+        }
+    }
+    uint64_t *cursor = table->cursor;
+    KT_HIP(hipMemsetAsync(cursor, 0, 8, ctx->stream));
+    KT_HIP(hipMemsetAsync(words, 0, 16, ctx->stream));
+    const uint32_t k = (uint32_t)table->k, mid = (k - 1u) / 2u;
+    const HetArgs h{probed_of(table), min_count, max_count, k, positions == KT_HET_MIDDLE ? mid : 0u,
+                    positions == KT_HET_MIDDLE ? mid + 1u : k, nodes, n_nodes, nodes + n_t, nodes + 2 * n_t, n_cand, d_census};
+    const TableWalk w = view_of(table, n_t);
+    if (int rc = launch_walk(ctx, w, w.v.n, (uint64_t)BLOCK * HET_UNROLL, [&](auto form, dim3 grid) {
+            hipLaunchKernelGGL(het_nodes_kernel<decltype(form)::value>, grid, dim3(BLOCK), 0, ctx->stream, w.v, h);
+        }))
+        return rc;
+    // (the nodes and the candidates are counted on the device only: the grid is the device's, whatever their number)
+    const dim3 grid(grid_for(ctx, (n_t + BLOCK - 1) / BLOCK, 4));
+    hipLaunchKernelGGL(het_scan_kernel, grid, dim3(BLOCK), 0, ctx->stream, h);
+    const HetOut o{d_a, sort ? b_unsorted : d_b, index, max_out, cursor, d_matrix, n_rows, n_cols};
+    hipLaunchKernelGGL(het_verify_kernel, grid, dim3(BLOCK), 0, ctx->stream, h, o);
+    KT_HIP(hipGetLastError());
+    uint64_t n = 0;
+    KT_HIP(hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KT_HIP(hipStreamSynchronize(ctx->stream));
+    *n_out = n;
+    const uint64_t written = n < max_out ? n : max_out;
+    if (sort && written) {
+        // (a result that did not fit is not a result: the caller repeats the call; its second keys still go to their array)
+        if (written == n)
+            if (int rc = kt_sort_pairs(ctx, d_a, index, n, 2u * k)) return rc;
+        hipLaunchKernelGGL(het_gather_kernel, dim3(grid_for(ctx, (written + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
+                           (const uint64_t *)b_unsorted, (const uint32_t *)index, written, d_b);
+        KT_HIP(hipGetLastError());
+    }
+    // the counts of the emitted keys, in the order they are left in: they need not ride through the sort
+    if (d_ca && written)
+        if (int rc = lookup_counts(table, d_a, written, d_ca)) return rc;
+    if (d_cb && written)
+        if (int rc = lookup_counts(table, d_b, written, d_cb)) return rc;
+    call.back(keys_a, (const uint64_t *)d_a, written);
+    call.back(keys_b, (const uint64_t *)d_b, written);
+    call.back(counts_a, (const uint32_t *)d_ca, written);
+    call.back(counts_b, (const uint32_t *)d_cb, written);
+    if (call.host() && (census || matrix)) {
+        std::unique_ptr<uint64_t[]> s;
+        if (int rc = call.fetch((const uint64_t *)(d_b + max_out), KT_HET_CENSUS + cells, &s)) return rc;
+        if (census)
+            for (int j = 0; j < KT_HET_CENSUS; j++) census[j] += s[j];
+        for (uint64_t i = 0; i < cells; i++) matrix[i] += s[KT_HET_CENSUS + i];
+    }
+    if (int rc = call.finish()) return rc;
+    if (max_out && n > max_out) return call.fail("max_out smaller than the result (*n_out pairs)");
     return KT_OK;
 }
 

@@ -138,6 +138,10 @@ GRAPH_CENSUS_NAMES = ("nodes", "occurrences", "degree_sum", "end_sides", "isolat
     "degree_%d_%d" % (dl, dr) for dl in range(5) for dr in range(5))
 
 
+# the cells of Counter.hetmers' census, in order (kt_ctr_hetmers)
+HET_CENSUS_NAMES = ("nodes", "occurrences", "degree_0", "degree_1", "degree_2_or_more", "pairs", "minor_sum", "major_sum")
+
+
 UNITIG_CIRCULAR = 1  # Counter.unitigs' flag bit (KT_UNITIG_CIRCULAR): the unitig is a cycle, linearised at its smallest k-mer
 
 
@@ -769,6 +773,45 @@ class Counter:
         n = C.c_uint64()
         check(_lib.lib().kt_ctr_graph(self._h, int(min_count), hi, _ptr(keys), _ptr(info), _ptr(counts), int(max_out),
                                       C.byref(n), _ptr(census), KT_MEM_DEVICE, int(bool(sort))))
+        return n.value
+
+    def hetmers(self, min_count=1, max_count=None, middle=False, sort=True, matrix=None, census=False):
+        """The heterozygous k-mer pairs of the table (Smudgeplot's hetkmers): the pairs {a, b} of k-mers with min_count <=
+        count <= max_count (None: no upper bound) that differ in exactly one base - any base, or with middle=True (odd k)
+        the middle one - and have no other such partner, as numpy (keys_a u64, keys_b u64, counts_a u32, counts_b u32),
+        a < b as canonical words, ascending by a with sort.  matrix=(n_rows, n_cols): also the u64 matrix m[r, c] = pairs
+        with min(minor count, n_rows - 1) == r and min(major count, n_cols - 1) == c.  census=True: also the KT_HET_CENSUS
+        u64 cells named by HET_CENSUS_NAMES.  A count-only call, which fills matrix and census, then one call sized by it
+        (kt_ctr_hetmers)."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        pos = _lib.KT_HET_MIDDLE if middle else _lib.KT_HET_ALL
+        n = C.c_uint64()
+        cen = np.zeros(_lib.KT_HET_CENSUS, np.uint64)
+        n_rows, n_cols = (int(matrix[0]), int(matrix[1])) if matrix is not None else (0, 0)
+        m = np.zeros((n_rows, n_cols), np.uint64) if matrix is not None else None
+        check(_lib.lib().kt_ctr_hetmers(self._h, int(min_count), hi, pos, None, None, None, None, 0, C.byref(n), _ptr(m),
+                                        n_rows, n_cols, _ptr(cen), KT_MEM_HOST, 0))
+        keys_a, keys_b = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        counts_a, counts_b = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        if n.value:
+            check(_lib.lib().kt_ctr_hetmers(self._h, int(min_count), hi, pos, _ptr(keys_a), _ptr(keys_b), _ptr(counts_a),
+                                            _ptr(counts_b), n.value, C.byref(n), None, 0, 0, None, KT_MEM_HOST, int(bool(sort))))
+        out = (keys_a, keys_b, counts_a, counts_b)
+        if matrix is not None:
+            out += (m,)
+        return out + (cen,) if census else out
+
+    def hetmers_device(self, keys_a, keys_b, counts_a, counts_b, max_out, min_count=1, max_count=None, middle=False, sort=True,
+                       matrix=None, n_rows=0, n_cols=0, census=None):
+        """hetmers into device tensors of max_out entries (keys u64 / counts u32 bit patterns; either counts may be None;
+        None, None, None, None, 0 only counts the pairs) and, added, into `matrix` (n_rows x n_cols u64 on the device, or
+        None) and `census` (KT_HET_CENSUS u64 on the device, or None); returns the number of pairs.  Raises KmertoolsError
+        (KT_ERR_ARG) when 0 < max_out < that number."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        n = C.c_uint64()
+        check(_lib.lib().kt_ctr_hetmers(self._h, int(min_count), hi, _lib.KT_HET_MIDDLE if middle else _lib.KT_HET_ALL,
+                                        _ptr(keys_a), _ptr(keys_b), _ptr(counts_a), _ptr(counts_b), int(max_out), C.byref(n),
+                                        _ptr(matrix), int(n_rows), int(n_cols), _ptr(census), KT_MEM_DEVICE, int(bool(sort))))
         return n.value
 
     def unitigs(self, min_count=1, max_count=None):
