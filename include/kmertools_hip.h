@@ -41,6 +41,7 @@ extern "C" {
 #define KT_ERR_FULL 4     /* k-mer table ran out of slots (raise capacity) */
 #define KT_ERR_NODEVICE 5 /* no usable gfx950 device */
 #define KT_ERR_BADNT 6    /* kt_cgr_points: a byte outside ACGTUacgtu ("Bad nucleotide, unable to proceed") */
+#define KT_ERR_IO 7       /* table files: an unreadable, unwritable or malformed file; message names what was wrong */
 
 #define KT_MEM_HOST 0
 #define KT_MEM_DEVICE 1
@@ -559,6 +560,48 @@ int kt_ctr_simplify(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint3
  * having built the table in its own slots: nothing is lost - kt_ctr_size, kt_ctr_export into arrays of that size, further
  * adds all work - and the target arrays hold nothing usable (they are never written past max_out). */
 int kt_ctr_export_target(kt_ctr *ctr, uint64_t *keys_dev, uint32_t *counts_dev, uint64_t max_out);
+
+/* ---- table files ("ktab" version 1, DESIGN.md, Table files): a counted table on disk (KMC databases, jellyfish .jf, meryl) ----
+ * No reference counterpart: the reference writes text (counter/src/lib.rs:220-230) and reads nothing back.
+ * A file is a 16-byte header ("KTAB", u32 version, u32 k, u32 0) and one or more SECTIONS up to its end; a section is a
+ * sorted run of (canonical key, count) entries: a 32-byte header ("KSEC", u32 S, u64 n, u64 n_overflow, u64 occurrences)
+ * and, with P = max(0, 2k - 8S), u64 offsets[2^P + 1], n * S suffix bytes, n count bytes (255 = the next value of the
+ * overflow list), n_overflow * u32, padding to 8 bytes.  A key may appear in several sections; on load its counts add. */
+
+/* Host only (no context, no GPU): the file's k, its sections and the sums of their headers' entries and occurrences
+ * (any of the four may be NULL).  Checks the file header, the chain of section headers and every section's length against
+ * the file's size.  KT_ERR_ARG: a null path; KT_ERR_IO: unreadable or malformed, kt_last_error() names the first thing
+ * that was wrong. */
+int kt_table_file_info(const char *path, int *k, uint64_t *sections, uint64_t *entries, uint64_t *occurrences);
+
+/* Host only: the full structural validation - what kt_table_file_info checks, S in 1..8 and P <= 24, n_overflow <= n,
+ * nothing behind the last section, and every section's offsets[]: offsets[0] == 0, never decreasing, none above n, the
+ * last one == n.  Everything a kernel could index by; the content (keys ascending, canonical and below 4^k, count bytes,
+ * overflow values, the sums) is validated on the device by kt_ctr_add_file.  Reads the offsets in pieces of 8 MiB. */
+int kt_table_file_check(const char *path);
+
+/* Writes the table's entries with min_count <= count <= max_count as ONE section: creates the file (written under a
+ * temporary name beside it and renamed into place), or with append != 0 and an existing file adds a section to it (the
+ * file must be a whole table file of the table's k; a failure truncates it back to what it was).  No error leaves a partial
+ * section behind.  The entries are staged as by kt_ctr_export_stage_range (what was staged before is replaced), copied,
+ * sorted and packed on the device; the parts cross to the host through two page-locked slabs of 8 MiB.  For a given k the section's bytes are
+ * a function of the set of (key, count) alone: not of the table's form, capacity or history.  The table's content is not
+ * changed, in whatever form it is (probing image, dense after a bulk build, counted into an export target, direct).
+ * *n_saved (may be NULL) = the entries written; an empty selection writes an empty section.  Synchronises.
+ * KT_ERR_ARG: a null table or path, min_count > max_count, append to a file of another k; KT_ERR_FULL: an overflowed
+ * table; KT_ERR_IO: the file cannot be written (or, with append, is not a valid table file).  Device scratch: 24 bytes
+ * per entry for the copy and its sort, S + 9 per entry and 8 * 2^P for the parts. */
+int kt_ctr_save(kt_ctr *table, const char *path, uint32_t min_count, uint32_t max_count, int append, uint64_t *n_saved);
+
+/* table[key] += count for every entry of every section of the file, section by section through kt_ctr_add_pairs on the
+ * device (so the table may hold entries already, and keys that several sections share add up).  kt_table_file_check runs
+ * before the first launch; each section's content is validated by the kernels that unpack it, with every index clamped: a
+ * bad file gives KT_ERR_IO, never an access out of bounds.  A section that fails adds nothing and ends the call; the
+ * sections before it stay added.  *n_added (may be NULL) = the entries of the sections added (not the growth of
+ * kt_ctr_size: keys the table held stay one entry).  Synchronises.  KT_ERR_ARG: a null table or path, a file of another
+ * k; KT_ERR_FULL as kt_ctr_add_pairs (seen by the next kt_ctr_size).  Device scratch: S + 17 bytes per entry of the
+ * largest section and 8 * 2^P. */
+int kt_ctr_add_file(kt_ctr *table, const char *path, uint64_t *n_added);
 
 /* replaces: CgrComputer::vectorise_one, composition/src/cgr.rs:127-144 (corners from cgr_maps,
  * :12-36) and python CgrComputer.vectorise_one/_batch, pybindings/src/cgr.rs:38-62.

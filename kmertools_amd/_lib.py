@@ -12,7 +12,7 @@ _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get("KT_LIB", _HERE / "libkmertools_hip.so"))  # KT_LIB: A/B builds
 
 KT_OK = 0
-KT_ERR_ARG, KT_ERR_HIP, KT_ERR_NOMEM, KT_ERR_FULL, KT_ERR_NODEVICE, KT_ERR_BADNT = 1, 2, 3, 4, 5, 6
+KT_ERR_ARG, KT_ERR_HIP, KT_ERR_NOMEM, KT_ERR_FULL, KT_ERR_NODEVICE, KT_ERR_BADNT, KT_ERR_IO = 1, 2, 3, 4, 5, 6, 7
 KT_MEM_HOST, KT_MEM_DEVICE = 0, 1
 KT_F64, KT_F32, KT_U32 = 0, 1, 2
 KT_EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
@@ -65,6 +65,10 @@ SYMBOLS = {
     "kt_ctr_export_stage": (_i, [_vp, C.POINTER(_u64)]),
     "kt_ctr_export_fetch": (_i, [_vp, _u64, _u64, _vp, _vp]),
     "kt_ctr_export_stage_range": (_i, [_vp, _u32, _u32, C.POINTER(_u64)]),
+    "kt_table_file_info": (_i, [C.c_char_p, C.POINTER(_i), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "kt_table_file_check": (_i, [C.c_char_p]),
+    "kt_ctr_save": (_i, [_vp, C.c_char_p, _u32, _u32, _i, C.POINTER(_u64)]),
+    "kt_ctr_add_file": (_i, [_vp, C.c_char_p, C.POINTER(_u64)]),
     "kt_ctr_spectrum": (_i, [_vp, _vp, _u32, _vp, _i]),
     "kt_ctr_compare": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _i]),
     "kt_ctr_setop": (_i, [_vp, _vp, _i, _i, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64), _i, _i]),

@@ -1014,6 +1014,36 @@ static std::string create_tables(kt_ctx *ctx, int k, TablePlan &plan, kt_ctr **c
     }
 }
 
+// ---- --table FILE: a table file (kt_ctr_save) in place of counting (every command that makes one table) ---------------------------------------------------------
+// The table of a table file: planned from the file's headers (1.9 slots per entry, as every plan), created, loaded.  The
+// file must fit the device in one pass - loading in hash-partition passes is not built.
+static std::string table_from_file(Device &dev, const std::string &path, int k, uint64_t bytes_per_slot, const char *name, kt_ctr **table) {
+    Lap setup;
+    int fk = 0;
+    uint64_t sections = 0, entries = 0;
+    if (kt_table_file_info(path.c_str(), &fk, &sections, &entries, nullptr) != KT_OK) return kt_last_error();
+    if (fk != k) return "--table " + path + " holds k = " + std::to_string(fk) + ", not " + std::to_string(k);
+    if (std::string e = dev.ensure(); !e.empty()) return e;
+    TablePlan plan;
+    plan.want[0] = std::max<uint64_t>(1024, entries + entries / 10 * 9);
+    plan.plan(dev.ctx, bytes_per_slot, false);
+    const std::string no_fit = std::string(name) + ": the table file does not fit the device in one pass, and table files are not loaded in "
+                               "several passes (" + std::to_string(entries) + " entries want " + std::to_string(plan.want[0]) + " slots, room for ";
+    if (plan.passes > 1) return no_fit + std::to_string(plan.room) + ")";
+    if (const int rc = kt_ctr_create(dev.ctx, k, plan.want[0], table); rc != KT_OK)
+        return rc == KT_ERR_NOMEM ? no_fit + "fewer: " + kt_last_error() + ")" : std::string(kt_last_error());
+    const double t_setup = setup();
+    uint64_t added = 0;
+    if (kt_ctr_add_file(*table, path.c_str(), &added) != KT_OK) return kt_last_error();
+    if (getenv("KT_CLI_TIMING")) {
+        uint64_t slots = plan.want[0];
+        (void)kt_ctr_capacity(*table, &slots);
+        fprintf(stderr, "[timing] %s table file: table of %llu slots %.3f s, %llu section(s) with %llu entries loaded %.3f s\n", name,
+                (unsigned long long)slots, t_setup, (unsigned long long)sections, (unsigned long long)added, setup());
+    }
+    return "";
+}
+
 // One walk over an input into a table: add(b) is the library's call (kt_ctr_add_reads, kt_ctr_add_reads_part); a batch
 // whose reads have no bases is not passed on.
 template <class Add>
@@ -1029,6 +1059,12 @@ std::string CountComputer::count() {
     // init(): pre-pass for record count and total length (counter/src/lib.rs:236-249); here it
     // sizes the HBM table instead of the reference's partition count
     Lap setup;
+    if (input_is_table_) {  // --table: nothing is counted; the file must fit in one pass on one device
+        if (ctr_) kt_ctr_destroy(ctr_);
+        ctr_ = nullptr;
+        passes_ = 1;
+        return table_from_file(dev_, in_path_, ksize_, 16, "table", &ctr_);
+    }
     if (in_path_ == "-") return "ctr reads its input more than once and cannot take stdin";  // (the reference panics
                                                                                             // on SeqFormat::get("-"))
     InputBound in;
@@ -1065,6 +1101,10 @@ std::string CountComputer::count() {
     TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
     writer.set_range(min_count_, max_count_);
     uint64_t heap_after_first = 0, rss_after_first = 0;
+    struct Partial {  // --save-table out of core: removed unless the run gets to rename it
+        std::string path;
+        ~Partial() { if (!path.empty()) unlink(path.c_str()); }
+    } partial;
     for (uint32_t pass = 0; pass < passes_; pass++) {
         if (pass && !reader.rewind()) return reader.error();
         Lap lap;
@@ -1087,6 +1127,10 @@ std::string CountComputer::count() {
             if (!out) return "Unable to write to file: " + path;
             if (std::string e = writer.write(out, ctr_, &n_pass); !e.empty()) return e;
         }
+        if (!save_table_.empty()) {  // one section per pass (a k-mer lives in one partition), under a name of its own until
+            partial.path = save_table_ + ".partial";  // the last pass is in: a run that fails leaves no file that looks whole
+            if (std::string e = save_table(ctr_, partial.path, pass != 0); !e.empty()) return e;
+        }
         pt.t[3] += lap();
         if (timing) {
             // the ceiling's books, per pass: the program's own buffers by their capacities, the allocator's total, and
@@ -1104,6 +1148,10 @@ std::string CountComputer::count() {
         if (kt_ctr_clear(ctr_) != KT_OK) return kt_last_error();
     }
     if (out) fclose(out);
+    if (!partial.path.empty()) {
+        if (rename(partial.path.c_str(), save_table_.c_str()) != 0) return "Unable to write to file: " + save_table_;
+        partial.path.clear();
+    }
     if (timing && passes_ > 1) {
         const MemReport r = mem_report();
         fprintf(stderr, "[timing] ctr out of core: %u passes, slabs of %llu entries, malloc peak at a slab boundary %llu kB, growth since the end "
@@ -1271,6 +1319,16 @@ std::string CountComputer::count_sharded(uint64_t max_distinct) {
     return err;
 }
 
+// --save-table: the table's entries in the count range as one section of the table file
+std::string CountComputer::save_table(kt_ctr *t, const std::string &path, bool append) {
+    Lap lap;
+    uint64_t n = 0;
+    if (kt_ctr_save(t, path.c_str(), min_count_, max_count_, append ? 1 : 0, &n) != KT_OK) return kt_last_error();
+    if (getenv("KT_CLI_TIMING"))
+        fprintf(stderr, "[timing] ctr --save-table: section of %llu entries %s %.3f s\n", (unsigned long long)n, append ? "appended" : "written", lap());
+    return "";
+}
+
 std::string CountComputer::merge(bool /*del: no temp files exist to delete*/) {
     // out of core: count() wrote every partition's lines as it completed (and summed their spectra)
     if (passes_ > 1) return histo_max_ ? write_histo() : "";
@@ -1300,6 +1358,8 @@ std::string CountComputer::merge(bool /*del: no temp files exist to delete*/) {
     if (!ctr_) return "count() has not run";
     PhaseTimer pt("ctr merge");
     Lap lap;
+    if (!save_table_.empty())
+        if (std::string e = save_table(ctr_, save_table_, false); !e.empty()) return e;
     if (histo_max_) {
         if (std::string e = add_spectrum(ctr_); !e.empty()) return e;
         if (std::string e = write_histo(); !e.empty()) return e;
@@ -1352,6 +1412,7 @@ std::string CovComputer::build_table() {
     ctr_->set_device(device_);
     ctr_->set_devices(n_devices_);
     ctr_->set_keep_shards(true);
+    ctr_->set_input_is_table(kmer_is_table_);
     ctr_->set_pass_hook([this](uint32_t pass, uint32_t passes, kt_ctr *t) { return cov_pass(pass, passes, t); });
     std::string e = ctr_->count();
     if (e.empty()) e = ctr_->merge(true);  // the reference leaves kmers.counts behind as well
@@ -1526,13 +1587,14 @@ void FilterComputer::emit(const Batch &b, const uint32_t *n, const uint32_t *s, 
 
 // the table a read-level command looks its k-mers up in: counted as by `ctr`, no kmers.histo and no kmers.counts, `hook`
 // for every complete pass of an out-of-core count
-static CountComputer *make_lookup_counter(const std::string &in, int k, int threads, double memory_ceil_gb, int device,
+static CountComputer *make_lookup_counter(const std::string &in, bool in_is_table, int k, int threads, double memory_ceil_gb, int device,
                                           std::function<std::string(uint32_t, uint32_t, kt_ctr *)> hook) {
     CountComputer *c = new CountComputer(in, ".", k);
     c->set_threads(threads);
     c->set_max_memory(memory_ceil_gb);
     c->set_device(device);
     c->set_histo(0, true);
+    c->set_input_is_table(in_is_table);
     c->set_pass_hook(std::move(hook));
     return c;
 }
@@ -1543,7 +1605,7 @@ std::string FilterComputer::filter() {
     acc_s_.clear();
     acc_w_.clear();
     kept_.seen = Cursor();
-    ctr_ = make_lookup_counter(in_path_kmer_, ksize_, threads_, memory_ceil_gb_, device_,
+    ctr_ = make_lookup_counter(in_path_kmer_, kmer_is_table_, ksize_, threads_, memory_ceil_gb_, device_,
                                [this](uint32_t pass, uint32_t passes, kt_ctr *t) { return filter_pass(pass, passes, t); });
     if (std::string e = ctr_->count(); !e.empty()) return e;
     const bool resident = ctr_->passes() == 1;  // else: the numbers were combined pass by pass (filter_pass)
@@ -1624,7 +1686,7 @@ std::string ProfileComputer::profile() {
     acc_.clear();
     acc_.shrink_to_fit();
     kept_.seen = Cursor();
-    ctr_ = make_lookup_counter(in_path_kmer_, ksize_, threads_, memory_ceil_gb_, device_,
+    ctr_ = make_lookup_counter(in_path_kmer_, kmer_is_table_, ksize_, threads_, memory_ceil_gb_, device_,
                                [this](uint32_t pass, uint32_t passes, kt_ctr *t) { return profile_pass(pass, passes, t); });
     if (std::string e = ctr_->count(); !e.empty()) return e;
     const bool resident = ctr_->passes() == 1;  // else: the positions were filled pass by pass (profile_pass)
@@ -1747,7 +1809,7 @@ std::string CorrectComputer::table_pass(bool support, uint32_t pass, uint32_t pa
 }
 
 CountComputer *CorrectComputer::new_counter(bool support) {
-    return make_lookup_counter(in_path_kmer_, ksize_, threads_, memory_ceil_gb_, device_, [this, support](uint32_t pass, uint32_t passes, kt_ctr *t) {
+    return make_lookup_counter(in_path_kmer_, kmer_is_table_, ksize_, threads_, memory_ceil_gb_, device_, [this, support](uint32_t pass, uint32_t passes, kt_ctr *t) {
         return table_pass(support, pass, passes, t);
     });
 }
@@ -1877,17 +1939,34 @@ std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_
 
 // What `compare` and `setop` share: both tables of a pass on one device, `bytes_per_slot` of HBM for every slot of either
 // (16: the slot itself), pass p holding hash partition p of both.  Creates the tables; on an error none is left.
-static std::string two_tables_setup(Device &dev, const std::string &in_a, const std::string &in_b, int k, uint64_t bytes_per_slot,
-                                    const char *what, uint32_t *passes, kt_ctr **ta, kt_ctr **tb) {
+// A side that is a table file (a_is_table / b_is_table: the path is the file's) is sized from the file's headers and must be
+// loaded whole: with such a side a plan of several passes is refused.
+static std::string two_tables_setup(Device &dev, const std::string &in_a, bool a_is_table, const std::string &in_b, bool b_is_table, int k,
+                                    uint64_t bytes_per_slot, const char *what, uint32_t *passes, kt_ctr **ta, kt_ctr **tb) {
     Lap setup;
     InputBound a, b;
-    if (std::string e = slots_wanted(in_a, k, &a, dev); !e.empty()) return e;
-    if (std::string e = slots_wanted(in_b, k, &b, dev); !e.empty()) return e;
+    uint64_t file_entries = 0;
+    for (auto [path, is_table, in] : {std::make_tuple(&in_a, a_is_table, &a), std::make_tuple(&in_b, b_is_table, &b)}) {
+        if (!is_table) {
+            if (std::string e = slots_wanted(*path, k, in, dev); !e.empty()) return e;
+            continue;
+        }
+        int fk = 0;
+        uint64_t entries = 0;
+        if (kt_table_file_info(path->c_str(), &fk, nullptr, &entries, nullptr) != KT_OK) return kt_last_error();
+        if (fk != k) return "the table file " + *path + " holds k = " + std::to_string(fk) + ", not " + std::to_string(k);
+        in->want = std::max<uint64_t>(1024, entries + entries / 10 * 9);
+        file_entries += entries;
+    }
     if (std::string e = dev.ensure(); !e.empty()) return e;
     TablePlan plan;
     plan.n = 2;
     plan.want[0] = a.want, plan.want[1] = b.want;
     plan.plan(dev.ctx, bytes_per_slot, false);
+    if ((a_is_table || b_is_table) && plan.passes > 1)
+        return std::string(what) + ": the table file does not fit the device in one pass beside the other table, and table files are not "
+               "loaded in several passes (" + std::to_string(file_entries) + " entries in table files, " + std::to_string(a.want + b.want) +
+               " slots wanted, room for " + std::to_string(plan.room) + ")";
     kt_ctr **const tables[2] = {ta, tb};
     if (std::string e = create_tables(dev.ctx, k, plan, tables); !e.empty()) return e;
     *passes = plan.passes;
@@ -1902,10 +1981,19 @@ static std::string two_tables_setup(Device &dev, const std::string &in_a, const 
 }
 
 // pass `pass` of `passes`: both tables cleared (after the first pass) and filled with their inputs' hash partition
-static std::string two_tables_count(uint32_t pass, uint32_t passes, SeqReader &ra, SeqReader &rb, kt_ctr *ta, kt_ctr *tb,
-                                    Batch &b, PhaseTimer &pt, Lap &lap) {
+// (a side whose reader was not opened is a table file, file_a / file_b: loaded whole - the plan has one pass then)
+static std::string two_tables_count(uint32_t pass, uint32_t passes, SeqReader &ra, SeqReader &rb, const std::string *file_a,
+                                    const std::string *file_b, kt_ctr *ta, kt_ctr *tb, Batch &b, PhaseTimer &pt, Lap &lap) {
     if (pass && (kt_ctr_clear(ta) != KT_OK || kt_ctr_clear(tb) != KT_OK)) return kt_last_error();
-    for (auto [reader, table] : {std::make_pair(&ra, ta), std::make_pair(&rb, tb)}) {
+    for (auto [reader, table, file] : {std::make_tuple(&ra, ta, file_a), std::make_tuple(&rb, tb, file_b)}) {
+        if (file) {
+            Lap load;
+            uint64_t added = 0;
+            if (kt_ctr_add_file(table, file->c_str(), &added) != KT_OK) return kt_last_error();
+            if (getenv("KT_CLI_TIMING"))
+                fprintf(stderr, "[timing] table file: %llu entries loaded %.3f s\n", (unsigned long long)added, load());
+            continue;
+        }
         if (pass && !reader->rewind()) return reader->error();
         kt_ctr *t = table;  // (a structured binding cannot be captured)
         if (std::string e = fill_table(*reader, b, pt, lap, [&](const Batch &bb) {
@@ -1919,18 +2007,18 @@ static std::string two_tables_count(uint32_t pass, uint32_t passes, SeqReader &r
 
 std::string CompareComputer::compare() {
     release();
-    if (std::string e = two_tables_setup(dev_, in_a_, in_b_, ksize_, 16, "compare", &passes_, &ta_, &tb_); !e.empty()) return e;
+    if (std::string e = two_tables_setup(dev_, in_a_, a_is_table_, in_b_, b_is_table_, ksize_, 16, "compare", &passes_, &ta_, &tb_); !e.empty()) return e;
     const uint32_t R = max_a_ + 1, C = max_b_ + 1;
     std::vector<uint64_t> m((size_t)R * C, 0);
     uint64_t tot[6] = {0, 0, 0, 0, 0, 0};
     PhaseTimer pt("compare");
     SeqReader ra, rb;
-    if (!ra.open(in_a_, false)) return ra.error();
-    if (!rb.open(in_b_, false)) return rb.error();
+    if (!a_is_table_ && !ra.open(in_a_, false)) return ra.error();
+    if (!b_is_table_ && !rb.open(in_b_, false)) return rb.error();
     Batch b;
     for (uint32_t pass = 0; pass < passes_; pass++) {
         Lap lap;
-        if (std::string e = two_tables_count(pass, passes_, ra, rb, ta_, tb_, b, pt, lap); !e.empty()) return e;
+        if (std::string e = two_tables_count(pass, passes_, ra, rb, a_is_table_ ? &in_a_ : nullptr, b_is_table_ ? &in_b_ : nullptr, ta_, tb_, b, pt, lap); !e.empty()) return e;
         if (kt_ctr_compare(ta_, tb_, m.data(), R, C, tot, KT_MEM_HOST) != KT_OK) return kt_last_error();
         pt.t[1] += lap();
     }
@@ -1956,7 +2044,7 @@ std::string SetopComputer::setop() {
     release();
     // HBM per slot: the slot (16) + its share of the result and of the sort's second pair - at most every entry of both
     // tables, 12 bytes, twice, with 1.9 slots per entry: 24 / 1.9 < 13
-    if (std::string e = two_tables_setup(dev_, in_a_, in_b_, ksize_, 16 + 13, "setop", &passes_, &ta_, &tb_); !e.empty()) return e;
+    if (std::string e = two_tables_setup(dev_, in_a_, a_is_table_, in_b_, b_is_table_, ksize_, 16 + 13, "setop", &passes_, &ta_, &tb_); !e.empty()) return e;
     const std::string cpath = out_dir_ + "/kmers.counts", spath = out_dir_ + "/setop.stats";
     FILE *out = fopen(cpath.c_str(), "wb");
     if (!out) return "Unable to write to file: " + cpath;
@@ -1973,13 +2061,13 @@ std::string SetopComputer::setop() {
     std::vector<uint32_t> counts;
     PhaseTimer pt("setop");
     SeqReader ra, rb;
-    if (!ra.open(in_a_, false)) return ra.error();
-    if (!rb.open(in_b_, false)) return rb.error();
+    if (!a_is_table_ && !ra.open(in_a_, false)) return ra.error();
+    if (!b_is_table_ && !rb.open(in_b_, false)) return rb.error();
     Batch b;
     const bool plain_a = min_a_ == 1 && max_a_ == 0xFFFFFFFFu, plain_b = min_b_ == 1 && max_b_ == 0xFFFFFFFFu;
     for (uint32_t pass = 0; pass < passes_; pass++) {
         Lap lap;
-        if (std::string e = two_tables_count(pass, passes_, ra, rb, ta_, tb_, b, pt, lap); !e.empty()) return e;
+        if (std::string e = two_tables_count(pass, passes_, ra, rb, a_is_table_ ? &in_a_ : nullptr, b_is_table_ ? &in_b_ : nullptr, ta_, tb_, b, pt, lap); !e.empty()) return e;
         uint64_t n_a = 0, n_b = 0, in_a = 0, in_b = 0, n = 0;
         if (kt_ctr_size(ta_, &n_a) != KT_OK || kt_ctr_size(tb_, &n_b) != KT_OK) return kt_last_error();
         // what can qualify at most sizes the host arrays: one call, no counting call before it
@@ -2033,8 +2121,11 @@ static std::string graph_census_name(int j) {
 
 // What `graph` and `unitigs` share: one table, and the whole of it on the device - a plan of several passes is refused
 // before anything is counted or written.  whole_table plans and creates it (`name`: the command, in the texts - its
-// PhaseTimer starts only afterwards, so a refusal prints no phase line), fill_whole_table counts the input into it.
-static std::string whole_table(Device &dev, const std::string &path, int k, uint64_t bytes_per_slot, const char *name, kt_ctr **table) {
+// PhaseTimer starts only afterwards, so a refusal prints no phase line), fill_whole_table counts the input into it.  With
+// a table file whole_table loads the file instead (table_from_file) and the caller skips fill_whole_table.
+static std::string whole_table(Device &dev, const std::string &path, const std::string &table_file, int k, uint64_t bytes_per_slot,
+                               const char *name, kt_ctr **table) {
+    if (!table_file.empty()) return table_from_file(dev, table_file, k, bytes_per_slot, name, table);
     Lap setup;
     InputBound in;
     if (std::string e = slots_wanted(path, k, &in, dev); !e.empty()) return e;
@@ -2069,13 +2160,15 @@ std::string GraphComputer::graph() {
     table_ = nullptr;
     // HBM per slot: the slot (16) + its share of the result (key, info, count: 16 bytes a node) and of the sort's second
     // pair (12), with 1.9 slots per entry: 28 / 1.9 < 15
-    if (std::string e = whole_table(dev_, in_path_, ksize_, 16 + 15, "graph", &table_); !e.empty()) return e;
+    if (std::string e = whole_table(dev_, in_path_, table_file_, ksize_, 16 + 15, "graph", &table_); !e.empty()) return e;
     PhaseTimer pt("graph");
     SeqReader reader;
-    if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     Lap lap;
-    if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    if (table_file_.empty()) {  // (else whole_table loaded the file: there is nothing to count)
+        if (!reader.open(in_path_, false)) return reader.error();
+        if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    }
     // what can be a node at most sizes the host arrays: one call, no counting call before it
     uint64_t bound = 0, n = 0, census[KT_GRAPH_CENSUS] = {};
     if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
@@ -2133,13 +2226,15 @@ std::string HetmerComputer::hetmers() {
     table_ = nullptr;
     // HBM per slot: the slot (16) + its share of the nodes and candidates (24 bytes an entry), and of the result and the sort
     // (at most one pair per two entries: 24 + 12 + 12 bytes a pair), with 1.9 slots per entry: 48 / 1.9 < 26
-    if (std::string e = whole_table(dev_, in_path_, ksize_, 16 + 26, "hetmers", &table_); !e.empty()) return e;
+    if (std::string e = whole_table(dev_, in_path_, table_file_, ksize_, 16 + 26, "hetmers", &table_); !e.empty()) return e;
     PhaseTimer pt("hetmers");
     SeqReader reader;
-    if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     Lap lap;
-    if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    if (table_file_.empty()) {  // (else whole_table loaded the file: there is nothing to count)
+        if (!reader.open(in_path_, false)) return reader.error();
+        if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    }
     // every k-mer is in at most one pair: half the entries size the host arrays, one call, no counting call before it
     uint64_t bound = 0, n = 0, census[KT_HET_CENSUS] = {};
     if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
@@ -2244,13 +2339,15 @@ std::string UnitigComputer::unitigs() {
     // two link offsets in place of bases the run does not write (36), its class and mark (2) - the list of keys to erase (8 a
     // node) lies where the sort's keys lay, the erase's surviving pairs (12) where the nodes lay - and per slot one bit of the
     // erase's mask: 38 / 1.9 + 1 / 8 < 21.  Popping bubbles (kt_ctr_simplify) claims no more than that.
-    if (std::string e = whole_table(dev_, in_path_, ksize_, clip_ || pop_ ? 16 + 74 + 21 : 16 + 74, "unitigs", &table_); !e.empty()) return e;
+    if (std::string e = whole_table(dev_, in_path_, table_file_, ksize_, clip_ || pop_ ? 16 + 74 + 21 : 16 + 74, "unitigs", &table_); !e.empty()) return e;
     PhaseTimer pt("unitigs");
     SeqReader reader;
-    if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
     Lap lap;
-    if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    if (table_file_.empty()) {  // (else whole_table loaded the file: there is nothing to count)
+        if (!reader.open(in_path_, false)) return reader.error();
+        if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    }
     if (pop_) {  // the table is simplified in place, tips (with clip_) and bubbles in the same rounds
         uint64_t st[KT_SIMPLIFY_STATS] = {};
         if (kt_ctr_simplify(table_, min_count_, max_count_, clip_ ? tip_nodes_ : 0u, bubble_nodes_, clip_rounds_,

@@ -129,6 +129,10 @@ class CountComputer {
     // --histo-max H (--histo): merge() also writes {out_dir}/kmers.histo, the spectrum of the whole table in H lines (the
     // last: H or more occurrences); only = --histo-only: no kmers.counts at all
     void set_histo(uint32_t h, bool only) { histo_max_ = h, histo_only_ = only; }
+    // --save-table: the entries in the count range also go to this table file (kt_ctr_save), one section per pass
+    void set_save_table(const std::string &path) { save_table_ = path; }
+    // --table: the input path is a table file; count() loads it (one pass, one device) instead of counting reads
+    void set_input_is_table(bool on) { input_is_table_ = on; }
     // counter/src/lib.rs:69-90.  No temp files: one resident table - or, when the distinct k-mers cannot fit the HBM,
     // `passes()` passes over the input, one hash partition each, written to kmers.counts as they complete.
     std::string count();
@@ -159,6 +163,9 @@ class CountComputer {
     bool histo_only_ = false;
     std::vector<uint64_t> histo_;  // the spectrum, summed over passes / shards (histo_max_ + 1 bins)
     std::string add_spectrum(kt_ctr *t);
+    std::string save_table_;
+    bool input_is_table_ = false;
+    std::string save_table(kt_ctr *t, const std::string &path, bool append);
     std::string write_histo() const;
     // --devices N: the shards stay on their GPUs after count(); merge() writes them out one after the other, in slabs
     std::vector<kt_sharded *> shards_;
@@ -185,6 +192,8 @@ class CovComputer {
     void set_norm(bool n) { norm_ = n; }
     void set_delim(std::string d) { delim_ = std::move(d); }
     void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    // --table: the k-mer table is loaded from this table file (kt_ctr_add_file) instead of counted
+    void set_kmer_table(std::string p) { in_path_kmer_ = std::move(p), kmer_is_table_ = true; }
     void set_max_memory(double gb) { memory_ceil_gb_ = gb; }
     void set_device(int d) { device_ = d; }
     void set_devices(int n) { n_devices_ = n < 1 ? 1 : n; }  // --devices N: the table sharded over N GPUs, every read looked up in every shard
@@ -193,6 +202,7 @@ class CovComputer {
 
   private:
     std::string in_path_, in_path_kmer_, out_dir_, delim_ = " ";
+    bool kmer_is_table_ = false;
     int ksize_, threads_ = 0, device_ = 0, n_devices_ = 1;
     uint64_t bin_size_, bin_count_;
     bool norm_ = true;
@@ -224,6 +234,8 @@ class FilterComputer {
     FilterComputer(const FilterComputer &) = delete;
     FilterComputer &operator=(const FilterComputer &) = delete;
     void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    // --table: the k-mer table is loaded from this table file (kt_ctr_add_file) instead of counted
+    void set_kmer_table(std::string p) { in_path_kmer_ = std::move(p), kmer_is_table_ = true; }
     void set_count_range(uint32_t lo, uint32_t hi) { min_count_ = lo, max_count_ = hi; }
     void set_min_solid(double f) { min_solid_ = f; }
     void set_trim(bool t) { trim_ = t; }
@@ -234,6 +246,7 @@ class FilterComputer {
 
   private:
     std::string in_path_, in_path_kmer_, out_path_;
+    bool kmer_is_table_ = false;
     int ksize_, threads_ = 0, device_ = 0;
     uint32_t min_count_ = 2, max_count_ = 0xFFFFFFFFu;
     double min_solid_ = 1.0, memory_ceil_gb_ = 6.0;
@@ -262,6 +275,8 @@ class CorrectComputer {
     CorrectComputer(const CorrectComputer &) = delete;
     CorrectComputer &operator=(const CorrectComputer &) = delete;
     void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    // --table: the k-mer table is loaded from this table file (kt_ctr_add_file) instead of counted
+    void set_kmer_table(std::string p) { in_path_kmer_ = std::move(p), kmer_is_table_ = true; }
     void set_count_range(uint32_t lo, uint32_t hi) { min_count_ = lo, max_count_ = hi; }
     void set_min_support(uint32_t s) { min_support_ = s; }
     void set_max_corrections(uint32_t n) { max_corrections_ = n; }  // 0: no limit
@@ -273,6 +288,7 @@ class CorrectComputer {
 
   private:
     std::string in_path_, in_path_kmer_, out_path_, stats_path_;
+    bool kmer_is_table_ = false;
     int ksize_, threads_ = 0, device_ = 0;
     uint32_t min_count_ = 2, max_count_ = 0xFFFFFFFFu, min_support_ = 1, max_corrections_ = 0;
     double memory_ceil_gb_ = 6.0;
@@ -300,6 +316,8 @@ class ProfileComputer {
     ProfileComputer(const ProfileComputer &) = delete;
     ProfileComputer &operator=(const ProfileComputer &) = delete;
     void set_kmer_path(std::string p) { in_path_kmer_ = std::move(p); }
+    // --table: the k-mer table is loaded from this table file (kt_ctr_add_file) instead of counted
+    void set_kmer_table(std::string p) { in_path_kmer_ = std::move(p), kmer_is_table_ = true; }
     void set_positions(bool p) { positions_ = p; }
     void set_threads(int t) { threads_ = t; }
     void set_max_memory(double gb) { memory_ceil_gb_ = gb; }
@@ -308,6 +326,7 @@ class ProfileComputer {
 
   private:
     std::string in_path_, in_path_kmer_, out_dir_;
+    bool kmer_is_table_ = false;
     int ksize_, threads_ = 0, device_ = 0;
     double memory_ceil_gb_ = 6.0;
     bool positions_ = false;
@@ -334,11 +353,14 @@ class CompareComputer {
     void set_threads(int t) { threads_ = t; }
     void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // (accepted; the tables live in HBM)
     void set_device(int d) { dev_.index = d; }
+    // --table / --alt-table: that side's table is loaded from a table file; the path takes the input's place
+    void set_tables(bool a_is_table, bool b_is_table) { a_is_table_ = a_is_table, b_is_table_ = b_is_table; }
     std::string compare();  // "" or the error message
     uint32_t passes() const { return passes_; }
 
   private:
     std::string in_a_, in_b_, out_dir_;
+    bool a_is_table_ = false, b_is_table_ = false;
     int ksize_, threads_ = 0;
     uint32_t max_a_ = 1000, max_b_ = 100, passes_ = 1;
     double memory_ceil_gb_ = 6.0;
@@ -368,10 +390,13 @@ class SetopComputer {
     void set_threads(int t) { threads_ = t; }
     void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // the text slabs shrink with it; the tables live in HBM
     void set_device(int d) { dev_.index = d; }
+    // --table / --alt-table: that side's table is loaded from a table file; the path takes the input's place
+    void set_tables(bool a_is_table, bool b_is_table) { a_is_table_ = a_is_table, b_is_table_ = b_is_table; }
     std::string setop();  // "" or the error message
 
   private:
     std::string in_a_, in_b_, out_dir_;
+    bool a_is_table_ = false, b_is_table_ = false;
     int ksize_, threads_ = 0, op_ = 0, rule_ = 0;
     uint32_t min_a_ = 1, max_a_ = 0xFFFFFFFFu, min_b_ = 1, max_b_ = 0xFFFFFFFFu, passes_ = 1;
     bool acgt_ = false;
@@ -395,6 +420,8 @@ class GraphComputer {
     void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
     void set_acgt_output(bool a) { acgt_ = a; }
     void set_stats_only(bool s) { stats_only_ = s; }
+    // --table: the table is loaded from this table file (kt_ctr_add_file) instead of counted from the input
+    void set_table_file(std::string p) { table_file_ = std::move(p); }
     void set_threads(int t) { threads_ = t; }
     void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // the text slabs shrink with it; the table lives in HBM
     void set_device(int d) { dev_.index = d; }
@@ -402,6 +429,7 @@ class GraphComputer {
 
   private:
     std::string in_path_, out_dir_;
+    std::string table_file_;
     int ksize_, threads_ = 0;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
     bool acgt_ = false, stats_only_ = false;
@@ -427,6 +455,8 @@ class HetmerComputer {
     void set_middle(bool m) { middle_ = m; }
     void set_max_counts(uint32_t max_minor, uint32_t max_major) { max_minor_ = max_minor, max_major_ = max_major; }
     void set_stats_only(bool s) { stats_only_ = s; }
+    // --table: the table is loaded from this table file (kt_ctr_add_file) instead of counted from the input
+    void set_table_file(std::string p) { table_file_ = std::move(p); }
     void set_threads(int t) { threads_ = t; }
     void set_max_memory(double gb) { memory_ceil_gb_ = gb; }  // (accepted; the table lives in HBM)
     void set_device(int d) { dev_.index = d; }
@@ -434,6 +464,7 @@ class HetmerComputer {
 
   private:
     std::string in_path_, out_dir_;
+    std::string table_file_;
     int ksize_, threads_ = 0;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu, max_minor_ = 500, max_major_ = 1000;
     bool middle_ = false, stats_only_ = false;
@@ -463,6 +494,8 @@ class UnitigComputer {
     UnitigComputer &operator=(const UnitigComputer &) = delete;
     void set_range(uint32_t min_count, uint32_t max_count) { min_count_ = min_count, max_count_ = max_count; }
     void set_stats_only(bool s) { stats_only_ = s; }
+    // --table: the table is loaded from this table file (kt_ctr_add_file) instead of counted from the input
+    void set_table_file(std::string p) { table_file_ = std::move(p); }
     void set_links(bool gfa, bool fa_links) { gfa_ = gfa, fa_links_ = fa_links; }
     // before anything is written, the tips of at most tip_nodes k-mers (drop_isolated: the isolated unitigs that short, too)
     // are erased from the table, for at most `rounds` rounds
@@ -477,6 +510,7 @@ class UnitigComputer {
 
   private:
     std::string in_path_, out_dir_;
+    std::string table_file_;
     int ksize_;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
     bool stats_only_ = false, gfa_ = false, fa_links_ = false;

@@ -136,6 +136,42 @@ std::string required_str(const std::map<std::string, std::string> &f, const char
 #define HELP_ESTIMATE_SHARDED \
     HELP_ESTIMATE_("                               Not with --devices above 1: the sharded table keeps its bound.\n")
 
+// ---- --table FILE / --alt-table FILE: a table file (ctr --save-table) in place of counting an input ---------------------------
+#define SPEC_TABLE {0, "table", true}
+#define SPEC_ALT_TABLE {0, "alt-table", true}
+// (`counted`: the flag of the input the table would otherwise be counted from)
+#define HELP_TABLE_(flag, counted, sharded)                                                                                  \
+    "      " flag " <FILE>           Load the table from this table file (ctr --save-table) instead of counting\n"            \
+    "                               " counted ", which is then not given; --k-size must be the file's k.\n"                 \
+    "                               Not with --estimate-size" sharded ".\n"
+#define HELP_TABLE HELP_TABLE_("--table", "--input", "")
+#define HELP_TABLE_CTR HELP_TABLE_("--table", "--input", " or --devices above 1")
+#define HELP_TABLE_ALT_INPUT HELP_TABLE_("--table", "--alt-input (default: the input)", "")
+#define HELP_TABLE_COV HELP_TABLE_("--table", "--alt-input (default: the input)", " or --devices above 1")
+#define HELP_TABLES HELP_TABLE_("--table", "--input (A)", "") \
+    "      --alt-table <FILE>       The same for --alt-input (B); either one or both may be table files.\n"
+
+// The flag's checks, before any device work and before the output directory is made: the file is read on the host only
+// (kt_table_file_info).  `flag`: "table" or "alt-table"; `counted` / `counted_text`: the flag it stands in for.  Returns the
+// file's path, "" without the flag.
+std::string table_flag(const std::map<std::string, std::string> &f, int k, const char *flag = "table", const char *counted = "input",
+                       const char *counted_text = "--input <INPUT>") {
+    const auto it = f.find(flag);
+    if (it == f.end()) return "";
+    const std::string name = std::string("'--") + flag + " <FILE>'";
+    if (f.count(counted)) usage_error("the argument " + name + " cannot be used with '" + counted_text + "'");
+    if (f.count("estimate-size")) usage_error("the argument " + name + " cannot be used with '--estimate-size'");
+    if (f.count("devices") && ranged(f, "devices", 1, 64, false, 1) > 1)
+        usage_error("the argument " + name + " cannot be used with '--devices <N>' above 1");
+    int fk = 0;
+    if (kt_table_file_info(it->second.c_str(), &fk, nullptr, nullptr, nullptr) != KT_OK)
+        usage_error("invalid value '" + it->second + "' for " + name + ": " + kt_last_error());
+    if (fk != k)
+        usage_error("invalid value '" + std::to_string(k) + "' for '--k-size <K_SIZE>': the table file " + it->second + " holds k = " +
+                    std::to_string(fk));
+    return it->second;
+}
+
 struct EstimateFlags {
     bool on = false;
     int p = 14;
@@ -243,6 +279,11 @@ const char *HELP_CTR =
     "                           (lines \"count<TAB>k-mers\", count = 1..H; the last line counts H or more)\n"
     "      --histo-max <H>      Highest count of kmers.histo [default: 10000]\n"
     "      --histo-only         Write kmers.histo and no kmers.counts (implies --histo)\n"
+    "      --save-table <FILE>  Also write the k-mers in the count range to this table file (binary, sorted, 6 bytes\n"
+    "                           a k-mer at k = 31; one section per pass), which graph, unitigs and hetmers load\n"
+    "                           with --table instead of counting again.  Works with --histo-only.  Not with --devices\n"
+    "                           above 1.\n"
+    HELP_TABLE_CTR
     HELP_ESTIMATE_SHARDED
     "  -h, --help               Print help\n";
 
@@ -262,6 +303,7 @@ const char *HELP_COV =
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
     "      --devices <N>            Shard the table over N GPUs, --device .. --device + N - 1 [default: 1]\n"
+    HELP_TABLE_COV
     HELP_ESTIMATE_SHARDED
     "  -h, --help                   Print help\n";
 
@@ -281,7 +323,8 @@ int cmd_cov(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},    {'a', "alt-input", true}, {'o', "output", true},
                                      {'k', "k-size", true},   {'p', "preset", true},    {'s', "bin-size", true},
                                      {'c', "bin-count", true}, {'m', "memory", true},   {0, "counts", false},
-                                     {'t', "threads", true},  {0, "device", true},      {0, "devices", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true},  {0, "device", true},      {0, "devices", true}, 
+                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_COV);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 7, 31, false, 15);
@@ -293,9 +336,10 @@ int cmd_cov(int argc, char **argv, int from) {
     if (preset != "csv" && preset != "tsv" && preset != "spc")
         usage_error("invalid value '" + preset + "' for '--preset <PRESET>'\n  [possible values: csv, tsv, spc]");
     const EstimateFlags est = estimate_flags(f);
+    const std::string table = table_flag(f, k, "table", "alt-input", "--alt-input <ALT_INPUT>");
     if (int rc = make_out_dir(out)) return rc;
-    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
-    for (const std::string &p : {in, kin}) {
+    const std::string kin = !table.empty() ? table : f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : table.empty() ? std::vector<std::string>{in, kin} : std::vector<std::string>{in}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
             return 101;  // SeqFormat::get(...).unwrap()
@@ -305,7 +349,8 @@ int cmd_cov(int argc, char **argv, int from) {
     return run_table_command(est, [&]() -> std::string {  // (101: build_table().unwrap() / unwraps inside compute_coverages)
         CovComputer cov(in, out, k, bin_size, bin_count);
         if (threads > 0) cov.set_threads(threads);
-        if (f.count("alt-input")) cov.set_kmer_path(kin);
+        if (!table.empty()) cov.set_kmer_table(table);
+        else if (f.count("alt-input")) cov.set_kmer_path(kin);
         if (f.count("counts")) cov.set_norm(false);
         cov.set_max_memory((double)mem);
         cov.set_delim(preset == "csv" ? "," : preset == "tsv" ? "\t" : " ");
@@ -424,9 +469,11 @@ int cmd_ctr(int argc, char **argv, int from) {
                                      {'m', "memory", true}, {'a', "acgt", false},  {'t', "threads", true},
                                      {0, "device", true},   {0, "devices", true},
                                      {0, "min-count", true}, {0, "max-count", true}, {0, "histo", false},
-                                     {0, "histo-max", true}, {0, "histo-only", false}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {0, "histo-max", true}, {0, "histo-only", false}, {0, "save-table", true},
+                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_CTR);
-    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    // (--table FILE stands in for --input: the table file is dumped, filtered, re-saved)
+    const std::string in = f.count("table") && !f.count("input") ? f.at("table") : required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     const uint64_t mem = ranged(f, "memory", 6, 128, false, 6);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
@@ -439,8 +486,12 @@ int cmd_ctr(int argc, char **argv, int from) {
     const uint64_t histo_max = ranged(f, "histo-max", 1, (1u << 24) - 1, false, 10000);
     const bool histo_only = f.count("histo-only") != 0, histo = histo_only || f.count("histo") != 0;
     const EstimateFlags est = estimate_flags(f);
+    const std::string table = table_flag(f, k);
+    const std::string save_table = f.count("save-table") ? f.at("save-table") : "";
+    if (!save_table.empty() && ranged(f, "devices", 1, 64, false, 1) > 1)
+        usage_error("the argument '--save-table <FILE>' cannot be used with '--devices <N>' above 1");
     if (int rc = make_out_dir(out)) return rc;
-    if (format_from_path(in) == SeqFormat::Unknown) {
+    if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {
         // CountComputer::new unwraps SeqFormat::get (counter/src/lib.rs:38): unknown extension - "-" included - panics
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
@@ -455,6 +506,8 @@ int cmd_ctr(int argc, char **argv, int from) {
         ctr.set_device(device);
         ctr.set_count_range((uint32_t)min_count, (uint32_t)max_count);
         if (histo) ctr.set_histo((uint32_t)histo_max, histo_only);
+        ctr.set_save_table(save_table);
+        ctr.set_input_is_table(!table.empty());
         std::string e = ctr.count();
         if (e.empty()) e = ctr.merge(true);
         return e;
@@ -480,6 +533,7 @@ const char *HELP_FILTER =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE_ALT_INPUT
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
@@ -487,7 +541,7 @@ int cmd_filter(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},      {'o', "output", true},     {'k', "k-size", true},
                                      {'a', "alt-input", true},  {0, "min-count", true},    {0, "max-count", true},
                                      {0, "min-solid", true},    {0, "trim", false},        {'m', "memory", true},
-                                     {'t', "threads", true},    {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true},    {0, "device", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_FILTER);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -510,8 +564,9 @@ int cmd_filter(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
-    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
-    for (const std::string &p : {in, kin}) {
+    const std::string table = table_flag(f, k, "table", "alt-input", "--alt-input <ALT_INPUT>");
+    const std::string kin = !table.empty() ? table : f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : table.empty() ? std::vector<std::string>{in, kin} : std::vector<std::string>{in}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
             return 101;
@@ -520,7 +575,8 @@ int cmd_filter(int argc, char **argv, int from) {
     return run_table_command(est, [&]() -> std::string {
         FilterComputer flt(in, out, k);
         if (threads > 0) flt.set_threads(threads);
-        flt.set_kmer_path(kin);
+        if (!table.empty()) flt.set_kmer_table(table);
+        else flt.set_kmer_path(kin);
         flt.set_count_range((uint32_t)min_count, (uint32_t)max_count);
         flt.set_min_solid(min_solid);
         flt.set_trim(trim);
@@ -556,6 +612,7 @@ const char *HELP_CORRECT =
     "                               kept across the passes of an out-of-core count)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE_ALT_INPUT
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
@@ -563,7 +620,8 @@ int cmd_correct(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},       {'o', "output", true},          {'k', "k-size", true},
                                      {'a', "alt-input", true},   {0, "min-count", true},         {0, "max-count", true},
                                      {0, "min-support", true},   {0, "max-corrections", true},   {0, "stats", true},
-                                     {'m', "memory", true},      {'t', "threads", true},         {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'m', "memory", true},      {'t', "threads", true},         {0, "device", true}, 
+                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_CORRECT);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -579,8 +637,9 @@ int cmd_correct(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
-    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
-    for (const std::string &p : {in, kin}) {
+    const std::string table = table_flag(f, k, "table", "alt-input", "--alt-input <ALT_INPUT>");
+    const std::string kin = !table.empty() ? table : f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : table.empty() ? std::vector<std::string>{in, kin} : std::vector<std::string>{in}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
             return 101;
@@ -589,7 +648,8 @@ int cmd_correct(int argc, char **argv, int from) {
     return run_table_command(est, [&]() -> std::string {
         CorrectComputer cor(in, out, k);
         if (threads > 0) cor.set_threads(threads);
-        cor.set_kmer_path(kin);
+        if (!table.empty()) cor.set_kmer_table(table);
+        else cor.set_kmer_path(kin);
         cor.set_count_range((uint32_t)min_count, (uint32_t)max_count);
         cor.set_min_support((uint32_t)min_support);
         cor.set_max_corrections((uint32_t)max_corrections);
@@ -619,15 +679,19 @@ const char *HELP_COMPARE =
     "                               hold every distinct k-mer, the inputs are counted in several passes)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLES
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_compare(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},  {'a', "alt-input", true}, {'o', "output", true},
                                      {'k', "k-size", true}, {0, "max-a", true},       {0, "max-b", true},
-                                     {'m', "memory", true}, {'t', "threads", true},   {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'m', "memory", true}, {'t', "threads", true},   {0, "device", true}, 
+                                     SPEC_TABLE, SPEC_ALT_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_COMPARE);
-    const std::string in = required_str(f, "input"), alt = required_str(f, "alt-input"), out = required_str(f, "output");
+    // (--table FILE stands in for --input, --alt-table FILE for --alt-input)
+    const std::string in = f.count("table") ? f.at("table") : required_str(f, "input");
+    const std::string alt = f.count("alt-table") ? f.at("alt-table") : required_str(f, "alt-input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     // everything is checked before any device work
     const uint64_t max_a = ranged(f, "max-a", 1, (1u << 24) - 1, false, 1000);
@@ -639,15 +703,18 @@ int cmd_compare(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
+    const bool a_table = !table_flag(f, k).empty();
+    const bool b_table = !table_flag(f, k, "alt-table", "alt-input", "--alt-input <ALT_INPUT>").empty();
     if (int rc = make_out_dir(out)) return rc;
-    for (const std::string &p : {in, alt}) {
-        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+    for (const std::string &p : {a_table ? std::string() : in, b_table ? std::string() : alt}) {
+        if (!p.empty() && format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
             return 101;
         }
     }
     return run_table_command(est, [&]() -> std::string {
         CompareComputer cmp(in, alt, out, k);
+        cmp.set_tables(a_table, b_table);
         cmp.set_max_counts((uint32_t)max_a, (uint32_t)max_b);
         if (threads > 0) cmp.set_threads(threads);
         cmp.set_max_memory((double)mem);
@@ -678,13 +745,14 @@ const char *HELP_PROFILE =
     "                               kept across the passes of an out-of-core count)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE_ALT_INPUT
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_profile(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},  {'k', "k-size", true},
                                      {'a', "alt-input", true}, {0, "positions", false}, {'m', "memory", true},
-                                     {'t', "threads", true},   {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true},   {0, "device", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_PROFILE);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 1, 31, true, 0);
@@ -693,8 +761,9 @@ int cmd_profile(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
-    const std::string kin = f.count("alt-input") ? f.at("alt-input") : in;
-    for (const std::string &p : {in, kin}) {
+    const std::string table = table_flag(f, k, "table", "alt-input", "--alt-input <ALT_INPUT>");
+    const std::string kin = !table.empty() ? table : f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : table.empty() ? std::vector<std::string>{in, kin} : std::vector<std::string>{in}) {
         if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
             return 101;
@@ -704,7 +773,8 @@ int cmd_profile(int argc, char **argv, int from) {
     return run_table_command(est, [&]() -> std::string {
         ProfileComputer prof(in, out, k);
         if (threads > 0) prof.set_threads(threads);
-        prof.set_kmer_path(kin);
+        if (!table.empty()) prof.set_kmer_table(table);
+        else prof.set_kmer_path(kin);
         prof.set_positions(f.count("positions") != 0);
         prof.set_max_memory((double)mem);
         prof.set_device(device);
@@ -864,6 +934,7 @@ const char *HELP_SETOP =
     "                               fit, the inputs are counted in several passes; the text is written in slabs)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLES
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
@@ -887,9 +958,11 @@ int cmd_setop(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},  {'a', "alt-input", true}, {'o', "output", true}, {'k', "k-size", true},
                                      {0, "op", true},       {0, "count", true},       {0, "min-a", true},    {0, "max-a", true},
                                      {0, "min-b", true},    {0, "max-b", true},       {0, "acgt", false},    {'m', "memory", true},
-                                     {'t', "threads", true}, {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true}, {0, "device", true}, SPEC_TABLE, SPEC_ALT_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_SETOP);
-    const std::string in = required_str(f, "input"), alt = required_str(f, "alt-input"), out = required_str(f, "output");
+    // (--table FILE stands in for --input, --alt-table FILE for --alt-input)
+    const std::string in = f.count("table") ? f.at("table") : required_str(f, "input");
+    const std::string alt = f.count("alt-table") ? f.at("alt-table") : required_str(f, "alt-input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     // everything is checked before any device work and before the output directory is made
     static_assert(KT_SET_INTERSECT == 0 && KT_SET_SUBTRACT == 1 && KT_SET_UNION == 2 && KT_SET_XOR == 3, "the order of --op's values");
@@ -909,8 +982,10 @@ int cmd_setop(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
-    for (const std::string &p : {in, alt}) {
-        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
+    const bool a_table = !table_flag(f, k).empty();
+    const bool b_table = !table_flag(f, k, "alt-table", "alt-input", "--alt-input <ALT_INPUT>").empty();
+    for (const std::string &p : {a_table ? std::string() : in, b_table ? std::string() : alt}) {
+        if (!p.empty() && format_from_path(p) == SeqFormat::Unknown) {  // "-" included: both inputs are read more than once
             fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
             return 101;
         }
@@ -918,6 +993,7 @@ int cmd_setop(int argc, char **argv, int from) {
     if (int rc = make_out_dir(out)) return rc;
     return run_table_command(est, [&]() -> std::string {
         SetopComputer so(in, alt, out, k);
+        so.set_tables(a_table, b_table);
         so.set_op(op, rule);
         so.set_ranges((uint32_t)lo[0], (uint32_t)hi[0], (uint32_t)lo[1], (uint32_t)hi[1]);
         so.set_acgt_output(f.count("acgt") != 0);
@@ -951,15 +1027,17 @@ const char *HELP_GRAPH =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (the table lives in HBM; the text is written in slabs)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
 int cmd_graph(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
                                      {0, "max-count", true},   {0, "acgt", false},         {0, "stats-only", false}, {'m', "memory", true},
-                                     {'t', "threads", true},   {0, "device", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true},   {0, "device", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_GRAPH);
-    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    // (--table FILE stands in for --input)
+    const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     // everything is checked before any device work and before the output directory is made
     const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
@@ -970,13 +1048,15 @@ int cmd_graph(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
-    if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+    const std::string table = table_flag(f, k);
+    if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
     return run_table_command(est, [&]() -> std::string {
         GraphComputer gc(in, out, k);
+        gc.set_table_file(table);
         gc.set_range((uint32_t)lo, (uint32_t)hi);
         gc.set_acgt_output(f.count("acgt") != 0);
         gc.set_stats_only(f.count("stats-only") != 0);
@@ -1017,6 +1097,7 @@ const char *HELP_HETMERS =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
@@ -1024,9 +1105,10 @@ int cmd_hetmers(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},   {'o', "output", true},    {'k', "k-size", true},    {0, "min-count", true},
                                      {0, "max-count", true}, {0, "middle", false},     {0, "max-minor", true},   {0, "max-major", true},
                                      {0, "stats-only", false}, {'m', "memory", true},  {'t', "threads", true},   {0, "device", true},
-                                     SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_HETMERS);
-    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    // (--table FILE stands in for --input)
+    const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     // everything is checked before any device work and before the output directory is made
     const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
@@ -1045,13 +1127,15 @@ int cmd_hetmers(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
-    if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+    const std::string table = table_flag(f, k);
+    if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
     return run_table_command(est, [&]() -> std::string {
         HetmerComputer hc(in, out, k);
+        hc.set_table_file(table);
         hc.set_range((uint32_t)lo, (uint32_t)hi);
         hc.set_middle(middle);
         hc.set_max_counts((uint32_t)max_minor, (uint32_t)max_major);
@@ -1114,6 +1198,7 @@ const char *HELP_UNITIGS =
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE
     HELP_ESTIMATE
     "  -h, --help                   Print help\n";
 
@@ -1122,9 +1207,10 @@ int cmd_unitigs(int argc, char **argv, int from) {
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
                                      {0, "device", true},      {0, "gfa", false},          {0, "links", false},
                                      {0, "clip-tips", false},  {0, "tip-nodes", true},     {0, "clip-rounds", true},
-                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
-    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    // (--table FILE stands in for --input)
+    const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
     // everything is checked before any device work and before the output directory is made
     const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
@@ -1147,13 +1233,15 @@ int cmd_unitigs(int argc, char **argv, int from) {
             usage_error(std::string("the argument '--") + needs + "' requires '--clip-tips'");
     if (f.count("bubble-nodes") && !pop) usage_error("the argument '--bubble-nodes' requires '--pop-bubbles'");
     const EstimateFlags est = estimate_flags(f);
-    if (format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
+    const std::string table = table_flag(f, k);
+    if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
     return run_table_command(est, [&]() -> std::string {
         UnitigComputer uc(in, out, k);
+        uc.set_table_file(table);
         uc.set_links(gfa, links);
         if (clip) uc.set_clip((uint32_t)tip_nodes, (uint32_t)clip_rounds, f.count("drop-isolated") != 0);
         if (pop) uc.set_bubbles((uint32_t)bubble_nodes, (uint32_t)clip_rounds);

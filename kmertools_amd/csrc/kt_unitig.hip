@@ -48,14 +48,15 @@
 // marks (h to k) - and every entry point says which of them it runs, and into which Outputs.
 #include "kt_device.hpp"
 #include "kt_launch.hpp"
+#include "kt_scan.hpp"
 
 namespace {
 
 using namespace ktl;
 
-constexpr int BLOCK = 256, WAVES = BLOCK / 64;
+constexpr int BLOCK = 256;
 constexpr uint32_t NIL = 0xFFFFFFFFu;
-constexpr uint32_t SCAN_ITEMS = 4, SCAN_TILE = BLOCK * SCAN_ITEMS;
+static_assert(BLOCK == SCAN_BLOCK, "the scans of kt_scan.hpp run in this file's workgroups");
 constexpr uint32_t CIRC = 0x80000000u;  // in slen: the unitig is a cycle; in place.y: the node is spelled forward
 constexpr uint32_t ERR_DEGREE = 1u, ERR_SEARCH = 2u, ERR_MUTUAL = 4u, ERR_CHAIN = 8u, ERR_CYCLE = 16u, ERR_LINK = 32u;
 
@@ -228,35 +229,13 @@ __global__ __launch_bounds__(BLOCK) void unitig_place_kernel(const uint64_t *__r
     slen[i] = pos == 0u && start == (uint32_t)i ? len : 0u;
 }
 
-// inclusive prefix sums of a and b over the workgroup's threads; *ta, *tb = the sums
-__device__ __forceinline__ void block_scan2(uint64_t &a, uint64_t &b, uint64_t (*wsum)[2], uint64_t *ta, uint64_t *tb) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t ua = __shfl_up(a, off, 64), ub = __shfl_up(b, off, 64);
-        if (lane >= (uint32_t)off) a += ua, b += ub;
-    }
-    if (lane == 63u) wsum[wave][0] = a, wsum[wave][1] = b;
-    ktd::lds_barrier();
-    uint64_t pa = 0, pb = 0, sa = 0, sb = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < (uint32_t)WAVES; x++) {
-        const uint64_t xa = wsum[x][0], xb = wsum[x][1];
-        if (x < wave) pa += xa, pb += xb;
-        sa += xa, sb += xb;
-    }
-    ktd::lds_barrier();  // (wsum is rewritten by the next call)
-    a += pa, b += pb;
-    *ta = sa, *tb = sb;
-}
-
 // a start node's unitig: 1 unitig, nodes + k - 1 bases
 __device__ __forceinline__ uint64_t bases_of(uint32_t sl, uint32_t k) { return sl ? (uint64_t)(sl & ~CIRC) + k - 1u : 0ull; }
 
 // The exclusive scan over n items, two sums at once, is written once over a functor F: word(i) is item i's one u32,
 // add(word, a, b) what it contributes to the two sums (word 0, the filler past n, contributes nothing), put(i, a, b) takes
 // the sums over the items before i, total() is thread 0's after the last put.  Three launches: the tiles' sums, one
-// workgroup over those, and the tiles again.
+// workgroup over those, and the tiles again (block_scan2 and the three kernels: kt_scan.hpp, shared with kt_tablefile.hip).
 
 // stage d, over nodes: (is start, bases) -> ex_id[i], ex_off[i] = unitigs and bases that start at nodes before i
 struct NodeScan {
@@ -269,58 +248,6 @@ struct NodeScan {
     __device__ __forceinline__ void put(uint64_t i, uint64_t a, uint64_t b) const { ex_id[i] = (uint32_t)a, ex_off[i] = b; }
     __device__ __forceinline__ void total() const {}
 };
-
-// tile t (SCAN_TILE items) -> tiles[2t], tiles[2t + 1] = its two sums
-template <class F>
-__global__ __launch_bounds__(BLOCK) void unitig_tile_sum_kernel(F f, uint64_t n, uint64_t *__restrict__ tiles) {
-    __shared__ uint64_t wsum[WAVES][2];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t a = 0, b = 0, ta, tb;
-#pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) f.add(base + j < n ? f.word(base + j) : 0u, a, b);
-    block_scan2(a, b, wsum, &ta, &tb);
-    if (threadIdx.x == 0) tiles[2ull * blockIdx.x] = ta, tiles[2ull * blockIdx.x + 1] = tb;
-}
-
-// one workgroup: the tiles' sums into their exclusive prefixes, the totals into *sum_a and *sum_b
-__global__ __launch_bounds__(BLOCK) void unitig_tile_scan_kernel(uint64_t *__restrict__ tiles, uint64_t T,
-                                                                 unsigned long long *__restrict__ sum_a,
-                                                                 unsigned long long *__restrict__ sum_b) {
-    __shared__ uint64_t wsum[WAVES][2];
-    uint64_t ca = 0, cb = 0;
-    for (uint64_t c0 = 0; c0 < T; c0 += BLOCK) {
-        const uint64_t t = c0 + threadIdx.x;
-        const uint64_t va = t < T ? tiles[2 * t] : 0, vb = t < T ? tiles[2 * t + 1] : 0;
-        uint64_t a = va, b = vb, ta, tb;
-        block_scan2(a, b, wsum, &ta, &tb);
-        if (t < T) tiles[2 * t] = ca + a - va, tiles[2 * t + 1] = cb + b - vb;
-        ca += ta, cb += tb;
-    }
-    if (threadIdx.x == 0) *sum_a = ca, *sum_b = cb;
-}
-
-// every item's put(), from its tile's exclusive prefix in `tiles`
-template <class F>
-__global__ __launch_bounds__(BLOCK) void unitig_scan_apply_kernel(F f, uint64_t n, const uint64_t *__restrict__ tiles) {
-    __shared__ uint64_t wsum[WAVES][2];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t v[SCAN_ITEMS];
-    uint64_t a = 0, b = 0, ta, tb;
-#pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        v[j] = base + j < n ? f.word(base + j) : 0u;
-        f.add(v[j], a, b);
-    }
-    const uint64_t own_a = a, own_b = b;
-    block_scan2(a, b, wsum, &ta, &tb);
-    uint64_t ra = tiles[2ull * blockIdx.x] + a - own_a, rb = tiles[2ull * blockIdx.x + 1] + b - own_b;
-#pragma unroll
-    for (uint32_t j = 0; j < SCAN_ITEMS; j++) {
-        if (base + j < n) f.put(base + j, ra, rb);
-        f.add(v[j], ra, rb);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) f.total();
-}
 
 // ---- e. spelling -----------------------------------------------------------------------------------------------------
 
@@ -748,9 +675,9 @@ struct Run {
         // d. placing, ids and offsets
         hipLaunchKernelGGL(unitig_place_kernel, blocks_for(n), B, 0, st, ra, link, cval, n, place, slen, w);
         const NodeScan scan{slen, k, ex_id, ex_off};
-        hipLaunchKernelGGL(unitig_tile_sum_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
-        hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), B, 0, st, tiles, (uint64_t)T.x, &w->n_unitigs, &w->n_bases);
-        hipLaunchKernelGGL(unitig_scan_apply_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
+        hipLaunchKernelGGL(scan2_tile_sum_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
+        hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, st, tiles, (uint64_t)T.x, &w->n_unitigs, &w->n_bases);
+        hipLaunchKernelGGL(scan2_apply_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
         if (int rc = check_words("the nodes' links do not form paths and cycles")) return rc;
         nu = h.n_unitigs, n_bases = h.n_bases;
         return KT_OK;
@@ -762,8 +689,8 @@ struct Run {
         if (int rc = carve(call, kt::AUX0, &lw, 1, &deg, n_ends, &ltiles, 2ull * T.x)) return rc;
         KT_HIP(hipMemsetAsync(lw, 0, (uint8_t *)ltiles - (uint8_t *)lw, st));
         hipLaunchKernelGGL(unitig_end_degree_kernel, blocks_for(2 * n), B, 0, st, link_args(Outputs{}));
-        hipLaunchKernelGGL(unitig_tile_sum_kernel<EndScan>, T, B, 0, st, EndScan{deg, n_ends, lw, nullptr}, n_ends, ltiles);
-        hipLaunchKernelGGL(unitig_tile_scan_kernel, dim3(1), B, 0, st, ltiles, (uint64_t)T.x, &lw->n_links, &lw->unused);
+        hipLaunchKernelGGL(scan2_tile_sum_kernel<EndScan>, T, B, 0, st, EndScan{deg, n_ends, lw, nullptr}, n_ends, ltiles);
+        hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, st, ltiles, (uint64_t)T.x, &lw->n_links, &lw->unused);
         return fetch(&n_links, &lw->n_links, 8);
     }
     LinkArgs link_args(const Outputs &o) const {  // (f writes deg and reads no output; max_links guards g's stores)
@@ -794,7 +721,7 @@ struct Run {
     // rule puts it
     int emit(const Outputs &o) {
         const EndScan scan{deg, n_ends, lw, o.link_offsets};
-        hipLaunchKernelGGL(unitig_scan_apply_kernel<EndScan>, blocks_for(n_ends, SCAN_TILE), dim3(BLOCK), 0, st, scan, n_ends, ltiles);
+        hipLaunchKernelGGL(scan2_apply_kernel<EndScan>, blocks_for(n_ends, SCAN_TILE), dim3(BLOCK), 0, st, scan, n_ends, ltiles);
         if (n_links) hipLaunchKernelGGL(unitig_end_emit_kernel, blocks_for(2 * n), dim3(BLOCK), 0, st, link_args(o));
         return check_words("a unitig end's neighbour is not at an end of its own unitig");
     }

@@ -9,6 +9,7 @@
   torch is only plumbing here (allocation, streams, torch.distributed).
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -126,6 +127,18 @@ def card_merge(into, other):
         raise ValueError("card_merge: %d registers into %d" % (other.size, into.size))
     check(_lib.lib().kt_card_merge(_ptr(into), _ptr(other), _card_p(into)))
     return into
+
+
+def table_file_info(path):
+    """k, sections, entries and occurrences of a table file, from its headers (host only: kt_table_file_info)"""
+    k, s, e, o = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(_lib.lib().kt_table_file_info(os.fsencode(path), C.byref(k), C.byref(s), C.byref(e), C.byref(o)))
+    return {"k": k.value, "sections": s.value, "entries": e.value, "occurrences": o.value}
+
+
+def table_file_check(path):
+    """the full structural validation of a table file (host only: kt_table_file_check); raises KmertoolsError"""
+    check(_lib.lib().kt_table_file_check(os.fsencode(path)))
 
 
 def card_rel_error(p):
@@ -979,6 +992,36 @@ class Counter:
             order = np.argsort(keys, kind="stable")
             keys, counts = keys[order], counts[order]
         return keys, counts
+
+    def save(self, path, min_count=1, max_count=None, append=False):
+        """writes the entries with min_count <= count <= max_count as one section of the table file `path` (created, or
+        with append=True extended); returns how many entries went (kt_ctr_save)"""
+        n = C.c_uint64()
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        check(_lib.lib().kt_ctr_save(self._h, os.fsencode(path), int(min_count), hi, int(bool(append)), C.byref(n)))
+        return n.value
+
+    def add_file(self, path):
+        """table[key] += count for every entry of every section of the table file `path`; returns the entries read
+        (kt_ctr_add_file)"""
+        n = C.c_uint64()
+        check(_lib.lib().kt_ctr_add_file(self._h, os.fsencode(path), C.byref(n)))
+        return n.value
+
+    @classmethod
+    def from_file(cls, ctx, path, slots=None):
+        """a new table of the file's k holding the file; slots=None sizes it as the command line does: 1.9 slots per entry
+        of the file, at least 1024"""
+        info = table_file_info(path)
+        if slots is None:
+            slots = max(1024, info["entries"] + info["entries"] // 10 * 9)
+        t = cls(ctx, info["k"], slots)
+        try:
+            t.add_file(path)
+        except Exception:
+            t.close()
+            raise
+        return t
 
 
 class Sharded:

@@ -2,7 +2,7 @@
 by kt_synth_reads from a random genome, both strands, 1 % substitutions, k = 31, min_count = 2), everything written in both.
 One process, warm-ups first, medians of 5 between events on the context's stream, with minimum and maximum.  The linked
 call contains the unlinked one; what the link stages add comes from a kernel trace of this same script (unitig_end_*_kernel,
-and unitig_tile_scan_kernel once more per linked call) beside stage b's unitig_link_kernel in the same trace.
+and scan2_tile_scan_kernel once more per linked call) beside stage b's unitig_link_kernel in the same trace.
 
     python tools/unitig_links_timing.py [--genome 20000000] [--coverage 30] [--out profiles/unitig_links_timing.txt]
 
