@@ -754,6 +754,67 @@ int kt_correct_apply(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
                      uint32_t min_support, uint32_t max_corrections, uint8_t *out_bases, uint32_t *n_single,
                      uint32_t *n_ambiguous, int mem);
 
+/* Reads threaded onto the unitigs of a table (`kmertools thread`; what Bifrost query, GGCAT query and GraphAligner's exact
+ * mode answer on the CPU).  replaces: nothing - the reference has no such operation.  Three calls: the first makes a table
+ * whose "count" is a k-mer's position in a set of sequences, the second looks a batch's k-mers up in it and orients the
+ * answer, the third - a pure function of arrays, split off as kt_profile_stats and kt_correct_apply are - folds the per-base
+ * answers into runs along the unitigs.
+ *
+ * kt_ctr_index_sequences: `index` is an EMPTY table of the sequences' k, created and sized by the caller (room for one entry
+ * per window).  Every valid window (inside one sequence, ACGT only, as in every k-mer walk here) that starts at global base G
+ * with forward k-mer f and reverse complement r puts key min(f, r) with value 1 + 2 * G + S into the table: S = 1 when f > r
+ * (the sequence shows the reverse complement of the canonical k-mer), S = 0 otherwise, a palindrome included.  The value is
+ * the key's "count" for every reader of the table (kt_ctr_lookup returns it).  *n_kmers = the number of windows.
+ * The sequences must hold every canonical k-mer at most once.  That is so for the unitigs of kt_ctr_unitigs: every solid
+ * k-mer lies in exactly one unitig, once; a circular unitig repeats its first k - 1 bases but no k-mer; a palindromic node is
+ * a unitig of its own.  `mem` says where bases and offsets live; both kinds synchronise (the check below needs the size).
+ * KT_ERR_ARG: a null index or n_kmers, a bad mem, a null buffer with n_seqs > 0, one shard of a sharded table, a table that
+ * is not empty, offsets[n_seqs] > 2^31 - 2 (the value must stay at or below 0xFFFFFFFE; decided from the offsets alone, before
+ * any base is read), and a table that holds fewer entries than *n_kmers after the build: a k-mer occurred twice and its values
+ * added up - the message says so, *n_kmers is set and the table is cleared.  KT_ERR_FULL as in kt_ctr_add_pairs.
+ * Device scratch: 12 bytes per base. */
+int kt_ctr_index_sequences(kt_ctr *index, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, uint64_t *n_kmers,
+                           int mem);
+
+/* Oriented positions per base: kt_ctr_profile's contract (`hits` has offsets[n_reads] u32 entries indexed by global base,
+ * only valid window starts are written, the caller fills with KT_NO_KMER once) with another value.  A k-mer absent from
+ * the index gives 0.  A present one with table value v = 1 + 2 * G + S gives 1 + ((v - 1) ^ t): the slot's word 2 * G + S with
+ * t folded into its low bit, where t = 1 when the read shows the reverse complement of the canonical k-mer (f > r) and 0
+ * otherwise.  So (hits[j] - 1) >> 1 is G, and bit 0 of hits[j] - 1 is a = S ^ t: 1 means the read runs antiparallel to the
+ * indexed sequence there.  The strand comes out of the one walk that makes the key; no second pass is made.
+ * There is no n_parts: the index must be resident, as for kt_ctr_graph.  KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued
+ * on the context's stream.  KT_ERR_ARG: a null index, a bad mem, a null buffer with n_reads > 0, one shard of a sharded table. */
+int kt_ctr_thread_hits(kt_ctr *index, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *hits, int mem);
+
+/* Such hits folded into RUNS along the unitigs (no table: a function of the arrays).  hits: read_offsets[n_reads] entries;
+ * unitig_offsets: n_unitigs + 1 entries, the offsets of the sequences that were indexed; k: their k-mer size (1..31).
+ * With G_j = (hits[j] - 1) >> 1 and a_j = (hits[j] - 1) & 1, position j is a HIT when hits[j] is neither 0 nor KT_NO_KMER,
+ * G_j < unitig_offsets[n_unitigs] and the window lies inside its unitig: with u_j the unitig that holds base G_j
+ * (unitig_offsets[u] <= G_j < unitig_offsets[u + 1]) and p_j = G_j - unitig_offsets[u_j], p_j <= len_u - k.  Any other
+ * value that is neither 0 nor KT_NO_KMER is no hit and is counted as a bad value.
+ * j CONTINUES j - 1 when both are hits of the same read, a_j == a_{j-1}, u_j == u_{j-1} and G_j == G_{j-1} + 1 (a = 0) or
+ * G_j == G_{j-1} - 1 (a = 1).  (For k >= 2 the unitig condition follows from the others; for k = 1 it does not.)  A RUN is a
+ * maximal stretch of positions each continuing the one before; a walk around a circular unitig starts a new run where it
+ * wraps.  Runs are numbered by ascending j.  Per run: run_start = the global read base of its first k-mer, run_len = its
+ * k-mers, run_unitig = 2 * u + a, run_upos = p of its first k-mer in read order (the greatest p of an antiparallel run).
+ * run_offsets (n_reads + 1 entries, may be NULL): run_offsets[i] = the first run of read i, run_offsets[n_reads] = *n_runs.
+ * unitig_hits[u] / unitig_runs[u] (n_unitigs u64 each, may be NULL) are ADDED to - the hits and the runs on unitig u -, so the
+ * caller zeroes them once and accumulates over batches; they are added to by a call that writes runs (max_runs > 0) only, so
+ * that the counting call and the one sized by it do not add twice.  tally (may be NULL; KT_THREAD_TALLY u64, overwritten):
+ * [0] windows (entries other than KT_NO_KMER), [1] hits, [2] misses (value 0), [3] bad values, [4] runs, [5] reads with at
+ * least one hit.
+ * *n_runs is always exact.  max_runs == 0 only counts (the run arrays may be NULL) and still fills run_offsets and tally;
+ * 0 < max_runs < *n_runs writes nothing and returns KT_ERR_ARG with the number set.  KT_MEM_HOST synchronises; KT_MEM_DEVICE
+ * writes on the context's stream and synchronises to learn the sizes.  KT_ERR_ARG: a null ctx or n_runs, a bad mem, k outside
+ * 1..31, a null input with n_reads > 0 (null unitig_offsets with n_unitigs > 0), a null run array with max_runs > 0, a read of
+ * 2^32 bases or more, more than 2^31 - 1 unitigs or unitig bases.  On every one of these errors the outputs are untouched.
+ * Device scratch: one bit per read base and per unitig base, 16 bytes per 1024 read bases. */
+#define KT_THREAD_TALLY 6
+int kt_thread_runs(kt_ctx *ctx, const uint32_t *hits, const uint64_t *read_offsets, uint64_t n_reads,
+                   const uint64_t *unitig_offsets, uint64_t n_unitigs, int k, uint64_t *run_start, uint32_t *run_len,
+                   uint32_t *run_unitig, uint32_t *run_upos, uint64_t *run_offsets, uint64_t max_runs, uint64_t *n_runs,
+                   uint64_t *unitig_hits, uint64_t *unitig_runs, uint64_t *tally, int mem);
+
 /* Bottom-s MinHash sketches of the reads of a batch (`kmertools sketch`; what Mash does, and sourmash with `num`).
  * replaces: nothing - the reference has no such operation.  No table is involved.
  * A read's k-mers are its valid windows, canonical, as for every other k-mer walk here (1 <= k <= 31); a k-mer's hash is

@@ -2469,7 +2469,12 @@ std::string UnitigComputer::unitigs() {
         const uint64_t values[6] = {nl, edges, dead, isolated, self, max_deg};
         std::string s;
         append_stats_rows(s, names, values, 6);
-        if (std::string e = write_text_file(out_dir_ + "/unitigs.links.stats", s); !e.empty()) return e;
+        if (!thread_)
+            if (std::string e = write_text_file(out_dir_ + "/unitigs.links.stats", s); !e.empty()) return e;
+    }
+    if (thread_) {  // (`thread` writes its own statistics)
+        pt.t[3] += lap();
+        return thread_onto(bases, offsets, sums);
     }
     // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
     std::vector<uint64_t> lens((size_t)nu);
@@ -2494,6 +2499,122 @@ std::string UnitigComputer::unitigs() {
     std::string s;
     append_stats_rows(s, names, values, 8);
     if (std::string e = write_text_file(out_dir_ + "/unitigs.stats", s); !e.empty()) return e;
+    pt.t[3] += lap();
+    return "";
+}
+
+// `thread`: the unitigs (host arrays, as kt_ctr_unitigs filled them) become the index, the records of thread_reads_ are
+// walked in the usual batches.  The counted table has done its work by now and makes room for the index.
+std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets,
+                                        const std::vector<uint64_t> &sums) {
+    PhaseTimer pt("thread");
+    Lap lap;
+    const uint64_t nu = offsets.size() - 1, nb = offsets[nu], k = (uint64_t)ksize_;
+    if (table_) kt_ctr_destroy(table_);
+    table_ = nullptr;
+    const uint64_t windows = nb - nu * (k - 1);
+    if (kt_ctr_create(dev_.ctx, ksize_, std::max<uint64_t>(1024, windows + windows / 10 * 9), &table_) != KT_OK) return kt_last_error();
+    uint64_t indexed = 0;
+    static const uint64_t no_offsets[1] = {0};
+    if (kt_ctr_index_sequences(table_, nb ? bases.data() : (const uint8_t *)"", nu ? offsets.data() : no_offsets, nu, &indexed, KT_MEM_HOST) != KT_OK)
+        return kt_last_error();
+    pt.t[1] += lap();
+
+    SeqReader reader;
+    if (!reader.open(thread_reads_, false)) return reader.error();
+    const std::string gpath = out_dir_ + "/thread.gaf";
+    FILE *fg = stats_only_ ? nullptr : fopen(gpath.c_str(), "wb");
+    if (!stats_only_ && !fg) return "Unable to write to file: " + gpath;
+    Batch batch;
+    std::vector<uint32_t> hits, rl, ru, rp;
+    std::vector<uint64_t> rs, roff, uh((size_t)nu, 0), ur((size_t)nu, 0);
+    uint64_t n_reads = 0, n_bases = 0, n_windows = 0, n_hits = 0, n_misses = 0, n_runs = 0, n_chains = 0, with_hit = 0, whole = 0;
+    std::string text;
+    auto ulen = [&](uint32_t e) { return offsets[(e >> 1) + 1] - offsets[e >> 1]; };
+    std::string err = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, true, &pt, &lap, nullptr, [&](const Batch &b, const Cursor &) -> std::string {
+        const uint64_t n = b.n_reads(), total = b.offsets[n];
+        hits.assign(total, KT_NO_KMER);
+        if (total && kt_ctr_thread_hits(table_, bases_ptr(b), b.offsets.data(), n, hits.data(), KT_MEM_HOST) != KT_OK) return kt_last_error();
+        // a counting call, then one sized by it
+        uint64_t nr = 0, tally[KT_THREAD_TALLY] = {};
+        roff.resize(n + 1);
+        if (kt_thread_runs(dev_.ctx, hits.data(), b.offsets.data(), n, nu ? offsets.data() : no_offsets, nu, ksize_, nullptr, nullptr, nullptr,
+                           nullptr, roff.data(), 0, &nr, nullptr, nullptr, tally, KT_MEM_HOST) != KT_OK)
+            return kt_last_error();
+        rs.resize(nr), rl.resize(nr), ru.resize(nr), rp.resize(nr);
+        if (nr && kt_thread_runs(dev_.ctx, hits.data(), b.offsets.data(), n, offsets.data(), nu, ksize_, rs.data(), rl.data(), ru.data(), rp.data(),
+                                 roff.data(), nr, &nr, uh.data(), ur.data(), tally, KT_MEM_HOST) != KT_OK)
+            return kt_last_error();
+        pt.t[1] += lap();
+        n_reads += n, n_bases += total, n_windows += tally[0], n_hits += tally[1], n_misses += tally[2], n_runs += tally[4], with_hit += tally[5];
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t o = b.offsets[i], len = b.offsets[i + 1] - o;
+            uint64_t chains_here = 0, first_qs = 0, last_qe = 0;
+            for (uint64_t r = roff[i]; r < roff[i + 1];) {
+                // the chain that starts with run r: each further run starts where the one before stopped, at the first k-mer
+                // of its oriented unitig, the one before having ended at the last k-mer of its own
+                uint64_t e = r + 1, plen = ulen(ru[r]);
+                for (; e < roff[i + 1]; e++) {
+                    const uint64_t L = ulen(ru[e]), L0 = ulen(ru[e - 1]);
+                    const bool starts = rp[e] == (ru[e] & 1u ? L - k : 0);
+                    const bool ended = ru[e - 1] & 1u ? rp[e - 1] + 1 == rl[e - 1] : rp[e - 1] + rl[e - 1] - 1 == L0 - k;
+                    if (rs[e] != rs[e - 1] + rl[e - 1] || !starts || !ended) break;
+                    plen += L - (k - 1);
+                }
+                const uint64_t qs = rs[r] - o, qe = rs[e - 1] - o + rl[e - 1] - 1 + k;
+                const uint64_t ps = ru[r] & 1u ? ulen(ru[r]) - k - rp[r] : rp[r];
+                if (!chains_here++) first_qs = qs;
+                last_qe = qe;
+                if (fg) {
+                    append_name(text, b.headers[i]);
+                    text += '\t';
+                    append_uint(text, len);
+                    text += '\t';
+                    append_uint(text, qs);
+                    text += '\t';
+                    append_uint(text, qe);
+                    text += "\t+\t";
+                    for (uint64_t x = r; x < e; x++) {
+                        text += ru[x] & 1u ? '<' : '>';
+                        append_uint(text, ru[x] >> 1);
+                    }
+                    for (const uint64_t v : {plen, ps, ps + qe - qs, qe - qs, qe - qs}) {
+                        text += '\t';
+                        append_uint(text, v);
+                    }
+                    text += "\t255\n";
+                }
+                r = e;
+            }
+            n_chains += chains_here;
+            whole += chains_here == 1 && first_qs == 0 && last_qe == len;
+        }
+        pt.t[2] += lap();
+        if (fg && !text.empty() && fwrite(text.data(), 1, text.size(), fg) != text.size()) return "Unable to write to file: " + gpath;
+        text.clear();
+        pt.t[3] += lap();
+        return "";
+    });
+    if (fg && fclose(fg) != 0 && err.empty()) err = "Unable to write to file: " + gpath;
+    if (!err.empty()) return err;
+
+    uint64_t unitigs_hit = 0;
+    for (uint64_t u = 0; u < nu; u++) {
+        const uint64_t len = offsets[u + 1] - offsets[u], nodes = len - (k - 1);
+        char line[200];
+        const int h = snprintf(line, sizeof line, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6f\n", (unsigned long long)u, (unsigned long long)len,
+                               (unsigned long long)nodes, (unsigned long long)sums[u], (unsigned long long)uh[u], (unsigned long long)ur[u],
+                               (double)uh[u] / (double)nodes);
+        text.append(line, (size_t)h);
+        unitigs_hit += uh[u] != 0;
+    }
+    if (std::string e = write_text_file(out_dir_ + "/thread.unitigs", text); !e.empty()) return e;
+    static const char *names[10] = {"reads", "bases", "windows", "hits", "misses", "runs", "chains", "reads_with_hit",
+                                    "reads_one_chain_end_to_end", "unitigs_hit"};
+    const uint64_t values[10] = {n_reads, n_bases, n_windows, n_hits, n_misses, n_runs, n_chains, with_hit, whole, unitigs_hit};
+    std::string s;
+    append_stats_rows(s, names, values, 10);
+    if (std::string e = write_text_file(out_dir_ + "/thread.stats", s); !e.empty()) return e;
     pt.t[3] += lap();
     return "";
 }

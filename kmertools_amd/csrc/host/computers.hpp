@@ -506,9 +506,19 @@ class UnitigComputer {
     // are erased, for at most `rounds` rounds - the rounds of set_clip, where both are given
     void set_bubbles(uint32_t bubble_nodes, uint32_t rounds) { pop_ = true, bubble_nodes_ = bubble_nodes, clip_rounds_ = rounds; }
     void set_device(int d) { dev_.index = d; }
+    // `thread`: the unitigs are written as `unitigs --gfa` writes unitigs.fa and unitigs.gfa (stats_only: not at all) and no
+    // other unitigs.* file; then the records of reads_path are threaded onto them (kt_ctr_index_sequences over the unitigs,
+    // kt_ctr_thread_hits and kt_thread_runs per batch): {out_dir}/thread.gaf (one line per chain of runs; not with
+    // stats_only), thread.unitigs (per unitig: id, bases, nodes, count sum, hits, runs, hits / nodes) and thread.stats
+    void set_thread(std::string reads_path, bool stats_only) {
+        thread_ = true, thread_reads_ = std::move(reads_path), gfa_ = !stats_only, fa_links_ = false, stats_only_ = stats_only;
+    }
     std::string unitigs();  // "" or the error message
 
   private:
+    std::string thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &sums);
+    bool thread_ = false;
+    std::string thread_reads_;
     std::string in_path_, out_dir_;
     std::string table_file_;
     int ksize_;

@@ -5,7 +5,7 @@
 // filter, not in the reference) follows the same conventions, and so do `compare` (two inputs' k-mer tables side by side)
 // and `profile` (per-position k-mer counts and per-sequence medians) and `setop` (intersect / subtract / union / xor of two
 // inputs' k-mer tables) and `sketch` (MinHash sketches and Mash distances) and `graph` (de Bruijn adjacency of the counted
-// k-mers) and `unitigs` (that graph's maximal unitigs) and `hetmers` (the heterozygous k-mer pairs) and `card` (a HyperLogLog estimate of the distinct k-mers, which
+// k-mers) and `unitigs` (that graph's maximal unitigs) and `hetmers` (the heterozygous k-mer pairs) and `thread` (reads mapped onto those unitigs) and `card` (a HyperLogLog estimate of the distinct k-mers, which
 // also sizes the tables of the others: --estimate-size).
 #include <math.h>
 #include <stdio.h>
@@ -227,6 +227,7 @@ const char *HELP_MAIN =
     "  graph   De Bruijn adjacency, unitig ends and node census of the counted k-mers\n"
     "  unitigs Maximal unitigs of the de Bruijn graph of the counted k-mers\n"
     "  hetmers Heterozygous k-mer pairs of the counted k-mers and their coverage matrix\n"
+    "  thread  Map reads onto the unitigs of the counted k-mers (exact k-mer threading), GAF output\n"
     "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
     "  card    Estimate the number of distinct k-mers (HyperLogLog), sizes tables\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
@@ -1252,6 +1253,77 @@ int cmd_unitigs(int argc, char **argv, int from) {
     });
 }
 
+const char *HELP_THREAD =
+    "Map reads onto the unitigs of the counted k-mers (exact k-mer threading), GAF output\n\n"
+    "Counts the canonical k-mers of --alt-input (or loads --table), makes the unitigs of the k-mers with min-count <= count <=\n"
+    "max-count exactly as `unitigs --gfa` does, and indexes them: every k-mer of the graph lies in exactly one unitig, once.\n"
+    "Every record of --input is then walked: each of its k-mers (windows over a non-ACGT base are none) is a HIT at (unitig,\n"
+    "offset, orientation) or a miss.  A RUN is a maximal stretch of consecutive hits that step along one unitig in one\n"
+    "orientation; a walk around a circular unitig starts a new run where it wraps.  A CHAIN is a maximal sequence of runs of one\n"
+    "record in which each run starts at the read position where the one before stopped and at the first k-mer of its oriented\n"
+    "unitig, the one before having ended at the last k-mer of its own - a walk through the graph without a gap.\n\n"
+    "Writes to {output}:\n"
+    "  unitigs.fa, unitigs.gfa  byte for byte those of `unitigs --gfa` for the same table and range: the ids below are theirs\n"
+    "  thread.gaf      one line per chain, 12 tab-separated columns: 1 read id (the header up to the first white space), 2 read\n"
+    "                  length, 3 qstart (the read position of the first k-mer), 4 qend (the last k-mer's position + k), 5 '+',\n"
+    "                  6 the path, '>u' (as written) or '<u' (reverse complement) per run, 7 path length (the sum of the unitigs'\n"
+    "                  lengths - (k - 1) * (runs - 1)), 8 start on the path, 9 end on the path (start + qend - qstart), 10 and 11\n"
+    "                  qend - qstart (all bases match), 12 255.  A record without a hit has no line.\n"
+    "  thread.unitigs  per unitig: id, bases, nodes (k-mers), count sum of the graph, hits, runs, hits / nodes\n"
+    "  thread.stats    \"name<TAB>value\" lines: reads, bases, windows, hits, misses, runs, chains, reads_with_hit,\n"
+    "                  reads_one_chain_end_to_end, unitigs_hit\n"
+    "The whole table must fit the device memory, as for `unitigs`; the unitigs may hold at most 2^31 - 2 bases.\n\n"
+    "Usage: kmertools thread [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
+    "Options:\n"
+    "  -i, --input <INPUT>          The records to thread\n"
+    "  -a, --alt-input <ALT_INPUT>  Input file path, for k-mer counting [default: the input]\n"
+    "  -o, --output <OUTPUT>        Output directory path\n"
+    "  -k, --k-size <K_SIZE>        k size for counting\n"
+    "      --min-count <N>          Lowest count of a node [default: 1]\n"
+    "      --max-count <N>          Highest count of a node [default: 4294967295]\n"
+    "      --stats-only             Write thread.unitigs and thread.stats only\n"
+    "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for unitigs; the table lives in HBM)\n"
+    "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for unitigs)\n"
+    "      --device <DEVICE>        GPU index [default: 0]\n"
+    HELP_TABLE_ALT_INPUT
+    HELP_ESTIMATE
+    "  -h, --help                   Print help\n";
+
+int cmd_thread(int argc, char **argv, int from) {
+    const std::vector<Spec> specs = {{'i', "input", true},     {'a', "alt-input", true}, {'o', "output", true},  {'k', "k-size", true},
+                                     {0, "min-count", true},   {0, "max-count", true},   {0, "stats-only", false}, {'m', "memory", true},
+                                     {'t', "threads", true},   {0, "device", true},      SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+    const auto f = parse_flags(argc, argv, from, specs, HELP_THREAD);
+    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
+    // everything is checked before any device work and before the output directory is made
+    const uint64_t lo = ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
+    const uint64_t hi = ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (lo > hi)
+        usage_error("invalid values for '--min-count' and '--max-count': " + std::to_string(lo) + " is greater than " + std::to_string(hi));
+    (void)ranged(f, "memory", 6, 128, false, 6);
+    (void)ranged(f, "threads", 0, 1 << 20, false, 0);
+    const int device = (int)ranged(f, "device", 0, 63, false, 0);
+    const EstimateFlags est = estimate_flags(f);
+    const std::string table = table_flag(f, k, "table", "alt-input", "--alt-input <ALT_INPUT>");
+    const std::string counted = !table.empty() ? "" : f.count("alt-input") ? f.at("alt-input") : in;
+    for (const std::string &p : table.empty() ? std::vector<std::string>{in, counted} : std::vector<std::string>{in}) {
+        if (format_from_path(p) == SeqFormat::Unknown) {  // "-" included: the inputs are sized and read from files
+            fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", p.c_str());
+            return 101;
+        }
+    }
+    if (int rc = make_out_dir(out)) return rc;
+    return run_table_command(est, [&]() -> std::string {
+        UnitigComputer uc(counted, out, k);
+        uc.set_table_file(table);
+        uc.set_range((uint32_t)lo, (uint32_t)hi);
+        uc.set_thread(in, f.count("stats-only") != 0);
+        uc.set_device(device);
+        return uc.unitigs();
+    });
+}
+
 // hidden: parse a file and print its records (CPU-only reader tests)
 int cmd_debug_read(int argc, char **argv, int from) {
     if (from >= argc) return 2;
@@ -1386,5 +1458,6 @@ int main(int argc, char **argv) {
     if (cmd == "graph") return cmd_graph(argc, argv, 2);
     if (cmd == "unitigs") return cmd_unitigs(argc, argv, 2);
     if (cmd == "hetmers") return cmd_hetmers(argc, argv, 2);
+    if (cmd == "thread") return cmd_thread(argc, argv, 2);
     usage_error("unrecognized subcommand '" + cmd + "'");
 }

@@ -18,44 +18,20 @@
 // kt_profile.hip's.
 #include "kt_internal.hpp"
 #include "kt_launch.hpp"
+#include "kt_probe.hpp"
 #include "kt_segment.hpp"
 #include "kt_table.hpp"
 
-#ifndef KT_COV_GROUP
-#define KT_COV_GROUP 8
-#endif
-
 namespace {
 
+using ktprobe::GROUP;
+using ktprobe::probe_windows;  // the probe pipeline (kt_probe.hpp; kt_thread.hip takes the strand from it as well)
 using ktseg::SegArgs;
 using ktseg::SegShared;
 using kttab::Probed;
 
 constexpr int BLOCK = ktseg::BLOCK;
-constexpr uint32_t GROUP = KT_COV_GROUP;  // table probes in flight per thread
 constexpr uint32_t ROWS_LDS = 6144;  // u32 cells of bin rows staged per segment (24 KB)
-
-// The probe pipeline over a thread's 32 window starts of a staged segment, GROUP at a time (rolled, so the k-mers never sit
-// in registers all at once): the group's canonical k-mers, the home-slot loads of those that are k-mers (w.okm) of the
-// table's hash partition in flight together, then sink(jj, wr, cnt): bit u of `wr` = window start jj + u was looked up,
-// cnt[u] = its occurrences (0: absent).
-template <class Sink>
-__device__ __forceinline__ void probe_windows(const Probed &t, ktseg::Window &w, Sink &&sink) {
-#pragma unroll 1
-    for (uint32_t jj = 0; jj < ktseg::PER_THREAD; jj += GROUP) {
-        uint64_t key[GROUP];
-        uint32_t cnt[GROUP] = {};
-        uint32_t wr = (w.okm >> jj) & ((1u << GROUP) - 1u);
-#pragma unroll
-        for (uint32_t u = 0; u < GROUP; u++) {
-            key[u] = w.f < w.r ? w.f : w.r;
-            w.step();
-            if (!t.mine(key[u])) wr &= ~(1u << u);
-        }
-        t.counts(key, wr, [&](uint32_t u, uint32_t n) { cnt[u] = n; });
-        sink(jj, wr, cnt);
-    }
-}
 
 struct CovArgs {
     Probed t;

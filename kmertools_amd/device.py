@@ -406,6 +406,42 @@ class Context:
                                out["n_present"], out["min"], out["median"], out["max"], out["sum"], KT_MEM_HOST)
         return out
 
+    # -- thread: hits (Counter.thread_hits) folded into runs along the unitigs -------------------
+    def thread_runs(self, hits, read_offsets, n_reads, unitig_offsets, n_unitigs, k, run_start=None, run_len=None,
+                    run_unitig=None, run_upos=None, run_offsets=None, max_runs=0, unitig_hits=None, unitig_runs=None,
+                    tally=None, mem=KT_MEM_DEVICE):
+        """maximal stretches of hits that step along one unitig in one orientation: per run its first read base (u64), its
+        k-mers, 2 * unitig + antiparallel and the offset of its first k-mer in the unitig (u32 arrays of max_runs);
+        run_offsets (u64, n_reads + 1) = the first run of every read; unitig_hits / unitig_runs (u64 per unitig) are added
+        to by a call that writes runs; tally (u64[6], overwritten) = windows, hits, misses, bad values, runs, reads with a
+        hit.  max_runs = 0 only counts.  Returns the number of runs; raises KmertoolsError (KT_ERR_ARG) when max_runs is
+        too small (kt_thread_runs)."""
+        n = C.c_uint64()
+        check(_lib.lib().kt_thread_runs(self._h, _ptr(hits), _ptr(read_offsets), int(n_reads), _ptr(unitig_offsets),
+                                        int(n_unitigs), int(k), _ptr(run_start), _ptr(run_len), _ptr(run_unitig),
+                                        _ptr(run_upos), _ptr(run_offsets), int(max_runs), C.byref(n), _ptr(unitig_hits),
+                                        _ptr(unitig_runs), _ptr(tally), mem))
+        return n.value
+
+    def thread_runs_host(self, hits, read_offsets, unitig_offsets, k, unitig_hits=None, unitig_runs=None):
+        """-> {"run_start" u64, "run_len", "run_unitig", "run_upos" u32, "run_offsets" u64, "tally" u64[6]} of host arrays;
+        unitig_hits / unitig_runs (u64 per unitig, or None) are added to.  A counting call, then one sized by it."""
+        hits = np.ascontiguousarray(hits, np.uint32)
+        read_offsets = np.ascontiguousarray(read_offsets, np.uint64)
+        unitig_offsets = np.ascontiguousarray(unitig_offsets, np.uint64)
+        n, nu = len(read_offsets) - 1, len(unitig_offsets) - 1
+        out = {"run_offsets": np.zeros(n + 1, np.uint64), "tally": np.zeros(_lib.KT_THREAD_TALLY, np.uint64)}
+        h = hits if hits.size else np.zeros(1, np.uint32)
+        nr = self.thread_runs(h, read_offsets, n, unitig_offsets, nu, k, run_offsets=out["run_offsets"], tally=out["tally"],
+                              mem=KT_MEM_HOST)
+        out["run_start"] = np.zeros(nr, np.uint64)
+        for name in ("run_len", "run_unitig", "run_upos"):
+            out[name] = np.zeros(nr, np.uint32)
+        if nr:
+            self.thread_runs(h, read_offsets, n, unitig_offsets, nu, k, out["run_start"], out["run_len"], out["run_unitig"],
+                             out["run_upos"], out["run_offsets"], nr, unitig_hits, unitig_runs, out["tally"], KT_MEM_HOST)
+        return out
+
     # -- correct: the decision over a support array (Counter.correct_support) ------------------
     def correct_apply(self, bases, offsets, n_reads, support, min_support=1, max_corrections=0, out_bases=None,
                       n_single=None, n_ambiguous=None, mem=KT_MEM_DEVICE):
@@ -659,6 +695,38 @@ class Counter:
         if n > 0 and prof.size:
             self.profile(bases, offsets, n, prof, KT_MEM_HOST)
         return prof
+
+    # -- thread: this table as a k-mer -> position index of a set of sequences (the unitigs) ------
+    def index_sequences(self, bases, offsets, n_seqs, mem=KT_MEM_DEVICE):
+        """fills this EMPTY table with (canonical k-mer, 1 + 2 * global base of the window + (the sequence shows its reverse
+        complement)) for every window of the sequences; returns the number of windows.  Raises KmertoolsError (KT_ERR_ARG)
+        when a k-mer occurs twice (the table is cleared) or the sequences hold more than 2^31 - 2 bases
+        (kt_ctr_index_sequences)"""
+        n = C.c_uint64()
+        check(_lib.lib().kt_ctr_index_sequences(self._h, _ptr(bases), _ptr(offsets), int(n_seqs), C.byref(n), mem))
+        return n.value
+
+    def index_sequences_host(self, bases, offsets):
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        return self.index_sequences(bases if bases.size else np.zeros(1, np.uint8), offsets, len(offsets) - 1, KT_MEM_HOST)
+
+    def thread_hits(self, bases, offsets, n_reads, hits, mem=KT_MEM_DEVICE):
+        """writes, for every valid window, 0 when its k-mer is not in this index and otherwise 1 + 2 * G + a - G: where the
+        k-mer lies in the indexed sequences, a = 1: the read runs antiparallel to them there - into hits[global base index
+        of its start], a u32 array of offsets[n_reads] entries that the caller filled with NO_KMER (kt_ctr_thread_hits)"""
+        check(_lib.lib().kt_ctr_thread_hits(self._h, _ptr(bases), _ptr(offsets), int(n_reads), _ptr(hits), mem))
+        return hits
+
+    def thread_hits_host(self, bases, offsets):
+        """-> u32 array, one entry per base (NO_KMER where no k-mer starts)"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        hits = np.full(int(offsets[-1]) if n > 0 else 0, NO_KMER, np.uint32)
+        if n > 0 and hits.size:
+            self.thread_hits(bases, offsets, n, hits, KT_MEM_HOST)
+        return hits
 
     # -- correct: repair read errors from the solid k-mers of this table ---------------------------
     def correct_support(self, bases, offsets, n_reads, profile, min_count, max_count, support, mem=KT_MEM_DEVICE,
@@ -1022,6 +1090,36 @@ class Counter:
             t.close()
             raise
         return t
+
+
+class UnitigIndex:
+    """The k-mer -> (unitig, offset, strand) index of a set of unitigs (host arrays: bases u8, offsets u64, as
+    Counter.unitigs returns them): owns the index table, sized from the number of k-mers the unitigs can hold."""
+
+    def __init__(self, ctx, k, bases, offsets):
+        self.ctx, self.k = ctx, k
+        self.offsets = np.ascontiguousarray(offsets, np.uint64)
+        bases = np.ascontiguousarray(bases, np.uint8)
+        lens = np.diff(self.offsets.astype(np.int64))
+        windows = int(np.maximum(lens - (k - 1), 0).sum())
+        self.table = Counter(ctx, k, max(1024, windows + windows // 10 * 9))  # (1.9 slots per entry, as the command line sizes)
+        try:
+            self.n_kmers = self.table.index_sequences_host(bases, self.offsets)
+        except Exception:
+            self.table.close()
+            raise
+
+    def close(self):
+        self.table.close()
+
+    def thread_host(self, bases, offsets, unitig_hits=None, unitig_runs=None):
+        """-> {"hits" u32 per base, "run_start", "run_len", "run_unitig", "run_upos", "run_offsets", "tally"} of host arrays
+        for a batch of reads (Counter.thread_hits_host, then Context.thread_runs_host)"""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        hits = self.table.thread_hits_host(bases, offsets)
+        out = self.ctx.thread_runs_host(hits, offsets, self.offsets, self.k, unitig_hits, unitig_runs)
+        out["hits"] = hits
+        return out
 
 
 class Sharded:
