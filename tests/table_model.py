@@ -13,6 +13,8 @@ answer for every call that reads a table - the restatements the reader tests alr
 A Model is also the `Table` those restatements take (keys, counts, count(keys)).  tests/test_table_lifecycle.py walks one
 kt_ctr and one Model through the same calls and compares every reader with it; the table's hash is restated here too
 (home_of), for the one thing a reference of the CONTENT cannot say: which keys' probe sequences wrap at a range's end."""
+import collections
+import functools
 import os
 import sys
 
@@ -107,13 +109,42 @@ class Model:
 
 # ---- the table's hash, restated (kt_device.hpp khash / nhash_top, kt_table.hpp probe_of) -----------------------------------
 
-def home_of(keys, k, log2_slots):
-    """(range, position inside it) of the home slot of canonical k-mers in a table of 2^log2_slots slots (a whole power of
-    two of at least 2^15: ranges of 8192 slots).  k <= 16: the top bits of nhash, a bijection of the 2k-bit words; else of
-    khash."""
+class Geometry(collections.namedtuple("Geometry", "cap n m8 range_slots n_ranges")):
+    """a table's shape (kt_table.hpp kttab::Geom): cap slots addressed by the top n hash bits, n_ranges ranges of range_slots
+    slots each (1024 * m8, or the whole table when it has fewer than 8192 slots)"""
+    __slots__ = ()
+
+    @property
+    def shift(self):
+        return 64 - self.n
+
+
+def geometry(cap_request, k=0):
+    """make_geom restated: the request rounded up to a power of two of at least 1024 slots and, from 2^15 slots on, down to
+    the least of 5..8 eighths of it that still holds the request (k does not change the shape: it selects the hash)"""
+    p, n = 1024, 10
+    while p < cap_request:
+        p, n = p << 1, n + 1
+    m8 = 8
+    if n >= 15:
+        while m8 > 5 and p // 8 * (m8 - 1) >= cap_request:
+            m8 -= 1
+    cap = p // 8 * m8
+    rs = cap if n < 13 else 1024 * m8
+    return Geometry(cap, n, m8, rs, cap // rs)
+
+
+def home_of(keys, k, geom):
+    """(range, position inside it) of the home slot of canonical k-mers in a table of shape `geom` - a Geometry, or the
+    log2 of a whole power of two of at least 2^15 slots (ranges of 8192 slots).  k <= 16: the top bits of nhash, a
+    bijection of the 2k-bit words; else of khash.  A table of fewer than 8192 slots is one range, the position the top n
+    bits themselves; else the top n - 13 bits are the range and the low 13, scaled to the range's 1024 * m8 slots, the
+    position (probe_of)."""
     keys = np.asarray(keys, np.uint64)
-    n = log2_slots
-    assert n >= 15
+    if not isinstance(geom, Geometry):
+        assert geom >= 15
+        geom = Geometry(1 << geom, geom, 8, 8192, 1 << (geom - 13))
+    n = geom.n
     if k <= 16:
         kb = 2 * k
         t = ((keys & np.uint64(0xFFFFFFFF)) * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)
@@ -124,7 +155,50 @@ def home_of(keys, k, log2_slots):
         h = keys * np.uint64(0x9E3779B97F4A7C15)  # (wraps modulo 2^64)
         h ^= h >> np.uint64(32)
         x = h >> np.uint64(64 - n)
-    return (x >> np.uint64(13)).astype(np.int64), (x & np.uint64(8191)).astype(np.int64)
+    x = x.astype(np.int64)
+    if n < 13:
+        return np.zeros(len(x), np.int64), x
+    return x >> 13, ((x & 8191) * geom.m8) >> 3
+
+
+class Layout:
+    """where linear probing puts keys: per key its range, home position, slot and displacement and whether its probe
+    sequence passed the range's end; per range how many keys it holds"""
+
+
+def layout(keys, k, geom):
+    """the keys placed range by range, in the order given: each goes to the first free slot from its home position on,
+    circularly inside its range.  Which slots end up taken, and how many keys pass a range's end, does not depend on the
+    order.  Raises when a range gets more keys than it has slots."""
+    keys = np.asarray(keys, np.uint64)
+    if not isinstance(geom, Geometry):
+        geom = Geometry(1 << geom, geom, 8, 8192, 1 << (geom - 13))
+    rs = geom.range_slots
+    L = Layout()
+    L.range, L.home = home_of(keys, k, geom)
+    L.fill = np.bincount(L.range, minlength=geom.n_ranges)
+    assert len(L.fill) == geom.n_ranges and (L.fill <= rs).all(), "a range holds more keys than slots"
+    L.slot = np.zeros(len(keys), np.int64)
+    for r in np.flatnonzero(L.fill):
+        nxt = list(range(rs + 1))  # nxt[s]: a slot >= s that may be free (followed to a fixed point); rs: past the end
+        members = np.flatnonzero(L.range == r)
+        for i, h in zip(members.tolist(), L.home[members].tolist()):
+            s = h
+            while True:
+                path = []
+                while nxt[s] != s:
+                    path.append(s)
+                    s = nxt[s]
+                for q in path:
+                    nxt[q] = s
+                if s < rs:
+                    break
+                s = 0  # (past the range's last slot: on from its first)
+            nxt[s] = s + 1
+            L.slot[i] = s
+    L.wrapped = L.slot < L.home
+    L.displacement = np.where(L.wrapped, L.slot + rs - L.home, L.slot - L.home)
+    return L
 
 
 def canonical_keys(rng, k, n):
@@ -133,15 +207,36 @@ def canonical_keys(rng, k, n):
     return np.sort(rng.choice(np.unique(gr.canon_np(x, k)), n, replace=False))
 
 
-def keys_homed_at(k, log2_slots, rng_range, position, n, seed=7):
-    """n distinct canonical k-mers whose home slot is `position` of range `rng_range`, by search over random k-mers"""
-    rng = np.random.default_rng(seed)
+class _Pool:
+    """the random canonical k-mers keys_homed_at searches: one stream per (k, seed), its draws kept (16 MB each; a search
+    rarely needs a third), so that every geometry and window of a test module searches the same arrays"""
+
+    def __init__(self, k, seed):
+        self.k, self.rng, self.drawn = k, np.random.default_rng(seed), []
+
+    def draw(self, i):
+        while len(self.drawn) <= i:
+            x = self.rng.integers(0, 1 << (2 * self.k), size=1 << 22, dtype=np.uint64)
+            x = x[x <= gr.rc_np(x, self.k)]
+            x.setflags(write=False)
+            self.drawn.append(x)
+        return self.drawn[i]
+
+
+@functools.lru_cache(maxsize=4)
+def _pool(k, seed):
+    return _Pool(k, seed)
+
+
+def keys_homed_at(k, geom, rng_range, position, n, seed=7):
+    """n distinct canonical k-mers (ascending) whose home slot lies in range `rng_range` at `position` - one position, or
+    a window (first, last) of positions, None for anywhere in the range - by search over random k-mers"""
+    lo, hi = (0, 1 << 62) if position is None else position if isinstance(position, tuple) else (position, position)
     found = np.zeros(0, np.uint64)
-    for _ in range(64):
-        x = rng.integers(0, 1 << (2 * k), size=1 << 22, dtype=np.uint64)
-        x = x[x <= gr.rc_np(x, k)]
-        r, p = home_of(x, k, log2_slots)
-        found = np.unique(np.concatenate([found, x[(r == rng_range) & (p == position)]]))
+    for i in range(64):
+        x = _pool(k, seed).draw(i)
+        r, p = home_of(x, k, geom)
+        found = np.unique(np.concatenate([found, x[(r == rng_range) & (p >= lo) & (p <= hi)]]))
         if len(found) >= n:
             return found[:n]
-    raise AssertionError("no %d keys homed at (%d, %d)" % (n, rng_range, position))
+    raise AssertionError("no %d keys homed at (%d, %s)" % (n, rng_range, position))
