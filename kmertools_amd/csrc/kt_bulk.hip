@@ -67,9 +67,6 @@ using kttab::Slot;
 using kttab::TableRef;
 
 constexpr int BLOCK = ktseg::BLOCK;       // 256
-#ifndef KT_BUILD_T
-#define KT_BUILD_T 1024
-#endif
 #ifndef KT_ABLATION
 #define KT_ABLATION 0  // 1 (tools/build_variant*.sh only): KT_BUILD_DBG bits can switch phases of build_kernel off for
 #endif                 // profiling.  The shipped library has no switch that skips work.
@@ -2096,7 +2093,7 @@ __global__ __launch_bounds__((swwc_t<K>()), (swwc_t<K>() / 256)) void part2_swwc
 //    bookkeeping, and the CU's scalar unit is busy half of the kernel's time): 27.6 against 18.5 ms.
 static_assert(LOG2_S == kttab::LOG2_RANGE, "a fine bucket is a range of the table");
 
-constexpr int BUILD_T = KT_BUILD_T;
+using kttab::BUILD_T;  // (KT_BUILD_T, kt_table.hpp)
 // claim lists of a dense build: the slot of every key a wave has placed first, in the order it placed them - three keys per
 // lane at most (a range of up to 3072 keys; ranges of hashed distinct keys hold ~2900)
 constexpr uint32_t LIST_CAP = 192, LIST_KEYS = LIST_CAP * (BUILD_T / 64);
@@ -2751,207 +2748,6 @@ __global__ __launch_bounds__(BLOCK) void spill_insert_kernel(const uint64_t *__r
         atomicAdd(reinterpret_cast<unsigned long long *>(distinct), (unsigned long long)fresh);
 }
 
-// dense -> image, in place: one workgroup per range reads the range's packed entries, inserts them into the LDS image
-// (distinct keys: plain CAS probing, counts carried along) and writes the whole range
-__global__ __launch_bounds__(BUILD_T) void materialize_kernel(Slot *__restrict__ slots, uint32_t RS, uint64_t n_ranges,
-                                                              uint32_t shift, uint32_t m8, uint32_t kbits,
-                                                              const uint32_t *__restrict__ range_counts) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    unsigned long long *const skeys = reinterpret_cast<unsigned long long *>(smem_raw);
-    uint32_t *const scounts = reinterpret_cast<uint32_t *>(smem_raw + (size_t)RS * 8);
-    const uint32_t tid = threadIdx.x;
-    for (uint64_t r = blockIdx.x; r < n_ranges; r += gridDim.x) {
-        for (uint32_t i = tid; i < RS; i += BUILD_T) {
-            skeys[i] = KT_EMPTY_KEY;
-            scounts[i] = 0;
-        }
-        ktd::lds_barrier();
-        const uint32_t D = range_counts[r];
-        uint4 *rs = reinterpret_cast<uint4 *>(slots + r * RS);
-        const uint64_t *dkeys = reinterpret_cast<const uint64_t *>(rs);  // the dense layout: keys[D], counts[D] at 8 * RS
-        const uint32_t *dcounts = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(rs) + (size_t)RS * 8);
-        for (uint32_t i = tid; i < D; i += BUILD_T) {
-            const uint64_t key = dkeys[i];
-            const uint32_t cnt = dcounts[i];
-            uint32_t s = (((uint32_t)(ktd::khash_k(key, kbits) >> shift) & (S - 1)) * m8) >> 3;
-            while (atomicCAS(&skeys[s], (unsigned long long)KT_EMPTY_KEY, (unsigned long long)key) != KT_EMPTY_KEY)
-                s = s + 1 == RS ? 0 : s + 1;  // (D <= RS: a free slot exists)
-            scounts[s] = cnt;
-        }
-        ktd::lds_barrier();  // (the image below overwrites what was just read: everything is in LDS by now)
-        for (uint32_t i = tid; i < RS; i += BUILD_T) {
-            const uint64_t key = skeys[i];
-            typedef uint32_t raw4 __attribute__((ext_vector_type(4)));
-            const raw4 raw = {(uint32_t)key, (uint32_t)(key >> 32), scounts[i], 0u};
-            __builtin_nontemporal_store(raw, reinterpret_cast<raw4 *>(rs + i));
-        }
-        ktd::lds_barrier();
-    }
-}
-
-// ---- dense table -> (keys, counts) ----------------------------------------------------------------------------
-// Ranges are taken in tiles of 256: tile sums (coalesced), a one-workgroup scan of the tile sums, and the copy kernel
-// scans the 256 counts of its tile itself - every read and write coalesced, no atomics, output in range order.
-constexpr uint32_t XT = 256;
-__global__ __launch_bounds__(XT) void tile_sums_kernel(const uint32_t *__restrict__ counts, uint64_t n,
-                                                       uint64_t *__restrict__ tile_sums) {
-    __shared__ uint32_t part[XT / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * XT + threadIdx.x;
-    uint32_t v = i < n ? counts[i] : 0u;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = (uint64_t)part[0] + part[1] + part[2] + part[3];
-}
-// tile_sums[t] -> exclusive prefix; tile_sums[n_tiles] = total.  One workgroup, tiles in chunks of 1024.
-__global__ __launch_bounds__(1024) void tile_scan_kernel(uint64_t *__restrict__ tile_sums, uint64_t n_tiles) {
-    __shared__ uint64_t wtot[16];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint64_t c0 = 0; c0 < n_tiles; c0 += 1024) {
-        const uint64_t i = c0 + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tile_sums[i] : 0;
-        uint64_t inc = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t u = __shfl_up(inc, off, 64);
-            if ((threadIdx.x & 63) >= (uint32_t)off) inc += u;
-        }
-        if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint64_t base = carry;
-        for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) base += wtot[w];
-        if (i < n_tiles) tile_sums[i] = base + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = base + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tile_sums[n_tiles] = carry;
-}
-// the counting pass of a filtered export (kt_table_dense_export_range): kept[r] = entries of range r with lo <= occurrences
-// <= hi, tile_sums[tile] = their sum over the tile's 256 ranges.  A wave per range, four 16-byte loads of counts in
-// flight per lane.
-__global__ __launch_bounds__(XT) void dense_kept_kernel(const Slot *__restrict__ slots, uint32_t RS, uint64_t n_ranges,
-                                                        const uint32_t *__restrict__ range_counts, uint32_t lo, uint32_t hi,
-                                                        uint32_t *__restrict__ kept, uint64_t *__restrict__ tile_sums) {
-    __shared__ uint32_t wsum[XT / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t r0 = (uint64_t)blockIdx.x * XT;
-    uint32_t mine = 0;
-    for (uint32_t r = wave; r < XT && r0 + r < n_ranges; r += XT / 64) {
-        const uint32_t D = range_counts[r0 + r], nq = (D + 3u) / 4u;
-        const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(slots + (r0 + r) * RS) + (size_t)RS * 8);
-        uint32_t k = 0;
-        for (uint32_t q0 = 0; q0 < nq; q0 += 256) {
-            uint4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t qi = q0 + 64u * u + lane;
-                v[u] = qi < nq ? q[qi] : make_uint4(0u, 0u, 0u, 0u);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t e = (q0 + 64u * u + lane) * 4u;
-                const uint32_t c0 = v[u].x + 1u, c1 = v[u].y + 1u, c2 = v[u].z + 1u, c3 = v[u].w + 1u;  // occurrences
-                k += (e < D && c0 >= lo && c0 <= hi) + (e + 1u < D && c1 >= lo && c1 <= hi) +
-                     (e + 2u < D && c2 >= lo && c2 <= hi) + (e + 3u < D && c3 >= lo && c3 <= hi);
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) k += __shfl_down(k, o, 64);
-        if (lane == 0) kept[r0 + r] = k;
-        mine += k;  // (lane 0's sum is the wave's)
-    }
-    if (lane == 0) wsum[wave] = mine;
-    __syncthreads();
-    if (tid == 0) tile_sums[blockIdx.x] = (uint64_t)wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-// FILTER: the ranges' offsets come from kept[] (dense_kept_kernel) and only the entries with lo <= occurrences <= hi are
-// copied (a ballot per 64 entries, in the range's order)
-template <bool FILTER>
-__global__ __launch_bounds__(XT) void dense_export_kernel(const Slot *__restrict__ slots, uint32_t RS, uint64_t n_ranges,
-                                                          const uint32_t *__restrict__ range_counts,
-                                                          const uint64_t *__restrict__ tile_offsets,
-                                                          uint64_t *__restrict__ out_keys,
-                                                          uint32_t *__restrict__ out_counts, uint64_t max_out,
-                                                          const uint32_t *__restrict__ kept, uint32_t lo, uint32_t hi) {
-    __shared__ uint32_t offs[XT + 1], cnt[XT], wt[XT / 64];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t r0 = (uint64_t)blockIdx.x * XT;
-    const uint32_t c = r0 + tid < n_ranges ? (FILTER ? kept : range_counts)[r0 + tid] : 0u;
-    uint32_t inc = c;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t u = __shfl_up(inc, off, 64);
-        if ((tid & 63) >= (uint32_t)off) inc += u;
-    }
-    if ((tid & 63) == 63) wt[tid >> 6] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < (tid >> 6); w++) base += wt[w];
-    offs[tid] = base + inc - c;
-    cnt[tid] = c;
-    __syncthreads();
-    const uint64_t t0 = tile_offsets[blockIdx.x];
-    if constexpr (FILTER) {
-        const uint32_t lane = tid & 63u;
-        for (uint32_t r = tid >> 6; r < XT && r0 + r < n_ranges; r += XT / 64) {
-            const uint32_t D = range_counts[r0 + r];
-            uint64_t o = t0 + offs[r];
-            const char *rs = reinterpret_cast<const char *>(slots + (r0 + r) * RS);
-            const uint64_t *dkeys = reinterpret_cast<const uint64_t *>(rs);
-            const uint32_t *dcounts = reinterpret_cast<const uint32_t *>(rs + (size_t)RS * 8);
-            for (uint32_t i0 = 0; i0 < D; i0 += 256) {
-                uint32_t vc[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint32_t i = i0 + 64u * u + lane;
-                    vc[u] = i < D ? dcounts[i] + 1u : 0u;  // occurrences (0: beyond the range's entries)
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint32_t i = i0 + 64u * u + lane;
-                    const bool keep = i < D && vc[u] >= lo && vc[u] <= hi;
-                    const uint64_t bal = __ballot(keep);
-                    if (keep) {
-                        const uint64_t at = o + __popcll(bal & ((1ull << lane) - 1ull));
-                        if (at < max_out) {
-                            out_keys[at] = dkeys[i];
-                            out_counts[at] = vc[u];
-                        }
-                    }
-                    o += __popcll(bal);
-                }
-            }
-        }
-        return;
-    }
-    // every wave copies ranges of its own (no workgroup barrier in the loop), four loads in flight per lane
-    for (uint32_t r = tid >> 6; r < XT && r0 + r < n_ranges; r += XT / 64) {
-        const uint32_t D = cnt[r];
-        const uint64_t o = t0 + offs[r];
-        const char *rs = reinterpret_cast<const char *>(slots + (r0 + r) * RS);
-        const uint64_t *dkeys = reinterpret_cast<const uint64_t *>(rs);
-        const uint32_t *dcounts = reinterpret_cast<const uint32_t *>(rs + (size_t)RS * 8);
-        for (uint32_t i0 = tid & 63u; i0 < D; i0 += 256) {
-            uint64_t vk[4];
-            uint32_t vc[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t i = i0 + 64u * u;
-                vk[u] = i < D ? dkeys[i] : 0;
-                vc[u] = i < D ? dcounts[i] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t i = i0 + 64u * u;
-                if (i < D && o + i < max_out) {
-                    out_keys[o + i] = vk[u];
-                    out_counts[o + i] = vc[u] + 1u;  // stored value is occurrences - 1
-                }
-            }
-        }
-    }
-}
-
 uint64_t env_u64(const char *name, uint64_t dflt) {
     const char *s = getenv(name);
     if (!s || !*s) return dflt;
@@ -3116,6 +2912,7 @@ struct kt_bulk_job {
     Level1 l1 = L1_EXACT;
     Level2 l2 = L2_GENERAL;
     Build built = BUILD_MERGE;
+    bool left_dense = false, left_in_target = false;  // how build() left the ranges: kt_ctr::built, once the job has succeeded
     uint32_t build_grid = 0;  // the build's launch: workgroups, dynamic LDS
     size_t build_lds = 0;
     size_t ksz() const { return narrow ? 4 : 8; }
@@ -3176,10 +2973,10 @@ struct kt_bulk_job {
         ctr = table;
         ctx = table->ctx;
         kn = knobs;
-        ctr->stage_n = 0;  // (a job changes the table: kt_ctr_export_stage's entries are stale)
+        ctr->stage.drop();  // (a job changes the table: kt_ctr_export_stage's entries are stale)
         open = false;
         srcs.clear();
-        merge = !ctr->empty;  // the table holds data: every range is rebuilt from what it has + the batch
+        merge = !ctr->fresh();  // the table holds data: every range is rebuilt from what it has + the batch
         if (merge)
             if (int rc = kt_table_image(ctr)) return rc;  // (a densely packed table gets its probing image first)
         narrow = ctr->k <= 16 && ctr->kbits != 0;  // (kt_ctr_create: every table of k <= 16 hashes with ktd::nhash)
@@ -3395,13 +3192,14 @@ struct kt_bulk_job {
         // 2: the caller's arrays are smaller than the table: the table is NOT lost - the counts stay in the table's own
         //    slots, kt_ctr_size / kt_ctr_export into large enough arrays work - and the call that counted reports
         //    KT_ERR_ARG once the build is done.
-        if (fl & 2u) ctr->xt_too_small = true;
+        const bool too_small = fl & 2u;
+        if (too_small) ctr->target_too_small();
         fl &= ~6u;
         KT_HIP(hipMemcpyAsync(ctr->flags, &fl, 4, hipMemcpyHostToDevice, ctx->stream));
         KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, ctx->stream));  // (a dense build starts from an empty table)
         KT_HIP(hipStreamSynchronize(ctx->stream));                 // (fl lives on this stack frame)
         if (kn.verbose) fprintf(stderr, "[bulk] export-target build redone into the table (%s)\n",
-                                ctr->xt_too_small ? "arrays too small" : "uneven blocks");
+                                too_small ? "arrays too small" : "uneven blocks");
         return KT_OK;
     }
 
@@ -3430,12 +3228,11 @@ struct kt_bulk_job {
         }
         if (!ext)
             if (int rc = launch_build<K>(built, ExtOut{})) return rc;
-        ctr->dense = dense;
-        ctr->dense_ext = ext;
+        left_dense = dense;
+        left_in_target = ext;
         if (dense) return KT_OK;
-        TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
         return launch(spill_insert_kernel, dim3(ctx->n_cu), dim3(BLOCK), 0, ctx->stream, m.spill_n, m.spill_keys, m.spill_counts,
-                      m.spill_cap, t, ctr->distinct);
+                      m.spill_cap, ktl::writable_of(ctr), ctr->distinct);
     }
 
     // KT_BULK_VERBOSE: one line per job - what it was planned for, and which kernels the stages above chose
@@ -3547,15 +3344,14 @@ int kt_ctr_count_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs)
     std::vector<uint64_t> h;
     const uint64_t blocks = record_descriptors(runs, n_runs, &h);
     if (!blocks) return KT_OK;
-    ctr->stage_n = 0;
-    if (int rc = ktl::table_ready(ctr)) return rc;  // (a dense table gets its probing image, a deferred clear happens now)
-    ctr->empty = false;
+    TableRef t;
+    if (int rc = ktl::table_write(ctr, &t)) return rc;  // (a dense table gets its probing image, a deferred clear happens now)
+    if (int rc = ktl::table_ready(ctr)) return rc;      // (an overflowed table is reported)
     uint64_t *d = nullptr;
     if (int rc = ctx->claim(kt::AUX2, h.size() * 8, "kt_ctr_count_records", &d)) return rc;
     KT_HIP(hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     KT_HIP(hipStreamSynchronize(ctx->stream));  // (h lives on this frame)
     RecordSource src{(const ktsk::RecRun *)d, (const uint64_t *)d + 2 * (size_t)n_runs, n_runs, (uint32_t)ctr->k, blocks};
-    TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
     return launch(count_records_kernel, dim3(ktl::grid_for(ctx, blocks, 8)), dim3(BLOCK), 0, ctx->stream, src, t, ctr->distinct);
 }
 
@@ -3573,10 +3369,8 @@ int kt_bulk_finish(kt_ctr *ctr) {
     });
     job->srcs.clear();
     if (rc == KT_OK) {
-        ctr->empty = false;
-        ctr->needs_clear = false;  // every slot was written
-        if (ctr->xt_too_small) {   // (the table is complete and usable; the caller's export arrays hold nothing)
-            ctr->xt_too_small = false;
+        ctr->built(job->left_dense, job->left_in_target);  // every slot was written
+        if (ctr->take_target_too_small()) {  // (the table is complete and usable; the caller's export arrays hold nothing)
             rc = kt::fail(KT_ERR_ARG, "kt_ctr_export_target: the arrays are smaller than the table - the counts are in the table "
                                       "(kt_ctr_size, then kt_ctr_export into arrays of that size), the target arrays hold nothing");
         }
@@ -3636,82 +3430,6 @@ int kt_bulk_build_keys(kt_ctr *ctr, const uint64_t *d_keys, uint64_t n_keys, int
     if (int rc = kt_bulk_add_keys(ctr, d_keys, n_keys)) return rc;
     if (int rc = kt_bulk_finish(ctr)) return rc;
     *done = 1;
-    return KT_OK;
-}
-
-// the probing image of a table that the last build left densely packed (in place; no-op otherwise)
-int kt_table_image(kt_ctr *ctr) {
-    if (!ctr->dense) return KT_OK;
-    if (ctr->dense_ext) {  // the entries are the caller's export arrays: back into an empty table, as (key, count) pairs
-        ctr->dense = false;
-        ctr->dense_ext = false;
-        // entries that kt_ctr_export_stage staged by pointing at those arrays go with them: from here on they are the
-        // caller's to reuse, and a fetch must not hand out what it has put there (kt_ctr_export_fetch says "stage first")
-        if (ctr->stage_keys == ctr->xt_keys) ctr->stage_n = 0;
-        return kt_ctr_reload_pairs(ctr, ctr->xt_keys, ctr->xt_counts);
-    }
-    kt_ctx *ctx = ctr->ctx;
-    const uint32_t RS = ctr->m8 << (LOG2_S - 3);
-    const uint64_t n_ranges = ctr->cap / RS;
-    uint64_t g = (uint64_t)ctx->n_cu * 4;
-    if (g > n_ranges) g = n_ranges;
-    if (int rc = launch(materialize_kernel, dim3((uint32_t)g), dim3(BUILD_T), (size_t)RS * 12, ctx->stream, (Slot *)ctr->slots, RS,
-                        n_ranges, ctr->shift, ctr->m8, ctr->kbits, ctr->range_counts))
-        return rc;
-    ctr->dense = false;
-    return KT_OK;
-}
-
-// kt_ctr_export of a densely packed table: d_keys / d_counts are device arrays of max_out entries; *n = entries in the table
-int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint64_t *n) {
-    kt_ctx *ctx = ctr->ctx;
-    if (ctr->dense_ext) {
-        // the build wrote entries [0, *distinct) of the export target: nothing to do when that is where the caller
-        // wants them, a plain copy otherwise
-        KT_HIP(hipMemcpyAsync(n, ctr->distinct, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-        const uint64_t w = *n < max_out ? *n : max_out;
-        if (w && d_keys != ctr->xt_keys) KT_HIP(hipMemcpyAsync(d_keys, ctr->xt_keys, w * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        if (w && d_counts != ctr->xt_counts) KT_HIP(hipMemcpyAsync(d_counts, ctr->xt_counts, w * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-        return KT_OK;
-    }
-    const uint32_t RS = ctr->m8 << (LOG2_S - 3);
-    const uint64_t n_ranges = ctr->cap / RS, n_tiles = (n_ranges + XT - 1) / XT;
-    uint64_t *tiles = nullptr;
-    if (int rc = ctx->claim(kt::AUX0, (n_tiles + 1) * 8, "kt_table_dense_export", &tiles)) return rc;
-    if (int rc = launch(tile_sums_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, ctr->range_counts, n_ranges, tiles)) return rc;
-    if (int rc = launch(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles)) return rc;
-    if (max_out)
-        if (int rc = launch(dense_export_kernel<false>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
-                            n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, nullptr, 1u, 0xFFFFFFFFu))
-            return rc;
-    KT_HIP(hipMemcpyAsync(n, tiles + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
-}
-
-// the same restricted to the entries with lo <= occurrences <= hi of a dense table whose ranges are its own slots (not an
-// export target): a counting pass over the ranges' counts (kept per range + tile sums), the tile scan, the filtered copy.
-// *n = the entries kept.  Scratch: the tile offsets and one u32 per range, next to each other in the context's AUX0.
-int kt_table_dense_export_range(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint32_t lo, uint32_t hi,
-                                uint64_t *n) {
-    kt_ctx *ctx = ctr->ctx;
-    const uint32_t RS = ctr->m8 << (LOG2_S - 3);
-    const uint64_t n_ranges = ctr->cap / RS, n_tiles = (n_ranges + XT - 1) / XT;
-    uint64_t *tiles = nullptr;
-    if (int rc = ctx->claim(kt::AUX0, (n_tiles + 1) * 8 + n_ranges * 4, "kt_table_dense_export_range", &tiles)) return rc;
-    uint32_t *kept = (uint32_t *)(tiles + n_tiles + 1);
-    if (int rc = launch(dense_kept_kernel, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS, n_ranges,
-                        ctr->range_counts, lo, hi, kept, tiles))
-        return rc;
-    if (int rc = launch(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles)) return rc;
-    if (max_out)
-        if (int rc = launch(dense_export_kernel<true>, dim3((uint32_t)n_tiles), dim3(XT), 0, ctx->stream, (const Slot *)ctr->slots, RS,
-                            n_ranges, ctr->range_counts, tiles, d_keys, d_counts, max_out, kept, lo, hi))
-            return rc;
-    KT_HIP(hipMemcpyAsync(n, tiles + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
     return KT_OK;
 }
 

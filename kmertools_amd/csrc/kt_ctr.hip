@@ -29,6 +29,10 @@ constexpr int BLOCK = ktseg::BLOCK;
 using kttab::Slot;
 using kttab::TableRef;
 using kttab::table_add;
+using kttab::TileShared;  // (the tile reservation of erase_survivors_kernel, shared with kt_table.hip's export kernels)
+using kttab::XPT;
+using kttab::XTILE;
+static_assert(BLOCK == kttab::BLOCK, "the tile reservation's workgroup");
 
 // new keys claimed by the thread -> the table's distinct counter: one atomic per wave, at the end of the kernel
 __device__ __forceinline__ void publish_fresh(uint32_t fresh, uint64_t *distinct) {
@@ -66,155 +70,6 @@ __global__ __launch_bounds__(BLOCK) void add_pairs_kernel(const uint64_t *__rest
         fresh += st == 2u;
     }
     publish_fresh(fresh, distinct);
-}
-
-__global__ __launch_bounds__(BLOCK) void table_clear_kernel(Slot *__restrict__ slots, uint64_t cap) {
-    const uint4 empty = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * BLOCK)
-        reinterpret_cast<uint4 *>(slots)[i] = empty;
-}
-
-// stream the table, compact occupied slots.  A workgroup takes tiles of 4096 slots (16 coalesced 16-byte loads per
-// thread, all in flight at once), ballots every load, scans the 64 (wave, load) popcounts and reserves the tile's
-// output range with ONE cursor atomic; every store instruction then writes one contiguous run.  (The first version
-// took one atomic per wave and 64 slots: 100 M atomics on one address for a 6.4 G-slot table = 1.2 s.)
-#ifndef KT_EXPORT_NT
-#define KT_EXPORT_NT 0  // bit 0: non-temporal loads of the slots, bit 1: non-temporal stores of the pairs (measured, see DESIGN)
-#endif
-#ifndef KT_EXPORT_XPT
-#define KT_EXPORT_XPT 16
-#endif
-constexpr uint32_t XPT = KT_EXPORT_XPT, XTILE = BLOCK * XPT;
-
-// the tile reservation: bal[j] = the wave's ballot of the entries of load j that are kept
-struct TileShared {
-    uint32_t runs[BLOCK / 64 * XPT];  // kept entries per (wave, load), then their exclusive prefix
-    uint64_t tile_base;
-    static_assert(BLOCK / 64 * XPT == 64, "one wave scans the runs, one per lane");
-    // reserves the tile's output range at the cursor and returns its start.  Every thread of the workgroup must be here (two
-    // barriers; one more is due before the next tile's call rewrites runs[] / tile_base).
-    __device__ __forceinline__ uint64_t reserve(const uint64_t (&bal)[XPT], uint64_t *cursor) {
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++)
-            if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
-        ktd::lds_barrier();
-        if (wave == 0) {  // 64 runs: one wave scans them and reserves the tile's output range
-            const uint32_t c = runs[lane];
-            uint32_t inc = c;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t u = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += u;
-            }
-            runs[lane] = inc - c;
-            if (lane == 63)
-                tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;
-        }
-        ktd::lds_barrier();
-        return tile_base;
-    }
-    // where this lane's kept entry of load j goes (base = what reserve returned)
-    __device__ __forceinline__ uint64_t pos(uint64_t base, uint64_t bal_j, uint32_t j) const {
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        return base + runs[wave * XPT + j] + __popcll(bal_j & ((1ull << lane) - 1ull));
-    }
-};
-
-// FILTER (kt_ctr_export_stage_range): only the slots whose occurrences lie in [lo, hi] are in the ballot
-template <bool FILTER = false>
-__global__ __launch_bounds__(BLOCK) void table_export_kernel(const Slot *__restrict__ slots, uint64_t cap,
-                                                             uint64_t *__restrict__ out_keys,
-                                                             uint32_t *__restrict__ out_counts, uint64_t max_out,
-                                                             uint64_t *__restrict__ cursor, uint32_t lo,
-                                                             uint32_t hi) {
-    __shared__ TileShared sm;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint64_t n_tiles = (cap + XTILE - 1) / XTILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint4 v[XPT];
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++) {
-            const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
-#if KT_EXPORT_NT & 1
-            typedef uint32_t raw4 __attribute__((ext_vector_type(4)));
-            if (i < cap) {
-                const raw4 r = __builtin_nontemporal_load(reinterpret_cast<const raw4 *>(slots) + i);
-                v[j] = make_uint4(r.x, r.y, r.z, r.w);
-            } else {
-                v[j] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-            }
-#else
-            v[j] = i < cap ? reinterpret_cast<const uint4 *>(slots)[i] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-#endif
-        }
-        uint64_t bal[XPT];
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++) {
-            if constexpr (FILTER) {
-                const uint32_t occ = v[j].z + 1u;
-                bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu && occ >= lo && occ <= hi);
-            } else {
-                bal[j] = __ballot((v[j].x & v[j].y) != 0xFFFFFFFFu);  // key != KT_EMPTY_KEY
-            }
-        }
-        const uint64_t base = sm.reserve(bal, cursor);
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++) {
-            if ((bal[j] >> lane) & 1ull) {
-                const uint64_t pos = sm.pos(base, bal[j], j);
-                if (pos < max_out) {
-#if KT_EXPORT_NT & 2
-                    __builtin_nontemporal_store(((uint64_t)v[j].y << 32) | v[j].x, out_keys + pos);
-                    __builtin_nontemporal_store(v[j].z + 1u, out_counts + pos);
-#else
-                    out_keys[pos] = ((uint64_t)v[j].y << 32) | v[j].x;
-                    out_counts[pos] = v[j].z + 1u;  // stored value is occurrences - 1
-#endif
-                }
-            }
-        }
-        ktd::lds_barrier();  // the reservation's LDS is rewritten by the next tile
-    }
-}
-
-// (key, occurrences) pairs -> the entries with lo <= occurrences <= hi, compacted (kt_ctr_export_stage_range over a table
-// whose entries are an export target's arrays).  The tiles of table_export_kernel over 4-byte counts; a key is read only
-// for an entry that is kept and fits: with max_out = 0 the kernel only counts, and reads the counts alone.
-__global__ __launch_bounds__(BLOCK) void pairs_filter_kernel(const uint64_t *__restrict__ keys,
-                                                             const uint32_t *__restrict__ counts, uint64_t n,
-                                                             uint32_t lo, uint32_t hi, uint64_t *__restrict__ out_keys,
-                                                             uint32_t *__restrict__ out_counts, uint64_t max_out,
-                                                             uint64_t *__restrict__ cursor) {
-    __shared__ TileShared sm;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint64_t n_tiles = (n + XTILE - 1) / XTILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t c[XPT];
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++) {
-            const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
-            c[j] = i < n ? counts[i] : 0u;
-        }
-        uint64_t bal[XPT];
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++) {
-            const uint64_t i = tile * XTILE + (uint64_t)j * BLOCK + tid;
-            bal[j] = __ballot(i < n && c[j] >= lo && c[j] <= hi);
-        }
-        const uint64_t base = sm.reserve(bal, cursor);
-#pragma unroll
-        for (uint32_t j = 0; j < XPT; j++) {
-            if ((bal[j] >> lane) & 1ull) {
-                const uint64_t pos = sm.pos(base, bal[j], j);
-                if (pos < max_out) {
-                    out_keys[pos] = keys[tile * XTILE + (uint64_t)j * BLOCK + tid];
-                    out_counts[pos] = c[j];
-                }
-            }
-        }
-        ktd::lds_barrier();
-    }
 }
 
 // ---- kt_ctr_erase: flag the slots of the keys to remove, compact the others, build the image again from them -------------
@@ -1150,120 +1005,11 @@ __global__ __launch_bounds__(BLOCK) void kmers_kernel(SegArgs a, uint64_t *__res
     }
 }
 
-int check_overflow(kt_ctr *ctr) {
-    uint32_t flag = 0;
-    KT_HIP(hipMemcpyAsync(&flag, ctr->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctr->ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctr->ctx->stream));
-    if (flag & 2u)  // (set by the range build that writes straight into the export target, kt_bulk.hip)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_export_target: the arrays are smaller than the table (its contents are lost: "
-                                    "kt_ctr_clear, then count again with larger arrays or without a target)");
-    if (flag) return kt::fail(KT_ERR_FULL, "k-mer table is full: raise capacity_slots");
-    return KT_OK;
-}
-
 }  // namespace
 
 using namespace ktl;
 
 extern "C" {
-
-int kt_ctr_create(kt_ctx *ctx, int k, uint64_t capacity_slots, kt_ctr **out) {
-    if (!ctx || !out) return kt::fail(KT_ERR_ARG, "kt_ctr_create: null");
-    *out = nullptr;
-    if (k < 1 || k > 31) return kt::fail(KT_ERR_ARG, "kt_ctr_create: k must be in 1..31");
-    if (int rc = ctx->use()) return rc;
-    const kttab::Geom geom = kttab::make_geom(capacity_slots, k);
-    const uint64_t cap = geom.cap;
-    kt_ctr *c = new (std::nothrow) kt_ctr();
-    if (!c) return kt::fail(KT_ERR_NOMEM, "kt_ctr_create: host alloc");
-    c->ctx = ctx;
-    c->k = k;
-    c->cap = cap;
-    c->shift = geom.shift;
-    c->m8 = geom.m8;
-    c->kbits = geom.kbits;
-    hipError_t e = hipMalloc((void **)&c->slots, cap * sizeof(Slot));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->flags, 64);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->cursor, 64);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->distinct, 64);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->range_counts, (cap / geom.range_slots() + 1) * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        kt_ctr_destroy(c);
-        return kt::fail(KT_ERR_NOMEM, std::string("kt_ctr_create: hipMalloc: ") + hipGetErrorString(e));
-    }
-    *out = c;
-    return kt_ctr_clear(c);
-}
-
-int kt_ctr_destroy(kt_ctr *ctr) {
-    if (!ctr) return KT_OK;
-    if (ctr->ctx) {
-        (void)hipSetDevice(ctr->ctx->device);
-        (void)hipStreamSynchronize(ctr->ctx->stream);
-    }
-    if (ctr->slots) (void)hipFree(ctr->slots);
-    if (ctr->flags) (void)hipFree(ctr->flags);
-    if (ctr->cursor) (void)hipFree(ctr->cursor);
-    if (ctr->distinct) (void)hipFree(ctr->distinct);
-    if (ctr->range_counts) (void)hipFree(ctr->range_counts);
-    ctr->b_ext.release();
-    ctr->b_stage_k.release();
-    ctr->b_stage_c.release();
-    ctr->b_keys1.release();
-    ctr->b_keys2.release();
-    ctr->b_meta.release();
-    ctr->b_desc.release();
-    ctr->b_pack.release();
-    kt_bulk_job_free(ctr->job);
-    delete ctr;
-    return KT_OK;
-}
-
-// Clearing is deferred: the bulk build (kt_bulk.hip) overwrites every slot, so a clear that is
-// followed by a whole-batch kt_ctr_add_reads never has to touch the table.
-static int ensure_cleared(kt_ctr *ctr) {
-    if (ctr->dense) return kt_table_image(ctr);  // (a dense table is never pending a clear)
-    if (!ctr->needs_clear) return KT_OK;
-    hipLaunchKernelGGL(table_clear_kernel, dim3(grid_for(ctr->ctx, (ctr->cap + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0,
-                       ctr->ctx->stream, (Slot *)ctr->slots, ctr->cap);
-    KT_HIP(hipGetLastError());
-    ctr->needs_clear = false;
-    return KT_OK;
-}
-}  // extern "C"
-int ktl::table_ready(kt_ctr *ctr) {
-    if (int rc = ensure_cleared(ctr)) return rc;
-    return check_overflow(ctr);
-}
-extern "C" {
-
-int kt_ctr_clear(kt_ctr *ctr) {
-    if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_clear: null");
-    if (int rc = ctr->ctx->use()) return rc;
-    KT_HIP(hipMemsetAsync(ctr->flags, 0, 64, ctr->ctx->stream));
-    KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, ctr->ctx->stream));
-    ctr->needs_clear = true;
-    ctr->empty = true;
-    ctr->dense = false;
-    ctr->dense_ext = false;
-    ctr->stage_n = 0;  // (what kt_ctr_export_stage staged is gone with the table's contents)
-    return KT_OK;
-}
-
-int kt_ctr_export_target(kt_ctr *ctr, uint64_t *keys_dev, uint32_t *counts_dev, uint64_t max_out) {
-    if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_export_target: null ctr");
-    if ((keys_dev == nullptr) != (counts_dev == nullptr))
-        return kt::fail(KT_ERR_ARG, "kt_ctr_export_target: both arrays or neither");
-    if (int rc = ctr->ctx->use()) return rc;
-    // a table whose entries live in the current target gets its own copy (the probing image) before the target moves
-    if (ctr->dense_ext && (keys_dev != ctr->xt_keys || counts_dev != ctr->xt_counts))
-        if (int rc = kt_table_image(ctr)) return rc;
-    ctr->xt_keys = keys_dev;
-    ctr->xt_counts = counts_dev;
-    ctr->xt_max = keys_dev ? max_out : 0;
-    ctr->stage_n = 0;  // (what was staged may have been the old target's arrays)
-    return KT_OK;
-}
 
 int kt_ctr_add_reads(kt_ctr *ctr, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int mem) {
     return kt_ctr_add_reads_part(ctr, bases, offsets, n_reads, mem, 1, 0);
@@ -1277,7 +1023,9 @@ int kt_ctr_add_reads_part(kt_ctr *ctr, const uint8_t *bases, const uint64_t *off
     Call call(ctx, mem, "kt_ctr_add_reads");
     if (int rc = call.enter()) return rc;
     if (n_reads == 0) return KT_OK;
-    ctr->stage_n = 0;  // the table changes: what kt_ctr_export_stage staged is no longer the table (fetch says so)
+    // the table is about to change: what kt_ctr_export_stage staged is no longer the table (fetch says so).  Here, not only
+    // in the gates below: a batch of reads without a base has ended the stage since the stage exists
+    ctr->stage.drop();
     if (!offsets) return call.fail("null offsets");
     if (int rc = call.batch(bases, offsets, n_reads)) return rc;
     if (call.total == 0) return KT_OK;
@@ -1289,11 +1037,10 @@ int kt_ctr_add_reads_part(kt_ctr *ctr, const uint8_t *bases, const uint64_t *off
         if (int rc = kt_bulk_build(ctr, call.bases, call.offsets, n_reads, call.total, n_parts, part, &done)) return rc;
         if (done) return call.finish();
     }
-    ctr->empty = false;
-    if (int rc = ensure_cleared(ctr)) return rc;
+    TableRef t;
+    if (int rc = table_write(ctr, &t)) return rc;
     SegArgs a;
     if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, ctr->k, &a)) return rc;
-    TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
     hipLaunchKernelGGL(count_reads_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, t, n_parts,
                        part, ctr->distinct);
     KT_HIP(hipGetLastError());
@@ -1307,7 +1054,7 @@ int kt_ctr_add_pairs(kt_ctr *ctr, const uint64_t *keys, const uint32_t *counts, 
     if (int rc = call.enter()) return rc;
     if (n == 0) return KT_OK;
     if (!keys) return call.fail("null keys");
-    ctr->stage_n = 0;  // (see kt_ctr_add_reads_part)
+    ctr->stage.drop();  // (before anything below can fail, as in kt_ctr_add_reads_part)
     const uint64_t *d_keys = nullptr;
     const uint32_t *d_counts = nullptr;
     if (int rc = call.in(kt::AUX1, keys, n, &d_keys)) return rc;
@@ -1320,35 +1067,18 @@ int kt_ctr_add_pairs(kt_ctr *ctr, const uint64_t *keys, const uint32_t *counts, 
         if (int rc = kt_bulk_build_keys(ctr, d_keys, n, &done)) return rc;
         if (done) return call.finish();
     }
-    ctr->empty = false;
-    if (int rc = ensure_cleared(ctr)) return rc;
-    TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
-    hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0,
-                       ctx->stream, d_keys, d_counts, n, t, ctr->distinct);
-    KT_HIP(hipGetLastError());
+    TableRef t;
+    if (int rc = table_write(ctr, &t)) return rc;
+    if (int rc = add_pairs(ctr, t, d_keys, d_counts, n)) return rc;
     return call.finish();
 }
 
 }  // extern "C"
 
-// an empty table filled from the (key, occurrences) pairs the export target holds (probing path; the rare road: a
-// table that was counted into its export arrays and is then added to or probed after all)
-int kt_ctr_reload_pairs(kt_ctr *ctr, const uint64_t *d_keys, const uint32_t *d_counts) {
-    kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
-    uint64_t n = 0;
-    KT_HIP(hipMemcpyAsync(&n, ctr->distinct, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    if (int rc = check_overflow(ctr)) return rc;  // (arrays that were too small hold nothing usable)
-    ctr->needs_clear = true;
-    if (int rc = ensure_cleared(ctr)) return rc;
-    KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, ctx->stream));
-    if (n == 0) return KT_OK;
-    TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
-    hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctx->stream,
-                       d_keys, d_counts, n, t, ctr->distinct);
-    KT_HIP(hipGetLastError());
-    return KT_OK;
+// n > 0 device pairs through the probing path (kt_ctr_add_pairs, kt_ctr_erase's survivors, kt_table.hip's load of a target's pairs)
+int ktl::add_pairs(kt_ctr *ctr, const TableRef &t, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n) {
+    return launch(add_pairs_kernel, dim3(grid_for(ctr->ctx, (n + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, ctr->ctx->stream, d_keys,
+                  d_counts, n, t, ctr->distinct);
 }
 
 // Scratch: AUX1 = the surviving pairs (12 bytes an entry of the table), AUX2 = the bitmask (one bit a slot), host keys in
@@ -1395,17 +1125,13 @@ extern "C" int kt_ctr_erase(kt_ctr *ctr, const uint64_t *keys, uint64_t n, uint6
         hipLaunchKernelGGL(erase_survivors_kernel, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0, st,
                            (const Slot *)ctr->slots, ctr->cap, (const uint32_t *)dead, live_keys, live_counts, n_t - gone, cursor + 1);
         KT_HIP(hipGetLastError());
-        // from here on the table changes: what kt_ctr_export_stage staged is no longer the table
-        ctr->stage_n = 0;
-        hipLaunchKernelGGL(table_clear_kernel, dim3(grid_for(ctx, (ctr->cap + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, st,
-                           (Slot *)ctr->slots, ctr->cap);
+        // from here on the table changes (the gate finds the image table_ready left): the slots emptied, the survivors back in
+        TableRef t;
+        if (int rc = table_write(ctr, &t)) return rc;
+        if (int rc = table_wipe(ctr)) return rc;
         KT_HIP(hipMemsetAsync(ctr->distinct, 0, 8, st));
-        if (n_t - gone) {
-            TableRef t{(Slot *)ctr->slots, ktl::geom_of(ctr), ctr->flags};
-            hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(ctx, (n_t - gone + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, st,
-                               (const uint64_t *)live_keys, (const uint32_t *)live_counts, n_t - gone, t, ctr->distinct);
-        }
-        KT_HIP(hipGetLastError());
+        if (n_t - gone)
+            if (int rc = add_pairs(ctr, t, live_keys, live_counts, n_t - gone)) return rc;
     }
     if (int rc = call.finish()) return rc;
     if (n_erased) *n_erased = gone;
@@ -1415,161 +1141,6 @@ extern "C" int kt_ctr_erase(kt_ctr *ctr, const uint64_t *keys, uint64_t n, uint6
 static int launch_spectrum(kt_ctr *ctr, uint64_t n, uint64_t *d_hist, uint32_t n_bins, uint64_t *d_totals);
 
 extern "C" {
-
-int kt_ctr_capacity(kt_ctr *ctr, uint64_t *slots) {
-    if (!ctr || !slots) return kt::fail(KT_ERR_ARG, "kt_ctr_capacity: null");
-    *slots = ctr->cap;
-    return KT_OK;
-}
-
-int kt_ctr_size(kt_ctr *ctr, uint64_t *distinct) {
-    if (!ctr || !distinct) return kt::fail(KT_ERR_ARG, "kt_ctr_size: null");
-    kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
-    // every insert path keeps the count of occupied slots (claims in the probing kernels, placed keys in the range
-    // builds), so the size is one 8-byte read - not a scan of the table
-    KT_HIP(hipMemcpyAsync(distinct, ctr->distinct, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return check_overflow(ctr);
-}
-
-int kt_ctr_export(kt_ctr *ctr, uint64_t *keys, uint32_t *counts, uint64_t max_out, uint64_t *n_out, int mem) {
-    if (!ctr || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export: null");
-    kt_ctx *ctx = ctr->ctx;
-    Call call(ctx, mem, "kt_ctr_export");
-    if (int rc = call.enter()) return rc;
-    if (max_out && (!keys || !counts)) return call.fail("null output");
-    if (!ctr->dense)
-        if (int rc = ensure_cleared(ctr)) return rc;
-    if (int rc = check_overflow(ctr)) return rc;
-    uint64_t *d_keys = keys;
-    uint32_t *d_counts = counts;
-    if (call.host() && max_out) {  // (what comes back is the entries written, known only after the pass)
-        if (int rc = call.scratch(kt::AUX1, max_out * 8, &d_keys)) return rc;
-        if (int rc = call.scratch(kt::AUX2, max_out * 4, &d_counts)) return rc;
-    }
-    uint64_t n = 0;
-    if (ctr->dense) {  // packed ranges: a coalesced copy, no compaction
-        if (ctr->dense_ext && call.host()) {  // ... or no copy at all: the build wrote the entries to the export target
-            d_keys = ctr->xt_keys;
-            d_counts = ctr->xt_counts;
-        }
-        if (int rc = kt_table_dense_export(ctr, d_keys, d_counts, max_out, &n)) return rc;
-    } else {
-        KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(table_export_kernel<false>, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)), dim3(BLOCK), 0,
-                           ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, max_out, ctr->cursor, 1u, 0xFFFFFFFFu);
-        KT_HIP(hipGetLastError());
-        KT_HIP(hipMemcpyAsync(&n, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    const uint64_t written = n < max_out ? n : max_out;
-    call.back(keys, (const uint64_t *)d_keys, written);
-    call.back(counts, (const uint32_t *)d_counts, written);
-    if (int rc = call.finish()) return rc;
-    *n_out = written;
-    if (n > max_out) return call.fail("max_out smaller than the table's size");
-    return KT_OK;
-}
-
-// The table's entries in pieces (out-of-core callers: the host never holds more than one piece).  kt_ctr_export_stage
-// puts all of them into a device-side staging area of the library (for a table counted into an export target: they are
-// there already) and reports how many; kt_ctr_export_fetch copies entries [first, first + count) to host arrays.
-int kt_ctr_export_stage(kt_ctr *ctr, uint64_t *n_out) {
-    if (!ctr || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage: null");
-    kt_ctx *ctx = ctr->ctx;
-    kt::ClaimScope scope(ctx);
-    if (int rc = ctx->use()) return rc;
-    uint64_t n = 0;
-    if (int rc = kt_ctr_size(ctr, &n)) return rc;
-    ctr->stage_keys = nullptr;
-    ctr->stage_counts = nullptr;
-    ctr->stage_n = 0;
-    if (n) {
-        if (ctr->dense && ctr->dense_ext) {
-            ctr->stage_keys = ctr->xt_keys;
-            ctr->stage_counts = ctr->xt_counts;
-        } else {
-            // (the table's own staging buffers - the context's scratch is re-reserved by any other call on the context:
-            // host-memory adds and exports, routing, cov, minimisers - ADVICE r4)
-            if (int rc = ctr->b_stage_k.reserve(n * 8)) return rc;
-            if (int rc = ctr->b_stage_c.reserve(n * 4)) return rc;
-            uint64_t got = 0;
-            if (int rc = kt_ctr_export(ctr, (uint64_t *)ctr->b_stage_k.p, (uint32_t *)ctr->b_stage_c.p, n, &got, KT_MEM_DEVICE)) return rc;
-            n = got;
-            ctr->stage_keys = (const uint64_t *)ctr->b_stage_k.p;
-            ctr->stage_counts = (const uint32_t *)ctr->b_stage_c.p;
-        }
-    }
-    ctr->stage_n = n;
-    *n_out = n;
-    return KT_OK;
-}
-
-// kt_ctr_export_stage restricted to lo <= occurrences <= hi, in whatever form the table is in: the probing image through
-// the export ballot with the predicate in it, dense ranges through a counting pass + the tile scan + a filtered copy
-// (kt_table_dense_export_range), an export target's pairs compacted into the table's own stage buffers (counted first:
-// kept x 12 bytes).  The first two stage into buffers of the table's size, as the unfiltered stage does.
-int kt_ctr_export_stage_range(kt_ctr *ctr, uint32_t min_count, uint32_t max_count, uint64_t *n_out) {
-    if (!ctr || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: null");
-    if (min_count > max_count) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: min_count > max_count");
-    if (min_count <= 1u && max_count == 0xFFFFFFFFu) return kt_ctr_export_stage(ctr, n_out);
-    kt_ctx *ctx = ctr->ctx;
-    kt::ClaimScope scope(ctx);
-    if (int rc = ctx->use()) return rc;
-    uint64_t n = 0;
-    if (int rc = kt_ctr_size(ctr, &n)) return rc;
-    ctr->stage_keys = nullptr;
-    ctr->stage_counts = nullptr;
-    ctr->stage_n = 0;
-    uint64_t kept = 0;
-    if (n) {
-        if (ctr->dense && ctr->dense_ext) {
-            const uint32_t grid = grid_for(ctx, (n + XTILE - 1) / XTILE, 8);
-            KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-            hipLaunchKernelGGL(pairs_filter_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, ctr->xt_keys, ctr->xt_counts, n,
-                               min_count, max_count, nullptr, nullptr, 0ull, ctr->cursor);
-            KT_HIP(hipGetLastError());
-            KT_HIP(hipMemcpyAsync(&kept, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KT_HIP(hipStreamSynchronize(ctx->stream));
-            if (kept) {
-                if (int rc = ctr->b_stage_k.reserve(kept * 8)) return rc;
-                if (int rc = ctr->b_stage_c.reserve(kept * 4)) return rc;
-                KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-                hipLaunchKernelGGL(pairs_filter_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, ctr->xt_keys, ctr->xt_counts,
-                                   n, min_count, max_count, (uint64_t *)ctr->b_stage_k.p, (uint32_t *)ctr->b_stage_c.p, kept,
-                                   ctr->cursor);
-                KT_HIP(hipGetLastError());
-                KT_HIP(hipStreamSynchronize(ctx->stream));
-            }
-        } else {
-            if (int rc = ctr->b_stage_k.reserve(n * 8)) return rc;
-            if (int rc = ctr->b_stage_c.reserve(n * 4)) return rc;
-            uint64_t *d_keys = (uint64_t *)ctr->b_stage_k.p;
-            uint32_t *d_counts = (uint32_t *)ctr->b_stage_c.p;
-            if (ctr->dense) {
-                if (int rc = kt_table_dense_export_range(ctr, d_keys, d_counts, n, min_count, max_count, &kept)) return rc;
-            } else {
-                if (int rc = ensure_cleared(ctr)) return rc;
-                KT_HIP(hipMemsetAsync(ctr->cursor, 0, 8, ctx->stream));
-                hipLaunchKernelGGL(table_export_kernel<true>, dim3(grid_for(ctx, (ctr->cap + XTILE - 1) / XTILE, 8)),
-                                   dim3(BLOCK), 0, ctx->stream, (const Slot *)ctr->slots, ctr->cap, d_keys, d_counts, n,
-                                   ctr->cursor, min_count, max_count);
-                KT_HIP(hipGetLastError());
-                KT_HIP(hipMemcpyAsync(&kept, ctr->cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-                KT_HIP(hipStreamSynchronize(ctx->stream));
-            }
-            if (kept > n) return kt::fail(KT_ERR_ARG, "kt_ctr_export_stage_range: more entries than the table's size");
-        }
-        if (kept) {
-            ctr->stage_keys = (const uint64_t *)ctr->b_stage_k.p;
-            ctr->stage_counts = (const uint32_t *)ctr->b_stage_c.p;
-        }
-    }
-    ctr->stage_n = kept;
-    *n_out = kept;
-    return KT_OK;
-}
 
 int kt_ctr_spectrum(kt_ctr *ctr, uint64_t *hist, uint32_t n_bins, uint64_t *totals, int mem) {
     if (!ctr || !hist) return kt::fail(KT_ERR_ARG, "kt_ctr_spectrum: null");
@@ -1609,13 +1180,16 @@ struct TableWalk {
     uint64_t entries;
 };
 static TableWalk view_of(const kt_ctr *ctr, uint64_t n) {
-    if (ctr->dense && ctr->dense_ext)
+    switch (ctr->form()) {
+    case kt::TableForm::Target:
         return {FORM_PAIRS, {ctr->xt_keys, ctr->xt_counts, n, 0u, (uint32_t)(((uintptr_t)ctr->xt_counts & 15u) / 4u), nullptr}, n};
-    if (ctr->dense) {
-        const uint32_t RS = ctr->m8 << (kttab::LOG2_RANGE - 3);
+    case kt::TableForm::Dense: {
+        const uint32_t RS = geom_of(ctr).range_slots();
         return {FORM_DENSE, {ctr->slots, nullptr, ctr->cap / RS, RS, 0u, ctr->range_counts}, n};
     }
-    return {FORM_PROBE, {ctr->slots, nullptr, ctr->cap, 0u, 0u, nullptr}, ctr->cap};
+    default:  // (n > 0: not a Stale table)
+        return {FORM_PROBE, {ctr->slots, nullptr, ctr->cap, 0u, 0u, nullptr}, ctr->cap};
+    }
 }
 
 // One launch over a table: launch(the form as a compile-time constant, the grid).  A flat form is shared out in tiles of
@@ -1926,20 +1500,6 @@ extern "C" int kt_ctr_hetmers(kt_ctr *table, uint32_t min_count, uint32_t max_co
 }
 
 extern "C" {
-
-int kt_ctr_export_fetch(kt_ctr *ctr, uint64_t first, uint64_t count, uint64_t *keys_host, uint32_t *counts_host) {
-    if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_export_fetch: null");
-    if (first > ctr->stage_n || count > ctr->stage_n - first)
-        return kt::fail(KT_ERR_ARG, "kt_ctr_export_fetch: beyond the staged entries (call kt_ctr_export_stage first)");
-    if (!count) return KT_OK;
-    if (!keys_host || !counts_host) return kt::fail(KT_ERR_ARG, "kt_ctr_export_fetch: null output");
-    kt_ctx *ctx = ctr->ctx;
-    if (int rc = ctx->use()) return rc;
-    KT_HIP(hipMemcpyAsync(keys_host, ctr->stage_keys + first, count * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipMemcpyAsync(counts_host, ctr->stage_counts + first, count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    KT_HIP(hipStreamSynchronize(ctx->stream));
-    return KT_OK;
-}
 
 int kt_ctr_route(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k,
                  int n_owners, uint64_t *keys_out, uint64_t *owner_counts, int mem) {

@@ -110,6 +110,45 @@ struct kt_seg_src {
     uint64_t cap1;
 };
 
+namespace kt {
+// The form a table (kt_ctr) is in: where its entries are and what its buffers hold ("The table's forms").
+//   Stale   the slots hold old data, cleared before anything reads or probes them; *distinct = 0
+//   Image   the slots are the probing image; *distinct = occupied slots
+//   Dense   every range's entries packed at its front (keys, then counts), range_counts[r] of them; *distinct = entries
+//   Target  the entries are the export target's arrays [0, *distinct), as (key, occurrences); the slots: the build's scratch
+// In every other form the target's arrays are the caller's.  Transitions - the functions of kt_ctr in brackets, and no other
+// code assigns the form:
+//   any -> Stale             kt_ctr_clear [cleared]
+//   Stale -> Image           the deferred clear is carried out for the first reader or probing writer [imaged]
+//   Dense, Target -> Image   kt_table_image, for whatever has to probe: the ranges materialised in place / the target's
+//                            pairs loaded into the wiped slots, the arrays the caller's again [imaged]
+//   Stale, Image -> Image, Dense, Target   a bulk job wrote every slot [built]: a fresh() table is left Dense - Target when
+//                            a target is set and took the entries - or, KT_BULK_DENSE=0, as its Image; a table with data
+//                            is imaged first and merged range by range into its Image
+// fresh(): nothing was inserted since the last clear - a Stale table, or an Image only readers have touched.  Every writer
+// ends it [written, built]; an erase that removes every entry does not bring it back.  A Dense or Target table is never fresh.
+enum class TableForm : uint8_t { Stale, Image, Dense, Target };
+
+// What kt_ctr_export_stage[_range] staged for kt_ctr_export_fetch: n entries in device memory - in the table's own stage
+// buffers or, all the entries of a Target-form table, in the target's arrays themselves.  Dropped by every call that changes
+// the table's content (ktl::table_write, the bulk job's plan, kt_ctr_clear) and by whatever hands the arrays it points at
+// back to the caller (kt_table_image of a Target-form table, kt_ctr_export_target).
+class Stage {
+public:
+    void set(const uint64_t *keys, const uint32_t *counts, uint64_t n) { keys_ = keys, counts_ = counts, n_ = n; }
+    void drop() { set(nullptr, nullptr, 0); }
+    bool aliases(const void *p) const { return n_ && keys_ == p; }  // the staged entries are the array at p
+    const uint64_t *keys() const { return keys_; }
+    const uint32_t *counts() const { return counts_; }
+    uint64_t n() const { return n_; }
+
+private:
+    const uint64_t *keys_ = nullptr;
+    const uint32_t *counts_ = nullptr;
+    uint64_t n_ = 0;
+};
+}  // namespace kt
+
 struct kt_bulk_job;  // kt_bulk.hip: the plan and buffers of a partition + range build in progress
 void kt_bulk_job_free(kt_bulk_job *job);
 
@@ -130,20 +169,13 @@ struct kt_ctr {
     // through the exact pass (of l2_buckets) - a caller that plans its jobs itself (kt_shard.hip) gives the next one more room
     uint32_t l2_redone = 0, l2_buckets = 0;
     bool paged_failed = false; // a bulk build overflowed a paged level-1 bucket: exact offsets from now on
-    bool empty = true;         // nothing inserted since the last clear (bulk build allowed)
-    bool needs_clear = true;   // slots hold stale data: clear before the incremental path / export
-    bool dense = false;        // the last (bulk) build left every range packed, not as a probing image (kt_table.hpp)
-    uint32_t *range_counts = nullptr;  // device, one per range: entries of the range while the table is dense
+    uint32_t *range_counts = nullptr;  // device, one per range: entries of the range while the table is Dense
     // export target (kt_ctr_export_target): device arrays of the caller that a fresh bulk build writes its packed
     // entries to instead of the ranges' own slots - the build's output IS the export (no copy pass afterwards)
     uint64_t *xt_keys = nullptr;
     uint32_t *xt_counts = nullptr;
     uint64_t xt_max = 0;
-    bool dense_ext = false;            // the table's entries ARE xt_keys / xt_counts [0, *distinct): (key, occurrences)
-    const uint64_t *stage_keys = nullptr;  // kt_ctr_export_stage: where the staged entries are (device), how many
-    const uint32_t *stage_counts = nullptr;
-    uint64_t stage_n = 0;
-    bool xt_too_small = false;         // the last build found the export target smaller than the table (reported by kt_bulk_finish)
+    kt::Stage stage;                   // what kt_ctr_export_stage[_range] staged
     kt::Scratch b_ext;                 // the export-target build's holes and the scratch behind the caller's arrays
     kt::Scratch b_stage_k, b_stage_c;  // kt_ctr_export_stage's copy of the entries (when they are not the export target's arrays)
     kt::Scratch b_keys1, b_keys2, b_meta;  // bulk-build buffers (kt_bulk.hip), kept across calls
@@ -154,6 +186,27 @@ struct kt_ctr {
     uint32_t *flags = nullptr; // [0] = overflow flag, device
     uint64_t *cursor = nullptr; // device scalar for export
     uint64_t *distinct = nullptr; // device scalar: occupied slots (kept by every insert path, so kt_ctr_size is one 8-byte read)
+
+    // ---- the form (kt::TableForm): read by form() / fresh(), assigned by the transitions below and by nothing else
+    kt::TableForm form() const { return form_; }
+    // nothing was inserted since the last clear: the next bulk job builds the ranges instead of merging into them
+    bool fresh() const { return fresh_; }
+    void cleared() { form_ = kt::TableForm::Stale, fresh_ = true; }  // kt_ctr_clear
+    void imaged() { form_ = kt::TableForm::Image; }                  // the slots hold the probing image now
+    void written() { fresh_ = false; }                               // a probing writer is about to insert (ktl::table_write)
+    // a bulk job has written every slot: packed ranges (`ext`: into the export target instead) or the probing image
+    void built(bool dense, bool ext) {
+        form_ = !dense ? kt::TableForm::Image : ext ? kt::TableForm::Target : kt::TableForm::Dense;
+        fresh_ = false;
+    }
+    // a deferred error: the build found the target smaller than the table and went into the slots; kt_bulk_finish reports it
+    void target_too_small() { xt_too_small_ = true; }
+    bool take_target_too_small() { const bool was = xt_too_small_; xt_too_small_ = false; return was; }
+
+private:
+    kt::TableForm form_ = kt::TableForm::Stale;
+    bool fresh_ = true;
+    bool xt_too_small_ = false;
 };
 
 // kt_oligo_generic.hip: histograms for k outside 3..7, counted in global memory (device pointers, enqueued)

@@ -23,8 +23,19 @@ inline kttab::Geom geom_of(const kt_ctr *ctr) { return kttab::Geom{ctr->cap, ctr
 inline kttab::Probed probed_of(const kt_ctr *ctr, uint32_t n_parts = 1, uint32_t part = 0) {
     return kttab::Probed{(const kttab::Slot *)ctr->slots, geom_of(ctr), n_parts, part};
 }
-// makes the table readable: performs a deferred clear, reports KT_ERR_FULL if it overflowed
+// ... and as the kernels that insert into it take it (after table_write)
+inline kttab::TableRef writable_of(const kt_ctr *ctr) { return kttab::TableRef{(kttab::Slot *)ctr->slots, geom_of(ctr), ctr->flags}; }
+// The readers' gate (kt_table.hip): brings the table to its probing image - a deferred clear is carried out, a Dense or
+// Target-form table imaged - and reports KT_ERR_FULL if it overflowed
 int table_ready(kt_ctr *ctr);
+// The probing writers' gate: drops the staged export (the table's content is about to change), brings the table to its
+// probing image as table_ready does - without the wait for the overflow flag - marks it no longer fresh and hands back
+// the reference the inserting kernels take.  The bulk job is the other writer (kt_bulk_job::plan, kt_ctr::built).
+int table_write(kt_ctr *ctr, kttab::TableRef *t);
+// every slot of the table freed (kt_table.hip's table_clear_kernel, on the context's stream); the form is the caller's business
+int table_wipe(kt_ctr *ctr);
+// table[d_keys[i]] += d_counts[i] (null: 1) for n > 0 device pairs through the probing path (kt_ctr.hip's add_pairs_kernel)
+int add_pairs(kt_ctr *ctr, const kttab::TableRef &t, const uint64_t *d_keys, const uint32_t *d_counts, uint64_t n);
 // d_counts[i] = occurrences of d_keys[i] in the table (0: absent), n > 0 device keys, on the context's stream; the table
 // holds its probing image (table_ready).  kt_cov.hip's lookup_kernel.
 int lookup_counts(kt_ctr *table, const uint64_t *d_keys, uint64_t n, uint32_t *d_counts);

@@ -747,9 +747,10 @@ struct Batch {
         s->last_kmers = kmers;
     }
     int route_pass(unsigned long long *h_cur) {
-        s->pend->empty = false;
+        TableRef t;  // (check() has made the pending table ready: the gate finds its probing image)
+        if (int rc = ktl::table_write(s->pend, &t)) return rc;
         s->pend_touched = true;
-        const PendRef pend{(Slot *)s->pend->slots, ktl::geom_of(s->pend), s->pend->flags, s->pend->distinct};
+        const PendRef pend{t.slots, t.g, t.flags, s->pend->distinct};
         const RouteArgs ra{a, 0, a.n_seg, s->m, s->w, (uint32_t)V, s->send, s->region_words, s->room, s->cursors, s->cursors + ktsk::MAX_OWNERS, pend};
         auto checked = [](hipError_t e) {
             return e == hipSuccess ? (int)KT_OK : kt::fail(KT_ERR_HIP, std::string("kt_sharded_add_reads: the route pass: ") + hipGetErrorString(e));

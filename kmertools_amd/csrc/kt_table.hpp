@@ -32,6 +32,11 @@ static_assert(sizeof(Slot) == 16, "slot layout");
 #define KT_LOG2_RANGE 13
 #endif
 constexpr uint32_t LOG2_RANGE = KT_LOG2_RANGE, RANGE_FULL = 1u << LOG2_RANGE;
+// threads of a workgroup that builds, or materialises, one range (kt_bulk.hip's build_kernel, kt_table.hip's materialize_kernel)
+#ifndef KT_BUILD_T
+#define KT_BUILD_T 1024
+#endif
+constexpr int BUILD_T = KT_BUILD_T;
 
 struct Geom {
     uint64_t cap;    // slots
@@ -150,6 +155,49 @@ struct Probed {
             if ((want >> u) & 1u) sink(u, count(h[u], key[u]));
     }
 };
+
+// ---- compaction by tiles: what the kernels that stream slots or pairs and keep some of them share (kt_table.hip's
+// table_export_kernel and pairs_filter_kernel, kt_ctr.hip's erase_survivors_kernel) ----
+constexpr int BLOCK = 256;  // their workgroup (ktseg::BLOCK: the users assert it)
+#ifndef KT_EXPORT_XPT
+#define KT_EXPORT_XPT 16
+#endif
+constexpr uint32_t XPT = KT_EXPORT_XPT, XTILE = BLOCK * XPT;
+
+// the tile reservation: bal[j] = the wave's ballot of the entries of load j that are kept
+struct TileShared {
+    uint32_t runs[BLOCK / 64 * XPT];  // kept entries per (wave, load), then their exclusive prefix
+    uint64_t tile_base;
+    static_assert(BLOCK / 64 * XPT == 64, "one wave scans the runs, one per lane");
+    // reserves the tile's output range at the cursor and returns its start.  Every thread of the workgroup must be here (two
+    // barriers; one more is due before the next tile's call rewrites runs[] / tile_base).
+    __device__ __forceinline__ uint64_t reserve(const uint64_t (&bal)[XPT], uint64_t *cursor) {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (uint32_t j = 0; j < XPT; j++)
+            if (lane == 0) runs[wave * XPT + j] = (uint32_t)__popcll(bal[j]);
+        ktd::lds_barrier();
+        if (wave == 0) {  // 64 runs: one wave scans them and reserves the tile's output range
+            const uint32_t c = runs[lane];
+            uint32_t inc = c;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t u = __shfl_up(inc, off, 64);
+                if (lane >= (uint32_t)off) inc += u;
+            }
+            runs[lane] = inc - c;
+            if (lane == 63)
+                tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;
+        }
+        ktd::lds_barrier();
+        return tile_base;
+    }
+    // where this lane's kept entry of load j goes (base = what reserve returned)
+    __device__ __forceinline__ uint64_t pos(uint64_t base, uint64_t bal_j, uint32_t j) const {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        return base + runs[wave * XPT + j] + __popcll(bal_j & ((1ull << lane) - 1ull));
+    }
+};
 #endif
 
 }  // namespace kttab
@@ -179,15 +227,8 @@ int kt_bulk_add_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs, 
 // ... and the same records through the probing path (one table_add per k-mer), outside any job
 int kt_ctr_count_records(kt_ctr *ctr, const ktsk::RecRun *runs, uint32_t n_runs);
 int kt_bulk_finish(kt_ctr *ctr);
-// A fresh bulk build leaves the table DENSE: every range holds its entries packed at the front of its slots
-// (kt_ctr.range_counts says how many) instead of a probing image - all that size / export need.  kt_table_image turns
-// it into the probing layout in place (called by whatever has to probe: incremental adds, merges, cov);
-// kt_table_dense_export writes the (key, count) pairs of a dense table to device arrays.
+// A fresh bulk build leaves the table Dense or, with an export target set, Target (kt::TableForm, kt_internal.hpp) - all
+// that size, the exports and the walkers need.  kt_table_image (kt_table.hip) turns either into the probing image, in place
+// or from the target's pairs; no-op for a table in another form.  Whatever has to probe gets there through ktl::table_ready
+// or ktl::table_write (kt_launch.hpp); the bulk job's plan calls it before a merge, kt_ctr_export_target before the target moves.
 int kt_table_image(kt_ctr *ctr);
-// kt_ctr.hip: an empty table filled from (key, occurrences) pairs on the device, *ctr->distinct of them (what
-// kt_table_image does for a table whose entries live in the export target)
-int kt_ctr_reload_pairs(kt_ctr *ctr, const uint64_t *d_keys, const uint32_t *d_counts);
-int kt_table_dense_export(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint64_t *n);
-// ... only the entries with lo <= occurrences <= hi (kt_ctr_export_stage_range); not for a table in an export target
-int kt_table_dense_export_range(kt_ctr *ctr, uint64_t *d_keys, uint32_t *d_counts, uint64_t max_out, uint32_t lo, uint32_t hi,
-                                uint64_t *n);

@@ -403,8 +403,8 @@ int write_section(kt_ctr *ctr, FILE *f, const std::string &path, uint64_t n) {
     uint32_t *counts = nullptr, *suffix = nullptr, *cbytes = nullptr, *overflow = nullptr;
     if (int rc = ctx->claim(kt::BASES, ktl::carve_parts<16>(nullptr, &keys, n, &counts, n), "kt_ctr_save", &pairs)) return rc;
     ktl::carve_parts<16>(pairs, &keys, n, &counts, n);
-    KT_HIP(hipMemcpyAsync(keys, ctr->stage_keys, n * 8, hipMemcpyDeviceToDevice, st));
-    KT_HIP(hipMemcpyAsync(counts, ctr->stage_counts, n * 4, hipMemcpyDeviceToDevice, st));
+    KT_HIP(hipMemcpyAsync(keys, ctr->stage.keys(), n * 8, hipMemcpyDeviceToDevice, st));
+    KT_HIP(hipMemcpyAsync(counts, ctr->stage.counts(), n * 4, hipMemcpyDeviceToDevice, st));
     if (int rc = kt_sort_pairs(ctx, keys, counts, n, B)) return rc;
     ctx->unclaim(kt::OUT), ctx->unclaim(kt::AUX0);  // (the sort's; what follows is queued behind it)
     const uint64_t sfx_dw = (n * S + 3) / 4, cb_dw = (n + 3) / 4;
