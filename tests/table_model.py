@@ -161,6 +161,53 @@ def home_of(keys, k, geom):
     return x >> 13, ((x & 8191) * geom.m8) >> 3
 
 
+def hash_inverse(x, k):
+    """the k-mer word whose hash is x (khash_inv / nhash_inv): for k > 16 x is the whole 64-bit khash; for k <= 16 the
+    2k-bit nhash.  Not every word that comes back is a k-mer (k > 16: below 4^k) or canonical: the caller keeps those."""
+    x = np.asarray(x, np.uint64)
+    if k <= 16:
+        kb = 2 * k
+        t = (x << np.uint64(32 - kb)) & np.uint64(0xFFFFFFFF)
+        t ^= t >> np.uint64(kb >> 1)  # (the fold is its own inverse)
+        return ((t >> np.uint64(32 - kb)) * np.uint64(0x0E8B2F51)) & np.uint64((1 << kb) - 1)
+    h = x ^ (x >> np.uint64(32))
+    return h * np.uint64(0xF1DE83E19937733D)  # (wraps modulo 2^64: the inverse of 0x9E3779B97F4A7C15)
+
+
+def keys_built_at(k, geom, rng_range, position, n, rng):
+    """n distinct canonical k-mers (ascending) whose home slot lies in range `rng_range` at `position` - one position, a
+    window (first, last) or None for anywhere in the range - BUILT from the hash's inverse, not searched for: the top
+    geom.n bits of the hash are chosen (the range, and 13 bits below it that scale to a wanted position), the bits below
+    are drawn from `rng` until enough of the words that come back are canonical k-mers - k = 31: one in eight; a khash word
+    is a k-mer once in 4^(32 - k), so for 16 < k < 28 or so this is no way to get keys.  What keys_homed_at cannot do on a
+    table of 2^20 ranges."""
+    g = geom
+    assert g.n >= 13 and 0 <= rng_range < g.n_ranges
+    lo, hi = (0, g.range_slots - 1) if position is None else position if isinstance(position, tuple) else (position, position)
+    low13 = np.arange(8192, dtype=np.int64)
+    low13 = low13[((low13 * g.m8) >> 3 >= lo) & ((low13 * g.m8) >> 3 <= hi)]
+    assert len(low13), "no hash bits give a position in %d..%d of a range of %d slots" % (lo, hi, g.range_slots)
+    width = 2 * k if k <= 16 else 64  # bits of the hash word
+    assert width >= g.n
+    free = width - g.n
+    found = np.zeros(0, np.uint64)
+    for _ in range(200):
+        m = 16 * n + 64
+        top = (np.uint64(rng_range) << np.uint64(13)) | rng.choice(low13, m).astype(np.uint64)
+        x = top << np.uint64(free)
+        if free:
+            x |= rng.integers(0, 1 << free, size=m, dtype=np.uint64)
+        key = hash_inverse(x, k)
+        if k > 16:
+            key = key[key < np.uint64(1 << (2 * k))]
+        key = key[key <= gr.rc_np(key, k)]
+        found = np.unique(np.concatenate([found, key]))
+        if len(found) >= n:
+            break
+    assert len(found) >= n, "only %d of %d keys built at (%d, %s)" % (len(found), n, rng_range, position)
+    return np.sort(rng.choice(found, n, replace=False))
+
+
 class Layout:
     """where linear probing puts keys: per key its range, home position, slot and displacement and whether its probe
     sequence passed the range's end; per range how many keys it holds"""
@@ -179,9 +226,14 @@ def layout(keys, k, geom):
     L.fill = np.bincount(L.range, minlength=geom.n_ranges)
     assert len(L.fill) == geom.n_ranges and (L.fill <= rs).all(), "a range holds more keys than slots"
     L.slot = np.zeros(len(keys), np.int64)
+    by_range = np.argsort(L.range, kind="stable")  # (the keys of a range in the order given; a table may have 2^20 ranges)
+    starts = np.concatenate([[0], np.cumsum(L.fill)])
     for r in np.flatnonzero(L.fill):
+        members = by_range[starts[r]:starts[r + 1]]
+        if len(members) == 1:  # (alone in its range: at home)
+            L.slot[members[0]] = L.home[members[0]]
+            continue
         nxt = list(range(rs + 1))  # nxt[s]: a slot >= s that may be free (followed to a fixed point); rs: past the end
-        members = np.flatnonzero(L.range == r)
         for i, h in zip(members.tolist(), L.home[members].tolist()):
             s = h
             while True:

@@ -1187,6 +1187,55 @@ def test_ctr_level2_write_combining_small(hctx, oracle, monkeypatch, capfd, k, m
 
 
 @pytest.mark.parametrize("k", [31, 15])
+@pytest.mark.parametrize("mix", ["uniform", "heavy"])
+@pytest.mark.parametrize("log2_slots,B2", [(24, 1024), (25, 2048)])
+def test_ctr_level2_fan_outs_of_huge_tables_small(hctx, oracle, monkeypatch, capfd, k, mix, log2_slots, B2):
+    """the level-2 fan-outs that only tables of 2^33 and 2^34 slots select by default, 1024 and 2048, at the smallest shapes
+    that give them: KT_BULK_B1=1 on 2^24 slots (256 MB) leaves level 2 ten hash bits, on 2^25 slots (512 MB) eleven.  The
+    line's l2= is what tests/big_tables.py restates of kt_bulk_job (level2_of): one line per fine bucket in LDS where
+    SwwcShared<K>::bytes(B2) fits 160 KB - 1024 buckets do, 2048 do not: the sort-buffer kernel -, behind a paged level 1
+    that left every fine bucket a cache line of fixed room or more.  600 random reads of 1000 bases: 290 (145) keys per
+    fine bucket for 320 (160) keys of room, so some buckets outgrow it and are redone with exact boundaries; heavy: four
+    reads of one 40-mer 600 times on top.  Then the same batch merged on top."""
+    import big_tables as bt
+    from kmertools_amd import device
+    monkeypatch.setenv("KT_BULK_MIN_BASES", "0")
+    monkeypatch.setenv("KT_BULK_VERBOSE", "1")
+    monkeypatch.setenv("KT_BULK_B1", "1")
+    monkeypatch.setenv("KT_BULK_MERGE_DIV", "1000000000")
+    rng = np.random.default_rng(700 + k + log2_slots)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    seqs = [bytes(rng.choice(acgt, size=1000)) for _ in range(600)]
+    if mix == "heavy":
+        seqs += [bytes(rng.choice(acgt, size=40)) * 600 for _ in range(4)]
+    bases, offsets = device.to_csr(seqs)
+    wk, wc = oracle.count_reads(bases, offsets, k)
+    assert (wc.max() > 500) == (mix == "heavy")
+    assert bt.split_bits(log2_slots, 1) == (1, B2.bit_length() - 1)
+    want_l2 = "swwc" if bt.swwc_lds(B2) <= 160 * 1024 else "fast"
+    assert want_l2 == {1024: "swwc", 2048: "fast"}[B2]
+    ctr = device.Counter(hctx, k, 1 << log2_slots)
+    assert ctr.capacity() == 1 << log2_slots
+    capfd.readouterr()
+    ctr.add_reads_host(bases, offsets)
+    lines = _bulk_lines(capfd)
+    assert len(lines) == 1, lines
+    assert _field(lines[0], "l2") == want_l2 == bt.level2_of_line(lines[0], log2_slots, 8 if k > 16 else 4, 1), lines
+    assert _field(lines[0], "build") == "dense"
+    assert ctr.size() == len(wk)
+    gk, gc = ctr.export_host()
+    assert np.array_equal(gk, wk) and np.array_equal(gc, wc)
+    ctr.add_reads_host(bases, offsets)
+    lines = _bulk_lines(capfd)
+    assert len(lines) == 1, lines
+    assert _field(lines[0], "l2") == want_l2 == bt.level2_of_line(lines[0], log2_slots, 8 if k > 16 else 4, 1), lines
+    assert _field(lines[0], "build") == "merge"
+    gk, gc = ctr.export_host()
+    assert np.array_equal(gk, wk) and np.array_equal(gc, 2 * wc)
+    ctr.close()
+
+
+@pytest.mark.parametrize("k", [31, 15])
 def test_ctr_bulk_build_deep_coverage(hctx, oracle, monkeypatch, capfd, k):
     """few distinct k-mers, each seen hundreds of times (deep coverage of a small genome): fine buckets are far from
     evenly filled, so the fixed-room attempt of level 2 gives way to exact boundaries bucket by bucket"""
