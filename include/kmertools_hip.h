@@ -815,6 +815,61 @@ int kt_thread_runs(kt_ctx *ctx, const uint32_t *hits, const uint64_t *read_offse
                    uint32_t *run_unitig, uint32_t *run_upos, uint64_t *run_offsets, uint64_t max_runs, uint64_t *n_runs,
                    uint64_t *unitig_hits, uint64_t *unitig_runs, uint64_t *tally, int mem);
 
+/* Which unitigs hang together: the weakly CONNECTED COMPONENTS of the unitig graph (`kmertools unitigs --components`; what
+ * khmer's partitioning, Bandage's component view and every binning front end start from).  replaces: nothing - the reference
+ * has no such operation.  No table: a function of the arrays kt_ctr_unitigs_linked leaves, in its vocabulary - end
+ * e = 2 * u + sign owns link_to[link_offsets[e] .. link_offsets[e + 1]), and a value f joins unitig e >> 1 to unitig f >> 1.
+ *   - a link joins its two unitigs whatever its direction; its mirror need not be present;
+ *   - a link to oneself (a circular unitig, a hairpin) joins nothing;
+ *   - a value f >= 2 * n_unitigs is a BAD link: counted, otherwise ignored (an end may own any number of links).
+ * component (n_unitigs u32): components are numbered by their smallest unitig, ascending - component[0] == 0,
+ * component[u] <= u, and a new number appears exactly at a component's smallest member.  The result is a function of the
+ * arrays alone: two calls give the same bytes.
+ * stats (may be NULL with max_components == 0): KT_COMPONENT_FIELDS u64 per component, *n_components rows overwritten:
+ * [0] unitigs, [1] nodes = the sum of len - (k - 1) over its unitigs (0 when unitig_offsets is NULL; unitig_offsets:
+ * n_unitigs + 1 entries as kt_ctr_unitigs gives them), [2] the sum of count_sums (0 when it is NULL), [3] the directed links its
+ * ends own, bad ones not counted, [4] its smallest unitig.
+ * tally (may be NULL; KT_COMPONENT_TALLY u64, overwritten): [0] components, [1] components of one unitig, [2] the most unitigs
+ * in one component, [3] the most nodes in one, [4] bad links, [5] the rounds the labelling took - informational, the only
+ * value that may differ between two calls.
+ * *n_components is always exact and component is written whenever the call succeeds.  max_components == 0 writes no stats;
+ * 0 < max_components < *n_components writes nothing and returns KT_ERR_ARG with the number set (n_unitigs rows always
+ * suffice).  n_unitigs == 0: *n_components = 0, a zeroed tally, nothing is launched.  KT_MEM_HOST synchronises; KT_MEM_DEVICE
+ * writes on the context's stream and synchronises to learn the sizes and, once per round, whether the labelling has settled.
+ * KT_ERR_ARG, each decided before anything is read, the outputs untouched: a null ctx or n_components, a bad mem, null
+ * link_offsets, link_to or component with n_unitigs > 0, null stats with max_components > 0, n_unitigs > 2^31 - 1, k outside
+ * 1..32 when unitig_offsets is given; and link_offsets[0] > link_offsets[2 * n_unitigs].  KT_ERR_HIP with an internal-error
+ * text if the labelling has not settled after n_unitigs + 1 rounds (it takes O(log n_unitigs)).
+ * Device scratch: 4 bytes per unitig and 4 per link, 16 per 1024 unitigs, 40 per component when stats is not the caller's
+ * device array; a host call's copies of its arrays besides. */
+#define KT_NO_COMPONENT 0xFFFFFFFFu
+#define KT_COMPONENT_FIELDS 5
+#define KT_COMPONENT_TALLY 6
+int kt_unitig_components(kt_ctx *ctx, const uint64_t *link_offsets, const uint32_t *link_to, uint64_t n_unitigs,
+                         const uint64_t *unitig_offsets, const uint64_t *count_sums, int k, uint32_t *component,
+                         uint64_t *stats, uint64_t max_components, uint64_t *n_components, uint64_t *tally, int mem);
+
+/* The reads of a batch split by component (`kmertools thread --components`): a fold of kt_thread_runs' run arrays
+ * (run_unitig, run_len: run_offsets[n_reads] entries; run_offsets: n_reads + 1) over kt_unitig_components' component array
+ * (n_unitigs entries, numbers below n_components).  A run is BAD when its unitig run_unitig >> 1 is >= n_unitigs or that
+ * unitig's component is >= n_components; bad runs are counted and otherwise ignored.
+ * read_component[i] (u32) = the component of read i's first run that is not bad, KT_NO_COMPONENT when it has none;
+ * read_mixed[i] (u8, may be NULL) = 1 when a later run of the read lies in another component, else 0.
+ * comp_reads[c] / comp_hits[c] (n_components u64 each, may be NULL) are ADDED to - one per read at its component; every
+ * run's run_len at that run's own component -, so the caller zeroes them once and accumulates over batches.
+ * tally (may be NULL; KT_READ_COMPONENT_TALLY u64, overwritten): [0] reads with a component, [1] reads without, [2] mixed
+ * reads, [3] bad runs.
+ * The work is linear in the runs: a read of up to 8 runs is one lane's, a longer one is walked by its whole wave.
+ * KT_MEM_HOST synchronises; KT_MEM_DEVICE writes on the context's stream and synchronises to learn the number of runs.
+ * KT_ERR_ARG: a null ctx, a bad mem, null run_offsets or read_component with n_reads > 0, null component with
+ * n_unitigs > 0, a null run array when there are runs, n_unitigs > 2^31 - 1, n_components > n_unitigs.  On every one of
+ * these errors the outputs are untouched.  Device scratch: 64 bytes; a host call's copies of its arrays besides. */
+#define KT_READ_COMPONENT_TALLY 4
+int kt_thread_read_components(kt_ctx *ctx, const uint32_t *run_unitig, const uint32_t *run_len, const uint64_t *run_offsets,
+                              uint64_t n_reads, const uint32_t *component, uint64_t n_unitigs, uint64_t n_components,
+                              uint32_t *read_component, uint8_t *read_mixed, uint64_t *comp_reads, uint64_t *comp_hits,
+                              uint64_t *tally, int mem);
+
 /* Bottom-s MinHash sketches of the reads of a batch (`kmertools sketch`; what Mash does, and sourmash with `num`).
  * replaces: nothing - the reference has no such operation.  No table is involved.
  * A read's k-mers are its valid windows, canonical, as for every other k-mer walk here (1 <= k <= 31); a k-mer's hash is

@@ -26,6 +26,7 @@ KT_TIP_KEEP, KT_TIP_TIP, KT_TIP_ISOLATED, KT_TIP_TALLY = 0, 1, 2, 4
 KT_CLIP_ISOLATED, KT_CLIP_STATS = 1, 8
 KT_BUBBLE_POP, KT_BUBBLE_TALLY, KT_SIMPLIFY_STATS = 4, 4, 12
 KT_THREAD_TALLY = 6
+KT_NO_COMPONENT, KT_COMPONENT_FIELDS, KT_COMPONENT_TALLY, KT_READ_COMPONENT_TALLY = 0xFFFFFFFF, 5, 6, 4
 
 # every symbol include/kmertools_hip.h declares: name -> (restype, argtypes)
 _vp, _u64, _u32, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -94,6 +95,8 @@ SYMBOLS = {
     "kt_ctr_index_sequences": (_i, [_vp, _vp, _vp, _u64, C.POINTER(_u64), _i]),
     "kt_ctr_thread_hits": (_i, [_vp, _vp, _vp, _u64, _vp, _i]),
     "kt_thread_runs": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _i, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _vp, _vp, _i]),
+    "kt_unitig_components": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _u64, C.POINTER(_u64), _vp, _i]),
+    "kt_thread_read_components": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _i]),
     "kt_ctr_correct_support": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _i, _u32, _u32]),
     "kt_correct_apply": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _i]),
     "kt_sketch_batch": (_i, [_vp, _vp, _vp, _u64, _i, _u32, _u64, _vp, _vp, _vp, _i]),

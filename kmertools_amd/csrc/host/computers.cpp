@@ -2370,7 +2370,7 @@ std::string UnitigComputer::unitigs() {
         if (std::string e = write_text_file(out_dir_ + "/unitigs.clip.stats", s); !e.empty()) return e;
     }
     // a count-only call, then one call sized by it; with the links only where a file asks for them
-    const bool linked = gfa_ || fa_links_;
+    const bool linked = gfa_ || fa_links_ || components_;
     uint64_t nu = 0, nb = 0, nl = 0;
     if ((linked ? kt_ctr_unitigs_linked(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, nullptr,
                                         nullptr, 0, &nl, KT_MEM_HOST)
@@ -2384,6 +2384,18 @@ std::string UnitigComputer::unitigs() {
                       : kt_ctr_unitigs(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(), nu,
                                        &nu, &nb, KT_MEM_HOST)) != KT_OK)
         return kt_last_error();
+    // the components of that graph: a number per unitig, a row per component
+    std::vector<uint32_t> comp(components_ ? (size_t)nu : 0);
+    std::vector<uint64_t> cstats(components_ ? (size_t)nu * KT_COMPONENT_FIELDS : 0);
+    uint64_t nc = 0, ctally[KT_COMPONENT_TALLY] = {};
+    if (components_) {
+        static const uint32_t no_link[1] = {0};
+        if (kt_unitig_components(dev_.ctx, loff.data(), nl ? lto.data() : no_link, nu, offsets.data(), sums.data(), ksize_, comp.data(),
+                                 cstats.data(), nu, &nc, ctally, KT_MEM_HOST) != KT_OK)
+            return kt_last_error();
+        cstats.resize((size_t)nc * KT_COMPONENT_FIELDS);
+    }
+    const bool tagged = components_ && !stats_only_;  // the CC:i: fields of unitigs.fa and unitigs.gfa
     pt.t[1] += lap();
     const uint64_t overlap = (uint64_t)ksize_ - 1;
     if (!stats_only_) {
@@ -2405,6 +2417,7 @@ std::string UnitigComputer::unitigs() {
                         const int l = snprintf(head, sizeof head, " L:%c:%u:%c", e & 1 ? '-' : '+', lto[j] >> 1, lto[j] & 1 ? '-' : '+');
                         s.append(head, (size_t)l);
                     }
+            if (tagged) s += " CC:i:" + std::to_string(comp[i]);
             s += '\n';
             s.append((const char *)bases.data() + offsets[i], (size_t)len);
             s += '\n';
@@ -2447,10 +2460,12 @@ std::string UnitigComputer::unitigs() {
                 const uint64_t len = offsets[i + 1] - offsets[i];
                 s += "S\t" + std::to_string(i) + '\t';
                 s.append((const char *)bases.data() + offsets[i], (size_t)len);
-                const int h = snprintf(line, sizeof line, "\tLN:i:%llu\tKC:i:%llu\tkm:f:%.1f%s\n", (unsigned long long)len,
+                const int h = snprintf(line, sizeof line, "\tLN:i:%llu\tKC:i:%llu\tkm:f:%.1f%s", (unsigned long long)len,
                                        (unsigned long long)sums[i], (double)sums[i] / (double)(len - overlap),
                                        flags[i] & KT_UNITIG_CIRCULAR ? "\tCL:i:1" : "");
                 s.append(line, (size_t)h);
+                if (tagged) s += "\tCC:i:" + std::to_string(comp[i]);
+                s += '\n';
                 flush(false);
             }
             for (uint64_t e = 0; e < 2 * nu; e++)
@@ -2472,9 +2487,31 @@ std::string UnitigComputer::unitigs() {
         if (!thread_)
             if (std::string e = write_text_file(out_dir_ + "/unitigs.links.stats", s); !e.empty()) return e;
     }
+    if (components_ && !(thread_ && stats_only_)) {
+        std::string s;
+        char line[200];
+        for (uint64_t c = 0; c < nc; c++) {
+            const uint64_t *r = &cstats[(size_t)c * KT_COMPONENT_FIELDS];
+            const int h = snprintf(line, sizeof line, "%llu\t%llu\t%llu\t%llu\t%llu\t%.1f\t%llu\t%llu\n", (unsigned long long)c,
+                                   (unsigned long long)r[0], (unsigned long long)r[1], (unsigned long long)(r[1] + overlap * r[0]),
+                                   (unsigned long long)r[2], (double)r[2] / (double)r[1], (unsigned long long)r[3], (unsigned long long)r[4]);
+            s.append(line, (size_t)h);
+        }
+        if (std::string e = write_text_file(out_dir_ + "/unitigs.components", s); !e.empty()) return e;
+    }
+    if (components_ && !thread_) {
+        static const char *names[4] = {"components", "singletons", "largest_unitigs", "largest_nodes"};
+        const uint64_t nodes = nb - nu * overlap;
+        std::string s;
+        append_stats_rows(s, names, ctally, 4);
+        char line[64];
+        const int h = snprintf(line, sizeof line, "largest_share\t%.4f\n", nodes ? (double)ctally[3] / (double)nodes : 0.0);
+        s.append(line, (size_t)h);
+        if (std::string e = write_text_file(out_dir_ + "/unitigs.components.stats", s); !e.empty()) return e;
+    }
     if (thread_) {  // (`thread` writes its own statistics)
         pt.t[3] += lap();
-        return thread_onto(bases, offsets, sums);
+        return thread_onto(bases, offsets, sums, comp, cstats);
     }
     // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
     std::vector<uint64_t> lens((size_t)nu);
@@ -2506,7 +2543,8 @@ std::string UnitigComputer::unitigs() {
 // `thread`: the unitigs (host arrays, as kt_ctr_unitigs filled them) become the index, the records of thread_reads_ are
 // walked in the usual batches.  The counted table has done its work by now and makes room for the index.
 std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets,
-                                        const std::vector<uint64_t> &sums) {
+                                        const std::vector<uint64_t> &sums, const std::vector<uint32_t> &comp,
+                                        const std::vector<uint64_t> &cstats) {
     PhaseTimer pt("thread");
     Lap lap;
     const uint64_t nu = offsets.size() - 1, nb = offsets[nu], k = (uint64_t)ksize_;
@@ -2525,6 +2563,19 @@ std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const
     const std::string gpath = out_dir_ + "/thread.gaf";
     FILE *fg = stats_only_ ? nullptr : fopen(gpath.c_str(), "wb");
     if (!stats_only_ && !fg) return "Unable to write to file: " + gpath;
+    // --components: every record's component (kt_thread_read_components over the batch's runs), thread.reads
+    const uint64_t nc = cstats.size() / KT_COMPONENT_FIELDS;
+    const std::string rpath = out_dir_ + "/thread.reads";
+    FILE *fr = components_ && !stats_only_ ? fopen(rpath.c_str(), "wb") : nullptr;
+    if (components_ && !stats_only_ && !fr) {
+        if (fg) fclose(fg);
+        return "Unable to write to file: " + rpath;
+    }
+    std::vector<uint32_t> rcomp;
+    std::vector<uint8_t> rmixed;
+    std::vector<uint64_t> creads((size_t)nc, 0), chits((size_t)nc, 0);
+    uint64_t with_comp = 0, n_mixed = 0;
+    std::string rtext;
     Batch batch;
     std::vector<uint32_t> hits, rl, ru, rp;
     std::vector<uint64_t> rs, roff, uh((size_t)nu, 0), ur((size_t)nu, 0);
@@ -2545,6 +2596,30 @@ std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const
         if (nr && kt_thread_runs(dev_.ctx, hits.data(), b.offsets.data(), n, offsets.data(), nu, ksize_, rs.data(), rl.data(), ru.data(), rp.data(),
                                  roff.data(), nr, &nr, uh.data(), ur.data(), tally, KT_MEM_HOST) != KT_OK)
             return kt_last_error();
+        if (components_ && n) {
+            static const uint32_t none[1] = {0};
+            uint64_t t[KT_READ_COMPONENT_TALLY] = {};
+            rcomp.resize(n), rmixed.resize(n);
+            if (kt_thread_read_components(dev_.ctx, nr ? ru.data() : none, nr ? rl.data() : none, roff.data(), n, nu ? comp.data() : none, nu,
+                                          nc, rcomp.data(), rmixed.data(), creads.data(), chits.data(), t, KT_MEM_HOST) != KT_OK)
+                return kt_last_error();
+            with_comp += t[0], n_mixed += t[2];
+            if (fr) {
+                for (uint64_t i = 0; i < n; i++) {
+                    uint64_t h = 0;
+                    for (uint64_t r = roff[i]; r < roff[i + 1]; r++) h += rl[r];
+                    append_name(rtext, b.headers[i]);
+                    rtext += '\t';
+                    if (rcomp[i] == KT_NO_COMPONENT) rtext += '*';
+                    else append_uint(rtext, rcomp[i]);
+                    rtext += rmixed[i] ? "\t1\t" : "\t0\t";
+                    append_uint(rtext, h);
+                    rtext += '\n';
+                }
+                if (!rtext.empty() && fwrite(rtext.data(), 1, rtext.size(), fr) != rtext.size()) return "Unable to write to file: " + rpath;
+                rtext.clear();
+            }
+        }
         pt.t[1] += lap();
         n_reads += n, n_bases += total, n_windows += tally[0], n_hits += tally[1], n_misses += tally[2], n_runs += tally[4], with_hit += tally[5];
         for (uint64_t i = 0; i < n; i++) {
@@ -2596,6 +2671,7 @@ std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const
         return "";
     });
     if (fg && fclose(fg) != 0 && err.empty()) err = "Unable to write to file: " + gpath;
+    if (fr && fclose(fr) != 0 && err.empty()) err = "Unable to write to file: " + rpath;
     if (!err.empty()) return err;
 
     uint64_t unitigs_hit = 0;
@@ -2614,6 +2690,23 @@ std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const
     const uint64_t values[10] = {n_reads, n_bases, n_windows, n_hits, n_misses, n_runs, n_chains, with_hit, whole, unitigs_hit};
     std::string s;
     append_stats_rows(s, names, values, 10);
+    if (components_) {
+        uint64_t comps_hit = 0;
+        text.clear();
+        for (uint64_t c = 0; c < nc; c++) {
+            const uint64_t *r = &cstats[(size_t)c * KT_COMPONENT_FIELDS];
+            for (const uint64_t v : {c, r[0], r[1], creads[c], chits[c]}) {
+                append_uint(text, v);
+                text += '\t';
+            }
+            text.back() = '\n';
+            comps_hit += chits[c] != 0;
+        }
+        if (std::string e = write_text_file(out_dir_ + "/thread.components", text); !e.empty()) return e;
+        static const char *cnames[3] = {"reads_with_component", "reads_mixed", "components_hit"};
+        const uint64_t cvalues[3] = {with_comp, n_mixed, comps_hit};
+        append_stats_rows(s, cnames, cvalues, 3);
+    }
     if (std::string e = write_text_file(out_dir_ + "/thread.stats", s); !e.empty()) return e;
     pt.t[3] += lap();
     return "";

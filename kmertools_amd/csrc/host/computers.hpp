@@ -505,6 +505,14 @@ class UnitigComputer {
     // before anything is written, of the branches of at most bubble_nodes k-mers between the same two ends all but the best
     // are erased, for at most `rounds` rounds - the rounds of set_clip, where both are given
     void set_bubbles(uint32_t bubble_nodes, uint32_t rounds) { pop_ = true, bubble_nodes_ = bubble_nodes, clip_rounds_ = rounds; }
+    // the connected components of the unitig graph (kt_unitig_components over the linked run's arrays, after set_clip /
+    // set_bubbles did their work): {out_dir}/unitigs.components (per component: component, unitigs, nodes, bases, count_sum, km,
+    // links, first_unitig) and unitigs.components.stats (components, singletons, largest_unitigs, largest_nodes, largest_share),
+    // unitigs.links.stats as with gfa, and - not with stats_only - " CC:i:{c}" behind every header line of unitigs.fa and
+    // "\tCC:i:{c}" behind every S line of unitigs.gfa.  With set_thread: unitigs.fa, unitigs.gfa and unitigs.components as
+    // above, thread.reads (per record: name, component or *, mixed, hits; not with stats_only), thread.components (per
+    // component: component, unitigs, nodes, reads, hits) and three more lines of thread.stats (kt_thread_read_components)
+    void set_components(bool c) { components_ = c; }
     void set_device(int d) { dev_.index = d; }
     // `thread`: the unitigs are written as `unitigs --gfa` writes unitigs.fa and unitigs.gfa (stats_only: not at all) and no
     // other unitigs.* file; then the records of reads_path are threaded onto them (kt_ctr_index_sequences over the unitigs,
@@ -516,7 +524,8 @@ class UnitigComputer {
     std::string unitigs();  // "" or the error message
 
   private:
-    std::string thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &sums);
+    std::string thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &sums,
+                            const std::vector<uint32_t> &comp, const std::vector<uint64_t> &cstats);
     bool thread_ = false;
     std::string thread_reads_;
     std::string in_path_, out_dir_;
@@ -524,7 +533,7 @@ class UnitigComputer {
     int ksize_;
     uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
     bool stats_only_ = false, gfa_ = false, fa_links_ = false;
-    bool clip_ = false, drop_isolated_ = false, pop_ = false;
+    bool clip_ = false, drop_isolated_ = false, pop_ = false, components_ = false;
     uint32_t tip_nodes_ = 0, clip_rounds_ = 8, bubble_nodes_ = 0;
     Device dev_;
     kt_ctr *table_ = nullptr;

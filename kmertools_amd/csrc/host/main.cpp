@@ -1179,6 +1179,14 @@ const char *HELP_UNITIGS =
     "of every round, so that a bubble behind a tip pops in the round after the tip went.  {output}/unitigs.simplify.stats then\n"
     "holds rounds, tips, tip_nodes, isolated, isolated_nodes, popped, popped_nodes, bubbles, occurrences (all erased) and\n"
     "converged, and takes the place of unitigs.clip.stats.\n\n"
+    "--components finds the connected components of the graph that is written (after --clip-tips / --pop-bubbles): two unitigs\n"
+    "are in one component when a chain of links, followed in either direction, joins them.  Components are numbered by their\n"
+    "smallest unitig.  {output}/unitigs.components holds one line per component:\n"
+    "component<TAB>unitigs<TAB>nodes<TAB>bases<TAB>count_sum<TAB>km<TAB>links<TAB>first_unitig (bases = nodes + (k - 1) * unitigs,\n"
+    "km = count_sum / nodes, links = the directed links its unitigs' ends own); {output}/unitigs.components.stats holds\n"
+    "components, singletons (components of one unitig), largest_unitigs, largest_nodes and largest_share (largest_nodes / nodes);\n"
+    "unitigs.links.stats is written as with --gfa.  Unless --stats-only is given, every header line of unitigs.fa gains\n"
+    "\" CC:i:{component}\" and every S line of unitigs.gfa \"<TAB>CC:i:{component}\", behind the other fields.\n\n"
     "Usage: kmertools unitigs [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
     "Options:\n"
     "  -i, --input <INPUT>          Input file path\n"
@@ -1196,6 +1204,8 @@ const char *HELP_UNITIGS =
     "      --pop-bubbles            Erase all but the best of parallel branches before the unitigs are written; also\n"
     "                               unitigs.simplify.stats\n"
     "      --bubble-nodes <N>       Longest branch of a bubble, in k-mers [default: 2k] (needs --pop-bubbles)\n"
+    "      --components             Also write unitigs.components, unitigs.components.stats and unitigs.links.stats; CC:i: fields\n"
+    "                               in unitigs.fa and unitigs.gfa (allowed with --stats-only)\n"
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for graph; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for graph)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
@@ -1208,7 +1218,7 @@ int cmd_unitigs(int argc, char **argv, int from) {
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
                                      {0, "device", true},      {0, "gfa", false},          {0, "links", false},
                                      {0, "clip-tips", false},  {0, "tip-nodes", true},     {0, "clip-rounds", true},
-                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, {0, "components", false}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
     // (--table FILE stands in for --input)
     const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
@@ -1244,6 +1254,7 @@ int cmd_unitigs(int argc, char **argv, int from) {
         UnitigComputer uc(in, out, k);
         uc.set_table_file(table);
         uc.set_links(gfa, links);
+        uc.set_components(f.count("components") != 0);
         if (clip) uc.set_clip((uint32_t)tip_nodes, (uint32_t)clip_rounds, f.count("drop-isolated") != 0);
         if (pop) uc.set_bubbles((uint32_t)bubble_nodes, (uint32_t)clip_rounds);
         uc.set_range((uint32_t)lo, (uint32_t)hi);
@@ -1272,6 +1283,14 @@ const char *HELP_THREAD =
     "  thread.unitigs  per unitig: id, bases, nodes (k-mers), count sum of the graph, hits, runs, hits / nodes\n"
     "  thread.stats    \"name<TAB>value\" lines: reads, bases, windows, hits, misses, runs, chains, reads_with_hit,\n"
     "                  reads_one_chain_end_to_end, unitigs_hit\n"
+    "With --components the unitigs' connected components are found as `unitigs --components` finds them, and:\n"
+    "  unitigs.fa, unitigs.gfa  are those of `unitigs --gfa --components` (a CC:i: field per unitig); unitigs.components as there\n"
+    "  thread.reads       one line per record of --input, in input order: name<TAB>component|*<TAB>mixed<TAB>hits - the\n"
+    "                     component of the record's first run (* without a run), 1 when a later run lies in another component\n"
+    "                     (else 0), and the record's hits\n"
+    "  thread.components  per component: component<TAB>unitigs<TAB>nodes<TAB>reads<TAB>hits (the records counted at the component\n"
+    "                     of their first run, every run's hits at its own)\n"
+    "  thread.stats       gains reads_with_component, reads_mixed, components_hit\n"
     "The whole table must fit the device memory, as for `unitigs`; the unitigs may hold at most 2^31 - 2 bases.\n\n"
     "Usage: kmertools thread [OPTIONS] --input <INPUT> --output <OUTPUT> --k-size <K_SIZE>\n\n"
     "Options:\n"
@@ -1281,7 +1300,9 @@ const char *HELP_THREAD =
     "  -k, --k-size <K_SIZE>        k size for counting\n"
     "      --min-count <N>          Lowest count of a node [default: 1]\n"
     "      --max-count <N>          Highest count of a node [default: 4294967295]\n"
-    "      --stats-only             Write thread.unitigs and thread.stats only\n"
+    "      --stats-only             Write thread.unitigs and thread.stats only (with --components: thread.components too)\n"
+    "      --components             Split the records by the connected component of the unitigs they land in: thread.reads,\n"
+    "                               thread.components, unitigs.components, CC:i: fields\n"
     "  -m, --memory <MEMORY>        Max memory in GB [default: 6] (accepted as for unitigs; the table lives in HBM)\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0] (accepted as for unitigs)\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
@@ -1292,7 +1313,7 @@ const char *HELP_THREAD =
 int cmd_thread(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'a', "alt-input", true}, {'o', "output", true},  {'k', "k-size", true},
                                      {0, "min-count", true},   {0, "max-count", true},   {0, "stats-only", false}, {'m', "memory", true},
-                                     {'t', "threads", true},   {0, "device", true},      SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true},   {0, "device", true},      {0, "components", false}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
     const auto f = parse_flags(argc, argv, from, specs, HELP_THREAD);
     const std::string in = required_str(f, "input"), out = required_str(f, "output");
     const int k = (int)ranged(f, "k-size", 10, 31, true, 0);
@@ -1319,6 +1340,7 @@ int cmd_thread(int argc, char **argv, int from) {
         uc.set_table_file(table);
         uc.set_range((uint32_t)lo, (uint32_t)hi);
         uc.set_thread(in, f.count("stats-only") != 0);
+        uc.set_components(f.count("components") != 0);
         uc.set_device(device);
         return uc.unitigs();
     });

@@ -1,6 +1,6 @@
 // kt_launch.hpp - what the host code of the extern "C" entry points shares: launch helpers of the segment front-end,
-// argument checks that several entry points make in the same words, ktl::launch and ktl::carve_parts (one kernel launch;
-// typed arrays cut from one buffer), and ktl::Call, the one path by which an entry point moves its arguments between the
+// argument checks that several entry points make in the same words, ktl::launch, ktl::carve_parts and ktl::carve (one kernel
+// launch; typed arrays cut from one buffer; one claim of a scratch buffer cut that way), and ktl::Call, the one path by which an entry point moves its arguments between the
 // caller's memory and the device.  Defined in kt_launch.hip, the templates here.
 #pragma once
 #include <memory>
@@ -144,5 +144,15 @@ private:
     Copy copies_[8];
     int n_copies_ = 0;
 };
+
+// carve(call, buf, &a, count_a, &b, count_b, ...): one claim of a scratch buffer, cut into typed arrays that each take a
+// multiple of 16 bytes (carve_parts)
+template <class... Parts>
+int carve(Call &call, kt::Buf buf, Parts... parts) {
+    uint8_t *b = nullptr;
+    if (int rc = call.scratch(buf, carve_parts<16>(nullptr, parts...), &b)) return rc;
+    carve_parts<16>(b, parts...);
+    return KT_OK;
+}
 
 }  // namespace ktl

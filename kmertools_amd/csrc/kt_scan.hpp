@@ -1,10 +1,10 @@
 // kt_scan.hpp - the exclusive scan over n items, two u64 sums at once, written once over a functor F (kt_unitig.hip's
-// stages d and g, kt_tablefile.hip's escape ranks, kt_thread.hip's run numbering): word(i) is item i's one u32, add(word, a, b) what it contributes to the
+// stages d and g, kt_tablefile.hip's escape ranks, kt_thread.hip's run numbering, kt_component.hip's component numbering): word(i) is item i's one u32, add(word, a, b) what it contributes to the
 // two sums (word 0, the filler past n, contributes nothing), put(i, a, b) takes the sums over the items before i, total()
 // is thread 0's after the last put.  Three launches: the tiles' sums (scan2_tile_sum_kernel), one workgroup over those
 // (scan2_tile_scan_kernel, which also leaves the two totals), and the tiles again (scan2_apply_kernel).
 // The kernels sit in an unnamed namespace: every translation unit that includes this gets its own copy of them in the
-// code object (three today - kt_unitig.hip, kt_tablefile.hip, kt_thread.hip; only scan2_tile_scan_kernel is no template and so
+// code object (four today - kt_unitig.hip, kt_tablefile.hip, kt_thread.hip, kt_component.hip; only scan2_tile_scan_kernel is no template and so
 // truly repeated: tolerable; a user that needs more of it should move them into a translation unit of their own).
 #pragma once
 #include "kt_device.hpp"

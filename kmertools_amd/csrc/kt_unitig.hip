@@ -410,16 +410,6 @@ dim3 blocks_for(uint64_t items, uint64_t per_block = BLOCK) { return dim3((uint3
 
 size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
-// carve(call, buf, &a, count_a, &b, count_b, ...): one claim of a scratch buffer, cut into typed arrays that each take a
-// multiple of 16 bytes (ktl::carve_parts).
-template <class... Parts>
-int carve(Call &call, kt::Buf buf, Parts... parts) {
-    uint8_t *b = nullptr;
-    if (int rc = call.scratch(buf, ktl::carve_parts<16>(nullptr, parts...), &b)) return rc;
-    ktl::carve_parts<16>(b, parts...);
-    return KT_OK;
-}
-
 // ---- h, i, j. tips ---------------------------------------------------------------------------------------------------
 
 // what the rule reads: the outputs of the linked run, on the device

@@ -25,6 +25,9 @@ CLIP_STATS_NAMES = ("rounds", "tips", "tip_nodes", "isolated", "isolated_nodes",
 BUBBLE_POP = 4  # Counter.unitig_bubbles' mark (KT_BUBBLE_POP): a bit beside TIP_TIP and TIP_ISOLATED
 SIMPLIFY_STATS_NAMES = ("rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "popped", "popped_nodes", "bubbles", "occurrences",
                         "converged")
+NO_COMPONENT = 0xFFFFFFFF  # KT_NO_COMPONENT: the component of a read without a run
+COMPONENT_FIELDS = 5  # KT_COMPONENT_FIELDS: the columns of Context.unitig_components' stats
+COMPONENT_STATS_NAMES = ("unitigs", "nodes", "count_sum", "links", "first_unitig")
 
 
 def _ptr(x):
@@ -440,6 +443,62 @@ class Context:
         if nr:
             self.thread_runs(h, read_offsets, n, unitig_offsets, nu, k, out["run_start"], out["run_len"], out["run_unitig"],
                              out["run_upos"], out["run_offsets"], nr, unitig_hits, unitig_runs, out["tally"], KT_MEM_HOST)
+        return out
+
+    # -- components: which unitigs hang together, and the reads split by them ------------------
+    def unitig_components(self, link_offsets, link_to, n_unitigs, component, unitig_offsets=None, count_sums=None, k=1, stats=None,
+                          max_components=0, tally=None, mem=KT_MEM_DEVICE):
+        """the weakly connected components of the unitig graph from Counter.unitig_links' link arrays: component (u32 per
+        unitig) = the component's number, components numbered by their smallest unitig; stats (u64, max_components x
+        COMPONENT_FIELDS: COMPONENT_STATS_NAMES) and tally (u64[6]: components, components of one unitig, most unitigs, most
+        nodes, bad links, rounds) are overwritten.  Returns the number of components; raises KmertoolsError (KT_ERR_ARG)
+        when 0 < max_components < that number (kt_unitig_components)."""
+        n = C.c_uint64()
+        check(_lib.lib().kt_unitig_components(self._h, _ptr(link_offsets), _ptr(link_to), int(n_unitigs), _ptr(unitig_offsets),
+                                              _ptr(count_sums), int(k), _ptr(component), _ptr(stats), int(max_components),
+                                              C.byref(n), _ptr(tally), mem))
+        return n.value
+
+    def unitig_components_host(self, link_offsets, link_to, unitig_offsets=None, count_sums=None, k=None):
+        """-> {"component" u32 per unitig, "stats" u64 (components x COMPONENT_FIELDS), "tally" u64[6]} of host arrays"""
+        link_offsets = np.ascontiguousarray(link_offsets, np.uint64)
+        link_to = np.ascontiguousarray(link_to, np.uint32)
+        nu = (len(link_offsets) - 1) // 2
+        if unitig_offsets is not None:
+            unitig_offsets = np.ascontiguousarray(unitig_offsets, np.uint64)
+        if count_sums is not None:
+            count_sums = np.ascontiguousarray(count_sums, np.uint64)
+        comp = np.zeros(nu, np.uint32)
+        stats = np.zeros((nu, _lib.KT_COMPONENT_FIELDS), np.uint64)
+        tally = np.zeros(_lib.KT_COMPONENT_TALLY, np.uint64)
+        nc = self.unitig_components(link_offsets, link_to if link_to.size else np.zeros(1, np.uint32), nu, comp, unitig_offsets,
+                                    count_sums, 1 if k is None else k, stats if nu else None, nu, tally, KT_MEM_HOST)
+        return {"component": comp, "stats": stats[:nc].copy(), "tally": tally}
+
+    def thread_read_components(self, run_unitig, run_len, run_offsets, n_reads, component, n_unitigs, n_components, read_component,
+                               read_mixed=None, comp_reads=None, comp_hits=None, tally=None, mem=KT_MEM_DEVICE):
+        """thread_runs' runs folded over unitig_components' component array: read_component (u32 per read) = the component of
+        the read's first run (NO_COMPONENT: none), read_mixed (u8 per read, or None) = a later run lies in another one;
+        comp_reads / comp_hits (u64 per component, or None) are added to; tally (u64[4], overwritten) = reads with a component,
+        without, mixed reads, bad runs (kt_thread_read_components)"""
+        check(_lib.lib().kt_thread_read_components(self._h, _ptr(run_unitig), _ptr(run_len), _ptr(run_offsets), int(n_reads),
+                                                   _ptr(component), int(n_unitigs), int(n_components), _ptr(read_component),
+                                                   _ptr(read_mixed), _ptr(comp_reads), _ptr(comp_hits), _ptr(tally), mem))
+
+    def thread_read_components_host(self, run_unitig, run_len, run_offsets, component, n_components, comp_reads=None, comp_hits=None):
+        """-> {"read_component" u32, "read_mixed" u8, "tally" u64[4]} of host arrays; comp_reads / comp_hits (u64 per
+        component, or None) are added to"""
+        run_unitig = np.ascontiguousarray(run_unitig, np.uint32)
+        run_len = np.ascontiguousarray(run_len, np.uint32)
+        run_offsets = np.ascontiguousarray(run_offsets, np.uint64)
+        component = np.ascontiguousarray(component, np.uint32)
+        n = len(run_offsets) - 1
+        out = {"read_component": np.zeros(n, np.uint32), "read_mixed": np.zeros(n, np.uint8),
+               "tally": np.zeros(_lib.KT_READ_COMPONENT_TALLY, np.uint64)}
+        one = np.zeros(1, np.uint32)
+        self.thread_read_components(run_unitig if run_unitig.size else one, run_len if run_len.size else one, run_offsets, n,
+                                    component if component.size else one, len(component), n_components, out["read_component"],
+                                    out["read_mixed"], comp_reads, comp_hits, out["tally"], KT_MEM_HOST)
         return out
 
     # -- correct: the decision over a support array (Counter.correct_support) ------------------
@@ -955,6 +1014,33 @@ class Counter:
                                                _ptr(count_sums), _ptr(flags), int(max_unitigs), C.byref(nu), C.byref(nb),
                                                _ptr(link_offsets), _ptr(link_to), int(max_links), C.byref(nl), KT_MEM_DEVICE))
         return nu.value, nb.value, nl.value
+
+    def unitig_components(self, min_count=1, max_count=None):
+        """The connected components of the unitig graph (unitig_links' unitigs and links): the linked run into device tensors,
+        then Context.unitig_components on them.  Returns {"component", "stats", "tally", "n_unitigs"} of host arrays."""
+        import torch
+        nu, nb, nl = self.unitigs_linked_device(None, 0, None, None, None, 0, None, None, 0, min_count, max_count)
+        out = {"component": np.zeros(nu, np.uint32), "stats": np.zeros((0, _lib.KT_COMPONENT_FIELDS), np.uint64),
+               "tally": np.zeros(_lib.KT_COMPONENT_TALLY, np.uint64), "n_unitigs": nu}
+        if not nu:
+            return out
+        dev = torch.device("cuda", self.ctx.device)
+        bases = torch.empty(nb, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(nu + 1, dtype=torch.int64, device=dev)
+        sums = torch.empty(nu, dtype=torch.int64, device=dev)
+        flags = torch.empty(nu, dtype=torch.int32, device=dev)
+        link_offsets = torch.empty(2 * nu + 1, dtype=torch.int64, device=dev)
+        link_to = torch.empty(max(nl, 1), dtype=torch.int32, device=dev)
+        self.unitigs_linked_device(bases, nb, offsets, sums, flags, nu, link_offsets, link_to, nl, min_count, max_count)
+        comp = torch.empty(nu, dtype=torch.int32, device=dev)
+        stats = torch.empty((nu, _lib.KT_COMPONENT_FIELDS), dtype=torch.int64, device=dev)
+        tally = torch.empty(_lib.KT_COMPONENT_TALLY, dtype=torch.int64, device=dev)
+        nc = self.ctx.unitig_components(link_offsets, link_to, nu, comp, offsets, sums, self.k, stats, nu, tally)
+        self.ctx.sync()
+        out["component"] = comp.cpu().numpy().view(np.uint32)
+        out["stats"] = stats[:nc].cpu().numpy().view(np.uint64)
+        out["tally"] = tally.cpu().numpy().view(np.uint64)
+        return out
 
     def unitig_tips(self, max_tip_nodes=None, min_count=1, max_count=None):
         """One round of the tip rule over unitigs()' numbering (kt_ctr_unitig_tips; the table is not changed): returns (marks u8:
