@@ -15,8 +15,10 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <thread>
 
+#include "outfile.hpp"
 #include "seqio.hpp"
 
 namespace kthost {
@@ -163,6 +165,26 @@ static void format_rows(uint64_t n, int threads, size_t bytes_per_row, std::vect
     for (auto &th : pool) th.join();
 }
 
+// Rows [0, n) as text into one file, or side by side into several: `slab` rows at a time (the host holds one slab's text),
+// each file's share of a slab formatted by fn(row, out) on the workers and written before the next file's; a failure ends it.
+template <class F>
+struct RowText {
+    OutFile &out;
+    size_t bytes_per_row;
+    F fn;
+    RowText(OutFile &o, size_t b, F f) : out(o), bytes_per_row(b), fn(f) {}
+};
+template <class... R>
+static void write_rows(uint64_t n, uint64_t slab, int threads, std::vector<std::string> &pieces, R... files) {
+    for (uint64_t i0 = 0; i0 < n && !(files.out.failed() || ...); i0 += slab) {
+        auto one = [&](auto &f) {
+            format_rows(std::min(slab, n - i0), threads, f.bytes_per_row, pieces, [&](uint64_t r, std::string &s) { f.fn(i0 + r, s); });
+            f.out.write(pieces);
+        };
+        (one(files), ...);
+    }
+}
+
 // ---- read -> device -> text pipeline ---------------------------------------------------------
 // The three stages of every vectoriser (parse a batch of records; one C-ABI call that stages the
 // batch to the GPU and brings the rows back; format + write the rows) run on their own threads
@@ -262,7 +284,8 @@ class Channel {
 
 // Writes formatted batches on its own thread, so formatting batch i + 1 overlaps the write of batch i.
 // write() swaps the caller's pieces with a drained spare (capacities survive, nothing is reallocated)
-// and blocks only when two batches are already waiting.
+// and blocks only when two batches are already waiting.  It takes the stream of an OutFile declared before it (leaving the
+// scope finishes the writer, then closes the file) and does not look at what fwrite returns: its commands report no write error.
 class AsyncWriter {
     using Pieces = std::vector<std::string>;
     FILE *out_;
@@ -375,15 +398,21 @@ static const uint8_t *bases_ptr(const Batch &b) { return b.bases.empty() ? (cons
 // ---- what the table commands share: small text files, the input walk, values kept across passes ------------------
 // a whole small file from a string: "" or the error message
 static std::string write_text_file(const std::string &path, const std::string &text) {
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + path;
-    const bool ok = fwrite(text.data(), 1, text.size(), out) == text.size();
-    return fclose(out) == 0 && ok ? "" : "Unable to write to file: " + path;
+    OutFile out;
+    if (std::string e = out.open(path); !e.empty()) return e;
+    out.write(text);
+    return out.close();
 }
 
 // "name\tvalue\n" lines (the *.stats files)
 static void append_stats_rows(std::string &s, const char *const *names, const uint64_t *values, size_t n) {
     for (size_t j = 0; j < n; j++) s += std::string(names[j]) + '\t' + std::to_string(values[j]) + '\n';
+}
+// a *.stats file of such lines and nothing else
+static std::string write_stats_file(const std::string &path, const char *const *names, const uint64_t *values, size_t n) {
+    std::string s;
+    append_stats_rows(s, names, values, n);
+    return write_text_file(path, s);
 }
 
 // one FASTA / FASTQ record: header line, `len` bases on one line, for FASTQ "+" and `len` quality bytes
@@ -417,6 +446,16 @@ static void append_uint(std::string &out, uint64_t v) {
     char buf[24];
     const auto e = std::to_chars(buf, buf + sizeof buf, v);
     out.append(buf, (size_t)(e.ptr - buf));
+}
+static std::string matrix_text(const std::vector<uint64_t> &m, uint32_t R, uint32_t C) {  // R lines of C tab-separated counts
+    std::string s;
+    s.reserve((size_t)R * C * 2);
+    for (uint32_t r = 0; r < R; r++)
+        for (uint32_t c = 0; c < C; c++) append_uint(s, m[(size_t)r * C + c]), s += c + 1 < C ? '\t' : '\n';
+    return s;
+}
+static void append_tab_uints(std::string &out, std::initializer_list<uint64_t> vs) {  // "\t{v}" for every v
+    for (const uint64_t v : vs) out += '\t', append_uint(out, v);
 }
 
 // The input walk of every command that does not go through run_pipeline: batches of at most max_bases / max_reads
@@ -525,20 +564,20 @@ double debug_emit_bench(uint64_t n_rows, uint64_t bins, bool norm, int threads, 
         const double c = (double)((i * 2654435761ull >> 7) % 5);
         w.rows[i] = norm ? c / 147.0 : c;
     }
-    FILE *out = fopen("/dev/null", "wb");
+    OutFile out;
+    (void)out.open("/dev/null");
     std::vector<std::string> pieces;
     PhaseTimer pt("debug-emit");
     double best = 1e30;
     for (int i = 0; i < reps; i++) {
         Lap lap;
         {
-            AsyncWriter writer(out, pt);
+            AsyncWriter writer(out.stream(), pt);
             emit_matrix(writer, w, bins, norm, " ", threads, pieces, pt);
         }
         const double d = lap();
         if (d < best) best = d;
     }
-    fclose(out);
     return best;
 }
 
@@ -574,8 +613,8 @@ std::string OligoComputer::vectorise() {
     // the reference sniffs the first byte on its batch path (stdin or raw counts) and trusts the
     // extension on its mmap path; an unknown extension falls back to sniffing here
     if (!reader.open(in_path_, in_path_ == "-" || !norm_)) return reader.error();
-    FILE *out = fopen(out_path_.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path_;
+    OutFile out;
+    if (std::string e = out.open(out_path_); !e.empty()) return e;
     // (the device context is created by the first device call: HIP start-up, 0.1-0.3 s, then runs while the reader
     // thread parses the first batch)
     uint64_t bins = 0;
@@ -588,12 +627,12 @@ std::string OligoComputer::vectorise() {
             line += h[i];
         }
         line += "\n";
-        fwrite(line.data(), 1, line.size(), out);
+        out.write(line);
     }
     std::vector<std::string> pieces;
     PhaseTimer pt("comp oligo");
-    AsyncWriter writer(out, pt);
-    const std::string err = run_pipeline(
+    AsyncWriter writer(out.stream(), pt);
+    return run_pipeline(
         reader, batch_bases(memory_), 1ull << 19, pt,
         [&](Work &w) -> std::string {
             if (std::string e = dev_.ensure(); !e.empty()) return e;
@@ -611,9 +650,6 @@ std::string OligoComputer::vectorise() {
             if (norm_) emit_matrix(writer, w, bins, true, delim_, threads_, pieces, pt);
             else emit_counts(writer, w, bins, delim_, threads_, pieces, pt);
         });
-    writer.finish();
-    fclose(out);
-    return err;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -623,12 +659,9 @@ OligoCgrComputer::OligoCgrComputer(std::string in_path, std::string out_path, in
 std::string OligoCgrComputer::vectorise() {
     SeqReader reader;
     if (!reader.open(in_path_, true)) return reader.error();  // oligocgr.rs:64-72 sniffs '>'
-    FILE *out = fopen(out_path_.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path_;
-    if (std::string e = dev_.ensure(); !e.empty()) {
-        fclose(out);
-        return e;
-    }
+    OutFile out;
+    if (std::string e = out.open(out_path_); !e.empty()) return e;
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
     uint64_t bins = 0;
     kt_bins(ksize_, 1, &bins);
     // the CGR point of every canonical k-mer is read-independent: build "(x,y," once
@@ -645,10 +678,10 @@ std::string OligoCgrComputer::vectorise() {
     }
     std::vector<std::string> pieces;
     PhaseTimer pt("comp cgr -k");
-    AsyncWriter writer(out, pt);
+    AsyncWriter writer(out.stream(), pt);
     // rows are 8 * bins bytes each: bound the batch by reads as well
     const uint64_t max_reads = bins >= 2048 ? 8192 : 262144;
-    const std::string err = run_pipeline(
+    return run_pipeline(
         reader, batch_bases(memory_), max_reads, pt,
         [&](Work &w) -> std::string {
             const uint64_t n = w.b.n_reads();
@@ -676,9 +709,6 @@ std::string OligoCgrComputer::vectorise() {
             pt.t[2] += lap();
             writer.write(pieces);
         });
-    writer.finish();
-    fclose(out);
-    return err;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -688,17 +718,14 @@ CgrComputer::CgrComputer(std::string in_path, std::string out_path, uint64_t vec
 std::string CgrComputer::vectorise() {
     SeqReader reader;
     if (!reader.open(in_path_, true)) return reader.error();  // cgr.rs:68-76 sniffs '>'
-    FILE *out = fopen(out_path_.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path_;
-    if (std::string e = dev_.ensure(); !e.empty()) {
-        fclose(out);
-        return e;
-    }
+    OutFile out;
+    if (std::string e = out.open(out_path_); !e.empty()) return e;
+    if (std::string e = dev_.ensure(); !e.empty()) return e;
     std::vector<std::string> pieces;
     PhaseTimer pt("comp cgr (whole sequence)");
-    AsyncWriter writer(out, pt);
+    AsyncWriter writer(out.stream(), pt);
     // 16 bytes of points and ~40 bytes of text per base: keep the batches small
-    const std::string err = run_pipeline(
+    return run_pipeline(
         reader, 16ull << 20, 1ull << 18, pt,
         [&](Work &w) -> std::string {
             const uint64_t n = w.b.n_reads();
@@ -730,9 +757,6 @@ std::string CgrComputer::vectorise() {
             pt.t[2] += lap();
             writer.write(pieces);
         });
-    writer.finish();
-    fclose(out);
-    return err;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -796,17 +820,17 @@ static uint64_t peak_rss_kb() { return mem_report().hwm_kb; }
 // freed blocks moved the process's peak by +-100 MB from run to run).
 class TableWriter {
   public:
-    TableWriter(bool acgt, int k, int threads, double ceil_gb) : acgt_(acgt), k_(k), threads_(threads) {
+    // --min-count / --max-count: only the entries with lo <= count <= hi are staged (kt_ctr_export_stage_range; the full
+    // range is kt_ctr_export_stage itself)
+    TableWriter(bool acgt, int k, int threads, double ceil_gb, uint32_t lo = 1, uint32_t hi = 0xFFFFFFFFu)
+        : acgt_(acgt), k_(k), threads_(threads), lo_(lo), hi_(hi) {
         // ~64 bytes of host memory per entry of a slab (12 of pairs, the rest text in flight): a million entries at a
         // time - 64 MB, far below any ceiling -m accepts (6 .. 128 GB); a sixteenth of the ceiling if that were smaller
         slab_ = (uint64_t)(ceil_gb * (double)(1ull << 30) / 16.0 / 64.0);
         if (slab_ > (1ull << 20)) slab_ = 1ull << 20;
         if (slab_ < (1ull << 16)) slab_ = 1ull << 16;
     }
-    // --min-count / --max-count: only the entries with lo <= count <= hi are staged (kt_ctr_export_stage_range; the full
-    // range is kt_ctr_export_stage itself)
-    void set_range(uint32_t lo, uint32_t hi) { lo_ = lo, hi_ = hi; }
-    std::string write(FILE *out, kt_ctr *ctr, uint64_t *n_out) {
+    std::string write(OutFile &out, kt_ctr *ctr, uint64_t *n_out) {
         uint64_t n = 0;
         if (kt_ctr_export_stage_range(ctr, lo_, hi_, &n) != KT_OK) return kt_last_error();
         if (n && keys_.empty()) {
@@ -824,13 +848,10 @@ class TableWriter {
         return "";
     }
     // the same lines from (key, count) pairs the caller holds on the host (setop's result), the text a slab at a time
-    std::string write_pairs(FILE *out, const uint64_t *keys, const uint32_t *counts, uint64_t n) {
-        for (uint64_t i0 = 0; i0 < n; i0 += slab_) {
-            if (std::string e = emit(out, keys + i0, counts + i0, n - i0 < slab_ ? n - i0 : slab_); !e.empty()) return e;
-            slabs_++;
-        }
+    std::string write_pairs(OutFile &out, const uint64_t *keys, const uint32_t *counts, uint64_t n) {
+        slabs_ += (n + slab_ - 1) / slab_;
         entries_ += n;
-        return "";
+        return emit(out, keys, counts, n);
     }
     // bytes held in the writer's own buffers (capacities: what stays allocated between slabs)
     uint64_t buffer_bytes() const {
@@ -843,24 +864,21 @@ class TableWriter {
     uint64_t slabs() const { return slabs_; }
 
   private:
-    // one slab's text, formatted on the workers and written
-    std::string emit(FILE *out, const uint64_t *keys, const uint32_t *counts, uint64_t m) {
+    // the text of m entries, a slab at a time, formatted on the workers and written
+    std::string emit(OutFile &out, const uint64_t *keys, const uint32_t *counts, uint64_t m) {
         // "{kmer}\t{count}\n" (or the ACGT form), counter/src/lib.rs:220-230
-        format_rows(m, threads_, acgt_ ? (size_t)k_ + 13 : 32, pieces_, [&](uint64_t i, std::string &s) {
+        write_rows(m, slab_, threads_, pieces_, RowText(out, acgt_ ? (size_t)k_ + 13 : 32, [&](uint64_t i, std::string &s) {
             append_kmer(s, keys[i], k_, acgt_);
-            s += '\t';
-            append_uint(s, counts[i]);
+            append_tab_uints(s, {counts[i]});
             s += '\n';
-        });
+        }));
         const uint64_t h = heap_in_use_kb();  // with a slab's pairs and its text in hand: the writer's high point
         if (h > heap_peak_kb_) heap_peak_kb_ = h;
-        for (const auto &p : pieces_)
-            if (fwrite(p.data(), 1, p.size(), out) != p.size()) return "Unable to write the table's lines";
-        return "";
+        return out.failed() ? "Unable to write the table's lines" : "";
     }
     bool acgt_;
     int k_, threads_;
-    uint32_t lo_ = 1, hi_ = 0xFFFFFFFFu;
+    uint32_t lo_, hi_;
     uint64_t slab_ = 0, slabs_ = 0, entries_ = 0, heap_peak_kb_ = 0;
     std::vector<uint64_t> keys_;
     std::vector<uint32_t> counts_;
@@ -1088,8 +1106,7 @@ std::string CountComputer::count() {
         fprintf(stderr, "[timing] ctr setup: sizing (pre-pass only for compressed input) %.3f s, device init %.3f s, table of %llu slots, %u pass(es) %.3f s\n",
                 t_stats, t_dev, (unsigned long long)slots, passes_, setup());
     }
-    FILE *out = nullptr;
-    const std::string path = out_dir_ + "/kmers.counts";
+    OutFile out;  // kmers.counts, out of core: opened when the first pass has lines for it
     PhaseTimer pt("ctr count (after the seq_stats pre-pass)");
     const bool timing = getenv("KT_CLI_TIMING") != nullptr;
     // One reader, one batch and one table writer serve every pass: a pass rewinds the reader (its threads, cuts and
@@ -1098,8 +1115,7 @@ std::string CountComputer::count() {
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
     Batch b;
-    TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
-    writer.set_range(min_count_, max_count_);
+    TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_, min_count_, max_count_);
     uint64_t heap_after_first = 0, rss_after_first = 0;
     struct Partial {  // --save-table out of core: removed unless the run gets to rename it
         std::string path;
@@ -1123,8 +1139,8 @@ std::string CountComputer::count() {
         // - its lines go to kmers.counts, and the table is reused
         uint64_t n_pass = 0;
         if (!histo_only_) {
-            if (!out) out = fopen(path.c_str(), "wb");
-            if (!out) return "Unable to write to file: " + path;
+            if (!out.is_open())
+                if (std::string e = out.open(out_dir_ + "/kmers.counts"); !e.empty()) return e;
             if (std::string e = writer.write(out, ctr_, &n_pass); !e.empty()) return e;
         }
         if (!save_table_.empty()) {  // one section per pass (a k-mer lives in one partition), under a name of its own until
@@ -1147,7 +1163,6 @@ std::string CountComputer::count() {
         }
         if (kt_ctr_clear(ctr_) != KT_OK) return kt_last_error();
     }
-    if (out) fclose(out);
     if (!partial.path.empty()) {
         if (rename(partial.path.c_str(), save_table_.c_str()) != 0) return "Unable to write to file: " + save_table_;
         partial.path.clear();
@@ -1334,21 +1349,17 @@ std::string CountComputer::merge(bool /*del: no temp files exist to delete*/) {
     if (passes_ > 1) return histo_max_ ? write_histo() : "";
     const std::string path = out_dir_ + "/kmers.counts";
     if (sharded_done_) {  // the shards, one after the other, each in slabs (the reference's line order is unspecified)
-        FILE *out = nullptr;
-        if (!histo_only_) {
-            out = fopen(path.c_str(), "wb");
-            if (!out) return "Unable to write to file: " + path;
-        }
+        OutFile out;
+        if (!histo_only_)
+            if (std::string e = out.open(path); !e.empty()) return e;
         std::string err;
-        TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
-        writer.set_range(min_count_, max_count_);
+        TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_, min_count_, max_count_);
         for (size_t r = 0; r < shards_.size() && err.empty(); r++) {
             kt_ctr *t = nullptr;
             if (kt_sharded_table(shards_[r], &t) != KT_OK) err = kt_last_error();
             else if (histo_max_ && !(err = add_spectrum(t)).empty()) break;  // (the shards' spectra are summed)
-            else if (out) err = writer.write(out, t, nullptr);
+            else if (out.is_open()) err = writer.write(out, t, nullptr);
         }
-        if (out) fclose(out);
         if (err.empty() && histo_max_) err = write_histo();
         if (getenv("KT_CLI_TIMING"))
             fprintf(stderr, "[timing] ctr --devices %d written: VmHWM %llu kB\n", n_devices_, (unsigned long long)peak_rss_kb());
@@ -1365,13 +1376,12 @@ std::string CountComputer::merge(bool /*del: no temp files exist to delete*/) {
         if (std::string e = write_histo(); !e.empty()) return e;
         if (histo_only_) return "";
     }
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + path;
-    TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
-    writer.set_range(min_count_, max_count_);
+    OutFile out;
+    if (std::string e = out.open(path); !e.empty()) return e;
+    TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_, min_count_, max_count_);
     const std::string e = writer.write(out, ctr_, nullptr);
     pt.t[2] += lap();
-    fclose(out);
+    (void)out.close();
     pt.t[3] += lap();
     if (getenv("KT_CLI_TIMING")) fprintf(stderr, "[timing] ctr merge: peak host memory (VmHWM) %llu kB\n", (unsigned long long)peak_rss_kb());
     return e;
@@ -1423,11 +1433,10 @@ std::string CovComputer::compute_coverages() {
     // the reference parses kmers.counts back into a HashMap (:82-92); the table is still in HBM here
     if (ctr_ && ctr_->passes() > 1) {
         // ... unless it took several passes: the rows were summed pass by pass (cov_pass); normalise, format, write
-        const std::string path = out_dir_ + "/kmers.vectors";
-        FILE *out = fopen(path.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + path;
+        OutFile out;
+        if (std::string e = out.open(out_dir_ + "/kmers.vectors"); !e.empty()) return e;
         PhaseTimer pt("cov (rows summed over the passes)");
-        AsyncWriter writer(out, pt);
+        AsyncWriter writer(out.stream(), pt);
         std::vector<std::string> pieces;
         const uint64_t bins = bin_count_, slab = bins >= 2048 ? 8192 : 1ull << 19, acc_reads = kept_.seen.reads;
         Work w;
@@ -1445,8 +1454,6 @@ std::string CovComputer::compute_coverages() {
             }
             emit_matrix(writer, w, bins, norm_, delim_, threads_, pieces, pt);
         }
-        writer.finish();
-        fclose(out);
         return "";
     }
     if (ctr_ && ctr_->n_shards() > 0) {
@@ -1458,11 +1465,10 @@ std::string CovComputer::compute_coverages() {
         const size_t N = ctr_->n_shards();
         SeqReader reader;
         if (!reader.open(in_path_, false)) return reader.error();
-        const std::string path = out_dir_ + "/kmers.vectors";
-        FILE *out = fopen(path.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + path;
+        OutFile out;
+        if (std::string e = out.open(out_dir_ + "/kmers.vectors"); !e.empty()) return e;
         PhaseTimer pt("cov (rows summed over the shards)");
-        AsyncWriter writer(out, pt);
+        AsyncWriter writer(out.stream(), pt);
         std::vector<std::string> pieces;
         const uint64_t bins = bin_count_;
         std::vector<std::vector<uint32_t>> part(N);
@@ -1508,22 +1514,19 @@ std::string CovComputer::compute_coverages() {
             }
             if (!more) break;
         }
-        writer.finish();
-        fclose(out);
         if (err.empty() && reader.failed()) err = reader.error();
         return err;
     }
     if (!ctr_ || !ctr_->table()) return "build_table() has not run";
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    const std::string path = out_dir_ + "/kmers.vectors";
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + path;
+    OutFile out;
+    if (std::string e = out.open(out_dir_ + "/kmers.vectors"); !e.empty()) return e;
     std::vector<std::string> pieces;
     const uint64_t bins = bin_count_;
     PhaseTimer pt("cov");
-    AsyncWriter writer(out, pt);
-    const std::string err = run_pipeline(
+    AsyncWriter writer(out.stream(), pt);
+    return run_pipeline(
         reader, batch_bases(256ull << 20), bins >= 2048 ? 8192 : 1ull << 19, pt,
         [&](Work &w) -> std::string {
             const uint64_t n = w.b.n_reads();
@@ -1535,9 +1538,6 @@ std::string CovComputer::compute_coverages() {
             return "";
         },
         [&](Work &w) { emit_matrix(writer, w, bins, norm_, delim_, threads_, pieces, pt); });  // :112-124
-    writer.finish();
-    fclose(out);
-    return err;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1613,8 +1613,8 @@ std::string FilterComputer::filter() {
     const bool fastq = format_from_path(in_path_) == SeqFormat::Fastq;
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    FILE *out = fopen(out_path_.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path_;
+    OutFile out;
+    if (std::string e = out.open(out_path_); !e.empty()) return e;
     PhaseTimer pt("filter");
     Lap lap;
     Batch batch;
@@ -1640,12 +1640,12 @@ std::string FilterComputer::filter() {
         text.clear();
         emit(b, pn, ps, pw, fastq, text);
         pt.t[2] += lap();
-        if (fwrite(text.data(), 1, text.size(), out) != text.size()) return "Unable to write to file: " + out_path_;
+        if (!out.write(text)) return out.close();
         pt.t[3] += lap();
         return "";
     });
     if (err.empty() && !resident) err = kept_.finish(false, end);
-    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path_;
+    if (std::string e = out.close(); err.empty()) err = e;
     return err;
 }
 
@@ -1695,14 +1695,9 @@ std::string ProfileComputer::profile() {
     if (!ctx) return "profile: no device context";
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    const std::string spath = out_dir_ + "/profile.stats", cpath = out_dir_ + "/profile.counts";
-    FILE *fs = fopen(spath.c_str(), "wb");
-    if (!fs) return "Unable to write to file: " + spath;
-    FILE *fc = positions_ ? fopen(cpath.c_str(), "wb") : nullptr;
-    if (positions_ && !fc) {
-        fclose(fs);
-        return "Unable to write to file: " + cpath;
-    }
+    OutFile fs, fc;  // profile.stats, and with positions_ profile.counts
+    if (std::string e = fs.open(out_dir_ + "/profile.stats"); !e.empty()) return e;
+    if (std::string e = positions_ ? fc.open(out_dir_ + "/profile.counts") : ""; !e.empty()) return e;
     PhaseTimer pt("profile");
     Lap lap;
     Batch batch;
@@ -1732,19 +1727,13 @@ std::string ProfileComputer::profile() {
         pt.t[1] += lap();
         for (uint64_t i = 0; i < n; i++) {
             append_name(text, b.headers[i]);
-            text += '\t';
-            append_uint(text, b.offsets[i + 1] - b.offsets[i]);
-            for (const uint32_t *col : {nk, np, mn, md}) {
-                text += '\t';
-                append_uint(text, col[i]);
-            }
+            append_tab_uints(text, {b.offsets[i + 1] - b.offsets[i], nk[i], np[i], mn[i], md[i]});
             text += '\t';
             append_fixed6(text, (double)sum[i] / (double)(nk[i] ? nk[i] : 1u));
-            text += '\t';
-            append_uint(text, mx[i]);
+            append_tab_uints(text, {mx[i]});
             text += '\n';
         }
-        if (fc)
+        if (fc.is_open())
             format_rows(n, threads_, 512, pieces, [&](uint64_t i, std::string &s) {
                 s += '>';
                 append_name(s, b.headers[i]);
@@ -1757,21 +1746,18 @@ std::string ProfileComputer::profile() {
                 s += '\n';
             });
         pt.t[2] += lap();
-        bool ok = fwrite(text.data(), 1, text.size(), fs) == text.size();
+        const bool ok = fs.write(text) && (!fc.is_open() || fc.write(pieces));
         text.clear();
-        if (fc)
-            for (const std::string &piece : pieces) ok = ok && fwrite(piece.data(), 1, piece.size(), fc) == piece.size();
         if (!ok) return "Unable to write to directory: " + out_dir_;
         pt.t[3] += lap();
         in_batch = false;
         return "";
     });
     // (an input without records - or none before the reader failed: the header line)
-    if (!in_batch && !text.empty() && fwrite(text.data(), 1, text.size(), fs) != text.size() && err.empty())
-        err = "Unable to write to file: " + spath;
+    if (!in_batch && !text.empty() && !fs.write(text) && err.empty()) err = fs.error();
     if (err.empty() && !resident) err = kept_.finish(false, end);
-    if (fclose(fs) != 0 && err.empty()) err = "Unable to write to file: " + spath;
-    if (fc && fclose(fc) != 0 && err.empty()) err = "Unable to write to file: " + cpath;
+    if (std::string e = fs.close(); err.empty()) err = e;
+    if (std::string e = fc.close(); err.empty()) err = e;
     return err;
 }
 
@@ -1839,8 +1825,8 @@ std::string CorrectComputer::correct() {
     const bool fastq = format_from_path(in_path_) == SeqFormat::Fastq;
     SeqReader reader;
     if (!reader.open(in_path_, false)) return reader.error();
-    FILE *out = fopen(out_path_.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path_;
+    OutFile out;
+    if (std::string e = out.open(out_path_); !e.empty()) return e;
     PhaseTimer pt("correct");
     Lap lap;
     Batch batch;
@@ -1880,18 +1866,16 @@ std::string CorrectComputer::correct() {
             append_record(text, fastq, b.headers[i], fixed.data() + o, fastq ? b.quals.data() + o : nullptr, len);
         }
         pt.t[2] += lap();
-        if (fwrite(text.data(), 1, text.size(), out) != text.size()) return "Unable to write to file: " + out_path_;
+        if (!out.write(text)) return out.close();
         pt.t[3] += lap();
         return "";
     });
     if (err.empty() && !resident) err = kept_.finish(false, end);
-    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path_;
+    if (std::string e = out.close(); err.empty()) err = e;
     if (err.empty() && !stats_path_.empty()) {
         static const char *names[6] = {"reads", "bases", "reads_corrected", "bases_corrected", "positions_ambiguous", "reads_over_limit"};
         const uint64_t values[6] = {end.reads, end.bases, reads_corrected, bases_corrected, ambiguous, over_limit};
-        std::string s;
-        append_stats_rows(s, names, values, 6);
-        err = write_text_file(stats_path_, s);
+        err = write_stats_file(stats_path_, names, values, 6);
     }
     return err;
 }
@@ -1909,20 +1893,10 @@ void CompareComputer::release() {
 }
 
 std::string CompareComputer::write(const std::vector<uint64_t> &m, const uint64_t *tot) const {
-    const uint32_t R = max_a_ + 1, C = max_b_ + 1;
-    std::string s;
-    s.reserve((size_t)R * C * 2);
-    char buf[24];
-    for (uint32_t r = 0; r < R; r++)
-        for (uint32_t c = 0; c < C; c++) {
-            const auto e = std::to_chars(buf, buf + sizeof buf, m[(size_t)r * C + c]);
-            s.append(buf, (size_t)(e.ptr - buf));
-            s += c + 1 < C ? '\t' : '\n';
-        }
-    if (std::string e = write_text_file(out_dir_ + "/compare.matrix", s); !e.empty()) return e;
+    if (std::string e = write_text_file(out_dir_ + "/compare.matrix", matrix_text(m, max_a_ + 1, max_b_ + 1)); !e.empty()) return e;
     // distinct_a, distinct_b, shared, occurrences_a, occurrences_b, shared_min; then the ratios (0 over a zero denominator)
     static const char *names[6] = {"distinct_a", "distinct_b", "shared", "occurrences_a", "occurrences_b", "shared_min"};
-    s.clear();
+    std::string s;
     append_stats_rows(s, names, tot, 6);
     auto ratio = [&](const char *name, uint64_t num, uint64_t den) {
         char b[FIXED6_BUF + 64];
@@ -2045,15 +2019,8 @@ std::string SetopComputer::setop() {
     // HBM per slot: the slot (16) + its share of the result and of the sort's second pair - at most every entry of both
     // tables, 12 bytes, twice, with 1.9 slots per entry: 24 / 1.9 < 13
     if (std::string e = two_tables_setup(dev_, in_a_, a_is_table_, in_b_, b_is_table_, ksize_, 16 + 13, "setop", &passes_, &ta_, &tb_); !e.empty()) return e;
-    const std::string cpath = out_dir_ + "/kmers.counts", spath = out_dir_ + "/setop.stats";
-    FILE *out = fopen(cpath.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + cpath;
-    struct Closer {
-        FILE *f;
-        ~Closer() {
-            if (f) fclose(f);
-        }
-    } closer{out};
+    OutFile out;
+    if (std::string e = out.open(out_dir_ + "/kmers.counts"); !e.empty()) return e;
     // distinct_a, distinct_b, in_a, in_b, emitted, emitted_occurrences
     uint64_t tot[6] = {0, 0, 0, 0, 0, 0};
     TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_);
@@ -2096,12 +2063,9 @@ std::string SetopComputer::setop() {
         if (std::string e = writer.write_pairs(out, keys.data(), counts.data(), n); !e.empty()) return e;
         pt.t[3] += lap();
     }
-    closer.f = nullptr;
-    if (fclose(out) != 0) return "Unable to write to file: " + cpath;
+    if (std::string e = out.close(); !e.empty()) return e;
     static const char *names[6] = {"distinct_a", "distinct_b", "in_a", "in_b", "emitted", "emitted_occurrences"};
-    std::string s;
-    append_stats_rows(s, names, tot, 6);
-    return write_text_file(spath, s);
+    return write_stats_file(out_dir_ + "/setop.stats", names, tot, 6);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2119,10 +2083,9 @@ static std::string graph_census_name(int j) {
     return "degree_" + std::to_string((j - 7) / 5) + "_" + std::to_string((j - 7) % 5);
 }
 
-// What `graph` and `unitigs` share: one table, and the whole of it on the device - a plan of several passes is refused
-// before anything is counted or written.  whole_table plans and creates it (`name`: the command, in the texts - its
-// PhaseTimer starts only afterwards, so a refusal prints no phase line), fill_whole_table counts the input into it.  With
-// a table file whole_table loads the file instead (table_from_file) and the caller skips fill_whole_table.
+// What `graph`, `hetmers` and `unitigs` share: one table, and the whole of it on the device - a plan of several passes is
+// refused before anything is counted or written.  whole_table plans and creates it (`name`: the command, in the texts), or
+// with a table file loads the file instead (table_from_file).
 static std::string whole_table(Device &dev, const std::string &path, const std::string &table_file, int k, uint64_t bytes_per_slot,
                                const char *name, kt_ctr **table) {
     if (!table_file.empty()) return table_from_file(dev, table_file, k, bytes_per_slot, name, table);
@@ -2148,27 +2111,38 @@ static std::string whole_table(Device &dev, const std::string &path, const std::
     }
     return "";
 }
-// (the reader and the batch stay the caller's, alive until the command is done, as the table's other users keep theirs)
-static std::string fill_whole_table(kt_ctr *table, SeqReader &reader, Batch &b, PhaseTimer &pt, Lap &lap) {
-    return fill_table(reader, b, pt, lap, [&](const Batch &bb) {
-        return kt_ctr_add_reads(table, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST);
-    });
-}
-
-std::string GraphComputer::graph() {
-    if (table_) kt_ctr_destroy(table_);
-    table_ = nullptr;
-    // HBM per slot: the slot (16) + its share of the result (key, info, count: 16 bytes a node) and of the sort's second
-    // pair (12), with 1.9 slots per entry: 28 / 1.9 < 15
-    if (std::string e = whole_table(dev_, in_path_, table_file_, ksize_, 16 + 15, "graph", &table_); !e.empty()) return e;
-    PhaseTimer pt("graph");
+// How those commands begin: the table of the last run destroyed, the new one made by whole_table and, unless a file was
+// loaded, the input counted into it.  A command constructs one of these first and keeps it until it returns: the reader and
+// the batch are members, alive until the command is done, as the table's other users keep theirs; the phase timer exists
+// only once whole_table has succeeded, so a refusal prints no phase line.
+struct WholeTableRun {
+    std::optional<PhaseTimer> timer;
     SeqReader reader;
     Batch b;
     Lap lap;
-    if (table_file_.empty()) {  // (else whole_table loaded the file: there is nothing to count)
-        if (!reader.open(in_path_, false)) return reader.error();
-        if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
+    std::string err;  // "" or why there is no table
+    void took(int phase) { timer->t[phase] += lap(); }  // the time since the last call, booked to that phase
+    WholeTableRun(Device &dev, const std::string &in_path, const std::string &table_file, int k, uint64_t bytes_per_slot, const char *name,
+                  kt_ctr **table) {
+        if (*table) kt_ctr_destroy(*table);
+        *table = nullptr;
+        err = whole_table(dev, in_path, table_file, k, bytes_per_slot, name, table);
+        if (!err.empty()) return;
+        timer.emplace(name);
+        lap = Lap();
+        if (!table_file.empty()) return;  // (there is nothing to count)
+        if (!reader.open(in_path, false)) err = reader.error();
+        else err = fill_table(reader, b, *timer, lap, [&](const Batch &bb) {
+            return kt_ctr_add_reads(*table, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST);
+        });
     }
+};
+
+std::string GraphComputer::graph() {
+    // HBM per slot: the slot (16) + its share of the result (key, info, count: 16 bytes a node) and of the sort's second
+    // pair (12), with 1.9 slots per entry: 28 / 1.9 < 15
+    WholeTableRun run(dev_, in_path_, table_file_, ksize_, 16 + 15, "graph", &table_);
+    if (!run.err.empty()) return run.err;
     // what can be a node at most sizes the host arrays: one call, no counting call before it
     uint64_t bound = 0, n = 0, census[KT_GRAPH_CENSUS] = {};
     if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
@@ -2177,39 +2151,32 @@ std::string GraphComputer::graph() {
     std::vector<uint32_t> info((size_t)bound), counts((size_t)bound);
     if (kt_ctr_graph(table_, min_count_, max_count_, keys.data(), info.data(), counts.data(), bound, &n, census, KT_MEM_HOST, 1) != KT_OK)
         return kt_last_error();
-    pt.t[1] += lap();
+    run.took(1);
     if (!stats_only_) {
-        const std::string npath = out_dir_ + "/graph.nodes";
-        FILE *out = fopen(npath.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + npath;
+        OutFile out;
+        if (std::string e = out.open(out_dir_ + "/graph.nodes"); !e.empty()) return e;
         // ~64 bytes of text a node, a slab at a time (TableWriter's bound)
         uint64_t slab = (uint64_t)(memory_ceil_gb_ * (double)(1ull << 30) / 16.0 / 64.0);
         slab = std::min<uint64_t>(std::max<uint64_t>(slab, 1ull << 16), 1ull << 20);
         std::vector<std::string> pieces;
-        bool ok = true;
-        for (uint64_t i0 = 0; i0 < n && ok; i0 += slab) {
-            format_rows(std::min(slab, n - i0), threads_, (size_t)ksize_ + 26, pieces, [&](uint64_t r, std::string &s) {
-                const uint64_t i = i0 + r;
-                append_kmer(s, keys[i], ksize_, acgt_);
-                s += '\t';
-                append_uint(s, counts[i]);
-                s += '\t';
-                for (int x = 0; x < 4; x++) s += info[i] >> (4 + x) & 1u ? "ACGT"[x] : '.';
-                s += '\t';
-                for (int x = 0; x < 4; x++) s += info[i] >> x & 1u ? "ACGT"[x] : '.';
-                s += '\t';
-                s += info[i] & 0x200u ? 'L' : '.';
-                s += info[i] & 0x100u ? 'R' : '.';
-                s += '\n';
-            });
-            for (const auto &p : pieces) ok = ok && fwrite(p.data(), 1, p.size(), out) == p.size();
-        }
-        if (fclose(out) != 0 || !ok) return "Unable to write to file: " + npath;
+        write_rows(n, slab, threads_, pieces, RowText(out, (size_t)ksize_ + 26, [&](uint64_t i, std::string &s) {
+            append_kmer(s, keys[i], ksize_, acgt_);
+            append_tab_uints(s, {counts[i]});
+            s += '\t';
+            for (int x = 0; x < 4; x++) s += info[i] >> (4 + x) & 1u ? "ACGT"[x] : '.';
+            s += '\t';
+            for (int x = 0; x < 4; x++) s += info[i] >> x & 1u ? "ACGT"[x] : '.';
+            s += '\t';
+            s += info[i] & 0x200u ? 'L' : '.';
+            s += info[i] & 0x100u ? 'R' : '.';
+            s += '\n';
+        }));
+        if (std::string e = out.close(); !e.empty()) return e;
     }
     std::string s;
     for (int j = 0; j < KT_GRAPH_CENSUS; j++) s += graph_census_name(j) + '\t' + std::to_string(census[j]) + '\n';
     if (std::string e = write_text_file(out_dir_ + "/graph.stats", s); !e.empty()) return e;
-    pt.t[3] += lap();
+    run.took(3);
     return "";
 }
 
@@ -2222,19 +2189,10 @@ HetmerComputer::~HetmerComputer() {
 }
 
 std::string HetmerComputer::hetmers() {
-    if (table_) kt_ctr_destroy(table_);
-    table_ = nullptr;
     // HBM per slot: the slot (16) + its share of the nodes and candidates (24 bytes an entry), and of the result and the sort
     // (at most one pair per two entries: 24 + 12 + 12 bytes a pair), with 1.9 slots per entry: 48 / 1.9 < 26
-    if (std::string e = whole_table(dev_, in_path_, table_file_, ksize_, 16 + 26, "hetmers", &table_); !e.empty()) return e;
-    PhaseTimer pt("hetmers");
-    SeqReader reader;
-    Batch b;
-    Lap lap;
-    if (table_file_.empty()) {  // (else whole_table loaded the file: there is nothing to count)
-        if (!reader.open(in_path_, false)) return reader.error();
-        if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
-    }
+    WholeTableRun run(dev_, in_path_, table_file_, ksize_, 16 + 26, "hetmers", &table_);
+    if (!run.err.empty()) return run.err;
     // every k-mer is in at most one pair: half the entries size the host arrays, one call, no counting call before it
     uint64_t bound = 0, n = 0, census[KT_HET_CENSUS] = {};
     if (kt_ctr_size(table_, &bound) != KT_OK) return kt_last_error();
@@ -2245,16 +2203,11 @@ std::string HetmerComputer::hetmers() {
     if (kt_ctr_hetmers(table_, min_count_, max_count_, middle_ ? KT_HET_MIDDLE : KT_HET_ALL, ka.data(), kb.data(), ca.data(), cb.data(),
                        bound, &n, m.data(), R, C, census, KT_MEM_HOST, 1) != KT_OK)
         return kt_last_error();
-    pt.t[1] += lap();
+    run.took(1);
     if (!stats_only_) {
-        const std::string ppath = out_dir_ + "/hetmers.pairs", cpath = out_dir_ + "/hetmers.cov";
-        FILE *outp = fopen(ppath.c_str(), "wb");
-        if (!outp) return "Unable to write to file: " + ppath;
-        FILE *outc = fopen(cpath.c_str(), "wb");
-        if (!outc) {
-            fclose(outp);
-            return "Unable to write to file: " + cpath;
-        }
+        OutFile outp, outc;
+        if (std::string e = outp.open(out_dir_ + "/hetmers.pairs"); !e.empty()) return e;
+        if (std::string e = outc.open(out_dir_ + "/hetmers.cov"); !e.empty()) return e;
         // B as written: the strand of b that differs from A at one allowed position, and that position.  Where both strands
         // do (double reach) it is b's forward strand, the lower position first.
         const uint32_t p_lo = middle_ ? (uint32_t)(ksize_ - 1) / 2u : 0u, p_hi = middle_ ? p_lo + 1u : (uint32_t)ksize_;
@@ -2268,57 +2221,35 @@ std::string HetmerComputer::hetmers() {
         };
         constexpr uint64_t slab = 1ull << 18;
         std::vector<std::string> pieces;
-        bool okp = true, okc = true;
-        for (uint64_t i0 = 0; i0 < n && okp && okc; i0 += slab) {
-            format_rows(std::min(slab, n - i0), threads_, 2 * (size_t)ksize_ + 30, pieces, [&](uint64_t r, std::string &s) {
-                const uint64_t i = i0 + r;
-                uint64_t bw = kb[i];
-                uint32_t pos = 0;
-                if (!one_sub(ka[i] ^ bw, &pos)) {
-                    bw = kt_rev_comp(kb[i], ksize_);
-                    (void)one_sub(ka[i] ^ bw, &pos);
-                }
-                append_kmer(s, ka[i], ksize_, true);
-                s += '\t';
-                append_kmer(s, bw, ksize_, true);
-                s += '\t';
-                append_uint(s, pos);
-                s += '\t';
-                append_uint(s, ca[i]);
-                s += '\t';
-                append_uint(s, cb[i]);
-                s += '\n';
-            });
-            for (const auto &p : pieces) okp = okp && fwrite(p.data(), 1, p.size(), outp) == p.size();
-            format_rows(std::min(slab, n - i0), threads_, 24, pieces, [&](uint64_t r, std::string &s) {
-                const uint64_t i = i0 + r;
-                append_uint(s, std::min(ca[i], cb[i]));
-                s += '\t';
-                append_uint(s, std::max(ca[i], cb[i]));
-                s += '\n';
-            });
-            for (const auto &p : pieces) okc = okc && fwrite(p.data(), 1, p.size(), outc) == p.size();
-        }
-        if (fclose(outp) != 0 || !okp) {
-            fclose(outc);
-            return "Unable to write to file: " + ppath;
-        }
-        if (fclose(outc) != 0 || !okc) return "Unable to write to file: " + cpath;
+        write_rows(n, slab, threads_, pieces,
+                   RowText(outp, 2 * (size_t)ksize_ + 30, [&](uint64_t i, std::string &s) {
+                       uint64_t bw = kb[i];
+                       uint32_t pos = 0;
+                       if (!one_sub(ka[i] ^ bw, &pos)) {
+                           bw = kt_rev_comp(kb[i], ksize_);
+                           (void)one_sub(ka[i] ^ bw, &pos);
+                       }
+                       append_kmer(s, ka[i], ksize_, true);
+                       s += '\t';
+                       append_kmer(s, bw, ksize_, true);
+                       append_tab_uints(s, {pos, ca[i], cb[i]});
+                       s += '\n';
+                   }),
+                   RowText(outc, 24, [&](uint64_t i, std::string &s) {
+                       append_uint(s, std::min(ca[i], cb[i]));
+                       append_tab_uints(s, {std::max(ca[i], cb[i])});
+                       s += '\n';
+                   }));
+        const std::string ep = outp.close(), ec = outc.close();
+        if (!ep.empty() || !ec.empty()) return ep.empty() ? ec : ep;
     }
-    std::string s;
-    s.reserve((size_t)R * C * 2);
-    for (uint32_t r = 0; r < R; r++)
-        for (uint32_t c = 0; c < C; c++) {
-            append_uint(s, m[(size_t)r * C + c]);
-            s += c + 1 < C ? '\t' : '\n';
-        }
-    if (std::string e = write_text_file(out_dir_ + "/hetmers.matrix", s); !e.empty()) return e;
+    if (std::string e = write_text_file(out_dir_ + "/hetmers.matrix", matrix_text(m, R, C)); !e.empty()) return e;
     static const char *names[KT_HET_CENSUS] = {"nodes", "occurrences", "degree_0", "degree_1", "degree_2_or_more", "pairs", "minor_sum", "major_sum"};
-    s = "k\t" + std::to_string(ksize_) + "\nmin_count\t" + std::to_string(min_count_) + "\nmax_count\t" + std::to_string(max_count_) +
+    std::string s = "k\t" + std::to_string(ksize_) + "\nmin_count\t" + std::to_string(min_count_) + "\nmax_count\t" + std::to_string(max_count_) +
         "\npositions\t" + (middle_ ? "middle" : "all") + "\n";
     for (int j = 0; j < KT_HET_CENSUS; j++) s += std::string(names[j]) + '\t' + std::to_string(census[j]) + '\n';
     if (std::string e = write_text_file(out_dir_ + "/hetmers.stats", s); !e.empty()) return e;
-    pt.t[3] += lap();
+    run.took(3);
     return "";
 }
 
@@ -2330,381 +2261,412 @@ UnitigComputer::~UnitigComputer() {
     if (table_) kt_ctr_destroy(table_);
 }
 
+// What the device calls of a run returned: the unitigs (kt_ctr_unitigs), with `linked` the links of every unitig end as
+// well (kt_ctr_unitigs_linked), with components the component of every unitig and a row per component.
+struct UnitigGraph {
+    uint64_t nu = 0, nb = 0, nl = 0, nc = 0;  // unitigs, their bases, directed links, components
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> offsets, sums;  // per unitig: where its bases begin (nu + 1 values), its count sum
+    std::vector<uint64_t> loff, cstats;   // 2 nu + 1 offsets into lto, by unitig end; nc rows of KT_COMPONENT_FIELDS
+    std::vector<uint32_t> flags, lto, comp;
+    uint64_t ctally[KT_COMPONENT_TALLY] = {};
+    uint64_t len(uint64_t i) const { return offsets[i + 1] - offsets[i]; }
+};
+
+// which files a run of unitigs() writes (the class comment in computers.hpp says when; `thread` has files of its own)
+struct UnitigFiles { bool fa, gfa, links_stats, components, components_stats, unitigs_stats; };
+
+// Of a link e -> f and its mirror (f ^ 1) -> (e ^ 1), the GFA and the edge count take the one that is not the larger as
+// (u, su is '-', v, sv is '-'), which is the order of (e, f) as pairs of numbers; a link that is its own mirror is there once.
+static bool not_larger_than_mirror(uint64_t e, uint64_t f) {
+    const uint64_t me = f ^ 1, mf = e ^ 1;
+    return e < me || (e == me && f <= mf);
+}
+
+// The tags of unitig i, `sep` in front of each: LN, KC, km, CL on a cycle, with fa_links (the FASTA header) an L per
+// directed link, CC with `tagged`.
+static void append_unitig_tags(std::string &s, const UnitigGraph &g, uint64_t i, uint64_t overlap, char sep, bool fa_links, bool tagged) {
+    const uint64_t len = g.len(i);
+    char buf[160];
+    const int h = snprintf(buf, sizeof buf, "%cLN:i:%llu%cKC:i:%llu%ckm:f:%.1f", sep, (unsigned long long)len, sep,
+                           (unsigned long long)g.sums[i], sep, (double)g.sums[i] / (double)(len - overlap));
+    s.append(buf, (size_t)h);
+    if (g.flags[i] & KT_UNITIG_CIRCULAR) (s += sep) += "CL:i:1";
+    if (fa_links)
+        for (uint64_t e = 2 * i; e < 2 * i + 2; e++)
+            for (uint64_t j = g.loff[e]; j < g.loff[e + 1]; j++) {
+                const int l = snprintf(buf, sizeof buf, "%cL:%c:%u:%c", sep, e & 1 ? '-' : '+', g.lto[j] >> 1, g.lto[j] & 1 ? '-' : '+');
+                s.append(buf, (size_t)l);
+            }
+    if (tagged) ((s += sep) += "CC:i:") += std::to_string(g.comp[i]);
+}
+
+static std::string write_fa(const std::string &path, const UnitigGraph &g, uint64_t overlap, bool fa_links, bool tagged) {
+    OutFile out;
+    if (std::string e = out.open(path); !e.empty()) return e;
+    for (uint64_t i = 0; i < g.nu && !out.failed(); i++) {
+        std::string &s = out.text();
+        s += '>';
+        append_uint(s, i);
+        append_unitig_tags(s, g, i, overlap, ' ', fa_links, tagged);
+        s += '\n';
+        s.append((const char *)g.bases.data() + g.offsets[i], (size_t)g.len(i));
+        s += '\n';
+    }
+    return out.close();
+}
+
+static std::string write_gfa(const std::string &path, const UnitigGraph &g, uint64_t overlap, bool tagged) {
+    OutFile out;
+    if (std::string e = out.open(path); !e.empty()) return e;
+    out.text() = "H\tVN:Z:1.0\n";
+    for (uint64_t i = 0; i < g.nu; i++) {
+        std::string &s = out.text();
+        s += "S\t";
+        append_uint(s, i);
+        s += '\t';
+        s.append((const char *)g.bases.data() + g.offsets[i], (size_t)g.len(i));
+        append_unitig_tags(s, g, i, overlap, '\t', false, tagged);
+        s += '\n';
+    }
+    for (uint64_t e = 0; e < 2 * g.nu; e++)
+        for (uint64_t j = g.loff[e]; j < g.loff[e + 1]; j++) {
+            const uint64_t f = g.lto[j];
+            if (!not_larger_than_mirror(e, f)) continue;
+            char line[160];
+            const int h = snprintf(line, sizeof line, "L\t%llu\t%c\t%llu\t%c\t%lluM\n", (unsigned long long)(e >> 1), e & 1 ? '-' : '+',
+                                   (unsigned long long)(f >> 1), f & 1 ? '-' : '+', (unsigned long long)overlap);
+            out.text().append(line, (size_t)h);
+        }
+    return out.close();
+}
+
+static std::string write_links_stats(const std::string &path, const UnitigGraph &g) {
+    uint64_t edges = 0, dead = 0, isolated = 0, self = 0, max_deg = 0;
+    for (uint64_t e = 0; e < 2 * g.nu; e++) {
+        const uint64_t d = g.loff[e + 1] - g.loff[e];
+        dead += d == 0;
+        isolated += (e & 1) && d == 0 && g.loff[e] == g.loff[e - 1];
+        max_deg = std::max(max_deg, d);
+        for (uint64_t j = g.loff[e]; j < g.loff[e + 1]; j++) {
+            self += (g.lto[j] >> 1) == (e >> 1);
+            edges += not_larger_than_mirror(e, g.lto[j]);
+        }
+    }
+    static const char *names[6] = {"links", "edges", "dead_ends", "isolated", "self_links", "max_end_degree"};
+    const uint64_t values[6] = {g.nl, edges, dead, isolated, self, max_deg};
+    return write_stats_file(path, names, values, 6);
+}
+
+// unitigs.components: component, unitigs, nodes, bases, count_sum, km, links, first_unitig
+static std::string write_components(const std::string &path, const UnitigGraph &g, uint64_t overlap) {
+    std::string s;
+    char line[200];
+    for (uint64_t c = 0; c < g.nc; c++) {
+        const uint64_t *r = &g.cstats[(size_t)c * KT_COMPONENT_FIELDS];
+        const int h = snprintf(line, sizeof line, "%llu\t%llu\t%llu\t%llu\t%llu\t%.1f\t%llu\t%llu\n", (unsigned long long)c,
+                               (unsigned long long)r[0], (unsigned long long)r[1], (unsigned long long)(r[1] + overlap * r[0]),
+                               (unsigned long long)r[2], (double)r[2] / (double)r[1], (unsigned long long)r[3], (unsigned long long)r[4]);
+        s.append(line, (size_t)h);
+    }
+    return write_text_file(path, s);
+}
+
+static std::string write_components_stats(const std::string &path, const UnitigGraph &g, uint64_t overlap) {
+    static const char *names[4] = {"components", "singletons", "largest_unitigs", "largest_nodes"};
+    const uint64_t nodes = g.nb - g.nu * overlap;
+    std::string s;
+    append_stats_rows(s, names, g.ctally, 4);
+    char line[64];
+    const int h = snprintf(line, sizeof line, "largest_share\t%.4f\n", nodes ? (double)g.ctally[3] / (double)nodes : 0.0);
+    s.append(line, (size_t)h);
+    return write_text_file(path, s);
+}
+
+static std::string write_unitig_stats(const std::string &path, const UnitigGraph &g, uint64_t overlap) {
+    // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
+    std::vector<uint64_t> lens((size_t)g.nu);
+    uint64_t occ = 0, circular = 0, singletons = 0, longest = 0, n50 = 0;
+    for (uint64_t i = 0; i < g.nu; i++) {
+        lens[i] = g.len(i);
+        occ += g.sums[i];
+        circular += g.flags[i] & KT_UNITIG_CIRCULAR ? 1 : 0;
+        singletons += lens[i] == overlap + 1;
+        longest = std::max(longest, lens[i]);
+    }
+    std::sort(lens.begin(), lens.end(), std::greater<uint64_t>());
+    for (uint64_t i = 0, run = 0; i < g.nu; i++) {
+        run += lens[i];
+        if (2 * run >= g.nb) {
+            n50 = lens[i];
+            break;
+        }
+    }
+    static const char *names[8] = {"unitigs", "bases", "nodes", "occurrences", "circular", "singletons", "longest", "n50"};
+    const uint64_t values[8] = {g.nu, g.nb, g.nb - g.nu * overlap, occ, circular, singletons, longest, n50};
+    return write_stats_file(path, names, values, 8);
+}
+
+// set_bubbles / set_clip: the table is simplified or clipped in place (every file describes that graph), its stats written
+std::string UnitigComputer::simplify_table() {
+    const uint32_t isolated = drop_isolated_ ? KT_CLIP_ISOLATED : 0u;
+    if (pop_) {  // tips (with clip_) and bubbles in the same rounds
+        uint64_t st[KT_SIMPLIFY_STATS] = {};
+        if (kt_ctr_simplify(table_, min_count_, max_count_, clip_ ? tip_nodes_ : 0u, bubble_nodes_, clip_rounds_, isolated, st) != KT_OK)
+            return kt_last_error();
+        static const char *names[10] = {"rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "popped", "popped_nodes", "bubbles",
+                                        "occurrences", "converged"};
+        const uint64_t values[10] = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9] ? 0ull : 1ull};
+        return write_stats_file(out_dir_ + "/unitigs.simplify.stats", names, values, 10);
+    }
+    if (clip_) {
+        uint64_t st[KT_CLIP_STATS] = {};
+        if (kt_ctr_clip_tips(table_, min_count_, max_count_, tip_nodes_, clip_rounds_, isolated, st) != KT_OK) return kt_last_error();
+        static const char *names[7] = {"rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "occurrences", "converged"};
+        const uint64_t values[7] = {st[0], st[1], st[2], st[3], st[4], st[5], st[6] ? 0ull : 1ull};
+        return write_stats_file(out_dir_ + "/unitigs.clip.stats", names, values, 7);
+    }
+    return "";
+}
+
+// g: a count-only call, then one sized by it (the links only where a file asks for them); with components_ the components
+std::string UnitigComputer::fetch_unitigs(bool linked, UnitigGraph &g) {
+    auto call = [&](bool sized) {
+        const uint64_t cap_b = sized ? g.nb : 0, cap_u = sized ? g.nu : 0, cap_l = sized ? g.nl : 0;
+        uint8_t *bases = sized ? g.bases.data() : nullptr;
+        uint64_t *offsets = sized ? g.offsets.data() : nullptr, *sums = sized ? g.sums.data() : nullptr;
+        uint32_t *flags = sized ? g.flags.data() : nullptr;
+        return linked ? kt_ctr_unitigs_linked(table_, min_count_, max_count_, bases, cap_b, offsets, sums, flags, cap_u, &g.nu, &g.nb,
+                                              sized ? g.loff.data() : nullptr, sized ? g.lto.data() : nullptr, cap_l, &g.nl, KT_MEM_HOST)
+                      : kt_ctr_unitigs(table_, min_count_, max_count_, bases, cap_b, offsets, sums, flags, cap_u, &g.nu, &g.nb, KT_MEM_HOST);
+    };
+    if (call(false) != KT_OK) return kt_last_error();
+    g.bases.resize((size_t)g.nb);
+    g.offsets.resize((size_t)g.nu + 1);
+    g.sums.resize((size_t)g.nu);
+    g.flags.resize((size_t)g.nu);
+    g.loff.resize(linked ? 2 * (size_t)g.nu + 1 : 0);
+    g.lto.resize((size_t)g.nl);
+    if (g.nu && call(true) != KT_OK) return kt_last_error();
+    if (components_) {
+        static const uint32_t no_link[1] = {0};
+        g.comp.resize((size_t)g.nu);
+        g.cstats.resize((size_t)g.nu * KT_COMPONENT_FIELDS);
+        if (kt_unitig_components(dev_.ctx, g.loff.data(), g.nl ? g.lto.data() : no_link, g.nu, g.offsets.data(), g.sums.data(), ksize_,
+                                 g.comp.data(), g.cstats.data(), g.nu, &g.nc, g.ctally, KT_MEM_HOST) != KT_OK)
+            return kt_last_error();
+        g.cstats.resize((size_t)g.nc * KT_COMPONENT_FIELDS);
+    }
+    return "";
+}
+
 std::string UnitigComputer::unitigs() {
-    if (table_) kt_ctr_destroy(table_);
-    table_ = nullptr;
+    const bool linked = gfa_ || fa_links_ || components_;
+    const UnitigFiles files = {!stats_only_, gfa_, linked && !thread_, components_ && !(thread_ && stats_only_), components_ && !thread_, !thread_};
+    const bool tagged = components_ && !stats_only_;  // the CC:i: fields of unitigs.fa and unitigs.gfa
     // HBM per slot: the slot (16) + its share of what kt_ctr_unitigs keeps when every entry is a node (16 + 64 bytes, 48 more
     // on cycles, the sort's second pair 12), with 1.9 slots per entry: 140 / 1.9 < 74
     // Clipping (kt_ctr_clip_tips) adds, per entry when every entry is a single-node unitig: its offset, count sum, flags and
     // two link offsets in place of bases the run does not write (36), its class and mark (2) - the list of keys to erase (8 a
     // node) lies where the sort's keys lay, the erase's surviving pairs (12) where the nodes lay - and per slot one bit of the
     // erase's mask: 38 / 1.9 + 1 / 8 < 21.  Popping bubbles (kt_ctr_simplify) claims no more than that.
-    if (std::string e = whole_table(dev_, in_path_, table_file_, ksize_, clip_ || pop_ ? 16 + 74 + 21 : 16 + 74, "unitigs", &table_); !e.empty()) return e;
-    PhaseTimer pt("unitigs");
-    SeqReader reader;
-    Batch b;
-    Lap lap;
-    if (table_file_.empty()) {  // (else whole_table loaded the file: there is nothing to count)
-        if (!reader.open(in_path_, false)) return reader.error();
-        if (std::string e = fill_whole_table(table_, reader, b, pt, lap); !e.empty()) return e;
-    }
-    if (pop_) {  // the table is simplified in place, tips (with clip_) and bubbles in the same rounds
-        uint64_t st[KT_SIMPLIFY_STATS] = {};
-        if (kt_ctr_simplify(table_, min_count_, max_count_, clip_ ? tip_nodes_ : 0u, bubble_nodes_, clip_rounds_,
-                            drop_isolated_ ? KT_CLIP_ISOLATED : 0u, st) != KT_OK)
-            return kt_last_error();
-        static const char *names[10] = {"rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "popped", "popped_nodes", "bubbles",
-                                        "occurrences", "converged"};
-        const uint64_t values[10] = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9] ? 0ull : 1ull};
-        std::string s;
-        append_stats_rows(s, names, values, 10);
-        if (std::string e = write_text_file(out_dir_ + "/unitigs.simplify.stats", s); !e.empty()) return e;
-    } else if (clip_) {  // the table is clipped in place: everything below describes the clipped graph
-        uint64_t st[KT_CLIP_STATS] = {};
-        if (kt_ctr_clip_tips(table_, min_count_, max_count_, tip_nodes_, clip_rounds_, drop_isolated_ ? KT_CLIP_ISOLATED : 0u, st) != KT_OK)
-            return kt_last_error();
-        static const char *names[7] = {"rounds", "tips", "tip_nodes", "isolated", "isolated_nodes", "occurrences", "converged"};
-        const uint64_t values[7] = {st[0], st[1], st[2], st[3], st[4], st[5], st[6] ? 0ull : 1ull};
-        std::string s;
-        append_stats_rows(s, names, values, 7);
-        if (std::string e = write_text_file(out_dir_ + "/unitigs.clip.stats", s); !e.empty()) return e;
-    }
-    // a count-only call, then one call sized by it; with the links only where a file asks for them
-    const bool linked = gfa_ || fa_links_ || components_;
-    uint64_t nu = 0, nb = 0, nl = 0;
-    if ((linked ? kt_ctr_unitigs_linked(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, nullptr,
-                                        nullptr, 0, &nl, KT_MEM_HOST)
-                : kt_ctr_unitigs(table_, min_count_, max_count_, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, KT_MEM_HOST)) != KT_OK)
-        return kt_last_error();
-    std::vector<uint8_t> bases((size_t)nb);
-    std::vector<uint64_t> offsets((size_t)nu + 1), sums((size_t)nu), loff(linked ? 2 * (size_t)nu + 1 : 0);
-    std::vector<uint32_t> flags((size_t)nu), lto((size_t)nl);
-    if (nu && (linked ? kt_ctr_unitigs_linked(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(),
-                                              nu, &nu, &nb, loff.data(), lto.data(), nl, &nl, KT_MEM_HOST)
-                      : kt_ctr_unitigs(table_, min_count_, max_count_, bases.data(), nb, offsets.data(), sums.data(), flags.data(), nu,
-                                       &nu, &nb, KT_MEM_HOST)) != KT_OK)
-        return kt_last_error();
-    // the components of that graph: a number per unitig, a row per component
-    std::vector<uint32_t> comp(components_ ? (size_t)nu : 0);
-    std::vector<uint64_t> cstats(components_ ? (size_t)nu * KT_COMPONENT_FIELDS : 0);
-    uint64_t nc = 0, ctally[KT_COMPONENT_TALLY] = {};
-    if (components_) {
-        static const uint32_t no_link[1] = {0};
-        if (kt_unitig_components(dev_.ctx, loff.data(), nl ? lto.data() : no_link, nu, offsets.data(), sums.data(), ksize_, comp.data(),
-                                 cstats.data(), nu, &nc, ctally, KT_MEM_HOST) != KT_OK)
-            return kt_last_error();
-        cstats.resize((size_t)nc * KT_COMPONENT_FIELDS);
-    }
-    const bool tagged = components_ && !stats_only_;  // the CC:i: fields of unitigs.fa and unitigs.gfa
-    pt.t[1] += lap();
+    WholeTableRun run(dev_, in_path_, table_file_, ksize_, clip_ || pop_ ? 16 + 74 + 21 : 16 + 74, "unitigs", &table_);
+    if (!run.err.empty()) return run.err;
+    if (std::string e = simplify_table(); !e.empty()) return e;
+    UnitigGraph g;
+    if (std::string e = fetch_unitigs(linked, g); !e.empty()) return e;
+    run.took(1);
     const uint64_t overlap = (uint64_t)ksize_ - 1;
-    if (!stats_only_) {
-        const std::string fpath = out_dir_ + "/unitigs.fa";
-        FILE *out = fopen(fpath.c_str(), "wb");
-        if (!out) return "Unable to write to file: " + fpath;
-        std::string s;
-        bool ok = true;
-        for (uint64_t i = 0; i < nu && ok; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            char head[160];
-            const int h = snprintf(head, sizeof head, ">%llu LN:i:%llu KC:i:%llu km:f:%.1f%s", (unsigned long long)i,
-                                   (unsigned long long)len, (unsigned long long)sums[i], (double)sums[i] / (double)(len - overlap),
-                                   flags[i] & KT_UNITIG_CIRCULAR ? " CL:i:1" : "");
-            s.append(head, (size_t)h);
-            if (fa_links_)
-                for (uint64_t e = 2 * i; e < 2 * i + 2; e++)
-                    for (uint64_t j = loff[e]; j < loff[e + 1]; j++) {
-                        const int l = snprintf(head, sizeof head, " L:%c:%u:%c", e & 1 ? '-' : '+', lto[j] >> 1, lto[j] & 1 ? '-' : '+');
-                        s.append(head, (size_t)l);
-                    }
-            if (tagged) s += " CC:i:" + std::to_string(comp[i]);
-            s += '\n';
-            s.append((const char *)bases.data() + offsets[i], (size_t)len);
-            s += '\n';
-            if (s.size() >= (1u << 22) || i + 1 == nu) {
-                ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-                s.clear();
-            }
+    std::string e;
+    if (files.fa) e = write_fa(out_dir_ + "/unitigs.fa", g, overlap, fa_links_, tagged);
+    if (e.empty() && files.gfa) e = write_gfa(out_dir_ + "/unitigs.gfa", g, overlap, tagged);
+    if (e.empty() && files.links_stats) e = write_links_stats(out_dir_ + "/unitigs.links.stats", g);
+    if (e.empty() && files.components) e = write_components(out_dir_ + "/unitigs.components", g, overlap);
+    if (e.empty() && files.components_stats) e = write_components_stats(out_dir_ + "/unitigs.components.stats", g, overlap);
+    if (e.empty() && files.unitigs_stats) e = write_unitig_stats(out_dir_ + "/unitigs.stats", g, overlap);
+    if (!e.empty()) return e;
+    run.took(3);
+    return thread_ ? thread_onto(g) : "";  // (`thread` writes its own statistics)
+}
+
+// a batch's runs (kt_thread_runs): start in the batch's bases, k-mers, oriented unitig, place in it; roff: a read's runs
+struct ReadRuns {
+    std::vector<uint64_t> rs, roff;
+    std::vector<uint32_t> rl, ru, rp;
+};
+
+// what `thread` adds up over the batches
+struct ThreadTotals {
+    uint64_t reads = 0, bases = 0, windows = 0, hits = 0, misses = 0, runs = 0, chains = 0, with_hit = 0, whole = 0;
+    uint64_t with_comp = 0, mixed = 0;                                      // --components
+    std::vector<uint64_t> unitig_hits, unitig_runs, comp_reads, comp_hits;  // per unitig, per component
+};
+
+// The runs [r0, r1) of a read that begins at base `o` of its batch, cut into chains: a chain goes on while each further run
+// starts where the one before stopped, at the first k-mer of its oriented unitig, the one before having ended at the last of
+// its own.  fn(r, e, qs, qe, ps, plen) per chain: its runs [r, e), its bases [qs, qe) of the read, its start in and the length of its path.
+template <class F>
+static void for_each_chain(const ReadRuns &R, const UnitigGraph &g, uint64_t k, uint64_t o, uint64_t r0, uint64_t r1, F fn) {
+    auto ulen = [&](uint32_t e) { return g.len(e >> 1); };
+    for (uint64_t r = r0; r < r1;) {
+        uint64_t e = r + 1, plen = ulen(R.ru[r]);
+        for (; e < r1; e++) {
+            const uint64_t L = ulen(R.ru[e]), L0 = ulen(R.ru[e - 1]);
+            const bool starts = R.rp[e] == (R.ru[e] & 1u ? L - k : 0);
+            const bool ended = R.ru[e - 1] & 1u ? R.rp[e - 1] + 1 == R.rl[e - 1] : R.rp[e - 1] + R.rl[e - 1] - 1 == L0 - k;
+            if (R.rs[e] != R.rs[e - 1] + R.rl[e - 1] || !starts || !ended) break;
+            plen += L - (k - 1);
         }
-        if (fclose(out) != 0 || !ok) return "Unable to write to file: " + fpath;
+        const uint64_t qs = R.rs[r] - o, qe = R.rs[e - 1] - o + R.rl[e - 1] - 1 + k;
+        const uint64_t ps = R.ru[r] & 1u ? ulen(R.ru[r]) - k - R.rp[r] : R.rp[r];
+        fn(r, e, qs, qe, ps, plen);
+        r = e;
     }
-    if (linked) {
-        // of a link e -> f and its mirror (f ^ 1) -> (e ^ 1), the GFA takes the one that is not the larger as (u, su is '-',
-        // v, sv is '-'), which is the order of (e, f) as pairs of numbers; a link that is its own mirror is there once
-        uint64_t edges = 0, dead = 0, isolated = 0, self = 0, max_deg = 0;
-        for (uint64_t e = 0; e < 2 * nu; e++) {
-            const uint64_t d = loff[e + 1] - loff[e];
-            dead += d == 0;
-            isolated += (e & 1) && d == 0 && loff[e] == loff[e - 1];
-            max_deg = std::max(max_deg, d);
-            for (uint64_t j = loff[e]; j < loff[e + 1]; j++) {
-                const uint64_t f = lto[j], me = f ^ 1, mf = e ^ 1;
-                self += (f >> 1) == (e >> 1);
-                edges += e < me || (e == me && f <= mf);
-            }
-        }
-        if (gfa_) {
-            const std::string gpath = out_dir_ + "/unitigs.gfa";
-            FILE *out = fopen(gpath.c_str(), "wb");
-            if (!out) return "Unable to write to file: " + gpath;
-            std::string s = "H\tVN:Z:1.0\n";
-            char line[160];
-            bool ok = true;
-            auto flush = [&](bool last) {
-                if (ok && (last || s.size() >= (1u << 22))) {
-                    ok = fwrite(s.data(), 1, s.size(), out) == s.size();
-                    s.clear();
-                }
-            };
-            for (uint64_t i = 0; i < nu; i++) {
-                const uint64_t len = offsets[i + 1] - offsets[i];
-                s += "S\t" + std::to_string(i) + '\t';
-                s.append((const char *)bases.data() + offsets[i], (size_t)len);
-                const int h = snprintf(line, sizeof line, "\tLN:i:%llu\tKC:i:%llu\tkm:f:%.1f%s", (unsigned long long)len,
-                                       (unsigned long long)sums[i], (double)sums[i] / (double)(len - overlap),
-                                       flags[i] & KT_UNITIG_CIRCULAR ? "\tCL:i:1" : "");
-                s.append(line, (size_t)h);
-                if (tagged) s += "\tCC:i:" + std::to_string(comp[i]);
-                s += '\n';
-                flush(false);
-            }
-            for (uint64_t e = 0; e < 2 * nu; e++)
-                for (uint64_t j = loff[e]; j < loff[e + 1]; j++) {
-                    const uint64_t f = lto[j], me = f ^ 1, mf = e ^ 1;
-                    if (!(e < me || (e == me && f <= mf))) continue;
-                    const int h = snprintf(line, sizeof line, "L\t%llu\t%c\t%llu\t%c\t%lluM\n", (unsigned long long)(e >> 1),
-                                           e & 1 ? '-' : '+', (unsigned long long)(f >> 1), f & 1 ? '-' : '+', (unsigned long long)overlap);
-                    s.append(line, (size_t)h);
-                    flush(false);
-                }
-            flush(true);
-            if (fclose(out) != 0 || !ok) return "Unable to write to file: " + gpath;
-        }
-        static const char *names[6] = {"links", "edges", "dead_ends", "isolated", "self_links", "max_end_degree"};
-        const uint64_t values[6] = {nl, edges, dead, isolated, self, max_deg};
-        std::string s;
-        append_stats_rows(s, names, values, 6);
-        if (!thread_)
-            if (std::string e = write_text_file(out_dir_ + "/unitigs.links.stats", s); !e.empty()) return e;
+}
+
+// thread.gaf: the line of one chain of a read of `len` bases
+static void append_gaf_line(std::string &text, const std::string &header, uint64_t len, const ReadRuns &R, uint64_t r, uint64_t e,
+                            uint64_t qs, uint64_t qe, uint64_t ps, uint64_t plen) {
+    append_name(text, header);
+    append_tab_uints(text, {len, qs, qe});
+    text += "\t+\t";
+    for (uint64_t x = r; x < e; x++) {
+        text += R.ru[x] & 1u ? '<' : '>';
+        append_uint(text, R.ru[x] >> 1);
     }
-    if (components_ && !(thread_ && stats_only_)) {
-        std::string s;
-        char line[200];
-        for (uint64_t c = 0; c < nc; c++) {
-            const uint64_t *r = &cstats[(size_t)c * KT_COMPONENT_FIELDS];
-            const int h = snprintf(line, sizeof line, "%llu\t%llu\t%llu\t%llu\t%llu\t%.1f\t%llu\t%llu\n", (unsigned long long)c,
-                                   (unsigned long long)r[0], (unsigned long long)r[1], (unsigned long long)(r[1] + overlap * r[0]),
-                                   (unsigned long long)r[2], (double)r[2] / (double)r[1], (unsigned long long)r[3], (unsigned long long)r[4]);
-            s.append(line, (size_t)h);
-        }
-        if (std::string e = write_text_file(out_dir_ + "/unitigs.components", s); !e.empty()) return e;
+    append_tab_uints(text, {plen, ps, ps + qe - qs, qe - qs, qe - qs, 255});
+    text += '\n';
+}
+
+// thread.reads: the lines of a batch - name, component or *, mixed, hits
+static void append_thread_reads(std::string &text, const Batch &b, const ReadRuns &R, const std::vector<uint32_t> &rcomp,
+                                const std::vector<uint8_t> &rmixed) {
+    for (uint64_t i = 0; i < b.n_reads(); i++) {
+        uint64_t h = 0;
+        for (uint64_t r = R.roff[i]; r < R.roff[i + 1]; r++) h += R.rl[r];
+        append_name(text, b.headers[i]);
+        text += '\t';
+        if (rcomp[i] == KT_NO_COMPONENT) text += '*';
+        else append_uint(text, rcomp[i]);
+        append_tab_uints(text, {rmixed[i] ? 1u : 0u, h});
+        text += '\n';
     }
-    if (components_ && !thread_) {
-        static const char *names[4] = {"components", "singletons", "largest_unitigs", "largest_nodes"};
-        const uint64_t nodes = nb - nu * overlap;
-        std::string s;
-        append_stats_rows(s, names, ctally, 4);
-        char line[64];
-        const int h = snprintf(line, sizeof line, "largest_share\t%.4f\n", nodes ? (double)ctally[3] / (double)nodes : 0.0);
-        s.append(line, (size_t)h);
-        if (std::string e = write_text_file(out_dir_ + "/unitigs.components.stats", s); !e.empty()) return e;
-    }
-    if (thread_) {  // (`thread` writes its own statistics)
-        pt.t[3] += lap();
-        return thread_onto(bases, offsets, sums, comp, cstats);
-    }
-    // n50: the length of the first unitig, longest first, at which twice the running sum of lengths reaches `bases`
-    std::vector<uint64_t> lens((size_t)nu);
-    uint64_t occ = 0, circular = 0, singletons = 0, longest = 0, n50 = 0;
-    for (uint64_t i = 0; i < nu; i++) {
-        lens[i] = offsets[i + 1] - offsets[i];
-        occ += sums[i];
-        circular += flags[i] & KT_UNITIG_CIRCULAR ? 1 : 0;
-        singletons += lens[i] == overlap + 1;
-        longest = std::max(longest, lens[i]);
-    }
-    std::sort(lens.begin(), lens.end(), std::greater<uint64_t>());
-    for (uint64_t i = 0, run = 0; i < nu; i++) {
-        run += lens[i];
-        if (2 * run >= nb) {
-            n50 = lens[i];
-            break;
-        }
-    }
-    static const char *names[8] = {"unitigs", "bases", "nodes", "occurrences", "circular", "singletons", "longest", "n50"};
-    const uint64_t values[8] = {nu, nb, nb - nu * overlap, occ, circular, singletons, longest, n50};
-    std::string s;
-    append_stats_rows(s, names, values, 8);
-    if (std::string e = write_text_file(out_dir_ + "/unitigs.stats", s); !e.empty()) return e;
-    pt.t[3] += lap();
-    return "";
 }
 
 // `thread`: the unitigs (host arrays, as kt_ctr_unitigs filled them) become the index, the records of thread_reads_ are
 // walked in the usual batches.  The counted table has done its work by now and makes room for the index.
-std::string UnitigComputer::thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets,
-                                        const std::vector<uint64_t> &sums, const std::vector<uint32_t> &comp,
-                                        const std::vector<uint64_t> &cstats) {
+std::string UnitigComputer::thread_onto(const UnitigGraph &g) {
     PhaseTimer pt("thread");
     Lap lap;
-    const uint64_t nu = offsets.size() - 1, nb = offsets[nu], k = (uint64_t)ksize_;
+    const std::vector<uint64_t> &offsets = g.offsets;
+    const uint64_t nu = offsets.size() - 1, nb = offsets[nu], k = (uint64_t)ksize_, nc = g.cstats.size() / KT_COMPONENT_FIELDS;
     if (table_) kt_ctr_destroy(table_);
     table_ = nullptr;
     const uint64_t windows = nb - nu * (k - 1);
     if (kt_ctr_create(dev_.ctx, ksize_, std::max<uint64_t>(1024, windows + windows / 10 * 9), &table_) != KT_OK) return kt_last_error();
     uint64_t indexed = 0;
     static const uint64_t no_offsets[1] = {0};
-    if (kt_ctr_index_sequences(table_, nb ? bases.data() : (const uint8_t *)"", nu ? offsets.data() : no_offsets, nu, &indexed, KT_MEM_HOST) != KT_OK)
+    if (kt_ctr_index_sequences(table_, nb ? g.bases.data() : (const uint8_t *)"", nu ? offsets.data() : no_offsets, nu, &indexed, KT_MEM_HOST) != KT_OK)
         return kt_last_error();
     pt.t[1] += lap();
 
     SeqReader reader;
     if (!reader.open(thread_reads_, false)) return reader.error();
-    const std::string gpath = out_dir_ + "/thread.gaf";
-    FILE *fg = stats_only_ ? nullptr : fopen(gpath.c_str(), "wb");
-    if (!stats_only_ && !fg) return "Unable to write to file: " + gpath;
-    // --components: every record's component (kt_thread_read_components over the batch's runs), thread.reads
-    const uint64_t nc = cstats.size() / KT_COMPONENT_FIELDS;
-    const std::string rpath = out_dir_ + "/thread.reads";
-    FILE *fr = components_ && !stats_only_ ? fopen(rpath.c_str(), "wb") : nullptr;
-    if (components_ && !stats_only_ && !fr) {
-        if (fg) fclose(fg);
-        return "Unable to write to file: " + rpath;
+    // thread.gaf, and with --components thread.reads: every record's component (kt_thread_read_components over the batch's runs)
+    OutFile fg, fr;
+    if (!stats_only_) {
+        if (std::string e = fg.open(out_dir_ + "/thread.gaf"); !e.empty()) return e;
+        if (components_)
+            if (std::string e = fr.open(out_dir_ + "/thread.reads"); !e.empty()) return e;
     }
-    std::vector<uint32_t> rcomp;
-    std::vector<uint8_t> rmixed;
-    std::vector<uint64_t> creads((size_t)nc, 0), chits((size_t)nc, 0);
-    uint64_t with_comp = 0, n_mixed = 0;
-    std::string rtext;
+    ThreadTotals T;
+    T.unitig_hits.assign((size_t)nu, 0), T.unitig_runs.assign((size_t)nu, 0);
+    T.comp_reads.assign((size_t)nc, 0), T.comp_hits.assign((size_t)nc, 0);
     Batch batch;
-    std::vector<uint32_t> hits, rl, ru, rp;
-    std::vector<uint64_t> rs, roff, uh((size_t)nu, 0), ur((size_t)nu, 0);
-    uint64_t n_reads = 0, n_bases = 0, n_windows = 0, n_hits = 0, n_misses = 0, n_runs = 0, n_chains = 0, with_hit = 0, whole = 0;
+    ReadRuns R;
+    std::vector<uint32_t> hits, rcomp;
+    std::vector<uint8_t> rmixed;
     std::string text;
-    auto ulen = [&](uint32_t e) { return offsets[(e >> 1) + 1] - offsets[e >> 1]; };
     std::string err = walk(reader, batch, TABLE_BATCH_BASES, 1ull << 20, true, &pt, &lap, nullptr, [&](const Batch &b, const Cursor &) -> std::string {
         const uint64_t n = b.n_reads(), total = b.offsets[n];
         hits.assign(total, KT_NO_KMER);
         if (total && kt_ctr_thread_hits(table_, bases_ptr(b), b.offsets.data(), n, hits.data(), KT_MEM_HOST) != KT_OK) return kt_last_error();
         // a counting call, then one sized by it
         uint64_t nr = 0, tally[KT_THREAD_TALLY] = {};
-        roff.resize(n + 1);
+        R.roff.resize(n + 1);
         if (kt_thread_runs(dev_.ctx, hits.data(), b.offsets.data(), n, nu ? offsets.data() : no_offsets, nu, ksize_, nullptr, nullptr, nullptr,
-                           nullptr, roff.data(), 0, &nr, nullptr, nullptr, tally, KT_MEM_HOST) != KT_OK)
+                           nullptr, R.roff.data(), 0, &nr, nullptr, nullptr, tally, KT_MEM_HOST) != KT_OK)
             return kt_last_error();
-        rs.resize(nr), rl.resize(nr), ru.resize(nr), rp.resize(nr);
-        if (nr && kt_thread_runs(dev_.ctx, hits.data(), b.offsets.data(), n, offsets.data(), nu, ksize_, rs.data(), rl.data(), ru.data(), rp.data(),
-                                 roff.data(), nr, &nr, uh.data(), ur.data(), tally, KT_MEM_HOST) != KT_OK)
+        R.rs.resize(nr), R.rl.resize(nr), R.ru.resize(nr), R.rp.resize(nr);
+        if (nr && kt_thread_runs(dev_.ctx, hits.data(), b.offsets.data(), n, offsets.data(), nu, ksize_, R.rs.data(), R.rl.data(), R.ru.data(),
+                                 R.rp.data(), R.roff.data(), nr, &nr, T.unitig_hits.data(), T.unitig_runs.data(), tally, KT_MEM_HOST) != KT_OK)
             return kt_last_error();
         if (components_ && n) {
             static const uint32_t none[1] = {0};
             uint64_t t[KT_READ_COMPONENT_TALLY] = {};
             rcomp.resize(n), rmixed.resize(n);
-            if (kt_thread_read_components(dev_.ctx, nr ? ru.data() : none, nr ? rl.data() : none, roff.data(), n, nu ? comp.data() : none, nu,
-                                          nc, rcomp.data(), rmixed.data(), creads.data(), chits.data(), t, KT_MEM_HOST) != KT_OK)
+            if (kt_thread_read_components(dev_.ctx, nr ? R.ru.data() : none, nr ? R.rl.data() : none, R.roff.data(), n, nu ? g.comp.data() : none,
+                                          nu, nc, rcomp.data(), rmixed.data(), T.comp_reads.data(), T.comp_hits.data(), t, KT_MEM_HOST) != KT_OK)
                 return kt_last_error();
-            with_comp += t[0], n_mixed += t[2];
-            if (fr) {
-                for (uint64_t i = 0; i < n; i++) {
-                    uint64_t h = 0;
-                    for (uint64_t r = roff[i]; r < roff[i + 1]; r++) h += rl[r];
-                    append_name(rtext, b.headers[i]);
-                    rtext += '\t';
-                    if (rcomp[i] == KT_NO_COMPONENT) rtext += '*';
-                    else append_uint(rtext, rcomp[i]);
-                    rtext += rmixed[i] ? "\t1\t" : "\t0\t";
-                    append_uint(rtext, h);
-                    rtext += '\n';
-                }
-                if (!rtext.empty() && fwrite(rtext.data(), 1, rtext.size(), fr) != rtext.size()) return "Unable to write to file: " + rpath;
-                rtext.clear();
+            T.with_comp += t[0], T.mixed += t[2];
+            if (fr.is_open()) {
+                append_thread_reads(text, b, R, rcomp, rmixed);
+                if (!fr.write(text)) return fr.close();
+                text.clear();
             }
         }
         pt.t[1] += lap();
-        n_reads += n, n_bases += total, n_windows += tally[0], n_hits += tally[1], n_misses += tally[2], n_runs += tally[4], with_hit += tally[5];
+        T.reads += n, T.bases += total, T.windows += tally[0], T.hits += tally[1], T.misses += tally[2], T.runs += tally[4], T.with_hit += tally[5];
         for (uint64_t i = 0; i < n; i++) {
             const uint64_t o = b.offsets[i], len = b.offsets[i + 1] - o;
             uint64_t chains_here = 0, first_qs = 0, last_qe = 0;
-            for (uint64_t r = roff[i]; r < roff[i + 1];) {
-                // the chain that starts with run r: each further run starts where the one before stopped, at the first k-mer
-                // of its oriented unitig, the one before having ended at the last k-mer of its own
-                uint64_t e = r + 1, plen = ulen(ru[r]);
-                for (; e < roff[i + 1]; e++) {
-                    const uint64_t L = ulen(ru[e]), L0 = ulen(ru[e - 1]);
-                    const bool starts = rp[e] == (ru[e] & 1u ? L - k : 0);
-                    const bool ended = ru[e - 1] & 1u ? rp[e - 1] + 1 == rl[e - 1] : rp[e - 1] + rl[e - 1] - 1 == L0 - k;
-                    if (rs[e] != rs[e - 1] + rl[e - 1] || !starts || !ended) break;
-                    plen += L - (k - 1);
-                }
-                const uint64_t qs = rs[r] - o, qe = rs[e - 1] - o + rl[e - 1] - 1 + k;
-                const uint64_t ps = ru[r] & 1u ? ulen(ru[r]) - k - rp[r] : rp[r];
+            for_each_chain(R, g, k, o, R.roff[i], R.roff[i + 1], [&](uint64_t r, uint64_t e, uint64_t qs, uint64_t qe, uint64_t ps, uint64_t plen) {
                 if (!chains_here++) first_qs = qs;
                 last_qe = qe;
-                if (fg) {
-                    append_name(text, b.headers[i]);
-                    text += '\t';
-                    append_uint(text, len);
-                    text += '\t';
-                    append_uint(text, qs);
-                    text += '\t';
-                    append_uint(text, qe);
-                    text += "\t+\t";
-                    for (uint64_t x = r; x < e; x++) {
-                        text += ru[x] & 1u ? '<' : '>';
-                        append_uint(text, ru[x] >> 1);
-                    }
-                    for (const uint64_t v : {plen, ps, ps + qe - qs, qe - qs, qe - qs}) {
-                        text += '\t';
-                        append_uint(text, v);
-                    }
-                    text += "\t255\n";
-                }
-                r = e;
-            }
-            n_chains += chains_here;
-            whole += chains_here == 1 && first_qs == 0 && last_qe == len;
+                if (fg.is_open()) append_gaf_line(text, b.headers[i], len, R, r, e, qs, qe, ps, plen);
+            });
+            T.chains += chains_here;
+            T.whole += chains_here == 1 && first_qs == 0 && last_qe == len;
         }
         pt.t[2] += lap();
-        if (fg && !text.empty() && fwrite(text.data(), 1, text.size(), fg) != text.size()) return "Unable to write to file: " + gpath;
+        if (!fg.write(text)) return fg.close();
         text.clear();
         pt.t[3] += lap();
         return "";
     });
-    if (fg && fclose(fg) != 0 && err.empty()) err = "Unable to write to file: " + gpath;
-    if (fr && fclose(fr) != 0 && err.empty()) err = "Unable to write to file: " + rpath;
+    const std::string eg = fg.close(), er = fr.close();
+    if (err.empty()) err = eg.empty() ? er : eg;
     if (!err.empty()) return err;
 
     uint64_t unitigs_hit = 0;
     for (uint64_t u = 0; u < nu; u++) {
-        const uint64_t len = offsets[u + 1] - offsets[u], nodes = len - (k - 1);
+        const uint64_t len = g.len(u), nodes = len - (k - 1);
         char line[200];
         const int h = snprintf(line, sizeof line, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6f\n", (unsigned long long)u, (unsigned long long)len,
-                               (unsigned long long)nodes, (unsigned long long)sums[u], (unsigned long long)uh[u], (unsigned long long)ur[u],
-                               (double)uh[u] / (double)nodes);
+                               (unsigned long long)nodes, (unsigned long long)g.sums[u], (unsigned long long)T.unitig_hits[u],
+                               (unsigned long long)T.unitig_runs[u], (double)T.unitig_hits[u] / (double)nodes);
         text.append(line, (size_t)h);
-        unitigs_hit += uh[u] != 0;
+        unitigs_hit += T.unitig_hits[u] != 0;
     }
     if (std::string e = write_text_file(out_dir_ + "/thread.unitigs", text); !e.empty()) return e;
     static const char *names[10] = {"reads", "bases", "windows", "hits", "misses", "runs", "chains", "reads_with_hit",
                                     "reads_one_chain_end_to_end", "unitigs_hit"};
-    const uint64_t values[10] = {n_reads, n_bases, n_windows, n_hits, n_misses, n_runs, n_chains, with_hit, whole, unitigs_hit};
+    const uint64_t values[10] = {T.reads, T.bases, T.windows, T.hits, T.misses, T.runs, T.chains, T.with_hit, T.whole, unitigs_hit};
     std::string s;
     append_stats_rows(s, names, values, 10);
     if (components_) {
         uint64_t comps_hit = 0;
         text.clear();
         for (uint64_t c = 0; c < nc; c++) {
-            const uint64_t *r = &cstats[(size_t)c * KT_COMPONENT_FIELDS];
-            for (const uint64_t v : {c, r[0], r[1], creads[c], chits[c]}) {
-                append_uint(text, v);
-                text += '\t';
-            }
-            text.back() = '\n';
-            comps_hit += chits[c] != 0;
+            const uint64_t *r = &g.cstats[(size_t)c * KT_COMPONENT_FIELDS];
+            append_uint(text, c);
+            append_tab_uints(text, {r[0], r[1], T.comp_reads[c], T.comp_hits[c]});
+            text += '\n';
+            comps_hit += T.comp_hits[c] != 0;
         }
         if (std::string e = write_text_file(out_dir_ + "/thread.components", text); !e.empty()) return e;
         static const char *cnames[3] = {"reads_with_component", "reads_mixed", "components_hit"};
-        const uint64_t cvalues[3] = {with_comp, n_mixed, comps_hit};
+        const uint64_t cvalues[3] = {T.with_comp, T.mixed, comps_hit};
         append_stats_rows(s, cnames, cvalues, 3);
     }
     if (std::string e = write_text_file(out_dir_ + "/thread.stats", s); !e.empty()) return e;
@@ -2736,12 +2698,6 @@ static void append_mmer(std::string &s, uint64_t kmer, int msize) {
     s += buf;
 }
 
-static void append_u64(std::string &s, uint64_t v) {
-    char buf[24];
-    const auto r = std::to_chars(buf, buf + sizeof buf, v);
-    s.append(buf, (size_t)(r.ptr - buf));
-}
-
 static std::string check_min_args(uint64_t wsize, int msize, const std::string &in_path) {
     if (msize < 1 || msize > 31) return "minimiser size must be in 1..31";
     if (wsize != 0 && wsize < (uint64_t)msize) return "window size must not be shorter than the minimiser";
@@ -2755,18 +2711,15 @@ std::string seq_to_min(uint64_t wsize, int msize, const std::string &in_path, co
     if (std::string e = check_min_args(wsize, msize, in_path); !e.empty()) return e;
     SeqReader reader;
     if (!reader.open(in_path, false)) return reader.error();
-    FILE *out = fopen(out_path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path;
+    OutFile out;
+    if (std::string e = out.open(out_path); !e.empty()) return e;
     Device dev;
     dev.index = device;
-    if (std::string e = dev.ensure(); !e.empty()) {
-        fclose(out);
-        return e;
-    }
+    if (std::string e = dev.ensure(); !e.empty()) return e;
     std::vector<std::string> pieces;
     PhaseTimer pt("min s2m");
-    AsyncWriter writer(out, pt);
-    const std::string err = run_pipeline(
+    AsyncWriter writer(out.stream(), pt);
+    return run_pipeline(
         reader, 64ull << 20, 1ull << 19, pt, [&](Work &w) { return minimiser_batch(dev.ctx, w, wsize, msize); },
         [&](Work &w) {
             Lap lap;
@@ -2779,9 +2732,9 @@ std::string seq_to_min(uint64_t wsize, int msize, const std::string &in_path, co
                     s += '\t';
                     append_mmer(s, km[j], msize);
                     s += ':';
-                    append_u64(s, st[j]);
+                    append_uint(s, st[j]);
                     s += '-';
-                    append_u64(s, en[j]);
+                    append_uint(s, en[j]);
                 }
                 s += "\t\n";
             });
@@ -2789,9 +2742,6 @@ std::string seq_to_min(uint64_t wsize, int msize, const std::string &in_path, co
             writer.write(pieces);
         },
         true);
-    writer.finish();
-    fclose(out);
-    return err;
 }
 
 // Rust's {:?} for a String: quotes, with \" \\ \t \n \r and other control characters escaped
@@ -2823,14 +2773,11 @@ std::string bin_sequences(uint64_t wsize, int msize, const std::string &in_path,
     if (std::string e = check_min_args(wsize, msize, in_path); !e.empty()) return e;
     SeqReader reader;
     if (!reader.open(in_path, false)) return reader.error();
-    FILE *out = fopen(out_path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path;
+    OutFile out;
+    if (std::string e = out.open(out_path); !e.empty()) return e;
     Device dev;
     dev.index = device;
-    if (std::string e = dev.ensure(); !e.empty()) {
-        fclose(out);
-        return e;
-    }
+    if (std::string e = dev.ensure(); !e.empty()) return e;
     // the whole file's triples are grouped by minimiser at the end, like the reference's in-memory map
     struct Hit {
         uint64_t kmer;
@@ -2852,10 +2799,7 @@ std::string bin_sequences(uint64_t wsize, int msize, const std::string &in_path,
             pt.t[2] += lap();
         },
         true);
-    if (!err.empty()) {
-        fclose(out);
-        return err;
-    }
+    if (!err.empty()) return err;
     Lap lap;
     // ascending minimiser text == ascending value of its low 2m bits (A < C < G < T is the 2-bit order)
     const uint64_t mask = msize >= 32 ? ~0ull : ((1ull << (2 * msize)) - 1ull);
@@ -2874,16 +2818,16 @@ std::string bin_sequences(uint64_t wsize, int msize, const std::string &in_path,
             s += '(';
             append_debug_str(s, ids[hits[i].id]);
             s += ", ";
-            append_u64(s, hits[i].start);
+            append_uint(s, hits[i].start);
             s += ", ";
-            append_u64(s, hits[i].end);
+            append_uint(s, hits[i].end);
             s += ')';
         }
         s += "]\n";
     });
     pt.t[2] += lap();
-    for (const auto &p : pieces) fwrite(p.data(), 1, p.size(), out);
-    fclose(out);
+    out.write(pieces);
+    (void)out.close();  // (no write error is reported here either, as with the ordered writer)
     pt.t[3] += lap();
     return "";
 }
@@ -2895,12 +2839,7 @@ SketchComputer::SketchComputer(std::string in_path, std::string out_dir, int ksi
 static void append_sketch_line(std::string &text, const std::string &id, uint64_t length, uint64_t kmers, uint32_t size,
                                const uint64_t *row) {
     text += id;
-    text += '\t';
-    append_uint(text, length);
-    text += '\t';
-    append_uint(text, kmers);
-    text += '\t';
-    append_uint(text, size);
+    append_tab_uints(text, {length, kmers, size});
     text += '\t';
     for (uint32_t t = 0; t < size; t++) {
         if (t) text += ',';
@@ -2913,8 +2852,8 @@ static void append_sketch_line(std::string &text, const std::string &id, uint64_
 std::string SketchComputer::sketch_input(const std::string &path, const std::string &out_path, Set &set, bool keep) {
     SeqReader reader;
     if (!reader.open(path, false)) return reader.error();
-    FILE *out = fopen(out_path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + out_path;
+    OutFile out;
+    if (std::string e = out.open(out_path); !e.empty()) return e;
     PhaseTimer pt("sketch");
     Lap lap;
     Batch b;
@@ -2970,8 +2909,8 @@ std::string SketchComputer::sketch_input(const std::string &path, const std::str
                     set.sizes.insert(set.sizes.end(), sizes.begin(), sizes.end());
                 }
                 pt.t[2] += lap();
-                if (fwrite(text.data(), 1, text.size(), out) != text.size()) {
-                    err = "Unable to write to file: " + out_path;
+                if (!out.write(text)) {
+                    err = out.close();
                     break;
                 }
                 pt.t[3] += lap();
@@ -2994,17 +2933,16 @@ std::string SketchComputer::sketch_input(const std::string &path, const std::str
             set.hashes.assign(run_h.begin(), run_h.begin() + s_);
             set.sizes.assign(1, run_s[0]);
         }
-        if (fwrite(text.data(), 1, text.size(), out) != text.size()) err = "Unable to write to file: " + out_path;
+        out.write(text);
     }
-    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + out_path;
+    if (std::string e = out.close(); err.empty()) err = e;
     return err;
 }
 
 // sketch.dist: the pairs i < j of `a` (b == nullptr) or every (i of a, j of b), a block of rows of the matrix at a time
 std::string SketchComputer::write_dist(const Set &a, const Set *b) {
-    const std::string path = out_dir_ + "/sketch.dist";
-    FILE *out = fopen(path.c_str(), "wb");
-    if (!out) return "Unable to write to file: " + path;
+    OutFile out;
+    if (std::string e = out.open(out_dir_ + "/sketch.dist"); !e.empty()) return e;
     const Set &bb = b ? *b : a;
     const uint64_t n_a = a.sizes.size(), n_b = bb.sizes.size();
     std::string err, text;
@@ -3040,10 +2978,10 @@ std::string SketchComputer::write_dist(const Set &a, const Set *b) {
                     text += '\n';
                 }
             }
-            if (fwrite(text.data(), 1, text.size(), out) != text.size()) err = "Unable to write to file: " + path;
+            if (!out.write(text)) err = out.close();
         }
     }
-    if (fclose(out) != 0 && err.empty()) err = "Unable to write to file: " + path;
+    if (std::string e = out.close(); err.empty()) err = e;
     return err;
 }
 
@@ -3089,15 +3027,9 @@ std::string CardComputer::card() {
         const std::string names[7] = {pre + "sequences", pre + "bases", pre + "kmers", pre + "precision", pre + "registers",
                                       pre + "zero_registers", pre + "distinct_estimate"};
         const uint64_t values[7] = {end.reads, end.bases, n_kmers, (uint64_t)p_, (uint64_t)m, zeros, (uint64_t)floor(est[i] + 0.5)};
-        for (int j = 0; j < 7; j++) {
-            const char *name = names[j].c_str();
-            append_stats_rows(s, &name, &values[j], 1);
-        }
+        for (int j = 0; j < 7; j++) s += names[j] + '\t' + std::to_string(values[j]) + '\n';
         append_fixed6_row(s, pre + "rel_std_error", kt_card_rel_error(p_));
-        const std::string wn = pre + "slots_wanted";
-        const char *name = wn.c_str();
-        const uint64_t want = std::min(in.want, slots_for_estimate(est[i], p_));
-        append_stats_rows(s, &name, &want, 1);
+        s += pre + "slots_wanted\t" + std::to_string(std::min(in.want, slots_for_estimate(est[i], p_))) + '\n';
 
         std::string r = std::to_string(p_) + '\t' + std::to_string(seed_) + '\t' + std::to_string(ksize_) + '\n';
         for (size_t j = 0; j < m; j++) {

@@ -20,7 +20,8 @@
 
 namespace kthost {
 
-struct Batch;  // seqio.hpp
+struct Batch;        // seqio.hpp
+struct UnitigGraph;  // computers.cpp: the unitigs, links and components as the device calls returned them
 
 // Rust `format!("{:.6}", x)` (oligo.rs:132-134) and `Display` for f64 (shortest round-trip,
 // positional notation, integral values without ".0": oligo.rs:136, oligocgr.rs:95)
@@ -524,8 +525,9 @@ class UnitigComputer {
     std::string unitigs();  // "" or the error message
 
   private:
-    std::string thread_onto(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &sums,
-                            const std::vector<uint32_t> &comp, const std::vector<uint64_t> &cstats);
+    std::string simplify_table();                            // set_clip / set_bubbles, and the stats file of it
+    std::string fetch_unitigs(bool linked, UnitigGraph &g);  // what the device calls return
+    std::string thread_onto(const UnitigGraph &g);
     bool thread_ = false;
     std::string thread_reads_;
     std::string in_path_, out_dir_;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "computers.hpp"
+#include "outfile.hpp"
 #include "seqio.hpp"
 
 using namespace kthost;
@@ -1435,6 +1436,102 @@ int cmd_debug_fixed6(int argc, char **argv, int from) {
     return bad ? 1 : 0;
 }
 
+// hidden: OutFile (outfile.hpp) through its paths, the scratch files in <dir>: a directory that does not exist, /dev/full
+// with little (the failure shows at close) and with much (it shows at the write), writes after a failure, a scope left
+// without close(), 9 MiB in pieces that straddle the flush threshold read back, a second close()
+int cmd_debug_outfile(int argc, char **argv, int from) {
+    if (from >= argc) return 2;
+    const std::string dir = argv[from];
+    int bad = 0;
+    auto check = [&](bool ok, const char *what) {
+        if (!ok) fprintf(stderr, "debug-outfile: %s\n", what), bad++;
+    };
+    auto slurp = [](const std::string &path) {
+        std::string s;
+        if (FILE *f = fopen(path.c_str(), "rb")) {
+            char buf[1 << 16];
+            for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) s.append(buf, n);
+            fclose(f);
+        }
+        return s;
+    };
+    {
+        OutFile o;
+        const std::string p = dir + "/no/such/dir/x";
+        check(o.open(p) == "Unable to write to file: " + p, "open in a missing directory: the message");
+        check(!o.is_open() && !o.failed(), "a file that did not open is not open and has not failed");
+        o.text() += "nowhere";
+        check(o.write("nowhere") && o.close().empty(), "a file that did not open swallows writes and closes clean");
+    }
+    const std::string full = "Unable to write to file: /dev/full";
+    {
+        OutFile o;
+        check(o.open("/dev/full").empty(), "open /dev/full");
+        check(o.write("0123456789") && !o.failed(), "10 bytes to /dev/full: buffered, no failure yet");
+        check(o.close() == full, "10 bytes to /dev/full: the failure at close");
+        check(o.close().empty() && !o.is_open(), "a second close has nothing to report");
+    }
+    {
+        OutFile o;
+        const std::string mib((size_t)1 << 20, 'x');
+        check(o.open("/dev/full").empty(), "open /dev/full again");
+        check(!o.write(mib) && o.failed(), "1 MiB to /dev/full: the failure at the write");
+        check(!o.write("more") && !o.write(std::vector<std::string>{"a", "b"}), "writes after a failure fail");
+        o.text() += "and more";
+        check(o.error() == full && o.close() == full, "1 MiB to /dev/full: the same message");
+        check(o.close().empty(), "the message comes once");
+    }
+    {
+        OutFile o;  // the buffered text alone, past the threshold: the failure shows when text() is asked for again
+        check(o.open("/dev/full").empty(), "open /dev/full a third time");
+        o.text().assign(OutFile::FLUSH_AT, 'y');
+        check(!o.failed(), "text below its next request is not written yet");
+        o.text() += "z";
+        check(o.failed() && o.close() == full, "a full buffer to /dev/full: the failure at the flush");
+    }
+    const std::string scoped = dir + "/outfile.scoped";
+    {
+        OutFile o;
+        check(o.open(scoped).empty(), "open a file to leave open");
+        o.text() += "left ";
+        o.write("open");
+        o.text() += "\n";
+    }
+    check(slurp(scoped) == "left open\n", "a scope left without close(): the destructor wrote and closed");
+    {
+        // 9 MiB: lines through text(), now and then a vector of pieces or a string straight through write(), in sizes
+        // that put the buffer just below, at and above the threshold
+        const std::string path = dir + "/outfile.big";
+        OutFile o;
+        check(o.open(path).empty(), "open the 9 MiB file");
+        std::string want, line;
+        uint64_t x = 88172645463325252ull;
+        for (uint64_t i = 0; want.size() < (9u << 20); i++) {
+            x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+            size_t len = (size_t)(x % 300000);
+            const size_t have = o.text().size();  // every seventh line fills the buffer to the threshold - 1, + 0, + 1
+            if (i % 7 == 6 && have + 2 <= OutFile::FLUSH_AT) len = OutFile::FLUSH_AT - have - 2 + (size_t)(i / 7 % 3);
+            line.assign(len, (char)('a' + i % 26));
+            line += '\n';
+            if (i % 5 == 3) {
+                const std::vector<std::string> pieces = {line.substr(0, line.size() / 2), "", line.substr(line.size() / 2)};
+                check(o.write(pieces), "pieces into the 9 MiB file");
+            } else if (i % 5 == 4) {
+                check(o.write(line), "a string into the 9 MiB file");
+            } else {
+                o.text() += line;
+            }
+            want += line;
+        }
+        check(o.close().empty() && o.close().empty(), "close the 9 MiB file, twice");
+        check(slurp(path) == want, "the 9 MiB file read back");
+        remove(path.c_str());
+    }
+    remove(scoped.c_str());
+    if (!bad) puts("outfile ok");
+    return bad ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -1461,6 +1558,7 @@ int main(int argc, char **argv) {
     if (cmd == "ctr") return cmd_ctr(argc, argv, 2);
     if (cmd == "debug-read") return cmd_debug_read(argc, argv, 2);
     if (cmd == "debug-fixed6") return cmd_debug_fixed6(argc, argv, 2);
+    if (cmd == "debug-outfile") return cmd_debug_outfile(argc, argv, 2);  // debug-outfile <dir>
     if (cmd == "debug-emit") {  // debug-emit <rows> <bins> <norm 0|1> <threads> <reps>
         if (argc < 7) return 2;
         const double s = debug_emit_bench(strtoull(argv[2], nullptr, 10), strtoull(argv[3], nullptr, 10), atoi(argv[4]) != 0,
