@@ -912,6 +912,70 @@ int kt_sketch_pairs(kt_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_siz
  * denom == 0); 1 when j == 0, else min(1, -ln(2j / (1 + j)) / k); j == 1 gives 0. */
 double kt_mash_distance(uint32_t shared, uint32_t denom, int k);
 
+/* ---- scaled (FracMinHash) sketches (`kmertools sketch --scaled`; what sourmash does with `scaled`) --------------------
+ * replaces: nothing - the reference has no such operation.
+ *   Hash of a window: h = mix64(canonical k-mer ^ seed), the formula printed above kt_sketch_batch, 1 <= k <= 31; a window
+ *   over a byte that is no nucleotide is none, as everywhere.
+ *   max_hash(scaled) = 0xFFFFFFFFFFFFFFFF / scaled (integer division, scaled >= 1; scaled == 0 is KT_ERR_ARG).  A hash is
+ *   KEPT when h <= max_hash; scaled = 1 keeps every k-mer.
+ *   A scaled sketch is the set of kept hashes, distinct and strictly ascending.  Every hash has an ABUNDANCE, how often its
+ *   k-mer occurred: a u32 that saturates at 0xFFFFFFFF where sums are formed, like KT_SETCNT_SUM.
+ *   The sketches of many sequences lie CSR: hashes[row_offsets[i] .. row_offsets[i+1]), abunds parallel to it, row_offsets of
+ *   n + 1 u64 with row_offsets[0] == 0.
+ * So the size of a sketch follows the content, the sketch of a union is the union of the sketches, and |A n B| / |A| is
+ * an unbiased estimate of the containment of A in B whatever the two sizes.  This is the project's hash, not sourmash's.
+ * Sizes, as in kt_ctr_unitig_tips: *n_out (a host word) is always exact; max_out == 0 only counts - the data arrays may be
+ * NULL, the offsets (and n_kmers, totals) are still filled -; with 0 < max_out < *n_out nothing else is written and the call
+ * returns KT_ERR_ARG with *n_out set.  On every error the outputs are untouched.  `mem` says where every array lives;
+ * KT_MEM_HOST synchronises, KT_MEM_DEVICE runs on the context's stream and synchronises only to learn sizes.
+ * Every result is exact and a function of the inputs alone. */
+
+/* the largest kept hash; 0 for scaled == 0 */
+uint64_t kt_scaled_max_hash(uint64_t scaled);
+
+/* The containment-to-ANI estimate (host helper, the one implementation of the formula): (shared / size)^(1/k); 0 when shared
+ * or size is 0, 1 when shared == size. */
+double kt_containment_ani(uint64_t shared, uint64_t size, int k);
+
+/* Row i = the scaled sketch of read i, its abundances the number of windows of that read with that k-mer (abunds may be
+ * NULL).  n_kmers[i] (u32 per read, may be NULL) = the read's windows with multiplicity.  n_reads == 0 sets *n_out = 0 and
+ * touches nothing else.
+ * KT_ERR_ARG: k outside 1..31, scaled == 0, a bad mem, a null ctx, n_out, offsets or row_offsets, null hashes with
+ * max_out > 0, a read of 2^32 bases or more, a batch whose kept windows, with multiplicity, number 2^32 or more.
+ * Device scratch: 16 bytes per 8192 bases, then about 70 bytes per kept window. */
+int kt_scaled_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k, uint64_t scaled,
+                    uint64_t seed, uint64_t *hashes, uint32_t *abunds, uint64_t max_out, uint64_t *row_offsets, uint32_t *n_kmers,
+                    uint64_t *n_out, int mem);
+
+/* Sketches of unions: row g of the output = the union of rows group_offsets[g] .. group_offsets[g+1] of the input (n_rows
+ * rows in the CSR layout above; abunds NULL = 1 each), abundances summed, saturating.  An empty group gives an empty row;
+ * out_offsets has n_groups + 1 entries; out_abunds may be NULL.  n_groups == 0 sets *n_out = 0 and touches nothing else.
+ * Input rows must be strictly ascending: a precondition, not checked.  Outputs must not overlap inputs.
+ * KT_ERR_ARG: a bad mem, a null ctx, n_out, row_offsets, group_offsets or out_offsets, null hashes where the groups hold
+ * any, null out_hashes with max_out > 0, group offsets that decrease or end above n_rows, groups that hold 2^32 hashes or
+ * more in all (with multiplicity).  Device scratch: about 80 bytes per hash of the groups. */
+int kt_scaled_merge(kt_ctx *ctx, const uint64_t *hashes, const uint32_t *abunds, const uint64_t *row_offsets, uint64_t n_rows,
+                    const uint64_t *group_offsets, uint64_t n_groups, uint64_t *out_hashes, uint32_t *out_abunds, uint64_t max_out,
+                    uint64_t *out_offsets, uint64_t *n_out, int mem);
+
+/* The scaled sketch of the table's entries whose count lies in [min_count, max_count] - the SOLID k-mers of a read set with
+ * min_count = 2 -, abunds (may be NULL) = their counts.  totals (may be NULL, in `mem`, overwritten): [0] the entries in
+ * the count range, [1] the sum of their counts.  A walker like kt_ctr_spectrum: the table is read in the form it is in, is
+ * not brought to its probing image, keeps a staged export and is left unchanged.
+ * KT_ERR_ARG: min_count == 0 or > max_count, scaled == 0, a bad mem, a null table or n_out, null hashes with max_out > 0,
+ * one shard of a sharded table, 2^32 kept entries or more; KT_ERR_FULL: an overflowed table.
+ * Device scratch: about 60 bytes per kept entry. */
+int kt_ctr_scaled(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint64_t scaled, uint64_t seed, uint64_t *hashes,
+                  uint32_t *abunds, uint64_t max_out, uint64_t *n_out, uint64_t *totals, int mem);
+
+/* shared[i*n_b + j] (u32, n_a x n_b row-major) = |A_i n B_j| for two sets of sketches in the CSR layout above.
+ * a_hashes == b_hashes (with the same offsets) is allowed: the matrix is symmetric, its diagonal the sizes.  Rows are of any
+ * length, 0 included; they must be strictly ascending (a precondition).  n_a == 0 or n_b == 0 touches nothing.
+ * KT_ERR_ARG: a bad mem, a null ctx, null offsets or shared, null hashes where rows hold any, a row of 2^32 entries or
+ * more. */
+int kt_scaled_pairs(kt_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_offsets, uint64_t n_a, const uint64_t *b_hashes,
+                    const uint64_t *b_offsets, uint64_t n_b, uint32_t *shared, int mem);
+
 /* HyperLogLog registers of the distinct canonical k-mers of a batch (`kmertools card`, `--estimate-size`; what ntCard, KMC's
  * estimator and Jellyfish's size hint give their users).  replaces: nothing - the reference has no such operation.  No
  * table is involved.

@@ -103,6 +103,12 @@ SYMBOLS = {
     "kt_sketch_merge": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _vp, _i]),
     "kt_sketch_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _i]),
     "kt_mash_distance": (C.c_double, [_u32, _u32, _i]),
+    "kt_scaled_max_hash": (_u64, [_u64]),
+    "kt_containment_ani": (C.c_double, [_u64, _u64, _i]),
+    "kt_scaled_batch": (_i, [_vp, _vp, _vp, _u64, _i, _u64, _u64, _vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _i]),
+    "kt_scaled_merge": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64), _i]),
+    "kt_ctr_scaled": (_i, [_vp, _u32, _u32, _u64, _u64, _vp, _vp, _u64, C.POINTER(_u64), _vp, _i]),
+    "kt_scaled_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _i]),
     "kt_card_add_reads": (_i, [_vp, _vp, _vp, _u64, _i, _i, _u64, _vp, _vp, _i]),
     "kt_card_merge": (_i, [_vp, _vp, _i]),
     "kt_card_estimate": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_u64)]),

@@ -2985,8 +2985,230 @@ std::string SketchComputer::write_dist(const Set &a, const Set *b) {
     return err;
 }
 
+// ---- sketch --scaled -------------------------------------------------------------------------------------------------------
+static void append_scaled_line(std::string &text, const std::string &id, uint64_t length, uint64_t kmers, uint64_t size,
+                               const uint64_t *row, const uint32_t *abunds) {
+    text += id;
+    append_tab_uints(text, {length, kmers, size});
+    text += '\t';
+    for (uint64_t t = 0; t < size; t++) {
+        if (t) text += ',';
+        append_uint(text, row[t]);
+    }
+    if (abunds) {
+        text += '\t';
+        for (uint64_t t = 0; t < size; t++) {
+            if (t) text += ',';
+            append_uint(text, abunds[t]);
+        }
+    }
+    text += '\n';
+}
+
+static std::string file_name_of(const std::string &path) {
+    const size_t slash = path.find_last_of('/');
+    return slash == std::string::npos ? path : path.substr(slash + 1);
+}
+
+// One sized call: `call(max_out, &n_out)` is tried with the room the arrays have; a result that does not fit is refused with
+// its exact size, the arrays grow to it and the call is made again.
+template <class CallFn>
+static int sized_call(std::vector<uint64_t> &hashes, std::vector<uint32_t> &abunds, uint64_t guess, uint64_t *n_out, CallFn call) {
+    if (hashes.size() < guess) hashes.resize(guess);
+    if (hashes.empty()) hashes.resize(1);
+    abunds.resize(hashes.size());
+    *n_out = 0;
+    int rc = call(hashes.size(), n_out);
+    if (rc == KT_ERR_ARG && *n_out > hashes.size()) {
+        hashes.resize(*n_out);
+        abunds.resize(*n_out);
+        rc = call(hashes.size(), n_out);
+    }
+    return rc;
+}
+
+// the scaled sketches of one input: its lines into out_path, the sketches themselves into `set` when sketch.contain wants them
+std::string SketchComputer::scaled_input(const std::string &path, const std::string &out_path, ScaledSet &set, bool keep) {
+    SeqReader reader;
+    if (!reader.open(path, false)) return reader.error();
+    OutFile out;
+    if (std::string e = out.open(out_path); !e.empty()) return e;
+    PhaseTimer pt("sketch");
+    Lap lap;
+    Batch b;
+    std::string text, err, name;
+    std::vector<uint64_t> hashes, ro, run_h, in_h, in_o, merged_h;  // run_*: --single, the sketch of everything read so far
+    std::vector<uint32_t> abunds, nk, run_a, in_a, merged_a;
+    uint64_t all_bases = 0, all_kmers = 0;
+    for (;;) {
+        const bool more = reader.next_batch(b, cli_batch_bases(256ull << 20), cli_batch_reads(1ull << 20), false, true);
+        pt.t[0] += lap();
+        const uint64_t n = b.n_reads();
+        if (n) {
+            ro.resize(n + 1);
+            nk.resize(n);
+            uint64_t n_out = 0;
+            const uint64_t guess = b.offsets[n] / scaled_ * 2 + 4096;
+            if (sized_call(hashes, abunds, guess, &n_out, [&](uint64_t room, uint64_t *got) {
+                    return kt_scaled_batch(dev_.ctx, bases_ptr(b), b.offsets.data(), n, ksize_, scaled_, seed_, hashes.data(), abunds.data(),
+                                           room, ro.data(), nk.data(), got, KT_MEM_HOST);
+                }) != KT_OK) {
+                err = kt_last_error();
+                break;
+            }
+            if (single_) {
+                // one group: the running sketch and the batch's rows
+                in_h.assign(run_h.begin(), run_h.end());
+                in_h.insert(in_h.end(), hashes.begin(), hashes.begin() + n_out);
+                in_a.assign(run_a.begin(), run_a.end());
+                in_a.insert(in_a.end(), abunds.begin(), abunds.begin() + n_out);
+                in_o.assign(1, 0);
+                for (uint64_t i = 0; i <= n; i++) in_o.push_back(run_h.size() + ro[i]);
+                const uint64_t go[2] = {0, n + 1};
+                uint64_t mo[2] = {0, 0}, m_out = 0;
+                if (sized_call(merged_h, merged_a, in_h.size(), &m_out, [&](uint64_t room, uint64_t *got) {
+                        return kt_scaled_merge(dev_.ctx, in_h.data(), in_a.data(), in_o.data(), n + 1, go, 1, merged_h.data(), merged_a.data(),
+                                               room, mo, got, KT_MEM_HOST);
+                    }) != KT_OK) {
+                    err = kt_last_error();
+                    break;
+                }
+                run_h.assign(merged_h.begin(), merged_h.begin() + m_out);
+                run_a.assign(merged_a.begin(), merged_a.begin() + m_out);
+                all_bases += b.offsets[n];
+                for (uint64_t i = 0; i < n; i++) all_kmers += nk[i];
+                pt.t[1] += lap();
+            } else {
+                pt.t[1] += lap();
+                text.clear();
+                for (uint64_t i = 0; i < n; i++) {
+                    name.clear();
+                    append_name(name, b.headers[i]);
+                    append_scaled_line(text, name, b.offsets[i + 1] - b.offsets[i], nk[i], ro[i + 1] - ro[i], hashes.data() + ro[i],
+                                       abund_ ? abunds.data() + ro[i] : nullptr);
+                    if (keep) {
+                        set.ids.push_back(name);
+                        set.offsets.push_back(set.hashes.size() + ro[i + 1]);
+                    }
+                }
+                if (keep) set.hashes.insert(set.hashes.end(), hashes.begin(), hashes.begin() + n_out);
+                pt.t[2] += lap();
+                if (!out.write(text)) {
+                    err = out.close();
+                    break;
+                }
+                pt.t[3] += lap();
+            }
+        }
+        if (!more) break;
+    }
+    if (err.empty() && reader.failed()) err = reader.error();
+    if (err.empty() && single_) {
+        name = file_name_of(path);
+        text.clear();
+        append_scaled_line(text, name, all_bases, all_kmers, run_h.size(), run_h.data(), abund_ ? run_a.data() : nullptr);
+        if (keep) {
+            set.ids.push_back(name);
+            set.hashes = run_h;
+            set.offsets = {0, run_h.size()};
+        }
+        out.write(text);
+    }
+    if (std::string e = out.close(); err.empty()) err = e;
+    return err;
+}
+
+// --table: the one sketch of a table file's k-mers in the count range (the file's sections are loaded into one table)
+std::string SketchComputer::scaled_table(const std::string &out_path, ScaledSet &set, bool keep) {
+    kt_ctr *table = nullptr;
+    if (std::string e = table_from_file(dev_, table_path_, ksize_, 16, "table", &table); !e.empty()) {
+        if (table) kt_ctr_destroy(table);
+        return e;
+    }
+    std::vector<uint64_t> hashes;
+    std::vector<uint32_t> abunds;
+    uint64_t entries = 0, n_out = 0, totals[2] = {0, 0};
+    std::string err;
+    if (kt_ctr_size(table, &entries) != KT_OK ||
+        sized_call(hashes, abunds, entries / scaled_ * 2 + 4096, &n_out, [&](uint64_t room, uint64_t *got) {
+            return kt_ctr_scaled(table, min_count_, max_count_, scaled_, seed_, hashes.data(), abunds.data(), room, got, totals, KT_MEM_HOST);
+        }) != KT_OK)
+        err = kt_last_error();
+    kt_ctr_destroy(table);
+    if (!err.empty()) return err;
+    OutFile out;
+    if (std::string e = out.open(out_path); !e.empty()) return e;
+    const std::string name = file_name_of(table_path_);
+    std::string text;
+    append_scaled_line(text, name, 0, totals[1], n_out, hashes.data(), abund_ ? abunds.data() : nullptr);
+    if (keep) {
+        set.ids.push_back(name);
+        set.hashes.assign(hashes.begin(), hashes.begin() + n_out);
+        set.offsets = {0, n_out};
+    }
+    out.write(text);
+    return out.close();
+}
+
+// sketch.contain: the pairs i < j of `a` (b == nullptr) or every (i of a, j of b), a block of rows of the matrix at a time
+std::string SketchComputer::write_contain(const ScaledSet &a, const ScaledSet *b) {
+    OutFile out;
+    if (std::string e = out.open(out_dir_ + "/sketch.contain"); !e.empty()) return e;
+    const ScaledSet &bb = b ? *b : a;
+    const uint64_t n_a = a.ids.size(), n_b = bb.ids.size();
+    std::string err, text;
+    if (n_a && n_b) {
+        // the block's u32 matrix stays within 1 GiB
+        uint64_t rows = (1ull << 30) / (4 * n_b);
+        rows = rows < 1 ? 1 : (rows > n_a ? n_a : rows);
+        std::vector<uint32_t> shared(rows * n_b);
+        for (uint64_t i0 = 0; i0 < n_a && err.empty(); i0 += rows) {
+            const uint64_t r = n_a - i0 < rows ? n_a - i0 : rows;
+            if (kt_scaled_pairs(dev_.ctx, a.hashes.data(), a.offsets.data() + i0, r, bb.hashes.data(), bb.offsets.data(), n_b, shared.data(),
+                                KT_MEM_HOST) != KT_OK) {
+                err = kt_last_error();
+                break;
+            }
+            text.clear();
+            for (uint64_t i = i0; i < i0 + r; i++) {
+                const uint64_t size_a = a.offsets[i + 1] - a.offsets[i];
+                for (uint64_t j = b ? 0 : i + 1; j < n_b; j++) {
+                    const uint64_t sh = shared[(i - i0) * n_b + j], size_b = bb.offsets[j + 1] - bb.offsets[j];
+                    const double ca = size_a ? (double)sh / (double)size_a : 0.0, cb = size_b ? (double)sh / (double)size_b : 0.0;
+                    if ((ca >= cb ? ca : cb) < min_contain_) continue;
+                    const uint64_t uni = size_a + size_b - sh;
+                    text += a.ids[i];
+                    text += '\t';
+                    text += bb.ids[j];
+                    append_tab_uints(text, {sh, size_a, size_b});
+                    for (const double x : {uni ? (double)sh / (double)uni : 0.0, ca, cb,
+                                           kt_containment_ani(sh, ca >= cb ? size_a : size_b, ksize_)}) {
+                        text += '\t';
+                        append_display(text, x);
+                    }
+                    text += '\n';
+                }
+            }
+            if (!out.write(text)) err = out.close();
+        }
+    }
+    if (std::string e = out.close(); err.empty()) err = e;
+    return err;
+}
+
 std::string SketchComputer::sketch() {
     if (std::string e = dev_.ensure(); !e.empty()) return e;
+    if (scaled_) {
+        ScaledSet sa, sb;
+        if (std::string e = table_path_.empty() ? scaled_input(in_path_, out_dir_ + "/sketch.tsv", sa, contain_)
+                                                : scaled_table(out_dir_ + "/sketch.tsv", sa, contain_);
+            !e.empty())
+            return e;
+        if (!alt_path_.empty())
+            if (std::string e = scaled_input(alt_path_, out_dir_ + "/sketch.alt.tsv", sb, contain_); !e.empty()) return e;
+        if (contain_) return write_contain(sa, alt_path_.empty() ? nullptr : &sb);
+        return "";
+    }
     Set a, b;
     if (std::string e = sketch_input(in_path_, out_dir_ + "/sketch.tsv", a, dist_); !e.empty()) return e;
     if (!alt_path_.empty())

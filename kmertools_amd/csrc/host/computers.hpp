@@ -546,10 +546,17 @@ class UnitigComputer {
 // matrix at a time; the formula is kt_mash_distance).  Writes {out_dir}/sketch.tsv ("id\tlength\tkmers\tsize\th0,h1,..."
 // per sketch, in input order), {out_dir}/sketch.alt.tsv for the second input and {out_dir}/sketch.dist
 // ("id_a\tid_b\tshared/denom\tjaccard\tdistance": the pairs i < j of the input, or every pair (input, alt input)).
+// With --scaled the sketches are scaled ones (kt_scaled_batch; --single: the running sketch and a batch's rows are one group
+// of kt_scaled_merge; --table: kt_ctr_scaled of a loaded table file stands in for the input): the same files, `size` the
+// row's length, with --abund a sixth column of abundances; --contain writes {out_dir}/sketch.contain
+// ("id_a\tid_b\tshared\tsize_a\tsize_b\tjaccard\ta_in_b\tb_in_a\tani", kt_scaled_pairs a block of rows at a time).
 class SketchComputer {
   public:
     SketchComputer(std::string in_path, std::string out_dir, int ksize, uint32_t sketch_size);
     void set_seed(uint64_t seed) { seed_ = seed; }
+    void set_scaled(uint64_t scaled, bool abund) { scaled_ = scaled, abund_ = abund; }
+    void set_table(std::string path, uint32_t min_count, uint32_t max_count) { table_path_ = std::move(path), min_count_ = min_count, max_count_ = max_count; }
+    void set_contain(bool c, double min_contain) { contain_ = c, min_contain_ = min_contain; }
     void set_single(bool s) { single_ = s; }
     void set_alt_path(std::string p) { alt_path_ = std::move(p); }
     void set_dist(bool d, double max_dist) { dist_ = d, max_dist_ = max_dist; }
@@ -572,6 +579,19 @@ class SketchComputer {
     Device dev_;
     std::string sketch_input(const std::string &path, const std::string &out_path, Set &set, bool keep);
     std::string write_dist(const Set &a, const Set *b);
+    // --scaled
+    struct ScaledSet {  // the scaled sketches of one input, CSR, kept for sketch.contain
+        std::vector<std::string> ids;
+        std::vector<uint64_t> hashes, offsets{0};
+    };
+    std::string table_path_;
+    uint64_t scaled_ = 0;
+    uint32_t min_count_ = 1, max_count_ = 0xFFFFFFFFu;
+    bool abund_ = false, contain_ = false;
+    double min_contain_ = 0.0;
+    std::string scaled_input(const std::string &path, const std::string &out_path, ScaledSet &set, bool keep);
+    std::string scaled_table(const std::string &out_path, ScaledSet &set, bool keep);
+    std::string write_contain(const ScaledSet &a, const ScaledSet *b);
 };
 
 // `card`: the HyperLogLog registers of the distinct canonical k-mers of an input (kt_card_add_reads over the input walk) and

@@ -229,7 +229,7 @@ const char *HELP_MAIN =
     "  unitigs Maximal unitigs of the de Bruijn graph of the counted k-mers\n"
     "  hetmers Heterozygous k-mer pairs of the counted k-mers and their coverage matrix\n"
     "  thread  Map reads onto the unitigs of the counted k-mers (exact k-mer threading), GAF output\n"
-    "  sketch  MinHash sketches of sequences and the Mash distances between them\n"
+    "  sketch  MinHash sketches of sequences and their Mash distances; scaled sketches, containment and ANI\n"
     "  card    Estimate the number of distinct k-mers (HyperLogLog), sizes tables\n"
     "  help    Print this message or the help of the given subcommand(s)\n\n"
     "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n";
@@ -785,7 +785,7 @@ int cmd_profile(int argc, char **argv, int from) {
 }
 
 const char *HELP_SKETCH =
-    "MinHash sketches of sequences and the Mash distances between them\n\n"
+    "MinHash sketches of sequences and the Mash distances between them; scaled sketches, containment and ANI\n\n"
     "A record's sketch is the --sketch-size smallest distinct hashes of its canonical k-mers (windows over a non-ACGT base\n"
     "are none), hash = splitmix64 finaliser of (k-mer xor --seed).  Writes {output}/sketch.tsv: one line per record in input\n"
     "order with its name (the header up to the first white space), length, k-mers, sketch size and the hashes, decimal,\n"
@@ -794,43 +794,90 @@ const char *HELP_SKETCH =
     "{output}/sketch.alt.tsv.  With --dist also {output}/sketch.dist, one line \"id_a<TAB>id_b<TAB>shared/denom<TAB>jaccard<TAB>distance\"\n"
     "per pair: the pairs i < j of the input, or every pair (record of the input, record of the alt input); denom = min(sketch\n"
     "size, hashes of the union), shared = those of the denom smallest of the union that both hold, jaccard = shared / denom,\n"
-    "distance = 1 when nothing is shared, else min(1, -ln(2j / (1 + j)) / k) (Mash).\n\n"
+    "distance = 1 when nothing is shared, else min(1, -ln(2j / (1 + j)) / k) (Mash).\n"
+    "With --scaled a sketch is instead EVERY distinct hash at or below (2^64 - 1) / N (FracMinHash: its size follows the\n"
+    "content, and shared / size estimates containment whatever the two sizes); the files keep their columns, size being the\n"
+    "number of hashes, and --abund adds a sixth column: how often each hash's k-mer occurred, comma-separated, parallel to\n"
+    "the hashes.  With --table the one sketch is that of a table file's k-mers whose count lies in --min-count..--max-count\n"
+    "(--min-count 2: the solid k-mers of a read set), the counts being the abundances: its name is the file's name, its\n"
+    "length 0, its k-mers the occurrences in the count range.  With --contain also {output}/sketch.contain, one line\n"
+    "\"id_a<TAB>id_b<TAB>shared<TAB>size_a<TAB>size_b<TAB>jaccard<TAB>a_in_b<TAB>b_in_a<TAB>ani\" per pair (the same pairs as sketch.dist):\n"
+    "jaccard = shared / (size_a + size_b - shared), a_in_b = shared / size_a, b_in_a = shared / size_b (0 for an empty\n"
+    "sketch), ani = the larger of the two containments to the power 1 / k.\n\n"
     "Usage: kmertools sketch [OPTIONS] --input <INPUT> --output <OUTPUT>\n\n"
     "Options:\n"
     "  -i, --input <INPUT>          Input file path\n"
     "  -o, --output <OUTPUT>        Output directory path\n"
     "  -k, --k-size <K_SIZE>        k size (1..31) [default: 21]\n"
     "  -s, --sketch-size <S>        Hashes per sketch (1..16384) [default: 1000]\n"
+    "      --scaled <N>             Scaled sketches: keep the hashes <= (2^64 - 1) / N (N >= 1); not with --sketch-size\n"
+    "      --abund                  With --scaled: a sixth column, the abundances of the hashes\n"
     "      --seed <SEED>            Hash seed [default: 0]\n"
     "      --single                 One sketch for the whole input\n"
     "  -a, --alt-input <ALT_INPUT>  Second input: its sketches, and the distances input x alt input\n"
+    "      --table <FILE>           With --scaled: sketch the k-mers of this table file (ctr --save-table) instead of\n"
+    "                               --input, which is then not given; --k-size must be the file's k\n"
+    "      --min-count <L>          With --table: k-mers with at least L occurrences [default: 1]\n"
+    "      --max-count <U>          With --table: k-mers with at most U occurrences [default: 4294967295]\n"
     "      --dist                   Also write sketch.dist\n"
     "      --max-dist <D>           Keep the lines of sketch.dist with distance <= D (0..1) [default: 1]\n"
+    "      --contain                With --scaled: also write sketch.contain\n"
+    "      --min-contain <C>        Keep the lines of sketch.contain whose larger containment is >= C (0..1) [default: 0]\n"
     "  -t, --threads <THREADS>      Thread count for computations 0=auto [default: 0]\n"
     "      --device <DEVICE>        GPU index [default: 0]\n"
     "  -h, --help                   Print help\n";
 
+// a flag's value as a number in 0..=1
+static double unit_value(const std::string &v, const char *flag) {
+    char *end = nullptr;
+    const double x = strtod(v.c_str(), &end);
+    if (v.empty() || *end || !(x >= 0.0 && x <= 1.0)) usage_error("invalid value '" + v + "' for '--" + flag + "': not a number in 0..=1");
+    return x;
+}
+
 int cmd_sketch(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},   {'o', "output", true},    {'k', "k-size", true}, {'s', "sketch-size", true},
                                      {0, "seed", true},      {0, "single", false},     {'a', "alt-input", true}, {0, "dist", false},
-                                     {0, "max-dist", true},  {'t', "threads", true},   {0, "device", true}};
+                                     {0, "max-dist", true},  {'t', "threads", true},   {0, "device", true},   {0, "scaled", true},
+                                     {0, "abund", false},    SPEC_TABLE,               {0, "min-count", true}, {0, "max-count", true},
+                                     {0, "contain", false},  {0, "min-contain", true}};
     const auto f = parse_flags(argc, argv, from, specs, HELP_SKETCH);
-    const std::string in = required_str(f, "input"), out = required_str(f, "output");
+    const bool has_table = f.count("table") != 0;
+    const std::string in = has_table && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
     // everything is checked before any device work and before the output directory is made
     const int k = (int)ranged(f, "k-size", 1, 31, false, 21);
     const uint32_t s = (uint32_t)ranged(f, "sketch-size", 1, KT_SKETCH_MAX_S, false, 1000);
     const uint64_t seed = ranged(f, "seed", 0, UINT64_MAX, false, 0);
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
-    const bool dist = f.count("dist") != 0;
-    double max_dist = 1.0;
+    bool is_scaled = false;
+    const uint64_t scaled = ranged(f, "scaled", 1, UINT64_MAX, false, 0, &is_scaled);
+    if (is_scaled && f.at("scaled")[0] == '-')  // (strtoull takes a sign and wraps)
+        usage_error("invalid value '" + f.at("scaled") + "' for '--scaled': invalid digit found in string");
+    const bool dist = f.count("dist") != 0, contain = f.count("contain") != 0;
+    if (is_scaled) {
+        if (f.count("sketch-size")) usage_error("the argument '--scaled <N>' cannot be used with '--sketch-size <S>'");
+        if (dist) usage_error("the argument '--dist' cannot be used with '--scaled <N>' (scaled sketches are compared by '--contain')");
+        if (f.count("max-dist")) usage_error("the argument '--max-dist <D>' cannot be used with '--scaled <N>'");
+    } else {
+        for (const char *flag : {"abund", "contain", "min-contain", "table"})
+            if (f.count(flag)) usage_error(std::string("the argument '--") + flag + "' requires '--scaled <N>'");
+    }
+    for (const char *flag : {"min-count", "max-count"})
+        if (f.count(flag) && !has_table) usage_error(std::string("the argument '--") + flag + "' requires '--table <FILE>'");
+    const uint32_t min_count = (uint32_t)ranged(f, "min-count", 1, 0xFFFFFFFFull, false, 1);
+    const uint32_t max_count = (uint32_t)ranged(f, "max-count", 1, 0xFFFFFFFFull, false, 0xFFFFFFFFull);
+    if (min_count > max_count) usage_error("'--min-count <L>' is above '--max-count <U>'");
+    double max_dist = 1.0, min_contain = 0.0;
     if (auto it = f.find("max-dist"); it != f.end()) {
         if (!dist) usage_error("the argument '--max-dist <D>' requires '--dist'");
-        char *end = nullptr;
-        max_dist = strtod(it->second.c_str(), &end);
-        if (it->second.empty() || *end || !(max_dist >= 0.0 && max_dist <= 1.0))
-            usage_error("invalid value '" + it->second + "' for '--max-dist': not a number in 0..=1");
+        max_dist = unit_value(it->second, "max-dist");
     }
+    if (auto it = f.find("min-contain"); it != f.end()) {
+        if (!contain) usage_error("the argument '--min-contain <C>' requires '--contain'");
+        min_contain = unit_value(it->second, "min-contain");
+    }
+    const std::string table = table_flag(f, k);
     const std::string alt = f.count("alt-input") ? f.at("alt-input") : "";
     for (const std::string &p : {in, alt}) {
         if (!p.empty() && format_from_path(p) == SeqFormat::Unknown) {
@@ -844,6 +891,11 @@ int cmd_sketch(int argc, char **argv, int from) {
     sk.set_single(f.count("single") != 0);
     sk.set_alt_path(alt);
     sk.set_dist(dist, max_dist);
+    if (is_scaled) {
+        sk.set_scaled(scaled, f.count("abund") != 0);
+        sk.set_table(table, min_count, max_count);
+        sk.set_contain(contain, min_contain);
+    }
     if (threads > 0) sk.set_threads(threads);
     sk.set_device(device);
     if (std::string e = sk.sketch(); !e.empty()) {

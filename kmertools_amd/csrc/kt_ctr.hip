@@ -926,6 +926,57 @@ __global__ __launch_bounds__(BLOCK) void het_gather_kernel(const uint64_t *__res
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) dst[i] = src[index[i]];
 }
 
+// ---- the scaled sketch of a table's entries (kt_ctr_scaled) ---------------------------------------------------------------
+// The table walked read-only in the form it is in (walk_entries), twice: the first walk counts - the entries whose count lies
+// in [lo, hi], their occurrences, and those of them whose hash mix64(key ^ seed) is at or below max_hash -, the second one,
+// with room for exactly that many, compacts the kept ones as (hash, count) by tile_emit.  Their order is the cursor's, which
+// does not matter: kt::scaled_finish sorts them, and a table's keys are distinct.
+constexpr uint32_t SCALED_UNROLL = 4, SCALED_SUMS = 3;
+
+struct ScaledWalk {
+    uint32_t lo, hi;
+    uint64_t seed, max_hash;
+};
+
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void scaled_count_kernel(TableView w, ScaledWalk s, uint64_t *__restrict__ cells) {
+    __shared__ unsigned long long sums[SCALED_SUMS];
+    if (threadIdx.x < SCALED_SUMS) sums[threadIdx.x] = 0ull;
+    ktd::lds_barrier();
+    uint32_t kept = 0, n = 0;
+    uint64_t occ = 0;
+    walk_entries<FORM, SCALED_UNROLL, false>(w, [&](const uint64_t (&key)[SCALED_UNROLL], const uint32_t (&cw)[SCALED_UNROLL]) {
+#pragma unroll
+        for (uint32_t u = 0; u < SCALED_UNROLL; u++) {
+            if (key[u] == KT_EMPTY_KEY || cw[u] < s.lo || cw[u] > s.hi) continue;
+            n++;
+            occ += cw[u];
+            kept += ktd::mix64(key[u] ^ s.seed) <= s.max_hash ? 1u : 0u;
+        }
+    });
+    uint64_t v[SCALED_SUMS] = {kept, n, occ};
+    het_add_sums(v, sums, cells);
+}
+
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void scaled_emit_kernel(TableView w, ScaledWalk s, uint64_t *cursor, uint64_t room,
+                                                            uint64_t *__restrict__ hashes, uint32_t *__restrict__ counts) {
+    __shared__ SetShared sm;
+    uint32_t step = 0;
+    walk_entries<FORM, SCALED_UNROLL, true>(w, [&](const uint64_t (&key)[SCALED_UNROLL], const uint32_t (&cw)[SCALED_UNROLL]) {
+        uint64_t h[SCALED_UNROLL];
+        uint32_t keep = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < SCALED_UNROLL; u++) {
+            h[u] = ktd::mix64(key[u] ^ s.seed);
+            keep |= (key[u] != KT_EMPTY_KEY && cw[u] >= s.lo && cw[u] <= s.hi && h[u] <= s.max_hash ? 1u : 0u) << u;
+        }
+        tile_emit<SCALED_UNROLL>(cursor, keep, sm, step, [&](uint32_t u, uint64_t pos) {
+            if (pos < room) hashes[pos] = h[u], counts[pos] = cw[u];
+        });
+    });
+}
+
 __global__ __launch_bounds__(BLOCK) void route_count_kernel(SegArgs a, uint32_t n_owners,
                                                             uint64_t *__restrict__ owner_counts) {
     __shared__ SegShared sm;
@@ -1497,6 +1548,55 @@ extern "C" int kt_ctr_hetmers(kt_ctr *table, uint32_t min_count, uint32_t max_co
     if (int rc = call.finish()) return rc;
     if (max_out && n > max_out) return call.fail("max_out smaller than the result (*n_out pairs)");
     return KT_OK;
+}
+
+extern "C" int kt_ctr_scaled(kt_ctr *table, uint32_t min_count, uint32_t max_count, uint64_t scaled, uint64_t seed, uint64_t *hashes,
+                             uint32_t *abunds, uint64_t max_out, uint64_t *n_out, uint64_t *totals, int mem) {
+    if (!table || !n_out) return kt::fail(KT_ERR_ARG, "kt_ctr_scaled: null");
+    kt_ctx *ctx = table->ctx;
+    Call call(ctx, mem, "kt_ctr_scaled");
+    if (int rc = call.refuse_shard(table)) return rc;
+    if (min_count == 0) return call.fail("min_count must be >= 1");
+    if (min_count > max_count) return call.fail("min_count > max_count");
+    if (scaled == 0) return call.fail("scaled must be >= 1");
+    if (int rc = call.enter()) return rc;
+    if (max_out && !hashes) return call.fail("null output");
+    uint64_t n_t = 0;
+    if (int rc = kt_ctr_size(table, &n_t)) return rc;  // (KT_ERR_FULL for an overflowed table)
+    // this call's sums: [0] kept entries, [1] entries in the count range, [2] their occurrences
+    uint64_t *d_sums = nullptr, sums[SCALED_SUMS] = {0, 0, 0};
+    if (int rc = call.scratch(kt::BASES, SCALED_SUMS * 8, &d_sums)) return rc;
+    KT_HIP(hipMemsetAsync(d_sums, 0, SCALED_SUMS * 8, ctx->stream));
+    const ScaledWalk s{min_count, max_count, seed, kt_scaled_max_hash(scaled)};
+    if (n_t) {  // the table is walked in the form it is in: nothing here brings it to its probing image
+        const TableWalk w = view_of(table, n_t);
+        if (int rc = launch_walk(ctx, w, w.v.n, (uint64_t)BLOCK * SCALED_UNROLL, [&](auto form, dim3 grid) {
+                hipLaunchKernelGGL(scaled_count_kernel<decltype(form)::value>, grid, dim3(BLOCK), 0, ctx->stream, w.v, s, d_sums);
+            }))
+            return rc;
+        KT_HIP(hipMemcpyAsync(sums, d_sums, SCALED_SUMS * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    const uint64_t kept = sums[0];
+    if (kept >= (1ull << 32)) return call.fail("2^32 kept entries or more (a larger scaled, or a narrower count range)");
+    uint64_t *el_h = nullptr;
+    uint32_t *el_c = nullptr;
+    if (kept) {
+        if (int rc = carve(call, kt::AUX1, &el_h, kept, &el_c, kept)) return rc;
+        uint64_t *cursor = table->cursor;
+        KT_HIP(hipMemsetAsync(cursor, 0, 8, ctx->stream));
+        const TableWalk w = view_of(table, n_t);
+        if (int rc = launch_walk(ctx, w, w.v.n, (uint64_t)BLOCK * SCALED_UNROLL, [&](auto form, dim3 grid) {
+                hipLaunchKernelGGL(scaled_emit_kernel<decltype(form)::value>, grid, dim3(BLOCK), 0, ctx->stream, w.v, s, cursor, kept, el_h, el_c);
+            }))
+            return rc;
+    }
+    const kt::ScaledElems e{el_h, el_c, nullptr, kept, 1};
+    const kt::ScaledOut o{hashes, abunds, max_out, nullptr, n_out, mem};
+    if (int rc = kt::scaled_finish(ctx, "kt_ctr_scaled", e, o)) return rc;
+    if (totals)
+        KT_HIP(hipMemcpyAsync(totals, d_sums + 1, 16, call.host() ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    return call.finish();
 }
 
 extern "C" {

@@ -218,6 +218,30 @@ int kt_oligo_generic_launch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *o
 int kt_sort_pairs(kt_ctx *ctx, uint64_t *keys, uint32_t *counts, uint64_t n, uint32_t key_bits);
 
 namespace kt {
+// kt_scaled.hip: the one routine that turns n < 2^32 (hash, abundance, row) elements in device memory into scaled sketches -
+// sorted by (row, hash), equal hashes of a row made one with their abundances summed (saturating) - and hands them to the
+// caller's arrays in `mem`.  kt_scaled_batch, kt_scaled_merge and kt_ctr_scaled (kt_ctr.hip) end here.
+struct ScaledElems {
+    uint64_t *keys;          // the n hashes, in any order; the routine sorts them in place
+    const uint32_t *abunds;  // their abundances, or null: 1 each
+    const uint64_t *rows;    // their rows (< n_rows), or null: all of row 0
+    uint64_t n, n_rows;
+};
+struct ScaledOut {
+    uint64_t *hashes;        // the caller's arrays, in `mem` (abunds and row_offsets may be null)
+    uint32_t *abunds;
+    uint64_t max_out;
+    uint64_t *row_offsets;   // n_rows + 1
+    uint64_t *n_out;         // host
+    int mem;
+};
+// Scratch: OUT and AUX0 (kt_sort_pairs) and AUX2, none of which the caller may hold; the elements are the caller's (AUX1,
+// BASES, ...).  Enqueues the copies into the caller's arrays and does not wait for them.  KT_ERR_ARG with *n_out set and
+// nothing else written when 0 < max_out < *n_out.
+int scaled_finish(kt_ctx *ctx, const char *who, const ScaledElems &e, const ScaledOut &o);
+}  // namespace kt
+
+namespace kt {
 // host-side table builders (kt_host.cpp)
 uint64_t rev_comp_bits(uint64_t kmer, int k);
 // fills lut_full[4^k]: rank of the canonical form of every k-mer; returns kcount

@@ -4,7 +4,7 @@
 // is thread 0's after the last put.  Three launches: the tiles' sums (scan2_tile_sum_kernel), one workgroup over those
 // (scan2_tile_scan_kernel, which also leaves the two totals), and the tiles again (scan2_apply_kernel).
 // The kernels sit in an unnamed namespace: every translation unit that includes this gets its own copy of them in the
-// code object (four today - kt_unitig.hip, kt_tablefile.hip, kt_thread.hip, kt_component.hip; only scan2_tile_scan_kernel is no template and so
+// code object (five today - kt_unitig.hip, kt_tablefile.hip, kt_thread.hip, kt_component.hip, kt_scaled.hip; only scan2_tile_scan_kernel is no template and so
 // truly repeated: tolerable; a user that needs more of it should move them into a translation unit of their own).
 #pragma once
 #include "kt_device.hpp"

@@ -103,6 +103,17 @@ def mash_distance(shared, denom, k):
     return float(_lib.lib().kt_mash_distance(int(shared), int(denom), int(k)))
 
 
+def scaled_max_hash(scaled):
+    """the largest hash a scaled sketch keeps, 0xFFFFFFFFFFFFFFFF // scaled; 0 for scaled == 0 (kt_scaled_max_hash)"""
+    return int(_lib.lib().kt_scaled_max_hash(int(scaled)))
+
+
+def containment_ani(shared, size, k):
+    """the containment-to-ANI estimate (shared / size) ** (1 / k): 0 when shared or size is 0, 1 when they are equal
+    (kt_containment_ani, the one implementation of the formula)"""
+    return float(_lib.lib().kt_containment_ani(int(shared), int(size), int(k)))
+
+
 def _card_p(registers):
     """the precision of a register array: its length is 2^p"""
     m = int(registers.size)
@@ -571,6 +582,80 @@ class Context:
         self.sketch_pairs(a_hashes, a_sizes, len(a_sizes), b_hashes, b_sizes, len(b_sizes), s, shared, denom, KT_MEM_HOST)
         return shared, denom
 
+    # -- scaled (FracMinHash) sketches: CSR rows of (hash, abundance), their unions, shared hashes of pairs ------
+    def scaled_sketch(self, bases, offsets, n_reads, k, scaled, hashes, abunds, max_out, row_offsets, n_kmers=None, seed=0,
+                      mem=KT_MEM_DEVICE):
+        """row i of (hashes u64, abunds u32 or None) = the distinct mix64(canonical k-mer ^ seed) <= scaled_max_hash(scaled)
+        of read i, ascending, with their multiplicities; row_offsets u64[n_reads + 1]; n_kmers (u32, may be None) = the
+        reads' windows.  Returns the number of hashes; max_out 0 only counts (hashes may be None), a smaller max_out than
+        the result raises KmertoolsError (kt_scaled_batch)"""
+        n = C.c_uint64()
+        check(_lib.lib().kt_scaled_batch(self._h, _ptr(bases), _ptr(offsets), int(n_reads), int(k), int(scaled), int(seed),
+                                         _ptr(hashes), _ptr(abunds), int(max_out), _ptr(row_offsets), _ptr(n_kmers), C.byref(n), mem))
+        return n.value
+
+    def scaled_sketch_host(self, bases, offsets, k, scaled, seed=0):
+        """-> (hashes u64[n_out], abunds u32[n_out], row_offsets u64[n + 1], n_kmers u32[n]): a count-only call, then one
+        call sized by it"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        row_offsets, n_kmers = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32)
+        if not n:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint32), row_offsets, n_kmers
+        b = bases if bases.size else np.zeros(1, np.uint8)
+        n_out = self.scaled_sketch(b, offsets, n, k, scaled, None, None, 0, row_offsets, None, seed, KT_MEM_HOST)
+        hashes, abunds = np.zeros(n_out, np.uint64), np.zeros(n_out, np.uint32)
+        if n_out:
+            self.scaled_sketch(b, offsets, n, k, scaled, hashes, abunds, n_out, row_offsets, n_kmers, seed, KT_MEM_HOST)
+        else:
+            self.scaled_sketch(b, offsets, n, k, scaled, None, None, 0, row_offsets, n_kmers, seed, KT_MEM_HOST)
+        return hashes, abunds, row_offsets, n_kmers
+
+    def scaled_merge(self, hashes, abunds, row_offsets, group_offsets, out_hashes=None, out_abunds=None, max_out=0,
+                     out_offsets=None, mem=KT_MEM_HOST):
+        """row g of the result = the union of rows group_offsets[g] .. group_offsets[g+1], abundances (None: 1 each) summed
+        and saturating (kt_scaled_merge).  Host arrays: -> (out_hashes, out_abunds, out_offsets), sized by a count-only
+        call.  Device tensors (mem=KT_MEM_DEVICE): the outputs and max_out are given, the number of hashes is returned."""
+        n_rows, n_groups = len(row_offsets) - 1, len(group_offsets) - 1
+        n = C.c_uint64()
+
+        def call(oh, oa, room, oo):
+            check(_lib.lib().kt_scaled_merge(self._h, _ptr(hashes), _ptr(abunds), _ptr(row_offsets), n_rows, _ptr(group_offsets),
+                                             n_groups, _ptr(oh), _ptr(oa), int(room), _ptr(oo), C.byref(n), mem))
+            return n.value
+
+        if mem != KT_MEM_HOST:
+            return call(out_hashes, out_abunds, max_out, out_offsets)
+        hashes = np.ascontiguousarray(hashes, np.uint64)
+        abunds = None if abunds is None else np.ascontiguousarray(abunds, np.uint32)
+        row_offsets = np.ascontiguousarray(row_offsets, np.uint64)
+        group_offsets = np.ascontiguousarray(group_offsets, np.uint64)
+        out_offsets = np.zeros(n_groups + 1, np.uint64)
+        n_out = call(None, None, 0, out_offsets) if n_groups else 0
+        out_hashes, out_abunds = np.zeros(n_out, np.uint64), np.zeros(n_out, np.uint32)
+        if n_out:
+            call(out_hashes, out_abunds, n_out, out_offsets)
+        return out_hashes, out_abunds, out_offsets
+
+    def scaled_pairs(self, a_hashes, a_offsets, n_a, b_hashes, b_offsets, n_b, shared, mem=KT_MEM_DEVICE):
+        """shared (u32, n_a x n_b) = the hashes every (row of a, row of b) has in common (kt_scaled_pairs); b may be a itself"""
+        check(_lib.lib().kt_scaled_pairs(self._h, _ptr(a_hashes), _ptr(a_offsets), int(n_a), _ptr(b_hashes), _ptr(b_offsets),
+                                         int(n_b), _ptr(shared), mem))
+
+    def scaled_pairs_host(self, a_hashes, a_offsets, b_hashes=None, b_offsets=None):
+        """-> shared u32[n_a, n_b]; without b: a against itself"""
+        a_hashes = np.ascontiguousarray(a_hashes, np.uint64)
+        a_offsets = np.ascontiguousarray(a_offsets, np.uint64)
+        if b_hashes is None:
+            b_hashes, b_offsets = a_hashes, a_offsets
+        else:
+            b_hashes = np.ascontiguousarray(b_hashes, np.uint64)
+            b_offsets = np.ascontiguousarray(b_offsets, np.uint64)
+        shared = np.zeros((len(a_offsets) - 1, len(b_offsets) - 1), np.uint32)
+        self.scaled_pairs(a_hashes, a_offsets, len(a_offsets) - 1, b_hashes, b_offsets, len(b_offsets) - 1, shared, KT_MEM_HOST)
+        return shared
+
     # -- card: HyperLogLog registers of the distinct canonical k-mers ----------------------------
     def card_add(self, bases, offsets, n_reads, k, registers, p=14, seed=0, n_kmers=None, mem=KT_MEM_DEVICE):
         """registers (u8, 2^p, zeroed once by the caller) are raised by the k-mers of the batch: register
@@ -828,6 +913,30 @@ class Counter:
         """adds the spectrum into `hist` (n_bins u64) and (distinct, occurrences) into `totals` (2 u64, or None)"""
         check(_lib.lib().kt_ctr_spectrum(self._h, _ptr(hist), int(n_bins), _ptr(totals), mem))
         return hist
+
+    def scaled_sketch(self, scaled, min_count=1, max_count=None, seed=0, hashes=None, abunds=None, max_out=0, totals=None,
+                      mem=KT_MEM_HOST):
+        """The scaled sketch of the table's k-mers with min_count <= count <= max_count, the counts as abundances
+        (kt_ctr_scaled; the table is walked in the form it is in and left as it is).  Host (the default): -> (hashes u64,
+        abunds u32, (entries in the count range, their occurrences)), sized by a count-only call.  mem=KT_MEM_DEVICE:
+        hashes / abunds tensors of max_out (None, 0 only counts) and totals (2 u64 or None) are given; returns the number
+        of hashes."""
+        hi = 0xFFFFFFFF if max_count is None else int(max_count)
+        n = C.c_uint64()
+
+        def call(h, a, room, t):
+            check(_lib.lib().kt_ctr_scaled(self._h, int(min_count), hi, int(scaled), int(seed), _ptr(h), _ptr(a), int(room), C.byref(n),
+                                           _ptr(t), mem))
+            return n.value
+
+        if mem != KT_MEM_HOST:
+            return call(hashes, abunds, max_out, totals)
+        tot = np.zeros(2, np.uint64)
+        n_out = call(None, None, 0, tot)
+        hashes, abunds = np.zeros(n_out, np.uint64), np.zeros(n_out, np.uint32)
+        if n_out:
+            call(hashes, abunds, n_out, tot)
+        return hashes, abunds, (int(tot[0]), int(tot[1]))
 
     COMPARE_TOTALS = ("distinct_a", "distinct_b", "shared", "occurrences_a", "occurrences_b", "shared_min")
 
