@@ -180,12 +180,8 @@ __device__ __forceinline__ uint32_t block_excl_scan(const uint32_t *cnt, uint32_
     uint32_t sum = 0;
     for (uint32_t i = 0; i < per; i++)
         if (lo + i < B) sum += cnt[lo + i];
-    uint32_t inc = sum;  // inclusive scan over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += v;
-    }
+    const uint32_t inc = ktd::wave_prefix(sum);
+    // (the step across the waves is not ktd::block_excl_scan: its second barrier here also publishes out[])
     if (lane == 63) tmp[wave] = inc;
     ktd::lds_barrier();
     uint32_t wbase = 0, total = 0;
@@ -736,7 +732,7 @@ __global__ __launch_bounds__(BLOCK) void count_records_kernel(RecordSource src, 
             fresh += st == 2u;
         });
     }
-    for (int o = 32; o > 0; o >>= 1) fresh += __shfl_down(fresh, o, 64);
+    fresh = ktd::wave_sum(fresh);
     if ((threadIdx.x & 63) == 0 && fresh) atomicAdd(reinterpret_cast<unsigned long long *>(distinct), (unsigned long long)fresh);
 }
 
@@ -2591,7 +2587,7 @@ __global__ __launch_bounds__(BUILD_T) __attribute__((amdgpu_num_sgpr(KT_BUILD_SG
         atomicMax(reinterpret_cast<unsigned long long *>(xo.extent), (unsigned long long)xend);
     }
     // the table's distinct counter: one atomic per wave
-    for (int o = 32; o > 0; o >>= 1) placed += __shfl_down(placed, o, 64);
+    placed = ktd::wave_sum(placed);
     if (lane == 0 && placed) atomicAdd(reinterpret_cast<unsigned long long *>(distinct), (unsigned long long)placed);
 }
 
@@ -2641,11 +2637,7 @@ __global__ __launch_bounds__(1024) void ext_scan_kernel(ExtOut xo, uint64_t *__r
             h[u] = i0 + u < nb ? XBLK - xo.fill[i0 + u] : 0u;
             v += h[u];
         }
-        uint64_t inc = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t u = __shfl_up(inc, off, 64);
-            if ((threadIdx.x & 63) >= (uint32_t)off) inc += u;
-        }
+        const uint64_t inc = ktd::wave_prefix(v);
         if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = inc;
         __syncthreads();
         uint64_t base = carry;
@@ -2743,7 +2735,7 @@ __global__ __launch_bounds__(BLOCK) void spill_insert_kernel(const uint64_t *__r
         if (st == 0u) atomicOr(t.flags, 1u);
         fresh += st == 2u;
     }
-    for (int o = 32; o > 0; o >>= 1) fresh += __shfl_down(fresh, o, 64);
+    fresh = ktd::wave_sum(fresh);
     if ((threadIdx.x & 63) == 0 && fresh)
         atomicAdd(reinterpret_cast<unsigned long long *>(distinct), (unsigned long long)fresh);
 }

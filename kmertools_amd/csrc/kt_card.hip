@@ -77,7 +77,7 @@ __global__ __launch_bounds__(BLOCK) void card_kernel(SegArgs a, uint64_t seed, u
     }
 
     // windows: per wave, then once per workgroup
-    for (uint32_t off = WAVE / 2; off; off >>= 1) mine += __shfl_down((unsigned long long)mine, off, WAVE);
+    mine = ktd::wave_sum(mine);
     if ((tid & (WAVE - 1)) == 0 && mine) {
         const uint32_t lo = (uint32_t)mine;
         const uint32_t before = atomicAdd(&wg_kmers[0], lo);

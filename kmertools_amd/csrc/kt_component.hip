@@ -34,11 +34,6 @@ __device__ __forceinline__ uint32_t label(const uint32_t *L, uint64_t u) {
     return __hip_atomic_load(L + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // once: L[u] = u
 __global__ __launch_bounds__(BLOCK) void label_init_kernel(uint32_t *__restrict__ L, uint64_t nu) {
     for (uint64_t u = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; u < nu; u += (uint64_t)gridDim.x * BLOCK) L[u] = (uint32_t)u;
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(BLOCK) void link_source_kernel(Links g, uint32_t *_
         n_bad += is_bad;
         src[x] = is_bad || (f >> 1) == u ? NONE : (uint32_t)u;
     }
-    n_bad = (uint32_t)wave_sum(n_bad);
+    n_bad = (uint32_t)ktd::wave_all_sum<uint64_t>(n_bad);
     if ((threadIdx.x & 63u) == 0 && n_bad) atomicAdd(bad, (unsigned long long)n_bad);
 }
 
@@ -128,7 +123,7 @@ __device__ __forceinline__ void grouped_add(unsigned long long *__restrict__ row
         } else {
 #pragma unroll
             for (int q = 0; q < N; q++) {
-                const uint64_t s = wave_sum(mine ? v[q] : 0);
+                const uint64_t s = ktd::wave_all_sum<uint64_t>(mine ? v[q] : 0);
                 if (lane == (uint32_t)leader && s) atomicAdd(rows + (uint64_t)cl * STRIDE + q, (unsigned long long)s);
             }
         }
@@ -174,12 +169,8 @@ __global__ __launch_bounds__(BLOCK) void component_tally_kernel(const unsigned l
         most_u = nu > most_u ? nu : most_u;
         most_n = nn > most_n ? nn : most_n;
     }
-    single = wave_sum(single);
-    for (int d = 32; d; d >>= 1) {
-        const uint64_t a = __shfl_xor(most_u, d, 64), b = __shfl_xor(most_n, d, 64);
-        most_u = a > most_u ? a : most_u;
-        most_n = b > most_n ? b : most_n;
-    }
+    single = ktd::wave_all_sum<uint64_t>(single);
+    most_u = ktd::wave_all_max(most_u), most_n = ktd::wave_all_max(most_n);
     if ((threadIdx.x & 63u) == 0) {
         if (single) atomicAdd(tally + 1, (unsigned long long)single);
         if (most_u) atomicMax(tally + 2, (unsigned long long)most_u);
@@ -220,7 +211,7 @@ __global__ __launch_bounds__(BLOCK) void run_hits_kernel(ReadArgs a, unsigned lo
         }
         if (comp_hits) grouped_add<1, 1>(comp_hits, c, v);
     }
-    n_bad = (uint32_t)wave_sum(n_bad);
+    n_bad = (uint32_t)ktd::wave_all_sum<uint64_t>(n_bad);
     if ((threadIdx.x & 63u) == 0 && n_bad) atomicAdd(tally + 3, (unsigned long long)n_bad);
 }
 
@@ -262,11 +253,7 @@ __global__ __launch_bounds__(BLOCK) void read_components_kernel(ReadArgs a, uint
             uint32_t my_c = NONE;
             bool my_mixed = false;
             walk_runs(a, rlo, rhi, lane, 64, &my_at, &my_c, &my_mixed);
-            uint64_t first_at = my_at;  // the read's first good run: the smallest index any lane met
-            for (int d = 32; d; d >>= 1) {
-                const uint64_t o = __shfl_xor(first_at, d, 64);
-                first_at = o < first_at ? o : first_at;
-            }
+            const uint64_t first_at = ktd::wave_all_min(my_at);  // the read's first good run: the smallest index any lane met
             const uint64_t holder = __ballot(my_at == first_at && my_c != NONE);
             uint32_t c0 = NONE;
             bool any_mixed = false;
@@ -291,7 +278,7 @@ __global__ __launch_bounds__(BLOCK) void read_components_kernel(ReadArgs a, uint
     const uint32_t sums[3] = {n_with, n_without, n_mixed};
 #pragma unroll
     for (int q = 0; q < 3; q++) {
-        const uint64_t s = wave_sum(sums[q]);
+        const uint64_t s = ktd::wave_all_sum<uint64_t>(sums[q]);
         if (lane == 0 && s) atomicAdd(tally + q, (unsigned long long)s);
     }
 }
@@ -356,7 +343,7 @@ extern "C" int kt_unitig_components(kt_ctx *ctx, const uint64_t *link_offsets, c
         }
     }
     // working arrays: the labels, every link's source unitig, the scan's tiles, the tally and the rounds' changed word
-    const uint64_t n_tiles = (nu + SCAN_TILE - 1) / SCAN_TILE;
+    const uint64_t n_tiles = scan2_tiles(nu);
     uint32_t *L = nullptr, *src = nullptr, *changed = nullptr;
     uint64_t *tiles = nullptr, *d_tally = nullptr;
     if (int rc = carve(call, kt::AUX0, &tiles, 2 * n_tiles, &d_tally, (uint64_t)8, &changed, (uint64_t)4, &L, nu, &src, n_links)) return rc;
@@ -385,11 +372,7 @@ extern "C" int kt_unitig_components(kt_ctx *ctx, const uint64_t *link_offsets, c
 
     // the numbering: the roots counted, then - there being room - numbered, and every unitig given its root's number
     RootScan scan{L, nullptr};
-    const dim3 T((uint32_t)n_tiles), B(SCAN_BLOCK);
-    hipLaunchKernelGGL(scan2_tile_sum_kernel<RootScan>, T, B, 0, st, scan, nu, tiles);
-    hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, st, tiles, n_tiles, (unsigned long long *)&d_tally[6],
-                       (unsigned long long *)&d_tally[7]);
-    KT_HIP(hipGetLastError());
+    if (int rc = scan2_sums(st, scan, nu, tiles, &d_tally[6], &d_tally[7])) return rc;
     uint64_t nc = 0;
     KT_HIP(hipMemcpyAsync(&nc, &d_tally[6], 8, hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
@@ -399,8 +382,7 @@ extern "C" int kt_unitig_components(kt_ctx *ctx, const uint64_t *link_offsets, c
     uint32_t *d_comp = nullptr;
     if (int rc = call.out(kt::AUX1, component, nu, &d_comp)) return rc;
     scan.component = d_comp;
-    hipLaunchKernelGGL(scan2_apply_kernel<RootScan>, T, B, 0, st, scan, nu, (const uint64_t *)tiles);
-    KT_HIP(hipGetLastError());
+    if (int rc = scan2_apply(st, scan, nu, tiles)) return rc;
     if (int rc = launch(number_kernel, grid_of(ctx, nu), dim3(BLOCK), 0, st, (const uint32_t *)L, d_comp, nu)) return rc;
 
     // the aggregates: in the caller's rows, or - a host call, or a tally with no rows to read the maxima from - in OUT

@@ -36,7 +36,7 @@ static_assert(BLOCK == kttab::BLOCK, "the tile reservation's workgroup");
 
 // new keys claimed by the thread -> the table's distinct counter: one atomic per wave, at the end of the kernel
 __device__ __forceinline__ void publish_fresh(uint32_t fresh, uint64_t *distinct) {
-    for (int o = 32; o > 0; o >>= 1) fresh += __shfl_down(fresh, o, 64);
+    fresh = ktd::wave_sum(fresh);
     if ((threadIdx.x & 63) == 0 && fresh)
         atomicAdd(reinterpret_cast<unsigned long long *>(distinct), (unsigned long long)fresh);
 }
@@ -321,16 +321,12 @@ __global__ __launch_bounds__(BLOCK) void spectrum_kernel(TableView tv, uint64_t 
     // the register tallies: one wave reduction per bin, lane 0 adds the wave's sums to the LDS bins
 #pragma unroll
     for (uint32_t j = 0; j < SPEC_REG; j++) {
-        uint32_t s = t.reg[j];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        const uint32_t s = ktd::wave_sum(t.reg[j]);
         if (lane == 0 && s) atomicAdd(&lds[j + 1u], s);  // (j + 1 <= top < lds_bins whenever s != 0)
     }
     if (totals) {
         uint64_t n_e = t.n, occ = t.occ;
-        for (int o = 32; o > 0; o >>= 1) {
-            n_e += __shfl_down(n_e, o, 64);
-            occ += __shfl_down(occ, o, 64);
-        }
+        ktd::wave_sums(n_e, occ);
         if (lane == 0 && n_e) {
             atomicAdd(reinterpret_cast<unsigned long long *>(totals), (unsigned long long)n_e);
             atomicAdd(reinterpret_cast<unsigned long long *>(totals + 1), (unsigned long long)occ);
@@ -405,18 +401,12 @@ __global__ __launch_bounds__(BLOCK) void compare_kernel(TableView a, CmpArgs c) 
     // is a cell of the matrix, and rows <= 4, columns <= 1 of the matrix lie inside the tile)
 #pragma unroll
     for (uint32_t j = 0; j < CMP_REG; j++) {
-        uint32_t s = t.reg[j];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        const uint32_t s = ktd::wave_sum(t.reg[j]);
         if (lane == 0 && s) atomicAdd(&lds[(j / 2u + 1u) * c.tile_cols + (j & 1u)], s);
     }
     {
         uint64_t n_e = t.n, occ = t.occ, sh = t.shared, smin = t.smin;
-        for (int o = 32; o > 0; o >>= 1) {
-            n_e += __shfl_down(n_e, o, 64);
-            occ += __shfl_down(occ, o, 64);
-            sh += __shfl_down(sh, o, 64);
-            smin += __shfl_down(smin, o, 64);
-        }
+        ktd::wave_sums(n_e, occ, sh, smin);
         if (lane == 0 && n_e) {
             atomicAdd(reinterpret_cast<unsigned long long *>(c.totals), (unsigned long long)n_e);
             atomicAdd(reinterpret_cast<unsigned long long *>(c.totals + 1), (unsigned long long)occ);
@@ -688,12 +678,9 @@ __global__ __launch_bounds__(BLOCK) void graph_kernel(TableView w, GraphArgs g) 
     // the register tallies: one wave reduction each, lane 0 adds the wave's sums to the workgroup's
     {
         uint64_t v[GRAPH_SUMS] = {t.n, t.occ, t.deg, t.ends, t.isolated, t.tips, t.branching};
-        uint32_t c11 = t.c11;
-        for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
-            for (uint32_t j = 0; j < GRAPH_SUMS; j++) v[j] += __shfl_down(v[j], o, 64);
-            c11 += __shfl_down(c11, o, 64);
-        }
+        for (uint32_t j = 0; j < GRAPH_SUMS; j++) v[j] = ktd::wave_sum(v[j]);
+        const uint32_t c11 = ktd::wave_sum(t.c11);
         if (lane == 0 && v[0]) {
 #pragma unroll
             for (uint32_t j = 0; j < GRAPH_SUMS; j++)
@@ -794,10 +781,8 @@ __device__ __forceinline__ void het_scan(const HetArgs &h, uint64_t F, HetScan &
 // one global atomic per non-zero cell.  Every thread of the workgroup must be here.
 template <uint32_t M>
 __device__ __forceinline__ void het_add_sums(uint64_t (&v)[M], unsigned long long *sums, uint64_t *cells) {
-    for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
-        for (uint32_t j = 0; j < M; j++) v[j] += __shfl_down(v[j], o, 64);
-    }
+    for (uint32_t j = 0; j < M; j++) v[j] = ktd::wave_sum(v[j]);
     if ((threadIdx.x & 63u) == 0) {
 #pragma unroll
         for (uint32_t j = 0; j < M; j++)

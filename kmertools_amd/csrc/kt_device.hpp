@@ -162,6 +162,110 @@ __device__ __forceinline__ double quot_f64(double c, double d, double y) {
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 
+// ---- reductions and scans over the wave and the workgroup, by shuffles (the DPP scan above keeps the users it has) --------
+// what two values combine to: op(mine, other)
+struct op_sum {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct op_min {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; }
+};
+struct op_max {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; }
+};
+
+// lane 0 gets the wave's sum / maximum (the other lanes a partial one)
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+    for (int o = 32; o > 0; o >>= 1) v = op(v, (T)__shfl_down(v, o, 64));
+    return v;
+}
+template <class T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, op_sum()); }
+template <class T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, op_max()); }
+// several sums in place, step by step together: the shuffles of a step are in flight at once
+template <class... T>
+__device__ __forceinline__ void wave_sums(T &...v) {
+    for (int o = 32; o > 0; o >>= 1) ((v += (T)__shfl_down(v, o, 64)), ...);
+}
+
+// every lane gets the wave's sum / minimum / maximum
+template <class T, class Op>
+__device__ __forceinline__ T wave_all_reduce(T v, Op op) {
+    for (int d = 32; d > 0; d >>= 1) v = op(v, (T)__shfl_xor(v, d, 64));
+    return v;
+}
+template <class T> __device__ __forceinline__ T wave_all_sum(T v) { return wave_all_reduce(v, op_sum()); }
+template <class T> __device__ __forceinline__ T wave_all_min(T v) { return wave_all_reduce(v, op_min()); }
+template <class T> __device__ __forceinline__ T wave_all_max(T v) { return wave_all_reduce(v, op_max()); }
+
+// two sums that travel together (kt_scan.hpp scans two at once)
+struct sum2 {
+    uint64_t a, b;
+};
+__device__ __forceinline__ sum2 operator+(sum2 x, sum2 y) { return {x.a + y.a, x.b + y.b}; }
+__device__ __forceinline__ sum2 operator-(sum2 x, sum2 y) { return {x.a - y.a, x.b - y.b}; }
+
+// the value of the lane `off` below (the lanes < off: their own)
+template <class T> __device__ __forceinline__ T lane_up(T v, int off) { return (T)__shfl_up(v, off, 64); }
+__device__ __forceinline__ sum2 lane_up(sum2 v, int off) { return {__shfl_up(v.a, off, 64), __shfl_up(v.b, off, 64)}; }
+
+// inclusive prefix over the lanes of the wave: lane l gets op over the lanes 0..l (the sum, unless told otherwise).
+// (No unroll pragma here or on the reductions above: some of the loops these replaced had one and some had none, the
+// compiler unrolls the six steps either way, and the kernels came out the same with it and without - NOTES.md.)
+template <class T, class Op = op_sum>
+__device__ __forceinline__ T wave_prefix(T v, Op op = Op()) {
+    const uint32_t lane = lane_id();
+    for (int off = 1; off < 64; off <<= 1) {
+        const T u = lane_up(v, off);
+        if (lane >= (uint32_t)off) v = op(v, u);
+    }
+    return v;
+}
+
+// exclusive prefix sum of v over the workgroup's 64 * WAVES threads (the inclusive one is this + v), *total = the sum
+// (there is a form without it); wsum: WAVES values in LDS.  Two barriers, the second behind the last read of wsum: the caller may rewrite it,
+// or call again, at once.  The barriers are lds_barrier, which does not wait for global memory traffic: the kernels that
+// synchronise their scan with __syncthreads() (kt_min.hip, kt_table.hip's and kt_bulk.hip's tile scans) keep their own
+// step across the waves and their own barrier, and take only wave_prefix from here.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_excl_scan(T v, T *wsum, T *total) {
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    const T inc = wave_prefix(v);
+    if (lane == 63u) wsum[wave] = inc;
+    lds_barrier();
+    T pre = T(), tot = T();
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
+        const T x = wsum[w];
+        if (w < wave) pre = pre + x;
+        tot = tot + x;
+    }
+    lds_barrier();
+    *total = tot;
+    return pre + inc - v;
+}
+template <int WAVES, class T>
+__device__ __forceinline__ T block_excl_scan(T v, T *wsum) {
+    T total;
+    return block_excl_scan<WAVES>(v, wsum, &total);
+}
+
+// the number of elements of a[0, n) (ascending) below x
+template <class P, class I>
+__device__ __forceinline__ I lower_bound(P a, I n, uint64_t x) {
+    I lo = 0, len = n;
+    while (len) {
+        const I half = len >> 1;
+        if (a[lo + half] < x) {
+            lo += half + 1;
+            len -= half + 1;
+        } else {
+            len = half;
+        }
+    }
+    return lo;
+}
+
 // a * b + c with 32-bit factors and a 64-bit sum: one v_mad_u64_u32 (written with 64-bit operands the compiler makes two)
 __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint32_t c) {
     return (uint64_t)a * (uint64_t)b + (uint64_t)c;

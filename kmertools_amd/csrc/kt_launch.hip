@@ -23,6 +23,16 @@ uint32_t grid_for(const kt_ctx *ctx, uint64_t work_items, uint32_t per_cu) {
     return (uint32_t)g;
 }
 
+dim3 pairs_grid(const kt_ctx *ctx, uint64_t n_a, uint64_t n_b, uint32_t b_per_wg) {
+    const uint64_t want = (uint64_t)ctx->n_cu * 8;
+    const uint64_t gx = n_a < want ? n_a : want;
+    uint64_t gy = want / gx ? want / gx : 1;
+    const uint64_t b_units = (n_b + b_per_wg - 1) / b_per_wg;
+    if (gy > b_units) gy = b_units;
+    if (gy > 65535) gy = 65535;
+    return dim3((uint32_t)gx, (uint32_t)gy);
+}
+
 int make_seg_args(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                   uint64_t total_bases, int k, ktseg::SegArgs *out) {
     const uint64_t n_seg = (total_bases + ktseg::SEG - 1) / ktseg::SEG;

@@ -14,6 +14,9 @@ namespace ktl {
 
 // min(work_items, n_cu * per_cu) workgroups, at least 1
 uint32_t grid_for(const kt_ctx *ctx, uint64_t work_items, uint32_t per_cu);
+// the grid of an all-pairs kernel (n_a > 0): a row of A per workgroup in x, the rows of B dealt to the waves of y, b_per_wg at
+// a time - as many in y as fill the device when A is small
+dim3 pairs_grid(const kt_ctx *ctx, uint64_t n_a, uint64_t n_b, uint32_t b_per_wg);
 // SegArgs for a device-resident CSR batch (launches seg_index_kernel into the context's scratch AUX0)
 int make_seg_args(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                   uint64_t total_bases, int k, ktseg::SegArgs *out);

@@ -110,11 +110,7 @@ __global__ __launch_bounds__(BLOCK) void gran_break_kernel(const uint8_t *__rest
         if (o >= p0 + GRAN) break;
         if (o + 1 > mine) mine = o + 1;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(mine, off, 64);
-        mine = o > mine ? o : mine;
-    }
+    mine = ktd::wave_max(mine);
     if (lane == 0) lastbreak[g] = mine;
 }
 
@@ -128,12 +124,7 @@ __device__ __forceinline__ uint64_t comb(uint64_t a, uint64_t b) {
 template <bool MAX>
 __device__ uint64_t block_scan1024(uint64_t v, uint64_t *total, uint64_t *tmp /*16*/) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc = comb<MAX>(inc, o);
-    }
+    const uint64_t inc = ktd::wave_prefix(v, [](uint64_t a, uint64_t b) { return comb<MAX>(a, b); });
     if (lane == 63) tmp[wave] = inc;
     __syncthreads();
     uint64_t base = 0, tot = 0;
@@ -143,7 +134,7 @@ __device__ uint64_t block_scan1024(uint64_t v, uint64_t *total, uint64_t *tmp /*
     }
     __syncthreads();
     if (total) *total = tot;
-    const uint64_t prev = __shfl_up(inc, 1, 64);
+    const uint64_t prev = ktd::lane_up(inc, 1);
     return comb<MAX>(base, lane ? prev : 0);
 }
 
@@ -223,29 +214,19 @@ struct TileShared {
 // exclusive max-scan of one value per thread over the 256-thread workgroup (identity: lowest)
 __device__ __forceinline__ int32_t block_max_excl(int32_t v, int32_t lowest, int32_t *tmp) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    int32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off && o > inc) inc = o;
-    }
+    const int32_t inc = ktd::wave_prefix(v, ktd::op_max());
     if (lane == 63) tmp[wave] = inc;
     __syncthreads();
     int32_t base = lowest;
     for (uint32_t w = 0; w < wave; w++) base = base > tmp[w] ? base : tmp[w];
-    const int32_t prev = __shfl_up(inc, 1, 64);
+    const int32_t prev = ktd::lane_up(inc, 1);
     const int32_t ex = lane ? prev : lowest;
     return base > ex ? base : ex;
 }
 
 __device__ __forceinline__ uint32_t block_sum_excl(uint32_t v, uint32_t *tmp, uint32_t *total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
+    const uint32_t inc = ktd::wave_prefix(v);
     if (lane == 63) tmp[wave] = inc;
     __syncthreads();
     uint32_t base = 0, tot = 0;
@@ -547,8 +528,7 @@ __global__ __launch_bounds__(BLOCK) void min_tile_kernel(MinArgs a, uint64_t *__
             const uint64_t is_prefix = __ballot((st & ST_MASK) == ST_PREFIX);
             const uint32_t first = is_prefix ? (uint32_t)__builtin_ctzll(is_prefix) : 64u;  // nearest tile with a prefix
             uint64_t part = tid <= first ? (uint64_t)(st & ~ST_MASK) : 0;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+            part = ktd::wave_sum(part);
             sum += __shfl(part, 0, 64);
             if (is_prefix) break;
             j0 -= 64;

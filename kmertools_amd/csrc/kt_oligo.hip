@@ -1143,11 +1143,7 @@ __global__ __launch_bounds__(256) void quotient_check_kernel(uint32_t d_lo, uint
             n++;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        bad += __shfl_down(bad, o, 64);
-        sum += __shfl_down(sum, o, 64);
-        n += __shfl_down(n, o, 64);
-    }
+    ktd::wave_sums(bad, sum, n);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(reinterpret_cast<unsigned long long *>(out), (unsigned long long)n);
         atomicAdd(reinterpret_cast<unsigned long long *>(out + 1), (unsigned long long)bad);

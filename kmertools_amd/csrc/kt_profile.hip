@@ -58,22 +58,6 @@ struct LongAcc {
     uint32_t prefix;  // the median's top 8 * (passes done) bits
 };
 
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-    for (int d = 32; d; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-    for (int d = 32; d; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-    for (int d = 32; d; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(BLOCK) void classify_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, Classes *cls,
                                                          uint64_t *__restrict__ list) {
     const uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -141,7 +125,7 @@ __global__ __launch_bounds__(BLOCK) void stats_wave_kernel(const uint32_t *__res
 #pragma unroll
             for (uint32_t e = 0; e < SHORT_PER_LANE; e++) take(x[e]);
         }
-        mx = wave_max(mx);
+        mx = ktd::wave_all_max(mx);
         uint32_t med = 0;
         if (o.median && n && mx) {
             // one bit per round from the top bit of the maximum down: entries that match the prefix and have a 0 next
@@ -162,8 +146,8 @@ __global__ __launch_bounds__(BLOCK) void stats_wave_kernel(const uint32_t *__res
             }
             med = prefix;
         }
-        if (o.min_count) mn = wave_min(mn);
-        if (o.sum) sum = wave_sum(sum);
+        if (o.min_count) mn = ktd::wave_all_min(mn);
+        if (o.sum) sum = ktd::wave_all_sum<uint64_t>(sum);
         if (lane == 0) {
             if (o.n_kmers) o.n_kmers[i] = n;
             if (o.n_present) o.n_present[i] = pres;
@@ -238,12 +222,12 @@ __global__ __launch_bounds__(BLOCK) void long_hist_kernel(const uint32_t *__rest
             __syncthreads();
             if (const uint32_t v = h[tid]) atomicAdd(&hist[(uint64_t)j * 256 + tid], v);
             if (PASS == 0) {
-                n = (uint32_t)wave_sum(n);
+                n = (uint32_t)ktd::wave_all_sum<uint64_t>(n);
                 if (n) {  // (wave-uniform)
-                    pres = (uint32_t)wave_sum(pres);
-                    mn = wave_min(mn);
-                    mx = wave_max(mx);
-                    sum = wave_sum(sum);
+                    pres = (uint32_t)ktd::wave_all_sum<uint64_t>(pres);
+                    mn = ktd::wave_all_min(mn);
+                    mx = ktd::wave_all_max(mx);
+                    sum = ktd::wave_all_sum<uint64_t>(sum);
                     if (lane == 0) {
                         atomicAdd(&acc[j].n, n);
                         if (pres) atomicAdd(&acc[j].present, pres);

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(BLOCK) void select_count_kernel(SegArgs a, uint64_t
         ktseg::for_each_kmer(a, g, sm, [&](uint64_t f, uint64_t r, uint64_t) {
             mine += ktd::mix64((f < r ? f : r) ^ seed) <= max_hash ? 1u : 0u;
         });
-        for (uint32_t off = WAVE / 2; off; off >>= 1) mine += __shfl_down(mine, off, WAVE);
+        mine = ktd::wave_sum(mine);
         if ((tid & (WAVE - 1)) == 0) wsum[tid / WAVE] = mine;
         ktd::lds_barrier();
         if (tid == 0) {
@@ -75,24 +75,6 @@ struct SegScan {
     __device__ __forceinline__ void total() const {}
 };
 
-// exclusive prefix sum of v over the workgroup's 256 threads (two barriers)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum) {
-    const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < (int)WAVE; off <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)inc, off, WAVE);
-        if (lane >= (uint32_t)off) inc += u;
-    }
-    if (lane == WAVE - 1) wsum[wave] = inc;
-    ktd::lds_barrier();
-    uint32_t pre = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < WAVES; w++) pre += w < wave ? wsum[w] : 0u;
-    ktd::lds_barrier();  // (wsum is rewritten by the next call)
-    return pre + inc - v;
-}
-
 // n_el: the room of hashes / rows (the scan's total; no store goes past it); n_kmers: null or zeroed
 __global__ __launch_bounds__(BLOCK) void select_emit_kernel(SegArgs a, uint64_t seed, uint64_t max_hash, const uint64_t *__restrict__ seg_base,
                                                             uint64_t n_el, uint64_t *__restrict__ hashes, uint64_t *__restrict__ rows,
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(BLOCK) void select_emit_kernel(SegArgs a, uint64_t 
             keys[j] = ktd::mix64(keys[j] ^ seed);
             km |= (((ok >> j) & 1u) && keys[j] <= max_hash ? 1u : 0u) << j;
         }
-        const uint64_t at = seg_base[g] + block_excl_scan((uint32_t)__popc(km), wsum);
+        const uint64_t at = seg_base[g] + ktd::block_excl_scan<WAVES>((uint32_t)__popc(km), wsum);
 #pragma unroll
         for (uint32_t j = 0; j < ktseg::PER_THREAD; j++) {
             if (!((km >> j) & 1u)) continue;
@@ -204,12 +186,7 @@ __global__ __launch_bounds__(BLOCK) void head_abund_kernel(const uint64_t *__res
 __global__ __launch_bounds__(BLOCK) void row_offsets_kernel(const uint64_t *__restrict__ rows, const uint32_t *__restrict__ pos, uint64_t n,
                                                             uint64_t n_heads, uint64_t n_rows, uint64_t *__restrict__ row_offsets) {
     for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r <= n_rows; r += (uint64_t)gridDim.x * BLOCK) {
-        uint64_t lo = 0, len = n;
-        while (len) {
-            const uint64_t half = len >> 1;
-            if (rows[lo + half] < r) lo += half + 1, len -= half + 1;
-            else len = half;
-        }
+        const uint64_t lo = ktd::lower_bound(rows, n, r);
         row_offsets[r] = lo < n ? pos[lo] : n_heads;
     }
 }
@@ -243,22 +220,6 @@ __global__ __launch_bounds__(BLOCK) void elem_groups_kernel(const uint64_t *__re
 
 // ---- pairs --------------------------------------------------------------------------------------------------------------------
 
-// the number of elements of a[0, n) (strictly ascending) below x
-template <class P>
-__device__ __forceinline__ uint32_t lower_bound(P a, uint32_t n, uint64_t x) {
-    uint32_t lo = 0, len = n;
-    while (len) {
-        const uint32_t half = len >> 1;
-        if (a[lo + half] < x) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
-
 // *max_len = the longest of the n rows of `offsets`
 __global__ __launch_bounds__(BLOCK) void max_row_kernel(const uint64_t *__restrict__ offsets, uint64_t n, uint64_t *max_len) {
     uint64_t m = 0;
@@ -289,8 +250,8 @@ __global__ __launch_bounds__(BLOCK) void scaled_pairs_kernel(const uint64_t *__r
                 uint32_t s = 0, e1 = tn ? nb : 0u;
                 if (tiles > 1 && e1) {  // what of B's row lies between the tile's ends
                     const uint64_t first = arow[0], last = arow[tn - 1];
-                    s = lower_bound(brow, nb, first);
-                    e1 = lower_bound(brow, nb, last);
+                    s = ktd::lower_bound(brow, nb, first);
+                    e1 = ktd::lower_bound(brow, nb, last);
                     if (e1 < nb && brow[e1] == last) e1++;
                 }
                 uint32_t cnt = 0;
@@ -299,7 +260,7 @@ __global__ __launch_bounds__(BLOCK) void scaled_pairs_kernel(const uint64_t *__r
                     bool m = false;
                     if (e < e1) {
                         const uint64_t y = brow[e];
-                        const uint32_t lb = lower_bound(arow, tn, y);
+                        const uint32_t lb = ktd::lower_bound(arow, tn, y);
                         m = lb < tn && arow[lb] == y;
                     }
                     cnt += (uint32_t)__popcll(__ballot(m));
@@ -313,25 +274,6 @@ __global__ __launch_bounds__(BLOCK) void scaled_pairs_kernel(const uint64_t *__r
         }
     }
 }
-
-template <class F>
-int run_scan_sums(kt_ctx *ctx, const F &f, uint64_t n, uint64_t *tiles, uint64_t *sums) {
-    const dim3 T((uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE)), B(SCAN_BLOCK);
-    hipLaunchKernelGGL(scan2_tile_sum_kernel<F>, T, B, 0, ctx->stream, f, n, tiles);
-    hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, ctx->stream, tiles, (uint64_t)T.x, (unsigned long long *)sums,
-                       (unsigned long long *)sums + 1);
-    KT_HIP(hipGetLastError());
-    return KT_OK;
-}
-template <class F>
-int run_scan_apply(kt_ctx *ctx, const F &f, uint64_t n, const uint64_t *tiles) {
-    const dim3 T((uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE)), B(SCAN_BLOCK);
-    hipLaunchKernelGGL(scan2_apply_kernel<F>, T, B, 0, ctx->stream, f, n, tiles);
-    KT_HIP(hipGetLastError());
-    return KT_OK;
-}
-
-uint64_t scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
 dim3 flat_grid(const kt_ctx *ctx, uint64_t n) { return dim3(ktl::grid_for(ctx, (n + BLOCK - 1) / BLOCK, 8)); }
 
@@ -359,7 +301,7 @@ int kt::scaled_finish(kt_ctx *ctx, const char *who, const ScaledElems &e, const 
         uint8_t *b = nullptr;
         auto parts = [&](uint8_t *at) {
             return carve_parts<16>(at, &perm, n, &rows2, multi ? n : 0, &keys0, multi ? n : 0, &pre, e.abunds ? n : 0, &pos, multi ? n : 0,
-                                   &out_h, n, &out_a, n, &bstart, n + 1, &roff, e.n_rows + 1, &tiles, 2 * scan_tiles(n) + 2, &sums,
+                                   &out_h, n, &out_a, n, &bstart, n + 1, &roff, e.n_rows + 1, &tiles, 2 * scan2_tiles(n) + 2, &sums,
                                    (uint64_t)4);
         };
         if (int rc = ctx->claim(kt::AUX2, parts(nullptr), who, &b)) return rc;
@@ -386,11 +328,11 @@ int kt::scaled_finish(kt_ctx *ctx, const char *who, const ScaledElems &e, const 
         KT_HIP(hipGetLastError());
     }
     if (e.abunds)
-        if (int rc = run_scan_sums(ctx, AbundScan{e.abunds, perm, pre}, n, tiles, sums + 2)) return rc;
+        if (int rc = scan2_sums(ctx->stream, AbundScan{e.abunds, perm, pre}, n, tiles, sums + 2, sums + 3)) return rc;
     if (e.abunds)
-        if (int rc = run_scan_apply(ctx, AbundScan{e.abunds, perm, pre}, n, tiles)) return rc;
+        if (int rc = scan2_apply(ctx->stream, AbundScan{e.abunds, perm, pre}, n, tiles)) return rc;
     HeadScan hs{e.keys, multi ? rows2 : nullptr, e.abunds ? pre : nullptr, sums + 2, n, 0, nullptr, nullptr, nullptr};
-    if (int rc = run_scan_sums(ctx, hs, n, tiles, sums)) return rc;
+    if (int rc = scan2_sums(ctx->stream, hs, n, tiles, sums, sums + 1)) return rc;
     uint64_t n_heads = 0;
     KT_HIP(hipMemcpyAsync(&n_heads, sums, 8, hipMemcpyDeviceToHost, ctx->stream));
     KT_HIP(hipStreamSynchronize(ctx->stream));
@@ -400,7 +342,7 @@ int kt::scaled_finish(kt_ctx *ctx, const char *who, const ScaledElems &e, const 
     hs.pos = multi ? pos : nullptr;
     if (emit) hs.out_h = out_h, hs.bstart = bstart;
     if (emit || multi)
-        if (int rc = run_scan_apply(ctx, hs, n, tiles)) return rc;
+        if (int rc = scan2_apply(ctx->stream, hs, n, tiles)) return rc;
     if (emit && o.abunds) {
         hipLaunchKernelGGL(head_abund_kernel, flat_grid(ctx, n_heads), block, 0, ctx->stream, (const uint64_t *)bstart, n_heads, out_a);
         KT_HIP(hipGetLastError());
@@ -457,13 +399,13 @@ extern "C" int kt_scaled_batch(kt_ctx *ctx, const uint8_t *bases, const uint64_t
         if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, k, &a)) return rc;
         uint32_t *seg_cnt = nullptr;
         uint64_t *tiles = nullptr, *sums = nullptr;
-        if (int rc = carve(call, kt::AUX2, &seg_base, a.n_seg, &seg_cnt, a.n_seg, &tiles, 2 * scan_tiles(a.n_seg) + 2, &sums, (uint64_t)2))
+        if (int rc = carve(call, kt::AUX2, &seg_base, a.n_seg, &seg_cnt, a.n_seg, &tiles, 2 * scan2_tiles(a.n_seg) + 2, &sums, (uint64_t)2))
             return rc;
         if (int rc = launch(select_count_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, seed, max_hash, seg_cnt))
             return rc;
         const SegScan scan{seg_cnt, seg_base};
-        if (int rc = run_scan_sums(ctx, scan, a.n_seg, tiles, sums)) return rc;
-        if (int rc = run_scan_apply(ctx, scan, a.n_seg, tiles)) return rc;
+        if (int rc = scan2_sums(ctx->stream, scan, a.n_seg, tiles, sums, sums + 1)) return rc;
+        if (int rc = scan2_apply(ctx->stream, scan, a.n_seg, tiles)) return rc;
         KT_HIP(hipMemcpyAsync(&n_el, sums, 8, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
         if (n_el >= (1ull << 32)) return call.fail("2^32 kept windows or more in one batch (give it in pieces and merge)");
@@ -599,14 +541,7 @@ extern "C" int kt_scaled_pairs(kt_ctx *ctx, const uint64_t *a_hashes, const uint
         if (max_len >= (1ull << 32)) return call.fail(long_row);
         if (max_len && (!a_hashes || !b_hashes)) return call.fail("null buffer");
     }
-    // a row of A per workgroup, the rows of B dealt to blockIdx.y's waves: enough of them to fill the device when A is small
-    const uint64_t want = (uint64_t)ctx->n_cu * 8;
-    const uint64_t gx = n_a < want ? n_a : want;
-    uint64_t gy = want / gx ? want / gx : 1;
-    const uint64_t b_units = (n_b + WAVES - 1) / WAVES;
-    if (gy > b_units) gy = b_units;
-    if (gy > 65535) gy = 65535;
-    if (int rc = launch(scaled_pairs_kernel, dim3((uint32_t)gx, (uint32_t)gy), dim3(BLOCK), 0, ctx->stream, d_a, d_ao, n_a, d_b, d_bo, n_b, d_sh))
+    if (int rc = launch(scaled_pairs_kernel, ktl::pairs_grid(ctx, n_a, n_b, WAVES), dim3(BLOCK), 0, ctx->stream, d_a, d_ao, n_a, d_b, d_bo, n_b, d_sh))
         return rc;
     call.back(shared, (const uint32_t *)d_sh, cells);
     return call.finish();

@@ -400,7 +400,7 @@ __global__ __launch_bounds__(BLOCK) void pack_pending_kernel(uint64_t *__restric
             mine++;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+    mine = ktd::wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(reinterpret_cast<unsigned long long *>(left), (unsigned long long)mine);
 }
 

@@ -63,45 +63,6 @@ union SegmentShared {
     SortShared srt;
 };
 
-// exclusive prefix sum of v over the workgroup's 256 threads, *total = the sum (two barriers)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < (int)WAVE; off <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)inc, off, WAVE);
-        if (lane >= (uint32_t)off) inc += u;
-    }
-    if (lane == WAVE - 1) wsum[wave] = inc;
-    ktd::lds_barrier();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < WAVES; w++) {
-        const uint32_t x = wsum[w];
-        if (w < wave) pre += x;
-        tot += x;
-    }
-    ktd::lds_barrier();  // (wsum is rewritten by the next call)
-    *total = tot;
-    return pre + inc - v;
-}
-
-// the number of elements of a[0, n) (strictly ascending) below x
-template <class P>
-__device__ __forceinline__ uint32_t lower_bound(P a, uint32_t n, uint64_t x) {
-    uint32_t lo = 0, len = n;
-    while (len) {
-        const uint32_t half = len >> 1;
-        if (a[lo + half] < x) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(BLOCK) void max_len_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, uint64_t *max_len) {
     uint64_t m = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * BLOCK) {
@@ -142,7 +103,7 @@ __global__ __launch_bounds__(BLOCK) void sketch_segment_kernel(ktseg::SegArgs a,
         ktseg::ReadCursor cur(a.offsets, a.seg_first, g, p0 < lim ? B0 + p0 : B0);
         if (tid == 0) s_first = cur.rid;
         uint32_t npieces;
-        const uint32_t qbase = block_excl_scan((uint32_t)__popc(bw), wsum, &npieces);  // (barriers: the staged masks are read)
+        const uint32_t qbase = ktd::block_excl_scan<WAVES>((uint32_t)__popc(bw), wsum, &npieces);  // (barriers: the staged masks are read)
         npieces += 1;
         const uint64_t r_first = s_first;
 
@@ -193,7 +154,7 @@ __global__ __launch_bounds__(BLOCK) void sketch_segment_kernel(ktseg::SegArgs a,
             const bool new_piece = valid && (i == 0 || sm.srt.pc[i - 1] != q);
             const bool first = valid && (new_piece || sm.srt.hk[i - 1] != sm.srt.hk[i]);
             uint32_t tot;
-            ex[c] = carry + block_excl_scan(first ? 1u : 0u, wsum, &tot);
+            ex[c] = carry + ktd::block_excl_scan<WAVES>(first ? 1u : 0u, wsum, &tot);
             carry += tot;
             fl |= (first ? 1u : 0u) << c;
             if (new_piece) sm.srt.pinfo[q] = (i << 16) | ex[c];
@@ -271,11 +232,11 @@ __device__ __forceinline__ void merge2(const uint64_t *X, uint32_t nx, const uin
         bool m = false;
         if (act) {
             x = X[i];
-            lb = lower_bound(Y, ny, x);
+            lb = ktd::lower_bound(Y, ny, x);
             m = lb < ny && Y[lb] == x;
         }
         uint32_t tot;
-        const uint32_t mb = carry + block_excl_scan(m ? 1u : 0u, wsum, &tot);
+        const uint32_t mb = carry + ktd::block_excl_scan<WAVES>(m ? 1u : 0u, wsum, &tot);
         carry += tot;
         if (act) {
             cm[i] = (uint16_t)mb;
@@ -287,7 +248,7 @@ __device__ __forceinline__ void merge2(const uint64_t *X, uint32_t nx, const uin
     ktd::lds_barrier();
     for (uint32_t j = tid; j < ny; j += BLOCK) {
         const uint64_t y = Y[j];
-        const uint32_t lb = lower_bound(X, nx, y);
+        const uint32_t lb = ktd::lower_bound(X, nx, y);
         if (lb < nx && X[lb] == y) continue;  // (written from X)
         const uint32_t rank = j + lb - cm[lb];
         if (rank < s) out[rank] = y;
@@ -383,7 +344,7 @@ __global__ __launch_bounds__(BLOCK) void sketch_pairs_kernel(const uint64_t *__r
                 bool m = false;
                 if (e < nb) {
                     const uint64_t y = brow[e];
-                    lb = lower_bound(arow, na, y);
+                    lb = ktd::lower_bound(arow, na, y);
                     m = lb < na && arow[lb] == y;
                 }
                 const uint64_t bal = __ballot(m);
@@ -563,14 +524,7 @@ extern "C" int kt_sketch_merge(kt_ctx *ctx, const uint64_t *hashes, const uint32
 
 static int pairs_device(kt_ctx *ctx, const uint64_t *a_h, const uint32_t *a_s, uint64_t n_a, const uint64_t *b_h, const uint32_t *b_s,
                         uint64_t n_b, uint32_t s, uint32_t *shared, uint32_t *denom) {
-    // a row of A per workgroup, the rows of B dealt to blockIdx.y's waves: enough of them to fill the device when A is small
-    const uint64_t want = (uint64_t)ctx->n_cu * 8;
-    const uint64_t gx = n_a < want ? n_a : want;
-    uint64_t gy = want / gx ? want / gx : 1;
-    const uint64_t b_units = (n_b + WAVES - 1) / WAVES;
-    if (gy > b_units) gy = b_units;
-    if (gy > 65535) gy = 65535;
-    const dim3 grid((uint32_t)gx, (uint32_t)gy);
+    const dim3 grid = ktl::pairs_grid(ctx, n_a, n_b, WAVES);
     if (s <= 2048)
         hipLaunchKernelGGL(sketch_pairs_kernel<2048>, grid, dim3(BLOCK), 0, ctx->stream, a_h, a_s, n_a, b_h, b_s, n_b, s, shared, denom);
     else

@@ -54,29 +54,6 @@ __global__ __launch_bounds__(BLOCK) void sort_hist_kernel(const uint64_t *__rest
         for (uint32_t d = lane; d < 256u; d += 64u) hist[(uint64_t)d * T + t] = cnt[wave][d];
 }
 
-// inclusive prefix sum of v over the workgroup's BLOCK threads; *total = the sum
-__device__ __forceinline__ uint64_t block_incl_scan(uint64_t v, uint64_t *wsum, uint64_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t u = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += u;
-    }
-    if (lane == 63u) wsum[wave] = inc;
-    ktd::lds_barrier();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
-        const uint64_t x = wsum[w];
-        if (w < wave) pre += x;
-        tot += x;
-    }
-    ktd::lds_barrier();  // (wsum is rewritten by the next call)
-    *total = tot;
-    return pre + inc;
-}
-
 __global__ __launch_bounds__(BLOCK) void sort_scan_kernel(uint64_t *__restrict__ hist, uint64_t T, uint64_t *__restrict__ totals) {
     __shared__ uint64_t wsum[WAVES];
     uint64_t *row = hist + (uint64_t)blockIdx.x * T;
@@ -85,8 +62,8 @@ __global__ __launch_bounds__(BLOCK) void sort_scan_kernel(uint64_t *__restrict__
         const uint64_t i = c0 + threadIdx.x;
         const uint64_t v = i < T ? row[i] : 0;
         uint64_t tot;
-        const uint64_t inc = block_incl_scan(v, wsum, &tot);
-        if (i < T) row[i] = carry + inc - v;
+        const uint64_t pre = ktd::block_excl_scan<WAVES>(v, wsum, &tot);
+        if (i < T) row[i] = carry + pre;
         carry += tot;
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
@@ -102,9 +79,7 @@ __global__ __launch_bounds__(BLOCK) void sort_scatter_kernel(const uint64_t *__r
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t t = (uint64_t)blockIdx.x * WAVES + wave;
     {
-        const uint64_t v = totals[threadIdx.x];
-        uint64_t tot;
-        dbase[threadIdx.x] = block_incl_scan(v, wsum, &tot) - v;
+        dbase[threadIdx.x] = ktd::block_excl_scan<WAVES>(totals[threadIdx.x], wsum);
     }
     ktd::lds_barrier();
     if (t < T)

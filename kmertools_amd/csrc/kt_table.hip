@@ -175,8 +175,7 @@ __global__ __launch_bounds__(XT) void tile_sums_kernel(const uint32_t *__restric
                                                        uint64_t *__restrict__ tile_sums) {
     __shared__ uint32_t part[XT / 64];
     const uint64_t i = (uint64_t)blockIdx.x * XT + threadIdx.x;
-    uint32_t v = i < n ? counts[i] : 0u;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const uint32_t v = ktd::wave_sum(i < n ? counts[i] : 0u);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = (uint64_t)part[0] + part[1] + part[2] + part[3];
@@ -190,11 +189,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(uint64_t *__restrict__ 
     for (uint64_t c0 = 0; c0 < n_tiles; c0 += 1024) {
         const uint64_t i = c0 + threadIdx.x;
         const uint64_t v = i < n_tiles ? tile_sums[i] : 0;
-        uint64_t inc = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t u = __shfl_up(inc, off, 64);
-            if ((threadIdx.x & 63) >= (uint32_t)off) inc += u;
-        }
+        const uint64_t inc = ktd::wave_prefix(v);
         if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = inc;
         __syncthreads();
         uint64_t base = carry;
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(XT) void dense_kept_kernel(const Slot *__restrict__
                      (e + 2u < D && c2 >= lo && c2 <= hi) + (e + 3u < D && c3 >= lo && c3 <= hi);
             }
         }
-        for (int o = 32; o > 0; o >>= 1) k += __shfl_down(k, o, 64);
+        k = ktd::wave_sum(k);
         if (lane == 0) kept[r0 + r] = k;
         mine += k;  // (lane 0's sum is the wave's)
     }
@@ -256,11 +251,7 @@ __global__ __launch_bounds__(XT) void dense_export_kernel(const Slot *__restrict
     const uint32_t tid = threadIdx.x;
     const uint64_t r0 = (uint64_t)blockIdx.x * XT;
     const uint32_t c = r0 + tid < n_ranges ? (FILTER ? kept : range_counts)[r0 + tid] : 0u;
-    uint32_t inc = c;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t u = __shfl_up(inc, off, 64);
-        if ((tid & 63) >= (uint32_t)off) inc += u;
-    }
+    const uint32_t inc = ktd::wave_prefix(c);
     if ((tid & 63) == 63) wt[tid >> 6] = inc;
     __syncthreads();
     uint32_t base = 0;

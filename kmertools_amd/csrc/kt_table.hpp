@@ -179,12 +179,7 @@ struct TileShared {
         ktd::lds_barrier();
         if (wave == 0) {  // 64 runs: one wave scans them and reserves the tile's output range
             const uint32_t c = runs[lane];
-            uint32_t inc = c;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t u = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += u;
-            }
+            const uint32_t inc = ktd::wave_prefix(c);
             runs[lane] = inc - c;
             if (lane == 63)
                 tile_base = inc ? atomicAdd(reinterpret_cast<unsigned long long *>(cursor), (unsigned long long)inc) : 0;

@@ -386,7 +386,7 @@ int write_section(kt_ctr *ctr, FILE *f, const std::string &path, uint64_t n) {
     kt_ctx *ctx = ctr->ctx;
     hipStream_t st = ctx->stream;
     const uint32_t S = pick_S(ctr->k, n), B = 2u * ctr->k, P = B > 8 * S ? B - 8 * S : 0;
-    const uint64_t nb1 = (1ull << P) + 1, T = (n + SCAN_TILE - 1) / SCAN_TILE;
+    const uint64_t nb1 = (1ull << P) + 1, T = scan2_tiles(n);
     uint8_t hdr[SEC_HDR] = {};
     memcpy(hdr, SEC_MAGIC, 4);
     put32(hdr + 4, S), put64(hdr + 8, n);
@@ -411,14 +411,12 @@ int write_section(kt_ctr *ctr, FILE *f, const std::string &path, uint64_t n) {
     const size_t part_bytes = ktl::carve_parts<16>(nullptr, &offsets, nb1, &suffix, sfx_dw, &cbytes, cb_dw, &overflow, n, &tiles, 2 * T, &sums, 2);
     if (int rc = ctx->claim(kt::AUX1, part_bytes, "kt_ctr_save", &parts)) return rc;
     ktl::carve_parts<16>(parts, &offsets, nb1, &suffix, sfx_dw, &cbytes, cb_dw, &overflow, n, &tiles, 2 * T, &sums, 2);
-    const dim3 G = blocks_for(n, BLOCK), GT = blocks_for(n, SCAN_TILE), Bk(BLOCK);
+    const dim3 G = blocks_for(n, BLOCK), Bk(BLOCK);
     hipLaunchKernelGGL(tf_offsets_kernel, G, Bk, 0, st, (const uint64_t *)keys, n, S, P, offsets);
     hipLaunchKernelGGL(tf_pack_kernel, G, Bk, 0, st, (const uint64_t *)keys, (const uint32_t *)counts, n, S, suffix, cbytes);
     const PackScan scan{counts, overflow};
-    hipLaunchKernelGGL(scan2_tile_sum_kernel<PackScan>, GT, Bk, 0, st, scan, n, tiles);
-    hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), Bk, 0, st, tiles, T, (unsigned long long *)sums, (unsigned long long *)sums + 1);
-    hipLaunchKernelGGL(scan2_apply_kernel<PackScan>, GT, Bk, 0, st, scan, n, (const uint64_t *)tiles);
-    KT_HIP(hipGetLastError());
+    if (int rc = scan2_sums(st, scan, n, tiles, sums, sums + 1)) return rc;
+    if (int rc = scan2_apply(st, scan, n, tiles)) return rc;
     uint64_t h_sums[2] = {0, 0};
     KT_HIP(hipMemcpyAsync(h_sums, sums, 16, hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
@@ -456,7 +454,7 @@ int load_section(kt_ctr *ctr, FILE *f, const std::string &path, const Section &s
                  Slabs &slab, uint64_t *piece) {
     kt_ctx *ctx = ctr->ctx;
     hipStream_t st = ctx->stream;
-    const uint64_t n = s.n, nb1 = (1ull << s.P) + 1, T = (n + SCAN_TILE - 1) / SCAN_TILE;
+    const uint64_t n = s.n, nb1 = (1ull << s.P) + 1, T = scan2_tiles(n);
     uint8_t *parts = nullptr, *suffix = nullptr, *cbytes = nullptr;
     uint64_t *keys = nullptr, *offsets = nullptr, *tiles = nullptr, *sums = nullptr;
     uint32_t *counts = nullptr, *overflow = nullptr, *flags = nullptr;
@@ -475,14 +473,11 @@ int load_section(kt_ctr *ctr, FILE *f, const std::string &path, const Section &s
     pos += n;
     if (int rc = up(ctx, f, pos, overflow, s.ovf_bytes, slab, piece, path)) return rc;
     KT_HIP(hipMemsetAsync(sums, 0, 48, st));  // (the four sums and the flag word behind them)
-    const dim3 G = blocks_for(n, BLOCK), GT = blocks_for(n, SCAN_TILE), Bk(BLOCK);
-    unsigned long long *su = (unsigned long long *)sums;
+    const dim3 G = blocks_for(n, BLOCK), Bk(BLOCK);
     const UnpackScan scan{cbytes, overflow, s.n_overflow, counts, flags};
-    hipLaunchKernelGGL(scan2_tile_sum_kernel<UnpackScan>, GT, Bk, 0, st, scan, n, tiles);
-    hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), Bk, 0, st, tiles, T, su, su + 1);
-    hipLaunchKernelGGL(scan2_apply_kernel<UnpackScan>, GT, Bk, 0, st, scan, n, (const uint64_t *)tiles);
-    hipLaunchKernelGGL(scan2_tile_sum_kernel<SumScan>, GT, Bk, 0, st, SumScan{counts}, n, tiles);
-    hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), Bk, 0, st, tiles, T, su + 2, su + 3);
+    if (int rc = scan2_sums(st, scan, n, tiles, sums, sums + 1)) return rc;
+    if (int rc = scan2_apply(st, scan, n, tiles)) return rc;
+    if (int rc = scan2_sums(st, SumScan{counts}, n, tiles, sums + 2, sums + 3)) return rc;
     hipLaunchKernelGGL(tf_keys_kernel, G, Bk, 0, st, (const uint64_t *)offsets, (const uint8_t *)suffix, n, s.S, s.P, ctr->k, keys, flags);
     KT_HIP(hipGetLastError());
     uint64_t h[6] = {};

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(BLOCK) void index_pairs_kernel(SegArgs a, uint64_t 
         }
         __syncthreads();  // sm is restaged by the next segment
     }
-    for (int d = 32; d; d >>= 1) mine += (uint32_t)__shfl_xor((int)mine, d);
+    mine = ktd::wave_all_sum(mine);
     if ((tid & 63u) == 0 && mine) atomicAdd(n_windows, (unsigned long long)mine);
 }
 
@@ -226,8 +226,7 @@ __global__ __launch_bounds__(BLOCK) void runs_tally_kernel(RunArgs c, unsigned l
     }
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        uint32_t v = n[q];
-        for (int d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+        const uint32_t v = ktd::wave_all_sum(n[q]);
         if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&tally[q], (unsigned long long)v);
     }
 }
@@ -262,7 +261,7 @@ __global__ __launch_bounds__(BLOCK) void reads_hit_kernel(const uint64_t *__rest
     uint32_t n = 0;
     for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < n_reads; r += (uint64_t)gridDim.x * BLOCK)
         n += run_offsets[r + 1] > run_offsets[r];
-    for (int d = 32; d; d >>= 1) n += (uint32_t)__shfl_xor((int)n, d);
+    n = ktd::wave_all_sum(n);
     if ((threadIdx.x & 63u) == 0 && n) atomicAdd(&tally[5], (unsigned long long)n);
 }
 
@@ -388,7 +387,7 @@ extern "C" int kt_thread_runs(kt_ctx *ctx, const uint32_t *hits, const uint64_t 
     if (int rc = call.in(kt::OFFSETS, read_offsets, n_reads + 1, &d_roff)) return rc;
     // working arrays: AUX0 = the scan's tiles and the tally, AUX1 = the bit arrays, a host call's unitig offsets and the run
     // offsets when the caller keeps none on the device
-    const uint64_t n_items = total + 1, n_tiles = (n_items + SCAN_TILE - 1) / SCAN_TILE;
+    const uint64_t n_items = total + 1, n_tiles = scan2_tiles(n_items);
     const uint64_t uwords = ub / 32 + 1, rwords = total / 32 + 1;
     const bool own_roff = call.host() || !run_offsets;
     const uint64_t n_uoff = call.host() && n_unitigs ? n_unitigs + 1 : 0, n_own = own_roff ? n_reads + 1 : 0;
@@ -419,11 +418,7 @@ extern "C" int kt_thread_runs(kt_ctx *ctx, const uint32_t *hits, const uint64_t 
     // run starts and run ends, counted: the totals land in the tally ([4] runs; [6] the ends, as many)
     const RunArgs c{d_hits, ubits, rbits, total, ub, (uint32_t)k};
     RunScan scan{c, d_roff, n_reads, nullptr, nullptr, d_run_offsets};
-    const dim3 T((uint32_t)n_tiles), B(SCAN_BLOCK);
-    hipLaunchKernelGGL(scan2_tile_sum_kernel<RunScan>, T, B, 0, st, scan, n_items, tiles);
-    hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, st, tiles, n_tiles, (unsigned long long *)&d_tally[4],
-                       (unsigned long long *)&d_tally[6]);
-    KT_HIP(hipGetLastError());
+    if (int rc = scan2_sums(st, scan, n_items, tiles, &d_tally[4], &d_tally[6])) return rc;
     uint64_t nr = 0;
     KT_HIP(hipMemcpyAsync(&nr, &d_tally[4], 8, hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
@@ -451,8 +446,7 @@ extern "C" int kt_thread_runs(kt_ctx *ctx, const uint32_t *hits, const uint64_t 
         scan.run_start = d_start;
         scan.run_last = d_len;
     }
-    hipLaunchKernelGGL(scan2_apply_kernel<RunScan>, T, B, 0, st, scan, n_items, (const uint64_t *)tiles);
-    KT_HIP(hipGetLastError());
+    if (int rc = scan2_apply(st, scan, n_items, tiles)) return rc;
     if (write && nr)
         if (int rc = launch(runs_finish_kernel, dim3(grid_for(ctx, (nr + BLOCK - 1) / BLOCK, 8)), dim3(BLOCK), 0, st, c, d_uoff, n_unitigs,
                             nr, (const uint64_t *)d_start, d_len, d_unitig, d_upos, (unsigned long long *)d_uh, (unsigned long long *)d_ur))

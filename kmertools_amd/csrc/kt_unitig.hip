@@ -235,7 +235,7 @@ __device__ __forceinline__ uint64_t bases_of(uint32_t sl, uint32_t k) { return s
 // The exclusive scan over n items, two sums at once, is written once over a functor F: word(i) is item i's one u32,
 // add(word, a, b) what it contributes to the two sums (word 0, the filler past n, contributes nothing), put(i, a, b) takes
 // the sums over the items before i, total() is thread 0's after the last put.  Three launches: the tiles' sums, one
-// workgroup over those, and the tiles again (block_scan2 and the three kernels: kt_scan.hpp, shared with kt_tablefile.hip).
+// workgroup over those, and the tiles again (kt_scan.hpp).
 
 // stage d, over nodes: (is start, bases) -> ex_id[i], ex_off[i] = unitigs and bases that start at nodes before i
 struct NodeScan {
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(BLOCK) void unitig_end_degree_kernel(LinkArgs a) { 
 __global__ __launch_bounds__(BLOCK) void unitig_end_emit_kernel(LinkArgs a) { unitig_end_links<true>(a); }
 
 // stage f / g, over ends: the degree -> link_offsets[e] = the links of the ends before e, link_offsets[n_ends] = all of them.
-// The second sum stays 0: block_scan2 and the one-workgroup tile scan are stage d's, and carry two.
+// The second sum stays 0: the workgroup scan over a ktd::sum2 and the one-workgroup tile scan are stage d's, and carry two.
 struct EndScan {
     const uint32_t *deg;
     uint64_t n_ends;
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(BLOCK) void unitig_tip_mark_kernel(TipArgs a, const
     uint64_t v[TIP_WORDS] = {tipped, tipped ? nodes : 0, alone, alone ? nodes : 0, tipped ? occ : 0, alone ? occ : 0};
 #pragma unroll
     for (int j = 0; j < TIP_WORDS; j++) {
-        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_down(v[j], o, 64);
+        v[j] = ktd::wave_sum(v[j]);
         if ((threadIdx.x & 63) == 0 && v[j]) atomicAdd(words + j, (unsigned long long)v[j]);
     }
 }
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(BLOCK) void unitig_bubble_mark_kernel(TipArgs a, ui
     uint64_t v[BUBBLE_WORDS] = {popped, popped ? n_u : 0, found && !popped, popped ? c_u : 0};
 #pragma unroll
     for (int j = 0; j < BUBBLE_WORDS; j++) {
-        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_down(v[j], o, 64);
+        v[j] = ktd::wave_sum(v[j]);
         if ((threadIdx.x & 63) == 0 && v[j]) atomicAdd(words + j, (unsigned long long)v[j]);
     }
 }
@@ -636,9 +636,9 @@ struct Run {
     // b to d, for n > 0: nu and n_bases
     int chains() {
         const uint64_t m = 2 * n;
-        const dim3 M = blocks_for(m), T = blocks_for(n, SCAN_TILE), B(BLOCK);
+        const dim3 M = blocks_for(m), B(BLOCK);
         uint64_t *ra = nullptr, *rb = nullptr;
-        if (int rc = carve(call, kt::AUX2, &w, 1, &link, m, &ra, m, &rb, m, &place, n, &slen, n, &ex_id, n, &ex_off, n, &tiles, 2ull * T.x))
+        if (int rc = carve(call, kt::AUX2, &w, 1, &link, m, &ra, m, &rb, m, &place, n, &slen, n, &ex_id, n, &ex_off, n, &tiles, 2 * scan2_tiles(n)))
             return rc;
         KT_HIP(hipMemsetAsync(w, 0, sizeof(Words), st));
         // b. links
@@ -665,9 +665,8 @@ struct Run {
         // d. placing, ids and offsets
         hipLaunchKernelGGL(unitig_place_kernel, blocks_for(n), B, 0, st, ra, link, cval, n, place, slen, w);
         const NodeScan scan{slen, k, ex_id, ex_off};
-        hipLaunchKernelGGL(scan2_tile_sum_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
-        hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, st, tiles, (uint64_t)T.x, &w->n_unitigs, &w->n_bases);
-        hipLaunchKernelGGL(scan2_apply_kernel<NodeScan>, T, B, 0, st, scan, n, tiles);
+        if (int rc = scan2_sums(st, scan, n, tiles, &w->n_unitigs, &w->n_bases)) return rc;
+        if (int rc = scan2_apply(st, scan, n, tiles)) return rc;
         if (int rc = check_words("the nodes' links do not form paths and cycles")) return rc;
         nu = h.n_unitigs, n_bases = h.n_bases;
         return KT_OK;
@@ -675,12 +674,11 @@ struct Run {
     // f. the ends' degrees and their sum (the graph's sort has given AUX0 back): n_ends and n_links
     int degrees() {
         n_ends = 2 * nu;
-        const dim3 T = blocks_for(n_ends, SCAN_TILE), B(BLOCK);
-        if (int rc = carve(call, kt::AUX0, &lw, 1, &deg, n_ends, &ltiles, 2ull * T.x)) return rc;
+        const dim3 B(BLOCK);
+        if (int rc = carve(call, kt::AUX0, &lw, 1, &deg, n_ends, &ltiles, 2 * scan2_tiles(n_ends))) return rc;
         KT_HIP(hipMemsetAsync(lw, 0, (uint8_t *)ltiles - (uint8_t *)lw, st));
         hipLaunchKernelGGL(unitig_end_degree_kernel, blocks_for(2 * n), B, 0, st, link_args(Outputs{}));
-        hipLaunchKernelGGL(scan2_tile_sum_kernel<EndScan>, T, B, 0, st, EndScan{deg, n_ends, lw, nullptr}, n_ends, ltiles);
-        hipLaunchKernelGGL(scan2_tile_scan_kernel, dim3(1), B, 0, st, ltiles, (uint64_t)T.x, &lw->n_links, &lw->unused);
+        if (int rc = scan2_sums(st, EndScan{deg, n_ends, lw, nullptr}, n_ends, ltiles, &lw->n_links, &lw->unused)) return rc;
         return fetch(&n_links, &lw->n_links, 8);
     }
     LinkArgs link_args(const Outputs &o) const {  // (f writes deg and reads no output; max_links guards g's stores)
@@ -711,7 +709,7 @@ struct Run {
     // rule puts it
     int emit(const Outputs &o) {
         const EndScan scan{deg, n_ends, lw, o.link_offsets};
-        hipLaunchKernelGGL(scan2_apply_kernel<EndScan>, blocks_for(n_ends, SCAN_TILE), dim3(BLOCK), 0, st, scan, n_ends, ltiles);
+        if (int rc = scan2_apply(st, scan, n_ends, ltiles)) return rc;
         if (n_links) hipLaunchKernelGGL(unitig_end_emit_kernel, blocks_for(2 * n), dim3(BLOCK), 0, st, link_args(o));
         return check_words("a unitig end's neighbour is not at an end of its own unitig");
     }

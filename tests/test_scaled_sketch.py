@@ -202,6 +202,28 @@ def test_kept_counts_around_the_sorts_tiles(torch_mod, ctx, oracle, kept, rows_)
         check_batch(torch_mod, ctx, sr.rows_of(hs, 1), bases, offsets, k, 1, 1, mode)
 
 
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1023, 1024, 1025, 262_143, 262_144, 262_145, 1_048_577 + 4096])
+@pytest.mark.parametrize("rows_", ["one row, one group", "three rows, two groups"])
+def test_merge_sizes_around_the_scans_tiles(torch_mod, ctx, n, rows_):
+    """n distinct hashes with abundances through the merge (its sort and its scans), at the edges of the workgroup scan
+    that the two share: the workgroup's 256 threads, the scan's tile of 1024 items, 256 such tiles - one more and the
+    one-workgroup scan of the tiles' sums takes a second chunk - and more than 256 wave tiles of 4096 pairs, where the
+    sort's scan of a digit's histogram row takes a second chunk"""
+    rng = np.random.default_rng(n)
+    h = np.unique(rng.integers(0, 1 << 63, size=n + 64, dtype=np.uint64))
+    assert len(h) >= n
+    h = rng.permutation(h)[:n]
+    a = rng.integers(1, 1000, size=n).astype(np.uint32)
+    if rows_ == "one row, one group":
+        order = np.argsort(h)
+        check_merge(torch_mod, ctx, h[order], a[order], np.array([0, n], U), [0, 1], (n, rows_))
+    else:
+        row = rng.integers(0, 3, size=n)
+        order = np.lexsort((h, row))  # by row, ascending inside a row
+        ro = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=3))]).astype(U)
+        check_merge(torch_mod, ctx, h[order], a[order], ro, [0, 2, 3], (n, rows_))
+
+
 def test_more_rows_than_one_digit_pair_of_the_row_sort(torch_mod, ctx, oracle):
     """70 000 reads of k + 3 bases, scaled = 1: the row ids take 17 bits, so the stable sort by row makes four digit passes"""
     k, n, L = 5, 70_000, 8
