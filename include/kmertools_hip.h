@@ -66,6 +66,14 @@ int kt_device_count(int *count);
 int kt_ctx_create(int device, void *stream, int own_stream, kt_ctx **out);
 int kt_ctx_destroy(kt_ctx *ctx);
 int kt_ctx_sync(kt_ctx *ctx);
+/* The context's workgroup budget: from the next launch on, the grids of this context are sized as if the device had n
+ * compute units (every grid-stride launch asks for min(work, CUs * a small factor) workgroups).  n = 0 restores the
+ * device's count, n above it is clamped to it.  Results never depend on it.  Useful for leaving room on a shared card;
+ * the tests use it to make every grid-stride loop take several trips at small sizes.  (What describes the hardware or a
+ * bulk job's plan - the XCD census, the partition geometry - stays on the device's count.) */
+int kt_ctx_set_cu_limit(kt_ctx *ctx, uint32_t n);
+/* the compute units the grids follow now (*n_cu) and the device's count (*n_cu_device); either pointer may be NULL */
+int kt_ctx_cu_limit(kt_ctx *ctx, uint32_t *n_cu, uint32_t *n_cu_device);
 /* free / total HBM of the context's device in bytes (hipMemGetInfo): lets a caller size a table to what fits */
 int kt_device_memory(kt_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 

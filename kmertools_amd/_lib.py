@@ -43,6 +43,8 @@ SYMBOLS = {
     "kt_host_register": (_i, [_vp, _vp, C.c_size_t]),
     "kt_host_unregister": (_i, [_vp, _vp]),
     "kt_ctx_sync": (_i, [_vp]),
+    "kt_ctx_set_cu_limit": (_i, [_vp, _u32]),
+    "kt_ctx_cu_limit": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "kt_bins": (_i, [_i, _i, C.POINTER(_u64)]),
     "kt_pos_map": (_i, [_i, _vp, _vp, C.POINTER(_u32)]),
     "kt_rev_comp": (_u64, [_u64, _i]),

@@ -2808,7 +2808,7 @@ static int xcc_sets(kt_ctx *ctx, uint32_t *nxs, uint32_t *xmap) {
         uint32_t *mask = nullptr, h = 0;
         if (int rc = ctx->claim(kt::AUX2, 256, "xcc_sets", &mask)) return rc;
         KT_HIP(hipMemsetAsync(mask, 0, 4, ctx->stream));
-        if (int rc = launch(xcc_census_kernel, dim3((uint32_t)ctx->n_cu * 4), dim3(64), 0, ctx->stream, mask)) return rc;
+        if (int rc = launch(xcc_census_kernel, dim3((uint32_t)ctx->n_cu_device * 4), dim3(64), 0, ctx->stream, mask)) return rc;
         KT_HIP(hipMemcpyAsync(&h, mask, 4, hipMemcpyDeviceToHost, ctx->stream));
         KT_HIP(hipStreamSynchronize(ctx->stream));
         ctx->unclaim(kt::AUX2);  // (read back: whoever plans the job may hold AUX2 next)
@@ -2988,7 +2988,7 @@ struct kt_bulk_job {
         p.B2 = 1u << p.b2;
         // persistent level-1 workgroups (the same for every source of the job): two per CU for the per-unit kernels; the wide
         // kernel launches G / 2 of them, one resident per CU (KT_BULK_G_MULT > 1: more, shorter-lived workgroups)
-        p.G = (uint32_t)ctx->n_cu * 2 * (uint32_t)(kn.g_mult ? kn.g_mult : 1);
+        p.G = (uint32_t)ctx->n_cu_device * 2 * (uint32_t)(kn.g_mult ? kn.g_mult : 1);
         // paged level 1: room per bucket = its share of the most keys there can be + 1/8 (region_room), every region
         // starting on a cache line whatever the key size
         paged = kn.paged != 0 && !ctr->paged_failed;
@@ -3019,7 +3019,7 @@ struct kt_bulk_job {
         // two sort buffers, the copy-out spread over the next round - or, a shape that does not fit the LDS, one buffer
         l1 = kn.s1y && Scatter1YShared<K, 1024>::bytes(p.B1) <= 160 * 1024 ? L1_SCATTER1Y : L1_SCATTER1X;
         const uint32_t mult = (uint32_t)(kn.g_mult ? kn.g_mult : 1);
-        const uint32_t cus = (uint32_t)ctx->n_cu > 2 * ctr->l1_spare_cus ? (uint32_t)ctx->n_cu - ctr->l1_spare_cus : (uint32_t)ctx->n_cu;
+        const uint32_t cus = (uint32_t)ctx->n_cu_device > 2 * ctr->l1_spare_cus ? (uint32_t)ctx->n_cu_device - ctr->l1_spare_cus : (uint32_t)ctx->n_cu_device;
         return with_source(r, [&](const auto &src) -> int {
             using S = std::decay_t<decltype(src)>;
             if (l1 == L1_SCATTER1Y)

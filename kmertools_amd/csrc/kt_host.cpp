@@ -134,7 +134,7 @@ int kt_ctx_create(int device, void *stream, int own_stream, kt_ctx **out) {
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, device);
-        if (e == hipSuccess) c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        if (e == hipSuccess) c->n_cu = c->n_cu_device = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     if (e == hipSuccess) {
         if (!own_stream) {
@@ -171,6 +171,19 @@ int kt_ctx_sync(kt_ctx *ctx) {
     if (!ctx) return kt::fail(KT_ERR_ARG, "kt_ctx_sync: null ctx");
     if (int rc = ctx->use()) return rc;
     KT_HIP(hipStreamSynchronize(ctx->stream));
+    return KT_OK;
+}
+
+int kt_ctx_set_cu_limit(kt_ctx *ctx, uint32_t n) {
+    if (!ctx) return kt::fail(KT_ERR_ARG, "kt_ctx_set_cu_limit: null ctx");
+    ctx->n_cu = n == 0 || n > (uint32_t)ctx->n_cu_device ? ctx->n_cu_device : (int)n;
+    return KT_OK;
+}
+
+int kt_ctx_cu_limit(kt_ctx *ctx, uint32_t *n_cu, uint32_t *n_cu_device) {
+    if (!ctx) return kt::fail(KT_ERR_ARG, "kt_ctx_cu_limit: null ctx");
+    if (n_cu) *n_cu = (uint32_t)ctx->n_cu;
+    if (n_cu_device) *n_cu_device = (uint32_t)ctx->n_cu_device;
     return KT_OK;
 }
 

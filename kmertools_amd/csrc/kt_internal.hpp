@@ -38,7 +38,8 @@ struct kt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    int n_cu = 256;
+    int n_cu_device = 256;  // the device's compute units: what measures the hardware or lays out a bulk job's plan
+    int n_cu = 256;         // the compute units the grids are sized by: n_cu_device, or less (kt_ctx_set_cu_limit)
     uint32_t xcc_n = 0, xcc_map = 0;  // XCDs that run this device's workgroups, XCC_ID -> dense index in nibbles (kt_bulk.hip's census)
     // device copies of the canonical-bin LUT (u16[4^k], lut[f] = 4 * rank(min(f, rc f)): the byte offset of the
     // bin's u32 counter inside a row), k = 1..7

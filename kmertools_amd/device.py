@@ -8,6 +8,7 @@
   context's stream without synchronising - what bench.py and the parity tests use.
   torch is only plumbing here (allocation, streams, torch.distributed).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -284,6 +285,25 @@ class Context:
 
     def sync(self):
         check(_lib.lib().kt_ctx_sync(self._h))
+
+    def cu_count(self):
+        """-> (the compute units this context's grids are sized by, the device's compute units)"""
+        n, dev = C.c_uint32(), C.c_uint32()
+        check(_lib.lib().kt_ctx_cu_limit(self._h, C.byref(n), C.byref(dev)))
+        return n.value, dev.value
+
+    @contextlib.contextmanager
+    def cu_limit(self, n):
+        """`with ctx.cu_limit(n):` - the launches inside size their grids as if the device had n compute units
+        (kt_ctx_set_cu_limit: 0 = the device's count, more than that is clamped); the value from before is put back on
+        the way out, also by an exception.  Results never depend on it: it leaves room on a shared card, and it lets a
+        test take every grid-stride loop round several times at small sizes."""
+        before, dev = self.cu_count()
+        check(_lib.lib().kt_ctx_set_cu_limit(self._h, int(n)))
+        try:
+            yield self
+        finally:
+            check(_lib.lib().kt_ctx_set_cu_limit(self._h, 0 if before == dev else before))
 
     # -- comp oligo / comp cgr -k ------------------------------------------------------
     def oligo(self, bases, offsets, n_reads, k, out, count_min=True, norm=True, total_step=1, dtype="f64",

@@ -2271,6 +2271,15 @@ def test_ctr_cfg4_routed_into_8_owners_full_size(torch_mod, ctx, oracle, monkeyp
     ctr.close()
 
 
+def quotient_checksum(d_lo, d_hi):
+    """the sum, modulo 2^64, of the bit patterns of numpy's c / d for all 0 <= c <= d, d_lo <= d <= d_hi"""
+    want = 0
+    for d in range(d_lo, d_hi + 1):
+        q = np.arange(d + 1, dtype=np.float64) / np.float64(d)
+        want = (want + int(q.view(np.uint64).sum(dtype=np.uint64))) % (1 << 64)
+    return want
+
+
 def test_quotient_exhaustive(hctx):
     """the reciprocal + fma normalisation against the IEEE division for every count / divisor pair a read of up to
     32 768 k-mers can produce (total_step 1 and 2: d = total_step * kmers, c <= kmers), and the device division
@@ -2278,8 +2287,4 @@ def test_quotient_exhaustive(hctx):
     n, bad, _ = hctx.selftest_quotient(1, 32768)
     assert n == sum(d + 1 for d in range(1, 32769)) and bad == 0
     n, bad, chk = hctx.selftest_quotient(1, 2048)
-    want = 0
-    for d in range(1, 2049):
-        q = np.arange(d + 1, dtype=np.float64) / np.float64(d)
-        want = (want + int(q.view(np.uint64).sum(dtype=np.uint64))) % (1 << 64)
-    assert bad == 0 and chk == want
+    assert bad == 0 and chk == quotient_checksum(1, 2048)
