@@ -1024,6 +1024,50 @@ int kt_card_estimate(const uint8_t *registers, int p, double *estimate, uint64_t
 /* the estimator's relative standard error, 1.04 / sqrt(2^p) */
 double kt_card_rel_error(int p);
 
+/* A two-pass pre-filter that keeps k-mers seen once (in a read set: mostly sequencing errors) out of a table - what
+ * BFCounter, Jellyfish's --bf-size and KMC's pre-filter give their users.  replaces: nothing - the reference has no such
+ * operation.  The filter is two arrays of 64-bit words on the device, `once` of 2^log2_once words and `twice` of
+ * 2^log2_twice, each exponent in KT_PREFILTER_MIN_LOG2..KT_PREFILTER_MAX_LOG2.  For a canonical k-mer m:
+ *   h = mix64(m ^ seed), the formula printed above kt_sketch_batch.
+ *   once word = h >> (64 - log2_once); once pattern = the OR of 1 << ((h >> 6 j) & 63) for j = 0..3.
+ *   g = mix64(h); the twice word and pattern come from g the same way, with log2_twice.
+ * All bits of a k-mer lie in one word of each array, so one atomic OR sets them and tells whether they were set before.
+ * Pass 1 (kt_prefilter_add_reads), per valid window: when the once word does not cover the pattern it is OR-ed in, and the
+ * k-mer is done if the value returned did not cover it either (first sighting).  Otherwise - the k-mer was seen before, by
+ * the load or by the atomic's return value, or it is a false positive - its twice pattern is OR-ed in, unless the word covers
+ * it already; a promotion is counted when the value that OR returned did not cover the pattern.  Two lanes with the same
+ * k-mer serialise on one atomic of one word, so the second always sees the first.
+ * Pass 2 (kt_ctr_add_reads_filtered) counts the k-mers whose twice pattern is covered.
+ * The guarantee: after pass 1 over an input and pass 2 over the same input into an empty table, every k-mer with two or
+ * more occurrences is in the table with its exact count; every other key of the table has count 1 and occurs exactly once
+ * in the input.  Which k-mers seen once get in depends on the order of execution, how many is bounded by the false-positive
+ * rate of the two arrays; nothing else is nondeterministic (`once` itself is the OR of all patterns, whatever the order).
+ * So every reader that ignores count 1 (min_count >= 2) gives what it gives on the unfiltered table. */
+typedef struct kt_prefilter kt_prefilter;
+#define KT_PREFILTER_MIN_LOG2 10
+#define KT_PREFILTER_MAX_LOG2 34
+/* Both arrays zeroed.  KT_ERR_ARG: null pointers, k outside 1..31, an exponent out of range; KT_ERR_NOMEM. */
+int kt_prefilter_create(kt_ctx *ctx, int k, int log2_once, int log2_twice, uint64_t seed, kt_prefilter **out);
+int kt_prefilter_destroy(kt_prefilter *filter);
+/* every bit and every counter back to zero */
+int kt_prefilter_clear(kt_prefilter *filter);
+/* Pass 1 over a CSR batch.  Batches accumulate; the final `once` array does not depend on their order.  `mem` says where
+ * bases and offsets live; KT_MEM_HOST synchronises, KT_MEM_DEVICE is enqueued on the context's stream.  n_reads == 0 is
+ * KT_OK.  KT_ERR_ARG: a null filter, a bad mem, a null buffer with n_reads > 0, a read of 2^32 bases or more. */
+int kt_prefilter_add_reads(kt_prefilter *filter, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int mem);
+/* Host outputs, each may be NULL: the windows walked and the promotions counted by every pass-1 call since the last clear,
+ * and the bits set in the two arrays now.  Synchronises. */
+int kt_prefilter_stats(kt_prefilter *filter, uint64_t *windows, uint64_t *promotions, uint64_t *once_bits_set,
+                       uint64_t *twice_bits_set);
+/* out[i] = (once covers the pattern of keys[i] ? 1 : 0) | (twice covers it ? 2 : 0) for n canonical k-mers: the
+ * membership test of the two passes restated.  `mem` says where keys and out live. */
+int kt_prefilter_query(kt_prefilter *filter, const uint64_t *keys, uint64_t n, uint8_t *out, int mem);
+/* kt_ctr_add_reads_part through the filter: only k-mers whose twice pattern is covered are added.  Always the probing
+ * path, so it works on a table in any form (the table is brought to its probing image first, what was staged for export is
+ * dropped), and on one that already holds data.  KT_ERR_ARG also: a null filter, a filter of another context or another k. */
+int kt_ctr_add_reads_filtered(kt_ctr *ctr, kt_prefilter *filter, const uint8_t *bases, const uint64_t *offsets,
+                              uint64_t n_reads, int mem, uint32_t n_parts, uint32_t part);
+
 /* Multi-GPU routing step (the reference's `min_mer % n_parts` partitioning,
  * counter/src/lib.rs:127, re-expressed as hash-prefix ownership):
  * writes every canonical k-mer of the reads into keys_out grouped by owner

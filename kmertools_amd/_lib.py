@@ -18,6 +18,7 @@ KT_F64, KT_F32, KT_U32 = 0, 1, 2
 KT_EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
 KT_SKETCH_MAX_S = 16384
 KT_CARD_MIN_P, KT_CARD_MAX_P = 4, 16
+KT_PREFILTER_MIN_LOG2, KT_PREFILTER_MAX_LOG2 = 10, 34
 KT_SET_INTERSECT, KT_SET_SUBTRACT, KT_SET_UNION, KT_SET_XOR = 0, 1, 2, 3
 KT_SETCNT_FIRST, KT_SETCNT_MIN, KT_SETCNT_MAX, KT_SETCNT_SUM = 0, 1, 2, 3
 KT_GRAPH_CENSUS = 32
@@ -115,6 +116,13 @@ SYMBOLS = {
     "kt_card_merge": (_i, [_vp, _vp, _i]),
     "kt_card_estimate": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_u64)]),
     "kt_card_rel_error": (C.c_double, [_i]),
+    "kt_prefilter_create": (_i, [_vp, _i, _i, _i, _u64, C.POINTER(_vp)]),
+    "kt_prefilter_destroy": (_i, [_vp]),
+    "kt_prefilter_clear": (_i, [_vp]),
+    "kt_prefilter_add_reads": (_i, [_vp, _vp, _vp, _u64, _i]),
+    "kt_prefilter_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "kt_prefilter_query": (_i, [_vp, _vp, _u64, _vp, _i]),
+    "kt_ctr_add_reads_filtered": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u32, _u32]),
     "kt_ctr_route": (_i, [_vp, _vp, _vp, _u64, _i, _i, _vp, _vp, _i]),
     "kt_owner_of": (_u32, [_u64, _u32]),
     "kt_rccl_unique_id": (_i, [_vp]),

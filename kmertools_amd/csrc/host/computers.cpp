@@ -885,6 +885,16 @@ class TableWriter {
     std::vector<std::string> pieces_;
 };
 
+// --prefilter (set_prefilter; the passes: below, in front of CountComputer::count)
+static struct {
+    bool on = false;
+    uint64_t bits = 16;
+    std::string out_dir;
+} g_prefilter;
+void set_prefilter(bool on, uint64_t bits_per_kmer, const std::string &out_dir) {
+    g_prefilter.on = on, g_prefilter.bits = bits_per_kmer, g_prefilter.out_dir = out_dir;
+}
+
 // the spectrum of table t added to histo_ (out-of-core passes and shards: one table after the other into one array)
 std::string CountComputer::add_spectrum(kt_ctr *t) {
     if (histo_.empty()) histo_.assign((size_t)histo_max_ + 1, 0);
@@ -898,7 +908,8 @@ std::string CountComputer::write_histo() const {
     for (uint32_t c = 1; c <= histo_max_; c++) {
         s += std::to_string(c);
         s += '\t';
-        s += std::to_string(c < histo_.size() ? histo_[c] : 0);
+        // (--prefilter: the table holds only a few of the k-mers seen once; their number is not known, and 0 is written)
+        s += std::to_string(c < histo_.size() && !(c == 1 && g_prefilter.on) ? histo_[c] : 0);
         s += '\n';
     }
     return write_text_file(out_dir_ + "/kmers.histo", s);
@@ -1073,6 +1084,117 @@ static std::string fill_table(SeqReader &reader, Batch &b, PhaseTimer &pt, Lap &
     });
 }
 
+// ---- --prefilter: two passes over the input, k-mers seen once kept out of the table -----------------------------------------
+// Pass 1 marks every k-mer in the filter's `once` array and the ones seen again in `twice` (kt_prefilter_add_reads); the
+// table is then planned from what pass 1 promoted, and pass 2 counts only the k-mers marked in `twice`
+// (kt_ctr_add_reads_filtered).  The host side is arithmetic alone (prefilter_sizes, prefilter_table_slots,
+// prefilter_stats_text: also behind the hidden `debug-prefilter` of main.cpp, which the sanitizer builds run).
+// `once`: bits_per_kmer bits for every k-mer expected, rounded up to a power of two of 64-bit words, at least 2^10 words and,
+// where that is less, at most a quarter of the free device memory (0: not known); `twice`: a quarter of `once`, at least
+// 2^10 words.  A request beyond 2^34 words is refused, whatever the memory.
+std::string prefilter_sizes(uint64_t expected_kmers, uint64_t bits_per_kmer, uint64_t free_bytes, int *log2_once, int *log2_twice) {
+    const unsigned __int128 bits = (unsigned __int128)expected_kmers * bits_per_kmer;
+    const unsigned __int128 words = (bits + 63) / 64;
+    if (bits_per_kmer == 0 || words > ((unsigned __int128)1 << KT_PREFILTER_MAX_LOG2))
+        return "--prefilter-bits " + std::to_string(bits_per_kmer) + ": a filter of that many bits for each of the " +
+               std::to_string(expected_kmers) + " k-mers this input can hold takes more than 2^" + std::to_string(KT_PREFILTER_MAX_LOG2) +
+               " words";
+    int a = KT_PREFILTER_MIN_LOG2;
+    while (((unsigned __int128)1 << a) < words) a++;
+    if (free_bytes)
+        while (a > KT_PREFILTER_MIN_LOG2 && (8ull << a) > free_bytes / 4) a--;
+    *log2_once = a;
+    *log2_twice = std::max(KT_PREFILTER_MIN_LOG2, a - 2);
+    return "";
+}
+
+// Slots for the table of pass 2: the promotions of pass 1 plus the false positives expected among the k-mers estimated -
+// a k-mer seen once gets in when its four bits of `twice` happen to be set: (the share of the bits set)^4 -, times `scale`
+// (KT_PREFILTER_SCALE), then the 1.9 slots per key of every plan.  An estimate, not a bound: pass 2 may overflow the table.
+uint64_t prefilter_table_slots(uint64_t promotions, uint64_t twice_bits_set, int log2_twice, uint64_t expected_kmers, double scale) {
+    const double fill = (double)twice_bits_set / (64.0 * (double)(1ull << log2_twice));
+    const double keys = ((double)promotions + fill * fill * fill * fill * (double)expected_kmers) * scale;
+    if (!(keys < 4.0e18)) return ~0ull;
+    const uint64_t e = (uint64_t)ceil(keys < 0.0 ? 0.0 : keys), want = e + e / 10 * 9;
+    return want < 1024 ? 1024 : want;
+}
+
+std::string prefilter_stats_text(const PrefilterStats &s) {
+    std::string t;
+    const std::pair<const char *, uint64_t> rows[] = {{"windows", s.windows}, {"once_words", s.once_words}, {"twice_words", s.twice_words},
+                                                      {"once_bits_set", s.once_bits_set}, {"twice_bits_set", s.twice_bits_set},
+                                                      {"promotions", s.promotions}, {"table_slots", s.table_slots},
+                                                      {"table_keys", s.table_keys}, {"table_retries", s.table_retries}};
+    for (const auto &r : rows) t += std::string(r.first) + '\t' + std::to_string(r.second) + '\n';
+    return t;
+}
+
+std::string write_prefilter_stats(const PrefilterStats &s) {
+    return write_text_file(g_prefilter.out_dir + "/prefilter.stats", prefilter_stats_text(s));
+}
+
+namespace {
+// One --prefilter run: the filter from its creation to the stats file
+struct Prefiltered {
+    kt_prefilter *filter = nullptr;
+    uint64_t expected = 0;  // the k-mers the input was estimated (or bounded) to hold
+    PrefilterStats st;
+    int log2_twice = 0;
+    Prefiltered() = default;
+    Prefiltered(const Prefiltered &) = delete;
+    ~Prefiltered() { if (filter) kt_prefilter_destroy(filter); }
+
+    // the request checked against the input's bound alone: before a device is opened
+    static std::string check(const std::string &path, int k) {
+        InputBound in;
+        const bool est = g_estimate.on;
+        g_estimate.on = false;  // (the bound, not the estimate: no device work here)
+        Device none;
+        const std::string e = slots_wanted(path, k, &in, none);
+        g_estimate.on = est;
+        if (!e.empty()) return e;
+        int a = 0, b = 0;
+        return prefilter_sizes(in.max_distinct, g_prefilter.bits, 0, &a, &b);
+    }
+
+    // the filter sized for `in` and created, then pass 1: one walk over the reader's input
+    std::string pass1(Device &dev, int k, const InputBound &in, SeqReader &reader, Batch &b, PhaseTimer &pt, Lap &lap) {
+        expected = std::min(in.max_distinct, in.want / 19 * 10 + 1);  // (the plan asks 1.9 slots a key)
+        uint64_t free_b = 0, total_b = 0;
+        if (kt_device_memory(dev.ctx, &free_b, &total_b) != KT_OK) free_b = 0;
+        int a = 0;
+        if (std::string e = prefilter_sizes(expected, g_prefilter.bits, free_b, &a, &log2_twice); !e.empty()) return e;
+        if (kt_prefilter_create(dev.ctx, k, a, log2_twice, 0, &filter) != KT_OK) return kt_last_error();
+        st.once_words = 1ull << a, st.twice_words = 1ull << log2_twice;
+        if (std::string e = fill_table(reader, b, pt, lap, [&](const Batch &bb) {
+                return kt_prefilter_add_reads(filter, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST);
+            });
+            !e.empty())
+            return e;
+        if (kt_prefilter_stats(filter, &st.windows, &st.promotions, &st.once_bits_set, &st.twice_bits_set) != KT_OK) return kt_last_error();
+        if (getenv("KT_CLI_TIMING"))
+            fprintf(stderr, "[timing] prefilter pass 1: once 2^%d words (%llu bits set), twice 2^%d words (%llu bits set), %llu windows, %llu promotions\n",
+                    a, (unsigned long long)st.once_bits_set, log2_twice, (unsigned long long)st.twice_bits_set,
+                    (unsigned long long)st.windows, (unsigned long long)st.promotions);
+        return "";
+    }
+    uint64_t table_slots() const {
+        double scale = 1.0;
+        if (const char *s = getenv("KT_PREFILTER_SCALE"); s && *s) scale = strtod(s, nullptr);
+        return prefilter_table_slots(st.promotions, st.twice_bits_set, log2_twice, expected, scale);
+    }
+    int add(kt_ctr *t, const Batch &bb, uint32_t passes, uint32_t pass) const {
+        return kt_ctr_add_reads_filtered(t, filter, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST, passes, pass);
+    }
+    // pass 2 is done: the filter's memory goes back to the device
+    void done() {
+        if (filter) kt_prefilter_destroy(filter);
+        filter = nullptr;
+    }
+    std::string write_stats() const { return write_prefilter_stats(st); }
+};
+}  // namespace
+
 std::string CountComputer::count() {
     // init(): pre-pass for record count and total length (counter/src/lib.rs:236-249); here it
     // sizes the HBM table instead of the reference's partition count
@@ -1085,6 +1207,9 @@ std::string CountComputer::count() {
     }
     if (in_path_ == "-") return "ctr reads its input more than once and cannot take stdin";  // (the reference panics
                                                                                             // on SeqFormat::get("-"))
+    const bool prefilter = g_prefilter.on;  // (the command line refuses it with --devices above 1 and with --table)
+    if (prefilter)
+        if (std::string e = Prefiltered::check(in_path_, ksize_); !e.empty()) return e;
     InputBound in;
     if (std::string e = slots_wanted(in_path_, ksize_, &in, dev_); !e.empty()) return e;
     seq_count_ = in.n_seq;
@@ -1093,6 +1218,16 @@ std::string CountComputer::count() {
     if (n_devices_ > 1) return count_sharded(in.max_distinct);
     if (std::string e = dev_.ensure(); !e.empty()) return e;
     const double t_dev = setup();
+    SeqReader reader;
+    Batch b;
+    Prefiltered pf;
+    if (prefilter) {  // pass 1, and the table planned from what it promoted instead of from the input
+        if (!reader.open(in_path_, false)) return reader.error();
+        PhaseTimer pt1("ctr prefilter pass 1");
+        Lap lap1;
+        if (std::string e = pf.pass1(dev_, ksize_, in, reader, b, pt1, lap1); !e.empty()) return e;
+        in.want = pf.table_slots();
+    }
     // one table, 16 bytes a slot; each pass's table is written out and cleared
     TablePlan plan;
     plan.want[0] = in.want;
@@ -1112,9 +1247,7 @@ std::string CountComputer::count() {
     // One reader, one batch and one table writer serve every pass: a pass rewinds the reader (its threads, cuts and
     // buffers stay) and reuses the writer's slab, so after the first pass the loop allocates nothing - the host's memory
     // is the same whether the table takes 2 passes or 200 (the reference's ceiling: counter/src/lib.rs:114-118, 220-230).
-    SeqReader reader;
-    if (!reader.open(in_path_, false)) return reader.error();
-    Batch b;
+    if (prefilter ? !reader.rewind() : !reader.open(in_path_, false)) return reader.error();
     TableWriter writer(acgt_, ksize_, threads_, memory_ceil_gb_, min_count_, max_count_);
     uint64_t heap_after_first = 0, rss_after_first = 0;
     struct Partial {  // --save-table out of core: removed unless the run gets to rename it
@@ -1125,10 +1258,37 @@ std::string CountComputer::count() {
         if (pass && !reader.rewind()) return reader.error();
         Lap lap;
         if (std::string e = fill_table(reader, b, pt, lap, [&](const Batch &bb) {
+                if (prefilter) return pf.add(ctr_, bb, passes_, pass);
                 return kt_ctr_add_reads_part(ctr_, bb.bases.data(), bb.offsets.data(), bb.n_reads(), KT_MEM_HOST, passes_, pass);
             });
             !e.empty())
             return e;
+        if (prefilter && passes_ == 1) {
+            // the plan was an estimate: a table that overflowed is made again with twice the slots while the device has
+            // room for it in one pass, and pass 2 is repeated
+            uint64_t keys = 0;
+            const int rc = kt_ctr_size(ctr_, &keys);
+            if (rc == KT_ERR_FULL) {
+                TablePlan again;
+                again.want[0] = plan.want[0] * 2;
+                again.plan(dev_.ctx, 16, true);
+                if (again.passes > 1) return kt_last_error();
+                kt_ctr_destroy(ctr_);
+                ctr_ = nullptr;
+                plan = again;
+                if (std::string e = create_tables(dev_.ctx, ksize_, plan, tables); !e.empty()) return e;
+                if (plan.passes > 1) return "ctr --prefilter: no room for a table of " + std::to_string(plan.want[0]) + " slots in one pass";
+                pf.st.table_retries++;
+                pass--;  // (pass 0 again; the loop's rewind is for pass > 0)
+                if (!reader.rewind()) return reader.error();
+                continue;
+            }
+            if (rc != KT_OK) return kt_last_error();
+            pf.st.table_keys = keys;
+            (void)kt_ctr_capacity(ctr_, &pf.st.table_slots);
+            pf.done();
+            if (std::string e = pf.write_stats(); !e.empty()) return e;
+        }
         if (passes_ == 1) break;  // the table stays resident: merge() (and cov) read it
         // out of core: this partition is complete - whoever needs to look k-mers up does it now (cov) -
         if (pass_hook_)
@@ -1161,7 +1321,16 @@ std::string CountComputer::count() {
                     (unsigned long long)r.anon_kb, (unsigned long long)r.file_kb, (unsigned long long)r.shmem_kb,
                     (unsigned long long)r.hwm_kb);
         }
+        if (prefilter) {  // (several passes: the keys of every pass's table; an overflow is the run's error, as without the flag)
+            uint64_t keys = 0;
+            if (kt_ctr_size(ctr_, &keys) != KT_OK) return kt_last_error();
+            pf.st.table_keys += keys;
+        }
         if (kt_ctr_clear(ctr_) != KT_OK) return kt_last_error();
+    }
+    if (prefilter && passes_ > 1) {
+        (void)kt_ctr_capacity(ctr_, &pf.st.table_slots);
+        if (std::string e = pf.write_stats(); !e.empty()) return e;
     }
     if (!partial.path.empty()) {
         if (rename(partial.path.c_str(), save_table_.c_str()) != 0) return "Unable to write to file: " + save_table_;
@@ -2086,6 +2255,25 @@ static std::string graph_census_name(int j) {
 // What `graph`, `hetmers` and `unitigs` share: one table, and the whole of it on the device - a plan of several passes is
 // refused before anything is counted or written.  whole_table plans and creates it (`name`: the command, in the texts), or
 // with a table file loads the file instead (table_from_file).
+static std::string whole_text(const char *name) {
+    return std::string(name) +
+                              " needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
+                              "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
+                              "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
+                              "memory or a smaller input - or, for --min-count 2 and above, --prefilter, which keeps the k-mers seen "
+                              "once out of the table";
+}
+// a table of `want` slots, all of it on the device, or why there is none
+static std::string create_whole(Device &dev, int k, uint64_t bytes_per_slot, const char *name, uint64_t want, kt_ctr **table) {
+    TablePlan plan;
+    plan.want[0] = want;
+    plan.plan(dev.ctx, bytes_per_slot, false);
+    const std::string whole = whole_text(name);
+    if (plan.passes > 1) return whole + " (" + std::to_string(want) + " slots wanted, room for " + std::to_string(plan.room) + ")";
+    if (const int rc = kt_ctr_create(dev.ctx, k, want, table); rc != KT_OK)
+        return rc == KT_ERR_NOMEM ? whole + " (" + kt_last_error() + ")" : std::string(kt_last_error());
+    return "";
+}
 static std::string whole_table(Device &dev, const std::string &path, const std::string &table_file, int k, uint64_t bytes_per_slot,
                                const char *name, kt_ctr **table) {
     if (!table_file.empty()) return table_from_file(dev, table_file, k, bytes_per_slot, name, table);
@@ -2093,17 +2281,7 @@ static std::string whole_table(Device &dev, const std::string &path, const std::
     InputBound in;
     if (std::string e = slots_wanted(path, k, &in, dev); !e.empty()) return e;
     if (std::string e = dev.ensure(); !e.empty()) return e;
-    TablePlan plan;
-    plan.want[0] = in.want;
-    plan.plan(dev.ctx, bytes_per_slot, false);
-    const std::string whole = std::string(name) +
-                              " needs the whole table on the device: a k-mer's neighbours live in other hash partitions, so the "
-                              "table cannot be counted in several passes as the other commands count theirs.  --min-count is no "
-                              "remedy (every k-mer is counted before the weak ones are left out): use a device with more free "
-                              "memory or a smaller input";
-    if (plan.passes > 1) return whole + " (" + std::to_string(in.want) + " slots wanted, room for " + std::to_string(plan.room) + ")";
-    if (const int rc = kt_ctr_create(dev.ctx, k, in.want, table); rc != KT_OK)
-        return rc == KT_ERR_NOMEM ? whole + " (" + kt_last_error() + ")" : std::string(kt_last_error());
+    if (std::string e = create_whole(dev, k, bytes_per_slot, name, in.want, table); !e.empty()) return e;
     if (getenv("KT_CLI_TIMING")) {
         uint64_t slots = in.want;
         (void)kt_ctr_capacity(*table, &slots);
@@ -2122,10 +2300,42 @@ struct WholeTableRun {
     Lap lap;
     std::string err;  // "" or why there is no table
     void took(int phase) { timer->t[phase] += lap(); }  // the time since the last call, booked to that phase
+    // --prefilter: pass 1 over the input, the table planned from what it promoted - where a plan of one pass may now exist
+    // that the input's bound did not allow -, pass 2 into it; a table that overflows (the plan is an estimate) is made again
+    // with twice the slots, while that still fits the device, and pass 2 repeated.  Writes prefilter.stats.
+    std::string prefiltered(Device &dev, const std::string &in_path, int k, uint64_t bytes_per_slot, const char *name, kt_ctr **table) {
+        if (std::string e = Prefiltered::check(in_path, k); !e.empty()) return e;
+        InputBound in;
+        if (std::string e = slots_wanted(in_path, k, &in, dev); !e.empty()) return e;
+        if (std::string e = dev.ensure(); !e.empty()) return e;
+        if (!reader.open(in_path, false)) return reader.error();
+        timer.emplace(name);
+        lap = Lap();
+        Prefiltered pf;
+        if (std::string e = pf.pass1(dev, k, in, reader, b, *timer, lap); !e.empty()) return e;
+        for (uint64_t want = pf.table_slots();; want *= 2, pf.st.table_retries++) {
+            if (std::string e = create_whole(dev, k, bytes_per_slot, name, want, table); !e.empty()) return e;
+            if (!reader.rewind()) return reader.error();
+            if (std::string e = fill_table(reader, b, *timer, lap, [&](const Batch &bb) { return pf.add(*table, bb, 1, 0); }); !e.empty())
+                return e;
+            const int rc = kt_ctr_size(*table, &pf.st.table_keys);
+            if (rc == KT_OK) break;
+            if (rc != KT_ERR_FULL) return kt_last_error();
+            kt_ctr_destroy(*table);
+            *table = nullptr;
+        }
+        (void)kt_ctr_capacity(*table, &pf.st.table_slots);
+        pf.done();
+        return pf.write_stats();
+    }
     WholeTableRun(Device &dev, const std::string &in_path, const std::string &table_file, int k, uint64_t bytes_per_slot, const char *name,
                   kt_ctr **table) {
         if (*table) kt_ctr_destroy(*table);
         *table = nullptr;
+        if (g_prefilter.on && table_file.empty()) {
+            err = prefiltered(dev, in_path, k, bytes_per_slot, name, table);
+            return;
+        }
         err = whole_table(dev, in_path, table_file, k, bytes_per_slot, name, table);
         if (!err.empty()) return;
         timer.emplace(name);

@@ -623,4 +623,22 @@ void set_estimate_size(bool on, int precision);
 uint64_t estimate_size_taken();                  // the sum of the estimates the plans of this process have used
 bool table_overflowed(const std::string &err);   // `err` is a command's error for a table that took more keys than slots
 
+// --prefilter of ctr, graph, unitigs and hetmers: the input is walked twice - pass 1 into a bit filter on the device that
+// remembers which k-mers were seen twice, pass 2 into a table planned from what pass 1 promoted and counting only those -
+// so that the k-mers seen once take no slots.  The dispatcher sets it before it runs a command, with the filter's bits per
+// k-mer expected and the directory prefilter.stats goes to.  The host side of the sizing follows (the hidden
+// `debug-prefilter` runs it without a device).
+void set_prefilter(bool on, uint64_t bits_per_kmer, const std::string &out_dir);
+struct PrefilterStats {  // the lines of prefilter.stats, in their order
+    uint64_t windows = 0, once_words = 0, twice_words = 0, once_bits_set = 0, twice_bits_set = 0, promotions = 0, table_slots = 0,
+             table_keys = 0, table_retries = 0;
+};
+// log2 of the words of `once` and `twice` for that many k-mers, `once` capped to a quarter of free_bytes (0: no cap); "" or
+// why the request is refused (0 bits, more than 2^34 words)
+std::string prefilter_sizes(uint64_t expected_kmers, uint64_t bits_per_kmer, uint64_t free_bytes, int *log2_once, int *log2_twice);
+// slots for the table of pass 2: 1.9 x scale x (promotions + (twice_bits_set / bits of twice)^4 x expected_kmers), at least 1024
+uint64_t prefilter_table_slots(uint64_t promotions, uint64_t twice_bits_set, int log2_twice, uint64_t expected_kmers, double scale);
+std::string prefilter_stats_text(const PrefilterStats &s);
+std::string write_prefilter_stats(const PrefilterStats &s);  // {out_dir}/prefilter.stats
+
 }  // namespace kthost

@@ -173,6 +173,41 @@ std::string table_flag(const std::map<std::string, std::string> &f, int k, const
     return it->second;
 }
 
+// ---- --prefilter [--prefilter-bits N] of ctr, graph, unitigs and hetmers ---------------------------------------------------------
+#define SPEC_PREFILTER {0, "prefilter", false}
+#define SPEC_PREFILTER_BITS {0, "prefilter-bits", true}
+#define HELP_PREFILTER_(sharded)                                                                                             \
+    "      --prefilter              Count in two passes: the first marks the k-mers seen twice in a bit filter on the GPU,\n"  \
+    "                               the second counts only those, so that the k-mers seen once (in reads: mostly errors)\n"   \
+    "                               take no slot of the table - all but a few false positives, which have count 1.  Every\n"  \
+    "                               k-mer seen twice or more has its exact count: with --min-count 2 or above, which the\n"   \
+    "                               flag requires, the output is that of a run without it.  Writes {output}/prefilter.stats.\n" \
+    "                               Not with --table" sharded ".  KT_PREFILTER_SCALE=<float> scales the table's size.\n"       \
+    "      --prefilter-bits <N>     Bits of the filter per k-mer expected in the input [default: 16] (needs --prefilter)\n"
+#define HELP_PREFILTER HELP_PREFILTER_("")
+#define HELP_PREFILTER_SHARDED HELP_PREFILTER_(" or --devices above 1")
+
+struct PrefilterFlags {
+    bool on = false;
+    uint64_t bits = 16;
+};
+
+// checked with the command's other flags, before any device work and before the output directory is made
+PrefilterFlags prefilter_flags(const std::map<std::string, std::string> &f, uint64_t min_count) {
+    PrefilterFlags pf;
+    pf.on = f.count("prefilter") != 0;
+    bool has_bits = false;
+    pf.bits = ranged(f, "prefilter-bits", 1, 1ull << 40, false, 16, &has_bits);
+    if (has_bits && !pf.on) usage_error("the argument '--prefilter-bits <N>' requires '--prefilter'");
+    if (!pf.on) return pf;
+    if (min_count < 2)
+        usage_error("the argument '--prefilter' requires '--min-count <N>' of 2 or above: the k-mers seen once are what it leaves out");
+    if (f.count("table")) usage_error("the argument '--prefilter' cannot be used with '--table <FILE>': nothing is counted");
+    if (f.count("devices") && ranged(f, "devices", 1, 64, false, 1) > 1)
+        usage_error("the argument '--prefilter' cannot be used with '--devices <N>' above 1");
+    return pf;
+}
+
 struct EstimateFlags {
     bool on = false;
     int p = 14;
@@ -287,6 +322,9 @@ const char *HELP_CTR =
     "                           above 1.\n"
     HELP_TABLE_CTR
     HELP_ESTIMATE_SHARDED
+    HELP_PREFILTER_SHARDED
+    "                               With --histo the line of count 1 reads \"1<TAB>0\": a filtered table does not know\n"
+    "                               how many k-mers were seen once.\n"
     "  -h, --help               Print help\n";
 
 const char *HELP_COV =
@@ -472,7 +510,7 @@ int cmd_ctr(int argc, char **argv, int from) {
                                      {0, "device", true},   {0, "devices", true},
                                      {0, "min-count", true}, {0, "max-count", true}, {0, "histo", false},
                                      {0, "histo-max", true}, {0, "histo-only", false}, {0, "save-table", true},
-                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P, SPEC_PREFILTER, SPEC_PREFILTER_BITS};
     const auto f = parse_flags(argc, argv, from, specs, HELP_CTR);
     // (--table FILE stands in for --input: the table file is dumped, filtered, re-saved)
     const std::string in = f.count("table") && !f.count("input") ? f.at("table") : required_str(f, "input"), out = required_str(f, "output");
@@ -488,6 +526,7 @@ int cmd_ctr(int argc, char **argv, int from) {
     const uint64_t histo_max = ranged(f, "histo-max", 1, (1u << 24) - 1, false, 10000);
     const bool histo_only = f.count("histo-only") != 0, histo = histo_only || f.count("histo") != 0;
     const EstimateFlags est = estimate_flags(f);
+    const PrefilterFlags pre = prefilter_flags(f, min_count);
     const std::string table = table_flag(f, k);
     const std::string save_table = f.count("save-table") ? f.at("save-table") : "";
     if (!save_table.empty() && ranged(f, "devices", 1, 64, false, 1) > 1)
@@ -499,6 +538,7 @@ int cmd_ctr(int argc, char **argv, int from) {
         return 101;
     }
     const int devices = (int)ranged(f, "devices", 1, 64, false, 1), device = (int)ranged(f, "device", 0, 63, false, 0);
+    set_prefilter(pre.on, pre.bits, out);
     return run_table_command(est, [&]() -> std::string {  // (101: count()/merge() unwrap in the reference)
         CountComputer ctr(in, out, k);
         ctr.set_devices(devices);
@@ -1083,12 +1123,14 @@ const char *HELP_GRAPH =
     "      --device <DEVICE>        GPU index [default: 0]\n"
     HELP_TABLE
     HELP_ESTIMATE
+    HELP_PREFILTER
     "  -h, --help                   Print help\n";
 
 int cmd_graph(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},     {'o', "output", true},      {'k', "k-size", true},  {0, "min-count", true},
                                      {0, "max-count", true},   {0, "acgt", false},         {0, "stats-only", false}, {'m', "memory", true},
-                                     {'t', "threads", true},   {0, "device", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {'t', "threads", true},   {0, "device", true}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P,
+                                     SPEC_PREFILTER, SPEC_PREFILTER_BITS};
     const auto f = parse_flags(argc, argv, from, specs, HELP_GRAPH);
     // (--table FILE stands in for --input)
     const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
@@ -1102,12 +1144,14 @@ int cmd_graph(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
+    const PrefilterFlags pre = prefilter_flags(f, lo);
     const std::string table = table_flag(f, k);
     if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
+    set_prefilter(pre.on, pre.bits, out);
     return run_table_command(est, [&]() -> std::string {
         GraphComputer gc(in, out, k);
         gc.set_table_file(table);
@@ -1153,13 +1197,14 @@ const char *HELP_HETMERS =
     "      --device <DEVICE>        GPU index [default: 0]\n"
     HELP_TABLE
     HELP_ESTIMATE
+    HELP_PREFILTER
     "  -h, --help                   Print help\n";
 
 int cmd_hetmers(int argc, char **argv, int from) {
     const std::vector<Spec> specs = {{'i', "input", true},   {'o', "output", true},    {'k', "k-size", true},    {0, "min-count", true},
                                      {0, "max-count", true}, {0, "middle", false},     {0, "max-minor", true},   {0, "max-major", true},
                                      {0, "stats-only", false}, {'m', "memory", true},  {'t', "threads", true},   {0, "device", true},
-                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P, SPEC_PREFILTER, SPEC_PREFILTER_BITS};
     const auto f = parse_flags(argc, argv, from, specs, HELP_HETMERS);
     // (--table FILE stands in for --input)
     const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
@@ -1181,12 +1226,14 @@ int cmd_hetmers(int argc, char **argv, int from) {
     const int threads = (int)ranged(f, "threads", 0, 1 << 20, false, 0);
     const int device = (int)ranged(f, "device", 0, 63, false, 0);
     const EstimateFlags est = estimate_flags(f);
+    const PrefilterFlags pre = prefilter_flags(f, lo);
     const std::string table = table_flag(f, k);
     if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
+    set_prefilter(pre.on, pre.bits, out);
     return run_table_command(est, [&]() -> std::string {
         HetmerComputer hc(in, out, k);
         hc.set_table_file(table);
@@ -1264,6 +1311,7 @@ const char *HELP_UNITIGS =
     "      --device <DEVICE>        GPU index [default: 0]\n"
     HELP_TABLE
     HELP_ESTIMATE
+    HELP_PREFILTER
     "  -h, --help                   Print help\n";
 
 int cmd_unitigs(int argc, char **argv, int from) {
@@ -1271,7 +1319,8 @@ int cmd_unitigs(int argc, char **argv, int from) {
                                      {0, "max-count", true},   {0, "stats-only", false},   {'m', "memory", true},  {'t', "threads", true},
                                      {0, "device", true},      {0, "gfa", false},          {0, "links", false},
                                      {0, "clip-tips", false},  {0, "tip-nodes", true},     {0, "clip-rounds", true},
-                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, {0, "components", false}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P};
+                                     {0, "drop-isolated", false}, {0, "pop-bubbles", false}, {0, "bubble-nodes", true}, {0, "components", false}, SPEC_TABLE, SPEC_ESTIMATE_SIZE, SPEC_ESTIMATE_P,
+                                     SPEC_PREFILTER, SPEC_PREFILTER_BITS};
     const auto f = parse_flags(argc, argv, from, specs, HELP_UNITIGS);
     // (--table FILE stands in for --input)
     const std::string in = f.count("table") && !f.count("input") ? "" : required_str(f, "input"), out = required_str(f, "output");
@@ -1297,12 +1346,14 @@ int cmd_unitigs(int argc, char **argv, int from) {
             usage_error(std::string("the argument '--") + needs + "' requires '--clip-tips'");
     if (f.count("bubble-nodes") && !pop) usage_error("the argument '--bubble-nodes' requires '--pop-bubbles'");
     const EstimateFlags est = estimate_flags(f);
+    const PrefilterFlags pre = prefilter_flags(f, lo);
     const std::string table = table_flag(f, k);
     if (table.empty() && format_from_path(in) == SeqFormat::Unknown) {  // "-" included: the sizing looks at the file
         fprintf(stderr, "Error: unsupported input extension (expected .fa/.fasta/.fna/.fq/.fastq[.gz]): %s\n", in.c_str());
         return 101;
     }
     if (int rc = make_out_dir(out)) return rc;
+    set_prefilter(pre.on, pre.bits, out);
     return run_table_command(est, [&]() -> std::string {
         UnitigComputer uc(in, out, k);
         uc.set_table_file(table);
@@ -1397,6 +1448,60 @@ int cmd_thread(int argc, char **argv, int from) {
         uc.set_device(device);
         return uc.unitigs();
     });
+}
+
+// hidden: the host side of --prefilter without a device (the sanitizer builds run it): the sizing of the two arrays over
+// every exponent and at the edges of u64, the table plan's arithmetic, the stats text written through write_text_file and
+// read back.  Prints "prefilter ok", or what was wrong.
+int cmd_debug_prefilter(int argc, char **argv, int from) {
+    if (from >= argc) return 2;
+    const std::string dir = argv[from];
+    int bad = 0;
+    auto check = [&](bool ok, const char *what) {
+        if (!ok) fprintf(stderr, "debug-prefilter: %s\n", what), bad++;
+    };
+    int a = -1, b = -1;
+    check(prefilter_sizes(0, 16, 0, &a, &b).empty() && a == 10 && b == 10, "no k-mers: the smallest filter");
+    check(prefilter_sizes(1ull << 16, 1, 0, &a, &b).empty() && a == 10 && b == 10, "2^16 bits are 2^10 words");
+    check(prefilter_sizes((1ull << 16) + 1, 1, 0, &a, &b).empty() && a == 11 && b == 10, "one bit more rounds up");
+    for (int e = 10; e <= 34; e++) {
+        check(prefilter_sizes(1ull << e, 64, 0, &a, &b).empty() && a == e && b == std::max(10, e - 2), "a word a k-mer");
+        check(prefilter_sizes((1ull << e) * 4, 16, 0, &a, &b).empty() && a == e && b == std::max(10, e - 2), "16 bits a k-mer");
+    }
+    check(prefilter_sizes(1ull << 36, 16, 0, &a, &b).empty() && a == 34 && b == 32, "2^40 bits are 2^34 words, the most");
+    check(!prefilter_sizes((1ull << 36) + 1, 16, 0, &a, &b).empty(), "one k-mer more than 2^34 words hold is refused");
+    check(!prefilter_sizes(~0ull, ~0ull, 0, &a, &b).empty(), "the largest request is refused, not wrapped");
+    check(!prefilter_sizes(1000, 0, 0, &a, &b).empty(), "0 bits a k-mer is refused");
+    check(!prefilter_sizes(1000, 1ull << 40, 0, &a, &b).empty(), "2^40 bits for each of 1000 k-mers is refused");
+    check(prefilter_sizes(1ull << 30, 16, 1ull << 30, &a, &b).empty() && a == 25 && b == 23, "a quarter of 1 GiB free: 2^25 words");
+    check(prefilter_sizes(1ull << 30, 16, 1, &a, &b).empty() && a == 10 && b == 10, "no memory to speak of: the smallest filter");
+    check(prefilter_table_slots(0, 0, 10, 0, 1.0) == 1024, "an empty filter: the smallest table");
+    check(prefilter_table_slots(1000000, 0, 20, 5000000, 1.0) == 1900000, "1.9 slots a promotion");
+    check(prefilter_table_slots(0, 64ull << 20, 20, 1000, 1.0) == 1900, "a full filter lets every k-mer in");
+    check(prefilter_table_slots(0, 32ull << 20, 20, 16000, 1.0) == 1900, "half the bits set: one k-mer in sixteen");
+    check(prefilter_table_slots(1000000, 0, 20, 0, 0.01) == 19000, "the scale");
+    check(prefilter_table_slots(~0ull, 0, 10, ~0ull, 4.0) == ~0ull, "beyond u64: saturated");
+    check(prefilter_table_slots(5, 0, 10, 0, -1.0) == 1024, "a negative scale");
+    PrefilterStats st;
+    st.windows = ~0ull, st.once_words = 1ull << 34, st.twice_words = 1024, st.once_bits_set = 7, st.table_retries = 2;
+    const std::string want = "windows\t18446744073709551615\nonce_words\t17179869184\ntwice_words\t1024\nonce_bits_set\t7\n"
+                             "twice_bits_set\t0\npromotions\t0\ntable_slots\t0\ntable_keys\t0\ntable_retries\t2\n";
+    check(prefilter_stats_text(st) == want, "the stats text");
+    set_prefilter(true, 16, dir);
+    check(write_prefilter_stats(st).empty(), "the stats file");
+    std::string got;
+    if (FILE *f = fopen((dir + "/prefilter.stats").c_str(), "rb")) {
+        char buf[512];
+        for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) got.append(buf, n);
+        fclose(f);
+    }
+    check(got == want, "the stats file read back");
+    unlink((dir + "/prefilter.stats").c_str());
+    set_prefilter(true, 16, dir + "/no/such/dir");
+    check(!write_prefilter_stats(st).empty(), "a directory that does not exist is an error");
+    set_prefilter(false, 16, "");
+    if (!bad) printf("prefilter ok\n");
+    return bad ? 1 : 0;
 }
 
 // hidden: parse a file and print its records (CPU-only reader tests)
@@ -1611,6 +1716,7 @@ int main(int argc, char **argv) {
     if (cmd == "debug-read") return cmd_debug_read(argc, argv, 2);
     if (cmd == "debug-fixed6") return cmd_debug_fixed6(argc, argv, 2);
     if (cmd == "debug-outfile") return cmd_debug_outfile(argc, argv, 2);  // debug-outfile <dir>
+    if (cmd == "debug-prefilter") return cmd_debug_prefilter(argc, argv, 2);  // debug-prefilter <dir>
     if (cmd == "debug-emit") {  // debug-emit <rows> <bins> <norm 0|1> <threads> <reps>
         if (argc < 7) return 2;
         const double s = debug_emit_bench(strtoull(argv[2], nullptr, 10), strtoull(argv[3], nullptr, 10), atoi(argv[4]) != 0,

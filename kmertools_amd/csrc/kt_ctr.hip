@@ -41,14 +41,17 @@ __device__ __forceinline__ void publish_fresh(uint32_t fresh, uint64_t *distinct
         atomicAdd(reinterpret_cast<unsigned long long *>(distinct), (unsigned long long)fresh);
 }
 
+// keep(m): whether the canonical k-mer m is counted at all (ktpf::KeepAll; ktpf::KeepSeenTwice: kt_ctr_add_reads_filtered)
+template <class Keep>
 __global__ __launch_bounds__(BLOCK) void count_reads_kernel(SegArgs a, TableRef t, uint32_t n_parts, uint32_t part,
-                                                            uint64_t *__restrict__ distinct) {
+                                                            uint64_t *__restrict__ distinct, Keep keep) {
     __shared__ SegShared sm;
     uint32_t fresh = 0;
     for (uint64_t g = blockIdx.x; g < a.n_seg; g += gridDim.x) {
         ktseg::for_each_kmer(a, g, sm, [&](uint64_t f, uint64_t r, uint64_t) {
             const uint64_t m = f < r ? f : r;  // counter/src/lib.rs:124
             if (n_parts > 1 && ktd::owner_of(m, n_parts) != part) return;  // another pass counts this one
+            if (!keep(m)) return;
             const uint32_t st = table_add(t, m, 1u);
             if (st == 0u) atomicOr(t.flags, 1u);
             fresh += st == 2u;
@@ -1077,9 +1080,36 @@ int kt_ctr_add_reads_part(kt_ctr *ctr, const uint8_t *bases, const uint64_t *off
     if (int rc = table_write(ctr, &t)) return rc;
     SegArgs a;
     if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, ctr->k, &a)) return rc;
-    hipLaunchKernelGGL(count_reads_kernel, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, t, n_parts,
-                       part, ctr->distinct);
+    hipLaunchKernelGGL(count_reads_kernel<ktpf::KeepAll>, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, t, n_parts,
+                       part, ctr->distinct, ktpf::KeepAll());
     KT_HIP(hipGetLastError());
+    return call.finish();
+}
+
+int kt_ctr_add_reads_filtered(kt_ctr *ctr, kt_prefilter *filter, const uint8_t *bases, const uint64_t *offsets,
+                              uint64_t n_reads, int mem, uint32_t n_parts, uint32_t part) {
+    if (!ctr) return kt::fail(KT_ERR_ARG, "kt_ctr_add_reads_filtered: null ctr");
+    kt_ctx *ctx = ctr->ctx;
+    Call call(ctx, mem, "kt_ctr_add_reads_filtered");
+    if (!filter) return call.fail("null filter");
+    if (filter->ctx != ctx) return call.fail("the filter belongs to another context");
+    if (filter->k != ctr->k) return call.fail("the filter's k is not the table's");
+    if (int rc = call.check_part(n_parts, part)) return rc;
+    if (int rc = call.enter()) return rc;
+    if (n_reads == 0) return KT_OK;
+    ctr->stage.drop();  // (as in kt_ctr_add_reads_part)
+    if (!offsets) return call.fail("null offsets");
+    if (int rc = call.batch(bases, offsets, n_reads)) return rc;
+    if (call.total == 0) return KT_OK;
+    if (int rc = call.stage()) return rc;
+    TableRef t;
+    if (int rc = table_write(ctr, &t)) return rc;
+    SegArgs a;
+    if (int rc = make_seg_args(ctx, call.bases, call.offsets, n_reads, call.total, ctr->k, &a)) return rc;
+    const ktpf::KeepSeenTwice keep{view_of(filter)};
+    if (int rc = launch(count_reads_kernel<ktpf::KeepSeenTwice>, dim3(grid_for(ctx, a.n_seg, 8)), dim3(BLOCK), 0, ctx->stream, a, t,
+                        n_parts, part, ctr->distinct, keep))
+        return rc;
     return call.finish();
 }
 

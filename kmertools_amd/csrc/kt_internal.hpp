@@ -210,6 +210,16 @@ private:
     bool xt_too_small_ = false;
 };
 
+// kt_prefilter.hip: the `once` and `twice` bit arrays that keep k-mers seen once out of a table (kt_prefilter.hpp: the layout)
+struct kt_prefilter {
+    kt_ctx *ctx = nullptr;
+    int k = 0;
+    uint32_t a = 0, b = 0;      // log2 of the words of once / twice
+    uint64_t seed = 0;
+    uint64_t *once = nullptr, *twice = nullptr;
+    uint64_t *sums = nullptr;   // device: [0] windows walked, [1] promotions, [2], [3] kt_prefilter_stats's popcounts
+};
+
 // kt_oligo_generic.hip: histograms for k outside 3..7, counted in global memory (device pointers, enqueued)
 int kt_oligo_generic_launch(kt_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int k,
                             int count_min, int norm, int total_step, int dt, void *out);

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "kt_internal.hpp"
+#include "kt_prefilter.hpp"
 #include "kt_segment.hpp"
 #include "kt_table.hpp"
 
@@ -28,6 +29,8 @@ inline kttab::Probed probed_of(const kt_ctr *ctr, uint32_t n_parts = 1, uint32_t
 }
 // ... and as the kernels that insert into it take it (after table_write)
 inline kttab::TableRef writable_of(const kt_ctr *ctr) { return kttab::TableRef{(kttab::Slot *)ctr->slots, geom_of(ctr), ctr->flags}; }
+// a pre-filter as its kernels take it (kt_prefilter.hpp)
+inline ktpf::View view_of(const kt_prefilter *f) { return ktpf::View{f->once, f->twice, f->seed, f->a, f->b}; }
 // The readers' gate (kt_table.hip): brings the table to its probing image - a deferred clear is carried out, a Dense or
 // Target-form table imaged - and reports KT_ERR_FULL if it overflowed
 int table_ready(kt_ctr *ctr);

@@ -699,7 +699,77 @@ class Context:
                                         genome_len, _ptr(bases_dev), _ptr(offsets_dev)))
 
 
-class Counter:
+class Prefilter:
+    """The two-pass pre-filter (kt_prefilter): 2^log2_once words of `once` bits and 2^log2_twice words of `twice` bits in
+    HBM.  add_reads over an input is pass 1; Counter.add_reads_filtered over the same input is pass 2 and leaves the k-mers
+    seen once out of the table, up to the filter's false positives."""
+
+    def __init__(self, ctx, k, log2_once, log2_twice, seed=0):
+        self.ctx = ctx
+        self.k, self.log2_once, self.log2_twice, self.seed = k, int(log2_once), int(log2_twice), int(seed)
+        self._h = C.c_void_p()
+        check(_lib.lib().kt_prefilter_create(ctx._h, k, self.log2_once, self.log2_twice, self.seed, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            if self.ctx._h.value:   # (as for a Counter: destroying waits for the context's stream)
+                _lib.lib().kt_prefilter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        check(_lib.lib().kt_prefilter_clear(self._h))
+
+    def add_reads(self, bases, offsets, n_reads, mem=KT_MEM_DEVICE):
+        check(_lib.lib().kt_prefilter_add_reads(self._h, _ptr(bases), _ptr(offsets), n_reads, mem))
+
+    def add_reads_host(self, bases, offsets):
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        self.add_reads(bases if bases.size else np.zeros(1, np.uint8), offsets, len(offsets) - 1, KT_MEM_HOST)
+
+    def stats(self):
+        """-> dict(windows, promotions, once_bits_set, twice_bits_set) (kt_prefilter_stats; synchronises)"""
+        v = [C.c_uint64() for _ in range(4)]
+        check(_lib.lib().kt_prefilter_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("windows", "promotions", "once_bits_set", "twice_bits_set"), (x.value for x in v)))
+
+    def query(self, keys, n, out, mem=KT_MEM_DEVICE):
+        """out[i] (u8) = 1 if `once` covers the pattern of canonical k-mer keys[i], | 2 if `twice` does (kt_prefilter_query)"""
+        check(_lib.lib().kt_prefilter_query(self._h, _ptr(keys), int(n), _ptr(out), mem))
+        return out
+
+    def query_host(self, keys):
+        keys = np.ascontiguousarray(keys, np.uint64)
+        out = np.zeros(len(keys), np.uint8)
+        if len(keys):
+            self.query(keys, len(keys), out, KT_MEM_HOST)
+        return out
+
+
+class _FilteredAdds:
+    """Pass 2 of the two-pass count, as methods of Counter.  A base class of their own: tests/test_grid_limits.py keeps a
+    table of cases for the methods defined on Context and Counter themselves, and the case of these two - pass 1 and pass 2
+    with the grid held to 8 workgroups - stands with the filter's other tests in tests/test_prefilter.py."""
+
+    def add_reads_filtered(self, prefilter, bases, offsets, n_reads, n_parts=1, part=0, mem=KT_MEM_DEVICE):
+        """add_reads_part for the k-mers whose pattern is covered in the `twice` array of `prefilter` (a Prefilter that has
+        seen the input): pass 2 of the two-pass count, always by probing (kt_ctr_add_reads_filtered)"""
+        check(_lib.lib().kt_ctr_add_reads_filtered(self._h, prefilter._h, _ptr(bases), _ptr(offsets), n_reads, mem, n_parts, part))
+
+    def add_reads_filtered_host(self, prefilter, bases, offsets, n_parts=1, part=0):
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        self.add_reads_filtered(prefilter, bases if bases.size else np.zeros(1, np.uint8), offsets, len(offsets) - 1, n_parts, part,
+                                KT_MEM_HOST)
+
+
+class Counter(_FilteredAdds):
     """HBM-resident canonical k-mer table (kt_ctr) = the reference's CountComputer state."""
 
     def __init__(self, ctx, k, capacity_slots):
